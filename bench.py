@@ -20,10 +20,12 @@ Workloads (BASELINE.json `configs`), picked with --workload:
 run would make: its shard through ssym_match_sharded with the full dictionary's bounds replayed into the bound exchange
 (DESIGN.md section 7); never a multi-GPU result.
 
-Beside the headline the line carries `early_abandon`, `cpu_baseline` and `secondary`: the reference's own metric (refcos),
-the chain, one query at a time, the MFCC front-end, host-resident targets, and `secondary.ragged` -- the reference's REAL
-segment shape (4096 x 4096 segments of 5...40 frames, src/sound.rs:330-343) in both metrics with rates on TRUE cells, and
-BASELINE's configs[0] on the reference's recordings.
+A plain run sets up, warms up, times --steps steps and prints the line.  With --full the line also carries
+`early_abandon`, `cpu_baseline` and `secondary`: the reference's own metric (refcos), the chain, one query at a time, the
+MFCC front-end, host-resident targets, and `secondary.ragged` -- the reference's REAL segment shape (4096 x 4096 segments
+of 5...40 frames, src/sound.rs:330-343) in both metrics with rates on TRUE cells, and BASELINE's configs[0] on the
+reference's recordings.  --dump-outputs DIR writes what the last timed step returned (per-target index and cost) as .npy
+files, so that two builds can be compared output for output on the same seeded inputs.
 """
 import argparse
 import glob
@@ -367,6 +369,22 @@ def secondary_cpu(out: dict) -> None:
         out["ragged"]["config0"]["cpu_oracle_one_thread_ms"] = {"refcos": (t1 - t0) * 1e3, "dtw": (t2 - t1) * 1e3}
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path: str, arrays: dict) -> None:
+    """--dump-outputs: every array (one value per target) as <path>/<name>.npy in float64 (indices included: exact below
+    2^53).  Above DUMP_LIMIT_BYTES in all, the same fixed, seeded sample of targets is kept of each, and its target numbers
+    are written as rows.npy."""
+    os.makedirs(path, exist_ok=True)
+    n = len(next(iter(arrays.values())))
+    if 8 * n * len(arrays) > DUMP_LIMIT_BYTES:
+        rows = np.sort(np.random.default_rng(0).choice(n, DUMP_LIMIT_BYTES // (8 * (len(arrays) + 1)), replace=False))
+        arrays = dict({k: v[rows] for k, v in arrays.items()}, rows=rows)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), np.asarray(a, dtype=np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -374,9 +392,14 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--workload", choices=sorted(WORKLOADS), default="c3",
                     help="BASELINE.json config: c3 = configs[2] (default, the metric's), c4 = configs[3], c5 = configs[4]")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what is reported beside the headline: early abandoning, the secondary legs "
+                         "(refcos, chain, mfcc, host batch, ragged) and the CPU baseline")
     ap.add_argument("--no-secondary", action="store_true",
-                    help="skip the refcos / chain / mfcc / early-abandon measurements reported beside the headline")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+                    help="with --full: skip the refcos / chain / mfcc / early-abandon measurements")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's per-target index and cost to DIR/<name>.npy (float64)")
     ap.add_argument("--src-per-gpu", type=int, default=0, help="WEAK scaling: this many sources per GPU (default: "
                     "the workload's sources split over the GPUs, strong scaling)")
     ap.add_argument("--sources", type=int, default=0)
@@ -391,6 +414,8 @@ def main():
                          "(ssym_comm_replay_bounds), so that selection and re-scoring see what that rank would see")
     ap.add_argument("--replay-rank", type=int, default=0)
     args = ap.parse_args()
+    if not args.full:
+        args.no_secondary = args.no_cpu_baseline = True
     if args.replay_world:
         if args.gpus != 1 or not (0 <= args.replay_rank < args.replay_world):
             sys.exit("--replay-world G needs --gpus 1 and 0 <= --replay-rank < G")
@@ -568,6 +593,8 @@ def main():
     pairs_per_step = (hi - lo) * m if args.replay_world else n_src_total * m
     value = pairs_per_step * args.steps / elapsed
     idx_host = fin_idx.cpu().numpy().view(np.uint32).astype(np.int64)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"match_idx": idx_host, "match_cost": fin_cost.cpu().numpy()})
     planted_ok = bool(np.array_equal(idx_host, grid.planted))
     if args.replay_world:      # one rank of a larger world: it answers the targets whose neighbour its shard holds
         mine = (grid.planted >= lo) & (grid.planted < hi)

@@ -5,6 +5,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -37,8 +38,19 @@ def test_bench_prints_one_json_line_with_the_contract_keys():
     assert line["value"] > 0 and abs(line["value"] - 512 * 256 / (line["ms_per_step"] * 1e-3)) / line["value"] < 1e-6
 
 
+def test_bench_plain_run_times_the_headline_only_and_dumps_its_last_step(tmp_path):
+    line = _run(["--dump-outputs", str(tmp_path)])
+    assert not {"early_abandon", "secondary", "cpu_baseline"} & set(line)      # those are --full's
+    assert line["steps"] == 2 and line["ms_per_step"] > 0 and line["config"]["indices_equal_planted"] is True
+    idx, cost = np.load(tmp_path / "match_idx.npy"), np.load(tmp_path / "match_cost.npy")
+    assert idx.dtype == cost.dtype == np.float64 and idx.shape == cost.shape == (256,)
+    from soundsym_amd import synth
+    assert np.array_equal(idx, synth.make_grid(512, 256, 64, 13, 0x5EED0003).planted)     # bench.py SEEDS["c3"]
+    assert np.all(np.isfinite(cost)) and np.all(cost >= 0)
+
+
 def test_bench_early_abandon_leg_is_identical_to_the_full_search():
-    line = _run([])                                   # with the secondary legs (refcos, chain, mfcc, early abandoning)
+    line = _run(["--full"])                           # with the secondary legs (refcos, chain, mfcc, early abandoning)
     ea = line["early_abandon"]
     assert ea["identical_to_full_search"] is True and ea["value"] > 0
     assert 0 < ea["filter_cells_swept_frac"] <= 1

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""tools/print_refcos_line.py <bench line.json> -- the refcos figures of a bench.py line (both filters) on one screen."""
+"""tools/print_refcos_line.py <bench line.json> -- the refcos figures of a `bench.py --full` line (both filters) on one screen."""
 import json, sys
 l = json.load(open(sys.argv[1]))
 r = l["secondary"]["refcos"]
