@@ -341,8 +341,12 @@ static int32_t build_derived(ssym_ctx *ctx, SegmentSet &set)
         });
         { int32_t rca = dev_alloc(ctx, (void **)&set.perm, sizeof(uint32_t) * set.n_pad); if (rca != SSYM_OK) return rca; }
         { int32_t rcs = stage_h2d(ctx, set.perm, set.h_perm.data(), sizeof(uint32_t) * set.n_pad); if (rcs != SSYM_OK) return rcs; }
-        { int32_t rca = dev_alloc(ctx, (void **)&set.len, sizeof(int32_t) * set.n_pad); if (rca != SSYM_OK) return rca; }
-        SSYM_HIP_CHECK(ctx, hipMemsetAsync(set.len, 0, sizeof(int32_t) * set.n_pad, st));
+        // + a zeroed tail of kLenTailPad ints: the multi-pair prefetch of dtw_filter_sp_kernel (MP) reads the 2 NP lengths
+        // of a task's pairs unclamped, up to 2 (NP - 1) = 4 ints past the last pair when the launch ends at n_pad / 2
+        // (pairs beyond pairLimit are masked in the kernel, but the bytes are read)
+        constexpr size_t kLenTailPad = 8;
+        { int32_t rca = dev_alloc(ctx, (void **)&set.len, sizeof(int32_t) * (set.n_pad + kLenTailPad)); if (rca != SSYM_OK) return rca; }
+        SSYM_HIP_CHECK(ctx, hipMemsetAsync(set.len, 0, sizeof(int32_t) * (set.n_pad + kLenTailPad), st));
         // [n_pad] max squared frame norm per slot (read by the kernels), then [n_pad] max |value| per slot (host only), then
         // [n_pad] the largest distance between a frame of the slot and the frame its filter record represents (written when
         // the records are built, dtw_filter.hip; read by the selection's margin, dtw_margin.hpp)

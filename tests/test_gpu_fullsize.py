@@ -51,6 +51,13 @@ def test_config3_4096x4096x128x13(dtw, oracle):
     for t in range(0, 4096, 256):
         want = oracle.dtw(g.sources[g.planted[t]].astype(np.float64), g.targets[t].astype(np.float64), 13)
         assert abs(cost[t] - want) <= 1e-12 * want
+    # a sample of targets checked end to end against the oracle (all 4096 sources each)
+    pick = np.arange(0, 4096, 256)
+    tsel, tosel = synth.Grid(g.sources, g.targets[pick], g.planted[pick], 128, 13).flat("targets")
+    want_idx, want_cost = oracle.dtw_match_all(sf.astype(np.float64), so, tsel.astype(np.float64), tosel, 13, nthreads=16)
+    assert np.array_equal(idx[pick], want_idx)
+    assert np.allclose(cost[pick], want_cost, rtol=1e-5, atol=0)
+    assert np.allclose(cost[pick], want_cost, rtol=1e-12, atol=0)
     # permuting the dictionary permutes the answers
     perm = synth.Stream(99).permutation(4096)
     d2 = dtw.dictionary(np.ascontiguousarray(g.sources[perm]).reshape(-1), so, 13)
@@ -225,7 +232,8 @@ def test_ragged_4096x4096_dtw(dtw, oracle, planted):
     """SoundDictionary::add_segments emits segments of seg / HOP frames (src/sound.rs:330-343, src/lib.rs:137): short
     and ragged.  The full-size ragged grid of bench.py's secondary.ragged through the filter path (one launch per
     class of source lengths on dtw_filter_sp_kernel), 16 sampled targets against the oracle over all 4096 sources,
-    run-to-run identical; the same search with SSYM_FILTER_SP=0 semantics is covered by test_gpu_numerics."""
+    run-to-run identical.  Each launch variant of these kernels, with every pair of its filter matrix within its bound
+    and the same bits under SSYM_FILTER_SP=0 / SSYM_SP_PAIRBLOCK=0 / SSYM_SP_MULTIPAIR=0: tests/test_gpu_filter_variants.py."""
     import bench
     if planted:
         src, tgt, pi = synth.make_ragged(4096, 4096, 5, 40, 13, bench.RAGGED_SEED + 1, planted=True)
