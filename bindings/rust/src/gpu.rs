@@ -12,6 +12,7 @@ use std::os::raw::{c_char, c_void};
 #[repr(C)] pub struct SsymSamples { _p: [u8; 0] }
 #[repr(C)] pub struct SsymComm { _p: [u8; 0] }
 #[repr(C)] pub struct SsymLocalGroup { _p: [u8; 0] }
+#[repr(C)] pub struct SsymGmm { _p: [u8; 0] }
 
 pub const SSYM_ABI_VERSION: i32 = 3;
 
@@ -35,6 +36,7 @@ pub const SSYM_DTW_FORCE_EXACT: u32 = 2;
 pub const SSYM_DTW_PRUNE: u32 = 4;
 pub const SSYM_MFCC_PAD_TAIL: u32 = 4;
 pub const SSYM_TOPK_MAX: u32 = 64;
+pub const SSYM_GMM_STANDARDIZE: u32 = 8;
 pub const SSYM_NO_MATCH: u32 = 0xffff_ffff;
 pub const SSYM_COMM_ID_BYTES: usize = 128;
 
@@ -156,6 +158,21 @@ extern "C" {
     pub fn ssym_mfcc_num_frames(n_samples: u64, flags: u32, out_frames: *mut u64) -> i32;
     pub fn ssym_mfcc(ctx: *mut SsymCtx, samples: *const f64, n_samples: u64, sample_rate: f64, n_coeffs: u32,
                      f_lo: f64, f_hi: f64, flags: u32, out_mfccs: *mut f64, out_mean: *mut f64) -> i32;
+
+    // partitioner: standardiser, Gaussian mixture, voting experts (own definitions -- parity unpinned)
+    pub fn ssym_standardize(ctx: *mut SsymCtx, feats: *const f64, n_frames: u64, dim: u32, flags: u32,
+                            out: *mut f64) -> i32;
+    pub fn ssym_gmm_train(ctx: *mut SsymCtx, feats: *const f64, n_frames: u64, dim: u32, n_components: u32,
+                          init_rows: *const u64, eps: f64, max_iters: u32, flags: u32, out: *mut *mut SsymGmm) -> i32;
+    pub fn ssym_gmm_get(gmm: *const SsymGmm, weights: *mut f64, means: *mut f64, covs: *mut f64, log_lik: *mut f64,
+                        iters: *mut u32) -> i32;
+    pub fn ssym_gmm_destroy(ctx: *mut SsymCtx, gmm: *mut SsymGmm) -> i32;
+    pub fn ssym_gmm_predict(ctx: *mut SsymCtx, gmm: *const SsymGmm, feats: *const f64, n_frames: u64, flags: u32,
+                            out_post: *mut f64, out_letters: *mut u8) -> i32;
+    pub fn ssym_vote_segments(ctx: *mut SsymCtx, symbols: *const u8, n: u64, alphabet: u32, depth: u32, threshold: u32,
+                              flags: u32, out_votes: *mut u32, out_seg_frames: *mut u64, n_segments: *mut u64) -> i32;
+    pub fn ssym_partition(ctx: *mut SsymCtx, gmm: *const SsymGmm, feats: *const f64, n_frames: u64, depth: u32,
+                          threshold: u32, flags: u32, out_seg_frames: *mut u64, n_segments: *mut u64) -> i32;
 }
 
 /// `Err(message)` for any status but SSYM_OK; SSYM_E_EMPTY_DICT keeps the crate's behaviour (a panic, :369).

@@ -56,6 +56,7 @@ typedef struct ssym_dict ssym_dict;       /* SoundDictionary's feature side (src
 typedef struct ssym_queries ssym_queries; /* the targets of one batch (SoundSequence::sounds)    */
 typedef struct ssym_samples ssym_samples; /* the dictionary sounds' SAMPLES, resident on the GPU   */
 typedef struct ssym_comm ssym_comm;       /* one rank of a source-sharded run: an RCCL communicator  */
+typedef struct ssym_gmm ssym_gmm;         /* a trained Gaussian mixture (the partitioner's model)    */
 
 enum {
     SSYM_OK = 0,
@@ -410,6 +411,52 @@ SSYM_API int32_t ssym_mfcc_num_frames(uint64_t n_samples, uint32_t flags, uint64
 SSYM_API int32_t ssym_mfcc(ssym_ctx *ctx, const double *samples, uint64_t n_samples, double sample_rate,
                   uint32_t n_coeffs, double f_lo, double f_hi, uint32_t flags, double *out_mfccs,
                   double *out_mean);
+
+/* Partitioner: what Partitioner / train_model / discretize_with_model (src/lib.rs:32-151) do --
+ * standardise the frames, fit a Gaussian mixture, label every frame with its most likely component (a "letter") and cut
+ * the letter string with voting experts.  PARITY UNPINNED: the reference's arithmetic is in un-vendored crates
+ * (rusty_machine, voting_experts); the definitions are this library's own, written down in csrc/partition.hip and
+ * DESIGN.md section 5.8.  Everything is f64 on the device and deterministic (a second call gives the same bits).
+ *   feats        n_frames * dim f64, frame-major (HOST; a device pointer with SSYM_OUT_DEVICE, which then also means the
+ *                posteriors / letters / symbols of that call are device memory)
+ *   flags        SSYM_OUT_DEVICE; SSYM_GMM_STANDARDIZE: standardise the frames first, with the statistics of the frames
+ *                of this call (rusty_machine's Standardizer is fitted on the data it transforms, src/lib.rs:56-60)
+ * Limits: 1 <= dim <= 64, 1 <= n_components <= 64, 2 <= alphabet <= 256, depth >= 2, alphabet^depth < 2^63,
+ * n < 2^31 symbols.  Every failure returns SSYM_E_INVALID with a message and touches no device memory. */
+#define SSYM_GMM_STANDARDIZE 8u
+/* Standardizer::default(): per column (x - mean) / sample standard deviation (n - 1); a column whose deviation is 0
+ * (or n < 2) maps to 0.  out: n_frames * dim f64 (HOST, or device with SSYM_OUT_DEVICE). */
+SSYM_API int32_t ssym_standardize(ssym_ctx *ctx, const double *feats, uint64_t n_frames, uint32_t dim, uint32_t flags,
+                         double *out);
+/* GaussianMixtureModel with CovOption::Regularized(eps) (the reference: K = 26, eps = 0.1, max_iters 5 in train_model,
+ * 1000 in discretize).  init_rows: n_components row indices (HOST) whose frames are the starting means -- the library
+ * draws nothing at random.  Needs n_frames >= n_components.  *out is released with ssym_gmm_destroy. */
+SSYM_API int32_t ssym_gmm_train(ssym_ctx *ctx, const double *feats, uint64_t n_frames, uint32_t dim,
+                       uint32_t n_components, const uint64_t *init_rows, double eps, uint32_t max_iters,
+                       uint32_t flags, ssym_gmm **out);
+/* the trained parameters (HOST, each nullable): weights [K], means [K][dim], covariances [K][dim][dim], the stored
+ * log-likelihood (that of the parameters before the last update; the constant (2 pi)^(dim/2) dropped) and the number
+ * of updates made */
+SSYM_API int32_t ssym_gmm_get(const ssym_gmm *gmm, double *weights, double *means, double *covs, double *log_lik,
+                     uint32_t *iters);
+SSYM_API int32_t ssym_gmm_destroy(ssym_ctx *ctx, ssym_gmm *gmm);
+/* posteriors (nullable, n_frames * K f64) and letters (n_frames u8: max_index of each posterior row,
+ * src/sound.rs:486-495) */
+SSYM_API int32_t ssym_gmm_predict(ssym_ctx *ctx, const ssym_gmm *gmm, const double *feats, uint64_t n_frames,
+                         uint32_t flags, double *out_post, uint8_t *out_letters);
+/* voting experts (cast_votes + split_string) on n symbols < alphabet.  out_votes: nullable, 2 * (n + 1) u32 (HOST):
+ * the frequency expert's votes per position 0..n, then the entropy expert's (a position's votes are their sum).
+ * out_seg_frames: room for n lengths (HOST); *n_segments of them are written, summing to n (0 segments for n = 0, one
+ * for 0 < n < depth). */
+SSYM_API int32_t ssym_vote_segments(ssym_ctx *ctx, const uint8_t *symbols, uint64_t n, uint32_t alphabet,
+                           uint32_t depth, uint32_t threshold, uint32_t flags, uint32_t *out_votes,
+                           uint64_t *out_seg_frames, uint64_t *n_segments);
+/* Partitioner::partition_other in frames (multiply by SSYM_MFCC_HOP for samples, src/lib.rs:137): predict + vote in
+ * one call, the letters kept on the device; alphabet = the model's n_components.  out_seg_frames: room for n_frames
+ * lengths (HOST). */
+SSYM_API int32_t ssym_partition(ssym_ctx *ctx, const ssym_gmm *gmm, const double *feats, uint64_t n_frames,
+                       uint32_t depth, uint32_t threshold, uint32_t flags, uint64_t *out_seg_frames,
+                       uint64_t *n_segments);
 
 #ifdef __cplusplus
 }

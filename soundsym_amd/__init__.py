@@ -11,18 +11,24 @@ from ._native import (  # noqa: F401
     SsymError,
     build,
 )
-from .engine import Engine, pack_segments  # noqa: F401
+from .engine import Engine, Gmm, pack_segments  # noqa: F401
 from .api import (  # noqa: F401
     BIN,
     HOP,
+    NCLUSTERS,
     NCOEFFS,
+    Partitioner,
     Sound,
     SoundDictionary,
     SoundSequence,
+    discretize,
+    discretize_with_model,
     length_fit,
+    train_model,
 )
 
 __all__ = [
-    "ABI_SYMBOLS", "BIN", "EmptyDictionaryError", "Engine", "HOP", "LIB_PATH", "NCOEFFS", "Sound",
-    "SoundDictionary", "SoundSequence", "SsymError", "build", "length_fit", "pack_segments",
+    "ABI_SYMBOLS", "BIN", "EmptyDictionaryError", "Engine", "Gmm", "HOP", "LIB_PATH", "NCLUSTERS", "NCOEFFS",
+    "Partitioner", "Sound", "SoundDictionary", "SoundSequence", "SsymError", "build", "discretize",
+    "discretize_with_model", "length_fit", "pack_segments", "train_model",
 ]

@@ -48,6 +48,8 @@ ABI_SYMBOLS = [
     "ssym_comm_unique_id", "ssym_comm_create", "ssym_comm_destroy", "ssym_match_sharded",
     "ssym_local_group_create", "ssym_local_group_destroy", "ssym_comm_create_local",
     "ssym_comm_available", "ssym_comm_set_timeout", "ssym_comm_is_dead", "ssym_comm_inject_fault", "ssym_comm_replay_bounds",
+    "ssym_standardize", "ssym_gmm_train", "ssym_gmm_get", "ssym_gmm_destroy", "ssym_gmm_predict", "ssym_vote_segments",
+    "ssym_partition",
 ]
 COMM_ID_BYTES = 128        # SSYM_COMM_ID_BYTES
 
@@ -55,6 +57,7 @@ COMM_ID_BYTES = 128        # SSYM_COMM_ID_BYTES
 NO_MATCH = 0xFFFFFFFF      # SSYM_NO_MATCH
 MFCC_PAD_TAIL = 4           # SSYM_MFCC_PAD_TAIL
 TOPK_MAX = 64              # SSYM_TOPK_MAX
+GMM_STANDARDIZE = 8        # SSYM_GMM_STANDARDIZE
 
 
 class SsymError(RuntimeError):
@@ -262,6 +265,20 @@ def lib() -> ctypes.CDLL:
     L.ssym_comm_inject_fault.argtypes = [vp, i32, i32]
     L.ssym_comm_replay_bounds.restype = i32
     L.ssym_comm_replay_bounds.argtypes = [vp, vp, ctypes.c_uint32]
+    L.ssym_standardize.restype = i32
+    L.ssym_standardize.argtypes = [vp, vp, u64, u32, u32, vp]
+    L.ssym_gmm_train.restype = i32
+    L.ssym_gmm_train.argtypes = [vp, vp, u64, u32, u32, vp, f64, u32, u32, pvp]
+    L.ssym_gmm_get.restype = i32
+    L.ssym_gmm_get.argtypes = [vp, vp, vp, vp, vp, vp]
+    L.ssym_gmm_destroy.restype = i32
+    L.ssym_gmm_destroy.argtypes = [vp, vp]
+    L.ssym_gmm_predict.restype = i32
+    L.ssym_gmm_predict.argtypes = [vp, vp, vp, u64, u32, vp, vp]
+    L.ssym_vote_segments.restype = i32
+    L.ssym_vote_segments.argtypes = [vp, vp, u64, u32, u32, u32, u32, vp, vp, vp]
+    L.ssym_partition.restype = i32
+    L.ssym_partition.argtypes = [vp, vp, vp, u64, u32, u32, u32, vp, vp]
     _lib = L
     return L
 

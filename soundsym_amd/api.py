@@ -8,6 +8,8 @@ Same names, argument meaning and error behaviour as the reference for the hot pa
     SoundDictionary.match_sound / at_distance               src/sound.rs:346, 351
     SoundSequence.new / from_timestamps / morph_to / clone_from_dictionary   src/sound.rs:392, 419, 440, 451
     SoundSequence.from_distances / to_sound                 src/sound.rs:405, 475
+    discretize / train_model / discretize_with_model        src/lib.rs:32-60
+    Partitioner (new / from_path / depth / threshold / train / partition / partition_other)   src/lib.rs:67-151
 
 Every comparison runs on the GPU through the C ABI (`engine.Engine`); this module only keeps the
 containers, does the length fit of src/sound.rs:456-465 on the matched samples, and translates
@@ -25,6 +27,8 @@ from ._native import NO_MATCH, EmptyDictionaryError
 from .engine import Engine, pack_segments
 
 NCOEFFS = 12   # src/lib.rs:22
+NCLUSTERS = 26 # src/lib.rs:23
+GMM_EPS = 0.1  # CovOption::Regularized(0.1), src/lib.rs:34, 45
 HOP = 256      # src/lib.rs:24
 BIN = 1024     # src/lib.rs:25
 
@@ -404,3 +408,102 @@ class SoundSequence:
         rate = self._sounds[0].sample_rate() if self._sounds else 44100.0
         ncoeffs = self._sounds[0].ncoeffs if self._sounds else NCOEFFS
         return Sound(samples, rate, None, None, ncoeffs)
+
+
+# ---- partitioner (src/lib.rs:32-151; DESIGN.md 5.8: own definitions, PARITY UNPINNED) ---------------------------------
+
+def _data(data, ncoeffs: int) -> np.ndarray:
+    x = np.ascontiguousarray(data, dtype=np.float64)
+    return x.reshape(-1, ncoeffs) if x.ndim == 1 else x
+
+
+def init_rows(n_rows: int, k: int = NCLUSTERS, seed=None) -> np.ndarray:
+    """The starting means of a mixture: k distinct rows drawn by a seeded generator (the library itself draws
+    nothing at random, so a model is a function of the data and these rows)."""
+    if n_rows < k:
+        raise ValueError(f"a mixture of {k} components needs at least {k} frames, got {n_rows}")
+    return np.sort(np.random.default_rng(seed).choice(n_rows, size=k, replace=False)).astype(np.uint64)
+
+
+def train_model(data, seed=None, engine: Optional[Engine] = None, max_iters: int = 5):
+    """train_model (src/lib.rs:43-54): standardise, then a 26-component mixture, CovOption::Regularized(0.1),
+    5 EM iterations, on the GPU (ssym_gmm_train).  data: [frames][ncoeffs] (or flat NCOEFFS-value frames)."""
+    e = engine or default_engine()
+    x = _data(data, NCOEFFS)
+    return e.gmm_train(x, x.shape[1], init_rows(x.shape[0], NCLUSTERS, seed), GMM_EPS, max_iters, standardize=True)
+
+
+def discretize_with_model(data, gmm, engine: Optional[Engine] = None) -> np.ndarray:
+    """discretize_with_model (src/lib.rs:56-60): standardise with the data's own statistics, then the posteriors
+    [frames][K] of the model."""
+    e = engine or gmm.engine
+    x = _data(data, gmm.dim)
+    return e.gmm_predict(gmm, x, standardize=True, want_post=True)[1]
+
+
+def discretize(data, seed=None, engine: Optional[Engine] = None) -> np.ndarray:
+    """discretize (src/lib.rs:32-41): train with up to 1000 EM iterations, then the posteriors of the same data."""
+    gmm = train_model(data, seed, engine, max_iters=1000)
+    try:
+        return discretize_with_model(data, gmm)
+    finally:
+        gmm.close()
+
+
+class Partitioner:
+    """Partitioner (src/lib.rs:67-151): cuts a sound into phoneme-like segments -- GMM letters per MFCC frame, then
+    voting experts over the letter string.  `sound` may be reassigned (examples/reconstruction.rs:72)."""
+
+    def __init__(self, sound: Sound, engine: Optional[Engine] = None):
+        self.sound = sound
+        self._depth = 5          # src/lib.rs:78-79
+        self._threshold = 4
+        self.model = None
+        self._engine = engine
+
+    @staticmethod
+    def new(sound: Sound, engine: Optional[Engine] = None) -> "Partitioner":
+        return Partitioner(sound, engine)
+
+    @staticmethod
+    def from_path(path, engine: Optional[Engine] = None) -> "Partitioner":
+        return Partitioner(Sound.from_path(path, engine=engine), engine)
+
+    def depth(self, n: Optional[int] = None):
+        """Builder: depth(n) sets the depth of the n-gram trie and returns the partitioner; depth() reads it."""
+        if n is None:
+            return self._depth
+        self._depth = int(n)
+        return self
+
+    def threshold(self, n: Optional[int] = None):
+        """Builder: threshold(n) sets the votes a boundary needs and returns the partitioner; threshold() reads it."""
+        if n is None:
+            return self._threshold
+        self._threshold = int(n)
+        return self
+
+    @property
+    def engine(self) -> Engine:
+        if self._engine is None:
+            self._engine = default_engine()
+        return self._engine
+
+    def train(self, seed=None) -> None:
+        """src/lib.rs:97-103: train_model on this partitioner's sound."""
+        if self.model is not None:
+            self.model.close()
+        self.model = train_model(self.sound.mfccs().reshape(-1, self.sound.ncoeffs), seed, self.engine)
+
+    def partition_other(self, sound: Sound) -> List[int]:
+        """src/lib.rs:108-141: segment lengths in SAMPLES (frames x HOP) of `sound`, cut with this model; the frames
+        are standardised with `sound`'s own statistics."""
+        if self.model is None:
+            raise RuntimeError("Must first train model")
+        frames = self.engine.partition(self.model, sound.mfccs().reshape(-1, sound.ncoeffs), self._depth,
+                                       self._threshold, standardize=True)
+        return [int(f) * HOP for f in frames]
+
+    def partition(self) -> List[int]:
+        """src/lib.rs:145-147."""
+        return self.partition_other(self.sound)

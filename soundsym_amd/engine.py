@@ -66,6 +66,29 @@ class _SamplesHandle:
             pass
 
 
+class Gmm:
+    """A trained Gaussian mixture (ssym_gmm): K components over `dim`-value frames, resident on the engine's GPU."""
+
+    def __init__(self, engine: "Engine", ptr: int, k: int, dim: int):
+        self.engine, self.ptr, self.k, self.dim = engine, ptr, k, dim
+        w, mu, cov = np.zeros(k), np.zeros((k, dim)), np.zeros((k, dim, dim))
+        ll, it = ctypes.c_double(), ctypes.c_uint32()
+        nat.check(nat.lib().ssym_gmm_get(ptr, w.ctypes.data, mu.ctypes.data, cov.ctypes.data, ctypes.byref(ll),
+                                         ctypes.byref(it)))
+        self.weights, self.means, self.covs, self.log_lik, self.iters = w, mu, cov, ll.value, it.value
+
+    def close(self):
+        if self.ptr and self.engine.ctx:
+            nat.lib().ssym_gmm_destroy(self.engine.ctx, self.ptr)
+        self.ptr = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class Comm:
     """One rank of a source-sharded run: an RCCL communicator bound to an Engine (ssym_comm)."""
 
@@ -388,6 +411,64 @@ class Engine:
         return (out, mean) if want_mean else out
 
     # -- reconstruction tail (F2) ------------------------------------------------------------
+    # partitioner (own definitions, parity unpinned) ------------------------------------------------
+    def standardize(self, feats, dim: int) -> np.ndarray:
+        """ssym_standardize: per column (x - mean) / sample std, fitted on `feats` itself ([frames][dim] f64)."""
+        x = np.ascontiguousarray(feats, dtype=np.float64).reshape(-1)
+        n = x.size // dim
+        out = np.zeros((n, dim))
+        nat.check(nat.lib().ssym_standardize(self.ctx, x.ctypes.data if n else None, n, dim, 0,
+                                             out.ctypes.data if n else None), self.ctx)
+        return out
+
+    def gmm_train(self, feats, dim: int, init_rows, eps: float = 0.1, max_iters: int = 5,
+                  standardize: bool = True) -> "Gmm":
+        """ssym_gmm_train: a Gaussian mixture with K = len(init_rows) components started at those frames."""
+        x = np.ascontiguousarray(feats, dtype=np.float64).reshape(-1)
+        rows = np.ascontiguousarray(init_rows, dtype=np.uint64)
+        out = ctypes.c_void_p()
+        flags = nat.GMM_STANDARDIZE if standardize else 0
+        nat.check(nat.lib().ssym_gmm_train(self.ctx, x.ctypes.data, x.size // dim, dim, rows.size, rows.ctypes.data,
+                                           float(eps), int(max_iters), flags, ctypes.byref(out)), self.ctx)
+        return Gmm(self, out.value, rows.size, dim)
+
+    def gmm_predict(self, gmm: "Gmm", feats, standardize: bool = True, want_post: bool = False):
+        """ssym_gmm_predict: letters [frames] u8 (and the posteriors [frames][K] when asked)."""
+        x = np.ascontiguousarray(feats, dtype=np.float64).reshape(-1)
+        n = x.size // gmm.dim
+        let = np.zeros(n, dtype=np.uint8)
+        post = np.zeros((n, gmm.k)) if want_post else None
+        flags = nat.GMM_STANDARDIZE if standardize else 0
+        nat.check(nat.lib().ssym_gmm_predict(self.ctx, gmm.ptr, x.ctypes.data if n else None, n, flags,
+                                             post.ctypes.data if want_post and n else None,
+                                             let.ctypes.data if n else None), self.ctx)
+        return (let, post) if want_post else let
+
+    def vote_segments(self, symbols, alphabet: int, depth: int = 5, threshold: int = 4, want_votes: bool = False):
+        """ssym_vote_segments: segment lengths (symbols) of a symbol string, optionally with the votes
+        ([2][n+1]: frequency expert, entropy expert)."""
+        s = np.ascontiguousarray(symbols, dtype=np.uint8).reshape(-1)
+        n = s.size
+        seg = np.zeros(max(n, 1), dtype=np.uint64)
+        votes = np.zeros((2, n + 1), dtype=np.uint32) if want_votes else None
+        m = ctypes.c_uint64()
+        nat.check(nat.lib().ssym_vote_segments(self.ctx, s.ctypes.data if n else None, n, alphabet, depth, threshold,
+                                               0, votes.ctypes.data if want_votes else None, seg.ctypes.data,
+                                               ctypes.byref(m)), self.ctx)
+        out = seg[:m.value].astype(np.int64)
+        return (out, votes) if want_votes else out
+
+    def partition(self, gmm: "Gmm", feats, depth: int = 5, threshold: int = 4, standardize: bool = True) -> np.ndarray:
+        """ssym_partition: predict + vote in one call; segment lengths in frames."""
+        x = np.ascontiguousarray(feats, dtype=np.float64).reshape(-1)
+        n = x.size // gmm.dim
+        seg = np.zeros(max(n, 1), dtype=np.uint64)
+        m = ctypes.c_uint64()
+        flags = nat.GMM_STANDARDIZE if standardize else 0
+        nat.check(nat.lib().ssym_partition(self.ctx, gmm.ptr, x.ctypes.data if n else None, n, depth, threshold,
+                                           flags, seg.ctypes.data, ctypes.byref(m)), self.ctx)
+        return seg[:m.value].astype(np.int64)
+
     def samples(self, samples, sample_offsets):
         """Make the dictionary sounds' samples resident (ssym_samples_create)."""
         smp = np.ascontiguousarray(samples, dtype=np.float64).reshape(-1)

@@ -3,6 +3,7 @@
   read_wav        Sound::from_path        src/sound.rs:116-126  (integer PCM, mono, sample / (i32::MAX >> (32 - bits)))
   write_wav32     Sound::write_file       src/sound.rs:129-143  (32-bit integer PCM, mono)
   audacity_labels_to_timestamps           src/sound.rs:510-532  (start \\t end \\t label; bad numbers -> 0.0)
+  write_splits    write_splits            src/lib.rs:155-178    (one 32-bit WAV per segment, {idx:05}_{split}.wav)
 """
 from __future__ import annotations
 
@@ -109,3 +110,19 @@ def audacity_labels_to_timestamps(path: str) -> List[Tuple[float, float, Optiona
                     return 0.0
             out.append((num(0), num(1), parts[2] if len(parts) > 2 else None))
     return out
+
+
+def write_splits(sound, splits, out_dir: str) -> List[str]:
+    """write_splits (src/lib.rs:155-178): the sound's samples taken in order, `split` samples per file (fewer when the
+    sound runs out), each written as a mono 32-bit WAV named {idx:05}_{split}.wav in out_dir.  Returns the paths."""
+    import os
+    samples = np.asarray(sound.samples(), dtype=np.float64)
+    rate = int(sound.sample_rate())
+    pos, paths = 0, []
+    for idx, split in enumerate(splits):
+        split = int(split)
+        path = os.path.join(str(out_dir), f"{idx:05}_{split}.wav")
+        write_wav32(path, samples[pos:pos + split], rate)
+        pos = min(pos + split, samples.size)
+        paths.append(path)
+    return paths
