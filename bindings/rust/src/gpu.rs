@@ -37,6 +37,9 @@ pub const SSYM_DTW_PRUNE: u32 = 4;
 pub const SSYM_MFCC_PAD_TAIL: u32 = 4;
 pub const SSYM_TOPK_MAX: u32 = 64;
 pub const SSYM_GMM_STANDARDIZE: u32 = 8;
+pub const SSYM_PITCH_VOICED: u32 = 16;
+pub const SSYM_PITCH_WINDOW: u64 = 2048;
+pub const SSYM_PITCH_HOP: u64 = 1024;
 pub const SSYM_NO_MATCH: u32 = 0xffff_ffff;
 pub const SSYM_COMM_ID_BYTES: usize = 128;
 
@@ -173,6 +176,15 @@ extern "C" {
                               flags: u32, out_votes: *mut u32, out_seg_frames: *mut u64, n_segments: *mut u64) -> i32;
     pub fn ssym_partition(ctx: *mut SsymCtx, gmm: *const SsymGmm, feats: *const f64, n_frames: u64, depth: u32,
                           threshold: u32, flags: u32, out_seg_frames: *mut u64, n_segments: *mut u64) -> i32;
+
+    // sound descriptors: max_power and pitch_confidence of a ragged batch (pitch: own definition -- parity unpinned)
+    pub fn ssym_pitch_num_windows(n_samples: u64, out_windows: *mut u64) -> i32;
+    pub fn ssym_sound_descriptors(ctx: *mut SsymCtx, samples: *const f64, sample_offsets: *const u64, n_sounds: u32,
+                                  rate: f64, f_min: f64, f_max: f64, voicing: f64, flags: u32,
+                                  out_max_power: *mut f64, out_pitch_conf: *mut f64) -> i32;
+    pub fn ssym_pitch_track(ctx: *mut SsymCtx, samples: *const f64, sample_offsets: *const u64, n_sounds: u32,
+                            rate: f64, f_min: f64, f_max: f64, voicing: f64, flags: u32, out_freq: *mut f64,
+                            out_strength: *mut f64, out_unvoiced: *mut f64) -> i32;
 }
 
 /// `Err(message)` for any status but SSYM_OK; SSYM_E_EMPTY_DICT keeps the crate's behaviour (a panic, :369).

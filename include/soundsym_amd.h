@@ -458,6 +458,43 @@ SSYM_API int32_t ssym_partition(ssym_ctx *ctx, const ssym_gmm *gmm, const double
                        uint32_t depth, uint32_t threshold, uint32_t flags, uint64_t *out_seg_frames,
                        uint64_t *n_segments);
 
+/* Sound descriptors: Sound::max_power and Sound::pitch_confidence (src/sound.rs:166-179; the
+ * analyses analyze_max_power / analyze_pitch_confidence, :244-269) for a ragged batch of sounds in one call.
+ * PARITY UNPINNED for the pitch side: the reference calls vox_box's pitch::<Hanning> (an un-vendored crate); the
+ * definition is this library's own, after Boersma (1993), written down in csrc/pitch.hip and DESIGN.md section 5.9.
+ * max_power is the reference's arithmetic.  Everything is f64 on the device and deterministic.
+ *   samples, sample_offsets  n_sounds + 1 SAMPLE offsets into `samples` (HOST memory, as for ssym_samples_create);
+ *                            empty sounds are allowed, n_sounds = 0 is a no-op
+ *   rate, f_min, f_max       the lag range [ceil(rate / f_max), floor(rate / f_min)]; the reference passes 44100, 100,
+ *                            500 whatever the sound's own rate (src/sound.rs:265)
+ *   voicing                  the voicing threshold of the unvoiced candidate (the reference: 0.2)
+ *   flags                    SSYM_PITCH_VOICED: a window scores its best voiced strength (0 without one) instead of
+ *                            the larger of that and the unvoiced candidate
+ * Limits: a finite rate > 0, 0 < f_min < f_max, a finite voicing, 2 <= ceil(rate / f_max) <= floor(rate / f_min) <= 682
+ * (three periods per window).  Every failure returns SSYM_E_INVALID with a message and touches no device memory. */
+#define SSYM_PITCH_WINDOW 2048
+#define SSYM_PITCH_HOP 1024
+#define SSYM_PITCH_OCTAVE_COST 0.01
+#define SSYM_PITCH_SILENCE 0.03
+#define SSYM_POWER_WINDOW 128
+#define SSYM_POWER_HOP 64
+#define SSYM_PITCH_VOICED 16u
+/* full pitch windows of a sound: (n - 2048) / 1024 + 1, 0 below 2048 samples */
+SSYM_API int32_t ssym_pitch_num_windows(uint64_t n_samples, uint64_t *out_windows);
+/* analyze_max_power + analyze_pitch_confidence (src/sound.rs:244-269) per sound; out_max_power / out_pitch_conf:
+ * nullable, n_sounds f64 each (HOST).  A sound shorter than a window has confidence 0, one shorter than 128 samples
+ * power 0. */
+SSYM_API int32_t ssym_sound_descriptors(ssym_ctx *ctx, const double *samples, const uint64_t *sample_offsets,
+                               uint32_t n_sounds, double rate, double f_min, double f_max, double voicing,
+                               uint32_t flags, double *out_max_power, double *out_pitch_conf);
+/* the per-window values behind pitch_confidence, sound-major (the windows of sound 0, then of sound 1, ...; counts
+ * from ssym_pitch_num_windows), each nullable, f64 (HOST): the best voiced candidate's frequency and strength (both 0
+ * when the window has none) and the unvoiced candidate's strength; all three NaN for a window holding a non-finite
+ * sample.  flags: as above (the values do not depend on SSYM_PITCH_VOICED). */
+SSYM_API int32_t ssym_pitch_track(ssym_ctx *ctx, const double *samples, const uint64_t *sample_offsets,
+                         uint32_t n_sounds, double rate, double f_min, double f_max, double voicing, uint32_t flags,
+                         double *out_freq, double *out_strength, double *out_unvoiced);
+
 #ifdef __cplusplus
 }
 #endif

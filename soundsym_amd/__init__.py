@@ -21,6 +21,7 @@ from .api import (  # noqa: F401
     Sound,
     SoundDictionary,
     SoundSequence,
+    analyze_sounds,
     discretize,
     discretize_with_model,
     length_fit,
@@ -29,6 +30,6 @@ from .api import (  # noqa: F401
 
 __all__ = [
     "ABI_SYMBOLS", "BIN", "EmptyDictionaryError", "Engine", "Gmm", "HOP", "LIB_PATH", "NCLUSTERS", "NCOEFFS",
-    "Partitioner", "Sound", "SoundDictionary", "SoundSequence", "SsymError", "build", "discretize",
+    "Partitioner", "Sound", "SoundDictionary", "SoundSequence", "SsymError", "analyze_sounds", "build", "discretize",
     "discretize_with_model", "length_fit", "pack_segments", "train_model",
 ]

@@ -49,7 +49,7 @@ ABI_SYMBOLS = [
     "ssym_local_group_create", "ssym_local_group_destroy", "ssym_comm_create_local",
     "ssym_comm_available", "ssym_comm_set_timeout", "ssym_comm_is_dead", "ssym_comm_inject_fault", "ssym_comm_replay_bounds",
     "ssym_standardize", "ssym_gmm_train", "ssym_gmm_get", "ssym_gmm_destroy", "ssym_gmm_predict", "ssym_vote_segments",
-    "ssym_partition",
+    "ssym_partition", "ssym_pitch_num_windows", "ssym_sound_descriptors", "ssym_pitch_track",
 ]
 COMM_ID_BYTES = 128        # SSYM_COMM_ID_BYTES
 
@@ -58,6 +58,8 @@ NO_MATCH = 0xFFFFFFFF      # SSYM_NO_MATCH
 MFCC_PAD_TAIL = 4           # SSYM_MFCC_PAD_TAIL
 TOPK_MAX = 64              # SSYM_TOPK_MAX
 GMM_STANDARDIZE = 8        # SSYM_GMM_STANDARDIZE
+PITCH_VOICED = 16          # SSYM_PITCH_VOICED
+PITCH_WINDOW, PITCH_HOP = 2048, 1024    # SSYM_PITCH_WINDOW, SSYM_PITCH_HOP
 
 
 class SsymError(RuntimeError):
@@ -279,6 +281,12 @@ def lib() -> ctypes.CDLL:
     L.ssym_vote_segments.argtypes = [vp, vp, u64, u32, u32, u32, u32, vp, vp, vp]
     L.ssym_partition.restype = i32
     L.ssym_partition.argtypes = [vp, vp, vp, u64, u32, u32, u32, vp, vp]
+    L.ssym_pitch_num_windows.restype = i32
+    L.ssym_pitch_num_windows.argtypes = [u64, vp]
+    L.ssym_sound_descriptors.restype = i32
+    L.ssym_sound_descriptors.argtypes = [vp, vp, vp, u32, f64, f64, f64, f64, u32, vp, vp]
+    L.ssym_pitch_track.restype = i32
+    L.ssym_pitch_track.argtypes = [vp, vp, vp, u32, f64, f64, f64, f64, u32, vp, vp, vp]
     _lib = L
     return L
 

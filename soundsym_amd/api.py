@@ -10,6 +10,7 @@ Same names, argument meaning and error behaviour as the reference for the hot pa
     SoundSequence.from_distances / to_sound                 src/sound.rs:405, 475
     discretize / train_model / discretize_with_model        src/lib.rs:32-60
     Partitioner (new / from_path / depth / threshold / train / partition / partition_other)   src/lib.rs:67-151
+    Sound.pitch_confidence / preload_pitch_confidence, analyze_sounds       src/sound.rs:170-179, 244-269
 
 Every comparison runs on the GPU through the C ABI (`engine.Engine`); this module only keeps the
 containers, does the length fit of src/sound.rs:456-465 on the matched samples, and translates
@@ -24,13 +25,16 @@ from typing import List, Optional, Sequence
 import numpy as np
 
 from ._native import NO_MATCH, EmptyDictionaryError
-from .engine import Engine, pack_segments
+from .engine import Engine, pack_segments, pitch_lags
 
 NCOEFFS = 12   # src/lib.rs:22
 NCLUSTERS = 26 # src/lib.rs:23
 GMM_EPS = 0.1  # CovOption::Regularized(0.1), src/lib.rs:34, 45
 HOP = 256      # src/lib.rs:24
 BIN = 1024     # src/lib.rs:25
+PITCH_RATE = 44100.0       # analyze_pitch_confidence passes this literal, whatever the sound's rate (src/sound.rs:265)
+PITCH_F_MIN, PITCH_F_MAX = 100.0, 500.0
+PITCH_VOICING = 0.2
 
 _default_engine: Optional[Engine] = None
 
@@ -105,6 +109,7 @@ class Sound:
         self._sample_rate = float(sample_rate)
         self.ncoeffs = int(ncoeffs)
         self._mfccs = None
+        self._pitch_confidence = None
         if mfccs is not None:
             m = np.ascontiguousarray(mfccs, dtype=np.float64).reshape(-1)
             if m.size % self.ncoeffs:
@@ -142,6 +147,20 @@ class Sound:
         from . import io as sio
         return sio.max_power(self._samples)
 
+    def pitch_confidence(self, engine: Optional[Engine] = None) -> float:
+        """src/sound.rs:170-175: the preloaded value, else analyze_pitch_confidence (:258-269) now, on the GPU
+        (ssym_sound_descriptors; its pitch arithmetic is this package's own definition, DESIGN.md 5.9, parity
+        unpinned), with the reference's literal arguments: rate 44100 (whatever this sound's rate), 100-500 Hz,
+        voicing threshold 0.2.  Not cached, as in the reference."""
+        if self._pitch_confidence is not None:
+            return self._pitch_confidence
+        return float(analyze_sounds([self], engine)[1][0])
+
+    def preload_pitch_confidence(self, engine: Optional[Engine] = None) -> None:
+        """src/sound.rs:177-179: analyse once and keep the value."""
+        self._pitch_confidence = None
+        self._pitch_confidence = self.pitch_confidence(engine)
+
     def mean_mfccs(self) -> np.ndarray:       # src/sound.rs:205, analyze_mean_mfccs :271-286
         m = self.mfccs().reshape(-1, self.ncoeffs)
         acc = np.zeros(self.ncoeffs)
@@ -165,6 +184,25 @@ class Sound:
 
     def num_frames(self) -> int:              # src/sound.rs:210
         return self.mfccs().size // self.ncoeffs
+
+
+def analyze_sounds(sounds: Sequence[Sound], engine: Optional[Engine] = None, rate: float = PITCH_RATE,
+                   f_min: float = PITCH_F_MIN, f_max: float = PITCH_F_MAX, voicing: float = PITCH_VOICING,
+                   voiced_only: bool = False):
+    """(max_power [n], pitch_confidence [n]) of a list of Sounds in ONE device call (ssym_sound_descriptors).  The
+    defaults are the reference's literals (src/sound.rs:265: rate 44100 whatever the sounds' own rates).  max_power is
+    the reference's arithmetic (equal to Sound.max_power() up to the summation order of the host helper); the pitch
+    side is this package's own definition (parity unpinned).  voiced_only scores a window by its best
+    voiced candidate alone (SSYM_PITCH_VOICED).  Arguments outside the limits raise ValueError before any device
+    work."""
+    pitch_lags(rate, f_min, f_max, voicing)
+    sounds = list(sounds)
+    if not sounds:
+        return np.zeros(0), np.zeros(0)
+    parts = [s.samples() for s in sounds]
+    offsets = np.concatenate([[0], np.cumsum([p.size for p in parts])]).astype(np.uint64)
+    e = engine or default_engine()
+    return e.sound_descriptors(np.concatenate(parts), offsets, rate, f_min, f_max, voicing, voiced_only)
 
 
 class SoundDictionary:

@@ -164,6 +164,20 @@ def comm_unique_id() -> bytes:
     return buf.raw
 
 
+def pitch_lags(rate: float, f_min: float, f_max: float, voicing: float = 0.2):
+    """The lag range (tau_lo, tau_hi) of ssym_sound_descriptors / ssym_pitch_track, or ValueError for arguments outside
+    their limits -- checked on the host, before anything reaches the device."""
+    import math
+    vals = [float(rate), float(f_min), float(f_max), float(voicing)]
+    if not all(math.isfinite(v) for v in vals) or not (vals[0] > 0 and 0 < vals[1] < vals[2]):
+        raise ValueError("need a finite rate > 0, 0 < f_min < f_max and a finite voicing threshold")
+    lo, hi = math.ceil(vals[0] / vals[2]), math.floor(vals[0] / vals[1])
+    if not (2 <= lo <= hi <= nat.PITCH_WINDOW // 3):
+        raise ValueError(f"need 2 <= ceil(rate / f_max) <= floor(rate / f_min) <= {nat.PITCH_WINDOW // 3}, "
+                         f"got {lo} and {hi}")
+    return lo, hi
+
+
 class Engine:
     """One ssym_ctx: one GPU, one stream, one metric / dtype configuration."""
 
@@ -468,6 +482,50 @@ class Engine:
         nat.check(nat.lib().ssym_partition(self.ctx, gmm.ptr, x.ctypes.data if n else None, n, depth, threshold,
                                            flags, seg.ctypes.data, ctypes.byref(m)), self.ctx)
         return seg[:m.value].astype(np.int64)
+
+    # sound descriptors (the pitch side is an own definition, parity unpinned) -------------------------
+    def _descriptor_inputs(self, samples, offsets, rate, f_min, f_max, voicing):
+        pitch_lags(rate, f_min, f_max, voicing)
+        x = np.ascontiguousarray(samples, dtype=np.float64).reshape(-1)
+        off = np.ascontiguousarray(offsets, dtype=np.uint64).reshape(-1)
+        if off.size < 1 or np.any(np.diff(off.astype(np.int64)) < 0) or int(off[-1]) > x.size:
+            raise ValueError("offsets: n_sounds + 1 non-decreasing sample offsets within `samples`")
+        return x, off
+
+    def sound_descriptors(self, samples, offsets, rate: float = 44100.0, f_min: float = 100.0, f_max: float = 500.0,
+                          voicing: float = 0.2, voiced_only: bool = False):
+        """ssym_sound_descriptors: (max_power [n], pitch_conf [n]) of the sounds samples[offsets[i]:offsets[i+1]]
+        (analyze_max_power / analyze_pitch_confidence, src/sound.rs:244-269), one call for the whole batch."""
+        x, off = self._descriptor_inputs(samples, offsets, rate, f_min, f_max, voicing)
+        n = off.size - 1
+        mp, pc = np.zeros(n), np.zeros(n)
+        flags = nat.PITCH_VOICED if voiced_only else 0
+        nat.check(nat.lib().ssym_sound_descriptors(self.ctx, x.ctypes.data if x.size else None, off.ctypes.data, n,
+                                                   float(rate), float(f_min), float(f_max), float(voicing), flags,
+                                                   mp.ctypes.data if n else None, pc.ctypes.data if n else None),
+                  self.ctx)
+        return mp, pc
+
+    def pitch_track(self, samples, offsets, rate: float = 44100.0, f_min: float = 100.0, f_max: float = 500.0,
+                    voicing: float = 0.2, voiced_only: bool = False):
+        """ssym_pitch_track: (freq, strength, unvoiced, window_offsets): per window the best voiced candidate's
+        frequency and strength (0 and 0 without one) and the unvoiced candidate's strength, sound-major; the windows of
+        sound i are [window_offsets[i], window_offsets[i+1])."""
+        x, off = self._descriptor_inputs(samples, offsets, rate, f_min, f_max, voicing)
+        n = off.size - 1
+        woff = np.zeros(n + 1, dtype=np.int64)
+        w = ctypes.c_uint64(0)
+        for i in range(n):
+            nat.check(nat.lib().ssym_pitch_num_windows(int(off[i + 1] - off[i]), ctypes.byref(w)))
+            woff[i + 1] = woff[i] + int(w.value)
+        nw = int(woff[-1])
+        freq, strength, unvoiced = np.zeros(nw), np.zeros(nw), np.zeros(nw)
+        flags = nat.PITCH_VOICED if voiced_only else 0
+        nat.check(nat.lib().ssym_pitch_track(self.ctx, x.ctypes.data if x.size else None, off.ctypes.data, n,
+                                             float(rate), float(f_min), float(f_max), float(voicing), flags,
+                                             freq.ctypes.data if nw else None, strength.ctypes.data if nw else None,
+                                             unvoiced.ctypes.data if nw else None), self.ctx)
+        return freq, strength, unvoiced, woff
 
     def samples(self, samples, sample_offsets):
         """Make the dictionary sounds' samples resident (ssym_samples_create)."""

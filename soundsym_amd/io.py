@@ -1,6 +1,8 @@
 """WAV and label I/O with the reference's conventions (host side only).
 
   read_wav        Sound::from_path        src/sound.rs:116-126  (integer PCM, mono, sample / (i32::MAX >> (32 - bits)))
+  read_wav_spec   the same, with the bit depth (examples/louder.rs:44-49)
+  write_wav_pcm   the examples' output in the input's spec (examples/louder.rs:58-65)
   write_wav32     Sound::write_file       src/sound.rs:129-143  (32-bit integer PCM, mono)
   audacity_labels_to_timestamps           src/sound.rs:510-532  (start \\t end \\t label; bad numbers -> 0.0)
   write_splits    write_splits            src/lib.rs:155-178    (one 32-bit WAV per segment, {idx:05}_{split}.wav)
@@ -18,6 +20,12 @@ I32_MAX = 2147483647
 def read_wav(path: str) -> Tuple[np.ndarray, float]:
     """Integer-PCM WAV -> (f64 samples, sample rate).  Multi-channel files are read interleaved as
     hound's `samples::<i32>()` does (the reference only ever uses mono files)."""
+    samples, rate, _bits = read_wav_spec(path)
+    return samples, rate
+
+
+def read_wav_spec(path: str) -> Tuple[np.ndarray, float, int]:
+    """read_wav, plus the file's bits per sample: (f64 samples, sample rate, bits)."""
     with open(path, "rb") as f:
         data = f.read()
     if data[:4] != b"RIFF" or data[8:12] != b"WAVE":
@@ -49,7 +57,34 @@ def read_wav(path: str) -> Tuple[np.ndarray, float]:
     else:
         raise ValueError(f"unsupported bit depth {bits}")
     div = float(I32_MAX >> (32 - bits))          # i32::max_value().wrapping_shr(32 - bits), :118-120
-    return ints.astype(np.float64) / div, float(rate)
+    return ints.astype(np.float64) / div, float(rate), int(bits)
+
+
+def write_wav_pcm(path: str, samples, sample_rate: float, bits: int) -> None:
+    """Mono integer PCM of `bits` (8, 16, 24 or 32) bits, each sample written as
+    `(sample * (i32::MAX >> (32 - bits)) as f64) as i32` (examples/louder.rs:61): truncated, NaN -> 0, clipped to the
+    depth's range."""
+    bits = int(bits)
+    if bits not in (8, 16, 24, 32):
+        raise ValueError(f"unsupported bit depth {bits}")
+    v = np.asarray(samples, dtype=np.float64).reshape(-1) * float(I32_MAX >> (32 - bits))
+    v = np.where(np.isnan(v), 0.0, v)
+    lo, hi = -(1 << (bits - 1)), (1 << (bits - 1)) - 1
+    q = np.trunc(np.clip(v, float(lo), float(hi))).astype(np.int64)
+    if bits == 8:
+        body = (q + 128).astype(np.uint8).tobytes()
+    elif bits == 16:
+        body = q.astype("<i2").tobytes()
+    elif bits == 24:
+        u = (q & 0xFFFFFF).astype(np.uint32)
+        body = np.stack([u & 0xFF, (u >> 8) & 0xFF, (u >> 16) & 0xFF], axis=1).astype(np.uint8).tobytes()
+    else:
+        body = q.astype("<i4").tobytes()
+    rate, block = int(sample_rate), bits // 8
+    hdr = b"RIFF" + struct.pack("<I", 36 + len(body)) + b"WAVE" + b"fmt " + struct.pack(
+        "<IHHIIHH", 16, 1, 1, rate, rate * block, block, bits) + b"data" + struct.pack("<I", len(body))
+    with open(path, "wb") as f:
+        f.write(hdr + body)
 
 
 def pcm32(samples: np.ndarray) -> np.ndarray:
