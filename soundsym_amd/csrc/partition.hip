@@ -11,7 +11,9 @@
 //                 max_iters times: E-step (log domain, max subtracted; the constant (2 pi)^(d/2) is DROPPED from every
 //                 density, as the crate drops it, so log_lik = sum_i log sum_k pi_k |S_k|^-1/2 exp(-maha / 2)); stop when
 //                 |log_lik - previous| < 1e-15 (previous starts at 0); M-step N_k = sum r, pi = N_k / n,
-//                 mu = sum r x / N_k, S = sum r x x^T / N_k - mu mu^T + eps I.  A component with N_k == 0 keeps mu and
+//                 mu = sum r x / N_k, S = sum r (x - mu)(x - mu)^T / N_k + eps I, formed from moments about the
+//                 data's column means c (mu = c + delta, S = sum r (x - c)(x - c)^T / N_k - delta delta^T + eps I;
+//                 moments about 0 would cancel for large offsets).  A component with N_k == 0 keeps mu and
 //                 S and gets weight 0 (the crate would produce NaN).  f64 throughout, Cholesky factors,
 //                 log det = 2 sum log L_jj
 //   letters       max_index of each posterior row (src/sound.rs:486-495): first strict maximum starting from (0, 0.0)
@@ -28,7 +30,8 @@
 // block walks its chunk in tiles of 32 frames; the means, inverse Cholesky factors and log coefficients of all K
 // components sit in LDS when they fit (d = 12, K = 26: 19 KB), else they are read through the same flat pointers from
 // global memory; 8 groups of 32 lanes take the components of the tile's frames, one lane per (frame, component)
-// Mahalanobis term; then every lane owns a few of the K (d+1)(d+2)/2 moments (1, x_i, x_i x_j) and adds the tile's
+// Mahalanobis term; then every lane owns a few of the K (d+1)(d+2)/2 moments about the column means c (1, y_i,
+// y_i y_j with y = x - c, a second copy of the tile) and adds the tile's
 // r-weighted values into the block's private partial slab.  Update: one block per component sums the slabs in block
 // order, forms pi, mu, S and re-factors.  Every EM iteration is enqueued up front; a device word makes the iterations
 // after convergence return at once, and the host synchronises once per call.  Voting: n-gram codes in base A (first
@@ -185,6 +188,7 @@ struct EStepArgs {
     uint64_t n;
     int d, K, M;                  // M = (d+1)(d+2)/2 moments per component
     const double *model;          // GmmLayout
+    const double *shift;          // train: [d] the moments are taken about (the data's column means)
     int model_in_lds;
     const uint16_t *tab;
     uint64_t chunk;               // frames per block, a multiple of kTile
@@ -201,8 +205,10 @@ __global__ __launch_bounds__(256) void gmm_estep_kernel(EStepArgs a)
     extern __shared__ double lds[];
     const int d = a.d, K = a.K, M = a.M, tid = threadIdx.x;
     const int xs_stride = d + 2, ps_stride = K + 1;
+    const bool train = a.part != nullptr;
     double *xs = lds;                                   // [kTile][d + 2]; column d = 1
-    double *ps = xs + kTile * xs_stride;                // [kTile][K + 1]: log terms, then posteriors
+    double *xc = xs + kTile * xs_stride;                // train: [kTile][d + 2], x - shift; column d = 1
+    double *ps = xc + (train ? kTile * xs_stride : 0);  // [kTile][K + 1]: log terms, then posteriors
     double *llt = ps + kTile * ps_stride;               // [kTile]
     uint16_t *tab = (uint16_t *)(llt + kTile);          // [M], padded to doubles below
     double *mlds = llt + kTile + (M + 3) / 4;
@@ -220,7 +226,6 @@ __global__ __launch_bounds__(256) void gmm_estep_kernel(EStepArgs a)
         linv = llinv;
         logc = llogc;
     }
-    const bool train = a.part != nullptr;
     const int A = K * M;
     double *slab = train ? a.part + (size_t)blockIdx.x * (A + 1) : nullptr;
     if (train)
@@ -234,7 +239,10 @@ __global__ __launch_bounds__(256) void gmm_estep_kernel(EStepArgs a)
         for (int q = tid; q < kTile * (d + 1); q += 256) {
             const int f = q / (d + 1), j = q % (d + 1);
             const uint64_t g = t0 + f;
-            xs[f * xs_stride + j] = g < f1 ? (j < d ? a.x[g * d + j] : 1.0) : 0.0;
+            const double v = g < f1 ? (j < d ? a.x[g * d + j] : 1.0) : 0.0;
+            xs[f * xs_stride + j] = v;
+            if (train)
+                xc[f * xs_stride + j] = g < f1 && j < d ? __dsub_rn(v, a.shift[j]) : v;
         }
         __syncthreads();
         {
@@ -294,7 +302,7 @@ __global__ __launch_bounds__(256) void gmm_estep_kernel(EStepArgs a)
                 const int i = tab[m] & 0xff, j = tab[m] >> 8;
                 double s = 0.0;
                 for (int f = 0; f < kTile; ++f)
-                    s = __dadd_rn(s, __dmul_rn(ps[f * ps_stride + k], __dmul_rn(xs[f * xs_stride + i], xs[f * xs_stride + j])));
+                    s = __dadd_rn(s, __dmul_rn(ps[f * ps_stride + k], __dmul_rn(xc[f * xs_stride + i], xc[f * xs_stride + j])));
                 slab[q] = __dadd_rn(slab[q], s);
             }
         }
@@ -309,13 +317,14 @@ __global__ __launch_bounds__(256) void gmm_estep_kernel(EStepArgs a)
 // it >= 0: iteration `it`'s convergence test and M-step.  state: [0] converged, [1] iterations, [2] factorisation failed;
 // llh[it] = the log-likelihood stored before iteration it (llh[0] = 0).
 __global__ __launch_bounds__(256) void gmm_update_kernel(double *__restrict__ model, int K, int d, int M,
-                                                         const double *__restrict__ part, int G, uint64_t n,
+                                                         const double *__restrict__ part,
+                                                         const double *__restrict__ shift, int G, uint64_t n,
                                                          double eps, int it, int *__restrict__ state,
                                                          double *__restrict__ llh)
 {
     __shared__ double S[kMaxMoments];
     __shared__ double C[kMaxDim * (kMaxDim + 1)];
-    __shared__ double mus[kMaxDim];
+    __shared__ double dl[kMaxDim];
     __shared__ int flag;
     const int k = blockIdx.x, tid = threadIdx.x, cs = d + 1;
     const GmmLayout L(K, d);
@@ -357,9 +366,11 @@ __global__ __launch_bounds__(256) void gmm_update_kernel(double *__restrict__ mo
             }
             return;
         }
+        // the slabs hold moments about c = shift: mu = c + delta, delta = sum r (x - c) / N_k,
+        // S = sum r (x - c)(x - c)^T / N_k - delta delta^T + eps I (no cancellation against |c|)
         for (int i = tid; i < d; i += 256) {
-            mus[i] = __ddiv_rn(S[P + i], Nk);
-            model[L.mu + (size_t)k * d + i] = mus[i];
+            dl[i] = __ddiv_rn(S[P + i], Nk);
+            model[L.mu + (size_t)k * d + i] = __dadd_rn(shift[i], dl[i]);
         }
         __syncthreads();
         for (int e = tid; e < P; e += 256) {
@@ -368,7 +379,7 @@ __global__ __launch_bounds__(256) void gmm_update_kernel(double *__restrict__ mo
             while ((j + 1) * (j + 2) / 2 <= e)
                 ++j;
             const int i = e - j * (j + 1) / 2;
-            double c = __dsub_rn(__ddiv_rn(S[e], Nk), __dmul_rn(mus[i], mus[j]));
+            double c = __dsub_rn(__ddiv_rn(S[e], Nk), __dmul_rn(dl[i], dl[j]));
             if (i == j)
                 c = __dadd_rn(c, eps);
             C[i * cs + j] = c;
@@ -740,10 +751,10 @@ static int32_t upload_table(ssym_ctx *ctx, Scratch &sc, int d, uint16_t **tab)
     return SSYM_OK;
 }
 
-static size_t estep_lds(int d, int K, int M, bool model_in_lds)
+static size_t estep_lds(int d, int K, int M, bool model_in_lds, bool train)
 {
     const GmmLayout L(K, d);
-    size_t dbl = (size_t)kTile * (d + 2) + (size_t)kTile * (K + 1) + kTile + (M + 3) / 4;
+    size_t dbl = (size_t)kTile * (d + 2) * (train ? 2 : 1) + (size_t)kTile * (K + 1) + kTile + (M + 3) / 4;
     if (model_in_lds)
         dbl += L.total - L.mu - (size_t)K * d * d;   // means, inverse factors, log coefficients
     return dbl * sizeof(double);
@@ -759,7 +770,7 @@ static int32_t launch_estep(ssym_ctx *ctx, EStepArgs a, int G)
 {
     const bool in_lds = model_fits_lds(a.d, a.K);
     a.model_in_lds = in_lds ? 1 : 0;
-    const size_t lds = estep_lds(a.d, a.K, a.M, in_lds);
+    const size_t lds = estep_lds(a.d, a.K, a.M, in_lds, a.part != nullptr);
     gmm_estep_kernel<<<G, 256, lds, ctx->stream>>>(a);
     SSYM_HIP_CHECK(ctx, hipGetLastError());
     return SSYM_OK;
@@ -775,7 +786,7 @@ static int32_t predict_dev(ssym_ctx *ctx, Scratch &sc, const ssym_gmm *gmm, cons
     int G;
     uint64_t chunk;
     chunking(ctx, n, 1, &G, &chunk);
-    EStepArgs a{z, n, d, K, M, gmm->dev, 0, tab, chunk, nullptr, nullptr, post, letters};
+    EStepArgs a{z, n, d, K, M, gmm->dev, nullptr, 0, tab, chunk, nullptr, nullptr, post, letters};
     return launch_estep(ctx, a, G);
 }
 
@@ -1036,12 +1047,13 @@ int32_t ssym_gmm_train(ssym_ctx *ctx, const double *feats, uint64_t n_frames, ui
         (rc = column_pass(ctx, sc, z, n_frames, d, 2, mean, tab, eps, K, g->dev + L.cov)) != SSYM_OK)
         return fail(rc);
     gmm_init_kernel<<<1, 256, 0, st>>>(z, d, K, rows, g->dev);
-    gmm_update_kernel<<<K, 256, 0, st>>>(g->dev, K, d, M, part, G, n_frames, eps, -1, state, llh);
+    gmm_update_kernel<<<K, 256, 0, st>>>(g->dev, K, d, M, part, mean, G, n_frames, eps, -1, state, llh);
+    // the moments are taken about the column means (mean), so the M-step does not cancel against large offsets
     for (uint32_t it = 0; it < max_iters; ++it) {
-        EStepArgs a{z, n_frames, d, K, M, g->dev, 0, tab, chunk, state, part, nullptr, nullptr};
+        EStepArgs a{z, n_frames, d, K, M, g->dev, mean, 0, tab, chunk, state, part, nullptr, nullptr};
         if ((rc = launch_estep(ctx, a, G)) != SSYM_OK)
             return fail(rc);
-        gmm_update_kernel<<<K, 256, 0, st>>>(g->dev, K, d, M, part, G, n_frames, eps, (int)it, state, llh);
+        gmm_update_kernel<<<K, 256, 0, st>>>(g->dev, K, d, M, part, mean, G, n_frames, eps, (int)it, state, llh);
     }
     e = hipGetLastError();
     g->host.resize(L.linv);

@@ -50,7 +50,8 @@ def posteriors(x, weights, means, covs):
 
 
 def gmm_train(x, init_rows, eps=0.1, max_iters=5):
-    """EM as DESIGN.md 5.8 states it.  Returns dict(weights, means, covs, log_lik, iters)."""
+    """EM as DESIGN.md 5.8 states it.  Returns dict(weights, means, covs, log_lik, iters, totals): totals[j] is the
+    log-likelihood computed at step j (the last one is the step that stopped the loop, when it converged)."""
     x = np.asarray(x, dtype=np.float64)
     n, d = x.shape
     K = len(init_rows)
@@ -59,10 +60,11 @@ def gmm_train(x, init_rows, eps=0.1, max_iters=5):
     c0 = (x - mu).T @ (x - mu) / (n - 1) + eps * np.eye(d)
     covs = np.repeat(c0[None], K, axis=0)
     weights = np.full(K, 1.0 / K)
-    log_lik, iters = 0.0, 0
+    log_lik, iters, totals = 0.0, 0, []
     for _ in range(max_iters):
         r, ll = posteriors(x, weights, means, covs)
         total = ll.sum()
+        totals.append(total)
         if abs(total - log_lik) < 1e-15:
             break
         log_lik = total
@@ -76,7 +78,7 @@ def gmm_train(x, init_rows, eps=0.1, max_iters=5):
             means[k] = (r[:, k:k + 1] * x).sum(axis=0) / Nk[k]
             dx = x - means[k]
             covs[k] = (r[:, k:k + 1] * dx).T @ dx / Nk[k] + eps * np.eye(d)
-    return dict(weights=weights, means=means, covs=covs, log_lik=log_lik, iters=iters)
+    return dict(weights=weights, means=means, covs=covs, log_lik=log_lik, iters=iters, totals=totals)
 
 
 def max_index(row) -> int:

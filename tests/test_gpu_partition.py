@@ -111,9 +111,10 @@ def _check_votes(eng, s, A, d, t):
     assert seg.sum() == N and np.all(seg > 0)
     vf, vh, margins, _ = ref.vote_details(s, d)
     assert np.array_equal(votes[0], vf), "frequency-expert votes differ"
-    # entropy expert: a window with a near-tie may put its vote on any of its d - 1 positions
+    # entropy expert: a window with a near-tie may put its vote on any of its d - 1 positions; an exact tie (margin 0)
+    # resolves to the first maximum on both sides and is not excused
     slack = np.zeros(N + 1, dtype=np.int64)
-    for w in np.nonzero(margins < 1e-9)[0]:
+    for w in np.nonzero((margins > 0) & (margins < 1e-9))[0]:
         slack[w + 1:w + d] += 1
     assert np.all(np.abs(votes[1].astype(np.int64) - vh) <= slack)
     total = votes[0].astype(np.int64) + votes[1]
