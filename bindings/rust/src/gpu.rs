@@ -161,6 +161,13 @@ extern "C" {
     pub fn ssym_mfcc_num_frames(n_samples: u64, flags: u32, out_frames: *mut u64) -> i32;
     pub fn ssym_mfcc(ctx: *mut SsymCtx, samples: *const f64, n_samples: u64, sample_rate: f64, n_coeffs: u32,
                      f_lo: f64, f_hi: f64, flags: u32, out_mfccs: *mut f64, out_mean: *mut f64) -> i32;
+    pub fn ssym_mfcc_batch(ctx: *mut SsymCtx, samples: *const f64, sample_offsets: *const u64, n_sounds: u32,
+                           sample_rate: f64, n_coeffs: u32, f_lo: f64, f_hi: f64, flags: u32,
+                           out_frame_offsets: *mut u64, out_mfccs: *mut f64, out_mean: *mut f64) -> i32;
+    // SoundSequence::new's neighbour distances (mean MFCCs, cosine_sim_angular)
+    pub fn ssym_sequence_distances(ctx: *mut SsymCtx, feats: *const f64, frame_offsets: *const u64, n_sounds: u32,
+                                   dim: u32, flags: u32, out_mean: *mut f64, out_sim: *mut f64,
+                                   out_dist: *mut f64) -> i32;
 
     // partitioner: standardiser, Gaussian mixture, voting experts (own definitions -- parity unpinned)
     pub fn ssym_standardize(ctx: *mut SsymCtx, feats: *const f64, n_frames: u64, dim: u32, flags: u32,

@@ -411,6 +411,35 @@ SSYM_API int32_t ssym_mfcc_num_frames(uint64_t n_samples, uint32_t flags, uint64
 SSYM_API int32_t ssym_mfcc(ssym_ctx *ctx, const double *samples, uint64_t n_samples, double sample_rate,
                   uint32_t n_coeffs, double f_lo, double f_hi, uint32_t flags, double *out_mfccs,
                   double *out_mean);
+/* analyze_mfccs for a ragged batch of sounds in one call.  Sound i is
+ * samples[sample_offsets[i] .. sample_offsets[i+1]); its frames are bit for bit what ssym_mfcc returns for those
+ * samples with the same rate / n_coeffs / f_lo / f_hi / flags, written at out_mfccs + out_frame_offsets[i] * n_coeffs.
+ *   sample_offsets     n_sounds + 1 (HOST), non-decreasing; empty sounds allowed; n_sounds = 0 is a no-op
+ *   flags              SSYM_MFCC_PAD_TAIL (a window reads zeros past ITS OWN sound's end, never the next sound),
+ *                      SSYM_OUT_DEVICE (out_mfccs is device memory)
+ *   out_frame_offsets  nullable, n_sounds + 1 u64 (HOST): prefix sums of ssym_mfcc_num_frames per sound
+ *   out_mfccs          total_frames * n_coeffs f64 (size it with ssym_mfcc_num_frames per sound)
+ *   out_mean           nullable, n_sounds * n_coeffs f64 (HOST): analyze_mean_mfccs per sound (src/sound.rs:271-286),
+ *                      NaN for a sound with no frame (the reference's 0 / 0; ssym_mfcc's own out_mean writes 0 there
+ *                      and stays as it is)
+ * Limits as ssym_mfcc.  Every failure of the arguments returns SSYM_E_INVALID with a message before device memory is
+ * touched, and leaves the host outputs unwritten. */
+SSYM_API int32_t ssym_mfcc_batch(ssym_ctx *ctx, const double *samples, const uint64_t *sample_offsets,
+                                 uint32_t n_sounds, double sample_rate, uint32_t n_coeffs, double f_lo, double f_hi,
+                                 uint32_t flags, uint64_t *out_frame_offsets, double *out_mfccs, double *out_mean);
+/* SoundSequence::new's distances (src/sound.rs:392-398) for a sequence of n_sounds feature blocks:
+ * out_dist[i] = cosine_sim_angular(mean_i, mean_{i+1}) (src/sound.rs:59-69), i < n_sounds - 1.  Definitions in
+ * csrc/sequence.hip and DESIGN.md section 5.10: mean as analyze_mean_mfccs (NaN for a block without frames), the
+ * reference's cosine_sim (squared norms, rulinalg's dot), its clamp (sim < -1 also maps to 1), acos * FRAC_1_PI.
+ *   feats, frame_offsets  as ssym_dict_create, f64 (HOST; feats is device memory with SSYM_OUT_DEVICE)
+ *   dim                   1 <= dim <= 64
+ *   out_mean  nullable, n_sounds * dim (HOST);  out_sim  nullable, n_sounds - 1 (HOST): the clamped similarity before
+ *   acos;  out_dist  nullable, n_sounds - 1 (HOST)
+ * Every failure of the arguments returns SSYM_E_INVALID with a message before device memory is touched, and leaves
+ * the host outputs unwritten. */
+SSYM_API int32_t ssym_sequence_distances(ssym_ctx *ctx, const double *feats, const uint64_t *frame_offsets,
+                                         uint32_t n_sounds, uint32_t dim, uint32_t flags,
+                                         double *out_mean, double *out_sim, double *out_dist);
 
 /* Partitioner: what Partitioner / train_model / discretize_with_model (src/lib.rs:32-151) do --
  * standardise the frames, fit a Gaussian mixture, label every frame with its most likely component (a "letter") and cut

@@ -21,7 +21,9 @@ from .api import (  # noqa: F401
     Sound,
     SoundDictionary,
     SoundSequence,
+    analyze_mfccs,
     analyze_sounds,
+    cosine_sim_angular,
     discretize,
     discretize_with_model,
     length_fit,
@@ -30,6 +32,7 @@ from .api import (  # noqa: F401
 
 __all__ = [
     "ABI_SYMBOLS", "BIN", "EmptyDictionaryError", "Engine", "Gmm", "HOP", "LIB_PATH", "NCLUSTERS", "NCOEFFS",
-    "Partitioner", "Sound", "SoundDictionary", "SoundSequence", "SsymError", "analyze_sounds", "build", "discretize",
+    "Partitioner", "Sound", "SoundDictionary", "SoundSequence", "SsymError", "analyze_mfccs", "analyze_sounds", "build",
+    "cosine_sim_angular", "discretize",
     "discretize_with_model", "length_fit", "pack_segments", "train_model",
 ]

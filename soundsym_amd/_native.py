@@ -50,6 +50,7 @@ ABI_SYMBOLS = [
     "ssym_comm_available", "ssym_comm_set_timeout", "ssym_comm_is_dead", "ssym_comm_inject_fault", "ssym_comm_replay_bounds",
     "ssym_standardize", "ssym_gmm_train", "ssym_gmm_get", "ssym_gmm_destroy", "ssym_gmm_predict", "ssym_vote_segments",
     "ssym_partition", "ssym_pitch_num_windows", "ssym_sound_descriptors", "ssym_pitch_track",
+    "ssym_mfcc_batch", "ssym_sequence_distances",
 ]
 COMM_ID_BYTES = 128        # SSYM_COMM_ID_BYTES
 
@@ -287,6 +288,10 @@ def lib() -> ctypes.CDLL:
     L.ssym_sound_descriptors.argtypes = [vp, vp, vp, u32, f64, f64, f64, f64, u32, vp, vp]
     L.ssym_pitch_track.restype = i32
     L.ssym_pitch_track.argtypes = [vp, vp, vp, u32, f64, f64, f64, f64, u32, vp, vp, vp]
+    L.ssym_mfcc_batch.restype = i32
+    L.ssym_mfcc_batch.argtypes = [vp, vp, vp, u32, f64, u32, f64, f64, u32, vp, vp, vp]
+    L.ssym_sequence_distances.restype = i32
+    L.ssym_sequence_distances.argtypes = [vp, vp, vp, u32, u32, u32, vp, vp, vp]
     _lib = L
     return L
 

@@ -11,6 +11,7 @@ Same names, argument meaning and error behaviour as the reference for the hot pa
     discretize / train_model / discretize_with_model        src/lib.rs:32-60
     Partitioner (new / from_path / depth / threshold / train / partition / partition_other)   src/lib.rs:67-151
     Sound.pitch_confidence / preload_pitch_confidence, analyze_sounds       src/sound.rs:170-179, 244-269
+    SoundSequence.distances, cosine_sim_angular, analyze_mfccs (batched)    src/sound.rs:392-398, 436, 59-69, 215-242
 
 Every comparison runs on the GPU through the C ABI (`engine.Engine`); this module only keeps the
 containers, does the length fit of src/sound.rs:456-465 on the matched samples, and translates
@@ -56,6 +57,37 @@ def frame_features(samples, sample_rate: float, ncoeffs: int = NCOEFFS, engine: 
     src/sound.rs:335) expects of a parent sound; pad_tail=False keeps full windows only."""
     e = engine or default_engine()
     return e.mfcc(samples, sample_rate, ncoeffs, pad_tail=pad_tail).reshape(-1)
+
+
+def analyze_mfccs(sample_arrays, sample_rate: float, ncoeffs: int = NCOEFFS, engine: Optional[Engine] = None,
+                  pad_tail: bool = False) -> List[np.ndarray]:
+    """analyze_mfccs (src/sound.rs:215-242) for many sounds of one sample rate in ONE device call (ssym_mfcc_batch):
+    a list of flat frame-major f64 arrays, array i bit for bit `Sound.from_samples(sample_arrays[i], rate,
+    None).mfccs()`.  The frame counts are host arithmetic; when no sound holds a frame, no device call is made."""
+    parts = [np.ascontiguousarray(a, dtype=np.float64).reshape(-1) for a in sample_arrays]
+    if not parts:
+        return []
+    frames = [Engine.mfcc_num_frames(p.size, pad_tail) for p in parts]
+    if not any(frames):
+        return [np.zeros(0) for _ in parts]
+    offsets = np.concatenate([[0], np.cumsum([p.size for p in parts])]).astype(np.uint64)
+    e = engine or default_engine()
+    feats, fo = e.mfcc_batch(np.concatenate(parts), offsets, sample_rate, ncoeffs, pad_tail=pad_tail)
+    flat = feats.reshape(-1)
+    return [flat[int(fo[i]) * ncoeffs:int(fo[i + 1]) * ncoeffs].copy() for i in range(len(parts))]
+
+
+def cosine_sim_angular(me, you, engine: Optional[Engine] = None) -> float:
+    """cosine_sim_angular (src/sound.rs:59-69) of two equally long vectors on the GPU: the reference's cosine_sim
+    (squared norms, rulinalg's dot), its clamp (a similarity below -1 also maps to 1), acos * FRAC_1_PI.  One
+    ssym_sequence_distances call on two one-frame sounds (a one-frame mean is the frame itself)."""
+    a = np.ascontiguousarray(me, dtype=np.float64).reshape(-1)
+    b = np.ascontiguousarray(you, dtype=np.float64).reshape(-1)
+    if a.size != b.size or a.size == 0:
+        raise ValueError("cosine_sim_angular: two non-empty vectors of the same length")
+    e = engine or default_engine()
+    dist = e.sequence_distances(np.concatenate([a, b]), np.array([0, 1, 2], dtype=np.uint64), a.size)
+    return float(dist[0])
 
 
 def _round_half_away(x: float) -> int:
@@ -224,13 +256,25 @@ class SoundDictionary:
     @staticmethod
     def from_path(path, engine: Optional[Engine] = None) -> "SoundDictionary":
         """SoundDictionary::from_path (src/sound.rs:304-321): every *.wav of a directory, in directory
-        order (sorted here, so that indices do not depend on the file system), features analysed."""
+        order (sorted here, so that indices do not depend on the file system), features analysed -- one
+        ssym_mfcc_batch per sample rate, each sound's features bit for bit those of Sound.from_path."""
         import os
+        from . import io as sio
         d = SoundDictionary(engine)
+        files = []
         for name in sorted(os.listdir(str(path))):
             if os.path.splitext(name)[1] != ".wav":
                 continue
-            d.sounds.append(Sound.from_path(os.path.join(str(path), name), engine=engine))
+            samples, rate = sio.read_wav(os.path.join(str(path), name))
+            files.append((np.ascontiguousarray(samples, dtype=np.float64).reshape(-1), float(rate),
+                          os.path.splitext(name)[0]))
+        feats = [None] * len(files)
+        for rate in dict.fromkeys(f[1] for f in files):
+            which = [i for i, f in enumerate(files) if f[1] == rate]
+            for i, m in zip(which, analyze_mfccs([files[i][0] for i in which], rate, NCOEFFS, engine)):
+                feats[i] = m
+        for (samples, rate, stem), m in zip(files, feats):
+            d.sounds.append(Sound(samples, rate, m, stem, NCOEFFS))
         return d
 
     @staticmethod
@@ -363,7 +407,11 @@ def length_fit(matched: np.ndarray, n_target: int) -> np.ndarray:
 
 
 class SoundSequence:
-    """Sequence of sounds (src/sound.rs:375-484); `distances` between neighbours is not kept."""
+    """Sequence of sounds (src/sound.rs:375-484).  The reference stores the angular distances between neighbours when
+    the sequence is built (SoundSequence::new, :392-398); here `sounds()` is a mutable list, so `distances()` computes
+    them from the current sounds on every call, on the GPU (ssym_sequence_distances).  Sounds without features (the
+    length-fitted sounds of clone_from_dictionary, to_sound()) are analysed for it as the reference re-analyses them
+    (:457-462), in one ssym_mfcc_batch per sample rate, and nothing is stored on the Sound."""
 
     def __init__(self, sounds: Sequence[Sound]):
         self._sounds = list(sounds)
@@ -375,21 +423,43 @@ class SoundSequence:
     def sounds(self) -> List[Sound]:                                    # src/sound.rs:432
         return self._sounds
 
+    def distances(self, engine: Optional[Engine] = None) -> np.ndarray:  # src/sound.rs:436 (values: :392-398)
+        """cosine_sim_angular of the mean MFCCs of each pair of neighbouring sounds: len(sounds) - 1 values, NaN
+        next to a sound without frames (its mean is 0 / 0).  Mixed ncoeffs raise ValueError before any device work."""
+        sounds = list(self._sounds)
+        if len(sounds) < 2:
+            return np.zeros(0)
+        dims = {s.ncoeffs for s in sounds}
+        if len(dims) != 1:
+            raise ValueError(f"distances: the sounds carry different ncoeffs {sorted(dims)}")
+        dim = dims.pop()
+        e = engine or default_engine()
+        feats = [s.mfccs() if s.has_mfccs() else None for s in sounds]
+        missing = [i for i, f in enumerate(feats) if f is None]
+        for rate in dict.fromkeys(sounds[i].sample_rate() for i in missing):
+            which = [i for i in missing if sounds[i].sample_rate() == rate]
+            for i, m in zip(which, analyze_mfccs([sounds[i].samples() for i in which], rate, dim, e)):
+                feats[i] = m
+        flat, off = pack_segments(feats, dim)
+        return e.sequence_distances(flat, off, dim)
+
     @staticmethod
     def from_timestamps(sound: Sound, timestamps, engine: Optional[Engine] = None) -> "SoundSequence":
         """SoundSequence::from_timestamps (src/sound.rs:419-430): one Sound per (start s, end s, label),
         samples [round(start * rate), round(end * rate)] INCLUSIVE (:422-424), features analysed.  The cast is Rust's
         saturating one: a negative or NaN time reads as sample 0 and the call proceeds; only an end beyond the sound
         (or a start beyond the end) fails, where the reference's slice panics."""
-        out = []
+        cuts = []
         smp, rate = sound.samples(), sound.sample_rate()
         for start, end, label in timestamps:
             a, b = _round_as_usize(start * rate), _round_as_usize(end * rate)        # `.round() as usize`, :422-423
             if b + 1 > smp.size or a > b + 1:
                 # the reference slices `samples[start_sample..end_sample + 1]` (:424) and panics out of range
                 raise IndexError(f"timestamp ({start}, {end}) -> samples [{a}, {b}] outside the sound's {smp.size} samples")
-            out.append(Sound.from_samples(smp[a:b + 1].copy(), rate, None, label, sound.ncoeffs, engine=engine))
-        return SoundSequence(out)
+            cuts.append((smp[a:b + 1].copy(), label))
+        # every sound's features in one ssym_mfcc_batch (Sound.from_samples' framing, bit for bit)
+        feats = analyze_mfccs([c[0] for c in cuts], rate, sound.ncoeffs, engine)
+        return SoundSequence([Sound(c[0], rate, m, c[1], sound.ncoeffs) for c, m in zip(cuts, feats)])
 
     @staticmethod
     def from_distances(distances: Sequence[float], start: Sound,
@@ -423,8 +493,8 @@ class SoundSequence:
             if diff == 0:
                 out.append(s)                                            # :463-464 shares the Arc
             else:
-                # :457-462 builds a new Sound from the fitted samples and re-analyses it; the
-                # re-analysis (MFCC) is outside this package, the samples are exact
+                # :457-462 builds a new Sound from the fitted samples and re-analyses it; here the
+                # fitted Sound carries no features and distances() analyses it when asked
                 out.append(Sound(length_fit(s.samples(), sound.samples().size), sound.sample_rate(),
                                  None, None, s.ncoeffs))
         return SoundSequence(out)

@@ -23,8 +23,17 @@
 //
 // Mapping: one frame per 256-thread workgroup, the 1024-point FFT in LDS (16 KB), two butterflies
 // per thread per stage; filter m and coefficient j are each one thread's sequential sum.
+//
+// Batch (ssym_mfcc_batch): a ragged batch of sounds, sound i = samples[off[i], off[i+1]).  Its frames
+// are numbered across the batch (the prefix sums of ssym_mfcc_num_frames per sound); a grid-stride loop takes one
+// frame per workgroup, which finds its sound by a wave-uniform binary search over the n + 1 frame offsets and runs
+// the same per-frame body (mfcc_frame) as the single-sound kernel on that sound's samples alone: a window reads
+// zeros past ITS sound's end (SSYM_MFCC_PAD_TAIL), never the next sound.  So every sound's frames are bit for bit
+// those of ssym_mfcc.  One upload of all samples, one launch (plus the means kernel of sequence.hip when out_mean
+// is asked), one copy back, one synchronisation per call.
 #include "ssym_internal.hpp"
 
+#include <algorithm>
 #include <cmath>
 #include <vector>
 
@@ -44,73 +53,273 @@ struct MfccTables {
 
 __device__ __forceinline__ uint32_t bitrev10(uint32_t i) { return __brev(i) >> 22; }
 
+// one frame: samples x[base .. base + 1024) of a sound of n samples (zeros past n) -> out[0 .. nCoeffs).  Called
+// by every thread of a 256-thread workgroup; re / im / logE are the workgroup's LDS, free on entry and on return.
+__device__ __forceinline__ void mfcc_frame(const double *__restrict__ x, uint64_t n, uint64_t base,
+                                           const MfccTables &tb, int nf, int nCoeffs, double *__restrict__ out,
+                                           double *re, double *im, double *logE)
+{
+    const int tid = threadIdx.x;
+#pragma unroll
+    for (int q = 0; q < kBin / 256; ++q) {
+        const int i = tid + 256 * q;
+        const uint64_t g = base + i;
+        const double v = g < n ? x[g] : 0.0;
+        const uint32_t r = bitrev10((uint32_t)i);
+        re[r] = __dmul_rn(v, tb.win[i]);
+        im[r] = 0.0;
+    }
+    __syncthreads();
+#pragma unroll 1
+    for (int s = 1; s <= 10; ++s) {
+        const int half = 1 << (s - 1);
+#pragma unroll
+        for (int q = 0; q < 2; ++q) {
+            const int b = tid + 256 * q;
+            const int j = b & (half - 1);
+            const int i0 = ((b >> (s - 1)) << s) + j, i1 = i0 + half;
+            const int k = j << (10 - s);
+            const double wr = tb.twRe[k], wi = tb.twIm[k];
+            const double xr = re[i1], xi = im[i1];
+            const double tr = __dsub_rn(__dmul_rn(wr, xr), __dmul_rn(wi, xi));
+            const double ti = __dadd_rn(__dmul_rn(wr, xi), __dmul_rn(wi, xr));
+            const double ar = re[i0], ai = im[i0];
+            re[i1] = __dsub_rn(ar, tr);
+            im[i1] = __dsub_rn(ai, ti);
+            re[i0] = __dadd_rn(ar, tr);
+            im[i0] = __dadd_rn(ai, ti);
+        }
+        __syncthreads();
+    }
+    // power spectrum into re[0..512] (each thread reads and writes its own bins only)
+    for (int k = tid; k < kSpec; k += 256) {
+        const double a = re[k], b = im[k];
+        re[k] = __dadd_rn(__dmul_rn(a, a), __dmul_rn(b, b));
+    }
+    __syncthreads();
+    if (tid < nf) {
+        const double *w = tb.weights + (size_t)tid * kSpec;
+        double e = 0.0;
+        for (int k = tb.lo[tid]; k < tb.hi[tid]; ++k)
+            e = __dadd_rn(e, __dmul_rn(w[k], re[k]));
+        logE[tid] = log(fmax(e, 1e-30));
+    }
+    __syncthreads();
+    if (tid < nCoeffs) {
+        const double *d = tb.dct + (size_t)tid * nf;
+        double c = 0.0;
+        for (int m = 0; m < nf; ++m)
+            c = __dadd_rn(c, __dmul_rn(logE[m], d[m]));
+        out[tid] = c;
+    }
+    __syncthreads();   // re / im / logE are reused by the next frame
+}
+
 __global__ __launch_bounds__(256) void mfcc_kernel(const double *__restrict__ samples, uint64_t nSamples,
                                                    uint64_t nFrames, MfccTables tb, int nf, int nCoeffs,
                                                    double *__restrict__ out)
 {
     __shared__ double re[kBin], im[kBin];
     __shared__ double logE[kMaxFilters];
-    const int tid = threadIdx.x;
+    for (uint64_t t = blockIdx.x; t < nFrames; t += gridDim.x)
+        mfcc_frame(samples, nSamples, t * kHop, tb, nf, nCoeffs, out + t * nCoeffs, re, im, logE);
+}
+
+// frameOff / smpOff: n + 1 offsets each (frames across the batch, samples from the batch's first sample)
+__global__ __launch_bounds__(256) void mfcc_batch_kernel(const double *__restrict__ samples,
+                                                         const uint64_t *__restrict__ frameOff,
+                                                         const uint64_t *__restrict__ smpOff, uint32_t nSounds,
+                                                         MfccTables tb, int nf, int nCoeffs, double *__restrict__ out)
+{
+    __shared__ double re[kBin], im[kBin];
+    __shared__ double logE[kMaxFilters];
+    const uint64_t nFrames = frameOff[nSounds];
     for (uint64_t t = blockIdx.x; t < nFrames; t += gridDim.x) {
-        const uint64_t base = t * kHop;
-#pragma unroll
-        for (int q = 0; q < kBin / 256; ++q) {
-            const int i = tid + 256 * q;
-            const uint64_t g = base + i;
-            const double v = g < nSamples ? samples[g] : 0.0;
-            const uint32_t r = bitrev10((uint32_t)i);
-            re[r] = __dmul_rn(v, tb.win[i]);
-            im[r] = 0.0;
+        // the sound s with frameOff[s] <= t < frameOff[s + 1] (the last such s: empty sounds hold no frame)
+        uint32_t lo = 0, hi = nSounds;
+        while (hi - lo > 1) {
+            const uint32_t mid = lo + (hi - lo) / 2;
+            if (frameOff[mid] <= t)
+                lo = mid;
+            else
+                hi = mid;
         }
-        __syncthreads();
-#pragma unroll 1
-        for (int s = 1; s <= 10; ++s) {
-            const int half = 1 << (s - 1);
-#pragma unroll
-            for (int q = 0; q < 2; ++q) {
-                const int b = tid + 256 * q;
-                const int j = b & (half - 1);
-                const int i0 = ((b >> (s - 1)) << s) + j, i1 = i0 + half;
-                const int k = j << (10 - s);
-                const double wr = tb.twRe[k], wi = tb.twIm[k];
-                const double xr = re[i1], xi = im[i1];
-                const double tr = __dsub_rn(__dmul_rn(wr, xr), __dmul_rn(wi, xi));
-                const double ti = __dadd_rn(__dmul_rn(wr, xi), __dmul_rn(wi, xr));
-                const double ar = re[i0], ai = im[i0];
-                re[i1] = __dsub_rn(ar, tr);
-                im[i1] = __dsub_rn(ai, ti);
-                re[i0] = __dadd_rn(ar, tr);
-                im[i0] = __dadd_rn(ai, ti);
-            }
-            __syncthreads();
-        }
-        // power spectrum into re[0..512] (each thread reads and writes its own bins only)
-        for (int k = tid; k < kSpec; k += 256) {
-            const double a = re[k], b = im[k];
-            re[k] = __dadd_rn(__dmul_rn(a, a), __dmul_rn(b, b));
-        }
-        __syncthreads();
-        if (tid < nf) {
-            const double *w = tb.weights + (size_t)tid * kSpec;
-            double e = 0.0;
-            for (int k = tb.lo[tid]; k < tb.hi[tid]; ++k)
-                e = __dadd_rn(e, __dmul_rn(w[k], re[k]));
-            logE[tid] = log(fmax(e, 1e-30));
-        }
-        __syncthreads();
-        if (tid < nCoeffs) {
-            const double *d = tb.dct + (size_t)tid * nf;
-            double c = 0.0;
-            for (int m = 0; m < nf; ++m)
-                c = __dadd_rn(c, __dmul_rn(logE[m], d[m]));
-            out[t * nCoeffs + tid] = c;
-        }
-        __syncthreads();   // re / im / logE are reused by the next frame
+        const uint64_t s0 = smpOff[lo], len = smpOff[lo + 1] - s0;
+        mfcc_frame(samples + s0, len, (t - frameOff[lo]) * kHop, tb, nf, nCoeffs, out + t * nCoeffs, re, im, logE);
     }
 }
 
 static double mel_of(double f) { return 1127.0 * std::log(1.0 + f / 700.0); }
 static double hz_of(double m) { return 700.0 * (std::exp(m / 1127.0) - 1.0); }
+
+// the host tables of one (rate, n_coeffs, f_lo, f_hi) in f64 (the oracle tabulates the same expressions), and where
+// each lies in `tab` / `range` (nf lower, then nf upper bin bounds)
+struct HostTables {
+    int nf = 0;
+    size_t oWin = 0, oTwRe = 0, oTwIm = 0, oW = 0, oDct = 0;
+    std::vector<double> tab;
+    std::vector<int> range;
+    MfccTables on(const double *dTab, const int *dRange) const
+    {
+        return MfccTables{dTab + oWin, dTab + oTwRe, dTab + oTwIm, dTab + oW, dRange, dRange + nf, dTab + oDct};
+    }
+};
+
+static void build_tables(HostTables &h, double sample_rate, uint32_t n_coeffs, double f_lo, double f_hi)
+{
+    const int nf = 2 * (int)n_coeffs + 2;
+    const double PI = 3.14159265358979323846;
+    h.nf = nf;
+    h.oWin = 0;
+    h.oTwRe = h.oWin + kBin;
+    h.oTwIm = h.oTwRe + kBin / 2;
+    h.oW = h.oTwIm + kBin / 2;
+    h.oDct = h.oW + (size_t)nf * kSpec;
+    std::vector<double> &tab = h.tab;
+    tab.assign(h.oDct + (size_t)n_coeffs * nf, 0.0);
+    for (int i = 0; i < kBin; ++i)
+        tab[h.oWin + i] = 0.5 - 0.5 * std::cos(2.0 * PI * (double)i / (double)kBin);
+    for (int k = 0; k < kBin / 2; ++k) {
+        tab[h.oTwRe + k] = std::cos(-2.0 * PI * (double)k / (double)kBin);
+        tab[h.oTwIm + k] = std::sin(-2.0 * PI * (double)k / (double)kBin);
+    }
+    std::vector<int> &range = h.range;
+    range.assign(2 * (size_t)nf, 0);
+    {
+        const double top = std::min(f_hi, 0.5 * sample_rate);
+        const double m0 = mel_of(f_lo), m1 = mel_of(top);
+        for (int m = 0; m < nf; ++m) {
+            const double h0 = hz_of(m0 + (m1 - m0) * (double)m / (double)(nf + 1));
+            const double h1 = hz_of(m0 + (m1 - m0) * (double)(m + 1) / (double)(nf + 1));
+            const double h2 = hz_of(m0 + (m1 - m0) * (double)(m + 2) / (double)(nf + 1));
+            int lo = kSpec, hi = 0;
+            for (int k = 0; k < kSpec; ++k) {
+                const double f = (double)k * sample_rate / (double)kBin;
+                double w = 0.0;
+                if (f > h0 && f <= h1)
+                    w = (f - h0) / (h1 - h0);
+                else if (f > h1 && f < h2)
+                    w = (h2 - f) / (h2 - h1);
+                tab[h.oW + (size_t)m * kSpec + k] = w;
+                if (w != 0.0) {
+                    lo = std::min(lo, k);
+                    hi = std::max(hi, k + 1);
+                }
+            }
+            range[m] = lo < hi ? lo : 0;
+            range[nf + m] = lo < hi ? hi : 0;
+        }
+    }
+    for (uint32_t j = 0; j < n_coeffs; ++j)
+        for (int m = 0; m < nf; ++m)
+            tab[h.oDct + (size_t)j * nf + m] = std::cos(PI * (double)(j + 1) * ((double)m + 0.5) / (double)nf);
+}
+
+static bool mfcc_args_ok(double sample_rate, uint32_t n_coeffs, double f_lo, double f_hi)
+{
+    return !(n_coeffs == 0 || n_coeffs > 64 || !(sample_rate > 0.0) || !(f_lo >= 0.0) || !(f_hi > f_lo));
+}
+
+#define SSYM_MFCC_TRY(expr)                    \
+    do {                                       \
+        const int32_t rc__ = (expr);           \
+        if (rc__ != SSYM_OK)                   \
+            return rc__;                       \
+    } while (0)
+
+static int32_t mfcc_batch(ssym_ctx *ctx, const double *samples, const uint64_t *off, uint32_t n, double rate,
+                          uint32_t nc, double f_lo, double f_hi, uint32_t flags, uint64_t *outFrameOff,
+                          double *outMfccs, double *outMean)
+{
+    const char *fn = "ssym_mfcc_batch";
+    if (!ctx)
+        return SSYM_E_INVALID;
+    if (!mfcc_args_ok(rate, nc, f_lo, f_hi)) {
+        ctx->err = std::string(fn) + ": need 1 <= n_coeffs <= 64, sample_rate > 0, 0 <= f_lo < f_hi";
+        return SSYM_E_INVALID;
+    }
+    if (n == 0)
+        return SSYM_OK;
+    if (!off) {
+        ctx->err = std::string(fn) + ": NULL sample_offsets";
+        return SSYM_E_INVALID;
+    }
+    // every check before any output or device memory is touched
+    std::vector<uint64_t> offs(2 * ((size_t)n + 1));      // frame offsets [n + 1], then rebased sample offsets [n + 1]
+    uint64_t *fo = offs.data(), *so = offs.data() + n + 1;
+    const uint64_t base = off[0];
+    for (uint32_t i = 0; i < n; ++i) {
+        if (off[i + 1] < off[i]) {
+            ctx->err = std::string(fn) + ": sample_offsets must not decrease";
+            return SSYM_E_INVALID;
+        }
+        uint64_t T = 0;
+        ssym_mfcc_num_frames(off[i + 1] - off[i], flags, &T);
+        fo[i + 1] = fo[i] + T;
+        so[i + 1] = off[i + 1] - base;
+    }
+    const uint64_t F = fo[n], total = so[n];
+    if (total && !samples) {
+        ctx->err = std::string(fn) + ": NULL samples";
+        return SSYM_E_INVALID;
+    }
+    if (F && !outMfccs) {
+        ctx->err = std::string(fn) + ": NULL out_mfccs";
+        return SSYM_E_INVALID;
+    }
+    if (F == 0) {                            // no frame anywhere: nothing runs on the device
+        if (outFrameOff)
+            std::copy(fo, fo + n + 1, outFrameOff);
+        if (outMean)
+            for (size_t i = 0; i < (size_t)n * nc; ++i)
+                outMean[i] = std::nan("");
+        return SSYM_OK;
+    }
+    SSYM_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    const bool outDev = (flags & SSYM_OUT_DEVICE) != 0;
+    HostTables ht;
+    build_tables(ht, rate, nc, f_lo, f_hi);
+
+    Blocks bl(ctx);
+    double *dTab = nullptr, *dX = nullptr, *dOut = nullptr, *dMean = nullptr;
+    int *dRange = nullptr;
+    uint64_t *dOff = nullptr;
+    SSYM_MFCC_TRY(bl.get(&dTab, ht.tab.size()));
+    SSYM_MFCC_TRY(bl.get(&dRange, ht.range.size()));
+    SSYM_MFCC_TRY(bl.get(&dOff, offs.size()));
+    SSYM_MFCC_TRY(bl.get(&dX, total));
+    if (outDev)
+        dOut = outMfccs;
+    else
+        SSYM_MFCC_TRY(bl.get(&dOut, F * nc));
+    if (outMean)
+        SSYM_MFCC_TRY(bl.get(&dMean, (size_t)n * nc));
+    SSYM_HIP_CHECK(ctx, hipMemcpyAsync(dTab, ht.tab.data(), ht.tab.size() * sizeof(double), hipMemcpyHostToDevice, st));
+    SSYM_HIP_CHECK(ctx, hipMemcpyAsync(dRange, ht.range.data(), ht.range.size() * sizeof(int), hipMemcpyHostToDevice,
+                                       st));
+    SSYM_HIP_CHECK(ctx, hipMemcpyAsync(dOff, offs.data(), offs.size() * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+    SSYM_HIP_CHECK(ctx, hipMemcpyAsync(dX, samples + base, total * sizeof(double), hipMemcpyHostToDevice, st));
+    const unsigned grid = (unsigned)std::min<uint64_t>(F, (uint64_t)ctx->num_cus * 16);
+    mfcc_batch_kernel<<<grid, 256, 0, st>>>(dX, dOff, dOff + n + 1, n, ht.on(dTab, dRange), ht.nf, (int)nc, dOut);
+    SSYM_HIP_CHECK(ctx, hipGetLastError());
+    if (outMean)
+        SSYM_MFCC_TRY(launch_frame_means(ctx, dOut, dOff, n, nc, dMean));
+    if (!outDev)
+        SSYM_HIP_CHECK(ctx, hipMemcpyAsync(outMfccs, dOut, F * nc * sizeof(double), hipMemcpyDeviceToHost, st));
+    std::vector<double> mean;
+    if (outMean) {
+        mean.resize((size_t)n * nc);
+        SSYM_HIP_CHECK(ctx, hipMemcpyAsync(mean.data(), dMean, mean.size() * sizeof(double), hipMemcpyDeviceToHost,
+                                           st));
+    }
+    SSYM_HIP_CHECK(ctx, hipStreamSynchronize(st));
+    if (outFrameOff)
+        std::copy(fo, fo + n + 1, outFrameOff);
+    if (outMean)
+        std::copy(mean.begin(), mean.end(), outMean);
+    return SSYM_OK;
+}
 
 }  // namespace ssym
 
@@ -136,7 +345,7 @@ int32_t ssym_mfcc(ssym_ctx *ctx, const double *samples, uint64_t n_samples, doub
     return guarded(ctx, [&]() -> int32_t {
     if (!ctx)
         return SSYM_E_INVALID;
-    if (n_coeffs == 0 || n_coeffs > 64 || !(sample_rate > 0.0) || !(f_lo >= 0.0) || !(f_hi > f_lo)) {
+    if (!mfcc_args_ok(sample_rate, n_coeffs, f_lo, f_hi)) {
         ctx->err = "ssym_mfcc: need 1 <= n_coeffs <= 64, sample_rate > 0, 0 <= f_lo < f_hi";
         return SSYM_E_INVALID;
     }
@@ -155,48 +364,12 @@ int32_t ssym_mfcc(ssym_ctx *ctx, const double *samples, uint64_t n_samples, doub
     hipStream_t st = ctx->stream;
     const bool outDev = (flags & SSYM_OUT_DEVICE) != 0;
 
-    // tables (host f64; the oracle tabulates the same expressions)
-    const int nf = 2 * (int)n_coeffs + 2;
-    const double PI = 3.14159265358979323846;
-    std::vector<double> tab;
-    const size_t oWin = 0, oTwRe = oWin + kBin, oTwIm = oTwRe + kBin / 2, oW = oTwIm + kBin / 2,
-                 oDct = oW + (size_t)nf * kSpec, nTab = oDct + (size_t)n_coeffs * nf;
-    tab.assign(nTab, 0.0);
-    for (int i = 0; i < kBin; ++i)
-        tab[oWin + i] = 0.5 - 0.5 * std::cos(2.0 * PI * (double)i / (double)kBin);
-    for (int k = 0; k < kBin / 2; ++k) {
-        tab[oTwRe + k] = std::cos(-2.0 * PI * (double)k / (double)kBin);
-        tab[oTwIm + k] = std::sin(-2.0 * PI * (double)k / (double)kBin);
-    }
-    std::vector<int> range(2 * (size_t)nf, 0);
-    {
-        const double top = std::min(f_hi, 0.5 * sample_rate);
-        const double m0 = mel_of(f_lo), m1 = mel_of(top);
-        for (int m = 0; m < nf; ++m) {
-            const double h0 = hz_of(m0 + (m1 - m0) * (double)m / (double)(nf + 1));
-            const double h1 = hz_of(m0 + (m1 - m0) * (double)(m + 1) / (double)(nf + 1));
-            const double h2 = hz_of(m0 + (m1 - m0) * (double)(m + 2) / (double)(nf + 1));
-            int lo = kSpec, hi = 0;
-            for (int k = 0; k < kSpec; ++k) {
-                const double f = (double)k * sample_rate / (double)kBin;
-                double w = 0.0;
-                if (f > h0 && f <= h1)
-                    w = (f - h0) / (h1 - h0);
-                else if (f > h1 && f < h2)
-                    w = (h2 - f) / (h2 - h1);
-                tab[oW + (size_t)m * kSpec + k] = w;
-                if (w != 0.0) {
-                    lo = std::min(lo, k);
-                    hi = std::max(hi, k + 1);
-                }
-            }
-            range[m] = lo < hi ? lo : 0;
-            range[nf + m] = lo < hi ? hi : 0;
-        }
-    }
-    for (uint32_t j = 0; j < n_coeffs; ++j)
-        for (int m = 0; m < nf; ++m)
-            tab[oDct + (size_t)j * nf + m] = std::cos(PI * (double)(j + 1) * ((double)m + 0.5) / (double)nf);
+    HostTables ht;
+    build_tables(ht, sample_rate, n_coeffs, f_lo, f_hi);
+    const std::vector<double> &tab = ht.tab;
+    const std::vector<int> &range = ht.range;
+    const size_t nTab = tab.size();
+    const int nf = ht.nf;
 
     double *dTab = nullptr, *dSmp = nullptr, *dOut = nullptr;
     int *dRange = nullptr;
@@ -217,7 +390,7 @@ int32_t ssym_mfcc(ssym_ctx *ctx, const double *samples, uint64_t n_samples, doub
         if (e == hipSuccess)
             e = hipMemcpyAsync(dSmp, samples, n_samples * sizeof(double), hipMemcpyHostToDevice, st);
         if (e == hipSuccess) {
-            MfccTables tb{dTab + oWin, dTab + oTwRe, dTab + oTwIm, dTab + oW, dRange, dRange + nf, dTab + oDct};
+            const MfccTables tb = ht.on(dTab, dRange);
             const unsigned grid = (unsigned)std::min<uint64_t>(T, (uint64_t)ctx->num_cus * 16);
             mfcc_kernel<<<grid, 256, 0, st>>>(dSmp, n_samples, T, tb, nf, (int)n_coeffs, dOut);
             e = hipGetLastError();
@@ -253,6 +426,16 @@ int32_t ssym_mfcc(ssym_ctx *ctx, const double *samples, uint64_t n_samples, doub
         return SSYM_E_HIP;
     }
     return SSYM_OK;
+    });
+}
+
+int32_t ssym_mfcc_batch(ssym_ctx *ctx, const double *samples, const uint64_t *sample_offsets, uint32_t n_sounds,
+                        double sample_rate, uint32_t n_coeffs, double f_lo, double f_hi, uint32_t flags,
+                        uint64_t *out_frame_offsets, double *out_mfccs, double *out_mean)
+{
+    return guarded(ctx, [&]() -> int32_t {
+        return mfcc_batch(ctx, samples, sample_offsets, n_sounds, sample_rate, n_coeffs, f_lo, f_hi, flags,
+                          out_frame_offsets, out_mfccs, out_mean);
     });
 }
 

@@ -237,28 +237,6 @@ __global__ __launch_bounds__(kThreads) void pitch_kernel(const double *__restric
     }
 }
 
-// a set of device blocks freed together
-struct Blocks {
-    ssym_ctx *ctx;
-    std::vector<void *> list;
-    explicit Blocks(ssym_ctx *c) : ctx(c) {}
-    ~Blocks()
-    {
-        for (void *p : list)
-            dev_free(ctx, p);
-    }
-    template <class T>
-    int32_t get(T **p, size_t count)
-    {
-        void *q = nullptr;
-        const int32_t rc = dev_alloc(ctx, &q, count * sizeof(T) > 0 ? count * sizeof(T) : 8);
-        if (rc == SSYM_OK)
-            list.push_back(q);
-        *p = (T *)q;
-        return rc;
-    }
-};
-
 #define SSYM_PITCH_TRY(expr)                   \
     do {                                       \
         const int32_t rc__ = (expr);           \

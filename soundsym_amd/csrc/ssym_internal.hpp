@@ -284,6 +284,34 @@ struct StageScope {                    // one per public entry point that moves 
     ~StageScope() { if (c) --c->api_depth; }
 };
 
+// a set of device blocks freed together (pitch.hip, mfcc.hip, sequence.hip)
+struct Blocks {
+    ssym_ctx *ctx;
+    std::vector<void *> list;
+    explicit Blocks(ssym_ctx *c) : ctx(c) {}
+    ~Blocks()
+    {
+        for (void *p : list)
+            dev_free(ctx, p);
+    }
+    template <class T>
+    int32_t get(T **p, size_t count)
+    {
+        void *q = nullptr;
+        const int32_t rc = dev_alloc(ctx, &q, count * sizeof(T) > 0 ? count * sizeof(T) : 8);
+        if (rc == SSYM_OK)
+            list.push_back(q);
+        *p = (T *)q;
+        return rc;
+    }
+};
+
+// sequence.hip: analyze_mean_mfccs per block of frames on ctx's stream (no synchronisation).  feats: the frames of
+// the blocks, frame-major, dim values each, block i = frames [off[i] - off[0], off[i + 1] - off[0]); off: n + 1 u64
+// (DEVICE); mean: n * dim f64 (DEVICE), NaN for a block without frames
+int32_t launch_frame_means(ssym_ctx *ctx, const double *feats, const uint64_t *off, uint32_t n, uint32_t dim,
+                           double *mean);
+
 // dtw_filter.hip
 bool filter_supported(const ssym_ctx *ctx, const SegmentSet &src, const SegmentSet &tgt);
 // a band the banded kernel cannot take: the unbanded filter runs instead and bounds the banded cost from below

@@ -424,6 +424,72 @@ class Engine:
         nat.check(rc, self.ctx)
         return (out, mean) if want_mean else out
 
+    def mfcc_batch(self, samples, sample_offsets, sample_rate: float, ncoeffs: int = 12, f_lo: float = 100.0,
+                   f_hi: float = 8000.0, pad_tail: bool = False, want_mean: bool = False, out=None):
+        """ssym_mfcc_batch: the MFCCs of the sounds samples[sample_offsets[i]:sample_offsets[i+1]] in one call,
+        each bit for bit what `mfcc` gives for that sound alone.  Returns (feats [F][ncoeffs], frame_offsets [n+1]
+        u64), plus the per-sound means [n][ncoeffs] (NaN for a sound without frames) when asked.  `out`: a caller's
+        contiguous f64 device tensor of F * ncoeffs values (SSYM_OUT_DEVICE), returned in place of feats."""
+        x = np.ascontiguousarray(samples, dtype=np.float64).reshape(-1)
+        off = np.ascontiguousarray(sample_offsets, dtype=np.uint64).reshape(-1)
+        if off.size < 1 or np.any(np.diff(off.astype(np.int64)) < 0) or int(off[-1]) > x.size:
+            raise ValueError("sample_offsets: n_sounds + 1 non-decreasing sample offsets within `samples`")
+        n = off.size - 1
+        flags = nat.MFCC_PAD_TAIL if pad_tail else 0
+        nframes = sum(self.mfcc_num_frames(int(off[i + 1] - off[i]), pad_tail) for i in range(n))
+        fo = np.zeros(n + 1, dtype=np.uint64)
+        mean = np.zeros((n, ncoeffs), dtype=np.float64)
+        if out is not None:
+            if not _is_device_tensor(out) or not out.is_contiguous() or out.numel() != nframes * ncoeffs or \
+                    str(out.dtype) != "torch.float64":
+                raise ValueError(f"out: a contiguous f64 device tensor of {nframes * ncoeffs} values")
+            feats, dst, flags = out, out.data_ptr() if nframes else None, flags | nat.OUT_DEVICE
+        else:
+            feats = np.zeros((nframes, ncoeffs), dtype=np.float64)
+            dst = feats.ctypes.data if nframes else None
+        nat.check(nat.lib().ssym_mfcc_batch(self.ctx, x.ctypes.data if x.size else None, off.ctypes.data, n,
+                                            float(sample_rate), ncoeffs, float(f_lo), float(f_hi), flags,
+                                            fo.ctypes.data, dst, mean.ctypes.data if want_mean and n else None),
+                  self.ctx)
+        return (feats, fo, mean) if want_mean else (feats, fo)
+
+    @staticmethod
+    def mfcc_num_frames(n_samples: int, pad_tail: bool = False) -> int:
+        """ssym_mfcc_num_frames (host arithmetic, no device)."""
+        t = ctypes.c_uint64(0)
+        nat.check(nat.lib().ssym_mfcc_num_frames(int(n_samples), nat.MFCC_PAD_TAIL if pad_tail else 0,
+                                                 ctypes.byref(t)))
+        return int(t.value)
+
+    def sequence_distances(self, feats, frame_offsets, dim: int, want_mean: bool = False, want_sim: bool = False):
+        """ssym_sequence_distances: SoundSequence::new's distances (src/sound.rs:392-398), cosine_sim_angular of the
+        mean features of each pair of neighbouring blocks: dist [n-1], plus the means [n][dim] and the clamped
+        similarities [n-1] when asked.  feats: host array or f64 device tensor, frame-major."""
+        off = np.ascontiguousarray(frame_offsets, dtype=np.uint64).reshape(-1)
+        if off.size < 1:
+            raise ValueError("frame_offsets: n_sounds + 1 offsets")
+        n = off.size - 1
+        flags = 0
+        if _is_device_tensor(feats):
+            if not feats.is_contiguous() or str(feats.dtype) != "torch.float64":
+                raise ValueError("feats: a contiguous f64 device tensor")
+            ptr, flags = feats.data_ptr() if feats.numel() else None, nat.OUT_DEVICE
+        else:
+            x = np.ascontiguousarray(feats, dtype=np.float64).reshape(-1)
+            ptr = x.ctypes.data if x.size else None
+        npairs = max(n - 1, 0)
+        mean, sim, dist = np.zeros((n, dim)), np.zeros(npairs), np.zeros(npairs)
+        nat.check(nat.lib().ssym_sequence_distances(self.ctx, ptr, off.ctypes.data, n, dim, flags,
+                                                    mean.ctypes.data if want_mean and n else None,
+                                                    sim.ctypes.data if want_sim and npairs else None,
+                                                    dist.ctypes.data if npairs else None), self.ctx)
+        res = (dist,)
+        if want_mean:
+            res += (mean,)
+        if want_sim:
+            res += (sim,)
+        return res if len(res) > 1 else dist
+
     # -- reconstruction tail (F2) ------------------------------------------------------------
     # partitioner (DESIGN.md 5.8; own definitions, parity unpinned) ------------------------------------------------
     def standardize(self, feats, dim: int) -> np.ndarray:
