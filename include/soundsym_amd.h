@@ -403,7 +403,9 @@ SSYM_API int32_t ssym_reconstruct(ssym_ctx *ctx, const ssym_samples *s, const ui
  *                (default: full windows only, (n_samples - 1024) / 256 + 1);
  *                SSYM_OUT_DEVICE: out_mfccs is a device pointer (feeds ssym_*_create_device)
  *   out_mfccs    frames * n_coeffs f64, frames as ssym_mfcc_num_frames reports
- *   out_mean     nullable, n_coeffs f64 (HOST): analyze_mean_mfccs (src/sound.rs:271-286) */
+ *   out_mean     nullable, n_coeffs f64 (HOST): analyze_mean_mfccs (src/sound.rs:271-286)
+ * Limits: 1 <= n_coeffs <= 64, sample_rate > 0, 0 <= f_lo < min(f_hi, sample_rate / 2), else SSYM_E_INVALID;
+ * f_hi above sample_rate / 2 is cut there. */
 #define SSYM_MFCC_BIN 1024
 #define SSYM_MFCC_HOP 256
 #define SSYM_MFCC_PAD_TAIL 4u

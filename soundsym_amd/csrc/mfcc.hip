@@ -215,9 +215,12 @@ static void build_tables(HostTables &h, double sample_rate, uint32_t n_coeffs, d
             tab[h.oDct + (size_t)j * nf + m] = std::cos(PI * (double)(j + 1) * ((double)m + 0.5) / (double)nf);
 }
 
+// the band must be non-empty below Nyquist: with f_lo >= min(f_hi, rate / 2) the mel grid runs from f_lo DOWN to
+// rate / 2, every filter weight is 0 and the coefficients would be the DCT of the constant 1e-30 floor
 static bool mfcc_args_ok(double sample_rate, uint32_t n_coeffs, double f_lo, double f_hi)
 {
-    return !(n_coeffs == 0 || n_coeffs > 64 || !(sample_rate > 0.0) || !(f_lo >= 0.0) || !(f_hi > f_lo));
+    return !(n_coeffs == 0 || n_coeffs > 64 || !(sample_rate > 0.0) || !(f_lo >= 0.0) || !(f_hi > f_lo) ||
+             !(f_lo < 0.5 * sample_rate));
 }
 
 #define SSYM_MFCC_TRY(expr)                    \
@@ -235,7 +238,7 @@ static int32_t mfcc_batch(ssym_ctx *ctx, const double *samples, const uint64_t *
     if (!ctx)
         return SSYM_E_INVALID;
     if (!mfcc_args_ok(rate, nc, f_lo, f_hi)) {
-        ctx->err = std::string(fn) + ": need 1 <= n_coeffs <= 64, sample_rate > 0, 0 <= f_lo < f_hi";
+        ctx->err = std::string(fn) + ": need 1 <= n_coeffs <= 64, sample_rate > 0, 0 <= f_lo < min(f_hi, sample_rate / 2)";
         return SSYM_E_INVALID;
     }
     if (n == 0)
@@ -346,7 +349,7 @@ int32_t ssym_mfcc(ssym_ctx *ctx, const double *samples, uint64_t n_samples, doub
     if (!ctx)
         return SSYM_E_INVALID;
     if (!mfcc_args_ok(sample_rate, n_coeffs, f_lo, f_hi)) {
-        ctx->err = "ssym_mfcc: need 1 <= n_coeffs <= 64, sample_rate > 0, 0 <= f_lo < f_hi";
+        ctx->err = "ssym_mfcc: need 1 <= n_coeffs <= 64, sample_rate > 0, 0 <= f_lo < min(f_hi, sample_rate / 2)";
         return SSYM_E_INVALID;
     }
     uint64_t T = 0;

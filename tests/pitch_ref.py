@@ -111,7 +111,7 @@ def windows(X, G, rate: float, f_min: float, f_max: float, voicing: float):
         has = np.any(cand, axis=1)
         strength = np.where(has, S[rows, k], 0.0)
         freq = np.where(has, rate / (taus[0, k] + delta[rows, k]), 0.0)
-        t = (L / G) / (SIGMA / (1.0 + voicing))
+        t = (L / G) / (SIGMA / np.float64(1.0 + voicing))      # v = -1: sigma / 0 = inf, as on the device
     u = voicing + np.fmax(0.0, 2.0 - t)                   # Rust's max: NaN (G = 0) gives u = voicing
     voiced = has & (strength >= u)
     score = np.where(voiced, strength, u)

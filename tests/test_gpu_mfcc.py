@@ -73,6 +73,8 @@ def test_mfcc_rejects_bad_arguments(eng):
         eng.mfcc(np.zeros(2048), 44100.0, 0)
     with pytest.raises(SsymError):
         eng.mfcc(np.zeros(2048), 44100.0, 12, f_lo=500.0, f_hi=100.0)
+    with pytest.raises(SsymError):                 # inverted band: no part of [f_lo, f_hi) below rate / 2
+        eng.mfcc(np.zeros(2048), 8000.0, 12, f_lo=5000.0, f_hi=8000.0)
 
 
 def test_mfcc_device_output_feeds_a_dictionary(eng, oracle):
