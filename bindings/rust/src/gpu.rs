@@ -13,6 +13,7 @@ use std::os::raw::{c_char, c_void};
 #[repr(C)] pub struct SsymComm { _p: [u8; 0] }
 #[repr(C)] pub struct SsymLocalGroup { _p: [u8; 0] }
 #[repr(C)] pub struct SsymGmm { _p: [u8; 0] }
+#[repr(C)] pub struct SsymStream { _p: [u8; 0] }
 
 pub const SSYM_ABI_VERSION: i32 = 3;
 
@@ -192,6 +193,25 @@ extern "C" {
     pub fn ssym_pitch_track(ctx: *mut SsymCtx, samples: *const f64, sample_offsets: *const u64, n_sounds: u32,
                             rate: f64, f_min: f64, f_max: f64, voicing: f64, flags: u32, out_freq: *mut f64,
                             out_strength: *mut f64, out_unvoiced: *mut f64) -> i32;
+
+    // streaming sounds: Sound::push_samples (src/sound.rs:145-164) with samples and analysis resident on the device
+    pub fn ssym_stream_create(ctx: *mut SsymCtx, n_lanes: u32, sample_rate: f64, n_coeffs: u32, f_lo: f64, f_hi: f64,
+                              capacity_hint_samples: u64, out: *mut *mut SsymStream) -> i32;
+    pub fn ssym_stream_destroy(ctx: *mut SsymCtx, st: *mut SsymStream) -> i32;
+    pub fn ssym_stream_push(ctx: *mut SsymCtx, st: *mut SsymStream, samples: *const f64, sample_offsets: *const u64,
+                            flags: u32, out_new_frames: *mut u64, out_mfccs: *mut f64) -> i32;
+    pub fn ssym_stream_seed(ctx: *mut SsymCtx, st: *mut SsymStream, lane: u32, samples: *const f64, n_samples: u64,
+                            mfccs: *const f64, n_frames: u64) -> i32;
+    pub fn ssym_stream_counts(st: *const SsymStream, out_n_samples: *mut u64, out_n_frames: *mut u64) -> i32;
+    pub fn ssym_stream_read(ctx: *mut SsymCtx, st: *mut SsymStream, lane: u32, first_frame: u64, n_frames: u64,
+                            flags: u32, out_mfccs: *mut f64) -> i32;
+    pub fn ssym_stream_frames_device(st: *const SsymStream, lane: u32, out_ptr: *mut *const f64,
+                                     out_n_frames: *mut u64) -> i32;
+    pub fn ssym_stream_samples_device(st: *const SsymStream, lane: u32, out_ptr: *mut *const f64,
+                                      out_n_samples: *mut u64) -> i32;
+    pub fn ssym_stream_descriptors(ctx: *mut SsymCtx, st: *mut SsymStream, out_max_power: *mut f64,
+                                   out_mean: *mut f64) -> i32;
+    pub fn ssym_stream_reset(ctx: *mut SsymCtx, st: *mut SsymStream, lane: u32) -> i32;
 }
 
 /// `Err(message)` for any status but SSYM_OK; SSYM_E_EMPTY_DICT keeps the crate's behaviour (a panic, :369).

@@ -57,6 +57,7 @@ typedef struct ssym_queries ssym_queries; /* the targets of one batch (SoundSequ
 typedef struct ssym_samples ssym_samples; /* the dictionary sounds' SAMPLES, resident on the GPU   */
 typedef struct ssym_comm ssym_comm;       /* one rank of a source-sharded run: an RCCL communicator  */
 typedef struct ssym_gmm ssym_gmm;         /* a trained Gaussian mixture (the partitioner's model)    */
+typedef struct ssym_stream ssym_stream;   /* growing sounds: samples + analysis resident on the GPU  */
 
 enum {
     SSYM_OK = 0,
@@ -525,6 +526,57 @@ SSYM_API int32_t ssym_sound_descriptors(ssym_ctx *ctx, const double *samples, co
 SSYM_API int32_t ssym_pitch_track(ssym_ctx *ctx, const double *samples, const uint64_t *sample_offsets,
                          uint32_t n_sounds, double rate, double f_min, double f_max, double voicing, uint32_t flags,
                          double *out_freq, double *out_strength, double *out_unvoiced);
+
+/* Streaming sounds: Sound::push_samples (src/sound.rs:145-164) with the samples, the MFCC
+ * frames, the running max_power and the running per-coefficient sums resident on the device.  A stream holds n_lanes
+ * independent sounds ("lanes") of one sample_rate / n_coeffs / f_lo / f_hi; the MFCC tables are built and uploaded
+ * once, at creation.  A push uploads only the new samples and analyses only the frames and power windows they
+ * complete.  After any sequence of pushes a lane holds, bit for bit, what ssym_mfcc (full windows, no
+ * SSYM_MFCC_PAD_TAIL), ssym_mfcc_batch (out_mean) and ssym_sound_descriptors (out_max_power) return for the
+ * concatenated samples.  The mean is the true mean of the frames held (the reference's running-mean update, :156-158,
+ * is not one and is not copied); pitch confidence is not part of a stream.
+ * Limits: n_lanes >= 1, a finite sample_rate, otherwise those of ssym_mfcc.  Every failure of the arguments returns
+ * SSYM_E_INVALID with a message before device memory is touched; a failed call leaves the stream as it was.  A stream
+ * belongs to the context that created it, and every call that takes both wants that context.
+ *   capacity_hint_samples  room reserved per lane (0: none); a lane's capacity doubles when it runs out, the old
+ *                          samples and frames are copied on the device and never uploaded again */
+SSYM_API int32_t ssym_stream_create(ssym_ctx *ctx, uint32_t n_lanes, double sample_rate, uint32_t n_coeffs, double f_lo,
+                                    double f_hi, uint64_t capacity_hint_samples, ssym_stream **out);
+SSYM_API int32_t ssym_stream_destroy(ssym_ctx *ctx, ssym_stream *st);
+/* append samples[sample_offsets[l] .. sample_offsets[l+1]) to lane l, for every lane, and analyse what that completes.
+ *   sample_offsets  n_lanes + 1 (HOST), non-decreasing; empty chunks are allowed
+ *   flags           SSYM_OUT_DEVICE: out_mfccs is device memory
+ *   out_new_frames  nullable, n_lanes u64 (HOST): frames this push added per lane
+ *   out_mfccs       nullable: the new frames, lane after lane, sum(out_new_frames) * n_coeffs f64 -- size it with
+ *                   ssym_stream_counts and ssym_mfcc_num_frames before the call
+ * One synchronisation per call. */
+SSYM_API int32_t ssym_stream_push(ssym_ctx *ctx, ssym_stream *st, const double *samples, const uint64_t *sample_offsets,
+                                  uint32_t flags, uint64_t *out_new_frames, double *out_mfccs);
+/* fill an EMPTY lane with a sound that exists already.  mfccs (nullable, n_frames * n_coeffs f64, HOST): the sound's
+ * frames, adopted as given (not analysed again, as :146-148 trusts them); n_frames must not exceed
+ * ssym_mfcc_num_frames(n_samples, 0), and frames the samples allow beyond n_frames are analysed by the next push.
+ * Without mfccs every frame is analysed now and n_frames is ignored.  Power and sums are computed on the device either
+ * way. */
+SSYM_API int32_t ssym_stream_seed(ssym_ctx *ctx, ssym_stream *st, uint32_t lane, const double *samples,
+                                  uint64_t n_samples, const double *mfccs, uint64_t n_frames);
+/* samples and frames held per lane: both nullable, n_lanes u64 each (HOST).  Host arithmetic, no device work. */
+SSYM_API int32_t ssym_stream_counts(const ssym_stream *st, uint64_t *out_n_samples, uint64_t *out_n_frames);
+/* frames [first_frame, first_frame + n_frames) of a lane: n_frames * n_coeffs f64 (HOST, or device memory with
+ * SSYM_OUT_DEVICE) */
+SSYM_API int32_t ssym_stream_read(ssym_ctx *ctx, ssym_stream *st, uint32_t lane, uint64_t first_frame, uint64_t n_frames,
+                                  uint32_t flags, double *out_mfccs);
+/* the resident buffers of a lane (DEVICE pointers, f64; NULL while the lane holds nothing), valid until the next push,
+ * seed or destroy of this stream: they feed ssym_partition, ssym_gmm_predict, ssym_sequence_distances (SSYM_OUT_DEVICE)
+ * and ssym_queries_create_device / ssym_dict_create_device without a copy */
+SSYM_API int32_t ssym_stream_frames_device(const ssym_stream *st, uint32_t lane, const double **out_ptr,
+                                           uint64_t *out_n_frames);
+SSYM_API int32_t ssym_stream_samples_device(const ssym_stream *st, uint32_t lane, const double **out_ptr,
+                                            uint64_t *out_n_samples);
+/* out_max_power: nullable, n_lanes f64 (HOST), 0 below 128 samples; out_mean: nullable, n_lanes * n_coeffs f64 (HOST),
+ * NaN for a lane without frames, as ssym_mfcc_batch writes it */
+SSYM_API int32_t ssym_stream_descriptors(ssym_ctx *ctx, ssym_stream *st, double *out_max_power, double *out_mean);
+/* empty one lane; its capacity stays */
+SSYM_API int32_t ssym_stream_reset(ssym_ctx *ctx, ssym_stream *st, uint32_t lane);
 
 #ifdef __cplusplus
 }

@@ -11,7 +11,7 @@ from ._native import (  # noqa: F401
     SsymError,
     build,
 )
-from .engine import Engine, Gmm, pack_segments  # noqa: F401
+from .engine import DeviceFrames, Engine, Gmm, Stream, pack_segments, stream_plan  # noqa: F401
 from .api import (  # noqa: F401
     BIN,
     HOP,
@@ -27,12 +27,13 @@ from .api import (  # noqa: F401
     discretize,
     discretize_with_model,
     length_fit,
+    push_sounds,
     train_model,
 )
 
 __all__ = [
-    "ABI_SYMBOLS", "BIN", "EmptyDictionaryError", "Engine", "Gmm", "HOP", "LIB_PATH", "NCLUSTERS", "NCOEFFS",
+    "ABI_SYMBOLS", "BIN", "DeviceFrames", "EmptyDictionaryError", "Engine", "Gmm", "HOP", "LIB_PATH", "NCLUSTERS", "NCOEFFS",
     "Partitioner", "Sound", "SoundDictionary", "SoundSequence", "SsymError", "analyze_mfccs", "analyze_sounds", "build",
     "cosine_sim_angular", "discretize",
-    "discretize_with_model", "length_fit", "pack_segments", "train_model",
+    "discretize_with_model", "length_fit", "pack_segments", "push_sounds", "Stream", "stream_plan", "train_model",
 ]

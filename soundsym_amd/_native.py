@@ -51,6 +51,9 @@ ABI_SYMBOLS = [
     "ssym_standardize", "ssym_gmm_train", "ssym_gmm_get", "ssym_gmm_destroy", "ssym_gmm_predict", "ssym_vote_segments",
     "ssym_partition", "ssym_pitch_num_windows", "ssym_sound_descriptors", "ssym_pitch_track",
     "ssym_mfcc_batch", "ssym_sequence_distances",
+    "ssym_stream_create", "ssym_stream_destroy", "ssym_stream_push", "ssym_stream_seed", "ssym_stream_counts",
+    "ssym_stream_read", "ssym_stream_frames_device", "ssym_stream_samples_device", "ssym_stream_descriptors",
+    "ssym_stream_reset",
 ]
 COMM_ID_BYTES = 128        # SSYM_COMM_ID_BYTES
 
@@ -61,6 +64,8 @@ TOPK_MAX = 64              # SSYM_TOPK_MAX
 GMM_STANDARDIZE = 8        # SSYM_GMM_STANDARDIZE
 PITCH_VOICED = 16          # SSYM_PITCH_VOICED
 PITCH_WINDOW, PITCH_HOP = 2048, 1024    # SSYM_PITCH_WINDOW, SSYM_PITCH_HOP
+MFCC_BIN, MFCC_HOP = 1024, 256          # SSYM_MFCC_BIN, SSYM_MFCC_HOP
+POWER_WINDOW, POWER_HOP = 128, 64       # SSYM_POWER_WINDOW, SSYM_POWER_HOP
 
 
 class SsymError(RuntimeError):
@@ -292,6 +297,26 @@ def lib() -> ctypes.CDLL:
     L.ssym_mfcc_batch.argtypes = [vp, vp, vp, u32, f64, u32, f64, f64, u32, vp, vp, vp]
     L.ssym_sequence_distances.restype = i32
     L.ssym_sequence_distances.argtypes = [vp, vp, vp, u32, u32, u32, vp, vp, vp]
+    L.ssym_stream_create.restype = i32
+    L.ssym_stream_create.argtypes = [vp, u32, f64, u32, f64, f64, u64, pvp]
+    L.ssym_stream_destroy.restype = i32
+    L.ssym_stream_destroy.argtypes = [vp, vp]
+    L.ssym_stream_push.restype = i32
+    L.ssym_stream_push.argtypes = [vp, vp, vp, vp, u32, vp, vp]
+    L.ssym_stream_seed.restype = i32
+    L.ssym_stream_seed.argtypes = [vp, vp, u32, vp, u64, vp, u64]
+    L.ssym_stream_counts.restype = i32
+    L.ssym_stream_counts.argtypes = [vp, vp, vp]
+    L.ssym_stream_read.restype = i32
+    L.ssym_stream_read.argtypes = [vp, vp, u32, u64, u64, u32, vp]
+    L.ssym_stream_frames_device.restype = i32
+    L.ssym_stream_frames_device.argtypes = [vp, u32, pvp, ctypes.POINTER(u64)]
+    L.ssym_stream_samples_device.restype = i32
+    L.ssym_stream_samples_device.argtypes = [vp, u32, pvp, ctypes.POINTER(u64)]
+    L.ssym_stream_descriptors.restype = i32
+    L.ssym_stream_descriptors.argtypes = [vp, vp, vp, vp]
+    L.ssym_stream_reset.restype = i32
+    L.ssym_stream_reset.argtypes = [vp, vp, u32]
     _lib = L
     return L
 

@@ -12,6 +12,7 @@ Same names, argument meaning and error behaviour as the reference for the hot pa
     Partitioner (new / from_path / depth / threshold / train / partition / partition_other)   src/lib.rs:67-151
     Sound.pitch_confidence / preload_pitch_confidence, analyze_sounds       src/sound.rs:170-179, 244-269
     SoundSequence.distances, cosine_sim_angular, analyze_mfccs (batched)    src/sound.rs:392-398, 436, 59-69, 215-242
+    Sound.push_samples / mfcc_arrays, push_sounds (one push for many sounds) src/sound.rs:145-164, 196-203
 
 Every comparison runs on the GPU through the C ABI (`engine.Engine`); this module only keeps the
 containers, does the length fit of src/sound.rs:456-465 on the matched samples, and translates
@@ -142,6 +143,8 @@ class Sound:
         self.ncoeffs = int(ncoeffs)
         self._mfccs = None
         self._pitch_confidence = None
+        self._stream = None                   # (Stream, lane) once push_samples / push_sounds has made it resident
+        self._blocks = [None, None]           # ... and the growing host stores of its samples and features
         if mfccs is not None:
             m = np.ascontiguousarray(mfccs, dtype=np.float64).reshape(-1)
             if m.size % self.ncoeffs:
@@ -217,6 +220,24 @@ class Sound:
     def num_frames(self) -> int:              # src/sound.rs:210
         return self.mfccs().size // self.ncoeffs
 
+    def mfcc_arrays(self) -> np.ndarray:      # src/sound.rs:196-203
+        """The features as [frames][ncoeffs] (a view of mfccs(): the reference's chunks of NCOEFFS)."""
+        return self.mfccs().reshape(-1, self.ncoeffs)
+
+    def push_samples(self, new_samples, engine: Optional[Engine] = None) -> None:
+        """Sound::push_samples (src/sound.rs:145-164): append samples and analyse what they complete.  The first call
+        makes the sound resident on the GPU (a one-lane ssym_stream seeded with the samples and the features, which
+        are trusted as given, :146-148; frames the samples allow beyond them are analysed with the push); every later
+        call uploads only the new samples.  Afterwards samples(), mfccs(), num_frames(),
+        max_power() and mean_mfccs() are those of the longer sound -- bit for bit the sound analysed whole.  A preloaded
+        pitch confidence stays as it was (:170-179)."""
+        push_sounds([self], [new_samples], engine)
+
+    def stream(self):
+        """(Stream, lane) holding this sound on the GPU after a push, else None: its frames_device() feeds the
+        partitioner and the matcher without a copy."""
+        return self._stream
+
 
 def analyze_sounds(sounds: Sequence[Sound], engine: Optional[Engine] = None, rate: float = PITCH_RATE,
                    f_min: float = PITCH_F_MIN, f_max: float = PITCH_F_MAX, voicing: float = PITCH_VOICING,
@@ -235,6 +256,63 @@ def analyze_sounds(sounds: Sequence[Sound], engine: Optional[Engine] = None, rat
     offsets = np.concatenate([[0], np.cumsum([p.size for p in parts])]).astype(np.uint64)
     e = engine or default_engine()
     return e.sound_descriptors(np.concatenate(parts), offsets, rate, f_min, f_max, voicing, voiced_only)
+
+
+def _appended(block, old: np.ndarray, new: np.ndarray):
+    """(block, old followed by new as a view of it): `block` is the Sound's own growing store (None before the first
+    push) and doubles when it runs out, a Vec's amortised push; the caller's arrays are never written to."""
+    n = old.size + new.size
+    if block is None or block.size < n:
+        block = np.empty(max(n, 2 * old.size), dtype=np.float64)
+        block[:old.size] = old
+    block[old.size:n] = new
+    return block, block[:n]
+
+
+def push_sounds(sounds: Sequence[Sound], chunks, engine: Optional[Engine] = None) -> None:
+    """Sound.push_samples for many sounds in ONE device call (a multi-lane ssym_stream_push): chunks[i] is appended to
+    sounds[i]; empty chunks are allowed.  The sounds must carry features and share a sample rate and ncoeffs
+    (ValueError otherwise, before any device work).  Sounds that were pushed together before keep their shared
+    stream; any other grouping opens a new one and seeds every lane once with the sound's samples and features."""
+    sounds = list(sounds)
+    parts = [np.ascontiguousarray(c, dtype=np.float64).reshape(-1) for c in chunks]
+    if len(parts) != len(sounds):
+        raise ValueError("push_sounds: one chunk per sound")
+    if not sounds:
+        return
+    if len({id(s) for s in sounds}) != len(sounds):
+        raise ValueError("push_sounds: a sound appears twice")
+    for s in sounds:
+        m = s.mfccs()                         # raises the ValueError of mfccs() for a sound without features
+        if m.size // s.ncoeffs > Engine.mfcc_num_frames(s.samples().size):
+            raise ValueError("push_samples: the sound carries more frames than its samples allow")
+    if len({s.sample_rate() for s in sounds}) != 1 or len({s.ncoeffs for s in sounds}) != 1:
+        raise ValueError("push_sounds: the sounds must share a sample rate and ncoeffs")
+    first = sounds[0]._stream
+    shared = first is not None and first[0].ptr and first[0].n_lanes == len(sounds) and \
+        (engine is None or first[0].engine is engine) and \
+        all(s._stream is not None and s._stream[0] is first[0] and s._stream[1] == i for i, s in enumerate(sounds))
+    if shared:
+        st = first[0]
+    else:
+        e = engine or default_engine()
+        st = e.stream(len(sounds), sounds[0].sample_rate(), sounds[0].ncoeffs,
+                      capacity=2 * max(s.samples().size + p.size for s, p in zip(sounds, parts)))
+        for i, s in enumerate(sounds):
+            st.seed(i, s.samples(), s.mfccs())
+        for i, s in enumerate(sounds):
+            if s._stream is not None and len({id(o) for o in sounds if o._stream and o._stream[0] is s._stream[0]}) \
+                    == s._stream[0].n_lanes:
+                s._stream[0].close()          # every sound of the old stream has moved here
+            s._stream = (st, i)
+    offsets = np.concatenate([[0], np.cumsum([p.size for p in parts])]).astype(np.uint64)
+    new, frames = st.push(np.concatenate(parts), offsets, want_frames=True)
+    flat, at = frames.reshape(-1), 0
+    for s, p, k in zip(sounds, parts, new):
+        k = int(k) * s.ncoeffs
+        s._blocks[0], s._samples = _appended(s._blocks[0], s._samples, p)
+        s._blocks[1], s._mfccs = _appended(s._blocks[1], s._mfccs, flat[at:at + k])
+        at += k
 
 
 class SoundDictionary:

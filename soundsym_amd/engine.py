@@ -89,6 +89,149 @@ class Gmm:
             pass
 
 
+class DeviceFrames:
+    """A view of f64 values in device memory owned by somebody else (a Stream's resident frames or samples): the raw
+    pointer and its shape.  It stands in for a contiguous float64 device tensor wherever the engine takes one
+    (queries / dictionary, sequence_distances, gmm_predict, partition).  `owner` is kept alive; the view itself is
+    valid only as long as the owner says (a Stream: until the next push, seed or close)."""
+
+    is_cuda = True
+    dtype = "torch.float64"
+
+    def __init__(self, ptr: int, rows: int, dim: int, owner=None):
+        self.ptr, self.shape, self.owner = int(ptr or 0), (int(rows), int(dim)), owner
+
+    def data_ptr(self) -> int:
+        return self.ptr
+
+    def numel(self) -> int:
+        return self.shape[0] * self.shape[1]
+
+    def is_contiguous(self) -> bool:
+        return True
+
+
+def stream_plan(n_old: int, n_add: int):
+    """What a push of `n_add` samples onto a sound of `n_old` analyses (host arithmetic only):
+    (first new frame, new frames, first new power window, new power windows) for full 1024 / 256 MFCC windows and full
+    128 / 64 power windows.  The old frames and windows plus the new ones are exactly those of the sound of
+    n_old + n_add samples."""
+    n_old, n_add = int(n_old), int(n_add)
+    if n_old < 0 or n_add < 0:
+        raise ValueError("stream_plan: sample counts must not be negative")
+
+    def count(n, size, hop):
+        return (n - size) // hop + 1 if n >= size else 0
+    f0, f1 = count(n_old, nat.MFCC_BIN, nat.MFCC_HOP), count(n_old + n_add, nat.MFCC_BIN, nat.MFCC_HOP)
+    w0, w1 = count(n_old, nat.POWER_WINDOW, nat.POWER_HOP), count(n_old + n_add, nat.POWER_WINDOW, nat.POWER_HOP)
+    return f0, f1 - f0, w0, w1 - w0
+
+
+class Stream:
+    """Growing sounds on the engine's GPU (ssym_stream): `n_lanes` independent sounds whose samples,
+    MFCC frames, max_power and per-coefficient sums stay resident; a push uploads and analyses only what is new."""
+
+    def __init__(self, engine: "Engine", ptr: int, n_lanes: int, ncoeffs: int, sample_rate: float):
+        self.engine, self.ptr, self.n_lanes, self.ncoeffs, self.sample_rate = engine, ptr, n_lanes, ncoeffs, sample_rate
+
+    def _lane(self, lane: int) -> int:
+        if not 0 <= int(lane) < self.n_lanes:
+            raise ValueError(f"lane {lane} outside 0..{self.n_lanes - 1}")
+        return int(lane)
+
+    def counts(self) -> Tuple[np.ndarray, np.ndarray]:
+        """(samples [n_lanes], frames [n_lanes]) held now (u64)."""
+        ns, nf = np.zeros(self.n_lanes, dtype=np.uint64), np.zeros(self.n_lanes, dtype=np.uint64)
+        nat.check(nat.lib().ssym_stream_counts(self.ptr, ns.ctypes.data, nf.ctypes.data), self.engine.ctx)
+        return ns, nf
+
+    def push(self, samples, sample_offsets=None, want_frames: bool = False):
+        """ssym_stream_push: lane l gets samples[sample_offsets[l]:sample_offsets[l+1]] (a one-lane stream takes the
+        bare chunk).  Returns the new frames per lane [n_lanes] u64, and with want_frames also the new frames
+        themselves, lane after lane, [sum][ncoeffs]."""
+        x = np.ascontiguousarray(samples, dtype=np.float64).reshape(-1)
+        if sample_offsets is None:
+            if self.n_lanes != 1:
+                raise ValueError("push: a stream of several lanes needs sample_offsets")
+            sample_offsets = [0, x.size]
+        off = np.ascontiguousarray(sample_offsets, dtype=np.uint64).reshape(-1)
+        if off.size != self.n_lanes + 1 or np.any(np.diff(off.astype(np.int64)) < 0) or int(off[-1]) > x.size:
+            raise ValueError("sample_offsets: n_lanes + 1 non-decreasing sample offsets within `samples`")
+        new = np.zeros(self.n_lanes, dtype=np.uint64)
+        out = None
+        if want_frames:
+            ns, nf = self.counts()
+            total = 0
+            for l in range(self.n_lanes):
+                f_all = stream_plan(int(ns[l]), int(off[l + 1] - off[l]))
+                total += max(f_all[0] + f_all[1] - int(nf[l]), 0)      # (a seeded lane may lag behind its samples)
+            out = np.zeros((total, self.ncoeffs), dtype=np.float64)
+        nat.check(nat.lib().ssym_stream_push(self.engine.ctx, self.ptr, x.ctypes.data if x.size else None,
+                                             off.ctypes.data, 0, new.ctypes.data,
+                                             out.ctypes.data if out is not None and out.size else None),
+                  self.engine.ctx)
+        return (new, out) if want_frames else new
+
+    def seed(self, lane: int, samples, mfccs=None) -> None:
+        """ssym_stream_seed: fill an empty lane with an existing sound; `mfccs` (whole frames) are adopted as given,
+        frames the samples allow beyond them are analysed by the next push; without them every frame is analysed."""
+        x = np.ascontiguousarray(samples, dtype=np.float64).reshape(-1)
+        m = None if mfccs is None else np.ascontiguousarray(mfccs, dtype=np.float64).reshape(-1)
+        if m is not None and m.size % self.ncoeffs:
+            raise ValueError("mfccs must hold whole frames of `ncoeffs` values")
+        frames = 0 if m is None else m.size // self.ncoeffs
+        # (with mfccs a non-NULL pointer is passed even for 0 frames: NULL means "analyse")
+        mp = None if m is None else (m.ctypes.data if m.size else np.zeros(1).ctypes.data)
+        nat.check(nat.lib().ssym_stream_seed(self.engine.ctx, self.ptr, self._lane(lane),
+                                             x.ctypes.data if x.size else None, x.size, mp, frames), self.engine.ctx)
+
+    def read(self, lane: int = 0, first_frame: int = 0, n_frames: Optional[int] = None) -> np.ndarray:
+        """ssym_stream_read: frames [first_frame, first_frame + n_frames) of a lane (default: to its end)."""
+        lane = self._lane(lane)
+        if n_frames is None:
+            n_frames = max(int(self.counts()[1][lane]) - int(first_frame), 0)
+        out = np.zeros((int(n_frames), self.ncoeffs), dtype=np.float64)
+        nat.check(nat.lib().ssym_stream_read(self.engine.ctx, self.ptr, lane, int(first_frame), int(n_frames), 0,
+                                             out.ctypes.data if out.size else None), self.engine.ctx)
+        return out
+
+    def frames_device(self, lane: int = 0) -> DeviceFrames:
+        """The lane's resident frames [frames][ncoeffs] as a device view, valid until the next push / seed / close."""
+        p, n = ctypes.c_void_p(), ctypes.c_uint64()
+        nat.check(nat.lib().ssym_stream_frames_device(self.ptr, self._lane(lane), ctypes.byref(p), ctypes.byref(n)),
+                  self.engine.ctx)
+        return DeviceFrames(p.value, n.value, self.ncoeffs, self)
+
+    def samples_device(self, lane: int = 0) -> DeviceFrames:
+        """The lane's resident samples [samples][1] as a device view, valid until the next push / seed / close."""
+        p, n = ctypes.c_void_p(), ctypes.c_uint64()
+        nat.check(nat.lib().ssym_stream_samples_device(self.ptr, self._lane(lane), ctypes.byref(p), ctypes.byref(n)),
+                  self.engine.ctx)
+        return DeviceFrames(p.value, n.value, 1, self)
+
+    def descriptors(self) -> Tuple[np.ndarray, np.ndarray]:
+        """(max_power [n_lanes], mean MFCCs [n_lanes][ncoeffs]; NaN for a lane without frames)."""
+        mp, mean = np.zeros(self.n_lanes), np.zeros((self.n_lanes, self.ncoeffs))
+        nat.check(nat.lib().ssym_stream_descriptors(self.engine.ctx, self.ptr, mp.ctypes.data, mean.ctypes.data),
+                  self.engine.ctx)
+        return mp, mean
+
+    def reset(self, lane: int = 0) -> None:
+        """Empty one lane; its capacity stays."""
+        nat.check(nat.lib().ssym_stream_reset(self.engine.ctx, self.ptr, self._lane(lane)), self.engine.ctx)
+
+    def close(self):
+        if self.ptr and self.engine.ctx:
+            nat.lib().ssym_stream_destroy(self.engine.ctx, self.ptr)
+        self.ptr = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class Comm:
     """One rank of a source-sharded run: an RCCL communicator bound to an Engine (ssym_comm)."""
 
@@ -453,6 +596,14 @@ class Engine:
                   self.ctx)
         return (feats, fo, mean) if want_mean else (feats, fo)
 
+    def stream(self, n_lanes: int, sample_rate: float, ncoeffs: int = 12, f_lo: float = 100.0, f_hi: float = 8000.0,
+               capacity: int = 0) -> Stream:
+        """ssym_stream_create: `n_lanes` growing sounds with resident analysis; `capacity`: samples reserved per lane."""
+        out = ctypes.c_void_p()
+        nat.check(nat.lib().ssym_stream_create(self.ctx, int(n_lanes), float(sample_rate), int(ncoeffs), float(f_lo),
+                                               float(f_hi), int(capacity), ctypes.byref(out)), self.ctx)
+        return Stream(self, out.value, int(n_lanes), int(ncoeffs), float(sample_rate))
+
     @staticmethod
     def mfcc_num_frames(n_samples: int, pad_tail: bool = False) -> int:
         """ssym_mfcc_num_frames (host arithmetic, no device)."""
@@ -513,7 +664,10 @@ class Engine:
         return Gmm(self, out.value, rows.size, dim)
 
     def gmm_predict(self, gmm: "Gmm", feats, standardize: bool = True, want_post: bool = False):
-        """ssym_gmm_predict: letters [frames] u8 (and the posteriors [frames][K] when asked)."""
+        """ssym_gmm_predict: letters [frames] u8 (and the posteriors [frames][K] when asked).  feats: a host array, or
+        f64 frames in device memory (a DeviceFrames view or a contiguous device tensor)."""
+        if _is_device_tensor(feats):
+            return self._gmm_predict_device(gmm, feats, standardize, want_post)
         x = np.ascontiguousarray(feats, dtype=np.float64).reshape(-1)
         n = x.size // gmm.dim
         let = np.zeros(n, dtype=np.uint8)
@@ -539,15 +693,44 @@ class Engine:
         return (out, votes) if want_votes else out
 
     def partition(self, gmm: "Gmm", feats, depth: int = 5, threshold: int = 4, standardize: bool = True) -> np.ndarray:
-        """ssym_partition: predict + vote in one call; segment lengths in frames."""
-        x = np.ascontiguousarray(feats, dtype=np.float64).reshape(-1)
-        n = x.size // gmm.dim
+        """ssym_partition: predict + vote in one call; segment lengths in frames.  feats: a host array, or f64 frames
+        in device memory (a DeviceFrames view or a contiguous device tensor), read in place."""
+        flags = nat.GMM_STANDARDIZE if standardize else 0
+        if _is_device_tensor(feats):
+            n, ptr = self._device_frames(feats, gmm.dim)
+            flags |= nat.OUT_DEVICE
+        else:
+            x = np.ascontiguousarray(feats, dtype=np.float64).reshape(-1)
+            n = x.size // gmm.dim
+            ptr = x.ctypes.data if n else None
         seg = np.zeros(max(n, 1), dtype=np.uint64)
         m = ctypes.c_uint64()
-        flags = nat.GMM_STANDARDIZE if standardize else 0
-        nat.check(nat.lib().ssym_partition(self.ctx, gmm.ptr, x.ctypes.data if n else None, n, depth, threshold,
+        nat.check(nat.lib().ssym_partition(self.ctx, gmm.ptr, ptr, n, depth, threshold,
                                            flags, seg.ctypes.data, ctypes.byref(m)), self.ctx)
         return seg[:m.value].astype(np.int64)
+
+    @staticmethod
+    def _device_frames(feats, dim: int):
+        if str(feats.dtype) != "torch.float64" or not feats.is_contiguous() or feats.numel() % dim:
+            raise ValueError(f"device features must be contiguous torch.float64 frames of {dim} values")
+        n = feats.numel() // dim
+        return n, (feats.data_ptr() if n else None)
+
+    def _gmm_predict_device(self, gmm: "Gmm", feats, standardize: bool, want_post: bool):
+        """gmm_predict on frames in device memory: with SSYM_OUT_DEVICE the call's outputs are device memory too, so
+        they land in torch tensors (torch only owns the memory) and come back as host arrays."""
+        import torch
+        n, ptr = self._device_frames(feats, gmm.dim)
+        dev = torch.device("cuda", self.device)
+        let = torch.empty(max(n, 1), dtype=torch.uint8, device=dev)
+        post = torch.empty(max(n, 1) * gmm.k, dtype=torch.float64, device=dev) if want_post else None
+        flags = nat.OUT_DEVICE | (nat.GMM_STANDARDIZE if standardize else 0)
+        nat.check(nat.lib().ssym_gmm_predict(self.ctx, gmm.ptr, ptr, n, flags,
+                                             post.data_ptr() if want_post and n else None,
+                                             let.data_ptr() if n else None), self.ctx)
+        self.synchronize()
+        letters = let[:n].cpu().numpy()
+        return (letters, post[:n * gmm.k].cpu().numpy().reshape(n, gmm.k)) if want_post else letters
 
     # sound descriptors (DESIGN.md 5.9; the pitch side is an own definition, parity unpinned) -------------------------
     def _descriptor_inputs(self, samples, offsets, rate, f_min, f_max, voicing):
