@@ -115,6 +115,13 @@ extern "C" {
                       distances: *const f64, n_steps: u32, out_idx: *mut u32, out_cost: *mut f64) -> i32;
     pub fn ssym_pair_matrix(ctx: *mut SsymCtx, dict: *const SsymDict, q: *const SsymQueries, exact: i32,
                             out_matrix: *mut f64) -> i32;
+    // DTW alignment of listed pairs (dtw contexts): warping paths, costs, target-frame -> source-frame maps
+    pub fn ssym_dtw_align_sizes(dict: *const SsymDict, q: *const SsymQueries, src_idx: *const u32, tgt_idx: *const u32,
+                                n_pairs: u32, index_base: u32, path_offsets: *mut u64, map_offsets: *mut u64) -> i32;
+    pub fn ssym_dtw_align(ctx: *mut SsymCtx, dict: *const SsymDict, q: *const SsymQueries, src_idx: *const u32,
+                          tgt_idx: *const u32, n_pairs: u32, index_base: u32, out_cost: *mut f64, out_len: *mut u32,
+                          path_offsets: *const u64, out_path: *mut u32, map_offsets: *const u64, out_map: *mut u32,
+                          flags: u32) -> i32;
 
     // source-sharded runs, exchange done by the caller (device pointers): filter / all-reduce(MIN) / finish / merge
     pub fn ssym_match_begin(ctx: *mut SsymCtx, dict: *const SsymDict, q: *const SsymQueries, distance: *const f64,

@@ -26,6 +26,7 @@
 #include <stdexcept>
 #include <string>
 #include <utility>
+#include <array>
 #include <vector>
 
 #include "soundsym_amd.h"
@@ -238,6 +239,50 @@ class SoundDictionary {
             for (uint32_t r = 0; r < k; ++r)
                 if (idx[t * k + r] != SSYM_NO_MATCH)
                     out[t].push_back(sounds[idx[t * k + r]]);
+        return out;
+    }
+    // the warping path of every target onto dictionary sound indices[t] (ssym_dtw_align; dtw contexts; the crate has
+    // no counterpart).  path: (source frame, target frame) cells in forward order; frame_map: the smallest source
+    // frame aligned with every target frame; both empty for a pair without a finite cost
+    struct Alignment {
+        double cost;
+        std::vector<std::array<uint32_t, 2>> path;
+        std::vector<uint32_t> frame_map;
+        uint32_t source_index;
+    };
+    std::vector<Alignment> align(const std::vector<ArcSound> &targets, const std::vector<uint32_t> &indices) const
+    {
+        if (sounds.empty())
+            throw EmptyDictionary();
+        const uint32_t n = (uint32_t)targets.size();
+        std::vector<double> flat;
+        std::vector<uint64_t> off;
+        pack_features(targets, flat, off);
+        ssym_queries *q = nullptr;
+        ctx_->check(ssym_queries_create(ctx_->get(), flat.data(), off.data(), n, (uint32_t)NCOEFFS, &q));
+        std::vector<uint64_t> poff(n + 1), moff(n + 1);
+        std::vector<double> cost(n);
+        std::vector<uint32_t> len(n), path, map;
+        int32_t rc = indices.size() == n ? ssym_dtw_align_sizes(resident(), q, indices.data(), nullptr, n, 0, poff.data(),
+                                                                moff.data())
+                                         : (int32_t)SSYM_E_INVALID;
+        if (rc == SSYM_OK) {
+            path.resize(2 * poff[n]);
+            map.resize(moff[n]);
+            rc = ssym_dtw_align(ctx_->get(), resident(), q, indices.data(), nullptr, n, 0, cost.data(), len.data(),
+                                poff.data(), path.data(), moff.data(), map.data(), 0);
+        }
+        ssym_queries_destroy(ctx_->get(), q);
+        ctx_->check(rc);
+        std::vector<Alignment> out(n);
+        for (uint32_t t = 0; t < n; ++t) {
+            out[t].cost = cost[t];
+            out[t].source_index = indices[t];
+            for (uint32_t s = 0; s < len[t]; ++s)
+                out[t].path.push_back({path[2 * (poff[t] + s)], path[2 * (poff[t] + s) + 1]});
+            if (len[t])
+                out[t].frame_map.assign(map.begin() + moff[t], map.begin() + moff[t + 1]);
+        }
         return out;
     }
     // from_distances' chain of at_distance calls, on the device in one call (ssym_chain)

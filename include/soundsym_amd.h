@@ -237,6 +237,38 @@ SSYM_API int32_t ssym_chain(ssym_ctx *ctx, ssym_dict *dict, const void *start_fe
 SSYM_API int32_t ssym_pair_matrix(ssym_ctx *ctx, const ssym_dict *dict, const ssym_queries *q,
                          int32_t exact, double *out_matrix);
 
+/* DTW alignment (dtw contexts only; DESIGN.md section 2 "Alignment" and section 5.12): for a list of (source, target)
+ * pairs the optimal warping path of the context's recurrence (its band and cost mode), the path's cost and a map from
+ * target frames onto source frames, in one call.  The reference has no counterpart: it never warps.
+ *   Pair p = (dictionary segment src_idx[p] - index_base, target tgt_idx[p]); tgt_idx == NULL: target p (n_pairs <=
+ *   n_targets), so ssym_match_queries' out_idx can be passed straight in.  Any pairing, repeats allowed.  src_idx[p] ==
+ *   SSYM_NO_MATCH: no path, cost +inf.  src_idx / tgt_idx / offsets are HOST memory.
+ *   Path: cells (i, j), i = source frame, j = target frame, from (0, 0) to (Fa - 1, Fb - 1), every step one of (+1,+1),
+ *   (+1,0), (0,+1); max(Fa, Fb) <= L <= Fa + Fb - 1 cells.  Found backwards from the end cell on the exact f64 D: at
+ *   (i, j), with dg = D(i-1,j-1), up = D(i-1,j), lf = D(i,j-1) (outside the matrix or the band: +inf), go diagonally if
+ *   dg <= up && dg <= lf, else up (i - 1) if up <= lf, else left (j - 1).
+ *   out_cost   n_pairs f64: D(Fa-1, Fb-1), the bits ssym_pair_matrix(exact = 1) returns for the pair
+ *   out_len    n_pairs u32: L, or 0 when the cost is not finite (an empty segment, a band that cuts every path, NaN
+ *              features, SSYM_NO_MATCH): then neither the path slot nor the map slot of the pair is written
+ *   out_path   2 u32 (i, j) per cell, forward order, pair p from cell index path_offsets[p] on
+ *   out_map    nullable; u32 per target frame, pair p from map_offsets[p] on: map[j] = the smallest i with (i, j) on the
+ *              path (non-decreasing, map[0] = 0)
+ *   flags      SSYM_OUT_DEVICE: out_cost, out_len, out_path and out_map are device memory
+ * ssym_dtw_align_sizes (host arithmetic, no device work) fills both offset arrays (n_pairs + 1 u64 each, starting at 0)
+ * with the room a pair can need: Fa + Fb - 1 cells and Fb map entries, 0 for SSYM_NO_MATCH or an empty segment.
+ * ssym_dtw_align accepts any non-decreasing offsets that leave at least that room per pair.
+ * Limits: every listed segment at most 4096 frames, dim <= 64; beyond them, and on a refcos context,
+ * SSYM_E_UNSUPPORTED.  NULL pointers, an index outside its set, a dim mismatch, decreasing or too small offsets:
+ * SSYM_E_INVALID; an empty dictionary with n_pairs > 0: SSYM_E_EMPTY_DICT -- all with a message, before device memory
+ * is touched and with the outputs unwritten.  n_pairs = 0 succeeds and does nothing.  One synchronisation per call. */
+SSYM_API int32_t ssym_dtw_align_sizes(const ssym_dict *dict, const ssym_queries *q, const uint32_t *src_idx,
+                                      const uint32_t *tgt_idx, uint32_t n_pairs, uint32_t index_base,
+                                      uint64_t *path_offsets, uint64_t *map_offsets);
+SSYM_API int32_t ssym_dtw_align(ssym_ctx *ctx, const ssym_dict *dict, const ssym_queries *q, const uint32_t *src_idx,
+                                const uint32_t *tgt_idx, uint32_t n_pairs, uint32_t index_base, double *out_cost,
+                                uint32_t *out_len, const uint64_t *path_offsets, uint32_t *out_path,
+                                const uint64_t *map_offsets, uint32_t *out_map, uint32_t flags);
+
 /* Source-sharded multi-GPU, dtw metric: the one real exchange the path has.  Each rank's filter gives,
  * per target, an upper bound on the best key in ITS shard; a rank whose shard does not hold a
  * target's neighbour would otherwise re-score ~10^2 of its own pairs per target for nothing.

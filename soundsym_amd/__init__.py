@@ -13,6 +13,7 @@ from ._native import (  # noqa: F401
 )
 from .engine import DeviceFrames, Engine, Gmm, Stream, pack_segments, stream_plan  # noqa: F401
 from .api import (  # noqa: F401
+    Alignment,
     BIN,
     HOP,
     NCLUSTERS,
@@ -32,7 +33,7 @@ from .api import (  # noqa: F401
 )
 
 __all__ = [
-    "ABI_SYMBOLS", "BIN", "DeviceFrames", "EmptyDictionaryError", "Engine", "Gmm", "HOP", "LIB_PATH", "NCLUSTERS", "NCOEFFS",
+    "ABI_SYMBOLS", "Alignment", "BIN", "DeviceFrames", "EmptyDictionaryError", "Engine", "Gmm", "HOP", "LIB_PATH", "NCLUSTERS", "NCOEFFS",
     "Partitioner", "Sound", "SoundDictionary", "SoundSequence", "SsymError", "analyze_mfccs", "analyze_sounds", "build",
     "cosine_sim_angular", "discretize",
     "discretize_with_model", "length_fit", "pack_segments", "push_sounds", "Stream", "stream_plan", "train_model",

@@ -54,6 +54,7 @@ ABI_SYMBOLS = [
     "ssym_stream_create", "ssym_stream_destroy", "ssym_stream_push", "ssym_stream_seed", "ssym_stream_counts",
     "ssym_stream_read", "ssym_stream_frames_device", "ssym_stream_samples_device", "ssym_stream_descriptors",
     "ssym_stream_reset",
+    "ssym_dtw_align_sizes", "ssym_dtw_align",
 ]
 COMM_ID_BYTES = 128        # SSYM_COMM_ID_BYTES
 
@@ -239,6 +240,10 @@ def lib() -> ctypes.CDLL:
     L.ssym_mfcc_num_frames.argtypes = [u64, u32, vp]
     L.ssym_mfcc.restype = i32
     L.ssym_mfcc.argtypes = [vp, vp, u64, f64, u32, f64, f64, u32, vp, vp]
+    L.ssym_dtw_align_sizes.restype = i32
+    L.ssym_dtw_align_sizes.argtypes = [vp, vp, vp, vp, u32, u32, vp, vp]
+    L.ssym_dtw_align.restype = i32
+    L.ssym_dtw_align.argtypes = [vp, vp, vp, vp, vp, u32, u32, vp, vp, vp, vp, vp, vp, u32]
     L.ssym_pair_matrix.restype = i32
     L.ssym_pair_matrix.argtypes = [vp, vp, vp, i32, vp]
     L.ssym_merge_shards.restype = i32

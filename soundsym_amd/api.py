@@ -315,6 +315,38 @@ def push_sounds(sounds: Sequence[Sound], chunks, engine: Optional[Engine] = None
         at += k
 
 
+class Alignment:
+    """One target aligned with a dictionary sound (ssym_dtw_align; definition in include/soundsym_amd.h and DESIGN.md
+    section 2): `source_index` into the dictionary's sounds, the DTW `cost` of the pair, `path` an (L, 2) uint32 array
+    of (source frame, target frame) cells from (0, 0) to the last frames, and `frame_map` a (target frames,) uint32
+    array with the smallest source frame aligned with every target frame.  A pair without a finite cost (an empty
+    sound, a band that cuts every path) has an empty path and an empty map."""
+
+    __slots__ = ("cost", "path", "frame_map", "source_index")
+
+    def __init__(self, cost: float, path, frame_map, source_index: int):
+        path = np.asarray(path, dtype=np.uint32)
+        if path.ndim != 2 or path.shape[1] != 2:
+            raise ValueError("path must be an (L, 2) array of (source frame, target frame) cells")
+        frame_map = np.asarray(frame_map, dtype=np.uint32)
+        if frame_map.ndim != 1:
+            raise ValueError("frame_map must hold one source frame per target frame")
+        self.cost, self.path, self.frame_map, self.source_index = float(cost), path, frame_map, int(source_index)
+
+    def __len__(self) -> int:
+        return int(self.path.shape[0])
+
+    def diagonal_share(self) -> float:
+        """Share of the path's steps that advance both sounds (1.0: no warping; 0.0 for a path of one cell)."""
+        if len(self) < 2:
+            return 0.0
+        d = np.diff(self.path.astype(np.int64), axis=0)
+        return float(np.mean((d[:, 0] == 1) & (d[:, 1] == 1)))
+
+    def __repr__(self) -> str:
+        return "Alignment(source_index=%d, cost=%r, cells=%d)" % (self.source_index, self.cost, len(self))
+
+
 class SoundDictionary:
     """Cache of Sounds searched by similarity (src/sound.rs:290-371)."""
 
@@ -463,6 +495,31 @@ class SoundDictionary:
         return self.engine.match_batch(self.resident(), flat, off, distances)
 
 
+    def align(self, targets: Sequence[Sound], indices=None) -> List["Alignment"]:
+        """The warping path of every target onto a dictionary sound (dtw engines; ssym_dtw_align).  indices=None:
+        every target is matched first (match_indices) and aligned with its match -- two library calls in all;
+        otherwise indices[t] is the dictionary sound target t is aligned with."""
+        if not self.sounds:
+            raise EmptyDictionaryError(-2, "empty dictionary")
+        targets = list(targets)
+        if indices is not None:
+            indices = np.asarray(indices, dtype=np.int64).reshape(-1)
+            if indices.size != len(targets):
+                raise ValueError("indices must name one dictionary sound per target")
+            if indices.size and (indices.min() < 0 or indices.max() >= len(self.sounds)):
+                raise ValueError("an index is outside the dictionary")
+        if not targets:
+            return []
+        flat, off = pack_segments([t.mfccs() for t in targets], self._dim(), self.engine.np_dtype)
+        q = self.engine.queries(flat, off, self._dim())
+        try:
+            if indices is None:
+                indices, _ = self.engine.match(self.resident(), q)
+            cost, _, paths, maps = self.engine.dtw_align(self.resident(), q, indices)
+        finally:
+            q.close()
+        return [Alignment(cost[t], paths[t], maps[t], int(indices[t])) for t in range(len(targets))]
+
     def candidates(self, targets: Sequence[Sound], k: int, distances=None) -> List[List[Sound]]:
         """The k best dictionary sounds per target, best first: what k
         successive at_distance calls (src/sound.rs:351) would return if each winner were removed."""
@@ -576,6 +633,12 @@ class SoundSequence:
                 out.append(Sound(length_fit(s.samples(), sound.samples().size), sound.sample_rate(),
                                  None, None, s.ncoeffs))
         return SoundSequence(out)
+
+    def align_to_dictionary(self, dict_: SoundDictionary) -> List[Alignment]:
+        """Every sound of the sequence matched against dict_ and aligned with its match (SoundDictionary.align)."""
+        if not self._sounds:
+            return []
+        return dict_.align(self._sounds)
 
     def reconstruct_from_dictionary(self, dict_: "SoundDictionary", want_pcm32: bool = False):
         """clone_from_dictionary(dict).to_sound().samples() in one go (src/sound.rs:451-480): match

@@ -1,0 +1,521 @@
+// dtw_align.hip -- DTW alignment: the optimal warping path of a list of (source, target) pairs, its cost and the
+// per-target-frame map onto source frames (DESIGN.md 2 "Alignment", 5.12).
+//
+// Role on the path: ssym_match_* answer "how far apart"; this answers "which frame goes with which" for the pairs a
+// match has chosen (thousands after one ssym_match_queries), in one launch and one synchronisation.
+//
+// Arithmetic: D is formed exactly as dtw_exact.hip forms it (f64, k ascending, sub / mul / add rounded separately,
+// the square root rounded separately, c + min3 with min3's comparisons in the same order), so D(Fa-1, Fb-1) has
+// the bits ssym_pair_matrix(exact = 1) returns.  The backward rule compares those exact values:
+//   dg = D(i-1,j-1), up = D(i-1,j), lf = D(i,j-1):  diagonal if dg <= up && dg <= lf, else up if up <= lf, else left.
+//
+// Mapping: one wave per pair, grid-stride over the list.
+//   forward   anti-diagonal wavefront over 64-row chunks as in dtw_exact_reg_kernel (lane = row, the row above by a
+//             DPP move, a chunk's bottom row handed to the next chunk through ONE LDS row that is overwritten in
+//             place: lane 63 writes column tau - 63 while lane 0 reads columns tau and tau - 1).  The lane's source
+//             frame sits in registers; target frames pass through an LDS ring of 128 frames that is refilled 64
+//             frames at a time (at step tau the lanes read columns tau - 63 ... tau), so the LDS a pair needs does
+//             not grow with the target.  Each lane has dg, up, lf in registers when it forms min3; the 2-bit step
+//             code goes into a dword of 16 codes per row, stored when full.  The direction matrix (Fa x ceil(Fb / 16)
+//             dwords) lives in LDS when it fits kAlignDirLdsBytes, else in this workgroup's slab of global scratch.
+//   backward  lane 0 walks the codes from (Fa-1, Fb-1) to (0, 0): one dependent read per step, one code byte into
+//             LDS per step.  Other waves of the CU hide it (a pair of 128 x 128 frames takes about 20 KB of LDS).
+//   output    the wave turns the reversed code string into cells with two ballots per 64 steps (i and j of path
+//             position f are the numbers of row / column steps before f) and writes the path in forward order and
+//             the map (the first cell of every column) with coalesced vector stores.
+#include "ssym_internal.hpp"
+
+#include <algorithm>
+#include <cmath>
+
+namespace ssym {
+
+// Limits of ssym_dtw_align (soundsym_amd.h): frames per segment of a listed pair, values per frame
+constexpr int kAlignMaxFrames = 4096;
+constexpr int kAlignMaxDim = 64;
+// a pair whose direction matrix (Fa * ceil(Fb / 16) * 4 bytes) is at most this keeps it in LDS, a larger one uses global scratch
+constexpr int kAlignDirLdsBytes = 16384;
+// global scratch of one call: at most this many bytes of direction slabs (one per workgroup)
+constexpr size_t kAlignScratchBytes = (size_t)512 << 20;
+constexpr int kAlignRing = 128;             // target frames resident in LDS (two blocks of 64)
+
+namespace {
+
+__device__ __forceinline__ double align_shfl_up1(double v)     // lane - 1's value (dtw_exact.hip: DPP wave_shr:1)
+{
+    int lo = __double2loint(v), hi = __double2hiint(v);
+    lo = __builtin_amdgcn_update_dpp(lo, lo, 0x138, 0xf, 0xf, false);
+    hi = __builtin_amdgcn_update_dpp(hi, hi, 0x138, 0xf, 0xf, false);
+    return __hiloint2double(hi, lo);
+}
+
+// LDS row stride of the ring: 2 (mod 4) doubles, so 128-bit reads by consecutive lanes tile the banks (dtw_exact.hip)
+template <int DIMR>
+constexpr int align_ld() { return DIMR % 4 == 2 ? DIMR : DIMR + 2; }
+
+struct AlignArgs {
+    const double *srcRaw;
+    const uint64_t *srcOff;
+    const double *tgtRaw;
+    const uint64_t *tgtOff;
+    uint32_t dim;
+    int band, squared;
+    const uint2 *pairs;          // (source, target); source 0xffffffff = no match
+    uint32_t nPairs;
+    const uint64_t *pathOff;     // [nPairs + 1] in steps
+    const uint64_t *mapOff;      // [nPairs + 1] in frames (NULL with map == NULL)
+    double *cost;                // [nPairs]
+    uint32_t *len;               // [nPairs]
+    uint2 *path;
+    uint32_t *map;               // nullable
+    uint32_t fbCap;              // even, >= the longest listed target
+    uint32_t ringRows;           // 64 or 128
+    uint32_t codeCap;            // bytes of the code string (>= longest Fa + Fb - 1, a multiple of 16)
+    uint32_t dirLdsBytes;        // LDS room of the direction matrix
+    uint32_t *slabs;             // global direction slabs, slabWords each (NULL: every listed pair fits LDS)
+    uint64_t slabWords;
+};
+
+template <int DIMR>
+__global__ __launch_bounds__(64) void dtw_align_kernel(const AlignArgs a)
+{
+    extern __shared__ __attribute__((aligned(16))) double smem[];
+    constexpr int LD = align_ld<DIMR>();
+    typedef double d2 __attribute__((ext_vector_type(2)));
+    double *bound = smem;                                           // [fbCap]   bottom row of the chunk above
+    double *ring = smem + a.fbCap;                                  // [ringRows][LD]
+    unsigned char *codes = reinterpret_cast<unsigned char *>(ring + (size_t)a.ringRows * LD);     // [codeCap]
+    uint32_t *dirLds = reinterpret_cast<uint32_t *>(codes + a.codeCap);                         // [dirLdsBytes / 4]
+    const double INF = __builtin_inf();
+    const int lane = threadIdx.x;
+    const int dim = (int)a.dim, band = a.band;
+    const uint32_t ringMask = a.ringRows - 1;
+
+    for (uint32_t k = blockIdx.x; k < a.nPairs; k += gridDim.x) {
+        const uint2 p = a.pairs[k];
+        int Fa = 0, Fb = 0;
+        if (p.x != 0xffffffffu) {
+            Fa = (int)(a.srcOff[p.x + 1] - a.srcOff[p.x]);
+            Fb = (int)(a.tgtOff[p.y + 1] - a.tgtOff[p.y]);
+        }
+        if (Fa == 0 || Fb == 0) {
+            if (lane == 0) {
+                a.cost[k] = INF;
+                a.len[k] = 0;
+            }
+            continue;
+        }
+        const double *a0 = a.srcRaw + a.srcOff[p.x] * dim;
+        const double *b0 = a.tgtRaw + a.tgtOff[p.y] * dim;
+        const uint32_t rowWords = ((uint32_t)Fb + 15) >> 4;
+        const bool dirInLds = (uint64_t)Fa * rowWords * 4 <= a.dirLdsBytes;
+        uint32_t *dirG = a.slabs + (size_t)blockIdx.x * a.slabWords;     // only touched when !dirInLds (then slabs != NULL)
+
+        __syncthreads();   // the previous pair's LDS reads are done
+        for (int j = lane; j < Fb; j += 64)
+            bound[j] = INF;
+        double result = INF;
+        for (int c0 = 0; c0 < Fa; c0 += 64) {
+            const int r = c0 + lane;
+            const bool rowValid = r < Fa;
+            const int rowsHere = min(64, Fa - c0);
+            double ar[DIMR];
+            {
+                const double *arow = a0 + (size_t)(rowValid ? r : c0) * dim;
+#pragma unroll
+                for (int e = 0; e < DIMR; ++e)
+                    ar[e] = e < dim ? arow[e] : 0.0;
+            }
+            int jlo = 0, jhi = Fb - 1;
+            if (band >= 0) {
+                jlo = max(0, c0 - band);
+                jhi = min(Fb - 1, c0 + rowsHere - 1 + band);
+            }
+            double mine = INF;      // D(r, j-1)
+            double diagReg = INF;   // D(r-1, j-1)
+            uint32_t pack = 0;      // step codes of this row's current group of 16 columns
+            const int tauEnd = jhi + rowsHere;     // exclusive: lane l works on column tau - l
+            for (int tau = jlo; tau < tauEnd; ++tau) {
+                if (tau == jlo || (tau & 63) == 0) {
+                    // the 64 target frames from column (tau & ~63) on enter the ring; the block they replace ended
+                    // at column (tau & ~63) - 65, and the lanes still read from column tau - 63 on
+                    const int f0 = tau & ~63;
+                    const int cnt = min(64, Fb - f0);
+                    __syncthreads();
+                    for (int i = lane; i < cnt * DIMR; i += 64) {
+                        const int fr = i / DIMR, e = i % DIMR;
+                        ring[(size_t)((uint32_t)(f0 + fr) & ringMask) * LD + e] = e < dim ? b0[(size_t)(f0 + fr) * dim + e] : 0.0;
+                    }
+                    __syncthreads();
+                }
+                const int j = tau - lane;
+                const int jc = min(max(j, 0), Fb - 1);
+                const d2 *bp = reinterpret_cast<const d2 *>(ring + (size_t)((uint32_t)jc & ringMask) * LD);
+                // sum_k (a_k - b_k)^2, k ascending, sub / mul / add rounded separately (the oracle's order); the
+                // zero padding adds +0.0 to a non-negative sum and leaves its bits alone
+                double acc = 0.0;
+#pragma unroll
+                for (int e0 = 0; e0 < DIMR; e0 += 8) {
+                    d2 bv[4];
+#pragma unroll
+                    for (int v = 0; v < 4; ++v)
+                        if (e0 + 2 * v < DIMR)
+                            bv[v] = bp[e0 / 2 + v];
+#pragma unroll
+                    for (int v = 0; v < 8; ++v)
+                        if (e0 + v < DIMR) {
+                            const double df = __dsub_rn(ar[e0 + v], bv[v / 2][v % 2]);
+                            acc = __dadd_rn(acc, __dmul_rn(df, df));
+                        }
+                }
+                const double c = a.squared ? acc : sqrt(acc);
+                double up = align_shfl_up1(mine);         // D(r-1, j) for lanes >= 1
+                double dg = diagReg;
+                if (lane == 0) {
+                    if (c0 == 0) {
+                        up = INF;
+                        dg = (j == 0) ? 0.0 : INF;        // virtual D(-1,-1) = 0
+                    } else {
+                        up = (j >= 0 && j < Fb) ? bound[j] : INF;
+                        dg = (j >= 1 && j <= Fb) ? bound[j - 1] : INF;
+                    }
+                }
+                const bool active = rowValid && j >= 0 && j < Fb;
+                if (active) {
+                    double cur = INF;
+                    const int dij = r - j;
+                    if (band < 0 || (dij <= band && -dij <= band)) {
+                        double best = up;                     // D(i-1, j)      (dtw_exact.hip's order)
+                        if (mine < best) best = mine;         // D(i,   j-1)
+                        if (dg < best) best = dg;             // D(i-1, j-1)
+                        cur = __dadd_rn(c, best);
+                        // the backward rule: ties prefer the diagonal, then the source step
+                        const uint32_t code = (dg <= up && dg <= mine) ? 0u : (up <= mine ? 1u : 2u);
+                        pack |= code << (2 * (j & 15));
+                    }
+                    if (j <= jhi && ((j & 15) == 15 || j == jhi)) {     // (columns beyond jhi are outside every row's band)
+                        const size_t w = (size_t)r * rowWords + ((uint32_t)j >> 4);
+                        if (dirInLds)
+                            dirLds[w] = pack;
+                        else
+                            dirG[w] = pack;
+                        pack = 0;
+                    }
+                    if (lane == 63)
+                        bound[j] = cur;
+                    if (r == Fa - 1 && j == Fb - 1)
+                        result = cur;
+                    mine = cur;
+                }
+                diagReg = up;
+            }
+        }
+        const double total = __shfl(result, (Fa - 1) & 63);
+        if (lane == 0)
+            a.cost[k] = total;
+        if (!(total < INF)) {      // +inf or NaN: no path (dtw_exact.hip never forms -inf: every term is >= 0)
+            if (lane == 0)
+                a.len[k] = 0;
+            continue;
+        }
+        // the codes this wave stored are read back by its lane 0: LDS after a barrier; the slab after the stores have
+        // left the wave (release) and by loads that bypass this CU's L1, which may hold lines of the previous pair
+        if (!dirInLds)
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+        __syncthreads();
+        int steps = 0;
+        if (lane == 0) {
+            int i = Fa - 1, j = Fb - 1;
+            while (i > 0 || j > 0) {
+                const size_t w = (size_t)i * rowWords + ((uint32_t)j >> 4);
+                const uint32_t word = dirInLds ? dirLds[w] : __hip_atomic_load(dirG + w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                uint32_t code = (word >> (2 * (j & 15))) & 3u;
+                // (row 0 can only go left and column 0 only up: the rule says so too, the walk never leaves the matrix)
+                code = i == 0 ? 2u : j == 0 ? 1u : code;
+                codes[steps++] = (unsigned char)code;
+                i -= code != 2u;
+                j -= code != 1u;
+            }
+        }
+        __syncthreads();
+        const int L = __builtin_amdgcn_readfirstlane(steps) + 1;
+        if (lane == 0)
+            a.len[k] = (uint32_t)L;
+        uint2 *path = a.path + a.pathOff[k];
+        uint32_t *map = a.map ? a.map + a.mapOff[k] : nullptr;
+        // path position f is entered by walk step L - 1 - f; its cell = (row steps, column steps) up to and including it
+        int ci = 0, cj = 0;
+        for (int base = 0; base < L; base += 64) {
+            const int f = base + lane;
+            uint32_t code = 3u;      // position 0 and positions beyond the path: no step
+            if (f >= 1 && f < L)
+                code = codes[L - 1 - f];
+            const bool di = code == 0u || code == 1u, dj = code == 0u || code == 2u;
+            const unsigned long long mi = __ballot(di), mj = __ballot(dj);
+            const unsigned long long le = lane == 63 ? ~0ull : ((2ull << lane) - 1);
+            const int i = ci + __popcll(mi & le), j = cj + __popcll(mj & le);
+            if (f < L) {
+                path[f] = make_uint2((uint32_t)i, (uint32_t)j);
+                if (map && (f == 0 || dj))
+                    map[j] = (uint32_t)i;        // the first cell of column j on the path holds its smallest i
+            }
+            ci += __popcll(mi);
+            cj += __popcll(mj);
+        }
+    }
+}
+
+// Fa + Fb - 1 steps and Fb map entries per pair, 0 for a pair without a source or with an empty segment
+inline void align_capacity(const SegmentSet &src, const SegmentSet &tgt, uint32_t s, uint32_t t, uint64_t *steps,
+                           uint64_t *frames)
+{
+    *steps = *frames = 0;
+    if (s == SSYM_NO_MATCH)
+        return;
+    const uint64_t fa = src.h_off[s + 1] - src.h_off[s], fb = tgt.h_off[t + 1] - tgt.h_off[t];
+    if (fa == 0 || fb == 0)
+        return;
+    *steps = fa + fb - 1;
+    *frames = fb;
+}
+
+// the argument checks ssym_dtw_align_sizes and ssym_dtw_align share (err: where the message goes)
+int32_t align_check(std::string &err, const ssym_dict *dict, const ssym_queries *q, const uint32_t *src_idx,
+                    const uint32_t *tgt_idx, uint32_t n_pairs, uint32_t index_base)
+{
+    if (!dict || !q) {
+        err = "ssym_dtw_align: dictionary or queries handle is NULL";
+        return SSYM_E_INVALID;
+    }
+    if (n_pairs == 0)
+        return SSYM_OK;
+    if (!src_idx) {
+        err = "ssym_dtw_align: src_idx is NULL";
+        return SSYM_E_INVALID;
+    }
+    if (dict->set.n == 0) {
+        err = "empty dictionary";
+        return SSYM_E_EMPTY_DICT;
+    }
+    if (dict->set.dim != q->set.dim) {
+        err = "dim mismatch between dictionary and targets";
+        return SSYM_E_INVALID;
+    }
+    if (!tgt_idx && n_pairs > q->set.n) {
+        err = "ssym_dtw_align: tgt_idx is NULL and n_pairs exceeds the number of targets";
+        return SSYM_E_INVALID;
+    }
+    for (uint32_t p = 0; p < n_pairs; ++p) {
+        if (src_idx[p] != SSYM_NO_MATCH && (src_idx[p] < index_base || src_idx[p] - index_base >= dict->set.n)) {
+            err = "ssym_dtw_align: src_idx[" + std::to_string(p) + "] is outside the dictionary";
+            return SSYM_E_INVALID;
+        }
+        if (tgt_idx && tgt_idx[p] >= q->set.n) {
+            err = "ssym_dtw_align: tgt_idx[" + std::to_string(p) + "] is outside the targets";
+            return SSYM_E_INVALID;
+        }
+    }
+    return SSYM_OK;
+}
+
+int32_t dtw_align(ssym_ctx *ctx, const ssym_dict *dict, const ssym_queries *q, const uint32_t *src_idx,
+                  const uint32_t *tgt_idx, uint32_t n_pairs, uint32_t index_base, double *out_cost, uint32_t *out_len,
+                  const uint64_t *path_offsets, uint32_t *out_path, const uint64_t *map_offsets, uint32_t *out_map,
+                  uint32_t flags)
+{
+    if (!ctx)
+        return SSYM_E_INVALID;
+    if (ctx->metric != SSYM_METRIC_DTW) {
+        ctx->err = "ssym_dtw_align: the context's metric is refcos, which has no alignment";
+        return SSYM_E_UNSUPPORTED;
+    }
+    int32_t rc = align_check(ctx->err, dict, q, src_idx, tgt_idx, n_pairs, index_base);
+    if (rc != SSYM_OK)
+        return rc;
+    if (n_pairs == 0)
+        return SSYM_OK;
+    if (!out_cost || !out_len || !path_offsets || !out_path || (out_map && !map_offsets)) {
+        ctx->err = "ssym_dtw_align: out_cost, out_len, path_offsets, out_path (and map_offsets with out_map) must not be NULL";
+        return SSYM_E_INVALID;
+    }
+    const SegmentSet &src = dict->set, &tgt = q->set;
+    // the pair list, the offsets against the capacities, the shape limits: all on the host, before any device work
+    std::vector<uint2> pairs(n_pairs);
+    uint64_t maxFa = 0, maxFb = 0, maxSlab = 0;
+    for (uint32_t p = 0; p < n_pairs; ++p) {
+        const uint32_t s = src_idx[p] == SSYM_NO_MATCH ? SSYM_NO_MATCH : src_idx[p] - index_base;
+        const uint32_t t = tgt_idx ? tgt_idx[p] : p;
+        pairs[p] = make_uint2(s, t);
+        uint64_t steps, frames;
+        align_capacity(src, tgt, s, t, &steps, &frames);
+        if (path_offsets[p + 1] < path_offsets[p] || path_offsets[p + 1] - path_offsets[p] < steps ||
+            (out_map && (map_offsets[p + 1] < map_offsets[p] || map_offsets[p + 1] - map_offsets[p] < frames))) {
+            ctx->err = "ssym_dtw_align: offsets of pair " + std::to_string(p) +
+                       " decrease or leave less room than ssym_dtw_align_sizes asks for";
+            return SSYM_E_INVALID;
+        }
+        if (steps == 0)
+            continue;
+        const uint64_t fa = steps + 1 - frames, fb = frames;
+        maxFa = std::max(maxFa, fa);
+        maxFb = std::max(maxFb, fb);
+        const uint64_t dirBytes = fa * ((fb + 15) / 16) * 4;
+        if (dirBytes > (uint64_t)kAlignDirLdsBytes)
+            maxSlab = std::max(maxSlab, dirBytes);
+    }
+    if (maxFa > (uint64_t)kAlignMaxFrames || maxFb > (uint64_t)kAlignMaxFrames || src.dim > (uint32_t)kAlignMaxDim) {
+        ctx->err = "ssym_dtw_align: a listed segment has more than " + std::to_string(kAlignMaxFrames) +
+                   " frames, or frames have more than " + std::to_string(kAlignMaxDim) + " values";
+        return SSYM_E_UNSUPPORTED;
+    }
+    SSYM_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    const bool outDev = (flags & SSYM_OUT_DEVICE) != 0;
+    const uint64_t pathTotal = path_offsets[n_pairs] - path_offsets[0];
+    const uint64_t mapTotal = out_map ? map_offsets[n_pairs] - map_offsets[0] : 0;
+
+    Blocks bl(ctx);
+    AlignArgs a{};
+    uint2 *dPairs = nullptr;
+    uint64_t *dOff = nullptr;        // path offsets, then map offsets, both rebased to the first pair's
+    rc = bl.get(&dPairs, n_pairs);
+    if (rc == SSYM_OK)
+        rc = bl.get(&dOff, 2 * ((size_t)n_pairs + 1));
+    std::vector<uint64_t> hOff(2 * ((size_t)n_pairs + 1));
+    for (uint32_t p = 0; p <= n_pairs; ++p) {
+        hOff[p] = path_offsets[p] - path_offsets[0];
+        hOff[(size_t)n_pairs + 1 + p] = out_map ? map_offsets[p] - map_offsets[0] : 0;
+    }
+    double *dCost = out_cost;
+    uint32_t *dLen = out_len, *dPath = out_path + 2 * path_offsets[0], *dMap = out_map ? out_map + map_offsets[0] : nullptr;
+    if (!outDev) {
+        if (rc == SSYM_OK)
+            rc = bl.get(&dCost, n_pairs);
+        if (rc == SSYM_OK)
+            rc = bl.get(&dLen, n_pairs);
+        if (rc == SSYM_OK)
+            rc = bl.get(&dPath, 2 * (size_t)pathTotal);
+        if (rc == SSYM_OK && out_map)
+            rc = bl.get(&dMap, (size_t)mapTotal);
+    }
+    const uint32_t fbEven = ((uint32_t)std::max<uint64_t>(maxFb, 1) + 1) & ~1u;
+    const int dimr = src.dim <= 14 ? 14 : src.dim <= 16 ? 16 : src.dim <= 40 ? 40 : 64;
+    const int ld = dimr % 4 == 2 ? dimr : dimr + 2;       // align_ld<>
+    a.ringRows = maxFb <= 64 ? 64 : kAlignRing;
+    a.codeCap = ((uint32_t)(maxFa + maxFb) + 15) & ~15u;
+    a.dirLdsBytes = (uint32_t)std::min<uint64_t>((uint64_t)kAlignDirLdsBytes, (maxFa * ((maxFb + 15) / 16) * 4 + 15) & ~15ull);
+    const size_t lds = (size_t)fbEven * sizeof(double) + (size_t)a.ringRows * ld * sizeof(double) + a.codeCap + a.dirLdsBytes;
+    unsigned grid = (unsigned)std::min<uint64_t>(n_pairs, (uint64_t)ctx->num_cus * 8);
+    if (maxSlab) {
+        // one slab per workgroup, as many workgroups as kAlignScratchBytes holds (128 for a 4096 x 4096 pair)
+        a.slabWords = (maxSlab + 3) / 4;
+        grid = (unsigned)std::min<uint64_t>(grid, std::max<uint64_t>(1, kAlignScratchBytes / (a.slabWords * 4)));
+        if (rc == SSYM_OK)
+            rc = bl.get(&a.slabs, (size_t)grid * a.slabWords);
+    }
+    if (rc != SSYM_OK)
+        return rc;
+    SSYM_HIP_CHECK(ctx, hipMemcpyAsync(dPairs, pairs.data(), sizeof(uint2) * n_pairs, hipMemcpyHostToDevice, st));
+    SSYM_HIP_CHECK(ctx, hipMemcpyAsync(dOff, hOff.data(), sizeof(uint64_t) * hOff.size(), hipMemcpyHostToDevice, st));
+    a.srcRaw = src.raw;
+    a.srcOff = src.off;
+    a.tgtRaw = tgt.raw;
+    a.tgtOff = tgt.off;
+    a.dim = src.dim;
+    a.band = ctx->band;
+    a.squared = ctx->squared;
+    a.pairs = dPairs;
+    a.nPairs = n_pairs;
+    a.pathOff = dOff;
+    a.mapOff = dOff + n_pairs + 1;
+    a.cost = dCost;
+    a.len = dLen;
+    a.path = reinterpret_cast<uint2 *>(dPath);
+    a.map = dMap;
+    a.fbCap = fbEven;
+#define SSYM_ALIGN_LAUNCH(D_)                                                                                  \
+    do {                                                                                                       \
+        auto kern = dtw_align_kernel<D_>;                                                                      \
+        if (lds > 64 * 1024)                                                                                   \
+            SSYM_HIP_CHECK(ctx, hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, \
+                                                    (int)lds));                                                \
+        kern<<<grid, 64, lds, st>>>(a);                                                                        \
+    } while (0)
+    switch (dimr) {
+    case 14: SSYM_ALIGN_LAUNCH(14); break;
+    case 16: SSYM_ALIGN_LAUNCH(16); break;
+    case 40: SSYM_ALIGN_LAUNCH(40); break;
+    default: SSYM_ALIGN_LAUNCH(64); break;
+    }
+#undef SSYM_ALIGN_LAUNCH
+    SSYM_HIP_CHECK(ctx, hipGetLastError());
+    if (outDev) {
+        SSYM_HIP_CHECK(ctx, hipStreamSynchronize(st));
+        return SSYM_OK;
+    }
+    // host outputs: only what the kernel wrote reaches the caller's buffers (a pair without a path leaves its slots alone)
+    std::vector<double> hCost(n_pairs);
+    std::vector<uint32_t> hLen(n_pairs), hPath(2 * (size_t)pathTotal), hMap((size_t)mapTotal);
+    SSYM_HIP_CHECK(ctx, hipMemcpyAsync(hCost.data(), dCost, sizeof(double) * n_pairs, hipMemcpyDeviceToHost, st));
+    SSYM_HIP_CHECK(ctx, hipMemcpyAsync(hLen.data(), dLen, sizeof(uint32_t) * n_pairs, hipMemcpyDeviceToHost, st));
+    if (pathTotal)
+        SSYM_HIP_CHECK(ctx, hipMemcpyAsync(hPath.data(), dPath, sizeof(uint32_t) * 2 * pathTotal, hipMemcpyDeviceToHost, st));
+    if (mapTotal)
+        SSYM_HIP_CHECK(ctx, hipMemcpyAsync(hMap.data(), dMap, sizeof(uint32_t) * mapTotal, hipMemcpyDeviceToHost, st));
+    SSYM_HIP_CHECK(ctx, hipStreamSynchronize(st));
+    std::copy(hCost.begin(), hCost.end(), out_cost);
+    std::copy(hLen.begin(), hLen.end(), out_len);
+    for (uint32_t p = 0; p < n_pairs; ++p) {
+        if (hLen[p] == 0)
+            continue;
+        std::copy(hPath.begin() + 2 * hOff[p], hPath.begin() + 2 * (hOff[p] + hLen[p]), out_path + 2 * path_offsets[p]);
+        if (out_map) {
+            const uint64_t m0 = hOff[(size_t)n_pairs + 1 + p], fb = tgt.h_off[pairs[p].y + 1] - tgt.h_off[pairs[p].y];
+            std::copy(hMap.begin() + m0, hMap.begin() + m0 + fb, out_map + map_offsets[p]);
+        }
+    }
+    return SSYM_OK;
+}
+
+}  // namespace
+}  // namespace ssym
+
+using namespace ssym;
+
+extern "C" {
+
+int32_t ssym_dtw_align_sizes(const ssym_dict *dict, const ssym_queries *q, const uint32_t *src_idx,
+                             const uint32_t *tgt_idx, uint32_t n_pairs, uint32_t index_base, uint64_t *path_offsets,
+                             uint64_t *map_offsets)
+{
+    return guarded(nullptr, [&]() -> int32_t {
+        std::string err;
+        const int32_t rc = align_check(err, dict, q, src_idx, tgt_idx, n_pairs, index_base);
+        if (rc != SSYM_OK)
+            return rc;
+        if (!path_offsets || !map_offsets)
+            return SSYM_E_INVALID;
+        path_offsets[0] = map_offsets[0] = 0;
+        for (uint32_t p = 0; p < n_pairs; ++p) {
+            uint64_t steps, frames;
+            align_capacity(dict->set, q->set, src_idx[p] == SSYM_NO_MATCH ? SSYM_NO_MATCH : src_idx[p] - index_base,
+                           tgt_idx ? tgt_idx[p] : p, &steps, &frames);
+            path_offsets[p + 1] = path_offsets[p] + steps;
+            map_offsets[p + 1] = map_offsets[p] + frames;
+        }
+        return SSYM_OK;
+    });
+}
+
+int32_t ssym_dtw_align(ssym_ctx *ctx, const ssym_dict *dict, const ssym_queries *q, const uint32_t *src_idx,
+                       const uint32_t *tgt_idx, uint32_t n_pairs, uint32_t index_base, double *out_cost,
+                       uint32_t *out_len, const uint64_t *path_offsets, uint32_t *out_path, const uint64_t *map_offsets,
+                       uint32_t *out_map, uint32_t flags)
+{
+    return guarded(ctx, [&]() -> int32_t {
+        return dtw_align(ctx, dict, q, src_idx, tgt_idx, n_pairs, index_base, out_cost, out_len, path_offsets, out_path,
+                         map_offsets, out_map, flags);
+    });
+}
+
+}  // extern "C"

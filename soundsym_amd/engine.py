@@ -32,6 +32,17 @@ def _is_device_tensor(x) -> bool:
     return hasattr(x, "data_ptr") and getattr(x, "is_cuda", False)
 
 
+def _align_indices(src_idx, tgt_idx):
+    """The pair list of dtw_align as contiguous uint32 arrays (tgt None: pair p uses target p)."""
+    src = np.ascontiguousarray(src_idx, dtype=np.uint32).reshape(-1)
+    tgt = None
+    if tgt_idx is not None:
+        tgt = np.ascontiguousarray(tgt_idx, dtype=np.uint32).reshape(-1)
+        if tgt.size != src.size:
+            raise ValueError("src_idx and tgt_idx must list the same number of pairs")
+    return src, tgt
+
+
 class _Handle:
     def __init__(self, engine: "Engine", ptr: int, n: int, dim: int, kind: str):
         self.engine, self.ptr, self.n, self.dim, self.kind = engine, ptr, n, dim, kind
@@ -549,6 +560,45 @@ class Engine:
         nat.check(nat.lib().ssym_pair_matrix(self.ctx, d.ptr, q.ptr, 1 if exact else 0,
                                              out.ctypes.data), self.ctx)
         return out
+
+    def dtw_align_sizes(self, d: _Handle, q: _Handle, src_idx, tgt_idx=None, index_base: int = 0):
+        """ssym_dtw_align_sizes: (path_offsets, map_offsets), n_pairs + 1 uint64 each -- the room a pair's path
+        (Fa + Fb - 1 cells) and map (Fb entries) can need.  Host arithmetic."""
+        src, tgt = _align_indices(src_idx, tgt_idx)
+        p_off = np.zeros(src.size + 1, dtype=np.uint64)
+        m_off = np.zeros(src.size + 1, dtype=np.uint64)
+        rc = nat.lib().ssym_dtw_align_sizes(d.ptr, q.ptr, src.ctypes.data, tgt.ctypes.data if tgt is not None else None,
+                                            src.size, index_base, p_off.ctypes.data, m_off.ctypes.data)
+        if rc == nat.SSYM_E_EMPTY_DICT:
+            raise nat.EmptyDictionaryError(rc, "empty dictionary")
+        if rc != nat.SSYM_OK:
+            raise nat.SsymError(rc, "ssym_dtw_align_sizes: an index is outside its set, or the sets do not go together")
+        return p_off, m_off
+
+    def dtw_align(self, d: _Handle, q: _Handle, src_idx, tgt_idx=None, index_base: int = 0, want_map: bool = True):
+        """ssym_dtw_align: the optimal warping path of every listed pair (source src_idx[p] - index_base, target
+        tgt_idx[p], or target p without tgt_idx), by the definition in include/soundsym_amd.h.  Returns (cost f64
+        [n], lengths uint32 [n], paths, maps): paths[p] is an (L, 2) uint32 array of (source frame, target frame)
+        cells in forward order, maps[p] a (Fb,) uint32 array with the smallest source frame of every target frame (or
+        None without want_map).  A pair without a finite cost has length 0, an empty path and an empty map.  The
+        arrays are views into one buffer each."""
+        src, tgt = _align_indices(src_idx, tgt_idx)
+        n = src.size
+        p_off, m_off = self.dtw_align_sizes(d, q, src, tgt, index_base)
+        cost = np.zeros(n, dtype=np.float64)
+        length = np.zeros(n, dtype=np.uint32)
+        path = np.zeros((int(p_off[-1]), 2), dtype=np.uint32)
+        fmap = np.zeros(int(m_off[-1]), dtype=np.uint32) if want_map else None
+        rc = nat.lib().ssym_dtw_align(self.ctx, d.ptr, q.ptr, src.ctypes.data, tgt.ctypes.data if tgt is not None else None,
+                                      n, index_base, cost.ctypes.data, length.ctypes.data, p_off.ctypes.data,
+                                      path.ctypes.data, m_off.ctypes.data if want_map else None,
+                                      fmap.ctypes.data if want_map else None, 0)
+        nat.check(rc, self.ctx)
+        paths = [path[int(p_off[p]):int(p_off[p]) + int(length[p])] for p in range(n)]
+        maps = None
+        if want_map:
+            maps = [fmap[int(m_off[p]):int(m_off[p + 1])] if length[p] else fmap[0:0] for p in range(n)]
+        return cost, length, paths, maps
 
     # -- feature front-end (F3) --------------------------------------------------------------
     def mfcc(self, samples, sample_rate: float, ncoeffs: int = 12, f_lo: float = 100.0, f_hi: float = 8000.0,
