@@ -220,7 +220,12 @@ SSYM_API int32_t ssym_match_one(ssym_ctx *ctx, const ssym_dict *dict, const void
  * step: in refcos the later steps are row lookups in the dictionary's self-similarity matrix,
  * which is computed on first use and kept with the dictionary (hence the non-const handle;
  * n^2 f64 of device memory) until ssym_dict_append changes it; in dtw every step re-scores the
- * dictionary against the current entry with the exact f64 kernel. */
+ * dictionary against the current entry with the exact f64 kernel.
+ * A step at which no key is below the fold's start (2.0 in refcos, +inf in dtw: zero-norm, NaN or empty entries only,
+ * a distance that far away, no pair inside the band) reports index 0 and the fold's start, and the chain goes on
+ * from entry 0 as the reference's fold does (src/sound.rs:361-369).  n_steps = 0 succeeds and does nothing; one step
+ * does not build the matrix.  NULL dict / distances / out_idx, or NULL start_feats with start_frames > 0:
+ * SSYM_E_INVALID; an empty dictionary: SSYM_E_EMPTY_DICT; the outputs are unwritten then. */
 SSYM_API int32_t ssym_chain(ssym_ctx *ctx, ssym_dict *dict, const void *start_feats, uint64_t start_frames,
                    const double *distances, uint32_t n_steps, uint32_t *out_idx, double *out_cost);
 
@@ -309,14 +314,22 @@ SSYM_API int32_t ssym_match_begin_pruned(ssym_ctx *ctx, const ssym_dict *dict, c
 /* Source-sharded multi-GPU: after an all-gather of every shard's (cost, global index) per target
  * (n_shards x n_targets each, shard-major, DEVICE memory), pick per target the shard entry with
  * the smallest cost, lowest global index on equal cost -- the same first-minimum rule as
- * src/sound.rs:361-367 because shards are ordered by index.  Outputs are DEVICE memory. */
+ * src/sound.rs:361-367 because shards are ordered by index.  Outputs are DEVICE memory.
+ * As in that fold a NaN key never wins: an entry whose key is NaN loses to every entry whose key is not, whichever
+ * shard holds it.  A column whose keys are ALL NaN returns shard 0's entry (index and cost) as it stands; a column of
+ * +inf returns the lowest index.  n_targets = 0 succeeds and does nothing; n_shards = 0 or a NULL costs_dev / idx_dev /
+ * out_idx_dev is SSYM_E_INVALID with nothing written; out_cost_dev may be NULL. */
 SSYM_API int32_t ssym_merge_shards(ssym_ctx *ctx, uint32_t n_shards, uint32_t n_targets,
                           const double *costs_dev, const uint32_t *idx_dev, uint32_t *out_idx_dev,
                           double *out_cost_dev);
 /* The same for matches made with per-target distances (morph_to, src/sound.rs:440-446): the shards
  * folded on |cost - distance|, so the merge does too.  `distance`: n_targets f64 in HOST memory, or
  * NULL (= ssym_merge_shards).  dtw costs only: refcos shards report the key itself, which
- * ssym_merge_shards already compares correctly. */
+ * ssym_merge_shards already compares correctly.
+ * Between ssym_match_begin and ssym_match_finish on the same context: a merge without distances leaves the pending
+ * step alone.  A merge WITH distances uploads them to where a begin with per-target distances keeps its own for the
+ * filter's finish, so it ends such a pair (ssym_match_finish then fails with "without ssym_match_begin"); it never lets
+ * finish return an answer for other distances. */
 SSYM_API int32_t ssym_merge_shards_at(ssym_ctx *ctx, uint32_t n_shards, uint32_t n_targets,
                              const double *costs_dev, const uint32_t *idx_dev, const double *distance,
                              uint32_t *out_idx_dev, double *out_cost_dev);
@@ -420,7 +433,16 @@ SSYM_API int32_t ssym_samples_destroy(ssym_ctx *ctx, ssym_samples *s);
  *   out_samples  nullable, out_offsets[n] f64 (HOST)
  *   out_pcm32    nullable, out_offsets[n] i32 (HOST): Sound::write_file's conversion
  *                `(i32::MAX as f64 * sample) as i32` (src/sound.rs:139; truncating, saturating,
- *                NaN -> 0) */
+ *                NaN -> 0)
+ * Samples are copied bit for bit (-0.0 and NaN payloads included); padding is +0.0.  A target or a sound of length 0,
+ * repeated indices and any n_targets are fine.  n_targets = 0, out_offsets[n] = 0 or both outputs NULL: SSYM_OK, nothing
+ * written.  NULL s / idx / out_offsets, out_offsets[0] != 0, decreasing offsets, an index >= n_sounds (SSYM_NO_MATCH
+ * included): SSYM_E_INVALID; a store of no sounds: SSYM_E_EMPTY_DICT -- all before device memory is touched, with the
+ * outputs unwritten.  ssym_samples_create: NULL or non-zero-based or decreasing offsets, NULL samples with a non-zero
+ * total: SSYM_E_INVALID and *out = NULL; n_sounds = 0 succeeds.
+ * Between ssym_match_begin and ssym_match_finish on the same context: neither call keeps or disturbs anything the
+ * pending step needs (ssym_reconstruct stages in scratch that finish fills afresh, ssym_samples_create allocates its
+ * own), so the pair goes on and ssym_match_finish returns what the uninterrupted sequence returns, bit for bit.  */
 SSYM_API int32_t ssym_reconstruct(ssym_ctx *ctx, const ssym_samples *s, const uint32_t *idx,
                          const uint64_t *out_offsets, uint32_t n_targets, double *out_samples,
                          int32_t *out_pcm32);

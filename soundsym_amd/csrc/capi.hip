@@ -1310,6 +1310,11 @@ int32_t ssym_merge_shards_at(ssym_ctx *ctx, uint32_t n_shards, uint32_t n_target
     StageScope stageScope(ctx);
     const double *distDev = nullptr;
     if (distance && n_targets) {
+        // ctx->dist is where a begin with per-target distances left them for its finish: that pair ends here
+        // (finish then reports "without begin"); a begin without distances, or one whose finish is a plain match, is
+        // not touched
+        if (ctx->pending.valid && ctx->pending.filter && ctx->pending.has_dist)
+            ctx->pending.valid = false;
         int32_t rc = ensure(ctx, ctx->dist, sizeof(double) * n_targets);
         if (rc == SSYM_OK)
             rc = stage_h2d(ctx, ctx->dist.ptr, distance, sizeof(double) * n_targets);

@@ -579,7 +579,8 @@ __global__ __launch_bounds__(128) void fold_final_topk_kernel(const uint32_t *__
 }
 
 // Source-sharded multi-GPU merge: smallest cost, lowest global index
-// on equal cost.  Shards are ordered by index, so this is the same first-minimum rule.
+// on equal cost.  Shards are ordered by index, so this is the same first-minimum rule.  The fold is seeded with
+// shard 0's entry; a column whose keys are all NaN keeps it.
 __global__ void merge_shards_kernel(uint32_t nShards, uint32_t nTgt, const double *__restrict__ costs,
                                     const uint32_t *__restrict__ idx, const double *__restrict__ dist,
                                     uint32_t *__restrict__ outIdx, double *__restrict__ outCost,
@@ -596,7 +597,8 @@ __global__ void merge_shards_kernel(uint32_t nShards, uint32_t nTgt, const doubl
         const double c = costs[g * costStride + t];
         const double k = fabs(c - d);
         const uint32_t i = idx[g * idxStride + t];
-        if (k < bk || (k == bk && i < bi)) {
+        // (a NaN key held from shard 0 gives way to the first key that is not NaN: NaN never wins, src/sound.rs:362)
+        if (k < bk || (k == bk && i < bi) || (bk != bk && k == k)) {
             bc = c;
             bk = k;
             bi = i;
