@@ -180,7 +180,10 @@ SSYM_API int32_t ssym_queries_destroy(ssym_ctx *ctx, ssym_queries *q);
  *   out_cost    nullable, n_targets f64: refcos -> the winning |sim - distance| (the reference's
  *               discarded `min_distance`, src/sound.rs:361-368); dtw -> the winner's DTW cost.
  *               When nothing beats the fold start the index is 0 (+ index_base) and the value is
- *               the fold start (2.0 / +inf), as in src/sound.rs:361-367.
+ *               the fold start (2.0 / +inf), as in src/sound.rs:361-367.  A target whose `distance` entry is NaN
+ *               or infinite is such a target on either metric: every key is NaN or +inf and none is below the
+ *               fold start, so it gets index 0 (+ index_base) and 2.0 / +inf.  So is a refcos target whose
+ *               distance lies 2.0 or more from every similarity (1e301, say).
  *   flags       SSYM_OUT_DEVICE, SSYM_DTW_FORCE_EXACT
  * Returns after the results are written (the stream is synchronised). */
 SSYM_API int32_t ssym_match_queries(ssym_ctx *ctx, const ssym_dict *dict, const ssym_queries *q,
@@ -195,7 +198,12 @@ SSYM_API int32_t ssym_match_queries(ssym_ctx *ctx, const ssym_dict *dict, const 
  * finite cost in dtw; NaN keys never enter, as in src/sound.rs:362).  When fewer than k entries
  * qualify the rest of the row is SSYM_NO_MATCH with cost NaN.  out_cost as in ssym_match_queries
  * (refcos: the key |sim - distance|; dtw: the cost).  1 <= k <= SSYM_TOPK_MAX.  dtw results are
- * those of an exact f64 evaluation of every pair, as for k = 1. */
+ * those of an exact f64 evaluation of every pair, as for k = 1.
+ * index_base is added to the entries that name a dictionary entry and to nothing else: a missing entry is
+ * SSYM_NO_MATCH itself whatever the base.  A NaN or infinite `distance` entry leaves nothing below the fold start
+ * for its target, so for k > 1 the whole row is SSYM_NO_MATCH / NaN.  k = 1 IS ssym_match_queries, outputs
+ * included: such a target then has index 0 + index_base and the fold start, not a missing entry.  Equal keys from
+ * either side of a distance (sim_1 - d = d - sim_2) are ordered by index like any other tie. */
 #define SSYM_TOPK_MAX 64u
 #define SSYM_NO_MATCH 0xffffffffu
 SSYM_API int32_t ssym_match_topk(ssym_ctx *ctx, const ssym_dict *dict, const ssym_queries *q,
@@ -287,9 +295,11 @@ SSYM_API int32_t ssym_dtw_align(ssym_ctx *ctx, const ssym_dict *dict, const ssym
  * dict / q / distance must stay alive between the two calls; flags as for ssym_match_queries.
  * Any other matching call on the context in between (it would use the same scratch) ends the pair:
  * ssym_match_finish then fails with "without ssym_match_begin".
- * Where the filter does not apply (refcos, shapes outside its limits) begin writes +inf and finish
- * is a plain ssym_match_queries, so callers need no second code path.  With one rank, or without
- * the all-reduce, the pair is equivalent to ssym_match_queries. */
+ * Where the filter does not apply (refcos, shapes outside its limits, features that are not finite, frames
+ * wider than the filter's 42 values together with per-target distances) begin writes +inf and finish is a
+ * plain ssym_match_queries -- for the distances and the index_base GIVEN TO BEGIN: begin keeps its own copy of
+ * them, and a later begin (with other distances, or without any) replaces them.  So callers need no second
+ * code path.  With one rank, or without the all-reduce, the pair is equivalent to ssym_match_queries. */
 SSYM_API int32_t ssym_match_begin(ssym_ctx *ctx, const ssym_dict *dict, const ssym_queries *q,
                          const double *distance, uint32_t index_base, double *bounds_dev);
 SSYM_API int32_t ssym_match_finish(ssym_ctx *ctx, const double *bounds_dev, uint32_t *out_idx,
