@@ -33,6 +33,7 @@ pub const SSYM_DTYPE_F64: i32 = 0;       // Sound::mfccs() is Vec<f64>
 pub const SSYM_DTYPE_F32: i32 = 1;
 
 pub const SSYM_OUT_DEVICE: u32 = 1;
+pub const SSYM_WARP_MAP_DEVICE: u32 = 32;
 pub const SSYM_DTW_FORCE_EXACT: u32 = 2;
 pub const SSYM_DTW_PRUNE: u32 = 4;
 pub const SSYM_MFCC_PAD_TAIL: u32 = 4;
@@ -164,6 +165,12 @@ extern "C" {
     pub fn ssym_samples_destroy(ctx: *mut SsymCtx, s: *mut SsymSamples) -> i32;
     pub fn ssym_reconstruct(ctx: *mut SsymCtx, s: *const SsymSamples, idx: *const u32, out_offsets: *const u64,
                             n_targets: u32, out_samples: *mut f64, out_pcm32: *mut i32) -> i32;
+    // warped reconstruction: every match resynthesised along ssym_dtw_align's target-frame -> source-frame map
+    // (overlap-add of Hann-windowed source frames); flags: SSYM_OUT_DEVICE, SSYM_WARP_MAP_DEVICE (frame_map and pair_len
+    // are device memory: ssym_dtw_align's device out_map / out_len pass straight in)
+    pub fn ssym_reconstruct_warped(ctx: *mut SsymCtx, s: *const SsymSamples, idx: *const u32, out_offsets: *const u64,
+                                   n_targets: u32, frame_map: *const u32, map_offsets: *const u64, map_frames: *const u32,
+                                   pair_len: *const u32, flags: u32, out_samples: *mut f64, out_pcm32: *mut i32) -> i32;
 
     // feature front-end (own MFCC definition -- parity with vox_box unpinned)
     pub fn ssym_mfcc_num_frames(n_samples: u64, flags: u32, out_frames: *mut u64) -> i32;

@@ -285,6 +285,53 @@ class SoundDictionary {
         }
         return out;
     }
+    // the reconstruction of the targets with dictionary sound indices[t] warped onto target t's timing: align, then
+    // resynthesise along each frame_map (ssym_dtw_align + ssym_reconstruct_warped; dtw contexts; the crate has no
+    // counterpart).  One stretch of targets[t]->samples().size() samples per target, concatenated; a pair without a
+    // finite cost takes clone_from_dictionary's length fit.  (The mirror holds no device memory of its own, so the
+    // maps pass through the host here; a caller with device buffers hands ssym_dtw_align's SSYM_OUT_DEVICE outputs
+    // to ssym_reconstruct_warped with SSYM_WARP_MAP_DEVICE.)
+    std::vector<double> warp(const std::vector<ArcSound> &targets, const std::vector<uint32_t> &indices) const
+    {
+        if (sounds.empty())
+            throw EmptyDictionary();
+        const uint32_t n = (uint32_t)targets.size();
+        std::vector<double> flat;
+        std::vector<uint64_t> off;
+        pack_features(targets, flat, off);
+        ssym_queries *q = nullptr;
+        ctx_->check(ssym_queries_create(ctx_->get(), flat.data(), off.data(), n, (uint32_t)NCOEFFS, &q));
+        std::vector<uint64_t> poff(n + 1), moff(n + 1), ooff(n + 1, 0), soff(sounds.size() + 1, 0);
+        std::vector<double> cost(n), samples, out;
+        std::vector<uint32_t> len(n), path, map, frames(n);
+        int32_t rc = indices.size() == n ? ssym_dtw_align_sizes(resident(), q, indices.data(), nullptr, n, 0, poff.data(),
+                                                                moff.data())
+                                         : (int32_t)SSYM_E_INVALID;
+        if (rc == SSYM_OK) {
+            path.resize(2 * poff[n]);
+            map.resize(moff[n]);
+            rc = ssym_dtw_align(ctx_->get(), resident(), q, indices.data(), nullptr, n, 0, cost.data(), len.data(),
+                                poff.data(), path.data(), moff.data(), map.data(), 0);
+        }
+        ssym_queries_destroy(ctx_->get(), q);
+        ctx_->check(rc);
+        for (std::size_t i = 0; i < sounds.size(); ++i) {
+            samples.insert(samples.end(), sounds[i]->samples().begin(), sounds[i]->samples().end());
+            soff[i + 1] = samples.size();
+        }
+        for (uint32_t t = 0; t < n; ++t) {
+            ooff[t + 1] = ooff[t] + targets[t]->samples().size();
+            frames[t] = (uint32_t)(moff[t + 1] - moff[t]);
+        }
+        ssym_samples *smp = nullptr;
+        ctx_->check(ssym_samples_create(ctx_->get(), samples.data(), soff.data(), (uint32_t)sounds.size(), &smp));
+        out.resize(ooff[n]);
+        rc = ssym_reconstruct_warped(ctx_->get(), smp, indices.data(), ooff.data(), n, map.data(), moff.data(),
+                                     frames.data(), len.data(), 0, out.data(), nullptr);
+        ssym_samples_destroy(ctx_->get(), smp);
+        ctx_->check(rc);
+        return out;
+    }
     // from_distances' chain of at_distance calls, on the device in one call (ssym_chain)
     std::vector<uint32_t> chain_indices(const Sound &start, const std::vector<double> &distances) const
     {

@@ -457,6 +457,46 @@ SSYM_API int32_t ssym_reconstruct(ssym_ctx *ctx, const ssym_samples *s, const ui
                          const uint64_t *out_offsets, uint32_t n_targets, double *out_samples,
                          int32_t *out_pcm32);
 
+/* Warped reconstruction (DESIGN.md section 2 "Warped reconstruction" and section 5.13): ssym_reconstruct with every
+ * match resynthesised along a target-frame -> source-frame map, so that it follows the target's timing instead of being
+ * cut off or padded.  The map is what ssym_dtw_align returns as out_map.  The reference has no counterpart: it never
+ * warps.  Definition, with HOP = 256, BIN = 1024 and the MFCC window w[m] = 0.5 - 0.5 cos(2 pi m / 1024) (built on the
+ * host with libm cos), for target t with n = out_offsets[t+1] - out_offsets[t] output samples, x[0 .. sLen) the samples of
+ * dictionary sound idx[t], F = map_frames[t] and map[0 .. F) = frame_map[map_offsets[t] ..], any u32 values:
+ *   Taps.  Output sample k < n has the taps j (target frames) with j * HOP <= k < j * HOP + BIN and j < F: at most four,
+ *   visited in ascending j.  m = k - j * HOP; p = map[j] * HOP + m in 64-bit arithmetic; the tap is valid when p < sLen.
+ *   Value.  num = sum of w[m] * x[p], den = sum of w[m] over the valid taps, both sums starting from +0.0, every product
+ *   and every sum rounded separately in f64 (no contraction).  out[k] = num / den (IEEE division) when den > 0, else
+ *   +0.0.  A tap whose source sample does not exist drops out of both sums, so a match does not fade where its look-ahead
+ *   frames run past its own samples.  (Non-finite samples give NaN with an unspecified payload.)
+ *   Fallback.  A target with F = 0, or with pair_len[t] = 0, takes ssym_reconstruct's length fit, bit for bit.
+ *   out_pcm32 is ssym_reconstruct's conversion applied to out[k].
+ * Plain overlap-add: repeated source frames can comb; no waveform-similarity search, no phase handling.
+ *   idx, out_offsets   as for ssym_reconstruct (HOST)
+ *   frame_map          u32 source frame per target frame (HOST; nullable when every map_frames[t] is 0)
+ *   map_offsets        n_targets + 1 u64 (HOST): target t's map starts at frame_map[map_offsets[t]]; non-decreasing, with
+ *                      map_offsets[t+1] - map_offsets[t] >= map_frames[t] (the offsets given to ssym_dtw_align)
+ *   map_frames         n_targets u32 (HOST): the target's frame count (0: length fit)
+ *   pair_len           nullable, n_targets u32 (HOST): ssym_dtw_align's out_len; 0 = no finite path, the length fit --
+ *                      the map slot of such a pair is never read
+ *   flags              SSYM_WARP_MAP_DEVICE: frame_map and pair_len are device memory, so ssym_dtw_align's device out_map
+ *                      and out_len pass straight in.  No map content can cause an out-of-range read, so a device map
+ *                      needs no validation.  SSYM_OUT_DEVICE: out_samples and out_pcm32 are device memory
+ *   out_samples, out_pcm32   nullable, out_offsets[n] f64 / i32 (HOST, or device with SSYM_OUT_DEVICE)
+ * n_targets = 0, out_offsets[n] = 0 or both outputs NULL: SSYM_OK, nothing written.  NULL s / idx / out_offsets /
+ * map_offsets / map_frames, a NULL frame_map while some map_frames[t] > 0, out_offsets[0] != 0, decreasing out_offsets or
+ * map_offsets, map_offsets[t+1] - map_offsets[t] < map_frames[t], an index >= n_sounds, unknown flag bits:
+ * SSYM_E_INVALID; a store of no sounds: SSYM_E_EMPTY_DICT -- all with a message in ssym_last_error, before device memory
+ * is touched and with the outputs unwritten.  One synchronisation per call; ssym_get_timings reports the synthesis kernel
+ * alone.  The call stages in the scratch ssym_reconstruct uses, so it may run between ssym_match_begin and
+ * ssym_match_finish as that call may. */
+#define SSYM_WARP_MAP_DEVICE 32u
+SSYM_API int32_t ssym_reconstruct_warped(ssym_ctx *ctx, const ssym_samples *s, const uint32_t *idx,
+                                         const uint64_t *out_offsets, uint32_t n_targets, const uint32_t *frame_map,
+                                         const uint64_t *map_offsets, const uint32_t *map_frames,
+                                         const uint32_t *pair_len, uint32_t flags, double *out_samples,
+                                         int32_t *out_pcm32);
+
 /* Feature front-end, the step before the hot path: what
  * Sound::from_samples(.., None, ..) computes through analyze_mfccs (src/sound.rs:215-242) --
  * 1024-sample Hanning windows hopped by 256 (src/lib.rs:24-25), per window `n_coeffs` MFCCs between

@@ -33,6 +33,7 @@ DTYPE_F32 = 1
 OUT_DEVICE = 1
 DTW_FORCE_EXACT = 2
 DTW_PRUNE = 4
+WARP_MAP_DEVICE = 32       # SSYM_WARP_MAP_DEVICE
 
 # every symbol include/soundsym_amd.h declares (tests check the library exports all of them)
 ABI_SYMBOLS = [
@@ -55,6 +56,7 @@ ABI_SYMBOLS = [
     "ssym_stream_read", "ssym_stream_frames_device", "ssym_stream_samples_device", "ssym_stream_descriptors",
     "ssym_stream_reset",
     "ssym_dtw_align_sizes", "ssym_dtw_align",
+    "ssym_reconstruct_warped",
 ]
 COMM_ID_BYTES = 128        # SSYM_COMM_ID_BYTES
 
@@ -254,6 +256,8 @@ def lib() -> ctypes.CDLL:
     L.ssym_samples_destroy.argtypes = [vp, vp]
     L.ssym_reconstruct.restype = i32
     L.ssym_reconstruct.argtypes = [vp, vp, vp, vp, u32, vp, vp]
+    L.ssym_reconstruct_warped.restype = i32
+    L.ssym_reconstruct_warped.argtypes = [vp, vp, vp, vp, u32, vp, vp, vp, vp, u32, vp, vp]
     L.ssym_comm_unique_id.restype = i32
     L.ssym_comm_unique_id.argtypes = [vp]
     L.ssym_comm_create.restype = i32

@@ -26,7 +26,7 @@ from typing import List, Optional, Sequence
 
 import numpy as np
 
-from ._native import NO_MATCH, EmptyDictionaryError
+from ._native import NO_MATCH, SSYM_E_UNSUPPORTED, EmptyDictionaryError, SsymError
 from .engine import Engine, pack_segments, pitch_lags
 
 NCOEFFS = 12   # src/lib.rs:22
@@ -520,6 +520,38 @@ class SoundDictionary:
             q.close()
         return [Alignment(cost[t], paths[t], maps[t], int(indices[t])) for t in range(len(targets))]
 
+    def warp(self, targets: Sequence[Sound], indices=None, want_pcm32: bool = False):
+        """The reconstruction of the targets with every match warped onto its target's timing (dtw engines): match
+        (unless indices[t] names the dictionary sound of target t), align with the outputs left on the device, and
+        resynthesise along the maps -- ssym_match_queries, ssym_dtw_align, ssym_reconstruct_warped; the maps never
+        visit the host.  Returns the concatenated samples, one stretch of len(target.samples()) per target (with
+        want_pcm32 also their 32-bit conversion).  A target without a finite alignment takes the length fit of
+        reconstruct_from_dictionary."""
+        if not self.sounds:
+            raise EmptyDictionaryError(-2, "empty dictionary")
+        if getattr(self.engine, "metric", None) != "dtw":
+            raise SsymError(SSYM_E_UNSUPPORTED, "warp follows dtw alignments: a refcos engine has none")
+        targets = list(targets)
+        if indices is not None:
+            indices = np.asarray(indices, dtype=np.int64).reshape(-1)
+            if indices.size != len(targets):
+                raise ValueError("indices must name one dictionary sound per target")
+            if indices.size and (indices.min() < 0 or indices.max() >= len(self.sounds)):
+                raise ValueError("an index is outside the dictionary")
+        if not targets:
+            return (np.zeros(0), np.zeros(0, dtype=np.int32)) if want_pcm32 else np.zeros(0)
+        flat, off = pack_segments([t.mfccs() for t in targets], self._dim(), self.engine.np_dtype)
+        out_off = np.concatenate([[0], np.cumsum([t.samples().size for t in targets])]).astype(np.uint64)
+        q = self.engine.queries(flat, off, self._dim())
+        try:
+            if indices is None:
+                indices, _ = self.engine.match(self.resident(), q)
+            _, lengths, _, maps, _, m_off = self.engine.dtw_align_device(self.resident(), q, indices)
+            return self.engine.reconstruct_warped(self.resident_samples(), indices, out_off, maps, m_off,
+                                                  np.diff(m_off.astype(np.int64)), lengths, want_pcm32)
+        finally:
+            q.close()
+
     def candidates(self, targets: Sequence[Sound], k: int, distances=None) -> List[List[Sound]]:
         """The k best dictionary sounds per target, best first: what k
         successive at_distance calls (src/sound.rs:351) would return if each winner were removed."""
@@ -650,6 +682,13 @@ class SoundSequence:
         lens = np.array([s.samples().size for s in self._sounds], dtype=np.uint64)
         out_off = np.concatenate([[0], np.cumsum(lens)]).astype(np.uint64)
         return dict_.engine.reconstruct(dict_.resident_samples(), idx, out_off, want_pcm32)
+
+    def reconstruct_warped_from_dictionary(self, dict_: "SoundDictionary", want_pcm32: bool = False):
+        """reconstruct_from_dictionary with every match warped onto its target's timing instead of cut off or padded
+        (SoundDictionary.warp: match, align, resynthesise along the alignment, all on the GPU; dtw engines)."""
+        if not self._sounds:
+            return (np.zeros(0), np.zeros(0, dtype=np.int32)) if want_pcm32 else np.zeros(0)
+        return dict_.warp(self._sounds, None, want_pcm32)
 
     def to_sound(self) -> Sound:                                        # src/sound.rs:475-483
         parts = [s.samples() for s in self._sounds]

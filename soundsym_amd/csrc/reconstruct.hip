@@ -9,13 +9,6 @@
 
 #include <new>
 
-struct ssym_samples {
-    double *samples = nullptr;
-    uint64_t *off = nullptr;
-    uint32_t n = 0;
-    uint64_t total = 0;
-};
-
 namespace ssym {
 
 // one workgroup per (target, 4096-sample chunk)

@@ -213,6 +213,14 @@ struct ssym_queries {
     ssym::SegmentSet set;
 };
 
+// the dictionary sounds' samples (reconstruct.hip creates and frees them; warp.hip reads them)
+struct ssym_samples {
+    double *samples = nullptr;      // device, [total]
+    uint64_t *off = nullptr;        // device, [n + 1] sample offsets
+    uint32_t n = 0;
+    uint64_t total = 0;
+};
+
 namespace ssym {
 
 #define SSYM_HIP_CHECK(ctx, call)                                                         \

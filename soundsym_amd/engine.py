@@ -43,6 +43,64 @@ def _align_indices(src_idx, tgt_idx):
     return src, tgt
 
 
+def _device_words(x, what: str):
+    """(pointer, count) of 32-bit words in device memory: a torch CUDA tensor of a 4-byte integer type, or a
+    DeviceFrames-style object (data_ptr / numel) whose owner vouches for the content."""
+    size = getattr(x, "element_size", None)
+    if callable(size) and size() != 4:
+        raise ValueError(f"{what}: a device tensor of 32-bit integers is needed")
+    contiguous = getattr(x, "is_contiguous", None)
+    if callable(contiguous) and not contiguous():
+        raise ValueError(f"{what}: the device tensor must be contiguous")
+    n = int(x.numel())
+    return (int(x.data_ptr()) if n else None), n
+
+
+def _warp_inputs(idx, out_offsets, maps, map_offsets, map_frames, pair_len):
+    """The arguments of reconstruct_warped, checked on the host before anything reaches the device.  Returns (idx u32
+    [n], out_offsets u64 [n + 1], map_offsets u64 [n + 1], map_frames u32 [n], map pointer, pair_len pointer, maps on
+    the device?, objects to keep alive for the call)."""
+    idx = np.ascontiguousarray(idx, dtype=np.uint32).reshape(-1)
+    n = idx.size
+    off = np.ascontiguousarray(out_offsets, dtype=np.uint64).reshape(-1)
+    m_off = np.ascontiguousarray(map_offsets, dtype=np.uint64).reshape(-1)
+    frames = np.ascontiguousarray(map_frames, dtype=np.uint32).reshape(-1)
+    if off.size != n + 1 or m_off.size != n + 1 or frames.size != n:
+        raise ValueError("reconstruct_warped: n + 1 out_offsets, n + 1 map_offsets and n map_frames for n indices")
+    if off[0] != 0 or np.any(off[1:] < off[:-1]):
+        raise ValueError("reconstruct_warped: out_offsets must start at 0 and not decrease")
+    if np.any(m_off[1:] < m_off[:-1]) or np.any(m_off[1:] - m_off[:-1] < frames):
+        raise ValueError("reconstruct_warped: map_offsets must not decrease and must leave map_frames[t] entries per target")
+    need = int(m_off[-1]) if frames.any() else 0
+    device = _is_device_tensor(maps) or (maps is None and _is_device_tensor(pair_len))
+    keep = [maps, pair_len]
+    if device:
+        map_ptr, have = _device_words(maps, "maps") if maps is not None else (None, 0)
+        len_ptr = None
+        if pair_len is not None:
+            if not _is_device_tensor(pair_len):
+                raise ValueError("reconstruct_warped: maps in device memory need pair_len in device memory too")
+            len_ptr, have_len = _device_words(pair_len, "pair_len")
+            if have_len < n:
+                raise ValueError("reconstruct_warped: pair_len holds fewer than n entries")
+    else:
+        if _is_device_tensor(pair_len):
+            raise ValueError("reconstruct_warped: pair_len in device memory needs maps in device memory too")
+        host = np.ascontiguousarray(maps if maps is not None else [], dtype=np.uint32).reshape(-1)
+        have, map_ptr = host.size, (host.ctypes.data if host.size else None)
+        len_ptr = None
+        keep.append(host)
+        if pair_len is not None:
+            plen = np.ascontiguousarray(pair_len, dtype=np.uint32).reshape(-1)
+            if plen.size != n:
+                raise ValueError("reconstruct_warped: pair_len must hold one entry per target")
+            len_ptr = plen.ctypes.data if n else None
+            keep.append(plen)
+    if have < need:
+        raise ValueError(f"reconstruct_warped: maps holds {have} entries, map_offsets asks for {need}")
+    return idx, off, m_off, frames, map_ptr, len_ptr, device, keep
+
+
 class _Handle:
     def __init__(self, engine: "Engine", ptr: int, n: int, dim: int, kind: str):
         self.engine, self.ptr, self.n, self.dim, self.kind = engine, ptr, n, dim, kind
@@ -600,6 +658,26 @@ class Engine:
             maps = [fmap[int(m_off[p]):int(m_off[p + 1])] if length[p] else fmap[0:0] for p in range(n)]
         return cost, length, paths, maps
 
+    def dtw_align_device(self, d: _Handle, q: _Handle, src_idx, tgt_idx=None, index_base: int = 0):
+        """ssym_dtw_align with SSYM_OUT_DEVICE: the outputs stay in device memory (torch tensors; torch only owns the
+        memory).  Returns (cost f64 [n], lengths i32 [n], paths i32 [cells * 2], maps i32 [map entries], path_offsets,
+        map_offsets); the 32-bit tensors hold the call's u32 values.  maps, lengths and map_offsets are what
+        reconstruct_warped takes."""
+        import torch
+        src, tgt = _align_indices(src_idx, tgt_idx)
+        n = src.size
+        p_off, m_off = self.dtw_align_sizes(d, q, src, tgt, index_base)
+        dev = torch.device("cuda", self.device)
+        cost = torch.empty(max(n, 1), dtype=torch.float64, device=dev)
+        length = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
+        path = torch.empty(max(2 * int(p_off[-1]), 1), dtype=torch.int32, device=dev)
+        fmap = torch.empty(max(int(m_off[-1]), 1), dtype=torch.int32, device=dev)
+        nat.check(nat.lib().ssym_dtw_align(self.ctx, d.ptr, q.ptr, src.ctypes.data,
+                                           tgt.ctypes.data if tgt is not None else None, n, index_base, cost.data_ptr(),
+                                           length.data_ptr(), p_off.ctypes.data, path.data_ptr(), m_off.ctypes.data,
+                                           fmap.data_ptr(), nat.OUT_DEVICE), self.ctx)
+        return cost[:n], length[:n], path[:2 * int(p_off[-1])], fmap[:int(m_off[-1])], p_off, m_off
+
     # -- feature front-end (F3) --------------------------------------------------------------
     def mfcc(self, samples, sample_rate: float, ncoeffs: int = 12, f_lo: float = 100.0, f_hi: float = 8000.0,
              pad_tail: bool = False, want_mean: bool = False):
@@ -845,6 +923,28 @@ class Engine:
         nat.check(nat.lib().ssym_reconstruct(self.ctx, smp.ptr, idx.ctypes.data, off.ctypes.data, idx.size,
                                              out.ctypes.data, pcm.ctypes.data if pcm is not None else None),
                   self.ctx)
+        return (out, pcm) if want_pcm32 else out
+
+    def reconstruct_warped(self, smp, idx, out_offsets, maps, map_offsets, map_frames, pair_len=None,
+                           want_pcm32: bool = False):
+        """ssym_reconstruct_warped: the matched sounds resynthesised along target-frame -> source-frame maps
+        (definition in include/soundsym_amd.h), concatenated.  maps: u32 source frame per target frame, target t from
+        map_offsets[t] on, map_frames[t] of them; pair_len: optional, 0 marks a target that takes reconstruct's
+        length fit (dtw_align's lengths).  maps and pair_len are numpy arrays, or both device memory (torch CUDA
+        tensors of a 32-bit integer type, DeviceFrames-style pointers): dtw_align_device's maps and lengths pass
+        straight in.  dtw engines only."""
+        if self.metric != "dtw":
+            raise nat.SsymError(nat.SSYM_E_UNSUPPORTED, "reconstruct_warped follows dtw alignments: a refcos engine has none")
+        idx, off, m_off, frames, map_ptr, len_ptr, device, keep = _warp_inputs(idx, out_offsets, maps, map_offsets,
+                                                                               map_frames, pair_len)
+        total = int(off[-1])
+        out = np.zeros(total, dtype=np.float64)
+        pcm = np.zeros(total, dtype=np.int32) if want_pcm32 else None
+        nat.check(nat.lib().ssym_reconstruct_warped(self.ctx, smp.ptr, idx.ctypes.data, off.ctypes.data, idx.size,
+                                                    map_ptr, m_off.ctypes.data, frames.ctypes.data, len_ptr,
+                                                    nat.WARP_MAP_DEVICE if device else 0, out.ctypes.data,
+                                                    pcm.ctypes.data if pcm is not None else None), self.ctx)
+        del keep
         return (out, pcm) if want_pcm32 else out
 
     def merge_shards(self, costs, idx, out_idx, out_cost, distance=None) -> None:

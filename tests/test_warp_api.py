@@ -1,0 +1,122 @@
+"""The warped-reconstruction interface without a device: the header, the ctypes binding and the Rust declarations name
+the new entry point and flag, the ABI version stands, and the Python argument checks come before any device work."""
+import os
+import re
+import types
+
+import numpy as np
+import pytest
+
+import soundsym_amd
+from soundsym_amd import Engine, SoundDictionary, SoundSequence
+from soundsym_amd import _native as nat
+from soundsym_amd.engine import DeviceFrames, _warp_inputs
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+NAME, FLAG = "ssym_reconstruct_warped", "SSYM_WARP_MAP_DEVICE"
+
+
+def _read(*parts):
+    return open(os.path.join(ROOT, *parts)).read()
+
+
+def test_header_binding_and_rust_name_the_call_and_the_flag(native_lib):
+    header, rust = _read("include", "soundsym_amd.h"), _read("bindings", "rust", "src", "gpu.rs")
+    assert re.search(r"SSYM_API\s+int32_t\s+%s\s*\(" % NAME, header)
+    assert NAME in nat.ABI_SYMBOLS and NAME in soundsym_amd.ABI_SYMBOLS
+    assert re.search(r"pub fn %s\s*\(" % NAME, rust)
+    assert hasattr(native_lib, NAME) and len(getattr(native_lib, NAME).argtypes) == 12
+    value = int(re.search(r"#define\s+%s\s+(\d+)u" % FLAG, header).group(1))
+    assert value == nat.WARP_MAP_DEVICE == int(re.search(r"pub const %s: u32 = (\d+);" % FLAG, rust).group(1))
+    # a bit of its own among the flags a call can meet
+    assert value & (nat.OUT_DEVICE | nat.DTW_FORCE_EXACT | nat.DTW_PRUNE | nat.GMM_STANDARDIZE | nat.PITCH_VOICED) == 0
+    assert "warp(" in _read("include", "soundsym.hpp")
+    assert "warp.hip" in _read("soundsym_amd", "csrc", "Makefile")
+
+
+def test_the_abi_version_stands(native_lib):
+    assert native_lib.ssym_abi_version() == 3 and "#define SSYM_ABI_VERSION 3" in _read("include", "soundsym_amd.h")
+    assert "pub const SSYM_ABI_VERSION: i32 = 3;" in _read("bindings", "rust", "src", "gpu.rs")
+
+
+def test_the_header_carries_the_definition():
+    header = _read("include", "soundsym_amd.h")
+    doc = header[header.index("Warped reconstruction"):header.index("ssym_reconstruct_warped(ssym_ctx")]
+    for phrase in ("HOP = 256", "BIN = 1024", "ascending j", "p < sLen", "den > 0", "+0.0", "length fit", "pair_len",
+                   "SSYM_WARP_MAP_DEVICE", "SSYM_OUT_DEVICE", "SSYM_E_EMPTY_DICT", "One synchronisation"):
+        assert phrase in doc, phrase
+    kernel = _read("soundsym_amd", "csrc", "warp.hip")
+    assert "__dadd_rn" in kernel and "__dmul_rn" in kernel and "__ddiv_rn" in kernel and "atomicAdd" not in kernel
+
+
+def test_a_null_context_is_refused_without_a_device(native_lib):
+    one = np.zeros(2, dtype=np.uint64)
+    assert native_lib.ssym_reconstruct_warped(None, None, None, one.ctypes.data, 1, None, one.ctypes.data, None, None, 0,
+                                              None, None) == nat.SSYM_E_INVALID
+
+
+def test_python_argument_errors_come_before_any_device_work():
+    idx, off = [0, 1], [0, 300, 900]
+    maps, m_off, frames = np.arange(6, dtype=np.uint32), [0, 2, 6], [2, 4]
+    out = _warp_inputs(idx, off, maps, m_off, frames, None)
+    assert out[0].dtype == np.uint32 and out[1].dtype == np.uint64 and out[2].dtype == np.uint64 and out[3].dtype == np.uint32
+    assert out[4] and out[5] is None and out[6] is False
+    assert _warp_inputs(idx, off, maps, m_off, frames, [5, 0])[5]
+    assert _warp_inputs(idx, off, None, [0, 0, 0], [0, 0], None)[4] is None          # no map wanted, none given
+    assert _warp_inputs([], [0], None, [0], [], None)[0].size == 0
+    bad = [
+        dict(out_offsets=[0, 300]),                      # n + 1 offsets
+        dict(out_offsets=[1, 300, 900]),                 # starts at 0
+        dict(out_offsets=[0, 900, 300]),                 # does not decrease
+        dict(map_offsets=[0, 2]),
+        dict(map_offsets=[0, 6, 2]),
+        dict(map_offsets=[0, 1, 6]),                     # room for one frame, two asked
+        dict(map_frames=[2]),
+        dict(maps=np.arange(5, dtype=np.uint32)),        # fewer entries than the offsets reach
+        dict(maps=None),
+        dict(pair_len=[1]),
+        dict(pair_len=DeviceFrames(4096, 2, 1)),         # device lengths with a host map
+        dict(maps=DeviceFrames(4096, 6, 1), pair_len=[1, 1]),
+        dict(maps=DeviceFrames(4096, 5, 1)),             # a device map too short
+    ]
+    for change in bad:
+        args = dict(idx=idx, out_offsets=off, maps=maps, map_offsets=m_off, map_frames=frames, pair_len=None)
+        args.update(change)
+        with pytest.raises(ValueError):
+            _warp_inputs(**args)
+    dev = _warp_inputs(idx, off, DeviceFrames(4096, 6, 1), m_off, frames, DeviceFrames(8192, 2, 1))
+    assert dev[4] == 4096 and dev[5] == 8192 and dev[6] is True
+
+    class Wide:                                          # a device tensor of 8-byte elements
+        is_cuda = True
+
+        def data_ptr(self): return 4096
+
+        def numel(self): return 6
+
+        def element_size(self): return 8
+
+    with pytest.raises(ValueError):
+        _warp_inputs(idx, off, Wide(), m_off, frames, None)
+
+
+def test_a_refcos_engine_and_an_empty_dictionary_are_refused_in_python():
+    refcos = types.SimpleNamespace(metric="refcos")
+    with pytest.raises(nat.SsymError) as err:
+        Engine.reconstruct_warped(refcos, None, [0], [0, 10], None, [0, 0], [0])
+    assert err.value.code == nat.SSYM_E_UNSUPPORTED
+    with pytest.raises(soundsym_amd.EmptyDictionaryError):
+        SoundDictionary(engine=object()).warp([])
+    d = SoundDictionary(engine=refcos)
+    d.sounds.append(object())
+    with pytest.raises(nat.SsymError) as err:
+        d.warp([])
+    assert err.value.code == nat.SSYM_E_UNSUPPORTED
+    # an empty sequence never reaches the dictionary, as reconstruct_from_dictionary
+    out = SoundSequence.new([]).reconstruct_warped_from_dictionary(None)
+    assert out.size == 0 and out.dtype == np.float64
+    out, pcm = SoundSequence.new([]).reconstruct_warped_from_dictionary(None, want_pcm32=True)
+    assert out.size == 0 and pcm.dtype == np.int32
+    for cls, name in ((Engine, "reconstruct_warped"), (Engine, "dtw_align_device"), (SoundDictionary, "warp"),
+                      (SoundSequence, "reconstruct_warped_from_dictionary")):
+        assert hasattr(cls, name)
