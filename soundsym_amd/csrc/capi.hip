@@ -1,4 +1,5 @@
-// capi.hip -- the C ABI of include/soundsym_amd.h on top of the kernels.
+// capi.hip -- the C ABI of include/soundsym_amd.h: handle lifetime, argument checks and the extern "C" wrappers
+// (the search behind the match calls: match.hip).
 #include "ssym_internal.hpp"
 
 #include <algorithm>
@@ -8,10 +9,39 @@
 
 using namespace ssym;
 
-// the tail behind the refcos search's results (refcos_mfma.hip, refcos_pack_tail): header words of its lists + timestamps
-constexpr size_t kTailBytes = 4 * sizeof(uint32_t) + 3 * sizeof(unsigned long long);
-
 static thread_local std::string g_create_err;
+
+static int32_t make_set(ssym_ctx *ctx, SegmentSet &set, const void *feats, bool on_device,
+                        const uint64_t *off, uint32_t n, uint32_t dim, bool is_source)
+{
+    SSYM_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+    int32_t rc = pack_segments(ctx, set, feats, on_device, off, n, dim, is_source);
+    if (rc != SSYM_OK)
+        free_segments(ctx, set);
+    return rc;
+}
+
+// ssym_dict_create* / ssym_queries_create*: a new handle (T: ssym_dict or ssym_queries) with the segments packed
+template <class T>
+static int32_t create_set_handle(ssym_ctx *ctx, const void *feats, bool on_device, const uint64_t *frame_offsets,
+                                 uint32_t n, uint32_t dim, bool is_source, T **out)
+{
+    return guarded(ctx, [&]() -> int32_t {
+    if (!ctx || !out)
+        return SSYM_E_INVALID;
+    *out = nullptr;
+    T *h = new (std::nothrow) T();
+    if (!h)
+        return SSYM_E_NOMEM;
+    int32_t rc = make_set(ctx, h->set, feats, on_device, frame_offsets, n, dim, is_source);
+    if (rc != SSYM_OK) {
+        delete h;
+        return rc;
+    }
+    *out = h;
+    return SSYM_OK;
+    });
+}
 
 extern "C" {
 
@@ -147,54 +177,16 @@ int32_t ssym_get_timings(const ssym_ctx *ctx, ssym_timings *out)
 }
 
 // ---- dictionary / queries -----------------------------------------------------------------------
-static int32_t make_set(ssym_ctx *ctx, SegmentSet &set, const void *feats, bool on_device,
-                        const uint64_t *off, uint32_t n, uint32_t dim, bool is_source)
-{
-    SSYM_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-    int32_t rc = pack_segments(ctx, set, feats, on_device, off, n, dim, is_source);
-    if (rc != SSYM_OK)
-        free_segments(ctx, set);
-    return rc;
-}
-
 int32_t ssym_dict_create(ssym_ctx *ctx, const void *feats, const uint64_t *frame_offsets,
                          uint32_t n_segments, uint32_t dim, ssym_dict **out)
 {
-    return guarded(ctx, [&]() -> int32_t {
-    if (!ctx || !out)
-        return SSYM_E_INVALID;
-    *out = nullptr;
-    ssym_dict *d = new (std::nothrow) ssym_dict();
-    if (!d)
-        return SSYM_E_NOMEM;
-    int32_t rc = make_set(ctx, d->set, feats, false, frame_offsets, n_segments, dim, true);
-    if (rc != SSYM_OK) {
-        delete d;
-        return rc;
-    }
-    *out = d;
-    return SSYM_OK;
-    });
+    return create_set_handle(ctx, feats, false, frame_offsets, n_segments, dim, true, out);
 }
 
 int32_t ssym_dict_create_device(ssym_ctx *ctx, const void *feats_dev, const uint64_t *frame_offsets,
                                 uint32_t n_segments, uint32_t dim, ssym_dict **out)
 {
-    return guarded(ctx, [&]() -> int32_t {
-    if (!ctx || !out)
-        return SSYM_E_INVALID;
-    *out = nullptr;
-    ssym_dict *d = new (std::nothrow) ssym_dict();
-    if (!d)
-        return SSYM_E_NOMEM;
-    int32_t rc = make_set(ctx, d->set, feats_dev, true, frame_offsets, n_segments, dim, true);
-    if (rc != SSYM_OK) {
-        delete d;
-        return rc;
-    }
-    *out = d;
-    return SSYM_OK;
-    });
+    return create_set_handle(ctx, feats_dev, true, frame_offsets, n_segments, dim, true, out);
 }
 
 int32_t ssym_dict_append(ssym_ctx *ctx, ssym_dict *dict, const void *feats,
@@ -236,41 +228,13 @@ int32_t ssym_dict_destroy(ssym_ctx *ctx, ssym_dict *dict)
 int32_t ssym_queries_create(ssym_ctx *ctx, const void *feats, const uint64_t *frame_offsets,
                             uint32_t n_targets, uint32_t dim, ssym_queries **out)
 {
-    return guarded(ctx, [&]() -> int32_t {
-    if (!ctx || !out)
-        return SSYM_E_INVALID;
-    *out = nullptr;
-    ssym_queries *q = new (std::nothrow) ssym_queries();
-    if (!q)
-        return SSYM_E_NOMEM;
-    int32_t rc = make_set(ctx, q->set, feats, false, frame_offsets, n_targets, dim, false);
-    if (rc != SSYM_OK) {
-        delete q;
-        return rc;
-    }
-    *out = q;
-    return SSYM_OK;
-    });
+    return create_set_handle(ctx, feats, false, frame_offsets, n_targets, dim, false, out);
 }
 
 int32_t ssym_queries_create_device(ssym_ctx *ctx, const void *feats_dev, const uint64_t *frame_offsets,
                                    uint32_t n_targets, uint32_t dim, ssym_queries **out)
 {
-    return guarded(ctx, [&]() -> int32_t {
-    if (!ctx || !out)
-        return SSYM_E_INVALID;
-    *out = nullptr;
-    ssym_queries *q = new (std::nothrow) ssym_queries();
-    if (!q)
-        return SSYM_E_NOMEM;
-    int32_t rc = make_set(ctx, q->set, feats_dev, true, frame_offsets, n_targets, dim, false);
-    if (rc != SSYM_OK) {
-        delete q;
-        return rc;
-    }
-    *out = q;
-    return SSYM_OK;
-    });
+    return create_set_handle(ctx, feats_dev, true, frame_offsets, n_targets, dim, false, out);
 }
 
 int32_t ssym_queries_destroy(ssym_ctx *ctx, ssym_queries *q)
@@ -286,35 +250,6 @@ int32_t ssym_queries_destroy(ssym_ctx *ctx, ssym_queries *q)
     });
 }
 
-// ---- the hot path -----------------------------------------------------------------------------------
-static float ev_ms(hipEvent_t a, hipEvent_t b)
-{
-    float ms = 0.f;
-    if (hipEventElapsedTime(&ms, a, b) != hipSuccess)
-        return 0.f;
-    return ms;
-}
-
-static int32_t check_match_args(ssym_ctx *ctx, const ssym_dict *dict, const ssym_queries *q)
-{
-    if (!ctx)
-        return SSYM_E_INVALID;
-    if (!dict || !q) {
-        ctx->err = "dictionary or queries handle is NULL";
-        return SSYM_E_INVALID;
-    }
-    if (dict->set.n == 0) {
-        // the reference indexes sounds[0] of an empty Vec and panics (src/sound.rs:369)
-        ctx->err = "empty dictionary";
-        return SSYM_E_EMPTY_DICT;
-    }
-    if (dict->set.dim != q->set.dim) {
-        ctx->err = "dim mismatch between dictionary and targets";
-        return SSYM_E_INVALID;
-    }
-    return SSYM_OK;
-}
-
 }  // extern "C"
 
 // filter costs live in record-slot coordinates; the caller sees segments in its own order
@@ -328,516 +263,6 @@ __global__ void f32_to_f64_matrix_kernel(const float *__restrict__ in, uint32_t 
         out[(size_t)permRow[r] * cols + permCol[c]] = (double)in[(size_t)r * ld + c];
 }
 
-// per-target values between slot order (inside) and the caller's target order (outside)
-__global__ void slots_to_targets_kernel(const double *__restrict__ bySlot, const uint32_t *__restrict__ perm,
-                                        uint32_t n, double *__restrict__ byTarget)
-{
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n)
-        byTarget[perm[i]] = bySlot[i];
-}
-__global__ void targets_to_slots_kernel(const double *__restrict__ byTarget, const uint32_t *__restrict__ perm,
-                                        uint32_t n, double *__restrict__ bySlot)
-{
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n)
-        bySlot[i] = byTarget[perm[i]];
-}
-
-// k_top = 1: ssym_match_queries (outputs [M]); k_top > 1: ssym_match_topk (outputs [M][k_top]).
-// phase 0: the whole match.  Phases 1 / 2 are ssym_match_begin / ssym_match_finish: phase 1 stops
-// after the filter and the per-target threshold (copied to bounds_dev), phase 2 takes the threshold
-// back from bounds_dev (after the ranks' all-reduce) and runs selection, re-scoring and the fold.
-constexpr uint32_t kFlagFewTargets = 0x80000000u;      // internal: set by ssym_match_batch / ssym_match_one for <= 4 targets
-
-static int32_t match_impl(ssym_ctx *ctx, const ssym_dict *dict, const ssym_queries *q,
-                          const double *distance, uint32_t index_base, uint32_t k_top, uint32_t *out_idx,
-                          double *out_cost, uint32_t flags, int phase = 0, double *bounds_dev = nullptr,
-                          const double *prune_cost_dev = nullptr /* phase 1: reduced candidate costs, by target */)
-{
-    StageScope stageScope(ctx);
-    int32_t rc = check_match_args(ctx, dict, q);
-    if (rc != SSYM_OK)
-        return rc;
-    const SegmentSet &src = dict->set;
-    const SegmentSet &tgt = q->set;
-    const uint32_t N = src.n, M = tgt.n;
-    ssym_timings tm{};
-    tm.n_pairs = (uint64_t)N * M;
-    if (M == 0) {
-        ctx->timings = tm;
-        return SSYM_OK;
-    }
-    if (!out_idx && phase != 1) {
-        ctx->err = "out_idx is NULL";
-        return SSYM_E_INVALID;
-    }
-    SSYM_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-    hipStream_t st = ctx->stream;
-    const bool outDev = (flags & SSYM_OUT_DEVICE) != 0;
-    if (phase != 2)
-        ctx->pipe_mask = 0;            // give-up counters of the exact kernel's pipelined variant: this call's start here
-    if (phase == 0) {
-        // any other call that uses the context's scratch ends a begin .. finish in progress (finish then reports
-        // "without begin") and drops the candidates of ssym_match_candidates: their buffers are shared
-        ctx->pending.cand = false;
-        ctx->pending.valid = false;
-    }
-    if (ctx->prune_default && phase == 0 && M >= 64)      // (a handful of targets: the extra launches cost more than they save)
-        flags |= SSYM_DTW_PRUNE;
-
-    // per-target distance (morph_to, src/sound.rs:440-446)
-    const double *distDev = nullptr;
-    if (phase == 2) {
-        distDev = ctx->pending.has_dist ? (const double *)ctx->dist.ptr : nullptr;   // uploaded by phase 1
-    } else if (distance) {
-        rc = ensure(ctx, ctx->dist, sizeof(double) * M);
-        if (rc != SSYM_OK)
-            return rc;
-        rc = stage_h2d(ctx, ctx->dist.ptr, distance, sizeof(double) * M);
-        if (rc != SSYM_OK)
-            return rc;
-        distDev = (const double *)ctx->dist.ptr;
-    }
-    uint32_t *idxDev = out_idx;
-    double *costDev = out_cost;
-    // refcos with host outputs: values, indices and four header words of the search's lists in ONE device block, so that
-    // one copy brings back everything the call synchronises for (a search of 0.23 ms notices four)
-    const size_t costBytes = sizeof(double) * (size_t)M * k_top;
-    const size_t idxBytes = (sizeof(uint32_t) * (size_t)M * k_top + 7) & ~(size_t)7;      // (the tail's stamps: 8-byte aligned)
-    uint32_t *hdrTail = nullptr;
-    if (!outDev && ctx->metric == SSYM_METRIC_REFCOS) {
-        rc = ensure(ctx, ctx->out_cost, costBytes + idxBytes + kTailBytes);
-        if (rc != SSYM_OK)
-            return rc;
-        costDev = (double *)ctx->out_cost.ptr;
-        idxDev = (uint32_t *)((char *)ctx->out_cost.ptr + costBytes);
-        hdrTail = (uint32_t *)((char *)idxDev + idxBytes);
-    } else if (!outDev) {
-        rc = ensure(ctx, ctx->out_idx, idxBytes);
-        if (rc != SSYM_OK)
-            return rc;
-        rc = ensure(ctx, ctx->out_cost, costBytes);
-        if (rc != SSYM_OK)
-            return rc;
-        idxDev = (uint32_t *)ctx->out_idx.ptr;
-        costDev = (double *)ctx->out_cost.ptr;
-    }
-
-    hipEvent_t *ev = ctx->ev;
-    bool outputsStaged = false;          // host outputs already copied and synchronised (refcos filter path)
-    bool stampsValid = false;            // refcos filter path: phase times from device timestamps instead of events
-    float stampMs[2] = {0.f, 0.f};
-    if (ctx->metric == SSYM_METRIC_REFCOS) {
-        // The plain first-minimum search goes through the f64 matrix pipe (refcos_mfma.hip): every pair's dot as a
-        // GEMM, a rigorous interval per key, and the reference's own arithmetic only on the few pairs that can
-        // hold a target's minimum (top-k: one of its k smallest keys) -- same bits out.  Small problems keep the exact
-        // tile kernel on every pair; so does a call whose candidate list overflowed.
-        // (a sharded step only enqueues: its candidate list's header travels in the gathered status like the dtw
-        //  lists', and the attempt every rank repeats after an overflow -- so_cap set -- takes the exact tile kernel)
-        // Top-k goes that way up to k = 64: the waves' own thresholds (the k-th smallest bound of 64 rows each) only decide
-        // what is LISTED; the threshold that selects the candidates is the k-th smallest bound over all of a target's listed
-        // pairs (refcos_mfma.hip, refcos_topk_*).  4096 x 4096 x 128f x 12d, k = 2 / 4 / 8 / 16 / 64: 0.41 / 0.47 / 0.63 / 0.93 /
-        // 2.9 ms against 3.2 / 3.1 / 3.3 / 3.9 / 7.0 ms on the exact tile kernel (tools/refcos_topk_timing.py).
-        const char *kmaxKnob = ssym_knob("SSYM_REFCOS_TOPK_MAX");                       // (measurements: where the filters stop paying)
-        const uint32_t kFilterMax = kmaxKnob ? (uint32_t)std::max(1, atoi(kmaxKnob)) : 64u;
-        bool viaMfma = !(ctx->stream_only && (ctx->so_cap || k_top > 1)) && k_top <= kFilterMax && refcos_mfma_supported(ctx, src, tgt);
-        ctx->so_refcos = false;
-        // Which filter: the integer one where both sets have its records; should ITS list overflow -- values so close that
-        // 23 bits of fixed point cannot tell them apart -- the f64 filter gets the search before the exact tile kernel does
-        // (a sharded step repeats with the tile kernel at once: one agreed repeat per step).
-        bool q8 = viaMfma && refcos_q8_ready(ctx, src, tgt);
-        // Timing without events: an event record between two kernels costs ~7 us of gap on the stream, three of them a
-        // tenth of a search of 0.2 ms; the search's first kernel, the first one after the main kernel and the last one
-        // read the device's wall clock instead (a sharded step keeps the events: comm.hip reads them).
-        const bool useStamps = !ctx->stream_only && ctx->wall_clock_khz > 0;
-        unsigned long long *stampsDev = nullptr;
-        if (viaMfma && useStamps) {
-            rc = ensure(ctx, ctx->stamps, 128);
-            if (rc != SSYM_OK)
-                return rc;
-            stampsDev = (unsigned long long *)ctx->stamps.ptr;
-        }
-        while (viaMfma) {
-            const uint32_t *h1dev = nullptr, *h2dev = nullptr;
-            uint32_t h1[2] = {0, 0}, h2[2] = {0, 0};
-            if (!stampsDev)
-                SSYM_HIP_CHECK(ctx, hipEventRecord(ev[0], st));
-            // (where the tail goes: behind the host outputs' device block, or -- device outputs -- behind the timestamps)
-            char *packed = (!ctx->stream_only && !outDev && hdrTail) ? stage_take(ctx, costBytes + idxBytes + kTailBytes) : nullptr;
-            uint32_t *tailDev = packed ? hdrTail : (stampsDev ? (uint32_t *)(stampsDev + 4) : nullptr);
-            rc = launch_refcos_match_mfma(ctx, src, tgt, distDev, index_base, idxDev, costDev, &h1dev, &h2dev, k_top, q8, stampsDev,
-                                          tailDev);
-            if (rc == SSYM_E_NOMEM && !ctx->stream_only) {
-                // the filters' lists did not fit (a top-k list of a large grid is a few GB): the exact tile kernel needs
-                // N x M x 8 bytes only and was the path of these calls before the filters took them
-                ctx->err.clear();
-                viaMfma = false;
-                break;
-            }
-            if (rc != SSYM_OK)
-                return rc;
-            tm.refcos_filter = q8 ? 2 : 1;
-            if (!stampsDev)
-                SSYM_HIP_CHECK(ctx, hipEventRecord(ev[2], st));
-            if (ctx->stream_only) {              // ssym_match_sharded reads the headers after the step's one synchronisation
-                ctx->so_hdr1 = h1dev;
-                ctx->so_hdr2 = h2dev;
-                ctx->so_refcos = true;
-                ctx->so_filter = false;
-                tm.used_filter = 1;
-                tm.main_launches = 1;
-                ctx->timings = tm;
-                return SSYM_OK;                  // (device outputs: the sharded step's send block)
-            }
-            // host outputs: results, headers and timestamps come back in one copy and under one synchronisation; should
-            // the list have overflowed the results are dropped and the exact kernel's staged instead
-            const size_t pendingBefore = ctx->pending_d2h.size();
-            unsigned long long tailHost[(kTailBytes + 7) / 8] = {0};
-            const unsigned char *tailAt = nullptr;
-            if (packed) {
-                SSYM_HIP_CHECK(ctx, hipMemcpyAsync(packed, costDev, costBytes + idxBytes + kTailBytes, hipMemcpyDeviceToHost, st));
-                if (out_cost)
-                    ctx->pending_d2h.push_back({out_cost, packed, costBytes});
-                ctx->pending_d2h.push_back({out_idx, packed + costBytes, sizeof(uint32_t) * (size_t)M * k_top});
-                outputsStaged = true;
-                tailAt = (const unsigned char *)packed + costBytes + idxBytes;
-            } else if (stampsDev) {              // device outputs (or no staging window): the tail alone comes back
-                SSYM_HIP_CHECK(ctx, hipMemcpyAsync(tailHost, tailDev, kTailBytes, hipMemcpyDeviceToHost, st));
-                tailAt = (const unsigned char *)tailHost;
-                if (!outDev) {
-                    rc = stage_d2h(ctx, out_idx, idxDev, sizeof(uint32_t) * (size_t)M * k_top);
-                    if (rc == SSYM_OK && out_cost)
-                        rc = stage_d2h(ctx, out_cost, costDev, costBytes);
-                    if (rc != SSYM_OK)
-                        return rc;
-                    outputsStaged = true;
-                }
-            } else {
-                SSYM_HIP_CHECK(ctx, hipMemcpyAsync(h1, h1dev, sizeof(h1), hipMemcpyDeviceToHost, st));
-                SSYM_HIP_CHECK(ctx, hipMemcpyAsync(h2, h2dev, sizeof(h2), hipMemcpyDeviceToHost, st));
-                if (!outDev) {
-                    rc = stage_d2h(ctx, out_idx, idxDev, sizeof(uint32_t) * (size_t)M * k_top);
-                    if (rc == SSYM_OK && out_cost)
-                        rc = stage_d2h(ctx, out_cost, costDev, costBytes);
-                    if (rc != SSYM_OK)
-                        return rc;
-                    outputsStaged = true;
-                }
-            }
-            SSYM_HIP_CHECK(ctx, hipStreamSynchronize(st));
-            if (tailAt) {
-                const uint32_t *t = (const uint32_t *)tailAt;
-                h1[0] = t[0]; h1[1] = t[1]; h2[0] = t[2]; h2[1] = t[3];
-                if (stampsDev) {
-                    unsigned long long ts[3];
-                    memcpy(ts, tailAt + 4 * sizeof(uint32_t), sizeof(ts));
-                    stampMs[0] = (float)((double)(ts[1] - ts[0]) / ctx->wall_clock_khz);       // main kernel (+ its init)
-                    stampMs[1] = (float)((double)(ts[2] - ts[1]) / ctx->wall_clock_khz);       // selection, exact keys, fold
-                    stampsValid = true;
-                }
-            }
-            if (h1[1]) {                     // more near-ties than the list holds
-                ctx->pending_d2h.resize(pendingBefore);
-                outputsStaged = false;
-                if (q8) {
-                    q8 = false;              // ... for the integer filter: the f64 filter next
-                    continue;
-                }
-                viaMfma = false;             // ... for the f64 filter too: the exact kernel on every pair
-                tm.refcos_filter = 0;
-                stampsValid = false;
-            } else {
-                tm.used_filter = 1;
-                tm.n_refined = h2[0];
-            }
-            break;
-        }
-        if (!viaMfma) {
-        rc = ensure(ctx, ctx->cmat, sizeof(double) * (size_t)N * M);
-        if (rc != SSYM_OK)
-            return rc;
-        double *sims = (double *)ctx->cmat.ptr;
-        SSYM_HIP_CHECK(ctx, hipEventRecord(ev[0], st));
-        rc = launch_refcos_sims(ctx, src, tgt, sims);
-        if (rc != SSYM_OK)
-            return rc;
-        SSYM_HIP_CHECK(ctx, hipEventRecord(ev[1], st));
-        rc = launch_refcos_argmin(ctx, N, M, sims, distDev, index_base, k_top, idxDev, costDev);
-        if (rc != SSYM_OK)
-            return rc;
-        SSYM_HIP_CHECK(ctx, hipEventRecord(ev[2], st));
-        }
-        tm.main_launches = 1;          // event times are read after the one synchronisation below
-    } else {
-        // frames wider than the filter's 42 values: the filter scores the first 42 and bounds the cost from
-        // below; that supports the plain first-minimum search (no per-target distances, k = 1)
-        const bool wide = filter_lower_bound_only(ctx, src, tgt);
-        // few short queries against a small dictionary: the exact kernel on every pair is one launch of a few
-        // thousand waves, the filter path a chain of ~20 launches (1 query x 1024 entries of 5...40 frames:
-        // 81 us against 227 us per call; from 16 queries on the filter path is the shorter one)
-        const bool fewPairs = (flags & kFlagFewTargets) && (uint64_t)N * M <= 8192 && src.max_frames + tgt.max_frames <= 128;
-        // (sharded runs on wide frames exchange bounds in cost space: no per-target distances there)
-        const bool useFilter = !(flags & SSYM_DTW_FORCE_EXACT) && !fewPairs && filter_supported(ctx, src, tgt) &&
-                               (!wide || phase == 0 || !(phase == 2 ? ctx->pending.has_dist : distance != nullptr));
-        tm.used_filter = useFilter ? 1 : 0;
-        if (useFilter) {
-            rc = ensure(ctx, ctx->cmat, sizeof(float) * (size_t)src.n_pad * tgt.n_pad);
-            if (rc != SSYM_OK)
-                return rc;
-            float *cmat = (float *)ctx->cmat.ptr;
-            // early abandoning applies to the plain first-minimum search of one unsharded call
-            // (phase 1: the candidates were scored by ssym_match_candidates, their costs reduced over the ranks;
-            //  phase 2: what phase 1 did)
-            const bool prune = phase == 2 ? ctx->pending.pruned
-                                          : (flags & SSYM_DTW_PRUNE) && k_top == 1 && !distDev &&
-                                                (phase == 0 ? true : (prune_cost_dev != nullptr && !wide));
-            if (phase != 2) {
-                SSYM_HIP_CHECK(ctx, hipEventRecord(ev[0], st));
-                const float *abandon = nullptr;
-                unsigned long long *colCtr = nullptr;
-                if (prune) {
-                    rc = phase == 0 ? launch_dtw_prune_candidates(ctx, src, tgt) : SSYM_OK;
-                    if (rc == SSYM_OK)
-                        rc = launch_dtw_prune_thresholds(ctx, src, tgt, prune_cost_dev, &abandon);
-                    if (rc != SSYM_OK)
-                        return rc;
-                    colCtr = (unsigned long long *)((char *)ctx->abandon.ptr + ctx->abandon.bytes) - 1;
-                    rc = zero_words(ctx, colCtr, sizeof(*colCtr));
-                    if (rc != SSYM_OK)
-                        return rc;
-                }
-                SSYM_HIP_CHECK(ctx, hipEventRecord(ev[6], st));
-                rc = launch_dtw_filter(ctx, src, tgt, cmat, abandon, colCtr, prune ? prune_cand_slots(ctx, tgt) : nullptr);
-                if (rc != SSYM_OK)
-                    return rc;
-                SSYM_HIP_CHECK(ctx, hipEventRecord(ev[1], st));
-                if (prune && ctx->stream_only) {     // through the pinned window: a pageable destination would block the host
-                    rc = stage_d2h(ctx, &ctx->pruned_cells, colCtr, sizeof(*colCtr));
-                    if (rc != SSYM_OK)
-                        return rc;
-                } else if (prune) {
-                    SSYM_HIP_CHECK(ctx, hipMemcpyAsync(&ctx->pruned_cells, colCtr, sizeof(*colCtr),
-                                                       hipMemcpyDeviceToHost, st));
-                }
-                rc = wide ? launch_dtw_bounds_partial(ctx, src, tgt, cmat, prune ? (const double *)ctx->prune_cost.ptr : nullptr, k_top, distDev)
-                          : launch_dtw_bounds(ctx, src, tgt, cmat, distDev, k_top,
-                                              prune ? (const double *)ctx->prune_cost.ptr : nullptr);
-                if (rc != SSYM_OK)
-                    return rc;
-            }
-            tm.pruned = prune ? 1 : 0;
-            tm.main_launches = ctx->filter_launches;     // one per class of source lengths (dtw_filter.hip)
-            if (phase == 1) {
-                // hand the threshold out: non-negative doubles (or +inf), bit for bit what stage 1 uses
-                slots_to_targets_kernel<<<(M + 255) / 256, 256, 0, st>>>((const double *)ctx->tmin.ptr, tgt.perm, M,
-                                                                         bounds_dev);
-                SSYM_HIP_CHECK(ctx, hipGetLastError());
-                ctx->pending.pruned = prune;
-                if (ctx->stream_only) {          // ssym_match_sharded: the times are read after the step's one synchronisation
-                    ctx->timings = tm;
-                    return SSYM_OK;
-                }
-                SSYM_HIP_CHECK(ctx, hipStreamSynchronize(st));
-                ctx->pending.main_ms = ev_ms(ev[6], ev[1]);
-                tm.main_ms = ctx->pending.main_ms;
-                ctx->timings = tm;
-                return SSYM_OK;
-            }
-            if (phase == 2) {
-                targets_to_slots_kernel<<<(M + 255) / 256, 256, 0, st>>>(bounds_dev, tgt.perm, M,
-                                                                         (double *)ctx->tmin.ptr);
-                SSYM_HIP_CHECK(ctx, hipGetLastError());
-                SSYM_HIP_CHECK(ctx, hipEventRecord(ev[0], st));
-            }
-            // list 1 (worst-case margin) is a few pairs per target when near-duplicates exist and
-            // ~10^2 when they do not; on overflow stage 1 reports the size it wanted, the later
-            // stages see the flag and do nothing, and the selection is redone with that room
-            // (exactness never depends on the capacity)
-            uint64_t cap = std::max<uint64_t>((256ull + 16ull * (k_top - 1)) * M, 65536);
-            if (ctx->stream_only && ctx->so_cap)
-                cap = ctx->so_cap;               // the size a previous attempt of this step asked for
-            cap = std::min<uint64_t>(cap, (uint64_t)N * M);
-            float sel_ms = 0.f, ref_ms = 0.f, red_ms = 0.f;
-            for (int attempt = 0; attempt < 2; ++attempt) {
-                SSYM_HIP_CHECK(ctx, hipEventRecord(ev[2], st));
-                rc = launch_dtw_select(ctx, src, tgt, cmat, distDev, (uint32_t)cap);          // stage 1
-                if (rc != SSYM_OK)
-                    return rc;
-                uint32_t *hdr1 = (uint32_t *)ctx->cand.ptr;
-                rc = ensure(ctx, ctx->cand_xmin, sizeof(float) * cap);
-                if (rc != SSYM_OK)
-                    return rc;
-                rc = launch_certify(ctx, src, tgt, hdr1, (const uint2 *)(hdr1 + 2), (uint32_t)cap,
-                                    (float *)ctx->cand_xmin.ptr);                               // certificates
-                if (rc != SSYM_OK)
-                    return rc;
-                const uint32_t *knownSrc =
-                    prune ? (const uint32_t *)((const uint2 *)((const uint32_t *)ctx->prune_pairs.ptr + 2) + M) : nullptr;
-                rc = launch_dtw_select2(ctx, src, tgt, cmat, (const float *)ctx->cand_xmin.ptr, distDev,
-                                        (uint32_t)cap, k_top, wide, knownSrc);                  // stage 2
-                if (rc != SSYM_OK)
-                    return rc;
-                SSYM_HIP_CHECK(ctx, hipEventRecord(ev[3], st));
-                rc = ensure(ctx, ctx->cand_cost, sizeof(double) * (cap + M));
-                if (rc != SSYM_OK)
-                    return rc;
-                uint32_t *hdr2 = (uint32_t *)ctx->cand2.ptr;
-                rc = launch_dtw_exact(ctx, src, tgt, (const uint2 *)(hdr2 + 2), hdr2, (uint32_t)cap,
-                                      (double *)ctx->cand_cost.ptr);
-                if (rc != SSYM_OK)
-                    return rc;
-                if (prune) {
-                    rc = launch_prune_append_known(ctx, M);
-                    if (rc != SSYM_OK)
-                        return rc;
-                }
-                SSYM_HIP_CHECK(ctx, hipEventRecord(ev[4], st));
-                rc = launch_dtw_final(ctx, src, tgt, distDev, (uint32_t)(cap + (prune ? M : 0)), index_base, k_top,
-                                      idxDev, costDev);
-                if (rc != SSYM_OK)
-                    return rc;
-                SSYM_HIP_CHECK(ctx, hipEventRecord(ev[5], st));
-                if (ctx->stream_only) {          // one attempt, enqueued only: the caller looks at the headers later
-                    ctx->so_hdr1 = hdr1;
-                    ctx->so_hdr2 = hdr2;
-                    ctx->so_cap = cap;
-                    ctx->so_filter = true;
-                    ctx->timings = tm;
-                    return SSYM_OK;
-                }
-                // ONE synchronisation per attempt: the lists' header words land in the pinned window (a copy into
-                // pageable memory is a host round trip of its own: three of them and a second synchronisation for the
-                // results were 60-80 us of a call), and the host results are requested in front of it -- an
-                // overflowing list 1 (rare) drops them and asks again after the repeat
-                uint32_t h1s[2] = {0, 0}, h2s[2] = {0, 0};
-                unsigned gaves[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-                uint32_t *hw = ctx->api_depth > 0 ? (uint32_t *)stage_take(ctx, 12 * sizeof(uint32_t)) : nullptr;
-                uint32_t *h1 = hw ? hw : h1s, *h2 = hw ? hw + 2 : h2s;
-                unsigned *gave = hw ? hw + 4 : gaves;
-                if (hw)
-                    memset(hw, 0, 12 * sizeof(uint32_t));
-                SSYM_HIP_CHECK(ctx, hipMemcpyAsync(h1, hdr1, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-                SSYM_HIP_CHECK(ctx, hipMemcpyAsync(h2, hdr2, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-                if (ctx->pipe_mask)
-                    SSYM_HIP_CHECK(ctx, hipMemcpyAsync(gave, ctx->pipe_flag.ptr, 8 * sizeof(unsigned), hipMemcpyDeviceToHost, st));
-                const size_t pendingBefore = ctx->pending_d2h.size();
-                bool stagedHere = false;
-                if (!outDev && ctx->api_depth > 0) {
-                    rc = stage_d2h(ctx, out_idx, idxDev, sizeof(uint32_t) * (size_t)M * k_top);
-                    if (rc == SSYM_OK && out_cost)
-                        rc = stage_d2h(ctx, out_cost, costDev, sizeof(double) * (size_t)M * k_top);
-                    if (rc != SSYM_OK)
-                        return rc;
-                    // (a result too large for the window went straight to the caller's memory: still behind this
-                    //  synchronisation, and harmlessly overwritten by a repeat)
-                    stagedHere = true;
-                }
-                SSYM_HIP_CHECK(ctx, hipStreamSynchronize(st));
-                for (int i = 0; i < 8; ++i)
-                    if ((ctx->pipe_mask >> i & 1u) && gave[i])
-                        ++tm.exact_redone;
-                ctx->pipe_mask = 0;
-                if (stagedHere) {
-                    if (h1[1] && !(attempt == 1 || cap == (uint64_t)N * M))
-                        ctx->pending_d2h.resize(pendingBefore);      // the repeat's results are the ones to hand over
-                    else
-                        outputsStaged = true;
-                }
-                if (attempt == 0 && phase != 2)
-                    sel_ms += ev_ms(ev[1], ev[2]);      // the per-target threshold (bounds) belongs to selection
-                sel_ms += ev_ms(ev[2], ev[3]);
-                ref_ms += ev_ms(ev[3], ev[4]);
-                red_ms += ev_ms(ev[4], ev[5]);
-                tm.n_refined = h2[0];
-                if (!h1[1])
-                    break;
-                if (attempt == 1 || cap == (uint64_t)N * M) {
-                    ctx->err = "dtw: candidate list overflow";
-                    return SSYM_E_NOMEM;
-                }
-                cap = h1[0];
-                if (cap >= 0xffffffffull) {
-                    ctx->err = "dtw: too many near-tied candidates for one batch";
-                    return SSYM_E_UNSUPPORTED;
-                }
-            }
-            tm.main_ms = phase == 2 ? ctx->pending.main_ms : ev_ms(ev[6], ev[1]);
-            if (!tm.pruned && ctx->band < 0)
-                tm.n_filter_cells = ctx->launched_cells * 64ull;      // from the launches' geometry (dtw_filter.hip)
-            if (tm.pruned) {
-                tm.prune_ms = phase == 2 ? 0.f : ev_ms(ev[0], ev[6]);
-                tm.n_filter_cells = ctx->pruned_cells * 64ull;
-                if (ctx->band < 0) {
-                    const double full = (double)src.n_pad * tgt.n_pad * src.frames_pad * std::max<uint32_t>(tgt.max_frames, 1);
-                    ctx->prune_swept = (float)std::min(1.0, (double)tm.n_filter_cells / full);
-                }
-            }
-            tm.select_ms = sel_ms;
-            tm.refine_ms = ref_ms;
-            tm.reduce_ms = red_ms;
-            tm.total_ms = ev_ms(ev[0], ev[5]) + (phase == 2 ? ctx->pending.main_ms : 0.f);
-        } else {
-            rc = ensure(ctx, ctx->cmat, sizeof(double) * (size_t)N * M);
-            if (rc != SSYM_OK)
-                return rc;
-            double *costs = (double *)ctx->cmat.ptr;
-            SSYM_HIP_CHECK(ctx, hipEventRecord(ev[0], st));
-            rc = launch_dtw_exact(ctx, src, tgt, nullptr, nullptr, 0, costs);
-            if (rc != SSYM_OK)
-                return rc;
-            SSYM_HIP_CHECK(ctx, hipEventRecord(ev[1], st));
-            rc = launch_dtw_final_allpairs(ctx, N, M, costs, distDev, index_base, k_top, idxDev, costDev);
-            if (rc != SSYM_OK)
-                return rc;
-            SSYM_HIP_CHECK(ctx, hipEventRecord(ev[2], st));
-            if (ctx->stream_only) {
-                ctx->so_filter = false;
-                ctx->timings = tm;
-                return SSYM_OK;
-            }
-            unsigned gave[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-            if (ctx->pipe_mask)
-                SSYM_HIP_CHECK(ctx, hipMemcpyAsync(gave, ctx->pipe_flag.ptr, sizeof(gave), hipMemcpyDeviceToHost, st));
-            SSYM_HIP_CHECK(ctx, hipStreamSynchronize(st));
-            for (int i = 0; i < 8; ++i)
-                if ((ctx->pipe_mask >> i & 1u) && gave[i])
-                    ++tm.exact_redone;
-            tm.refine_ms = ev_ms(ev[0], ev[1]);
-            tm.reduce_ms = ev_ms(ev[1], ev[2]);
-            tm.total_ms = ev_ms(ev[0], ev[2]);
-            tm.n_refined = (uint64_t)N * M;
-        }
-    }
-
-    if (!outDev && !outputsStaged) {
-        rc = stage_d2h(ctx, out_idx, idxDev, sizeof(uint32_t) * (size_t)M * k_top);
-        if (rc == SSYM_OK && out_cost)
-            rc = stage_d2h(ctx, out_cost, costDev, sizeof(double) * (size_t)M * k_top);
-        if (rc != SSYM_OK)
-            return rc;
-    }
-    if (ctx->stream_only) {              // refcos through ssym_match_sharded (device outputs)
-        ctx->so_filter = false;
-        ctx->timings = tm;
-        return SSYM_OK;
-    }
-    if ((!outDev || ctx->metric == SSYM_METRIC_REFCOS) && !outputsStaged)      // (staged: already synchronised above)
-        SSYM_HIP_CHECK(ctx, hipStreamSynchronize(st));
-    stage_finish(ctx);
-    if (ctx->metric == SSYM_METRIC_REFCOS && stampsValid) {
-        tm.main_ms = stampMs[0];
-        tm.reduce_ms = stampMs[1];
-        tm.total_ms = stampMs[0] + stampMs[1];
-    } else if (ctx->metric == SSYM_METRIC_REFCOS) {
-        tm.main_ms = ev_ms(ev[0], ev[1]);
-        tm.reduce_ms = ev_ms(ev[1], ev[2]);
-        tm.total_ms = ev_ms(ev[0], ev[2]);
-    }
-    ctx->timings = tm;
-    return SSYM_OK;
-}
-
 extern "C" {
 
 int32_t ssym_match_queries(ssym_ctx *ctx, const ssym_dict *dict, const ssym_queries *q,
@@ -845,7 +270,7 @@ int32_t ssym_match_queries(ssym_ctx *ctx, const ssym_dict *dict, const ssym_quer
                            double *out_cost, uint32_t flags)
 {
     return guarded(ctx, [&]() -> int32_t {
-    return match_impl(ctx, dict, q, distance, index_base, 1, out_idx, out_cost, flags);
+    return match(ctx, dict, q, distance, index_base, 1, out_idx, out_cost, flags);
     });
 }
 
@@ -859,126 +284,9 @@ int32_t ssym_match_topk(ssym_ctx *ctx, const ssym_dict *dict, const ssym_queries
         ctx->err = "ssym_match_topk: k must be in 1..SSYM_TOPK_MAX";
         return SSYM_E_INVALID;
     }
-    return match_impl(ctx, dict, q, distance, index_base, k, out_idx, out_cost, flags);
+    return match(ctx, dict, q, distance, index_base, k, out_idx, out_cost, flags);
     });
 }
-
-// Two-phase match for source-sharded runs (see the header).  A tiny kernel-free helper fills the
-// bounds with +inf when the filter does not apply; the all-reduce then changes nothing.
-static bool prune_applies(const ssym_ctx *ctx, const ssym_dict *dict, const ssym_queries *q)
-{
-    const bool wideFrames = filter_lower_bound_only(ctx, dict->set, q->set);
-    return ctx->metric == SSYM_METRIC_DTW && q->set.n > 0 && !wideFrames && filter_supported(ctx, dict->set, q->set);
-}
-
-__global__ void fill_f64_kernel(double *p, double v, uint32_t n)
-{
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n)
-        p[i] = v;
-}
-
-}  // extern "C"
-
-namespace ssym {
-
-int32_t match_candidates_impl(ssym_ctx *ctx, const ssym_dict *dict, const ssym_queries *q, double *cost_dev)
-{
-    int32_t rc = check_match_args(ctx, dict, q);
-    if (rc != SSYM_OK)
-        return rc;
-    if (!cost_dev) {
-        ctx->err = "ssym_match_candidates: cost_dev is NULL";
-        return SSYM_E_INVALID;
-    }
-    ssym_ctx::Pending &pd = ctx->pending;
-    pd = ssym_ctx::Pending{};
-    const uint32_t M = q->set.n;
-    if (M == 0)
-        return SSYM_OK;
-    SSYM_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-    if (prune_applies(ctx, dict, q)) {
-        rc = launch_dtw_prune_candidates(ctx, dict->set, q->set);
-        if (rc != SSYM_OK)
-            return rc;
-        slots_to_targets_kernel<<<(M + 255) / 256, 256, 0, ctx->stream>>>((const double *)ctx->prune_cost.ptr,
-                                                                          q->set.perm, M, cost_dev);
-        pd.cand = true;
-        pd.dict = dict;
-        pd.q = q;
-    } else {
-        fill_f64_kernel<<<(M + 255) / 256, 256, 0, ctx->stream>>>(cost_dev, (double)INFINITY, M);
-    }
-    SSYM_HIP_CHECK(ctx, hipGetLastError());
-    if (!ctx->stream_only)
-        SSYM_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    return SSYM_OK;
-}
-
-int32_t match_begin_impl(ssym_ctx *ctx, const ssym_dict *dict, const ssym_queries *q, const double *distance,
-                         uint32_t index_base, double *bounds_dev, const double *prune_cost_dev)
-{
-    int32_t rc = check_match_args(ctx, dict, q);
-    if (rc != SSYM_OK)
-        return rc;
-    if (!bounds_dev) {
-        ctx->err = "ssym_match_begin: bounds_dev is NULL";
-        return SSYM_E_INVALID;
-    }
-    ssym_ctx::Pending &pd = ctx->pending;
-    // the reduced candidate costs are only usable when THIS context scored its candidates for the same sets
-    // (finish appends them); otherwise the call is a plain begin
-    if (prune_cost_dev && !(pd.cand && pd.dict == dict && pd.q == q && !distance))
-        prune_cost_dev = nullptr;
-    pd = ssym_ctx::Pending{};
-    pd.dict = dict;
-    pd.q = q;
-    pd.index_base = index_base;
-    pd.has_dist = distance != nullptr;
-    const uint32_t M = q->set.n;
-    if (distance)
-        pd.dist_host.assign(distance, distance + M);
-    const bool wideFrames = filter_lower_bound_only(ctx, dict->set, q->set);
-    pd.filter = ctx->metric == SSYM_METRIC_DTW && M > 0 && filter_supported(ctx, dict->set, q->set) &&
-                (!wideFrames || !distance);
-    if (pd.filter) {
-        rc = match_impl(ctx, dict, q, distance, index_base, 1, nullptr, nullptr, prune_cost_dev ? SSYM_DTW_PRUNE : 0u, 1,
-                        bounds_dev, prune_cost_dev);
-        if (rc != SSYM_OK)
-            return rc;
-    } else if (M > 0) {
-        SSYM_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-        fill_f64_kernel<<<(M + 255) / 256, 256, 0, ctx->stream>>>(bounds_dev, (double)INFINITY, M);
-        SSYM_HIP_CHECK(ctx, hipGetLastError());
-        if (!ctx->stream_only)
-            SSYM_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    }
-    pd.valid = true;
-    return SSYM_OK;
-}
-
-int32_t match_finish_impl(ssym_ctx *ctx, const double *bounds_dev, uint32_t *out_idx, double *out_cost, uint32_t flags)
-{
-    ssym_ctx::Pending &pd = ctx->pending;
-    if (!pd.valid) {
-        ctx->err = "ssym_match_finish without ssym_match_begin";
-        return SSYM_E_INVALID;
-    }
-    pd.valid = false;
-    if (!bounds_dev) {
-        ctx->err = "ssym_match_finish: bounds_dev is NULL";
-        return SSYM_E_INVALID;
-    }
-    const double *dist = pd.has_dist ? pd.dist_host.data() : nullptr;
-    if (!pd.filter)
-        return match_impl(ctx, pd.dict, pd.q, dist, pd.index_base, 1, out_idx, out_cost, flags);
-    return match_impl(ctx, pd.dict, pd.q, dist, pd.index_base, 1, out_idx, out_cost, flags, 2,
-                      const_cast<double *>(bounds_dev));
-}
-
-}  // namespace ssym
-
-extern "C" {
 
 int32_t ssym_match_candidates(ssym_ctx *ctx, const ssym_dict *dict, const ssym_queries *q, double *cost_dev)
 {
@@ -1049,8 +357,7 @@ int32_t ssym_match_batch(ssym_ctx *ctx, const ssym_dict *dict, const void *tgt_f
         uint32_t *idxP = (uint32_t *)stage_take(ctx, sizeof(uint32_t) * n_targets);
         if (qP && offP && valP && idxP && (distP || !distance)) {
             SSYM_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-            ctx->pending.cand = false;
-            ctx->pending.valid = false;
+            drop_pending(ctx);
             if (qBytes)
                 memcpy(qP, (const char *)tgt_feats + (size_t)f0 * dict->set.dim * esz, qBytes);
             for (uint32_t i = 0; i <= n_targets; ++i)
@@ -1096,14 +403,14 @@ int32_t ssym_match_batch(ssym_ctx *ctx, const ssym_dict *dict, const void *tgt_f
     SSYM_HIP_CHECK(ctx, hipSetDevice(ctx->device));
     SSYM_HIP_CHECK(ctx, hipEventRecord(e0, ctx->stream));
     ctx->defer_sync = true;        // this call synchronises once, at the end of the match
-    // a handful of short dtw queries go to the exact kernel on every pair (match_impl, kFlagFewTargets): their
+    // a handful of short dtw queries go to the exact kernel on every pair (match.hip, kFlagFewTargets): their
     // pack can leave out everything only the filter needs
+    const bool fewTargets = n_targets <= 4;
     uint64_t maxQ = 0;
     if (tgt_frame_offsets)
         for (uint32_t i = 0; i < n_targets; ++i)
             maxQ = std::max<uint64_t>(maxQ, tgt_frame_offsets[i + 1] - tgt_frame_offsets[i]);
-    ctx->pack_light = ctx->metric == SSYM_METRIC_DTW && n_targets <= 4 && (uint64_t)dict->set.n * n_targets <= 8192 &&
-                      dict->set.max_frames + maxQ <= 128;
+    ctx->pack_light = ctx->metric == SSYM_METRIC_DTW && fewTargets && few_pairs(dict->set.n, n_targets, dict->set.max_frames, maxQ);
     int32_t rc = ssym_queries_create(ctx, tgt_feats, tgt_frame_offsets, n_targets, dict->set.dim, &q);
     ctx->pack_light = false;
     ctx->defer_sync = false;
@@ -1113,8 +420,8 @@ int32_t ssym_match_batch(ssym_ctx *ctx, const ssym_dict *dict, const void *tgt_f
     }
     SSYM_HIP_CHECK(ctx, hipEventRecord(e1, ctx->stream));
     // a handful of queries at a time is the reference's own call pattern (match_sound per target,
-    // src/sound.rs:453-454): what counts then is the length of the launch chain, see match_impl
-    rc = match_impl(ctx, dict, q, distance, 0, 1, out_idx, out_cost, n_targets <= 4 ? kFlagFewTargets : 0u);
+    // src/sound.rs:453-454): what counts then is the length of the launch chain, see few_pairs
+    rc = match(ctx, dict, q, distance, 0, 1, out_idx, out_cost, fewTargets ? kFlagFewTargets : 0u);
     if (rc == SSYM_OK)
         ctx->timings.pack_ms = ev_ms(e0, e1);
     else
@@ -1157,8 +464,7 @@ int32_t ssym_chain(ssym_ctx *ctx, ssym_dict *dict, const void *start_feats, uint
         return SSYM_E_EMPTY_DICT;
     }
     SSYM_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-    ctx->pending.cand = false;          // (the chain uses the scratch a begin .. finish would still need)
-    ctx->pending.valid = false;
+    drop_pending(ctx);          // (the chain uses the scratch a begin .. finish would still need)
     hipStream_t st = ctx->stream;
     const bool refcos = ctx->metric == SSYM_METRIC_REFCOS;
     const double init = refcos ? 2.0 : (double)INFINITY;
@@ -1248,8 +554,7 @@ int32_t ssym_pair_matrix(ssym_ctx *ctx, const ssym_dict *dict, const ssym_querie
         ctx->err = "out_matrix is NULL";
         return SSYM_E_INVALID;
     }
-    ctx->pending.cand = false;          // (the matrix lands in the scratch a begin .. finish would still need)
-    ctx->pending.valid = false;
+    drop_pending(ctx);          // (the matrix lands in the scratch a begin .. finish would still need)
     const SegmentSet &src = dict->set;
     const SegmentSet &tgt = q->set;
     const uint32_t N = src.n, M = tgt.n;

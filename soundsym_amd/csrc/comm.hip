@@ -195,12 +195,6 @@ __global__ void comm_status_kernel(const uint32_t *__restrict__ hdr1, uint32_t *
     status[3] = 0u;
 }
 
-static float ev_ms2(hipEvent_t a, hipEvent_t b)
-{
-    float ms = 0.f;
-    return hipEventElapsedTime(&ms, a, b) == hipSuccess ? ms : 0.f;
-}
-
 // out[i] = min(out[i], other[i]): the replayed bounds of a larger world join the exchange (ssym_comm_replay_bounds)
 __global__ void comm_min_with_kernel(double *__restrict__ out, const double *__restrict__ other, uint32_t n)
 {
@@ -801,13 +795,10 @@ int32_t match_sharded_step(ssym_ctx *ctx, ssym_comm *comm, const ssym_dict *dict
         const bool ownLists = finished && (ctx->so_filter || ctx->so_refcos) && ctx->so_hdr2;
         if (ownLists)
             SSYM_HIP_CHECK(ctx, hipMemcpyAsync(ownCount, ctx->so_hdr2, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-        const unsigned pipeMask = ctx->pipe_mask;
-        if (pipeMask && ctx->pipe_flag.ptr)
+        if (ctx->pipe_mask && ctx->pipe_flag.ptr)
             SSYM_HIP_CHECK(ctx, hipMemcpyAsync(gaveUp, ctx->pipe_flag.ptr, 8 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
         if (!outDev) {
-            rc = stage_d2h(ctx, out_idx, userIdx, sizeof(uint32_t) * M);
-            if (rc == SSYM_OK && out_cost)
-                rc = stage_d2h(ctx, out_cost, userCost, sizeof(double) * M);
+            rc = request_outputs(ctx, out_idx, userIdx, out_cost, userCost, M, 1);
             if (rc != SSYM_OK)
                 return rc;
         }
@@ -833,27 +824,22 @@ int32_t match_sharded_step(ssym_ctx *ctx, ssym_comm *comm, const ssym_dict *dict
                 *agreed = true;
                 return code;
             }
-        if (pipeMask) {
-            for (int i = 0; i < 8; ++i)
-                if ((pipeMask >> i & 1u) && gaveUp[i])
-                    ++tm.exact_redone;
-            ctx->pipe_mask = 0;
-        }
+        count_exact_giveups(ctx, gaveUp, tm);
         if (attempt == 0)
-            coll_ms += ev_ms2(cev[2], cev[3]) + (pruned ? ev_ms2(cev[0], cev[1]) : 0.f);
-        coll_ms += ev_ms2(cev[5], cev[6]);
+            coll_ms += ev_ms(cev[2], cev[3]) + (pruned ? ev_ms(cev[0], cev[1]) : 0.f);
+        coll_ms += ev_ms(cev[5], cev[6]);
         if (finished && ctx->so_filter) {
             hipEvent_t *ev = ctx->ev;
-            sel_ms += ev_ms2(ev[0], ev[3]);
-            ref_ms += ev_ms2(ev[3], ev[4]);
-            red_ms += ev_ms2(ev[4], ev[5]);
+            sel_ms += ev_ms(ev[0], ev[3]);
+            ref_ms += ev_ms(ev[3], ev[4]);
+            red_ms += ev_ms(ev[4], ev[5]);
             tm.n_refined = ownCount[0];
         } else if (finished && ctx->so_refcos) {       // refcos through the matrix pipe: main kernel | exact keys and fold
             tm.used_filter = 1;
-            tm.refcos_filter = ctx->timings.refcos_filter;     // (which filter the enqueueing call took: capi.hip)
+            tm.refcos_filter = ctx->timings.refcos_filter;     // (which filter the enqueueing call took: match.hip)
             tm.main_launches = 1;
-            tm.main_ms = ev_ms2(ctx->ev[0], ctx->ev[1]);
-            red_ms += ev_ms2(ctx->ev[1], ctx->ev[2]);
+            tm.main_ms = ev_ms(ctx->ev[0], ctx->ev[1]);
+            red_ms += ev_ms(ctx->ev[1], ctx->ev[2]);
             tm.n_refined = ownCount[0];
         }
         bool anyOverflow = false;
@@ -879,17 +865,8 @@ int32_t match_sharded_step(ssym_ctx *ctx, ssym_comm *comm, const ssym_dict *dict
     stage_finish(ctx);
     if (filterPath) {
         tm.main_launches = ctx->filter_launches;
-        tm.main_ms = ev_ms2(ctx->ev[6], ctx->ev[1]);
-        if (!tm.pruned && ctx->band < 0)
-            tm.n_filter_cells = ctx->launched_cells * 64ull;
-        if (tm.pruned) {
-            tm.n_filter_cells = ctx->pruned_cells * 64ull;
-            if (ctx->band < 0) {
-                const SegmentSet &src = dict->set, &tgt = q->set;
-                const double full = (double)src.n_pad * tgt.n_pad * src.frames_pad * std::max<uint32_t>(tgt.max_frames, 1);
-                ctx->prune_swept = (float)std::min(1.0, (double)tm.n_filter_cells / full);
-            }
-        }
+        tm.main_ms = ev_ms(ctx->ev[6], ctx->ev[1]);
+        account_filter_cells(ctx, dict->set, q->set, tm);
     } else if (!emptyShard && !refcos) {
         tm.n_refined = tm.n_pairs;
     }
@@ -897,9 +874,9 @@ int32_t match_sharded_step(ssym_ctx *ctx, ssym_comm *comm, const ssym_dict *dict
     tm.refine_ms = ref_ms;
     tm.reduce_ms = red_ms;
     tm.collective_ms = coll_ms;
-    tm.total_ms = ev_ms2(cev[4], cev[7]);
+    tm.total_ms = ev_ms(cev[4], cev[7]);
     if (pruned)
-        tm.prune_ms = ev_ms2(cev[4], cev[0]);
+        tm.prune_ms = ev_ms(cev[4], cev[0]);
     ctx->timings = tm;
     return SSYM_OK;
 }

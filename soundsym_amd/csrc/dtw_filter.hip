@@ -151,7 +151,7 @@ bool filter_supported(const ssym_ctx *ctx, const SegmentSet &src, const SegmentS
     if (src.light || tgt.light)
         return false;   // packed for the exact kernels only
     if (src.dim != tgt.dim)
-        return false;   // (frames wider than 42 values: capi.hip decides, the filter is then a lower bound only)
+        return false;   // (frames wider than 42 values: match.hip decides, the filter is then a lower bound only)
     if ((ctx->band < 0 || filter_band_as_bound(ctx, src, tgt)) && filter_shape((int)src.max_frames).nt == 0)
         return false;   // more than 4096 source frames
     if (!std::isfinite(src.max_abs) || !std::isfinite(tgt.max_abs))

@@ -322,7 +322,7 @@ static int32_t build_derived(ssym_ctx *ctx, SegmentSet &set)
         segment_norm_kernel<<<(n + 3) / 4, 256, 0, st>>>(set.raw, set.off, n, dim, set.norm);
         SSYM_HIP_CHECK(ctx, hipGetLastError());
     } else if (ctx->pack_light && !set.is_source) {
-        // a handful of short queries that will be scored by the exact kernel on every pair (capi.hip, kFlagFewTargets):
+        // a handful of short queries that will be scored by the exact kernel on every pair (match.hip, kFlagFewTargets):
         // no slot order, no statistics, no synchronisation for them
         set.light = true;
     } else {

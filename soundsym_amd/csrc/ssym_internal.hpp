@@ -386,7 +386,33 @@ int32_t launch_merge_shards(ssym_ctx *ctx, uint32_t n_shards, uint32_t n_targets
                             const double *costs, const uint32_t *idx, const double *dist_dev,
                             uint32_t *out_idx, double *out_cost, size_t cost_stride = 0, size_t idx_stride = 0);
 
-// capi.hip: the phases of a source-sharded match, shared with comm.hip.  With ctx->stream_only they only enqueue.
+// match.hip: the search.  Whole: one call; Begin / Finish: ssym_match_begin / ssym_match_finish, which split the dtw
+// filter route between the per-target bounds (out through bounds_dev) and the selection (bounds_dev back in).
+enum class Phase { Whole, Begin, Finish };
+constexpr uint32_t kFlagFewTargets = 0x80000000u;      // internal flag: set by ssym_match_batch / ssym_match_one for <= 4 targets
+int32_t check_match_args(ssym_ctx *ctx, const ssym_dict *dict, const ssym_queries *q);
+int32_t match(ssym_ctx *ctx, const ssym_dict *dict, const ssym_queries *q, const double *distance, uint32_t index_base,
+              uint32_t k_top, uint32_t *out_idx, double *out_cost, uint32_t flags, Phase phase = Phase::Whole,
+              double *bounds_dev = nullptr, const double *prune_cost_dev = nullptr /* Begin: reduced candidate costs, by target */);
+// so few and so short pairs that, for <= 4 targets, the exact dtw kernel on every pair beats the filter's launch chain
+bool few_pairs(uint64_t N, uint64_t M, uint64_t maxSrcFrames, uint64_t maxTgtFrames);
+// the indices, then the costs if asked, through the pinned window to the caller's memory (handed over by stage_finish)
+int32_t request_outputs(ssym_ctx *ctx, uint32_t *out_idx, const uint32_t *idxDev, double *out_cost, const double *costDev,
+                        uint32_t M, uint32_t k_top);
+// after the synchronisation that brought `gave` (ctx->pipe_flag's 8 words) back: the launches of ctx->pipe_mask whose
+// pipelined exact kernel gave up -> tm.exact_redone; the mask starts over
+void count_exact_giveups(ssym_ctx *ctx, const uint32_t *gave, ssym_timings &tm);
+// tm.n_filter_cells of a filter-route call (tm.pruned set), and ctx->prune_swept after a pruned one
+void account_filter_cells(ssym_ctx *ctx, const SegmentSet &src, const SegmentSet &tgt, ssym_timings &tm);
+// a call that uses the context's scratch ends a begin .. finish in progress (finish then reports "without begin") and
+// drops the candidates of ssym_match_candidates: their buffers are shared
+inline void drop_pending(ssym_ctx *ctx) { ctx->pending.cand = ctx->pending.valid = false; }
+inline float ev_ms(hipEvent_t a, hipEvent_t b)
+{
+    float ms = 0.f;
+    return hipEventElapsedTime(&ms, a, b) == hipSuccess ? ms : 0.f;
+}
+// the phases of a source-sharded match, shared with comm.hip.  With ctx->stream_only they only enqueue.
 int32_t match_candidates_impl(ssym_ctx *ctx, const ssym_dict *dict, const ssym_queries *q, double *cost_dev);
 int32_t match_begin_impl(ssym_ctx *ctx, const ssym_dict *dict, const ssym_queries *q, const double *distance,
                          uint32_t index_base, double *bounds_dev, const double *prune_cost_dev);

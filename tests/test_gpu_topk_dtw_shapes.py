@@ -260,7 +260,7 @@ def test_list_1_overflow_is_redone_and_gives_the_same_rows(oracle, dtw):
     src = [one.copy() for _ in range(n)]
     tgt = [x for x in synth.make_grid(m, 1, f, 13, 0x5EED0396).sources]
     c = _Case(oracle, dtw, src, tgt, 13)
-    cap0 = max((256 + 16 * (k - 1)) * m, 65536)                   # list 1's first capacity (capi.hip)
+    cap0 = max((256 + 16 * (k - 1)) * m, 65536)                   # list 1's first capacity (match.hip, dtw_filter_back)
     idx, _ = c.check(k, None, filter_route(more_than=cap0))
     assert np.array_equal(idx, np.tile(np.arange(k, dtype=np.uint32), (m, 1)))
     # (with distances the three targets whose distance is NaN or infinite list nothing: 197 x 600 pairs, still an overflow)
