@@ -172,6 +172,14 @@ extern "C" {
                                    n_targets: u32, frame_map: *const u32, map_offsets: *const u64, map_frames: *const u32,
                                    pair_len: *const u32, flags: u32, out_samples: *mut f64, out_pcm32: *mut i32) -> i32;
 
+    // WSOLA reconstruction: ssym_reconstruct_warped with every source frame moved by up to `search` (<= 512) samples to
+    // where it continues the frame before it best; out_pos (nullable): the u64 sample start of every source frame, laid
+    // out by map_offsets (device memory with SSYM_OUT_DEVICE)
+    pub fn ssym_reconstruct_wsola(ctx: *mut SsymCtx, s: *const SsymSamples, idx: *const u32, out_offsets: *const u64,
+                                  n_targets: u32, frame_map: *const u32, map_offsets: *const u64, map_frames: *const u32,
+                                  pair_len: *const u32, search: u32, flags: u32, out_pos: *mut u64, out_samples: *mut f64,
+                                  out_pcm32: *mut i32) -> i32;
+
     // feature front-end (own MFCC definition -- parity with vox_box unpinned)
     pub fn ssym_mfcc_num_frames(n_samples: u64, flags: u32, out_frames: *mut u64) -> i32;
     pub fn ssym_mfcc(ctx: *mut SsymCtx, samples: *const f64, n_samples: u64, sample_rate: f64, n_coeffs: u32,

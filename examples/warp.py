@@ -1,13 +1,17 @@
 #!/usr/bin/env python3
 """examples/warp.py -- a reconstruction whose matches follow the target's timing.
 
-    python examples/warp.py -s TARGET.wav -d DICT.wav -o OUT.wav [--plain PLAIN.wav] [--depth 5] [--threshold 4] [--seed 0]
+    python examples/warp.py -s TARGET.wav -d DICT.wav -o OUT.wav [--plain PLAIN.wav] [--search 0] [--depth 5] [--threshold 4]
+                            [--seed 0]
 
 Both recordings are cut by a Partitioner trained on the dictionary recording, as examples/reconstruction.py --partition
 cuts them.  Every target segment is matched against the dictionary's segments under DTW, aligned with its match, and the
 match is resynthesised along the alignment (SoundSequence.reconstruct_warped_from_dictionary: ssym_match_queries,
 ssym_dtw_align and ssym_reconstruct_warped, the alignment staying on the GPU).  --plain writes the length-fitted
 reconstruction (reconstruct_from_dictionary: matches cut off or padded with silence) beside it, to compare by ear.
+--search N (at most 512 samples) resynthesises with the waveform-similarity search instead (ssym_reconstruct_wsola): every
+source frame may move up to N samples to where it continues the frame before it in phase; the share of frames that did
+move is printed.
 """
 import argparse
 import os
@@ -27,6 +31,7 @@ def main(argv=None):
     ap.add_argument("-d", required=True, help="dictionary recording")
     ap.add_argument("-o", required=True, help="output path of the warped reconstruction")
     ap.add_argument("--plain", help="also write the length-fitted reconstruction here")
+    ap.add_argument("--search", type=int, default=0, help="WSOLA search width in samples (0: plain overlap-add)")
     ap.add_argument("--depth", type=int, default=5)
     ap.add_argument("--threshold", type=int, default=4)
     ap.add_argument("--seed", type=int, default=0, help="draws the mixture's starting frames")
@@ -41,7 +46,17 @@ def main(argv=None):
     cut = SoundDictionary.from_segments(target, partitioner.partition_other(target), engine=engine)
     sequence = SoundSequence.new([s for s in cut.sounds if s.num_frames() > 0])
 
-    samples, pcm = sequence.reconstruct_warped_from_dictionary(dictionary, want_pcm32=True)
+    if args.search:
+        samples, pcm, pos, m_off = dictionary.warp(sequence.sounds(), want_pcm32=True, search=args.search, want_pos=True)
+        aligned = dictionary.align(sequence.sounds())
+        moved = frames = 0
+        for t, al in enumerate(aligned):
+            nominal = np.asarray(al.frame_map, dtype=np.uint64) * np.uint64(256)
+            moved += int(np.count_nonzero(pos[int(m_off[t]):int(m_off[t]) + nominal.size] != nominal))
+            frames += nominal.size
+        print(f"search {args.search}: {moved} of {frames} frames ({100.0 * moved / max(frames, 1):.1f} %) moved off their nominal place")
+    else:
+        samples, pcm = sequence.reconstruct_warped_from_dictionary(dictionary, want_pcm32=True)
     write_wav32(args.o, sample_rate=target.sample_rate(), pcm=pcm)
     print(f"{len(dictionary.sounds)} dictionary segments, {len(sequence.sounds())} target segments, "
           f"{samples.size} samples -> {args.o}")

@@ -290,8 +290,10 @@ class SoundDictionary {
     // counterpart).  One stretch of targets[t]->samples().size() samples per target, concatenated; a pair without a
     // finite cost takes clone_from_dictionary's length fit.  (The mirror holds no device memory of its own, so the
     // maps pass through the host here; a caller with device buffers hands ssym_dtw_align's SSYM_OUT_DEVICE outputs
-    // to ssym_reconstruct_warped with SSYM_WARP_MAP_DEVICE.)
-    std::vector<double> warp(const std::vector<ArcSound> &targets, const std::vector<uint32_t> &indices) const
+    // to ssym_reconstruct_warped with SSYM_WARP_MAP_DEVICE.)  search > 0 (at most 512 samples): ssym_reconstruct_wsola
+    // instead -- every source frame may move that far to where it continues the frame before it in phase.
+    std::vector<double> warp(const std::vector<ArcSound> &targets, const std::vector<uint32_t> &indices,
+                             uint32_t search = 0) const
     {
         if (sounds.empty())
             throw EmptyDictionary();
@@ -326,8 +328,10 @@ class SoundDictionary {
         ssym_samples *smp = nullptr;
         ctx_->check(ssym_samples_create(ctx_->get(), samples.data(), soff.data(), (uint32_t)sounds.size(), &smp));
         out.resize(ooff[n]);
-        rc = ssym_reconstruct_warped(ctx_->get(), smp, indices.data(), ooff.data(), n, map.data(), moff.data(),
-                                     frames.data(), len.data(), 0, out.data(), nullptr);
+        rc = search ? ssym_reconstruct_wsola(ctx_->get(), smp, indices.data(), ooff.data(), n, map.data(), moff.data(),
+                                             frames.data(), len.data(), search, 0, nullptr, out.data(), nullptr)
+                    : ssym_reconstruct_warped(ctx_->get(), smp, indices.data(), ooff.data(), n, map.data(), moff.data(),
+                                              frames.data(), len.data(), 0, out.data(), nullptr);
         ssym_samples_destroy(ctx_->get(), smp);
         ctx_->check(rc);
         return out;

@@ -497,6 +497,37 @@ SSYM_API int32_t ssym_reconstruct_warped(ssym_ctx *ctx, const ssym_samples *s, c
                                          const uint32_t *pair_len, uint32_t flags, double *out_samples,
                                          int32_t *out_pcm32);
 
+/* WSOLA reconstruction (DESIGN.md section 2 "WSOLA" and section 5.14): ssym_reconstruct_warped with a waveform-similarity
+ * search.  Every source frame may start up to `search` samples off its nominal place map[j] * HOP, where it continues the
+ * frame laid down before it best, so that a periodic source stays periodic where the map repeats or skips frames.  With
+ * HOP, BIN, w[], x[0 .. sLen), F and map[0 .. F) as above and S = search, pos[j] is the sample start of source frame j:
+ *   pos[0] = map[0] * HOP.  For j >= 1: nom = map[j] * HOP (64-bit); the template is the natural continuation of the frame
+ *   before, tmpl[n] = x[pos[j-1] + HOP + n], n < BIN; for every lag d in -S .. S with 0 <= nom + d < sLen the candidate is
+ *   cand[n] = x[nom + d + n], n < BIN (in both, a sample at or beyond sLen reads +0.0).  c(d) = sum of tmpl[n] * cand[n],
+ *   e(d) = sum of cand[n] * cand[n], both sums from +0.0 in ascending n, every product and every sum rounded separately in
+ *   f64; score(d) = c / sqrt(e) (IEEE division and square root), 0 when e = 0.  pos[j] = nom + d*, d* the lag of the
+ *   greatest score, ties to the smaller |d|, then to the negative d.  A NaN score never wins; d* = 0 when no lag is
+ *   admissible or no admissible lag has a score that is a number.
+ *   Synthesis: the taps, value and out_pcm32 of ssym_reconstruct_warped with p = pos[j] + m in place of map[j] * HOP + m.
+ *   Fallback: exactly that call's (F = 0 or pair_len[t] = 0: the length fit).
+ * So search = 0 gives ssym_reconstruct_warped's output bit for bit, and on a diagonal map lag 0 is the template itself,
+ * the greatest score by Cauchy-Schwarz.  Still no phase vocoder and no transient handling; a repeated frame is a repeated
+ * frame, only laid down in phase.
+ *   search             S, at most 512 samples; more: SSYM_E_INVALID before any device work
+ *   out_pos            nullable, u64 per map slot laid out by map_offsets (HOST, or device with SSYM_OUT_DEVICE): pos[j]
+ *                      at out_pos[map_offsets[t] + j] for j < map_frames[t] of the targets that have a path; every other
+ *                      slot is left alone
+ * Every other argument, the flags, the checks, the no-op cases (out_pos alone does not make work) and the errors are
+ * ssym_reconstruct_warped's.  No map content and no sample content can cause an out-of-range read; a device map is not
+ * validated.  One synchronisation per call.  ssym_get_timings: main_ms the search kernel, reduce_ms the synthesis kernel,
+ * total_ms both.  The call stages in the scratch ssym_reconstruct uses, so it may run between ssym_match_begin and
+ * ssym_match_finish as that call may. */
+SSYM_API int32_t ssym_reconstruct_wsola(ssym_ctx *ctx, const ssym_samples *s, const uint32_t *idx,
+                                        const uint64_t *out_offsets, uint32_t n_targets, const uint32_t *frame_map,
+                                        const uint64_t *map_offsets, const uint32_t *map_frames,
+                                        const uint32_t *pair_len, uint32_t search, uint32_t flags, uint64_t *out_pos,
+                                        double *out_samples, int32_t *out_pcm32);
+
 /* Feature front-end, the step before the hot path: what
  * Sound::from_samples(.., None, ..) computes through analyze_mfccs (src/sound.rs:215-242) --
  * 1024-sample Hanning windows hopped by 256 (src/lib.rs:24-25), per window `n_coeffs` MFCCs between

@@ -56,7 +56,7 @@ ABI_SYMBOLS = [
     "ssym_stream_read", "ssym_stream_frames_device", "ssym_stream_samples_device", "ssym_stream_descriptors",
     "ssym_stream_reset",
     "ssym_dtw_align_sizes", "ssym_dtw_align",
-    "ssym_reconstruct_warped",
+    "ssym_reconstruct_warped", "ssym_reconstruct_wsola",
 ]
 COMM_ID_BYTES = 128        # SSYM_COMM_ID_BYTES
 
@@ -258,6 +258,8 @@ def lib() -> ctypes.CDLL:
     L.ssym_reconstruct.argtypes = [vp, vp, vp, vp, u32, vp, vp]
     L.ssym_reconstruct_warped.restype = i32
     L.ssym_reconstruct_warped.argtypes = [vp, vp, vp, vp, u32, vp, vp, vp, vp, u32, vp, vp]
+    L.ssym_reconstruct_wsola.restype = i32
+    L.ssym_reconstruct_wsola.argtypes = [vp, vp, vp, vp, u32, vp, vp, vp, vp, u32, u32, vp, vp, vp]
     L.ssym_comm_unique_id.restype = i32
     L.ssym_comm_unique_id.argtypes = [vp]
     L.ssym_comm_create.restype = i32

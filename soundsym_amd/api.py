@@ -27,7 +27,7 @@ from typing import List, Optional, Sequence
 import numpy as np
 
 from ._native import NO_MATCH, SSYM_E_UNSUPPORTED, EmptyDictionaryError, SsymError
-from .engine import Engine, pack_segments, pitch_lags
+from .engine import Engine, _wsola_search, pack_segments, pitch_lags
 
 NCOEFFS = 12   # src/lib.rs:22
 NCLUSTERS = 26 # src/lib.rs:23
@@ -520,17 +520,23 @@ class SoundDictionary:
             q.close()
         return [Alignment(cost[t], paths[t], maps[t], int(indices[t])) for t in range(len(targets))]
 
-    def warp(self, targets: Sequence[Sound], indices=None, want_pcm32: bool = False):
+    def warp(self, targets: Sequence[Sound], indices=None, want_pcm32: bool = False, search: int = 0,
+             want_pos: bool = False):
         """The reconstruction of the targets with every match warped onto its target's timing (dtw engines): match
         (unless indices[t] names the dictionary sound of target t), align with the outputs left on the device, and
         resynthesise along the maps -- ssym_match_queries, ssym_dtw_align, ssym_reconstruct_warped; the maps never
         visit the host.  Returns the concatenated samples, one stretch of len(target.samples()) per target (with
         want_pcm32 also their 32-bit conversion).  A target without a finite alignment takes the length fit of
-        reconstruct_from_dictionary."""
+        reconstruct_from_dictionary.  search > 0 (at most 512 samples): ssym_reconstruct_wsola in place of the last
+        call -- every source frame may move that far to continue the frame before it in phase; want_pos then also
+        returns the frames' sample starts and the map offsets they are laid out by (Engine.reconstruct_wsola)."""
         if not self.sounds:
             raise EmptyDictionaryError(-2, "empty dictionary")
         if getattr(self.engine, "metric", None) != "dtw":
             raise SsymError(SSYM_E_UNSUPPORTED, "warp follows dtw alignments: a refcos engine has none")
+        search = _wsola_search(search)
+        if want_pos and not search:
+            raise ValueError("want_pos needs search > 0: without a search the positions are the map times 256")
         targets = list(targets)
         if indices is not None:
             indices = np.asarray(indices, dtype=np.int64).reshape(-1)
@@ -539,7 +545,9 @@ class SoundDictionary:
             if indices.size and (indices.min() < 0 or indices.max() >= len(self.sounds)):
                 raise ValueError("an index is outside the dictionary")
         if not targets:
-            return (np.zeros(0), np.zeros(0, dtype=np.int32)) if want_pcm32 else np.zeros(0)
+            res = (np.zeros(0),) + ((np.zeros(0, dtype=np.int32),) if want_pcm32 else ())
+            res += (np.zeros(0, dtype=np.uint64), np.zeros(1, dtype=np.uint64)) if want_pos else ()
+            return res if len(res) > 1 else res[0]
         flat, off = pack_segments([t.mfccs() for t in targets], self._dim(), self.engine.np_dtype)
         out_off = np.concatenate([[0], np.cumsum([t.samples().size for t in targets])]).astype(np.uint64)
         q = self.engine.queries(flat, off, self._dim())
@@ -547,8 +555,12 @@ class SoundDictionary:
             if indices is None:
                 indices, _ = self.engine.match(self.resident(), q)
             _, lengths, _, maps, _, m_off = self.engine.dtw_align_device(self.resident(), q, indices)
-            return self.engine.reconstruct_warped(self.resident_samples(), indices, out_off, maps, m_off,
-                                                  np.diff(m_off.astype(np.int64)), lengths, want_pcm32)
+            if not search:
+                return self.engine.reconstruct_warped(self.resident_samples(), indices, out_off, maps, m_off,
+                                                      np.diff(m_off.astype(np.int64)), lengths, want_pcm32)
+            res = self.engine.reconstruct_wsola(self.resident_samples(), indices, out_off, maps, m_off,
+                                                np.diff(m_off.astype(np.int64)), lengths, search, want_pcm32, want_pos)
+            return res + (m_off,) if want_pos else res
         finally:
             q.close()
 
@@ -683,12 +695,14 @@ class SoundSequence:
         out_off = np.concatenate([[0], np.cumsum(lens)]).astype(np.uint64)
         return dict_.engine.reconstruct(dict_.resident_samples(), idx, out_off, want_pcm32)
 
-    def reconstruct_warped_from_dictionary(self, dict_: "SoundDictionary", want_pcm32: bool = False):
+    def reconstruct_warped_from_dictionary(self, dict_: "SoundDictionary", want_pcm32: bool = False, search: int = 0):
         """reconstruct_from_dictionary with every match warped onto its target's timing instead of cut off or padded
-        (SoundDictionary.warp: match, align, resynthesise along the alignment, all on the GPU; dtw engines)."""
+        (SoundDictionary.warp: match, align, resynthesise along the alignment, all on the GPU; dtw engines).
+        search > 0: with the waveform-similarity search of that width in samples (at most 512)."""
+        search = _wsola_search(search)
         if not self._sounds:
             return (np.zeros(0), np.zeros(0, dtype=np.int32)) if want_pcm32 else np.zeros(0)
-        return dict_.warp(self._sounds, None, want_pcm32)
+        return dict_.warp(self._sounds, None, want_pcm32, search)
 
     def to_sound(self) -> Sound:                                        # src/sound.rs:475-483
         parts = [s.samples() for s in self._sounds]

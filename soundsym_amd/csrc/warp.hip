@@ -15,7 +15,7 @@
 // only ever needs the window at tid, tid + 256, tid + 512 and tid + 768, which it keeps in registers.  The chunk touches
 // target frames chunk / 256 - 3 ... chunk / 256 + 15: their 19 source positions map[j] * HOP sit in LDS (sLen for a
 // frame outside [0, F): such a tap is never valid), every read of them a broadcast.
-#include "ssym_internal.hpp"
+#include "warp_common.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -23,12 +23,6 @@
 
 namespace ssym {
 namespace {
-
-constexpr int kWarpHop = SSYM_MFCC_HOP, kWarpBin = SSYM_MFCC_BIN;
-constexpr int kWarpTaps = kWarpBin / kWarpHop;                    // 4 windows cover a sample
-constexpr int kWarpChunk = 4096;                                  // samples per workgroup
-constexpr int kWarpFrames = kWarpChunk / kWarpHop + kWarpTaps - 1;    // 19 target frames reach into a chunk
-static_assert(kWarpHop == 256 && kWarpTaps == 4 && kWarpFrames == 19, "warp_kernel: 256 threads, one hop each");
 
 struct WarpArgs {
     const double *src;          // the store's samples
@@ -44,16 +38,6 @@ struct WarpArgs {
     double *out;                // nullable
     int32_t *pcm;               // nullable
 };
-
-// (i32::max_value() as f64 * sample) as i32, as reconstruct_kernel: truncate toward zero, saturate, NaN -> 0
-__device__ __forceinline__ int32_t warp_pcm32(double v)
-{
-    const double x = __dmul_rn(2147483647.0, v);
-    if (x != x) return 0;
-    if (x >= 2147483647.0) return 2147483647;
-    if (x <= -2147483648.0) return (int32_t)0x80000000;
-    return (int32_t)x;
-}
 
 __global__ __launch_bounds__(256) void warp_kernel(const WarpArgs a)
 {
@@ -146,19 +130,6 @@ __global__ __launch_bounds__(256) void warp_kernel(const WarpArgs a)
                 a.pcm[o0 + k] = warp_pcm32(r);
         }
     }
-}
-
-// w[m] = 0.5 - 0.5 cos(2 pi m / 1024): the text of build_tables (mfcc_frame.hpp), so the bits of the MFCC window
-const std::vector<double> &warp_window()
-{
-    static const std::vector<double> win = [] {
-        const double PI = 3.14159265358979323846;
-        std::vector<double> w(kWarpBin);
-        for (int i = 0; i < kWarpBin; ++i)
-            w[i] = 0.5 - 0.5 * std::cos(2.0 * PI * (double)i / (double)kWarpBin);
-        return w;
-    }();
-    return win;
 }
 
 int32_t reconstruct_warped(ssym_ctx *ctx, const ssym_samples *s, const uint32_t *idx, const uint64_t *out_offsets,

@@ -101,6 +101,18 @@ def _warp_inputs(idx, out_offsets, maps, map_offsets, map_frames, pair_len):
     return idx, off, m_off, frames, map_ptr, len_ptr, device, keep
 
 
+WSOLA_MAX_SEARCH = 512
+
+
+def _wsola_search(search) -> int:
+    """The search width of reconstruct_wsola, checked on the host: an integer in 0 ... 512."""
+    if isinstance(search, bool) or not isinstance(search, (int, np.integer)):
+        raise ValueError("search must be an integer number of samples")
+    if not 0 <= int(search) <= WSOLA_MAX_SEARCH:
+        raise ValueError(f"search must lie in 0 ... {WSOLA_MAX_SEARCH} samples")
+    return int(search)
+
+
 class _Handle:
     def __init__(self, engine: "Engine", ptr: int, n: int, dim: int, kind: str):
         self.engine, self.ptr, self.n, self.dim, self.kind = engine, ptr, n, dim, kind
@@ -946,6 +958,32 @@ class Engine:
                                                     pcm.ctypes.data if pcm is not None else None), self.ctx)
         del keep
         return (out, pcm) if want_pcm32 else out
+
+    def reconstruct_wsola(self, smp, idx, out_offsets, maps, map_offsets, map_frames, pair_len=None, search: int = 0,
+                          want_pcm32: bool = False, want_pos: bool = False):
+        """ssym_reconstruct_wsola: reconstruct_warped with every source frame moved by up to `search` samples (0 ... 512)
+        to where it continues the frame before it best (definition in include/soundsym_amd.h).  Arguments as
+        reconstruct_warped.  Returns the samples, with want_pcm32 also their 32-bit conversion, with want_pos also the
+        u64 sample start of every source frame, laid out by map_offsets (slots of targets without a path and slack
+        slots hold 2^64 - 1).  search = 0 gives reconstruct_warped's samples bit for bit.  dtw engines only."""
+        if self.metric != "dtw":
+            raise nat.SsymError(nat.SSYM_E_UNSUPPORTED, "reconstruct_wsola follows dtw alignments: a refcos engine has none")
+        search = _wsola_search(search)
+        idx, off, m_off, frames, map_ptr, len_ptr, device, keep = _warp_inputs(idx, out_offsets, maps, map_offsets,
+                                                                               map_frames, pair_len)
+        total = int(off[-1])
+        out = np.zeros(total, dtype=np.float64)
+        pcm = np.zeros(total, dtype=np.int32) if want_pcm32 else None
+        pos = np.full(int(m_off[-1]), np.iinfo(np.uint64).max, dtype=np.uint64) if want_pos else None
+        nat.check(nat.lib().ssym_reconstruct_wsola(self.ctx, smp.ptr, idx.ctypes.data, off.ctypes.data, idx.size,
+                                                   map_ptr, m_off.ctypes.data, frames.ctypes.data, len_ptr, search,
+                                                   nat.WARP_MAP_DEVICE if device else 0,
+                                                   pos.ctypes.data if pos is not None and pos.size else None,
+                                                   out.ctypes.data, pcm.ctypes.data if pcm is not None else None),
+                  self.ctx)
+        del keep
+        res = (out,) + ((pcm,) if want_pcm32 else ()) + ((pos,) if want_pos else ())
+        return res if len(res) > 1 else out
 
     def merge_shards(self, costs, idx, out_idx, out_cost, distance=None) -> None:
         """costs [G, M] f64, idx [G, M] 32-bit, outputs [M]: torch CUDA tensors on this GPU; distance:
