@@ -123,6 +123,14 @@ extern "C" {
                           tgt_idx: *const u32, n_pairs: u32, index_base: u32, out_cost: *mut f64, out_len: *mut u32,
                           path_offsets: *const u64, out_path: *mut u32, map_offsets: *const u64, out_map: *mut u32,
                           flags: u32) -> i32;
+    // DTW spotting (subsequence DTW; dtw contexts without a band): the span of a dictionary segment's frames a target
+    // aligns with best and its cost, per listed pair / the best segment per target; no spot: +inf and SSYM_NO_MATCH
+    pub fn ssym_dtw_spot(ctx: *mut SsymCtx, dict: *const SsymDict, q: *const SsymQueries, src_idx: *const u32,
+                         tgt_idx: *const u32, n_pairs: u32, index_base: u32, out_cost: *mut f64, out_start: *mut u32,
+                         out_end: *mut u32, flags: u32) -> i32;
+    pub fn ssym_spot_queries(ctx: *mut SsymCtx, dict: *const SsymDict, q: *const SsymQueries, index_base: u32,
+                             out_idx: *mut u32, out_cost: *mut f64, out_start: *mut u32, out_end: *mut u32,
+                             flags: u32) -> i32;
 
     // source-sharded runs, exchange done by the caller (device pointers): filter / all-reduce(MIN) / finish / merge
     pub fn ssym_match_begin(ctx: *mut SsymCtx, dict: *const SsymDict, q: *const SsymQueries, distance: *const f64,

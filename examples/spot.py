@@ -1,0 +1,65 @@
+#!/usr/bin/env python3
+"""examples/spot.py -- a reconstruction from recordings that were never cut.
+
+    python examples/spot.py -s TARGET.wav -d DICT.wav|DIR -o OUT.wav [--search 0] [--depth 5] [--threshold 4] [--seed 0]
+
+The target is cut by a Partitioner as examples/warp.py cuts it (trained on the first dictionary recording); the dictionary
+recordings stay whole.  Every target segment is located inside the recordings by subsequence DTW
+(SoundDictionary.spot: one ssym_spot_queries call), the spans are cut out (SoundDictionary.cut) and each is warped onto
+its target's timing (SoundDictionary.warp with the given indices: ssym_dtw_align and ssym_reconstruct_warped, or
+ssym_reconstruct_wsola with --search N).  The recording, span and cost of every target segment are printed; the cost is
+a sum along the path, not normalised by any length.
+"""
+import argparse
+import os
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+import numpy as np  # noqa: E402
+
+from soundsym_amd import Engine, Partitioner, Sound, SoundDictionary  # noqa: E402
+from soundsym_amd.io import write_wav32  # noqa: E402
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser()
+    ap.add_argument("-s", required=True, help="target recording")
+    ap.add_argument("-d", required=True, help="dictionary recording, or a directory of recordings")
+    ap.add_argument("-o", required=True, help="output path of the reconstruction")
+    ap.add_argument("--search", type=int, default=0, help="WSOLA search width in samples (0: plain overlap-add)")
+    ap.add_argument("--depth", type=int, default=5)
+    ap.add_argument("--threshold", type=int, default=4)
+    ap.add_argument("--seed", type=int, default=0, help="draws the mixture's starting frames")
+    args = ap.parse_args(argv)
+
+    engine = Engine(metric="dtw", dtype="f64")
+    if os.path.isdir(args.d):
+        dictionary = SoundDictionary.from_path(args.d, engine=engine)
+    else:
+        dictionary = SoundDictionary(engine)
+        dictionary.sounds.append(Sound.from_path(args.d, engine=engine))
+    dictionary.sounds = [s for s in dictionary.sounds if s.num_frames() > 0]
+    partitioner = Partitioner(dictionary.sounds[0], engine=engine).threshold(args.threshold).depth(args.depth)
+    partitioner.train(seed=args.seed)
+    target = Sound.from_path(args.s, engine=engine)
+    pieces = SoundDictionary.from_segments(target, partitioner.partition_other(target), engine=engine)
+    targets = [s for s in pieces.sounds if s.num_frames() > 0]
+
+    spots = dictionary.spot(targets)
+    for t, sp in enumerate(spots):
+        if not sp:
+            print(f"segment {t:4d} ({targets[t].num_frames():3d} frames): no spot")
+            continue
+        name = dictionary.sounds[sp.source_index].name or str(sp.source_index)
+        print(f"segment {t:4d} ({targets[t].num_frames():3d} frames): {name} frames {sp.start_frame}...{sp.end_frame} "
+              f"({sp.num_frames()} frames), cost {sp.cost:.6g}")
+    found = dictionary.cut(spots)
+    samples, pcm = found.warp(targets, indices=np.arange(len(targets)), want_pcm32=True, search=args.search)
+    write_wav32(args.o, sample_rate=target.sample_rate(), pcm=pcm)
+    print(f"{len(dictionary.sounds)} recordings, {len(targets)} target segments, {samples.size} samples -> {args.o}")
+    return samples
+
+
+if __name__ == "__main__":
+    main()

@@ -336,6 +336,44 @@ class SoundDictionary {
         ctx_->check(rc);
         return out;
     }
+    // where inside the dictionary's (unsegmented) recordings every target sounds: subsequence DTW (ssym_spot_queries, or
+    // ssym_dtw_spot with indices[t] naming the recording of target t; dtw contexts without a band; the crate has no
+    // counterpart).  Frames start_frame ... end_frame (inclusive) of sounds[source_index]; cost is the DTW cost of
+    // (those frames, the target), not normalised by any length.  No spot: cost +inf and all three SSYM_NO_MATCH
+    struct Spot {
+        uint32_t source_index, start_frame, end_frame;
+        double cost;
+        bool empty() const { return end_frame == SSYM_NO_MATCH; }
+    };
+    std::vector<Spot> spot(const std::vector<ArcSound> &targets, const std::vector<uint32_t> *indices = nullptr) const
+    {
+        if (sounds.empty())
+            throw EmptyDictionary();
+        const uint32_t n = (uint32_t)targets.size();
+        std::vector<double> flat;
+        std::vector<uint64_t> off;
+        pack_features(targets, flat, off);
+        ssym_queries *q = nullptr;
+        ctx_->check(ssym_queries_create(ctx_->get(), flat.data(), off.data(), n, (uint32_t)NCOEFFS, &q));
+        std::vector<uint32_t> idx(n), start(n), end(n);
+        std::vector<double> cost(n);
+        int32_t rc;
+        if (indices) {
+            idx = *indices;
+            rc = idx.size() == n ? ssym_dtw_spot(ctx_->get(), resident(), q, idx.data(), nullptr, n, 0, cost.data(),
+                                                 start.data(), end.data(), 0)
+                                 : (int32_t)SSYM_E_INVALID;
+        } else {
+            rc = ssym_spot_queries(ctx_->get(), resident(), q, 0, idx.data(), cost.data(), start.data(), end.data(), 0);
+        }
+        ssym_queries_destroy(ctx_->get(), q);
+        ctx_->check(rc);
+        std::vector<Spot> out(n);
+        for (uint32_t t = 0; t < n; ++t)
+            out[t] = end[t] == SSYM_NO_MATCH ? Spot{SSYM_NO_MATCH, SSYM_NO_MATCH, SSYM_NO_MATCH, cost[t]}
+                                             : Spot{idx[t], start[t], end[t], cost[t]};
+        return out;
+    }
     // from_distances' chain of at_distance calls, on the device in one call (ssym_chain)
     std::vector<uint32_t> chain_indices(const Sound &start, const std::vector<double> &distances) const
     {

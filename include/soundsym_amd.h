@@ -102,8 +102,8 @@ typedef struct ssym_config {
     int32_t reserved;      /* 0                                                                  */
 } ssym_config;
 
-/* Per-phase device time of the LAST ssym_match_* call on the context, measured with HIP events
- * recorded on the context's stream (milliseconds; 0 when a phase did not run).  One exception: a refcos search
+/* Per-phase device time of the LAST ssym_match_* (or ssym_dtw_spot / ssym_spot_queries) call on the context, measured
+ * with HIP events recorded on the context's stream (milliseconds; 0 when a phase did not run).  One exception: a refcos search
  * through a filter (refcos_filter 1 or 2) outside ssym_match_sharded is timed by the device's wall clock, read by
  * its first kernel, the first kernel after the main one and its last kernel -- an event record between two kernels
  * costs several microseconds of gap on the stream, which a search of 0.2 ms notices. */
@@ -281,6 +281,45 @@ SSYM_API int32_t ssym_dtw_align(ssym_ctx *ctx, const ssym_dict *dict, const ssym
                                 const uint32_t *tgt_idx, uint32_t n_pairs, uint32_t index_base, double *out_cost,
                                 uint32_t *out_len, const uint64_t *path_offsets, uint32_t *out_path,
                                 const uint64_t *map_offsets, uint32_t *out_map, uint32_t flags);
+
+/* DTW spotting (subsequence DTW; dtw contexts without a band; DESIGN.md section 2 "Spotting" and section 5.15): where
+ * inside an unsegmented dictionary recording a target aligns best.  The source side of the recurrence is open at both
+ * ends; the reference has no counterpart.  With c the context's local cost (its squared option applies), i a source
+ * frame 0 ... Fa - 1, j a target frame 0 ... Fb - 1:
+ *   D(i,0)  = c(i,0)                                    for every i (a path may start at any source frame)
+ *   D(i,j)  = c(i,j) + min(D(i-1,j), D(i,j-1), D(i-1,j-1)),  j >= 1, outside the matrix +inf
+ *   st(i,0) = i;  st(i,j) = st of the predecessor ssym_dtw_align's rule picks: with dg = D(i-1,j-1), up = D(i-1,j),
+ *             lf = D(i,j-1): diagonal if dg <= up && dg <= lf, else up if up <= lf, else left
+ *   end     = the smallest i at which D(i,Fb-1) is least (i ascending from (none, +inf), strict <: NaN never wins)
+ *   cost    = D(end,Fb-1);  start = st(end,Fb-1)
+ * in the arithmetic of ssym_pair_matrix(exact = 1) and ssym_dtw_align (f64, k ascending, every operation rounded
+ * separately).  So start is where ssym_dtw_align's backtrace from (end, Fb-1) first reaches column 0, cost has the bits
+ * of the plain DTW cost of (source frames start ... end, target) -- what ssym_pair_matrix(exact = 1) and ssym_dtw_align
+ * give for that cut -- and is the least such cost over all spans.  The cost is NOT normalised by any length.  What
+ * features that are not finite give is unspecified (no read leaves its buffer).
+ * ssym_dtw_spot: pair p = (dictionary segment src_idx[p] - index_base, target tgt_idx[p]); tgt_idx == NULL: target p
+ *   (n_pairs <= n_targets).  Any pairing, repeats allowed.  src_idx / tgt_idx are HOST memory.
+ *   out_cost   n_pairs f64;  out_start, out_end   n_pairs u32 each: the span's first and last source frame (inclusive)
+ *   No spot (src_idx[p] == SSYM_NO_MATCH, a segment without frames, no finite D(i,Fb-1)): cost +inf, start = end =
+ *   SSYM_NO_MATCH.
+ *   flags      SSYM_OUT_DEVICE: out_cost, out_start and out_end are device memory
+ * ssym_spot_queries: every dictionary segment against every target, then per target the first least cost over ascending
+ *   segment index (strict < from (SSYM_NO_MATCH, +inf)): out_idx n_targets u32 (+ index_base; SSYM_NO_MATCH itself when
+ *   no segment has a spot), out_cost / out_start / out_end those of that segment.  n_sources * n_targets < 2^32.
+ *   flags      SSYM_OUT_DEVICE: the four outputs are device memory
+ * Limits: targets of at most 4096 frames, dim <= 64; beyond them, on a refcos context and on a context with a band (a
+ * Sakoe-Chiba band has no meaning with a free start): SSYM_E_UNSUPPORTED.  A source may be as long as a dictionary
+ * segment can be: ssym_dict_create takes segments of up to 2^31 - 1 frames.  NULL pointers, an index outside its set, a
+ * dim mismatch: SSYM_E_INVALID; an empty dictionary with work to do (n_pairs > 0, n_targets > 0): SSYM_E_EMPTY_DICT --
+ * all with a message, before device memory is touched and with the outputs unwritten.  n_pairs = 0 / n_targets = 0
+ * succeeds and does nothing.  One synchronisation per call.  ssym_get_timings afterwards: main_ms = the spot kernel,
+ * reduce_ms = the fold of ssym_spot_queries, n_pairs = the pairs of the call. */
+SSYM_API int32_t ssym_dtw_spot(ssym_ctx *ctx, const ssym_dict *dict, const ssym_queries *q, const uint32_t *src_idx,
+                               const uint32_t *tgt_idx, uint32_t n_pairs, uint32_t index_base, double *out_cost,
+                               uint32_t *out_start, uint32_t *out_end, uint32_t flags);
+SSYM_API int32_t ssym_spot_queries(ssym_ctx *ctx, const ssym_dict *dict, const ssym_queries *q, uint32_t index_base,
+                                   uint32_t *out_idx, double *out_cost, uint32_t *out_start, uint32_t *out_end,
+                                   uint32_t flags);
 
 /* Source-sharded multi-GPU, dtw metric: the one real exchange the path has.  Each rank's filter gives,
  * per target, an upper bound on the best key in ITS shard; a rank whose shard does not hold a

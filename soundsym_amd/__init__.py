@@ -22,6 +22,7 @@ from .api import (  # noqa: F401
     Sound,
     SoundDictionary,
     SoundSequence,
+    Spot,
     analyze_mfccs,
     analyze_sounds,
     cosine_sim_angular,
@@ -34,7 +35,7 @@ from .api import (  # noqa: F401
 
 __all__ = [
     "ABI_SYMBOLS", "Alignment", "BIN", "DeviceFrames", "EmptyDictionaryError", "Engine", "Gmm", "HOP", "LIB_PATH", "NCLUSTERS", "NCOEFFS",
-    "Partitioner", "Sound", "SoundDictionary", "SoundSequence", "SsymError", "analyze_mfccs", "analyze_sounds", "build",
+    "Partitioner", "Sound", "SoundDictionary", "SoundSequence", "Spot", "SsymError", "analyze_mfccs", "analyze_sounds", "build",
     "cosine_sim_angular", "discretize",
     "discretize_with_model", "length_fit", "pack_segments", "push_sounds", "Stream", "stream_plan", "train_model",
 ]

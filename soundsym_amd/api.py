@@ -347,6 +347,49 @@ class Alignment:
         return "Alignment(source_index=%d, cost=%r, cells=%d)" % (self.source_index, self.cost, len(self))
 
 
+class Spot:
+    """Where inside a dictionary recording a target sounds (ssym_dtw_spot / ssym_spot_queries; definition in
+    include/soundsym_amd.h and DESIGN.md section 2 "Spotting"): `source_index` into the dictionary's sounds, the frames
+    `start_frame` ... `end_frame` (INCLUSIVE) of that recording, and `cost`, the DTW cost of (those frames, the target),
+    not normalised by any length.  A target without a spot (an empty sound, an empty recording) gives an empty Spot:
+    falsy, no frames, cost +inf."""
+
+    __slots__ = ("source_index", "start_frame", "end_frame", "cost")
+
+    def __init__(self, source_index: int, start_frame: int, end_frame: int, cost: float):
+        self.source_index, self.start_frame, self.end_frame = int(source_index), int(start_frame), int(end_frame)
+        self.cost = float(cost)
+        if not self.empty() and not 0 <= self.start_frame <= self.end_frame:
+            raise ValueError("a spot spans start_frame ... end_frame with 0 <= start_frame <= end_frame")
+
+    @staticmethod
+    def none() -> "Spot":
+        return Spot(NO_MATCH, NO_MATCH, NO_MATCH, float("inf"))
+
+    def empty(self) -> bool:
+        return NO_MATCH in (self.source_index, self.start_frame, self.end_frame)
+
+    def __bool__(self) -> bool:
+        return not self.empty()
+
+    def num_frames(self) -> int:
+        return 0 if self.empty() else self.end_frame - self.start_frame + 1
+
+    def sample_span(self, num_samples: int):
+        """(first sample, one past the last sample) of the span in a recording of num_samples samples: frame f starts
+        at sample f * HOP, and the last frame ends where the next one would start, or with the recording."""
+        if self.empty():
+            return (0, 0)
+        n = int(num_samples)
+        return (self.start_frame * HOP, min((self.end_frame + 1) * HOP, n))
+
+    def __repr__(self) -> str:
+        if self.empty():
+            return "Spot(empty)"
+        return "Spot(source_index=%d, frames=%d...%d, cost=%r)" % (self.source_index, self.start_frame, self.end_frame,
+                                                                   self.cost)
+
+
 class SoundDictionary:
     """Cache of Sounds searched by similarity (src/sound.rs:290-371)."""
 
@@ -564,6 +607,57 @@ class SoundDictionary:
         finally:
             q.close()
 
+    def spot(self, targets: Sequence[Sound], indices=None) -> List["Spot"]:
+        """Where inside the dictionary's (unsegmented) recordings every target sounds: subsequence DTW on the GPU (dtw
+        engines without a band).  indices=None: every recording is tried for every target and the best one kept, the
+        lower index on a tie -- one ssym_spot_queries call; otherwise indices[t] names the recording target t is
+        spotted in (ssym_dtw_spot).  A target without a spot gives an empty Spot."""
+        if not self.sounds:
+            raise EmptyDictionaryError(-2, "empty dictionary")
+        if getattr(self.engine, "metric", None) != "dtw":
+            raise SsymError(SSYM_E_UNSUPPORTED, "spot aligns with dtw: a refcos engine has no alignment")
+        targets = list(targets)
+        if indices is not None:
+            indices = np.asarray(indices, dtype=np.int64).reshape(-1)
+            if indices.size != len(targets):
+                raise ValueError("indices must name one dictionary sound per target")
+            if indices.size and (indices.min() < 0 or indices.max() >= len(self.sounds)):
+                raise ValueError("an index is outside the dictionary")
+        if not targets:
+            return []
+        flat, off = pack_segments([t.mfccs() for t in targets], self._dim(), self.engine.np_dtype)
+        q = self.engine.queries(flat, off, self._dim())
+        try:
+            if indices is None:
+                indices, cost, start, end = self.engine.spot_queries(self.resident(), q)
+            else:
+                cost, start, end = self.engine.dtw_spot(self.resident(), q, indices)
+        finally:
+            q.close()
+        return [Spot(int(indices[t]), int(start[t]), int(end[t]), cost[t]) if int(end[t]) != NO_MATCH else Spot.none()
+                for t in range(len(targets))]
+
+    def cut(self, spots: Sequence["Spot"]) -> "SoundDictionary":
+        """A dictionary with one Sound per spot: the recording's samples over spot.sample_span() and its feature frames
+        start_frame ... end_frame; an empty spot gives an empty Sound.  Sound t of the result is what target t was
+        spotted as, so align, warp and reconstruct_from_dictionary take it with indices = arange(len(spots))."""
+        out = SoundDictionary(self._engine)
+        for sp in spots:
+            if not sp:
+                ref = self.sounds[0] if self.sounds else None
+                out.sounds.append(Sound(np.zeros(0), ref.sample_rate() if ref else 44100.0, np.zeros(0), None,
+                                        ref.ncoeffs if ref else NCOEFFS))
+                continue
+            if not 0 <= sp.source_index < len(self.sounds):
+                raise ValueError("a spot names a sound outside the dictionary")
+            s = self.sounds[sp.source_index]
+            if sp.end_frame >= s.num_frames():
+                raise ValueError("a spot ends beyond its sound's frames")
+            a, b = sp.sample_span(s.samples().size)
+            feats = s.mfcc_arrays()[sp.start_frame:sp.end_frame + 1]
+            out.sounds.append(Sound(s.samples()[a:b].copy(), s.sample_rate(), feats.reshape(-1).copy(), s.name, s.ncoeffs))
+        return out
+
     def candidates(self, targets: Sequence[Sound], k: int, distances=None) -> List[List[Sound]]:
         """The k best dictionary sounds per target, best first: what k
         successive at_distance calls (src/sound.rs:351) would return if each winner were removed."""
@@ -683,6 +777,12 @@ class SoundSequence:
         if not self._sounds:
             return []
         return dict_.align(self._sounds)
+
+    def spot_in_dictionary(self, dict_: SoundDictionary) -> List[Spot]:
+        """Every sound of the sequence located inside dict_'s recordings (SoundDictionary.spot)."""
+        if not self._sounds:
+            return []
+        return dict_.spot(self._sounds)
 
     def reconstruct_from_dictionary(self, dict_: "SoundDictionary", want_pcm32: bool = False):
         """clone_from_dictionary(dict).to_sound().samples() in one go (src/sound.rs:451-480): match

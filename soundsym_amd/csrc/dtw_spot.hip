@@ -1,0 +1,534 @@
+// dtw_spot.hip -- DTW spotting (subsequence DTW): where inside an unsegmented source a target aligns best, for a list of
+// (source, target) pairs, and the best source per target (DESIGN.md 2 "Spotting", 5.15).
+//
+// Role on the path: every search compares a target with whole dictionary segments; this one leaves the source open at
+// both ends, so a dictionary of uncut recordings can be asked where a target sounds.  Per pair: the inclusive span
+// [start, end] of source frames and its cost, which is the plain DTW cost of (source[start ... end], target).
+//
+// Definition (i = source frame, j = target frame, c = the local cost of the context):
+//   D(i,0) = c(i,0), st(i,0) = i;   D(i,j) = c(i,j) + min(D(i-1,j), D(i,j-1), D(i-1,j-1)), outside the matrix +inf;
+//   st(i,j) = st of the predecessor the alignment rule picks: dg = D(i-1,j-1), up = D(i-1,j), lf = D(i,j-1):
+//             diagonal if dg <= up && dg <= lf, else up if up <= lf, else left;
+//   end = the smallest i at which D(i,Fb-1) is least (strict <, from +inf: NaN and +inf never win), cost = D(end,Fb-1),
+//   start = st(end,Fb-1).
+//
+// Arithmetic: dtw_exact.hip's and dtw_align.hip's (f64, k ascending, sub / mul / add rounded separately, the square root
+// rounded separately, c + min3 with min3's comparisons in the same order).
+//
+// Mapping: one wave per pair, grid-stride over the list; dtw_align.hip's forward pass (lane = source row of a 64-row
+// chunk, the row above by a DPP move, the lane's source frame in registers, target frames through an LDS ring of 128
+// frames refilled 64 at a time, a chunk's bottom row handed to the next chunk through ONE LDS row overwritten in place:
+// lane 63 writes column tau - 63 while lane 0 reads columns tau and tau - 1).  Everything carried between lanes and
+// through the hand-off row is a pair (D f64, st u32); the row has Fb entries, so the LDS a pair needs does not grow with
+// the source.  Every lane keeps the best D(r, Fb-1) of its own rows (chunks ascend, strict <: its lowest such row); one
+// wave reduction per pair orders the 64 candidates by (D, row).  No direction matrix, no backward walk: three scalars
+// per pair, written by lane 0.
+#include "ssym_internal.hpp"
+
+#include <algorithm>
+
+namespace ssym {
+
+// Limits of ssym_dtw_spot / ssym_spot_queries (soundsym_amd.h): frames of a target, values per frame.
+// A source has as many frames as a dictionary segment can (2^31 - 1).
+constexpr int kSpotMaxTargetFrames = 4096;
+constexpr int kSpotMaxDim = 64;
+constexpr int kSpotRing = 128;              // target frames resident in LDS (two blocks of 64)
+
+namespace {
+
+__device__ __forceinline__ int spot_shr1(int v)       // lane - 1's value (DPP wave_shr:1)
+{
+    return __builtin_amdgcn_update_dpp(v, v, 0x138, 0xf, 0xf, false);
+}
+__device__ __forceinline__ double spot_shr1(double v)
+{
+    return __hiloint2double(spot_shr1(__double2hiint(v)), spot_shr1(__double2loint(v)));
+}
+
+// LDS row stride of the ring: 2 (mod 4) doubles, so 128-bit reads by consecutive lanes tile the banks (dtw_exact.hip)
+template <int DIMR>
+constexpr int spot_ld() { return DIMR % 4 == 2 ? DIMR : DIMR + 2; }
+
+struct SpotArgs {
+    const double *srcRaw;
+    const uint64_t *srcOff;
+    const double *tgtRaw;
+    const uint64_t *tgtOff;
+    uint32_t dim;
+    int squared;
+    const uint2 *pairs;          // (source, target); source 0xffffffff = no match; NULL: pair k = (k / nTgt, k % nTgt)
+    uint32_t nTgt;
+    uint32_t nPairs;
+    double *cost;                // [nPairs]
+    uint32_t *start, *end;       // [nPairs]
+    uint32_t fbCap;              // even, >= the longest listed target
+    uint32_t ringRows;           // 64 or 128
+};
+
+template <int DIMR>
+__global__ __launch_bounds__(64) void dtw_spot_kernel(const SpotArgs a)
+{
+    extern __shared__ __attribute__((aligned(16))) double smem[];
+    constexpr int LD = spot_ld<DIMR>();
+    typedef double d2 __attribute__((ext_vector_type(2)));
+    double *boundD = smem;                                          // [fbCap]   bottom row of the chunk above: D ...
+    double *ring = smem + a.fbCap;                                  // [ringRows][LD]
+    uint32_t *boundS = reinterpret_cast<uint32_t *>(ring + (size_t)a.ringRows * LD);      // [fbCap]   ... and st
+    const double INF = __builtin_inf();
+    const int lane = threadIdx.x;
+    const int dim = (int)a.dim;
+    const uint32_t ringMask = a.ringRows - 1;
+
+    for (uint32_t k = blockIdx.x; k < a.nPairs; k += gridDim.x) {
+        uint2 p;
+        if (a.pairs)
+            p = a.pairs[k];
+        else
+            p = make_uint2(k / a.nTgt, k % a.nTgt);
+        uint32_t Fa = 0;             // (a dictionary segment has at most 2^31 - 1 frames: row numbers fit 32 bits)
+        int Fb = 0;
+        if (p.x != 0xffffffffu) {
+            Fa = (uint32_t)(a.srcOff[p.x + 1] - a.srcOff[p.x]);
+            Fb = (int)(a.tgtOff[p.y + 1] - a.tgtOff[p.y]);
+        }
+        if (Fa == 0 || Fb == 0) {
+            if (lane == 0) {
+                a.cost[k] = INF;
+                a.start[k] = 0xffffffffu;
+                a.end[k] = 0xffffffffu;
+            }
+            continue;
+        }
+        const double *a0 = a.srcRaw + a.srcOff[p.x] * dim;
+        const double *b0 = a.tgtRaw + a.tgtOff[p.y] * dim;
+
+        double bestD = INF;                 // this lane's rows: the least D(r, Fb-1) so far, its row and its start
+        uint32_t bestEnd = 0xffffffffu, bestSt = 0xffffffffu;
+        for (uint32_t c0 = 0; c0 < Fa; c0 += 64) {
+            const uint32_t r = c0 + (uint32_t)lane;
+            const bool rowValid = r < Fa;
+            const int rowsHere = (int)min(64u, Fa - c0);
+            double ar[DIMR];
+            {
+                const double *arow = a0 + (size_t)(rowValid ? r : c0) * dim;
+#pragma unroll
+                for (int e = 0; e < DIMR; ++e)
+                    ar[e] = e < dim ? arow[e] : 0.0;
+            }
+            double mineD = INF;             // D(r, j-1)
+            uint32_t mineS = 0xffffffffu;
+            double diagD = INF;             // D(r-1, j-1)
+            uint32_t diagS = 0xffffffffu;
+            const int tauEnd = Fb - 1 + rowsHere;     // exclusive: lane l works on column tau - l
+            for (int tau = 0; tau < tauEnd; ++tau) {
+                if ((tau & 63) == 0) {
+                    // the 64 target frames from column tau on enter the ring; the block they replace ended at column
+                    // tau - 65, and the lanes still read from column tau - 63 on.  (The barrier also orders the hand-off
+                    // row: the previous chunk's writes, and the previous pair's reads, are done before tau = 0 goes on.)
+                    const int cnt = min(64, Fb - tau);
+                    __syncthreads();
+                    for (int i = lane; i < cnt * DIMR; i += 64) {
+                        const int fr = i / DIMR, e = i % DIMR;
+                        ring[(size_t)((uint32_t)(tau + fr) & ringMask) * LD + e] = e < dim ? b0[(size_t)(tau + fr) * dim + e] : 0.0;
+                    }
+                    __syncthreads();
+                }
+                const int j = tau - lane;
+                const int jc = min(max(j, 0), Fb - 1);
+                const d2 *bp = reinterpret_cast<const d2 *>(ring + (size_t)((uint32_t)jc & ringMask) * LD);
+                // sum_k (a_k - b_k)^2, k ascending, sub / mul / add rounded separately (the oracle's order); the
+                // zero padding adds +0.0 to a non-negative sum and leaves its bits alone
+                double acc = 0.0;
+#pragma unroll
+                for (int e0 = 0; e0 < DIMR; e0 += 8) {
+                    d2 bv[4];
+#pragma unroll
+                    for (int v = 0; v < 4; ++v)
+                        if (e0 + 2 * v < DIMR)
+                            bv[v] = bp[e0 / 2 + v];
+#pragma unroll
+                    for (int v = 0; v < 8; ++v)
+                        if (e0 + v < DIMR) {
+                            const double df = __dsub_rn(ar[e0 + v], bv[v / 2][v % 2]);
+                            acc = __dadd_rn(acc, __dmul_rn(df, df));
+                        }
+                }
+                const double c = a.squared ? acc : sqrt(acc);
+                double upD = spot_shr1(mineD);            // D(r-1, j) and its start, for lanes >= 1
+                uint32_t upS = (uint32_t)spot_shr1((int)mineS);
+                double dgD = diagD;
+                uint32_t dgS = diagS;
+                if (lane == 0) {
+                    upD = dgD = INF;                      // above row 0 there is nothing
+                    upS = dgS = 0xffffffffu;
+                    if (c0 != 0) {
+                        if (j >= 0 && j < Fb) {
+                            upD = boundD[j];
+                            upS = boundS[j];
+                        }
+                        if (j >= 1 && j <= Fb) {
+                            dgD = boundD[j - 1];
+                            dgS = boundS[j - 1];
+                        }
+                    }
+                }
+                const bool active = rowValid && j >= 0 && j < Fb;
+                if (active) {
+                    double cur = c;                       // column 0: a path may start at any source frame
+                    uint32_t st = r;
+                    if (j > 0) {
+                        double best = upD;                    // D(i-1, j)      (dtw_exact.hip's order)
+                        if (mineD < best) best = mineD;       // D(i,   j-1)
+                        if (dgD < best) best = dgD;           // D(i-1, j-1)
+                        cur = __dadd_rn(c, best);
+                        // the alignment rule: ties prefer the diagonal, then the source step
+                        st = (dgD <= upD && dgD <= mineD) ? dgS : (upD <= mineD ? upS : mineS);
+                    }
+                    if (lane == 63) {
+                        boundD[j] = cur;
+                        boundS[j] = st;
+                    }
+                    if (j == Fb - 1 && cur < bestD) {
+                        bestD = cur;
+                        bestEnd = r;
+                        bestSt = st;
+                    }
+                    mineD = cur;
+                    mineS = st;
+                }
+                diagD = upD;
+                diagS = upS;
+            }
+        }
+        // the first minimum of the end column: the 64 lanes' candidates ordered by (D, row); a lane without one holds
+        // (+inf, 0xffffffff), which loses against every candidate and ties with its like
+#pragma unroll
+        for (int m = 32; m >= 1; m >>= 1) {
+            const double oD = __shfl_xor(bestD, m);
+            const uint32_t oE = (uint32_t)__shfl_xor((int)bestEnd, m), oS = (uint32_t)__shfl_xor((int)bestSt, m);
+            if (oD < bestD || (oD == bestD && oE < bestEnd)) {
+                bestD = oD;
+                bestEnd = oE;
+                bestSt = oS;
+            }
+        }
+        if (lane == 0) {
+            a.cost[k] = bestD;
+            a.start[k] = bestSt;
+            a.end[k] = bestEnd;
+        }
+    }
+}
+
+// the best source per target of an [nSrc][nTgt] result: the first minimum over ascending source index, strict < from
+// (SSYM_NO_MATCH, +inf).  One thread per target; consecutive threads read consecutive entries of a row.
+__global__ __launch_bounds__(256) void spot_fold_kernel(const double *cost, const uint32_t *start, const uint32_t *end,
+                                                        uint32_t nSrc, uint32_t nTgt, uint32_t indexBase,
+                                                        uint32_t *outIdx, double *outCost, uint32_t *outStart,
+                                                        uint32_t *outEnd)
+{
+    const uint32_t t = blockIdx.x * 256u + threadIdx.x;
+    if (t >= nTgt)
+        return;
+    double best = __builtin_inf();
+    uint32_t bi = 0xffffffffu;
+    for (uint32_t s = 0; s < nSrc; ++s) {
+        const double c = cost[(size_t)s * nTgt + t];
+        if (c < best) {
+            best = c;
+            bi = s;
+        }
+    }
+    uint32_t st = 0xffffffffu, en = 0xffffffffu;
+    if (bi != 0xffffffffu) {
+        st = start[(size_t)bi * nTgt + t];
+        en = end[(size_t)bi * nTgt + t];
+    }
+    outIdx[t] = bi == 0xffffffffu ? bi : bi + indexBase;
+    outCost[t] = best;
+    outStart[t] = st;
+    outEnd[t] = en;
+}
+
+// what both entry points refuse before anything else (err: where the message goes)
+int32_t spot_check_ctx(ssym_ctx *ctx, const char *fn)
+{
+    if (ctx->metric != SSYM_METRIC_DTW) {
+        ctx->err = std::string(fn) + ": the context's metric is refcos, which has no alignment to spot";
+        return SSYM_E_UNSUPPORTED;
+    }
+    if (ctx->band >= 0) {
+        ctx->err = std::string(fn) + ": a Sakoe-Chiba band has no meaning with a free start; use a context without one";
+        return SSYM_E_UNSUPPORTED;
+    }
+    return SSYM_OK;
+}
+
+// the spot kernel on ctx's stream: pairs (device, NULL = every (source, target)) -> cost / start / end (device)
+int32_t launch_spot(ssym_ctx *ctx, const SegmentSet &src, const SegmentSet &tgt, const uint2 *pairs, uint32_t n_pairs,
+                    uint64_t maxFb, double *cost, uint32_t *start, uint32_t *end)
+{
+    hipStream_t st = ctx->stream;
+    SpotArgs a{};
+    a.srcRaw = src.raw;
+    a.srcOff = src.off;
+    a.tgtRaw = tgt.raw;
+    a.tgtOff = tgt.off;
+    a.dim = src.dim;
+    a.squared = ctx->squared;
+    a.pairs = pairs;
+    a.nTgt = tgt.n;
+    a.nPairs = n_pairs;
+    a.cost = cost;
+    a.start = start;
+    a.end = end;
+    a.fbCap = ((uint32_t)std::max<uint64_t>(maxFb, 1) + 1) & ~1u;
+    a.ringRows = maxFb <= 64 ? 64 : kSpotRing;
+    const int dimr = src.dim <= 14 ? 14 : src.dim <= 16 ? 16 : src.dim <= 40 ? 40 : 64;
+    const int ld = dimr % 4 == 2 ? dimr : dimr + 2;       // spot_ld<>
+    // hand-off row (12 bytes per target frame, at most 48 KiB) + ring (at most 66 KiB)
+    const size_t lds = (size_t)a.fbCap * (sizeof(double) + sizeof(uint32_t)) + (size_t)a.ringRows * ld * sizeof(double);
+    const unsigned grid = (unsigned)std::min<uint64_t>(n_pairs, (uint64_t)ctx->num_cus * 8);
+#define SSYM_SPOT_LAUNCH(D_)                                                                                   \
+    do {                                                                                                       \
+        auto kern = dtw_spot_kernel<D_>;                                                                       \
+        if (lds > 64 * 1024)                                                                                   \
+            SSYM_HIP_CHECK(ctx, hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, \
+                                                    (int)lds));                                                \
+        kern<<<grid, 64, lds, st>>>(a);                                                                        \
+    } while (0)
+    switch (dimr) {
+    case 14: SSYM_SPOT_LAUNCH(14); break;
+    case 16: SSYM_SPOT_LAUNCH(16); break;
+    case 40: SSYM_SPOT_LAUNCH(40); break;
+    default: SSYM_SPOT_LAUNCH(64); break;
+    }
+#undef SSYM_SPOT_LAUNCH
+    SSYM_HIP_CHECK(ctx, hipGetLastError());
+    return SSYM_OK;
+}
+
+int32_t spot_limits(ssym_ctx *ctx, const char *fn, uint64_t maxFb, uint32_t dim)
+{
+    if (maxFb > (uint64_t)kSpotMaxTargetFrames || dim > (uint32_t)kSpotMaxDim) {
+        ctx->err = std::string(fn) + ": a target has more than " + std::to_string(kSpotMaxTargetFrames) +
+                   " frames, or frames have more than " + std::to_string(kSpotMaxDim) + " values";
+        return SSYM_E_UNSUPPORTED;
+    }
+    return SSYM_OK;
+}
+
+int32_t dtw_spot(ssym_ctx *ctx, const ssym_dict *dict, const ssym_queries *q, const uint32_t *src_idx,
+                 const uint32_t *tgt_idx, uint32_t n_pairs, uint32_t index_base, double *out_cost, uint32_t *out_start,
+                 uint32_t *out_end, uint32_t flags)
+{
+    if (!ctx)
+        return SSYM_E_INVALID;
+    int32_t rc = spot_check_ctx(ctx, "ssym_dtw_spot");
+    if (rc != SSYM_OK)
+        return rc;
+    if (!dict || !q) {
+        ctx->err = "ssym_dtw_spot: dictionary or queries handle is NULL";
+        return SSYM_E_INVALID;
+    }
+    if (n_pairs == 0)
+        return SSYM_OK;
+    if (!src_idx) {
+        ctx->err = "ssym_dtw_spot: src_idx is NULL";
+        return SSYM_E_INVALID;
+    }
+    const SegmentSet &src = dict->set, &tgt = q->set;
+    if (src.n == 0) {
+        ctx->err = "empty dictionary";
+        return SSYM_E_EMPTY_DICT;
+    }
+    if (src.dim != tgt.dim) {
+        ctx->err = "dim mismatch between dictionary and targets";
+        return SSYM_E_INVALID;
+    }
+    if (!tgt_idx && n_pairs > tgt.n) {
+        ctx->err = "ssym_dtw_spot: tgt_idx is NULL and n_pairs exceeds the number of targets";
+        return SSYM_E_INVALID;
+    }
+    if (!out_cost || !out_start || !out_end) {
+        ctx->err = "ssym_dtw_spot: out_cost, out_start and out_end must not be NULL";
+        return SSYM_E_INVALID;
+    }
+    // the pair list and the shape limits: on the host, before any device work
+    std::vector<uint2> pairs(n_pairs);
+    uint64_t maxFb = 0;
+    for (uint32_t p = 0; p < n_pairs; ++p) {
+        if (src_idx[p] != SSYM_NO_MATCH && (src_idx[p] < index_base || src_idx[p] - index_base >= src.n)) {
+            ctx->err = "ssym_dtw_spot: src_idx[" + std::to_string(p) + "] is outside the dictionary";
+            return SSYM_E_INVALID;
+        }
+        if (tgt_idx && tgt_idx[p] >= tgt.n) {
+            ctx->err = "ssym_dtw_spot: tgt_idx[" + std::to_string(p) + "] is outside the targets";
+            return SSYM_E_INVALID;
+        }
+        const uint32_t s = src_idx[p] == SSYM_NO_MATCH ? SSYM_NO_MATCH : src_idx[p] - index_base;
+        const uint32_t t = tgt_idx ? tgt_idx[p] : p;
+        pairs[p] = make_uint2(s, t);
+        if (s != SSYM_NO_MATCH && src.h_off[s + 1] > src.h_off[s])
+            maxFb = std::max(maxFb, tgt.h_off[t + 1] - tgt.h_off[t]);
+    }
+    rc = spot_limits(ctx, "ssym_dtw_spot", maxFb, src.dim);
+    if (rc != SSYM_OK)
+        return rc;
+    SSYM_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    const bool outDev = (flags & SSYM_OUT_DEVICE) != 0;
+
+    Blocks bl(ctx);
+    uint2 *dPairs = nullptr;
+    double *dCost = out_cost;
+    uint32_t *dStart = out_start, *dEnd = out_end;
+    rc = bl.get(&dPairs, n_pairs);
+    if (!outDev) {
+        if (rc == SSYM_OK)
+            rc = bl.get(&dCost, n_pairs);
+        if (rc == SSYM_OK)
+            rc = bl.get(&dStart, 2 * (size_t)n_pairs);
+        dEnd = dStart + n_pairs;
+    }
+    if (rc != SSYM_OK)
+        return rc;
+    SSYM_HIP_CHECK(ctx, hipMemcpyAsync(dPairs, pairs.data(), sizeof(uint2) * n_pairs, hipMemcpyHostToDevice, st));
+    SSYM_HIP_CHECK(ctx, hipEventRecord(ctx->ev[0], st));
+    rc = launch_spot(ctx, src, tgt, dPairs, n_pairs, maxFb, dCost, dStart, dEnd);
+    if (rc != SSYM_OK)
+        return rc;
+    SSYM_HIP_CHECK(ctx, hipEventRecord(ctx->ev[1], st));
+    std::vector<uint32_t> hSpan;
+    if (!outDev) {
+        hSpan.resize(2 * (size_t)n_pairs);
+        SSYM_HIP_CHECK(ctx, hipMemcpyAsync(out_cost, dCost, sizeof(double) * n_pairs, hipMemcpyDeviceToHost, st));
+        SSYM_HIP_CHECK(ctx, hipMemcpyAsync(hSpan.data(), dStart, sizeof(uint32_t) * 2 * n_pairs, hipMemcpyDeviceToHost, st));
+    }
+    SSYM_HIP_CHECK(ctx, hipStreamSynchronize(st));
+    if (!outDev) {
+        std::copy(hSpan.begin(), hSpan.begin() + n_pairs, out_start);
+        std::copy(hSpan.begin() + n_pairs, hSpan.end(), out_end);
+    }
+    ssym_timings tm{};
+    tm.main_ms = tm.total_ms = ev_ms(ctx->ev[0], ctx->ev[1]);
+    tm.main_launches = 1;
+    tm.n_pairs = n_pairs;
+    ctx->timings = tm;
+    return SSYM_OK;
+}
+
+int32_t spot_queries(ssym_ctx *ctx, const ssym_dict *dict, const ssym_queries *q, uint32_t index_base, uint32_t *out_idx,
+                     double *out_cost, uint32_t *out_start, uint32_t *out_end, uint32_t flags)
+{
+    if (!ctx)
+        return SSYM_E_INVALID;
+    int32_t rc = spot_check_ctx(ctx, "ssym_spot_queries");
+    if (rc != SSYM_OK)
+        return rc;
+    if (!dict || !q) {
+        ctx->err = "ssym_spot_queries: dictionary or queries handle is NULL";
+        return SSYM_E_INVALID;
+    }
+    const SegmentSet &src = dict->set, &tgt = q->set;
+    const uint32_t N = src.n, M = tgt.n;
+    if (M == 0)
+        return SSYM_OK;
+    if (N == 0) {
+        ctx->err = "empty dictionary";
+        return SSYM_E_EMPTY_DICT;
+    }
+    if (src.dim != tgt.dim) {
+        ctx->err = "dim mismatch between dictionary and targets";
+        return SSYM_E_INVALID;
+    }
+    if (!out_idx || !out_cost || !out_start || !out_end) {
+        ctx->err = "ssym_spot_queries: out_idx, out_cost, out_start and out_end must not be NULL";
+        return SSYM_E_INVALID;
+    }
+    if ((uint64_t)N * M > 0xffffffffull) {
+        ctx->err = "ssym_spot_queries: more than 2^32 - 1 (source, target) pairs in one call";
+        return SSYM_E_UNSUPPORTED;
+    }
+    const uint64_t maxFb = src.max_frames ? tgt.max_frames : 0;      // (sources without frames: nothing to run)
+    rc = spot_limits(ctx, "ssym_spot_queries", maxFb, src.dim);
+    if (rc != SSYM_OK)
+        return rc;
+    SSYM_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    const bool outDev = (flags & SSYM_OUT_DEVICE) != 0;
+    const uint32_t nPairs = N * M;
+
+    Blocks bl(ctx);
+    double *mCost = nullptr, *dCost = out_cost;
+    uint32_t *mSpan = nullptr, *dIdx = out_idx, *dStart = out_start, *dEnd = out_end;
+    rc = bl.get(&mCost, nPairs);
+    if (rc == SSYM_OK)
+        rc = bl.get(&mSpan, 2 * (size_t)nPairs);
+    if (!outDev) {
+        if (rc == SSYM_OK)
+            rc = bl.get(&dCost, M);
+        if (rc == SSYM_OK)
+            rc = bl.get(&dIdx, 3 * (size_t)M);
+        dStart = dIdx + M;
+        dEnd = dIdx + 2 * (size_t)M;
+    }
+    if (rc != SSYM_OK)
+        return rc;
+    SSYM_HIP_CHECK(ctx, hipEventRecord(ctx->ev[0], st));
+    rc = launch_spot(ctx, src, tgt, nullptr, nPairs, maxFb, mCost, mSpan, mSpan + nPairs);
+    if (rc != SSYM_OK)
+        return rc;
+    SSYM_HIP_CHECK(ctx, hipEventRecord(ctx->ev[1], st));
+    spot_fold_kernel<<<(M + 255) / 256, 256, 0, st>>>(mCost, mSpan, mSpan + nPairs, N, M, index_base, dIdx, dCost, dStart,
+                                                      dEnd);
+    SSYM_HIP_CHECK(ctx, hipGetLastError());
+    SSYM_HIP_CHECK(ctx, hipEventRecord(ctx->ev[2], st));
+    std::vector<uint32_t> hWords;
+    if (!outDev) {
+        hWords.resize(3 * (size_t)M);
+        SSYM_HIP_CHECK(ctx, hipMemcpyAsync(out_cost, dCost, sizeof(double) * M, hipMemcpyDeviceToHost, st));
+        SSYM_HIP_CHECK(ctx, hipMemcpyAsync(hWords.data(), dIdx, sizeof(uint32_t) * 3 * M, hipMemcpyDeviceToHost, st));
+    }
+    SSYM_HIP_CHECK(ctx, hipStreamSynchronize(st));
+    if (!outDev) {
+        std::copy(hWords.begin(), hWords.begin() + M, out_idx);
+        std::copy(hWords.begin() + M, hWords.begin() + 2 * (size_t)M, out_start);
+        std::copy(hWords.begin() + 2 * (size_t)M, hWords.end(), out_end);
+    }
+    ssym_timings tm{};
+    tm.main_ms = ev_ms(ctx->ev[0], ctx->ev[1]);
+    tm.reduce_ms = ev_ms(ctx->ev[1], ctx->ev[2]);
+    tm.total_ms = ev_ms(ctx->ev[0], ctx->ev[2]);
+    tm.main_launches = 1;
+    tm.n_pairs = nPairs;
+    ctx->timings = tm;
+    return SSYM_OK;
+}
+
+}  // namespace
+}  // namespace ssym
+
+using namespace ssym;
+
+extern "C" {
+
+int32_t ssym_dtw_spot(ssym_ctx *ctx, const ssym_dict *dict, const ssym_queries *q, const uint32_t *src_idx,
+                      const uint32_t *tgt_idx, uint32_t n_pairs, uint32_t index_base, double *out_cost,
+                      uint32_t *out_start, uint32_t *out_end, uint32_t flags)
+{
+    return guarded(ctx, [&]() -> int32_t {
+        return dtw_spot(ctx, dict, q, src_idx, tgt_idx, n_pairs, index_base, out_cost, out_start, out_end, flags);
+    });
+}
+
+int32_t ssym_spot_queries(ssym_ctx *ctx, const ssym_dict *dict, const ssym_queries *q, uint32_t index_base,
+                          uint32_t *out_idx, double *out_cost, uint32_t *out_start, uint32_t *out_end, uint32_t flags)
+{
+    return guarded(ctx, [&]() -> int32_t {
+        return spot_queries(ctx, dict, q, index_base, out_idx, out_cost, out_start, out_end, flags);
+    });
+}
+
+}  // extern "C"

@@ -690,6 +690,51 @@ class Engine:
                                            fmap.data_ptr(), nat.OUT_DEVICE), self.ctx)
         return cost[:n], length[:n], path[:2 * int(p_off[-1])], fmap[:int(m_off[-1])], p_off, m_off
 
+    def dtw_spot(self, d: _Handle, q: _Handle, src_idx, tgt_idx=None, index_base: int = 0):
+        """ssym_dtw_spot (subsequence DTW; dtw engines without a band): for every listed pair (source src_idx[p] -
+        index_base, target tgt_idx[p], or target p without tgt_idx) the span of the source's frames the target aligns
+        with best, by the definition in include/soundsym_amd.h.  Returns (cost f64 [n], start uint32 [n], end uint32
+        [n]); end is inclusive; a pair without a spot has cost +inf and start = end = NO_MATCH.  The cost is not
+        normalised by any length."""
+        src, tgt = _align_indices(src_idx, tgt_idx)
+        n = src.size
+        cost = np.zeros(n, dtype=np.float64)
+        start = np.zeros(n, dtype=np.uint32)
+        end = np.zeros(n, dtype=np.uint32)
+        rc = nat.lib().ssym_dtw_spot(self.ctx, d.ptr, q.ptr, src.ctypes.data, tgt.ctypes.data if tgt is not None else None,
+                                     n, index_base, cost.ctypes.data, start.ctypes.data, end.ctypes.data, 0)
+        nat.check(rc, self.ctx)
+        return cost, start, end
+
+    def dtw_spot_device(self, d: _Handle, q: _Handle, src_idx, tgt_idx=None, index_base: int = 0):
+        """ssym_dtw_spot with SSYM_OUT_DEVICE: (cost f64 [n], start i32 [n], end i32 [n]) as torch tensors in device
+        memory (torch only owns the memory; the 32-bit tensors hold the call's u32 values)."""
+        import torch
+        src, tgt = _align_indices(src_idx, tgt_idx)
+        n = src.size
+        dev = torch.device("cuda", self.device)
+        cost = torch.empty(max(n, 1), dtype=torch.float64, device=dev)
+        start = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
+        end = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
+        nat.check(nat.lib().ssym_dtw_spot(self.ctx, d.ptr, q.ptr, src.ctypes.data,
+                                          tgt.ctypes.data if tgt is not None else None, n, index_base, cost.data_ptr(),
+                                          start.data_ptr(), end.data_ptr(), nat.OUT_DEVICE), self.ctx)
+        return cost[:n], start[:n], end[:n]
+
+    def spot_queries(self, d: _Handle, q: _Handle, index_base: int = 0):
+        """ssym_spot_queries: every dictionary segment spotted against every target, then the first least cost per
+        target over ascending segment index.  Returns (idx uint32 [m] (+ index_base; NO_MATCH where no segment has a
+        spot), cost f64 [m], start uint32 [m], end uint32 [m]) -- the span is the winning segment's."""
+        m = q.n
+        idx = np.zeros(m, dtype=np.uint32)
+        cost = np.zeros(m, dtype=np.float64)
+        start = np.zeros(m, dtype=np.uint32)
+        end = np.zeros(m, dtype=np.uint32)
+        rc = nat.lib().ssym_spot_queries(self.ctx, d.ptr, q.ptr, index_base, idx.ctypes.data, cost.ctypes.data,
+                                         start.ctypes.data, end.ctypes.data, 0)
+        nat.check(rc, self.ctx)
+        return idx, cost, start, end
+
     # -- feature front-end (F3) --------------------------------------------------------------
     def mfcc(self, samples, sample_rate: float, ncoeffs: int = 12, f_lo: float = 100.0, f_hi: float = 8000.0,
              pad_tail: bool = False, want_mean: bool = False):
