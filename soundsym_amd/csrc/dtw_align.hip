@@ -4,29 +4,22 @@
 // Role on the path: ssym_match_* answer "how far apart"; this answers "which frame goes with which" for the pairs a
 // match has chosen (thousands after one ssym_match_queries), in one launch and one synchronisation.
 //
-// Arithmetic: D is formed exactly as dtw_exact.hip forms it (f64, k ascending, sub / mul / add rounded separately,
-// the square root rounded separately, c + min3 with min3's comparisons in the same order), so D(Fa-1, Fb-1) has
-// the bits ssym_pair_matrix(exact = 1) returns.  The backward rule compares those exact values:
-//   dg = D(i-1,j-1), up = D(i-1,j), lf = D(i,j-1):  diagonal if dg <= up && dg <= lf, else up if up <= lf, else left.
+// Arithmetic: dtw_wave.hpp's, so D(Fa-1, Fb-1) has the bits ssym_pair_matrix(exact = 1) returns; the backward rule is
+// its predecessor rule on those exact values.
 //
 // Mapping: one wave per pair, grid-stride over the list.
-//   forward   anti-diagonal wavefront over 64-row chunks as in dtw_exact_reg_kernel (lane = row, the row above by a
-//             DPP move, a chunk's bottom row handed to the next chunk through ONE LDS row that is overwritten in
-//             place: lane 63 writes column tau - 63 while lane 0 reads columns tau and tau - 1).  The lane's source
-//             frame sits in registers; target frames pass through an LDS ring of 128 frames that is refilled 64
-//             frames at a time (at step tau the lanes read columns tau - 63 ... tau), so the LDS a pair needs does
-//             not grow with the target.  Each lane has dg, up, lf in registers when it forms min3; the 2-bit step
-//             code goes into a dword of 16 codes per row, stored when full.  The direction matrix (Fa x ceil(Fb / 16)
-//             dwords) lives in LDS when it fits kAlignDirLdsBytes, else in this workgroup's slab of global scratch.
+//   forward   dtw_wave.hpp's wavefront, inside the band if there is one, from a virtual D(-1,-1) = 0.  Each lane has
+//             dg, up, lf in registers when it forms min3; the 2-bit step code goes into a dword of 16 codes per row,
+//             stored when full.  The direction matrix (Fa x ceil(Fb / 16) dwords) lives in LDS when it fits
+//             kAlignDirLdsBytes, else in this workgroup's slab of global scratch.
 //   backward  lane 0 walks the codes from (Fa-1, Fb-1) to (0, 0): one dependent read per step, one code byte into
 //             LDS per step.  Other waves of the CU hide it (a pair of 128 x 128 frames takes about 20 KB of LDS).
 //   output    the wave turns the reversed code string into cells with two ballots per 64 steps (i and j of path
 //             position f are the numbers of row / column steps before f) and writes the path in forward order and
 //             the map (the first cell of every column) with coalesced vector stores.
-#include "ssym_internal.hpp"
+#include "dtw_wave.hpp"
 
 #include <algorithm>
-#include <cmath>
 
 namespace ssym {
 
@@ -37,21 +30,8 @@ constexpr int kAlignMaxDim = 64;
 constexpr int kAlignDirLdsBytes = 16384;
 // global scratch of one call: at most this many bytes of direction slabs (one per workgroup)
 constexpr size_t kAlignScratchBytes = (size_t)512 << 20;
-constexpr int kAlignRing = 128;             // target frames resident in LDS (two blocks of 64)
 
 namespace {
-
-__device__ __forceinline__ double align_shfl_up1(double v)     // lane - 1's value (dtw_exact.hip: DPP wave_shr:1)
-{
-    int lo = __double2loint(v), hi = __double2hiint(v);
-    lo = __builtin_amdgcn_update_dpp(lo, lo, 0x138, 0xf, 0xf, false);
-    hi = __builtin_amdgcn_update_dpp(hi, hi, 0x138, 0xf, 0xf, false);
-    return __hiloint2double(hi, lo);
-}
-
-// LDS row stride of the ring: 2 (mod 4) doubles, so 128-bit reads by consecutive lanes tile the banks (dtw_exact.hip)
-template <int DIMR>
-constexpr int align_ld() { return DIMR % 4 == 2 ? DIMR : DIMR + 2; }
 
 struct AlignArgs {
     const double *srcRaw;
@@ -80,8 +60,7 @@ template <int DIMR>
 __global__ __launch_bounds__(64) void dtw_align_kernel(const AlignArgs a)
 {
     extern __shared__ __attribute__((aligned(16))) double smem[];
-    constexpr int LD = align_ld<DIMR>();
-    typedef double d2 __attribute__((ext_vector_type(2)));
+    constexpr int LD = wave_ld(DIMR);
     double *bound = smem;                                           // [fbCap]   bottom row of the chunk above
     double *ring = smem + a.fbCap;                                  // [ringRows][LD]
     unsigned char *codes = reinterpret_cast<unsigned char *>(ring + (size_t)a.ringRows * LD);     // [codeCap]
@@ -120,7 +99,7 @@ __global__ __launch_bounds__(64) void dtw_align_kernel(const AlignArgs a)
             const bool rowValid = r < Fa;
             const int rowsHere = min(64, Fa - c0);
             double ar[DIMR];
-            {
+            {   // wave_load_frame's text: see the note at the ring refill below
                 const double *arow = a0 + (size_t)(rowValid ? r : c0) * dim;
 #pragma unroll
                 for (int e = 0; e < DIMR; ++e)
@@ -137,8 +116,8 @@ __global__ __launch_bounds__(64) void dtw_align_kernel(const AlignArgs a)
             const int tauEnd = jhi + rowsHere;     // exclusive: lane l works on column tau - l
             for (int tau = jlo; tau < tauEnd; ++tau) {
                 if (tau == jlo || (tau & 63) == 0) {
-                    // the 64 target frames from column (tau & ~63) on enter the ring; the block they replace ended
-                    // at column (tau & ~63) - 65, and the lanes still read from column tau - 63 on
+                    // wave_refill(..., tau & ~63), written out: called as functions, this and the frame load above
+                    // change the register allocation of this kernel (not of dtw_spot_kernel) and <40> runs 1 - 3 % slower
                     const int f0 = tau & ~63;
                     const int cnt = min(64, Fb - f0);
                     __syncthreads();
@@ -149,27 +128,8 @@ __global__ __launch_bounds__(64) void dtw_align_kernel(const AlignArgs a)
                     __syncthreads();
                 }
                 const int j = tau - lane;
-                const int jc = min(max(j, 0), Fb - 1);
-                const d2 *bp = reinterpret_cast<const d2 *>(ring + (size_t)((uint32_t)jc & ringMask) * LD);
-                // sum_k (a_k - b_k)^2, k ascending, sub / mul / add rounded separately (the oracle's order); the
-                // zero padding adds +0.0 to a non-negative sum and leaves its bits alone
-                double acc = 0.0;
-#pragma unroll
-                for (int e0 = 0; e0 < DIMR; e0 += 8) {
-                    d2 bv[4];
-#pragma unroll
-                    for (int v = 0; v < 4; ++v)
-                        if (e0 + 2 * v < DIMR)
-                            bv[v] = bp[e0 / 2 + v];
-#pragma unroll
-                    for (int v = 0; v < 8; ++v)
-                        if (e0 + v < DIMR) {
-                            const double df = __dsub_rn(ar[e0 + v], bv[v / 2][v % 2]);
-                            acc = __dadd_rn(acc, __dmul_rn(df, df));
-                        }
-                }
-                const double c = a.squared ? acc : sqrt(acc);
-                double up = align_shfl_up1(mine);         // D(r-1, j) for lanes >= 1
+                const double c = wave_cell_cost(ar, ring, ringMask, min(max(j, 0), Fb - 1), a.squared);
+                double up = shfl_up1(mine);               // D(r-1, j) for lanes >= 1
                 double dg = diagReg;
                 if (lane == 0) {
                     if (c0 == 0) {
@@ -185,13 +145,8 @@ __global__ __launch_bounds__(64) void dtw_align_kernel(const AlignArgs a)
                     double cur = INF;
                     const int dij = r - j;
                     if (band < 0 || (dij <= band && -dij <= band)) {
-                        double best = up;                     // D(i-1, j)      (dtw_exact.hip's order)
-                        if (mine < best) best = mine;         // D(i,   j-1)
-                        if (dg < best) best = dg;             // D(i-1, j-1)
-                        cur = __dadd_rn(c, best);
-                        // the backward rule: ties prefer the diagonal, then the source step
-                        const uint32_t code = (dg <= up && dg <= mine) ? 0u : (up <= mine ? 1u : 2u);
-                        pack |= code << (2 * (j & 15));
+                        cur = __dadd_rn(c, wave_min3(up, mine, dg));
+                        pack |= wave_pred(up, mine, dg) << (2 * (j & 15));
                     }
                     if (j <= jhi && ((j & 15) == 15 || j == jhi)) {     // (columns beyond jhi are outside every row's band)
                         const size_t w = (size_t)r * rowWords + ((uint32_t)j >> 4);
@@ -279,45 +234,6 @@ inline void align_capacity(const SegmentSet &src, const SegmentSet &tgt, uint32_
     *frames = fb;
 }
 
-// the argument checks ssym_dtw_align_sizes and ssym_dtw_align share (err: where the message goes)
-int32_t align_check(std::string &err, const ssym_dict *dict, const ssym_queries *q, const uint32_t *src_idx,
-                    const uint32_t *tgt_idx, uint32_t n_pairs, uint32_t index_base)
-{
-    if (!dict || !q) {
-        err = "ssym_dtw_align: dictionary or queries handle is NULL";
-        return SSYM_E_INVALID;
-    }
-    if (n_pairs == 0)
-        return SSYM_OK;
-    if (!src_idx) {
-        err = "ssym_dtw_align: src_idx is NULL";
-        return SSYM_E_INVALID;
-    }
-    if (dict->set.n == 0) {
-        err = "empty dictionary";
-        return SSYM_E_EMPTY_DICT;
-    }
-    if (dict->set.dim != q->set.dim) {
-        err = "dim mismatch between dictionary and targets";
-        return SSYM_E_INVALID;
-    }
-    if (!tgt_idx && n_pairs > q->set.n) {
-        err = "ssym_dtw_align: tgt_idx is NULL and n_pairs exceeds the number of targets";
-        return SSYM_E_INVALID;
-    }
-    for (uint32_t p = 0; p < n_pairs; ++p) {
-        if (src_idx[p] != SSYM_NO_MATCH && (src_idx[p] < index_base || src_idx[p] - index_base >= dict->set.n)) {
-            err = "ssym_dtw_align: src_idx[" + std::to_string(p) + "] is outside the dictionary";
-            return SSYM_E_INVALID;
-        }
-        if (tgt_idx && tgt_idx[p] >= q->set.n) {
-            err = "ssym_dtw_align: tgt_idx[" + std::to_string(p) + "] is outside the targets";
-            return SSYM_E_INVALID;
-        }
-    }
-    return SSYM_OK;
-}
-
 int32_t dtw_align(ssym_ctx *ctx, const ssym_dict *dict, const ssym_queries *q, const uint32_t *src_idx,
                   const uint32_t *tgt_idx, uint32_t n_pairs, uint32_t index_base, double *out_cost, uint32_t *out_len,
                   const uint64_t *path_offsets, uint32_t *out_path, const uint64_t *map_offsets, uint32_t *out_map,
@@ -329,7 +245,7 @@ int32_t dtw_align(ssym_ctx *ctx, const ssym_dict *dict, const ssym_queries *q, c
         ctx->err = "ssym_dtw_align: the context's metric is refcos, which has no alignment";
         return SSYM_E_UNSUPPORTED;
     }
-    int32_t rc = align_check(ctx->err, dict, q, src_idx, tgt_idx, n_pairs, index_base);
+    int32_t rc = check_pair_list(ctx->err, "ssym_dtw_align", dict, q, src_idx, tgt_idx, n_pairs, index_base);
     if (rc != SSYM_OK)
         return rc;
     if (n_pairs == 0)
@@ -343,11 +259,9 @@ int32_t dtw_align(ssym_ctx *ctx, const ssym_dict *dict, const ssym_queries *q, c
     std::vector<uint2> pairs(n_pairs);
     uint64_t maxFa = 0, maxFb = 0, maxSlab = 0;
     for (uint32_t p = 0; p < n_pairs; ++p) {
-        const uint32_t s = src_idx[p] == SSYM_NO_MATCH ? SSYM_NO_MATCH : src_idx[p] - index_base;
-        const uint32_t t = tgt_idx ? tgt_idx[p] : p;
-        pairs[p] = make_uint2(s, t);
+        pairs[p] = pair_at(src_idx, tgt_idx, index_base, p);
         uint64_t steps, frames;
-        align_capacity(src, tgt, s, t, &steps, &frames);
+        align_capacity(src, tgt, pairs[p].x, pairs[p].y, &steps, &frames);
         if (path_offsets[p + 1] < path_offsets[p] || path_offsets[p + 1] - path_offsets[p] < steps ||
             (out_map && (map_offsets[p + 1] < map_offsets[p] || map_offsets[p + 1] - map_offsets[p] < frames))) {
             ctx->err = "ssym_dtw_align: offsets of pair " + std::to_string(p) +
@@ -398,13 +312,12 @@ int32_t dtw_align(ssym_ctx *ctx, const ssym_dict *dict, const ssym_queries *q, c
         if (rc == SSYM_OK && out_map)
             rc = bl.get(&dMap, (size_t)mapTotal);
     }
-    const uint32_t fbEven = ((uint32_t)std::max<uint64_t>(maxFb, 1) + 1) & ~1u;
-    const int dimr = src.dim <= 14 ? 14 : src.dim <= 16 ? 16 : src.dim <= 40 ? 40 : 64;
-    const int ld = dimr % 4 == 2 ? dimr : dimr + 2;       // align_ld<>
-    a.ringRows = maxFb <= 64 ? 64 : kAlignRing;
+    const int dimr = wave_dimr(src.dim);
+    a.fbCap = wave_fb_cap(maxFb);
+    a.ringRows = wave_ring_rows(maxFb);
     a.codeCap = ((uint32_t)(maxFa + maxFb) + 15) & ~15u;
     a.dirLdsBytes = (uint32_t)std::min<uint64_t>((uint64_t)kAlignDirLdsBytes, (maxFa * ((maxFb + 15) / 16) * 4 + 15) & ~15ull);
-    const size_t lds = (size_t)fbEven * sizeof(double) + (size_t)a.ringRows * ld * sizeof(double) + a.codeCap + a.dirLdsBytes;
+    const size_t lds = (size_t)a.fbCap * sizeof(double) + wave_ring_bytes(a.ringRows, dimr) + a.codeCap + a.dirLdsBytes;
     unsigned grid = (unsigned)std::min<uint64_t>(n_pairs, (uint64_t)ctx->num_cus * 8);
     if (maxSlab) {
         // one slab per workgroup, as many workgroups as kAlignScratchBytes holds (128 for a 4096 x 4096 pair)
@@ -432,23 +345,9 @@ int32_t dtw_align(ssym_ctx *ctx, const ssym_dict *dict, const ssym_queries *q, c
     a.len = dLen;
     a.path = reinterpret_cast<uint2 *>(dPath);
     a.map = dMap;
-    a.fbCap = fbEven;
-#define SSYM_ALIGN_LAUNCH(D_)                                                                                  \
-    do {                                                                                                       \
-        auto kern = dtw_align_kernel<D_>;                                                                      \
-        if (lds > 64 * 1024)                                                                                   \
-            SSYM_HIP_CHECK(ctx, hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                                    (int)lds));                                                \
-        kern<<<grid, 64, lds, st>>>(a);                                                                        \
-    } while (0)
-    switch (dimr) {
-    case 14: SSYM_ALIGN_LAUNCH(14); break;
-    case 16: SSYM_ALIGN_LAUNCH(16); break;
-    case 40: SSYM_ALIGN_LAUNCH(40); break;
-    default: SSYM_ALIGN_LAUNCH(64); break;
-    }
-#undef SSYM_ALIGN_LAUNCH
-    SSYM_HIP_CHECK(ctx, hipGetLastError());
+    rc = wave_launch(ctx, SSYM_WAVE_KERNEL(dtw_align_kernel, dimr), grid, lds, a);
+    if (rc != SSYM_OK)
+        return rc;
     if (outDev) {
         SSYM_HIP_CHECK(ctx, hipStreamSynchronize(st));
         return SSYM_OK;
@@ -490,16 +389,16 @@ int32_t ssym_dtw_align_sizes(const ssym_dict *dict, const ssym_queries *q, const
 {
     return guarded(nullptr, [&]() -> int32_t {
         std::string err;
-        const int32_t rc = align_check(err, dict, q, src_idx, tgt_idx, n_pairs, index_base);
+        const int32_t rc = check_pair_list(err, "ssym_dtw_align", dict, q, src_idx, tgt_idx, n_pairs, index_base);
         if (rc != SSYM_OK)
             return rc;
         if (!path_offsets || !map_offsets)
             return SSYM_E_INVALID;
         path_offsets[0] = map_offsets[0] = 0;
         for (uint32_t p = 0; p < n_pairs; ++p) {
+            const uint2 pr = pair_at(src_idx, tgt_idx, index_base, p);
             uint64_t steps, frames;
-            align_capacity(dict->set, q->set, src_idx[p] == SSYM_NO_MATCH ? SSYM_NO_MATCH : src_idx[p] - index_base,
-                           tgt_idx ? tgt_idx[p] : p, &steps, &frames);
+            align_capacity(dict->set, q->set, pr.x, pr.y, &steps, &frames);
             path_offsets[p + 1] = path_offsets[p] + steps;
             map_offsets[p + 1] = map_offsets[p] + frames;
         }

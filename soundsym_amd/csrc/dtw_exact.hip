@@ -13,23 +13,12 @@
 // by a wave shuffle, D(i-1, j-1) is the value shuffled in one step earlier, D(i, j-1) is the
 // lane's own previous value.  The bottom row of a chunk is handed to the next chunk through LDS.
 // Both segments' frames are staged in LDS when they fit, else read through L1/L2.
-#include "ssym_internal.hpp"
+#include "dtw_wave.hpp"
 
 #include <algorithm>
 #include <type_traits>
 
 namespace ssym {
-
-// value of lane - 1 (lane 0 keeps its own): one DPP move per half (wave_shr:1, gfx9 encoding 0x138)
-// instead of a ds_bpermute round trip through the LDS crossbar -- the shuffle sits on the critical
-// path of every anti-diagonal step
-__device__ __forceinline__ double shfl_up1(double v)
-{
-    int lo = __double2loint(v), hi = __double2hiint(v);
-    lo = __builtin_amdgcn_update_dpp(lo, lo, 0x138, 0xf, 0xf, false);
-    hi = __builtin_amdgcn_update_dpp(hi, hi, 0x138, 0xf, 0xf, false);
-    return __hiloint2double(hi, lo);
-}
 
 template <bool LDS_FRAMES>
 __global__ __launch_bounds__(64) void dtw_exact_kernel(
@@ -197,7 +186,7 @@ constexpr int exact_ld(bool f32)
 {
     // row stride in elements: 16-byte aligned rows whose 128-bit reads by consecutive lanes tile the banks
     return f32 ? ((DIMR + 3) / 4 * 4) + ((((DIMR + 3) / 4 * 4) % 8 == 4) ? 0 : 4)      // = 4 (mod 8) floats
-               : ((DIMR % 4 == 2) ? DIMR : DIMR + 2);                                     // = 2 (mod 4) doubles
+               : wave_ld(DIMR);                                                           // = 2 (mod 4) doubles
 }
 
 template <int DIMR, int PARTS = 1, typename BT = double>
@@ -1013,7 +1002,7 @@ int32_t launch_dtw_exact(ssym_ctx *ctx, const SegmentSet &src, const SegmentSet 
                                                                                                    : dim <= 96 ? 96 : 0;
     const bool bf32 = ctx->dtype == SSYM_DTYPE_F32;     // every feature buffer of the context was f32: exact in float
     const int up4 = (dimr + 3) / 4 * 4;
-    const int ldr = bf32 ? up4 + (up4 % 8 == 4 ? 0 : 4) : ((dimr % 4 == 2) ? dimr : dimr + 2);   // exact_ld<>
+    const int ldr = bf32 ? up4 + (up4 % 8 == 4 ? 0 : 4) : wave_ld(dimr);     // exact_ld<>
     // staged target rows: all of them, or (banded) the widest window a 64-row chunk can reach
     // (a chunk of 64 rows reaches 64 + 2 r columns; an even count keeps the rows 16-byte aligned.  Two rows of slack here
     // cost configs[4] a workgroup per CU: 6 x 26 KB fit the 160 KB, 5 x 27 KB did)

@@ -12,18 +12,12 @@
 //   end = the smallest i at which D(i,Fb-1) is least (strict <, from +inf: NaN and +inf never win), cost = D(end,Fb-1),
 //   start = st(end,Fb-1).
 //
-// Arithmetic: dtw_exact.hip's and dtw_align.hip's (f64, k ascending, sub / mul / add rounded separately, the square root
-// rounded separately, c + min3 with min3's comparisons in the same order).
-//
-// Mapping: one wave per pair, grid-stride over the list; dtw_align.hip's forward pass (lane = source row of a 64-row
-// chunk, the row above by a DPP move, the lane's source frame in registers, target frames through an LDS ring of 128
-// frames refilled 64 at a time, a chunk's bottom row handed to the next chunk through ONE LDS row overwritten in place:
-// lane 63 writes column tau - 63 while lane 0 reads columns tau and tau - 1).  Everything carried between lanes and
-// through the hand-off row is a pair (D f64, st u32); the row has Fb entries, so the LDS a pair needs does not grow with
-// the source.  Every lane keeps the best D(r, Fb-1) of its own rows (chunks ascend, strict <: its lowest such row); one
-// wave reduction per pair orders the 64 candidates by (D, row).  No direction matrix, no backward walk: three scalars
-// per pair, written by lane 0.
-#include "ssym_internal.hpp"
+// Arithmetic and mapping: dtw_wave.hpp's wavefront, one wave per pair, grid-stride over the list, with a free start in
+// column 0.  Everything carried between lanes and through the hand-off row is a pair (D f64, st u32); the row has Fb
+// entries, so the LDS a pair needs does not grow with the source.  Every lane keeps the best D(r, Fb-1) of its own rows
+// (chunks ascend, strict <: its lowest such row); one wave reduction per pair orders the 64 candidates by (D, row).  No
+// direction matrix, no backward walk: three scalars per pair, written by lane 0.
+#include "dtw_wave.hpp"
 
 #include <algorithm>
 
@@ -33,22 +27,8 @@ namespace ssym {
 // A source has as many frames as a dictionary segment can (2^31 - 1).
 constexpr int kSpotMaxTargetFrames = 4096;
 constexpr int kSpotMaxDim = 64;
-constexpr int kSpotRing = 128;              // target frames resident in LDS (two blocks of 64)
 
 namespace {
-
-__device__ __forceinline__ int spot_shr1(int v)       // lane - 1's value (DPP wave_shr:1)
-{
-    return __builtin_amdgcn_update_dpp(v, v, 0x138, 0xf, 0xf, false);
-}
-__device__ __forceinline__ double spot_shr1(double v)
-{
-    return __hiloint2double(spot_shr1(__double2hiint(v)), spot_shr1(__double2loint(v)));
-}
-
-// LDS row stride of the ring: 2 (mod 4) doubles, so 128-bit reads by consecutive lanes tile the banks (dtw_exact.hip)
-template <int DIMR>
-constexpr int spot_ld() { return DIMR % 4 == 2 ? DIMR : DIMR + 2; }
 
 struct SpotArgs {
     const double *srcRaw;
@@ -70,8 +50,7 @@ template <int DIMR>
 __global__ __launch_bounds__(64) void dtw_spot_kernel(const SpotArgs a)
 {
     extern __shared__ __attribute__((aligned(16))) double smem[];
-    constexpr int LD = spot_ld<DIMR>();
-    typedef double d2 __attribute__((ext_vector_type(2)));
+    constexpr int LD = wave_ld(DIMR);
     double *boundD = smem;                                          // [fbCap]   bottom row of the chunk above: D ...
     double *ring = smem + a.fbCap;                                  // [ringRows][LD]
     uint32_t *boundS = reinterpret_cast<uint32_t *>(ring + (size_t)a.ringRows * LD);      // [fbCap]   ... and st
@@ -110,53 +89,21 @@ __global__ __launch_bounds__(64) void dtw_spot_kernel(const SpotArgs a)
             const bool rowValid = r < Fa;
             const int rowsHere = (int)min(64u, Fa - c0);
             double ar[DIMR];
-            {
-                const double *arow = a0 + (size_t)(rowValid ? r : c0) * dim;
-#pragma unroll
-                for (int e = 0; e < DIMR; ++e)
-                    ar[e] = e < dim ? arow[e] : 0.0;
-            }
+            wave_load_frame(ar, a0 + (size_t)(rowValid ? r : c0) * dim, dim);
             double mineD = INF;             // D(r, j-1)
             uint32_t mineS = 0xffffffffu;
             double diagD = INF;             // D(r-1, j-1)
             uint32_t diagS = 0xffffffffu;
             const int tauEnd = Fb - 1 + rowsHere;     // exclusive: lane l works on column tau - l
             for (int tau = 0; tau < tauEnd; ++tau) {
-                if ((tau & 63) == 0) {
-                    // the 64 target frames from column tau on enter the ring; the block they replace ended at column
-                    // tau - 65, and the lanes still read from column tau - 63 on.  (The barrier also orders the hand-off
-                    // row: the previous chunk's writes, and the previous pair's reads, are done before tau = 0 goes on.)
-                    const int cnt = min(64, Fb - tau);
-                    __syncthreads();
-                    for (int i = lane; i < cnt * DIMR; i += 64) {
-                        const int fr = i / DIMR, e = i % DIMR;
-                        ring[(size_t)((uint32_t)(tau + fr) & ringMask) * LD + e] = e < dim ? b0[(size_t)(tau + fr) * dim + e] : 0.0;
-                    }
-                    __syncthreads();
-                }
+                // (the refill's barrier also orders the hand-off row: the previous chunk's writes, and the previous pair's
+                // reads, are done before tau = 0 goes on)
+                if ((tau & 63) == 0)
+                    wave_refill<DIMR>(ring, ringMask, b0, dim, Fb, tau);
                 const int j = tau - lane;
-                const int jc = min(max(j, 0), Fb - 1);
-                const d2 *bp = reinterpret_cast<const d2 *>(ring + (size_t)((uint32_t)jc & ringMask) * LD);
-                // sum_k (a_k - b_k)^2, k ascending, sub / mul / add rounded separately (the oracle's order); the
-                // zero padding adds +0.0 to a non-negative sum and leaves its bits alone
-                double acc = 0.0;
-#pragma unroll
-                for (int e0 = 0; e0 < DIMR; e0 += 8) {
-                    d2 bv[4];
-#pragma unroll
-                    for (int v = 0; v < 4; ++v)
-                        if (e0 + 2 * v < DIMR)
-                            bv[v] = bp[e0 / 2 + v];
-#pragma unroll
-                    for (int v = 0; v < 8; ++v)
-                        if (e0 + v < DIMR) {
-                            const double df = __dsub_rn(ar[e0 + v], bv[v / 2][v % 2]);
-                            acc = __dadd_rn(acc, __dmul_rn(df, df));
-                        }
-                }
-                const double c = a.squared ? acc : sqrt(acc);
-                double upD = spot_shr1(mineD);            // D(r-1, j) and its start, for lanes >= 1
-                uint32_t upS = (uint32_t)spot_shr1((int)mineS);
+                const double c = wave_cell_cost(ar, ring, ringMask, min(max(j, 0), Fb - 1), a.squared);
+                double upD = shfl_up1(mineD);             // D(r-1, j) and its start, for lanes >= 1
+                uint32_t upS = (uint32_t)shfl_up1((int)mineS);
                 double dgD = diagD;
                 uint32_t dgS = diagS;
                 if (lane == 0) {
@@ -178,12 +125,9 @@ __global__ __launch_bounds__(64) void dtw_spot_kernel(const SpotArgs a)
                     double cur = c;                       // column 0: a path may start at any source frame
                     uint32_t st = r;
                     if (j > 0) {
-                        double best = upD;                    // D(i-1, j)      (dtw_exact.hip's order)
-                        if (mineD < best) best = mineD;       // D(i,   j-1)
-                        if (dgD < best) best = dgD;           // D(i-1, j-1)
-                        cur = __dadd_rn(c, best);
-                        // the alignment rule: ties prefer the diagonal, then the source step
-                        st = (dgD <= upD && dgD <= mineD) ? dgS : (upD <= mineD ? upS : mineS);
+                        cur = __dadd_rn(c, wave_min3(upD, mineD, dgD));
+                        const uint32_t pred = wave_pred(upD, mineD, dgD);
+                        st = pred == 0u ? dgS : pred == 1u ? upS : mineS;
                     }
                     if (lane == 63) {
                         boundD[j] = cur;
@@ -269,7 +213,6 @@ int32_t spot_check_ctx(ssym_ctx *ctx, const char *fn)
 int32_t launch_spot(ssym_ctx *ctx, const SegmentSet &src, const SegmentSet &tgt, const uint2 *pairs, uint32_t n_pairs,
                     uint64_t maxFb, double *cost, uint32_t *start, uint32_t *end)
 {
-    hipStream_t st = ctx->stream;
     SpotArgs a{};
     a.srcRaw = src.raw;
     a.srcOff = src.off;
@@ -283,30 +226,13 @@ int32_t launch_spot(ssym_ctx *ctx, const SegmentSet &src, const SegmentSet &tgt,
     a.cost = cost;
     a.start = start;
     a.end = end;
-    a.fbCap = ((uint32_t)std::max<uint64_t>(maxFb, 1) + 1) & ~1u;
-    a.ringRows = maxFb <= 64 ? 64 : kSpotRing;
-    const int dimr = src.dim <= 14 ? 14 : src.dim <= 16 ? 16 : src.dim <= 40 ? 40 : 64;
-    const int ld = dimr % 4 == 2 ? dimr : dimr + 2;       // spot_ld<>
+    a.fbCap = wave_fb_cap(maxFb);
+    a.ringRows = wave_ring_rows(maxFb);
+    const int dimr = wave_dimr(src.dim);
     // hand-off row (12 bytes per target frame, at most 48 KiB) + ring (at most 66 KiB)
-    const size_t lds = (size_t)a.fbCap * (sizeof(double) + sizeof(uint32_t)) + (size_t)a.ringRows * ld * sizeof(double);
+    const size_t lds = (size_t)a.fbCap * (sizeof(double) + sizeof(uint32_t)) + wave_ring_bytes(a.ringRows, dimr);
     const unsigned grid = (unsigned)std::min<uint64_t>(n_pairs, (uint64_t)ctx->num_cus * 8);
-#define SSYM_SPOT_LAUNCH(D_)                                                                                   \
-    do {                                                                                                       \
-        auto kern = dtw_spot_kernel<D_>;                                                                       \
-        if (lds > 64 * 1024)                                                                                   \
-            SSYM_HIP_CHECK(ctx, hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                                    (int)lds));                                                \
-        kern<<<grid, 64, lds, st>>>(a);                                                                        \
-    } while (0)
-    switch (dimr) {
-    case 14: SSYM_SPOT_LAUNCH(14); break;
-    case 16: SSYM_SPOT_LAUNCH(16); break;
-    case 40: SSYM_SPOT_LAUNCH(40); break;
-    default: SSYM_SPOT_LAUNCH(64); break;
-    }
-#undef SSYM_SPOT_LAUNCH
-    SSYM_HIP_CHECK(ctx, hipGetLastError());
-    return SSYM_OK;
+    return wave_launch(ctx, SSYM_WAVE_KERNEL(dtw_spot_kernel, dimr), grid, lds, a);
 }
 
 int32_t spot_limits(ssym_ctx *ctx, const char *fn, uint64_t maxFb, uint32_t dim)
@@ -328,48 +254,20 @@ int32_t dtw_spot(ssym_ctx *ctx, const ssym_dict *dict, const ssym_queries *q, co
     int32_t rc = spot_check_ctx(ctx, "ssym_dtw_spot");
     if (rc != SSYM_OK)
         return rc;
-    if (!dict || !q) {
-        ctx->err = "ssym_dtw_spot: dictionary or queries handle is NULL";
-        return SSYM_E_INVALID;
-    }
-    if (n_pairs == 0)
-        return SSYM_OK;
-    if (!src_idx) {
-        ctx->err = "ssym_dtw_spot: src_idx is NULL";
-        return SSYM_E_INVALID;
-    }
-    const SegmentSet &src = dict->set, &tgt = q->set;
-    if (src.n == 0) {
-        ctx->err = "empty dictionary";
-        return SSYM_E_EMPTY_DICT;
-    }
-    if (src.dim != tgt.dim) {
-        ctx->err = "dim mismatch between dictionary and targets";
-        return SSYM_E_INVALID;
-    }
-    if (!tgt_idx && n_pairs > tgt.n) {
-        ctx->err = "ssym_dtw_spot: tgt_idx is NULL and n_pairs exceeds the number of targets";
-        return SSYM_E_INVALID;
-    }
+    rc = check_pair_list(ctx->err, "ssym_dtw_spot", dict, q, src_idx, tgt_idx, n_pairs, index_base);
+    if (rc != SSYM_OK || n_pairs == 0)
+        return rc;
     if (!out_cost || !out_start || !out_end) {
         ctx->err = "ssym_dtw_spot: out_cost, out_start and out_end must not be NULL";
         return SSYM_E_INVALID;
     }
+    const SegmentSet &src = dict->set, &tgt = q->set;
     // the pair list and the shape limits: on the host, before any device work
     std::vector<uint2> pairs(n_pairs);
     uint64_t maxFb = 0;
     for (uint32_t p = 0; p < n_pairs; ++p) {
-        if (src_idx[p] != SSYM_NO_MATCH && (src_idx[p] < index_base || src_idx[p] - index_base >= src.n)) {
-            ctx->err = "ssym_dtw_spot: src_idx[" + std::to_string(p) + "] is outside the dictionary";
-            return SSYM_E_INVALID;
-        }
-        if (tgt_idx && tgt_idx[p] >= tgt.n) {
-            ctx->err = "ssym_dtw_spot: tgt_idx[" + std::to_string(p) + "] is outside the targets";
-            return SSYM_E_INVALID;
-        }
-        const uint32_t s = src_idx[p] == SSYM_NO_MATCH ? SSYM_NO_MATCH : src_idx[p] - index_base;
-        const uint32_t t = tgt_idx ? tgt_idx[p] : p;
-        pairs[p] = make_uint2(s, t);
+        pairs[p] = pair_at(src_idx, tgt_idx, index_base, p);
+        const uint32_t s = pairs[p].x, t = pairs[p].y;
         if (s != SSYM_NO_MATCH && src.h_off[s + 1] > src.h_off[s])
             maxFb = std::max(maxFb, tgt.h_off[t + 1] - tgt.h_off[t]);
     }
@@ -427,22 +325,16 @@ int32_t spot_queries(ssym_ctx *ctx, const ssym_dict *dict, const ssym_queries *q
     int32_t rc = spot_check_ctx(ctx, "ssym_spot_queries");
     if (rc != SSYM_OK)
         return rc;
-    if (!dict || !q) {
-        ctx->err = "ssym_spot_queries: dictionary or queries handle is NULL";
-        return SSYM_E_INVALID;
-    }
+    rc = check_handles(ctx->err, "ssym_spot_queries", dict, q);
+    if (rc != SSYM_OK)
+        return rc;
     const SegmentSet &src = dict->set, &tgt = q->set;
     const uint32_t N = src.n, M = tgt.n;
     if (M == 0)
         return SSYM_OK;
-    if (N == 0) {
-        ctx->err = "empty dictionary";
-        return SSYM_E_EMPTY_DICT;
-    }
-    if (src.dim != tgt.dim) {
-        ctx->err = "dim mismatch between dictionary and targets";
-        return SSYM_E_INVALID;
-    }
+    rc = check_sets(ctx->err, src, tgt);
+    if (rc != SSYM_OK)
+        return rc;
     if (!out_idx || !out_cost || !out_start || !out_end) {
         ctx->err = "ssym_spot_queries: out_idx, out_cost, out_start and out_end must not be NULL";
         return SSYM_E_INVALID;

@@ -1,0 +1,195 @@
+// dtw_wave.hpp -- the anti-diagonal wavefront forward pass dtw_align.hip and dtw_spot.hip share (and the lane - 1 move
+// and ring stride dtw_exact.hip shares with them), each piece written once, plus the pair-list checks of their entry
+// points.  Each kernel keeps its own step loop; what is here is what must not differ between them.  (dtw_align_kernel
+// still carries the text of wave_load_frame and wave_refill in its body, for the reason given there: change them together.)
+//
+// The pass: one wave per pair, grid-stride over the list.  Lane l owns source row c0 + l of a 64-row chunk and works on
+// target column j = tau - l at step tau.  D(i-1, j) comes from lane l - 1 by a DPP move, D(i-1, j-1) is what came one step
+// earlier, D(i, j-1) is the lane's own previous value.  The lane's source frame sits in registers (wave_load_frame);
+// target frames pass through an LDS ring of 128 frames refilled 64 at a time (wave_refill: at step tau the lanes read
+// columns tau - 63 ... tau), so the LDS a pair needs does not grow with the target.  A chunk's bottom row is handed to
+// the next chunk through ONE LDS row overwritten in place: lane 63 writes column tau - 63 while lane 0 reads columns tau
+// and tau - 1 (the kernels' own code: what the row carries differs).  Frames are zero-padded to DIMR = 14 / 16 / 40 / 64.
+//
+// Arithmetic: D is formed exactly as dtw_exact.hip forms it (f64, k ascending, sub / mul / add rounded separately, the
+// square root rounded separately, c + min3 with min3's comparisons in the same order), so a cost has the bits
+// ssym_pair_matrix(exact = 1) returns.  The predecessor rule compares those exact values:
+//   dg = D(i-1,j-1), up = D(i-1,j), lf = D(i,j-1):  diagonal if dg <= up && dg <= lf, else up if up <= lf, else left.
+#pragma once
+#include "ssym_internal.hpp"
+
+#include <algorithm>
+
+namespace ssym {
+
+constexpr int kWaveRing = 128;              // target frames resident in LDS (two blocks of 64)
+
+// ---- device -------------------------------------------------------------------------------------------------------------
+
+// value of lane - 1 (lane 0 keeps its own): one DPP move per half (wave_shr:1, gfx9 encoding 0x138)
+// instead of a ds_bpermute round trip through the LDS crossbar -- the shuffle sits on the critical
+// path of every anti-diagonal step
+__device__ __forceinline__ int shfl_up1(int v) { return __builtin_amdgcn_update_dpp(v, v, 0x138, 0xf, 0xf, false); }
+__device__ __forceinline__ double shfl_up1(double v)
+{
+    int lo = __double2loint(v), hi = __double2hiint(v);
+    lo = __builtin_amdgcn_update_dpp(lo, lo, 0x138, 0xf, 0xf, false);
+    hi = __builtin_amdgcn_update_dpp(hi, hi, 0x138, 0xf, 0xf, false);
+    return __hiloint2double(hi, lo);
+}
+
+// LDS row stride of f64 frames padded to dimr values: 2 (mod 4) doubles, so rows are 16-byte aligned and 128-bit reads
+// by consecutive lanes tile the banks
+constexpr int wave_ld(int dimr) { return dimr % 4 == 2 ? dimr : dimr + 2; }
+
+// the lane's source frame into registers, zero-padded
+template <int DIMR>
+__device__ __forceinline__ void wave_load_frame(double (&ar)[DIMR], const double *arow, int dim)
+{
+#pragma unroll
+    for (int e = 0; e < DIMR; ++e)
+        ar[e] = e < dim ? arow[e] : 0.0;
+}
+
+// the 64 target frames from column f0 on enter the ring, zero-padded; the block they replace ended at column f0 - 65,
+// and the lanes still read from column f0 - 63 on.  Every lane of the wave calls it.
+template <int DIMR>
+__device__ __forceinline__ void wave_refill(double *ring, uint32_t ringMask, const double *b0, int dim, int Fb, int f0)
+{
+    const int cnt = min(64, Fb - f0);
+    __syncthreads();
+    for (int i = threadIdx.x; i < cnt * DIMR; i += 64) {
+        const int fr = i / DIMR, e = i % DIMR;
+        ring[(size_t)((uint32_t)(f0 + fr) & ringMask) * wave_ld(DIMR) + e] = e < dim ? b0[(size_t)(f0 + fr) * dim + e] : 0.0;
+    }
+    __syncthreads();
+}
+
+// c(i, jc): sum_k (a_k - b_k)^2, k ascending, sub / mul / add rounded separately (the oracle's order), then the square
+// root unless squared; the zero padding adds +0.0 to a non-negative sum and leaves its bits alone
+template <int DIMR>
+__device__ __forceinline__ double wave_cell_cost(const double (&ar)[DIMR], const double *ring, uint32_t ringMask, int jc,
+                                                 int squared)
+{
+    typedef double d2 __attribute__((ext_vector_type(2)));
+    const d2 *bp = reinterpret_cast<const d2 *>(ring + (size_t)((uint32_t)jc & ringMask) * wave_ld(DIMR));
+    double acc = 0.0;
+#pragma unroll
+    for (int e0 = 0; e0 < DIMR; e0 += 8) {
+        d2 bv[4];
+#pragma unroll
+        for (int v = 0; v < 4; ++v)
+            if (e0 + 2 * v < DIMR)
+                bv[v] = bp[e0 / 2 + v];
+#pragma unroll
+        for (int v = 0; v < 8; ++v)
+            if (e0 + v < DIMR) {
+                const double df = __dsub_rn(ar[e0 + v], bv[v / 2][v % 2]);
+                acc = __dadd_rn(acc, __dmul_rn(df, df));
+            }
+    }
+    return squared ? acc : sqrt(acc);
+}
+
+// min3 in dtw_exact.hip's comparison order
+__device__ __forceinline__ double wave_min3(double up, double lf, double dg)
+{
+    double best = up;                 // D(i-1, j)
+    if (lf < best) best = lf;         // D(i,   j-1)
+    if (dg < best) best = dg;         // D(i-1, j-1)
+    return best;
+}
+
+// the predecessor rule: ties prefer the diagonal, then the source step.  0 = diagonal, 1 = up, 2 = left
+__device__ __forceinline__ uint32_t wave_pred(double up, double lf, double dg)
+{
+    return (dg <= up && dg <= lf) ? 0u : (up <= lf ? 1u : 2u);
+}
+
+// ---- host: launch geometry ----------------------------------------------------------------------------------------------
+
+inline int wave_dimr(uint32_t dim) { return dim <= 14 ? 14 : dim <= 16 ? 16 : dim <= 40 ? 40 : 64; }
+// entries of the hand-off row: even (what follows it in LDS stays 16-byte aligned), >= the longest listed target
+inline uint32_t wave_fb_cap(uint64_t maxFb) { return ((uint32_t)std::max<uint64_t>(maxFb, 1) + 1) & ~1u; }
+inline uint32_t wave_ring_rows(uint64_t maxFb) { return maxFb <= 64 ? 64 : kWaveRing; }
+inline size_t wave_ring_bytes(uint32_t ringRows, int dimr) { return (size_t)ringRows * wave_ld(dimr) * sizeof(double); }
+
+// the instantiation of kernel template K_ (one wave per workgroup, one argument struct) for wave_dimr's value
+#define SSYM_WAVE_KERNEL(K_, dimr_) \
+    ((dimr_) == 14 ? K_<14> : (dimr_) == 16 ? K_<16> : (dimr_) == 40 ? K_<40> : K_<64>)
+
+template <class Args>
+inline int32_t wave_launch(ssym_ctx *ctx, void (*kern)(Args), unsigned grid, size_t lds, const Args &a)
+{
+    if (lds > 64 * 1024)
+        SSYM_HIP_CHECK(ctx, hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    kern<<<grid, 64, lds, ctx->stream>>>(a);
+    SSYM_HIP_CHECK(ctx, hipGetLastError());
+    return SSYM_OK;
+}
+
+// ---- host: argument checks (fn: the entry point's name, err: where the message goes) -----------------------------------
+
+inline int32_t check_handles(std::string &err, const char *fn, const ssym_dict *dict, const ssym_queries *q)
+{
+    if (!dict || !q) {
+        err = std::string(fn) + ": dictionary or queries handle is NULL";
+        return SSYM_E_INVALID;
+    }
+    return SSYM_OK;
+}
+
+// what a call with something to do needs of its two sets
+inline int32_t check_sets(std::string &err, const SegmentSet &src, const SegmentSet &tgt)
+{
+    if (src.n == 0) {
+        err = "empty dictionary";
+        return SSYM_E_EMPTY_DICT;
+    }
+    if (src.dim != tgt.dim) {
+        err = "dim mismatch between dictionary and targets";
+        return SSYM_E_INVALID;
+    }
+    return SSYM_OK;
+}
+
+// a (src_idx, tgt_idx, n_pairs, index_base) list against a dictionary and a query set.  An empty list is fine whatever
+// else holds: the caller returns after it.
+inline int32_t check_pair_list(std::string &err, const char *fn, const ssym_dict *dict, const ssym_queries *q,
+                               const uint32_t *src_idx, const uint32_t *tgt_idx, uint32_t n_pairs, uint32_t index_base)
+{
+    int32_t rc = check_handles(err, fn, dict, q);
+    if (rc != SSYM_OK || n_pairs == 0)
+        return rc;
+    const std::string name(fn);
+    if (!src_idx) {
+        err = name + ": src_idx is NULL";
+        return SSYM_E_INVALID;
+    }
+    rc = check_sets(err, dict->set, q->set);
+    if (rc != SSYM_OK)
+        return rc;
+    if (!tgt_idx && n_pairs > q->set.n) {
+        err = name + ": tgt_idx is NULL and n_pairs exceeds the number of targets";
+        return SSYM_E_INVALID;
+    }
+    for (uint32_t p = 0; p < n_pairs; ++p) {
+        if (src_idx[p] != SSYM_NO_MATCH && (src_idx[p] < index_base || src_idx[p] - index_base >= dict->set.n)) {
+            err = name + ": src_idx[" + std::to_string(p) + "] is outside the dictionary";
+            return SSYM_E_INVALID;
+        }
+        if (tgt_idx && tgt_idx[p] >= q->set.n) {
+            err = name + ": tgt_idx[" + std::to_string(p) + "] is outside the targets";
+            return SSYM_E_INVALID;
+        }
+    }
+    return SSYM_OK;
+}
+
+// entry p of a checked list as (source, target) in the sets' own indices; SSYM_NO_MATCH stays
+inline uint2 pair_at(const uint32_t *src_idx, const uint32_t *tgt_idx, uint32_t index_base, uint32_t p)
+{
+    return make_uint2(src_idx[p] == SSYM_NO_MATCH ? SSYM_NO_MATCH : src_idx[p] - index_base, tgt_idx ? tgt_idx[p] : p);
+}
+
+}  // namespace ssym

@@ -365,6 +365,7 @@ def test_every_listed_error_leaves_the_outputs_untouched():
     assert call(src_idx=np.array([1, 2, 0], dtype=np.uint32), base=1) == inv              # below index_base
     assert call(tgt_idx=np.array([0, 3, 1], dtype=np.uint32)) == inv                      # beyond the targets
     assert call(src_idx=np.array([0, 1, 2, 3], dtype=np.uint32), n=4) == inv              # NULL tgt_idx, 4 pairs, 3 targets
+    assert call(src_idx=np.array([0, 4, 1], dtype=np.uint32), null=("cost",)) == inv      # two faults in one call
     other = s.e.queries(np.zeros(3 * 13), np.array([0, 1, 2, 3], dtype=np.uint64), 13)    # a set of another dimension
     assert call(q=other.ptr) == inv and call_q(q=other.ptr) == inv
     empty = s.e.dictionary(np.zeros(0), np.zeros(1, dtype=np.uint64), dim)
