@@ -131,6 +131,12 @@ extern "C" {
     pub fn ssym_spot_queries(ctx: *mut SsymCtx, dict: *const SsymDict, q: *const SsymQueries, index_base: u32,
                              out_idx: *mut u32, out_cost: *mut f64, out_start: *mut u32, out_end: *mut u32,
                              flags: u32) -> i32;
+    // occurrences: up to max_spots (1 ... 64) pairwise disjoint spans per listed pair, best first, [n_pairs][max_spots]
+    // row-major; max_cost: n_pairs thresholds in host memory or null; slots beyond out_count[p]: +inf and SSYM_NO_MATCH
+    pub fn ssym_dtw_spot_all(ctx: *mut SsymCtx, dict: *const SsymDict, q: *const SsymQueries, src_idx: *const u32,
+                             tgt_idx: *const u32, n_pairs: u32, index_base: u32, max_spots: u32, max_cost: *const f64,
+                             out_count: *mut u32, out_cost: *mut f64, out_start: *mut u32, out_end: *mut u32,
+                             flags: u32) -> i32;
 
     // source-sharded runs, exchange done by the caller (device pointers): filter / all-reduce(MIN) / finish / merge
     pub fn ssym_match_begin(ctx: *mut SsymCtx, dict: *const SsymDict, q: *const SsymQueries, distance: *const f64,

@@ -374,6 +374,58 @@ class SoundDictionary {
                                              : Spot{idx[t], start[t], end[t], cost[t]};
         return out;
     }
+    // every place a target sounds: per target its occurrences by ascending cost, pairwise disjoint within a recording
+    // (ssym_dtw_spot_all, one call).  With indices, target t is searched in sounds[indices[t]]; without, in every sound:
+    // max_spots (1 ... 64) then applies per sound and a target's list is merged by (cost, source index, end).  max_cost:
+    // an occurrence costs at most that (NULL: no threshold)
+    std::vector<std::vector<Spot>> spot_all(const std::vector<ArcSound> &targets, const std::vector<uint32_t> *indices = nullptr,
+                                            uint32_t max_spots = 8, const double *max_cost = nullptr) const
+    {
+        if (sounds.empty())
+            throw EmptyDictionary();
+        const uint32_t n = (uint32_t)sounds.size(), m = (uint32_t)targets.size();
+        std::vector<std::vector<Spot>> out(m);
+        if (m == 0)
+            return out;
+        std::vector<uint32_t> src, tgt;
+        if (indices) {
+            src = *indices;
+            for (uint32_t t = 0; t < m; ++t)
+                tgt.push_back(t);
+        } else {
+            for (uint32_t s = 0; s < n; ++s)
+                for (uint32_t t = 0; t < m; ++t) {
+                    src.push_back(s);
+                    tgt.push_back(t);
+                }
+        }
+        const size_t np = tgt.size(), K = max_spots;
+        std::vector<double> flat;
+        std::vector<uint64_t> off;
+        pack_features(targets, flat, off);
+        ssym_queries *q = nullptr;
+        ctx_->check(ssym_queries_create(ctx_->get(), flat.data(), off.data(), m, (uint32_t)NCOEFFS, &q));
+        std::vector<uint32_t> count(np), start(np * K), end(np * K);
+        std::vector<double> cost(np * K), limit(max_cost ? np : 0, max_cost ? *max_cost : 0.0);
+        const int32_t rc = src.size() == np ? ssym_dtw_spot_all(ctx_->get(), resident(), q, src.data(), tgt.data(), (uint32_t)np,
+                                                                0, max_spots, max_cost ? limit.data() : nullptr, count.data(),
+                                                                cost.data(), start.data(), end.data(), 0)
+                                            : (int32_t)SSYM_E_INVALID;
+        ssym_queries_destroy(ctx_->get(), q);
+        ctx_->check(rc);
+        for (size_t p = 0; p < np; ++p)
+            for (uint32_t k = 0; k < count[p]; ++k)
+                out[tgt[p]].push_back(Spot{src[p], start[p * K + k], end[p * K + k], cost[p * K + k]});
+        for (auto &spots : out)
+            std::stable_sort(spots.begin(), spots.end(), [](const Spot &a, const Spot &b) {
+                if (a.cost != b.cost)
+                    return a.cost < b.cost;
+                if (a.source_index != b.source_index)
+                    return a.source_index < b.source_index;
+                return a.end_frame < b.end_frame;
+            });
+        return out;
+    }
     // from_distances' chain of at_distance calls, on the device in one call (ssym_chain)
     std::vector<uint32_t> chain_indices(const Sound &start, const std::vector<double> &distances) const
     {

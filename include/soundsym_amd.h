@@ -321,6 +321,42 @@ SSYM_API int32_t ssym_spot_queries(ssym_ctx *ctx, const ssym_dict *dict, const s
                                    uint32_t *out_idx, double *out_cost, uint32_t *out_start, uint32_t *out_end,
                                    uint32_t flags);
 
+/* Occurrences (DESIGN.md section 2 "Occurrences" and section 5.16): up to K pairwise disjoint spans per (source, target)
+ * pair, best first -- every place a target sounds inside a recording, not only the best one.  c, D, st, the squared
+ * option and the arithmetic are those of ssym_dtw_spot above.  For one pair with Fa, Fb >= 1:
+ *   delta(i) = D(i,Fb-1),  s(i) = st(i,Fb-1)            for i = 0 ... Fa - 1 (the end-column profile)
+ *   candidate: an end i with delta(i) finite and delta(i) <= max_cost (+inf when max_cost is NULL), not yet dead
+ *   pick m   : the candidate with the least delta, among equals the smallest i (i ascending from (none, +inf), strict <)
+ *              -> occurrence m = (cost delta(i*), start s(i*), end i*)
+ *   kill     : every end i with s(i) <= i* and i >= s(i*) is dead from now on (its span [s(i), i] shares a frame with
+ *              [s(i*), i*]; i* itself is among them)
+ *   stop     : after K picks, or when no candidate is left
+ *   count    = picks made;  slots count ... K - 1 hold (+inf, SSYM_NO_MATCH, SSYM_NO_MATCH)
+ *   nothing  : Fa = 0, Fb = 0, source SSYM_NO_MATCH -> count 0
+ * So, without max_cost, occurrence 0 is ssym_dtw_spot's result for the pair bit for bit; costs do not decrease with m and
+ * equal costs come in ascending end; spans are pairwise disjoint in frames (touching, end_a + 1 = start_b, is allowed);
+ * every occurrence's cost has the bits of the plain DTW cost of (source frames start ... end, target), what
+ * ssym_pair_matrix(exact = 1) gives for that cut; a NaN delta(i) is never a candidate.  The cost is NOT normalised by any
+ * length: without max_cost the later occurrences of a recording that holds the target fewer than K times are spans the
+ * target merely fits least badly.
+ * ssym_dtw_spot_all: the pair list is ssym_dtw_spot's in every respect (tgt_idx == NULL, repeats, index_base,
+ *   SSYM_NO_MATCH sources, HOST memory).
+ *   max_spots  K, 1 ... 64
+ *   max_cost   HOST memory, n_pairs f64, one threshold per pair; NULL: none
+ *   out_count  n_pairs u32;  out_cost  n_pairs * K f64;  out_start, out_end  n_pairs * K u32 each, row-major [n_pairs][K]
+ *   flags      SSYM_OUT_DEVICE: the four outputs are device memory
+ * Limits: those of ssym_dtw_spot (targets of at most 4096 frames, dim <= 64, no band, no refcos), and every listed
+ * source at most 2^24 = 16777216 frames (the profile lives in device scratch at 12 bytes per source frame; a call's scratch
+ * stays within 512 MiB): beyond them SSYM_E_UNSUPPORTED.  max_spots 0 or > 64, a NaN in max_cost, NULL pointers, an index
+ * outside its set, a dim mismatch: SSYM_E_INVALID; an empty dictionary with n_pairs > 0: SSYM_E_EMPTY_DICT -- all with a
+ * message, before device memory is touched and with the outputs unwritten.  n_pairs = 0 succeeds and does nothing
+ * (max_spots, max_cost and the outputs are not looked at then).  One synchronisation per call.  ssym_get_timings afterwards: main_ms = the kernel (forward pass and selection are one
+ * launch), n_pairs = the pairs of the call. */
+SSYM_API int32_t ssym_dtw_spot_all(ssym_ctx *ctx, const ssym_dict *dict, const ssym_queries *q, const uint32_t *src_idx,
+                                   const uint32_t *tgt_idx, uint32_t n_pairs, uint32_t index_base, uint32_t max_spots,
+                                   const double *max_cost, uint32_t *out_count, double *out_cost, uint32_t *out_start,
+                                   uint32_t *out_end, uint32_t flags);
+
 /* Source-sharded multi-GPU, dtw metric: the one real exchange the path has.  Each rank's filter gives,
  * per target, an upper bound on the best key in ITS shard; a rank whose shard does not hold a
  * target's neighbour would otherwise re-score ~10^2 of its own pairs per target for nothing.

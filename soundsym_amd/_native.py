@@ -56,7 +56,7 @@ ABI_SYMBOLS = [
     "ssym_stream_read", "ssym_stream_frames_device", "ssym_stream_samples_device", "ssym_stream_descriptors",
     "ssym_stream_reset",
     "ssym_dtw_align_sizes", "ssym_dtw_align",
-    "ssym_dtw_spot", "ssym_spot_queries",
+    "ssym_dtw_spot", "ssym_spot_queries", "ssym_dtw_spot_all",
     "ssym_reconstruct_warped", "ssym_reconstruct_wsola",
 ]
 COMM_ID_BYTES = 128        # SSYM_COMM_ID_BYTES
@@ -251,6 +251,8 @@ def lib() -> ctypes.CDLL:
     L.ssym_dtw_spot.argtypes = [vp, vp, vp, vp, vp, u32, u32, vp, vp, vp, u32]
     L.ssym_spot_queries.restype = i32
     L.ssym_spot_queries.argtypes = [vp, vp, vp, u32, vp, vp, vp, vp, u32]
+    L.ssym_dtw_spot_all.restype = i32
+    L.ssym_dtw_spot_all.argtypes = [vp, vp, vp, vp, vp, u32, u32, u32, vp, vp, vp, vp, vp, u32]
     L.ssym_pair_matrix.restype = i32
     L.ssym_pair_matrix.argtypes = [vp, vp, vp, i32, vp]
     L.ssym_merge_shards.restype = i32

@@ -637,6 +637,53 @@ class SoundDictionary:
         return [Spot(int(indices[t]), int(start[t]), int(end[t]), cost[t]) if int(end[t]) != NO_MATCH else Spot.none()
                 for t in range(len(targets))]
 
+    def spot_all(self, targets: Sequence[Sound], indices=None, max_spots: int = 8, max_cost=None) -> List[List["Spot"]]:
+        """Every place a target sounds inside the dictionary's recordings: per target its occurrences by ascending cost,
+        pairwise disjoint within a recording (ssym_dtw_spot_all, one call; dtw engines without a band).  With indices,
+        target t is searched in recording indices[t] and max_cost is a scalar or one value per target; without, in every
+        recording -- max_spots then applies per recording, max_cost is a scalar, and a target's list is merged by
+        (cost, source index, end).  An occurrence costs at most max_cost; the cost is not normalised by any length, so
+        without max_cost the list goes on with spans the target merely fits least badly."""
+        if not self.sounds:
+            raise EmptyDictionaryError(-2, "empty dictionary")
+        if getattr(self.engine, "metric", None) != "dtw":
+            raise SsymError(SSYM_E_UNSUPPORTED, "spot_all aligns with dtw: a refcos engine has no alignment")
+        targets = list(targets)
+        if not 1 <= int(max_spots) <= 64:
+            raise ValueError("max_spots must be 1 ... 64")
+        n, m = len(self.sounds), len(targets)
+        if max_cost is not None:
+            max_cost = np.asarray(max_cost, dtype=np.float64)
+            if max_cost.ndim and (indices is None or max_cost.size != m):
+                raise ValueError("max_cost must be a scalar, or with indices one value per target")
+            if np.isnan(max_cost).any():
+                raise ValueError("max_cost must not be NaN")
+        if indices is not None:
+            indices = np.asarray(indices, dtype=np.int64).reshape(-1)
+            if indices.size != m:
+                raise ValueError("indices must name one dictionary sound per target")
+            if indices.size and (indices.min() < 0 or indices.max() >= n):
+                raise ValueError("an index is outside the dictionary")
+        if not targets:
+            return []
+        if indices is None:
+            src, tgt = np.repeat(np.arange(n), m), np.tile(np.arange(m), n)
+        else:
+            src, tgt = indices, np.arange(m)
+        flat, off = pack_segments([t.mfccs() for t in targets], self._dim(), self.engine.np_dtype)
+        q = self.engine.queries(flat, off, self._dim())
+        try:
+            count, cost, start, end = self.engine.dtw_spot_all(self.resident(), q, src, tgt, max_spots=int(max_spots),
+                                                               max_cost=max_cost)
+        finally:
+            q.close()
+        out: List[List[Spot]] = [[] for _ in range(m)]
+        for p in range(src.size):
+            out[int(tgt[p])] += [Spot(int(src[p]), int(start[p, k]), int(end[p, k]), cost[p, k]) for k in range(int(count[p]))]
+        for spots in out:
+            spots.sort(key=lambda sp: (sp.cost, sp.source_index, sp.end_frame))
+        return out
+
     def cut(self, spots: Sequence["Spot"]) -> "SoundDictionary":
         """A dictionary with one Sound per spot: the recording's samples over spot.sample_span() and its feature frames
         start_frame ... end_frame; an empty spot gives an empty Sound.  Sound t of the result is what target t was
@@ -783,6 +830,12 @@ class SoundSequence:
         if not self._sounds:
             return []
         return dict_.spot(self._sounds)
+
+    def spot_all_in_dictionary(self, dict_: SoundDictionary, max_spots: int = 8, max_cost=None) -> List[List[Spot]]:
+        """Every occurrence of every sound of the sequence inside dict_'s recordings (SoundDictionary.spot_all)."""
+        if not self._sounds:
+            return []
+        return dict_.spot_all(self._sounds, max_spots=max_spots, max_cost=max_cost)
 
     def reconstruct_from_dictionary(self, dict_: "SoundDictionary", want_pcm32: bool = False):
         """clone_from_dictionary(dict).to_sound().samples() in one go (src/sound.rs:451-480): match

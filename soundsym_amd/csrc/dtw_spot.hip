@@ -17,6 +17,13 @@
 // entries, so the LDS a pair needs does not grow with the source.  Every lane keeps the best D(r, Fb-1) of its own rows
 // (chunks ascend, strict <: its lowest such row); one wave reduction per pair orders the 64 candidates by (D, row).  No
 // direction matrix, no backward walk: three scalars per pair, written by lane 0.
+//
+// Occurrences (ssym_dtw_spot_all; DESIGN.md 2 "Occurrences", 5.16): the same forward pass with the end column kept.  A
+// lane's last value of a chunk IS (D(r, Fb-1), st(r, Fb-1)), so the profile costs no register: one 8-byte and one 4-byte
+// store per lane per chunk into the workgroup's scratch slot.  The wave then picks up to K disjoint spans from its slot:
+// pick 0 is the end reduction above; every further pick is one pass that kills what the previous pick overlaps (+inf into
+// the profile) and finds the first least survivor.  Lane l only ever touches entries i = l (mod 64), the ones it wrote
+// itself, so the passes need no exchange through memory, only the (D, row) butterfly.
 #include "dtw_wave.hpp"
 
 #include <algorithm>
@@ -27,6 +34,12 @@ namespace ssym {
 // A source has as many frames as a dictionary segment can (2^31 - 1).
 constexpr int kSpotMaxTargetFrames = 4096;
 constexpr int kSpotMaxDim = 64;
+// Limits of ssym_dtw_spot_all: occurrences per pair, and frames of a listed source -- the profile lives in global scratch
+// at 12 bytes per source frame, 192 MiB for one pair at this length.  The scratch of a call stays within
+// kSpotAllScratchBytes: one slot per workgroup, fewer workgroups for longer sources.
+constexpr uint32_t kSpotAllMaxSpots = 64;
+constexpr uint64_t kSpotAllMaxSourceFrames = 16777216;          // 2^24
+constexpr size_t kSpotAllScratchBytes = (size_t)512 << 20;
 
 namespace {
 
@@ -46,8 +59,50 @@ struct SpotArgs {
     uint32_t ringRows;           // 64 or 128
 };
 
-template <int DIMR>
-__global__ __launch_bounds__(64) void dtw_spot_kernel(const SpotArgs a)
+// ssym_dtw_spot_all: cost / start / end are [nPairs][maxSpots].  A struct of its own: the spot kernels' arguments, and
+// with them their register figures, stay what they were.
+struct SpotAllArgs : SpotArgs {
+    uint32_t maxSpots;           // K
+    uint32_t *count;             // [nPairs]
+    const double *maxCost;       // [nPairs], NULL: none
+    double *profD;               // [gridDim.x][slotFrames]  the end column of the workgroup's current pair: D ...
+    uint32_t *profS;             // [gridDim.x][slotFrames]  ... and st
+    uint64_t slotFrames;         // >= the longest listed source
+};
+
+// the first minimum among the 64 lanes' candidates (bestD f64, bestEnd u32, bestSt u32), ordered by (D, row), in every
+// lane; a lane without a candidate holds (+inf, 0xffffffff), which loses against every candidate and ties with its like.
+// One text for the kernel's end reduction and for the selection passes, as a macro: the same lines as a function cost
+// dtw_spot_kernel<64> 18 spilled VGPRs and dtw_spot_kernel<14> one more register
+#define SSYM_SPOT_FIRST_MIN(bestD, bestEnd, bestSt)                                                                       \
+    _Pragma("unroll") for (int m_ = 32; m_ >= 1; m_ >>= 1)                                                                \
+    {                                                                                                                     \
+        const double oD_ = __shfl_xor(bestD, m_);                                                                         \
+        const uint32_t oE_ = (uint32_t)__shfl_xor((int)bestEnd, m_), oS_ = (uint32_t)__shfl_xor((int)bestSt, m_);         \
+        if (oD_ < bestD || (oD_ == bestD && oE_ < bestEnd)) {                                                             \
+            bestD = oD_;                                                                                                  \
+            bestEnd = oE_;                                                                                                \
+            bestSt = oS_;                                                                                                 \
+        }                                                                                                                 \
+    }
+
+// pair k of ssym_dtw_spot_all has cnt occurrences: the count, and the slots behind them (maxSpots <= 64: one per lane)
+__device__ __forceinline__ void spot_all_pad(const SpotAllArgs &a, uint32_t k, uint32_t cnt)
+{
+    const uint32_t m = threadIdx.x;
+    if (m == 0)
+        a.count[k] = cnt;
+    if (m >= cnt && m < a.maxSpots) {
+        const size_t o = (size_t)k * a.maxSpots + m;
+        a.cost[o] = __builtin_inf();
+        a.start[o] = 0xffffffffu;
+        a.end[o] = 0xffffffffu;
+    }
+}
+
+// ALL (ssym_dtw_spot_all, Args = SpotAllArgs): keep the end column and pick up to a.maxSpots disjoint spans from it
+template <int DIMR, bool ALL = false, class Args = SpotArgs>
+__global__ __launch_bounds__(64) void dtw_spot_kernel(const Args a)
 {
     extern __shared__ __attribute__((aligned(16))) double smem[];
     constexpr int LD = wave_ld(DIMR);
@@ -72,7 +127,9 @@ __global__ __launch_bounds__(64) void dtw_spot_kernel(const SpotArgs a)
             Fb = (int)(a.tgtOff[p.y + 1] - a.tgtOff[p.y]);
         }
         if (Fa == 0 || Fb == 0) {
-            if (lane == 0) {
+            if constexpr (ALL) {
+                spot_all_pad(a, k, 0u);
+            } else if (lane == 0) {
                 a.cost[k] = INF;
                 a.start[k] = 0xffffffffu;
                 a.end[k] = 0xffffffffu;
@@ -144,20 +201,52 @@ __global__ __launch_bounds__(64) void dtw_spot_kernel(const SpotArgs a)
                 diagD = upD;
                 diagS = upS;
             }
-        }
-        // the first minimum of the end column: the 64 lanes' candidates ordered by (D, row); a lane without one holds
-        // (+inf, 0xffffffff), which loses against every candidate and ties with its like
-#pragma unroll
-        for (int m = 32; m >= 1; m >>= 1) {
-            const double oD = __shfl_xor(bestD, m);
-            const uint32_t oE = (uint32_t)__shfl_xor((int)bestEnd, m), oS = (uint32_t)__shfl_xor((int)bestSt, m);
-            if (oD < bestD || (oD == bestD && oE < bestEnd)) {
-                bestD = oD;
-                bestEnd = oE;
-                bestSt = oS;
+            // a valid row's last active step was column Fb - 1: what the lane carries is its entry of the profile
+            if constexpr (ALL) {
+                if (rowValid) {
+                    a.profD[(size_t)blockIdx.x * a.slotFrames + r] = mineD;
+                    a.profS[(size_t)blockIdx.x * a.slotFrames + r] = mineS;
+                }
             }
         }
-        if (lane == 0) {
+        // the first minimum of the end column
+        SSYM_SPOT_FIRST_MIN(bestD, bestEnd, bestSt)
+        if constexpr (ALL) {
+            double *pD = a.profD + (size_t)blockIdx.x * a.slotFrames;
+            uint32_t *pS = a.profS + (size_t)blockIdx.x * a.slotFrames;
+            const double maxCost = a.maxCost ? a.maxCost[k] : INF;
+            const size_t o = (size_t)k * a.maxSpots;
+            uint32_t cnt = 0;
+            __threadfence_block();
+            // the least survivor is a candidate or nothing is (bestEnd names a row: bestD is finite)
+            while (bestEnd != 0xffffffffu && bestD <= maxCost) {
+                if (lane == 0) {
+                    a.cost[o + cnt] = bestD;
+                    a.start[o + cnt] = bestSt;
+                    a.end[o + cnt] = bestEnd;
+                }
+                if (++cnt == a.maxSpots)
+                    break;
+                // kill every end whose span [st(i), i] shares a frame with the pick's, and find the first least survivor
+                const uint32_t pickS = bestSt, pickE = bestEnd;
+                bestD = INF;
+                bestEnd = bestSt = 0xffffffffu;
+#pragma unroll 4
+                for (uint32_t i = (uint32_t)lane; i < Fa; i += 64) {
+                    const double d = pD[i];
+                    const uint32_t s = pS[i];
+                    if (s <= pickE && i >= pickS) {
+                        pD[i] = INF;
+                    } else if (d < bestD) {
+                        bestD = d;
+                        bestEnd = i;
+                        bestSt = s;
+                    }
+                }
+                SSYM_SPOT_FIRST_MIN(bestD, bestEnd, bestSt)
+            }
+            spot_all_pad(a, k, cnt);
+        } else if (lane == 0) {
             a.cost[k] = bestD;
             a.start[k] = bestSt;
             a.end[k] = bestEnd;
@@ -317,6 +406,139 @@ int32_t dtw_spot(ssym_ctx *ctx, const ssym_dict *dict, const ssym_queries *q, co
     return SSYM_OK;
 }
 
+int32_t dtw_spot_all(ssym_ctx *ctx, const ssym_dict *dict, const ssym_queries *q, const uint32_t *src_idx,
+                     const uint32_t *tgt_idx, uint32_t n_pairs, uint32_t index_base, uint32_t max_spots,
+                     const double *max_cost, uint32_t *out_count, double *out_cost, uint32_t *out_start, uint32_t *out_end,
+                     uint32_t flags)
+{
+    const char *fn = "ssym_dtw_spot_all";
+    if (!ctx)
+        return SSYM_E_INVALID;
+    int32_t rc = spot_check_ctx(ctx, fn);
+    if (rc != SSYM_OK)
+        return rc;
+    rc = check_pair_list(ctx->err, fn, dict, q, src_idx, tgt_idx, n_pairs, index_base);
+    if (rc != SSYM_OK || n_pairs == 0)
+        return rc;
+    if (max_spots == 0 || max_spots > kSpotAllMaxSpots) {
+        ctx->err = std::string(fn) + ": max_spots must be 1 ... " + std::to_string(kSpotAllMaxSpots);
+        return SSYM_E_INVALID;
+    }
+    if (!out_count || !out_cost || !out_start || !out_end) {
+        ctx->err = std::string(fn) + ": out_count, out_cost, out_start and out_end must not be NULL";
+        return SSYM_E_INVALID;
+    }
+    const SegmentSet &src = dict->set, &tgt = q->set;
+    // the pair list, the thresholds and the shape limits: on the host, before any device work
+    std::vector<uint2> pairs(n_pairs);
+    uint64_t maxFa = 0, maxFb = 0;
+    for (uint32_t p = 0; p < n_pairs; ++p) {
+        if (max_cost && max_cost[p] != max_cost[p]) {
+            ctx->err = std::string(fn) + ": max_cost[" + std::to_string(p) + "] is NaN";
+            return SSYM_E_INVALID;
+        }
+        pairs[p] = pair_at(src_idx, tgt_idx, index_base, p);
+        const uint32_t s = pairs[p].x, t = pairs[p].y;
+        if (s == SSYM_NO_MATCH)
+            continue;
+        const uint64_t fa = src.h_off[s + 1] - src.h_off[s], fb = tgt.h_off[t + 1] - tgt.h_off[t];
+        maxFa = std::max(maxFa, fa);
+        if (fa)
+            maxFb = std::max(maxFb, fb);
+    }
+    rc = spot_limits(ctx, fn, maxFb, src.dim);
+    if (rc != SSYM_OK)
+        return rc;
+    if (maxFa > kSpotAllMaxSourceFrames) {
+        ctx->err = std::string(fn) + ": a listed source has more than " + std::to_string(kSpotAllMaxSourceFrames) +
+                   " frames (the end-column profile takes 12 bytes of scratch per source frame)";
+        return SSYM_E_UNSUPPORTED;
+    }
+    SSYM_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    const bool outDev = (flags & SSYM_OUT_DEVICE) != 0;
+    const size_t K = max_spots, nOut = (size_t)n_pairs * K;
+
+    // one profile slot per workgroup, as many workgroups as kSpotAllScratchBytes holds (2 for a 2^24-frame source)
+    SpotAllArgs a{};
+    a.slotFrames = std::max<uint64_t>(maxFa, 1);
+    const unsigned grid = (unsigned)std::min<uint64_t>(
+        std::min<uint64_t>(n_pairs, (uint64_t)ctx->num_cus * 8),
+        std::max<uint64_t>(1, kSpotAllScratchBytes / (a.slotFrames * (sizeof(double) + sizeof(uint32_t)))));
+
+    Blocks bl(ctx);
+    uint2 *dPairs = nullptr;
+    double *dMax = nullptr, *dCost = out_cost;
+    uint32_t *dCount = out_count, *dStart = out_start, *dEnd = out_end;
+    rc = bl.get(&dPairs, n_pairs);
+    if (rc == SSYM_OK && max_cost)
+        rc = bl.get(&dMax, n_pairs);
+    if (rc == SSYM_OK)
+        rc = bl.get(&a.profD, (size_t)grid * a.slotFrames);
+    if (rc == SSYM_OK)
+        rc = bl.get(&a.profS, (size_t)grid * a.slotFrames);
+    if (!outDev) {
+        if (rc == SSYM_OK)
+            rc = bl.get(&dCost, nOut);
+        if (rc == SSYM_OK)
+            rc = bl.get(&dStart, 2 * nOut + n_pairs);          // start, end, count: one copy back
+        dEnd = dStart + nOut;
+        dCount = dStart + 2 * nOut;
+    }
+    if (rc != SSYM_OK)
+        return rc;
+    SSYM_HIP_CHECK(ctx, hipMemcpyAsync(dPairs, pairs.data(), sizeof(uint2) * n_pairs, hipMemcpyHostToDevice, st));
+    if (max_cost)
+        SSYM_HIP_CHECK(ctx, hipMemcpyAsync(dMax, max_cost, sizeof(double) * n_pairs, hipMemcpyHostToDevice, st));
+    a.srcRaw = src.raw;
+    a.srcOff = src.off;
+    a.tgtRaw = tgt.raw;
+    a.tgtOff = tgt.off;
+    a.dim = src.dim;
+    a.squared = ctx->squared;
+    a.pairs = dPairs;
+    a.nTgt = tgt.n;
+    a.nPairs = n_pairs;
+    a.cost = dCost;
+    a.start = dStart;
+    a.end = dEnd;
+    a.fbCap = wave_fb_cap(maxFb);
+    a.ringRows = wave_ring_rows(maxFb);
+    a.maxSpots = max_spots;
+    a.count = dCount;
+    a.maxCost = dMax;
+    const int dimr = wave_dimr(src.dim);
+    const size_t lds = (size_t)a.fbCap * (sizeof(double) + sizeof(uint32_t)) + wave_ring_bytes(a.ringRows, dimr);
+    SSYM_HIP_CHECK(ctx, hipEventRecord(ctx->ev[0], st));
+    rc = wave_launch(ctx,
+                     dimr == 14   ? dtw_spot_kernel<14, true, SpotAllArgs>
+                     : dimr == 16 ? dtw_spot_kernel<16, true, SpotAllArgs>
+                     : dimr == 40 ? dtw_spot_kernel<40, true, SpotAllArgs>
+                                  : dtw_spot_kernel<64, true, SpotAllArgs>,
+                     grid, lds, a);
+    if (rc != SSYM_OK)
+        return rc;
+    SSYM_HIP_CHECK(ctx, hipEventRecord(ctx->ev[1], st));
+    std::vector<uint32_t> hWords;
+    if (!outDev) {
+        hWords.resize(2 * nOut + n_pairs);
+        SSYM_HIP_CHECK(ctx, hipMemcpyAsync(out_cost, dCost, sizeof(double) * nOut, hipMemcpyDeviceToHost, st));
+        SSYM_HIP_CHECK(ctx, hipMemcpyAsync(hWords.data(), dStart, sizeof(uint32_t) * hWords.size(), hipMemcpyDeviceToHost, st));
+    }
+    SSYM_HIP_CHECK(ctx, hipStreamSynchronize(st));
+    if (!outDev) {
+        std::copy(hWords.begin(), hWords.begin() + nOut, out_start);
+        std::copy(hWords.begin() + nOut, hWords.begin() + 2 * nOut, out_end);
+        std::copy(hWords.begin() + 2 * nOut, hWords.end(), out_count);
+    }
+    ssym_timings tm{};
+    tm.main_ms = tm.total_ms = ev_ms(ctx->ev[0], ctx->ev[1]);
+    tm.main_launches = 1;
+    tm.n_pairs = n_pairs;
+    ctx->timings = tm;
+    return SSYM_OK;
+}
+
 int32_t spot_queries(ssym_ctx *ctx, const ssym_dict *dict, const ssym_queries *q, uint32_t index_base, uint32_t *out_idx,
                      double *out_cost, uint32_t *out_start, uint32_t *out_end, uint32_t flags)
 {
@@ -412,6 +634,17 @@ int32_t ssym_dtw_spot(ssym_ctx *ctx, const ssym_dict *dict, const ssym_queries *
 {
     return guarded(ctx, [&]() -> int32_t {
         return dtw_spot(ctx, dict, q, src_idx, tgt_idx, n_pairs, index_base, out_cost, out_start, out_end, flags);
+    });
+}
+
+int32_t ssym_dtw_spot_all(ssym_ctx *ctx, const ssym_dict *dict, const ssym_queries *q, const uint32_t *src_idx,
+                          const uint32_t *tgt_idx, uint32_t n_pairs, uint32_t index_base, uint32_t max_spots,
+                          const double *max_cost, uint32_t *out_count, double *out_cost, uint32_t *out_start,
+                          uint32_t *out_end, uint32_t flags)
+{
+    return guarded(ctx, [&]() -> int32_t {
+        return dtw_spot_all(ctx, dict, q, src_idx, tgt_idx, n_pairs, index_base, max_spots, max_cost, out_count, out_cost,
+                            out_start, out_end, flags);
     });
 }
 

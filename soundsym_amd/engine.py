@@ -43,6 +43,24 @@ def _align_indices(src_idx, tgt_idx):
     return src, tgt
 
 
+def _spot_all_args(src, max_spots, max_cost):
+    """(K, per-pair thresholds as a contiguous f64 array or None) of dtw_spot_all, checked before the library is asked."""
+    k = int(max_spots)
+    if not 1 <= k <= 64:
+        raise ValueError("max_spots must be 1 ... 64")
+    if max_cost is None:
+        return k, None
+    mc = np.asarray(max_cost, dtype=np.float64)
+    if mc.ndim == 0:
+        mc = np.full(src.size, float(mc))
+    mc = np.ascontiguousarray(mc.reshape(-1))
+    if mc.size != src.size:
+        raise ValueError("max_cost must be a scalar or one value per pair")
+    if np.isnan(mc).any():
+        raise ValueError("max_cost must not be NaN")
+    return k, mc
+
+
 def _device_words(x, what: str):
     """(pointer, count) of 32-bit words in device memory: a torch CUDA tensor of a 4-byte integer type, or a
     DeviceFrames-style object (data_ptr / numel) whose owner vouches for the content."""
@@ -720,6 +738,44 @@ class Engine:
                                           tgt.ctypes.data if tgt is not None else None, n, index_base, cost.data_ptr(),
                                           start.data_ptr(), end.data_ptr(), nat.OUT_DEVICE), self.ctx)
         return cost[:n], start[:n], end[:n]
+
+    def dtw_spot_all(self, d: _Handle, q: _Handle, src_idx, tgt_idx=None, index_base: int = 0, max_spots: int = 8,
+                     max_cost=None):
+        """ssym_dtw_spot_all: for every listed pair (as in dtw_spot) up to max_spots (1 ... 64) pairwise disjoint spans
+        of the source the target aligns with, best first, by the definition in include/soundsym_amd.h ("Occurrences").
+        max_cost: a scalar or one value per pair; an occurrence costs at most that.  Returns (count uint32 [n], cost f64
+        [n, K], start uint32 [n, K], end uint32 [n, K]); slots from count[p] on hold +inf and NO_MATCH."""
+        src, tgt = _align_indices(src_idx, tgt_idx)
+        k, mc = _spot_all_args(src, max_spots, max_cost)
+        n = src.size
+        count = np.zeros(n, dtype=np.uint32)
+        cost = np.zeros((n, k), dtype=np.float64)
+        start = np.zeros((n, k), dtype=np.uint32)
+        end = np.zeros((n, k), dtype=np.uint32)
+        rc = nat.lib().ssym_dtw_spot_all(self.ctx, d.ptr, q.ptr, src.ctypes.data, tgt.ctypes.data if tgt is not None else None,
+                                         n, index_base, k, mc.ctypes.data if mc is not None else None, count.ctypes.data,
+                                         cost.ctypes.data, start.ctypes.data, end.ctypes.data, 0)
+        nat.check(rc, self.ctx)
+        return count, cost, start, end
+
+    def dtw_spot_all_device(self, d: _Handle, q: _Handle, src_idx, tgt_idx=None, index_base: int = 0, max_spots: int = 8,
+                            max_cost=None):
+        """ssym_dtw_spot_all with SSYM_OUT_DEVICE: (count i32 [n], cost f64 [n, K], start i32 [n, K], end i32 [n, K]) as
+        torch tensors in device memory (torch only owns the memory; the 32-bit tensors hold the call's u32 values)."""
+        src, tgt = _align_indices(src_idx, tgt_idx)
+        k, mc = _spot_all_args(src, max_spots, max_cost)
+        import torch
+        n = src.size
+        dev = torch.device("cuda", self.device)
+        count = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
+        cost = torch.empty((max(n, 1), k), dtype=torch.float64, device=dev)
+        start = torch.empty((max(n, 1), k), dtype=torch.int32, device=dev)
+        end = torch.empty((max(n, 1), k), dtype=torch.int32, device=dev)
+        nat.check(nat.lib().ssym_dtw_spot_all(self.ctx, d.ptr, q.ptr, src.ctypes.data,
+                                              tgt.ctypes.data if tgt is not None else None, n, index_base, k,
+                                              mc.ctypes.data if mc is not None else None, count.data_ptr(),
+                                              cost.data_ptr(), start.data_ptr(), end.data_ptr(), nat.OUT_DEVICE), self.ctx)
+        return count[:n], cost[:n], start[:n], end[:n]
 
     def spot_queries(self, d: _Handle, q: _Handle, index_base: int = 0):
         """ssym_spot_queries: every dictionary segment spotted against every target, then the first least cost per
