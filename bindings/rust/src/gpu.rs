@@ -14,6 +14,7 @@ use std::os::raw::{c_char, c_void};
 #[repr(C)] pub struct SsymLocalGroup { _p: [u8; 0] }
 #[repr(C)] pub struct SsymGmm { _p: [u8; 0] }
 #[repr(C)] pub struct SsymStream { _p: [u8; 0] }
+#[repr(C)] pub struct SsymSpotter { _p: [u8; 0] }
 
 pub const SSYM_ABI_VERSION: i32 = 3;
 
@@ -248,6 +249,23 @@ extern "C" {
     pub fn ssym_stream_descriptors(ctx: *mut SsymCtx, st: *mut SsymStream, out_max_power: *mut f64,
                                    out_mean: *mut f64) -> i32;
     pub fn ssym_stream_reset(ctx: *mut SsymCtx, st: *mut SsymStream, lane: u32) -> i32;
+
+    // watching: the targets of a query set spotted in growing sources, resumable push by push
+    pub fn ssym_spotter_create(ctx: *mut SsymCtx, q: *const SsymQueries, n_lanes: u32, max_cost: *const f64,
+                               out: *mut *mut SsymSpotter) -> i32;
+    pub fn ssym_spotter_destroy(ctx: *mut SsymCtx, sp: *mut SsymSpotter) -> i32;
+    pub fn ssym_spotter_push(ctx: *mut SsymCtx, sp: *mut SsymSpotter, feats: *const f64, frame_offsets: *const u64,
+                             flags: u32, out_n_events: *mut u64, out_profile_cost: *mut f64,
+                             out_profile_start: *mut u32) -> i32;
+    pub fn ssym_spotter_follow(ctx: *mut SsymCtx, sp: *mut SsymSpotter, stream: *const SsymStream, flags: u32,
+                               out_n_events: *mut u64, out_profile_cost: *mut f64, out_profile_start: *mut u32) -> i32;
+    pub fn ssym_spotter_events(ctx: *mut SsymCtx, sp: *const SsymSpotter, out_lane: *mut u32, out_target: *mut u32,
+                               out_cost: *mut f64, out_start: *mut u32, out_end: *mut u32, flags: u32) -> i32;
+    pub fn ssym_spotter_flush(ctx: *mut SsymCtx, sp: *mut SsymSpotter, lane: u32, out_n_events: *mut u64) -> i32;
+    pub fn ssym_spotter_best(ctx: *mut SsymCtx, sp: *const SsymSpotter, out_cost: *mut f64, out_start: *mut u32,
+                             out_end: *mut u32, flags: u32) -> i32;
+    pub fn ssym_spotter_counts(sp: *const SsymSpotter, out_frames: *mut u64) -> i32;
+    pub fn ssym_spotter_reset(ctx: *mut SsymCtx, sp: *mut SsymSpotter, lane: u32) -> i32;
 }
 
 /// `Err(message)` for any status but SSYM_OK; SSYM_E_EMPTY_DICT keeps the crate's behaviour (a panic, :369).

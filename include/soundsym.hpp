@@ -466,6 +466,102 @@ class SoundDictionary {
     mutable std::vector<ArcSound> packed_;
 };
 
+// The targets of one query set watched in n_lanes growing sources (ssym_spotter; soundsym_amd.h "Watching"): a push costs
+// the new frames alone, best() is SoundDictionary::spot's answer for what a lane has consumed, and occurrences come as
+// events under a causal rule (not spot_all's greedy: a span once emitted is never revised).
+class Spotter {
+  public:
+    using Spot = SoundDictionary::Spot;
+    struct Event {
+        uint32_t lane, target;
+        Spot spot;                  // source_index = the lane
+    };
+    Spotter(std::shared_ptr<Context> ctx, const std::vector<ArcSound> &targets, uint32_t n_lanes = 1,
+            const std::vector<double> *max_cost = nullptr)
+        : ctx_(std::move(ctx)), lanes_(n_lanes), targets_((uint32_t)targets.size())
+    {
+        if (max_cost && max_cost->size() != targets.size())
+            throw Error(SSYM_E_INVALID, "max_cost must hold one value per target");
+        std::vector<double> flat;
+        std::vector<uint64_t> off;
+        pack_features(targets, flat, off);
+        ctx_->check(ssym_queries_create(ctx_->get(), flat.data(), off.data(), targets_, (uint32_t)NCOEFFS, &q_));
+        const int32_t rc = ssym_spotter_create(ctx_->get(), q_, n_lanes, max_cost ? max_cost->data() : nullptr, &sp_);
+        if (rc != SSYM_OK) {
+            ssym_queries_destroy(ctx_->get(), q_);
+            ctx_->check(rc);
+        }
+    }
+    ~Spotter()
+    {
+        ssym_spotter_destroy(ctx_->get(), sp_);      // the spotter reads the queries: it goes first
+        ssym_queries_destroy(ctx_->get(), q_);
+    }
+    Spotter(const Spotter &) = delete;
+    Spotter &operator=(const Spotter &) = delete;
+
+    // lane l consumes frames [frame_offsets[l], frame_offsets[l + 1]) of feats (NCOEFFS values each); the events it emits
+    std::vector<Event> push(const std::vector<double> &feats, const std::vector<uint64_t> &frame_offsets)
+    {
+        if (frame_offsets.size() != (size_t)lanes_ + 1)
+            throw Error(SSYM_E_INVALID, "frame_offsets must hold n_lanes + 1 entries");
+        uint64_t n = 0;
+        ctx_->check(ssym_spotter_push(ctx_->get(), sp_, feats.data(), frame_offsets.data(), 0, &n, nullptr, nullptr));
+        return events(n);
+    }
+    // every lane consumes, in place, what the stream's lane holds beyond the frames consumed
+    std::vector<Event> follow(const ssym_stream *stream)
+    {
+        uint64_t n = 0;
+        ctx_->check(ssym_spotter_follow(ctx_->get(), sp_, stream, 0, &n, nullptr, nullptr));
+        return events(n);
+    }
+    // "the lane has ended": what it has pending
+    std::vector<Event> flush(uint32_t lane)
+    {
+        uint64_t n = 0;
+        ctx_->check(ssym_spotter_flush(ctx_->get(), sp_, lane, &n));
+        return events(n);
+    }
+    // [lane * n_targets + target]: the best span of what the lane has consumed
+    std::vector<Spot> best() const
+    {
+        const size_t np = (size_t)lanes_ * targets_;
+        std::vector<double> cost(np);
+        std::vector<uint32_t> start(np), end(np);
+        ctx_->check(ssym_spotter_best(ctx_->get(), sp_, cost.data(), start.data(), end.data(), 0));
+        std::vector<Spot> out(np);
+        for (size_t p = 0; p < np; ++p)
+            out[p] = end[p] == SSYM_NO_MATCH ? Spot{SSYM_NO_MATCH, SSYM_NO_MATCH, SSYM_NO_MATCH, cost[p]}
+                                             : Spot{(uint32_t)(p / targets_), start[p], end[p], cost[p]};
+        return out;
+    }
+    std::vector<uint64_t> counts() const
+    {
+        std::vector<uint64_t> out(lanes_);
+        ctx_->check(ssym_spotter_counts(sp_, out.data()));
+        return out;
+    }
+    void reset(uint32_t lane) { ctx_->check(ssym_spotter_reset(ctx_->get(), sp_, lane)); }
+
+  private:
+    std::vector<Event> events(uint64_t n) const
+    {
+        std::vector<uint32_t> lane(n), tgt(n), start(n), end(n);
+        std::vector<double> cost(n);
+        if (n)
+            ctx_->check(ssym_spotter_events(ctx_->get(), sp_, lane.data(), tgt.data(), cost.data(), start.data(), end.data(), 0));
+        std::vector<Event> out(n);
+        for (uint64_t k = 0; k < n; ++k)
+            out[k] = Event{lane[k], tgt[k], Spot{lane[k], start[k], end[k], cost[k]}};
+        return out;
+    }
+    std::shared_ptr<Context> ctx_;
+    uint32_t lanes_ = 0, targets_ = 0;
+    ssym_queries *q_ = nullptr;
+    ssym_spotter *sp_ = nullptr;
+};
+
 // One rank of a SoundDictionary split over the GPUs of one node (source-axis shards, one rank -- thread or process --
 // per GPU): rank g holds sounds [lo, lo + shard.size()) of the whole dictionary and is handed the same targets as every
 // other rank; match_indices returns GLOBAL indices, the same complete answer on every rank, bit for bit the unsharded

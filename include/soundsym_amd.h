@@ -58,6 +58,7 @@ typedef struct ssym_samples ssym_samples; /* the dictionary sounds' SAMPLES, res
 typedef struct ssym_comm ssym_comm;       /* one rank of a source-sharded run: an RCCL communicator  */
 typedef struct ssym_gmm ssym_gmm;         /* a trained Gaussian mixture (the partitioner's model)    */
 typedef struct ssym_stream ssym_stream;   /* growing sounds: samples + analysis resident on the GPU  */
+typedef struct ssym_spotter ssym_spotter; /* targets watched in growing sources: resumable spotting   */
 
 enum {
     SSYM_OK = 0,
@@ -787,6 +788,71 @@ SSYM_API int32_t ssym_stream_samples_device(const ssym_stream *st, uint32_t lane
 SSYM_API int32_t ssym_stream_descriptors(ssym_ctx *ctx, ssym_stream *st, double *out_max_power, double *out_mean);
 /* empty one lane; its capacity stays */
 SSYM_API int32_t ssym_stream_reset(ssym_ctx *ctx, ssym_stream *st, uint32_t lane);
+
+/* Watching (DESIGN.md section 2 "Watching" and section 5.17): streaming DTW spotting.  A spotter watches n_lanes
+ * independent growing sources ("lanes") for every target of one query set.  c, D, st, the squared option and the
+ * arithmetic are those of ssym_dtw_spot; i is the absolute frame number within everything the lane has consumed, j a
+ * target frame; for lane l and target t the profile is that of "Occurrences": delta(i) = D(i,Fb-1), s(i) = st(i,Fb-1).
+ *   resume  : after consuming n frames the spotter holds, per (l,t): n, row n-1 of (D, st) [Fb entries each], the running
+ *             best, and the reporting state below.  Consuming frames n ... n+m-1 computes rows n ... n+m-1 from that row.
+ *   best    : (cost, start, end) = the first least delta(i) over i ascending from (none, +inf), strict < -- ssym_dtw_spot's
+ *             rule: after any push it is ssym_dtw_spot's result for (the frames consumed so far, target), bit for bit
+ *   report  : per (l,t), state pend = none, last = none.  For i ascending with (d, s) = (delta(i), s(i)):
+ *               1. if pend and s > pend.end:           emit pend;  last = pend.end;  pend = none
+ *               2. candidate  iff  d is finite, d <= max_cost[t] (+inf when none is given; NaN fails) and
+ *                                  (last = none or s > last)
+ *               3. if candidate and (pend = none or d < pend.cost):   pend = (d, s, i)
+ *   flush   : if pend: emit pend; last = pend.end; pend = none        (an explicit call: "the lane has ended")
+ *   nothing : a target without frames never has a candidate; its best is (+inf, SSYM_NO_MATCH, SSYM_NO_MATCH)
+ * So: however the frames of a lane are cut into pushes, the profile, the best after every push and the events (with the
+ * push that emits each) are bit for bit those of one push of the whole; the emitted spans of one (l,t) are pairwise
+ * disjoint in frames and their ends ascend; every emitted cost has the bits ssym_pair_matrix(exact = 1) gives for (frames
+ * start ... end, target); of a run of mutually overlapping candidates the first least is reported; an event is emitted by
+ * the push that consumes the first row i with s(i) > pend.end, or by a flush -- never earlier, never lost.  The rule is
+ * causal and is NOT ssym_dtw_spot_all's greedy: it decides with what it has seen, and a later, better span that overlaps a
+ * span already emitted is rejected by step 2, not preferred.  The cost is NOT normalised by any length.
+ * ssym_spotter_create: q's resident features are READ BY THE SPOTTER FOR AS LONG AS IT LIVES: destroy the spotter first.
+ *   max_cost   HOST memory, n_targets f64, one threshold per target; NULL: none
+ *   The state, 12 bytes x (frames of all targets) x n_lanes, is allocated here.  An empty query set is allowed.
+ * ssym_spotter_push: appends feats[frame_offsets[l] .. frame_offsets[l+1]) (frames of q's dim, f64, HOST memory whatever
+ *   the context's dtype) to lane l, for every lane; empty chunks are allowed.
+ *   frame_offsets      n_lanes + 1 (HOST), non-decreasing
+ *   out_n_events       the events this call emitted (read them with ssym_spotter_events)
+ *   out_profile_cost, out_profile_start   nullable: the new rows' delta (f64) and s (u32), laid out [lane][target][new row]
+ *                      (HOST, or device memory with SSYM_OUT_DEVICE)
+ * ssym_spotter_follow: for every lane, consumes the frames the stream's lane holds beyond those consumed, read in place
+ *   (ssym_stream_frames_device: no copy).  q's dim must equal the stream's n_coeffs and the lane counts must be equal; a
+ *   lane that holds fewer frames than were consumed (the stream was reset) is SSYM_E_INVALID: call ssym_spotter_reset.
+ *   Outputs as for ssym_spotter_push; the new rows of lane l are the stream's frame count minus ssym_spotter_counts'.
+ * ssym_spotter_events: the events of the last push / follow / flush, out_n_events of them, ordered by (lane, target, end);
+ *   every output nullable: lane, target, start, end u32, cost f64 (HOST, or device memory with SSYM_OUT_DEVICE).
+ * ssym_spotter_flush: the flush of one lane for every target; the lane goes on consuming afterwards.
+ * ssym_spotter_best: [n_lanes][n_targets], each output nullable (HOST, or device memory with SSYM_OUT_DEVICE).
+ * ssym_spotter_counts: frames consumed per lane, n_lanes u64 (HOST).  Host arithmetic, no device work.
+ * ssym_spotter_reset: one lane back to "nothing consumed" (best, pend and last included).
+ * Limits: those of ssym_dtw_spot (a dtw context without a band, targets of at most 4096 frames, dim <= 64), and a lane
+ * consumes at most 2^31 - 1 = 2147483647 frames (st is u32): beyond them SSYM_E_UNSUPPORTED.  n_lanes = 0, a NaN in
+ * max_cost, NULL handles, NULL frame_offsets / out_n_events / feats with frames to read, decreasing offsets, a lane
+ * outside the spotter, a handle of another context: SSYM_E_INVALID -- all with a message, before device memory is touched
+ * and with the spotter as it was.  The profile of a call lives in device scratch at 12 bytes per (pair, new row); a push
+ * whose profile would exceed 512 MiB runs as several slices of rows in the same call, with the same results.  Two
+ * synchronisations per slice (the events are counted, the log grown, then written).  ssym_get_timings afterwards:
+ * main_ms = the forward kernel(s), reduce_ms = the reporting, n_pairs = n_lanes * n_targets. */
+SSYM_API int32_t ssym_spotter_create(ssym_ctx *ctx, const ssym_queries *q, uint32_t n_lanes, const double *max_cost,
+                                     ssym_spotter **out);
+SSYM_API int32_t ssym_spotter_destroy(ssym_ctx *ctx, ssym_spotter *sp);
+SSYM_API int32_t ssym_spotter_push(ssym_ctx *ctx, ssym_spotter *sp, const double *feats, const uint64_t *frame_offsets,
+                                   uint32_t flags, uint64_t *out_n_events, double *out_profile_cost,
+                                   uint32_t *out_profile_start);
+SSYM_API int32_t ssym_spotter_follow(ssym_ctx *ctx, ssym_spotter *sp, const ssym_stream *stream, uint32_t flags,
+                                     uint64_t *out_n_events, double *out_profile_cost, uint32_t *out_profile_start);
+SSYM_API int32_t ssym_spotter_events(ssym_ctx *ctx, const ssym_spotter *sp, uint32_t *out_lane, uint32_t *out_target,
+                                     double *out_cost, uint32_t *out_start, uint32_t *out_end, uint32_t flags);
+SSYM_API int32_t ssym_spotter_flush(ssym_ctx *ctx, ssym_spotter *sp, uint32_t lane, uint64_t *out_n_events);
+SSYM_API int32_t ssym_spotter_best(ssym_ctx *ctx, const ssym_spotter *sp, double *out_cost, uint32_t *out_start,
+                                   uint32_t *out_end, uint32_t flags);
+SSYM_API int32_t ssym_spotter_counts(const ssym_spotter *sp, uint64_t *out_frames);
+SSYM_API int32_t ssym_spotter_reset(ssym_ctx *ctx, ssym_spotter *sp, uint32_t lane);
 
 #ifdef __cplusplus
 }

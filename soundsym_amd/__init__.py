@@ -11,7 +11,7 @@ from ._native import (  # noqa: F401
     SsymError,
     build,
 )
-from .engine import DeviceFrames, Engine, Gmm, Stream, pack_segments, stream_plan  # noqa: F401
+from .engine import DeviceFrames, Engine, Gmm, Spotter, Stream, pack_segments, stream_plan  # noqa: F401
 from .api import (  # noqa: F401
     Alignment,
     BIN,
@@ -23,6 +23,7 @@ from .api import (  # noqa: F401
     SoundDictionary,
     SoundSequence,
     Spot,
+    Watch,
     analyze_mfccs,
     analyze_sounds,
     cosine_sim_angular,
@@ -31,11 +32,12 @@ from .api import (  # noqa: F401
     length_fit,
     push_sounds,
     train_model,
+    watch,
 )
 
 __all__ = [
     "ABI_SYMBOLS", "Alignment", "BIN", "DeviceFrames", "EmptyDictionaryError", "Engine", "Gmm", "HOP", "LIB_PATH", "NCLUSTERS", "NCOEFFS",
     "Partitioner", "Sound", "SoundDictionary", "SoundSequence", "Spot", "SsymError", "analyze_mfccs", "analyze_sounds", "build",
     "cosine_sim_angular", "discretize",
-    "discretize_with_model", "length_fit", "pack_segments", "push_sounds", "Stream", "stream_plan", "train_model",
+    "discretize_with_model", "length_fit", "pack_segments", "push_sounds", "Spotter", "Stream", "stream_plan", "train_model", "Watch", "watch",
 ]

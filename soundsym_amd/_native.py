@@ -55,6 +55,8 @@ ABI_SYMBOLS = [
     "ssym_stream_create", "ssym_stream_destroy", "ssym_stream_push", "ssym_stream_seed", "ssym_stream_counts",
     "ssym_stream_read", "ssym_stream_frames_device", "ssym_stream_samples_device", "ssym_stream_descriptors",
     "ssym_stream_reset",
+    "ssym_spotter_create", "ssym_spotter_destroy", "ssym_spotter_push", "ssym_spotter_follow", "ssym_spotter_events",
+    "ssym_spotter_flush", "ssym_spotter_best", "ssym_spotter_counts", "ssym_spotter_reset",
     "ssym_dtw_align_sizes", "ssym_dtw_align",
     "ssym_dtw_spot", "ssym_spot_queries", "ssym_dtw_spot_all",
     "ssym_reconstruct_warped", "ssym_reconstruct_wsola",
@@ -335,6 +337,24 @@ def lib() -> ctypes.CDLL:
     L.ssym_stream_descriptors.argtypes = [vp, vp, vp, vp]
     L.ssym_stream_reset.restype = i32
     L.ssym_stream_reset.argtypes = [vp, vp, u32]
+    L.ssym_spotter_create.restype = i32
+    L.ssym_spotter_create.argtypes = [vp, vp, u32, vp, pvp]
+    L.ssym_spotter_destroy.restype = i32
+    L.ssym_spotter_destroy.argtypes = [vp, vp]
+    L.ssym_spotter_push.restype = i32
+    L.ssym_spotter_push.argtypes = [vp, vp, vp, vp, u32, ctypes.POINTER(u64), vp, vp]
+    L.ssym_spotter_follow.restype = i32
+    L.ssym_spotter_follow.argtypes = [vp, vp, vp, u32, ctypes.POINTER(u64), vp, vp]
+    L.ssym_spotter_events.restype = i32
+    L.ssym_spotter_events.argtypes = [vp, vp, vp, vp, vp, vp, vp, u32]
+    L.ssym_spotter_flush.restype = i32
+    L.ssym_spotter_flush.argtypes = [vp, vp, u32, ctypes.POINTER(u64)]
+    L.ssym_spotter_best.restype = i32
+    L.ssym_spotter_best.argtypes = [vp, vp, vp, vp, vp, u32]
+    L.ssym_spotter_counts.restype = i32
+    L.ssym_spotter_counts.argtypes = [vp, vp]
+    L.ssym_spotter_reset.restype = i32
+    L.ssym_spotter_reset.argtypes = [vp, vp, u32]
     _lib = L
     return L
 

@@ -390,6 +390,78 @@ class Spot:
                                                                    self.cost)
 
 
+class Watch:
+    """Targets watched in growing Sounds (`watch`): the sounds' shared stream followed by a Spotter.  Events are
+    (sound index, target index, Spot) with Spot.source_index the sound index; frames are those of the sound, so
+    Spot.sample_span applies as it is."""
+
+    def __init__(self, sounds, stream, spotter, queries):
+        self.sounds, self.stream, self.spotter, self._queries = sounds, stream, spotter, queries
+
+    def _events(self):
+        lane, tgt, cost, start, end = self.spotter.events()
+        return [(int(lane[k]), int(tgt[k]), Spot(int(lane[k]), int(start[k]), int(end[k]), cost[k]))
+                for k in range(lane.size)]
+
+    def poll(self):
+        """Consume what the sounds have gained since the last poll (in place, on the GPU) and return the events that
+        emits, ordered by (sound, target, end)."""
+        self.spotter.follow(self.stream)
+        return self._events()
+
+    def flush(self):
+        """"The sounds have ended": what is pending is emitted, for every sound."""
+        out = []
+        for lane in range(self.spotter.n_lanes):
+            self.spotter.flush(lane)
+            out += self._events()
+        return out
+
+    def best(self):
+        """[sound][target] the best span so far as a Spot (SoundDictionary.spot's for what was consumed)."""
+        cost, start, end = self.spotter.best()
+        return [[Spot(l, int(start[l, t]), int(end[l, t]), cost[l, t]) if int(end[l, t]) != NO_MATCH else Spot.none()
+                 for t in range(cost.shape[1])] for l in range(cost.shape[0])]
+
+    def close(self):
+        self.spotter.close()
+        self._queries.close()
+
+
+def watch(sounds: Sequence[Sound], targets: Sequence[Sound], max_cost=None, engine: Optional[Engine] = None) -> Watch:
+    """Watch for `targets` in Sounds that are fed with push_samples / push_sounds (streaming DTW spotting, DESIGN.md
+    section 2 "Watching"; dtw engines without a band).  The sounds must be resident and share one stream, sound i in lane
+    i -- what one push_sounds(sounds, ...) leaves -- ValueError otherwise, before any device work.  max_cost: a scalar or
+    one value per target.  The first poll consumes everything the sounds hold."""
+    sounds, targets = list(sounds), list(targets)
+    first = sounds[0]._stream if sounds else None
+    if first is None or not first[0].ptr or first[0].n_lanes != len(sounds) or \
+            any(s._stream is None or s._stream[0] is not first[0] or s._stream[1] != i for i, s in enumerate(sounds)):
+        raise ValueError("watch: the sounds must share one stream (feed them together with push_sounds first)")
+    st = first[0]
+    e = engine or st.engine
+    if e is not st.engine:
+        raise ValueError("watch: the engine must be the one that holds the sounds' stream")
+    if getattr(e, "metric", None) != "dtw":
+        raise SsymError(SSYM_E_UNSUPPORTED, "watch aligns with dtw: a refcos engine has no alignment")
+    if any(t.ncoeffs != st.ncoeffs for t in targets):
+        raise ValueError("watch: the targets' ncoeffs must be the sounds'")
+    if max_cost is not None:
+        mc = np.asarray(max_cost, dtype=np.float64)
+        if mc.ndim and mc.size != len(targets):
+            raise ValueError("max_cost must be a scalar or one value per target")
+        if np.isnan(mc).any():
+            raise ValueError("max_cost must not be NaN")
+    flat, off = pack_segments([t.mfccs() for t in targets], st.ncoeffs, e.np_dtype)
+    q = e.queries(flat, off, st.ncoeffs)
+    try:
+        sp = e.spotter(q, len(sounds), max_cost)
+    except Exception:
+        q.close()
+        raise
+    return Watch(sounds, st, sp, q)
+
+
 class SoundDictionary:
     """Cache of Sounds searched by similarity (src/sound.rs:290-371)."""
 

@@ -70,22 +70,6 @@ struct SpotAllArgs : SpotArgs {
     uint64_t slotFrames;         // >= the longest listed source
 };
 
-// the first minimum among the 64 lanes' candidates (bestD f64, bestEnd u32, bestSt u32), ordered by (D, row), in every
-// lane; a lane without a candidate holds (+inf, 0xffffffff), which loses against every candidate and ties with its like.
-// One text for the kernel's end reduction and for the selection passes, as a macro: the same lines as a function cost
-// dtw_spot_kernel<64> 18 spilled VGPRs and dtw_spot_kernel<14> one more register
-#define SSYM_SPOT_FIRST_MIN(bestD, bestEnd, bestSt)                                                                       \
-    _Pragma("unroll") for (int m_ = 32; m_ >= 1; m_ >>= 1)                                                                \
-    {                                                                                                                     \
-        const double oD_ = __shfl_xor(bestD, m_);                                                                         \
-        const uint32_t oE_ = (uint32_t)__shfl_xor((int)bestEnd, m_), oS_ = (uint32_t)__shfl_xor((int)bestSt, m_);         \
-        if (oD_ < bestD || (oD_ == bestD && oE_ < bestEnd)) {                                                             \
-            bestD = oD_;                                                                                                  \
-            bestEnd = oE_;                                                                                                \
-            bestSt = oS_;                                                                                                 \
-        }                                                                                                                 \
-    }
-
 // pair k of ssym_dtw_spot_all has cnt occurrences: the count, and the slots behind them (maxSpots <= 64: one per lane)
 __device__ __forceinline__ void spot_all_pad(const SpotAllArgs &a, uint32_t k, uint32_t cnt)
 {

@@ -106,6 +106,22 @@ __device__ __forceinline__ uint32_t wave_pred(double up, double lf, double dg)
     return (dg <= up && dg <= lf) ? 0u : (up <= lf ? 1u : 2u);
 }
 
+// the first minimum among the 64 lanes' candidates (bestD f64, bestEnd u32, bestSt u32), ordered by (D, row), in every
+// lane; a lane without a candidate holds (+inf, 0xffffffff), which loses against every candidate and ties with its like.
+// One text for the spot kernels' end reduction, the selection passes and the spotter, as a macro: the same lines as a function cost
+// dtw_spot_kernel<64> 18 spilled VGPRs and dtw_spot_kernel<14> one more register
+#define SSYM_SPOT_FIRST_MIN(bestD, bestEnd, bestSt)                                                                       \
+    _Pragma("unroll") for (int m_ = 32; m_ >= 1; m_ >>= 1)                                                                \
+    {                                                                                                                     \
+        const double oD_ = __shfl_xor(bestD, m_);                                                                         \
+        const uint32_t oE_ = (uint32_t)__shfl_xor((int)bestEnd, m_), oS_ = (uint32_t)__shfl_xor((int)bestSt, m_);         \
+        if (oD_ < bestD || (oD_ == bestD && oE_ < bestEnd)) {                                                             \
+            bestD = oD_;                                                                                                  \
+            bestEnd = oE_;                                                                                                \
+            bestSt = oS_;                                                                                                 \
+        }                                                                                                                 \
+    }
+
 // ---- host: launch geometry ----------------------------------------------------------------------------------------------
 
 inline int wave_dimr(uint32_t dim) { return dim <= 14 ? 14 : dim <= 16 ? 16 : dim <= 40 ? 40 : 64; }

@@ -320,6 +320,9 @@ struct Blocks {
 int32_t launch_frame_means(ssym_ctx *ctx, const double *feats, const uint64_t *off, uint32_t n, uint32_t dim,
                            double *mean);
 
+// stream.hip: lanes, values per frame and owning context of a stream
+void stream_shape(const ssym_stream *st, uint32_t *n_lanes, uint32_t *n_coeffs, const ssym_ctx **ctx);
+
 // dtw_filter.hip
 bool filter_supported(const ssym_ctx *ctx, const SegmentSet &src, const SegmentSet &tgt);
 // a band the banded kernel cannot take: the unbanded filter runs instead and bounds the banded cost from below

@@ -556,6 +556,16 @@ int32_t stream_reset(ssym_ctx *ctx, ssym_stream *st, uint32_t lane)
 }
 
 }  // namespace
+
+// what ssym_spotter_follow (dtw_spotter.hip) checks a stream against; the frames it reads come through
+// ssym_stream_frames_device
+void stream_shape(const ssym_stream *st, uint32_t *n_lanes, uint32_t *n_coeffs, const ssym_ctx **ctx)
+{
+    *n_lanes = st->nLanes;
+    *n_coeffs = st->nc;
+    *ctx = st->ctx;
+}
+
 }  // namespace ssym
 
 using namespace ssym;

@@ -331,6 +331,132 @@ class Stream:
             pass
 
 
+def _spotter_args(q, n_lanes, max_cost):
+    """(lanes, per-target thresholds as a contiguous f64 array or None) of Engine.spotter, checked before the library is
+    asked."""
+    lanes = int(n_lanes)
+    if lanes < 1:
+        raise ValueError("n_lanes must be at least 1")
+    if max_cost is None:
+        return lanes, None
+    mc = np.asarray(max_cost, dtype=np.float64)
+    if mc.ndim == 0:
+        mc = np.full(q.n, float(mc))
+    mc = np.ascontiguousarray(mc.reshape(-1))
+    if mc.size != q.n:
+        raise ValueError("max_cost must be a scalar or one value per target")
+    if np.isnan(mc).any():
+        raise ValueError("max_cost must not be NaN")
+    return lanes, mc
+
+
+class Spotter:
+    """The targets of a query set watched in `n_lanes` growing sources (ssym_spotter; definition in
+    include/soundsym_amd.h and DESIGN.md section 2 "Watching"): a push costs the new frames alone, the best span so far is
+    ssym_dtw_spot's for everything consumed, and occurrences are reported as events by a causal rule.  The spotter reads
+    the query set's resident features for as long as it lives: it keeps `q` alive and must be closed before it."""
+
+    def __init__(self, engine: "Engine", ptr: int, q: _Handle, n_lanes: int):
+        self.engine, self.ptr, self.q, self.n_lanes, self.n_targets, self.dim = engine, ptr, q, n_lanes, q.n, q.dim
+        self.n_events = 0
+
+    def _run(self, call, new_rows, want_profile: bool):
+        n = ctypes.c_uint64()
+        pd = ps = None
+        if want_profile:
+            total = int(np.sum(new_rows)) * self.n_targets
+            pd, ps = np.zeros(total, dtype=np.float64), np.zeros(total, dtype=np.uint32)
+        nat.check(call(ctypes.byref(n), pd.ctypes.data if pd is not None and pd.size else None,
+                       ps.ctypes.data if ps is not None and ps.size else None), self.engine.ctx)
+        self.n_events = int(n.value)
+        if not want_profile:
+            return self.n_events
+        cuts = np.cumsum([0] + [int(r) * self.n_targets for r in new_rows])
+        shape = lambda x: [x[cuts[l]:cuts[l + 1]].reshape(self.n_targets, int(new_rows[l])) for l in range(self.n_lanes)]
+        return self.n_events, shape(pd), shape(ps)
+
+    def push(self, feats, frame_offsets=None, want_profile: bool = False):
+        """ssym_spotter_push: lane l consumes the frames feats[frame_offsets[l]:frame_offsets[l+1]] ([frames][dim]; a
+        one-lane spotter takes the bare block).  Returns the number of events emitted, and with want_profile also the new
+        rows of the profile per lane: two lists of [n_targets][new rows] arrays (delta f64, s uint32)."""
+        x = np.ascontiguousarray(feats, dtype=np.float64).reshape(-1)
+        if x.size % self.dim:
+            raise ValueError(f"feats must hold whole frames of {self.dim} values")
+        if frame_offsets is None:
+            if self.n_lanes != 1:
+                raise ValueError("push: a spotter of several lanes needs frame_offsets")
+            frame_offsets = [0, x.size // self.dim]
+        off = np.ascontiguousarray(frame_offsets, dtype=np.uint64).reshape(-1)
+        if off.size != self.n_lanes + 1 or np.any(np.diff(off.astype(np.int64)) < 0) or int(off[-1]) * self.dim > x.size:
+            raise ValueError("frame_offsets: n_lanes + 1 non-decreasing frame offsets within `feats`")
+        L = nat.lib()
+        call = lambda n, pd, ps: L.ssym_spotter_push(self.engine.ctx, self.ptr, x.ctypes.data if x.size else None,
+                                                     off.ctypes.data, 0, n, pd, ps)
+        return self._run(call, np.diff(off.astype(np.int64)), want_profile)
+
+    def follow(self, stream: "Stream", want_profile: bool = False):
+        """ssym_spotter_follow: every lane consumes, in place, the frames the stream's lane holds beyond those consumed.
+        Returns as push."""
+        if stream.n_lanes != self.n_lanes or stream.ncoeffs != self.dim:
+            raise ValueError("follow: the stream's lanes and ncoeffs must be the spotter's lanes and dim")
+        new = stream.counts()[1].astype(np.int64) - self.counts().astype(np.int64)
+        L = nat.lib()
+        call = lambda n, pd, ps: L.ssym_spotter_follow(self.engine.ctx, self.ptr, stream.ptr, 0, n, pd, ps)
+        return self._run(call, np.maximum(new, 0), want_profile)
+
+    def events(self):
+        """The events of the last push / follow / flush, ordered by (lane, target, end): (lane uint32 [n], target uint32
+        [n], cost f64 [n], start uint32 [n], end uint32 [n]); end is inclusive."""
+        n = self.n_events
+        lane, tgt, start, end = (np.zeros(n, dtype=np.uint32) for _ in range(4))
+        cost = np.zeros(n, dtype=np.float64)
+        if n:
+            nat.check(nat.lib().ssym_spotter_events(self.engine.ctx, self.ptr, lane.ctypes.data, tgt.ctypes.data,
+                                                    cost.ctypes.data, start.ctypes.data, end.ctypes.data, 0), self.engine.ctx)
+        return lane, tgt, cost, start, end
+
+    def flush(self, lane: int = 0) -> int:
+        """ssym_spotter_flush: "the lane has ended" -- what it has pending is emitted.  Returns the number of events."""
+        if not 0 <= int(lane) < self.n_lanes:
+            raise ValueError(f"lane {lane} outside 0..{self.n_lanes - 1}")
+        n = ctypes.c_uint64()
+        nat.check(nat.lib().ssym_spotter_flush(self.engine.ctx, self.ptr, int(lane), ctypes.byref(n)), self.engine.ctx)
+        self.n_events = int(n.value)
+        return self.n_events
+
+    def best(self):
+        """(cost f64, start uint32, end uint32), each [n_lanes][n_targets]: ssym_dtw_spot's result for what every lane has
+        consumed so far; +inf and NO_MATCH where there is none."""
+        shape = (self.n_lanes, self.n_targets)
+        cost, start, end = np.zeros(shape), np.zeros(shape, dtype=np.uint32), np.zeros(shape, dtype=np.uint32)
+        nat.check(nat.lib().ssym_spotter_best(self.engine.ctx, self.ptr, cost.ctypes.data, start.ctypes.data,
+                                              end.ctypes.data, 0), self.engine.ctx)
+        return cost, start, end
+
+    def counts(self) -> np.ndarray:
+        """Frames consumed per lane [n_lanes] (u64)."""
+        out = np.zeros(self.n_lanes, dtype=np.uint64)
+        nat.check(nat.lib().ssym_spotter_counts(self.ptr, out.ctypes.data), self.engine.ctx)
+        return out
+
+    def reset(self, lane: int = 0) -> None:
+        """One lane back to "nothing consumed"."""
+        if not 0 <= int(lane) < self.n_lanes:
+            raise ValueError(f"lane {lane} outside 0..{self.n_lanes - 1}")
+        nat.check(nat.lib().ssym_spotter_reset(self.engine.ctx, self.ptr, int(lane)), self.engine.ctx)
+
+    def close(self):
+        if self.ptr and self.engine.ctx:
+            nat.lib().ssym_spotter_destroy(self.engine.ctx, self.ptr)
+        self.ptr = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class Comm:
     """One rank of a source-sharded run: an RCCL communicator bound to an Engine (ssym_comm)."""
 
@@ -844,6 +970,15 @@ class Engine:
         nat.check(nat.lib().ssym_stream_create(self.ctx, int(n_lanes), float(sample_rate), int(ncoeffs), float(f_lo),
                                                float(f_hi), int(capacity), ctypes.byref(out)), self.ctx)
         return Stream(self, out.value, int(n_lanes), int(ncoeffs), float(sample_rate))
+
+    def spotter(self, q: _Handle, n_lanes: int = 1, max_cost=None) -> Spotter:
+        """ssym_spotter_create: the targets of `q` watched in `n_lanes` growing sources (dtw engines without a band).
+        max_cost: a scalar or one value per target; an event costs at most that."""
+        lanes, mc = _spotter_args(q, n_lanes, max_cost)
+        out = ctypes.c_void_p()
+        nat.check(nat.lib().ssym_spotter_create(self.ctx, q.ptr, lanes, mc.ctypes.data if mc is not None else None,
+                                                ctypes.byref(out)), self.ctx)
+        return Spotter(self, out.value, q, lanes)
 
     @staticmethod
     def mfcc_num_frames(n_samples: int, pad_tail: bool = False) -> int:
