@@ -263,7 +263,9 @@ SSYM_API int32_t ssym_pair_matrix(ssym_ctx *ctx, const ssym_dict *dict, const ss
  *   dg <= up && dg <= lf, else up (i - 1) if up <= lf, else left (j - 1).
  *   out_cost   n_pairs f64: D(Fa-1, Fb-1), the bits ssym_pair_matrix(exact = 1) returns for the pair
  *   out_len    n_pairs u32: L, or 0 when the cost is not finite (an empty segment, a band that cuts every path, NaN
- *              features, SSYM_NO_MATCH): then neither the path slot nor the map slot of the pair is written
+ *              features, SSYM_NO_MATCH): then neither the path slot nor the map slot of the pair is written.  A pair
+ *              with a feature that is not finite has the exact kernel's cost, ssym_pair_matrix(exact = 1)'s: +inf or
+ *              NaN, never finite (every path crosses the poisoned row or column)
  *   out_path   2 u32 (i, j) per cell, forward order, pair p from cell index path_offsets[p] on
  *   out_map    nullable; u32 per target frame, pair p from map_offsets[p] on: map[j] = the smallest i with (i, j) on the
  *              path (non-decreasing, map[0] = 0)
@@ -296,8 +298,12 @@ SSYM_API int32_t ssym_dtw_align(ssym_ctx *ctx, const ssym_dict *dict, const ssym
  * in the arithmetic of ssym_pair_matrix(exact = 1) and ssym_dtw_align (f64, k ascending, every operation rounded
  * separately).  So start is where ssym_dtw_align's backtrace from (end, Fb-1) first reaches column 0, cost has the bits
  * of the plain DTW cost of (source frames start ... end, target) -- what ssym_pair_matrix(exact = 1) and ssym_dtw_align
- * give for that cut -- and is the least such cost over all spans.  The cost is NOT normalised by any length.  What
- * features that are not finite give is unspecified (no read leaves its buffer).
+ * give for that cut -- and is the least such cost over all spans.  The cost is NOT normalised by any length.
+ * Features that are not finite: min compares from D(i-1,j), then D(i,j-1), then D(i-1,j-1), strict <, so a NaN source
+ * frame makes every later end a non-candidate for a target of two or more frames (D(i-1,j) carries the NaN down every
+ * column j >= 1; column 0 restarts, so a one-frame target loses that row alone), and a NaN target frame makes every
+ * end NaN or +inf: no spot.  +-inf and a value whose squared difference overflows cost +inf in their own row, and the
+ * rows behind it spot again.  Neither NaN nor +inf wins; no read leaves its buffer.
  * ssym_dtw_spot: pair p = (dictionary segment src_idx[p] - index_base, target tgt_idx[p]); tgt_idx == NULL: target p
  *   (n_pairs <= n_targets).  Any pairing, repeats allowed.  src_idx / tgt_idx are HOST memory.
  *   out_cost   n_pairs f64;  out_start, out_end   n_pairs u32 each: the span's first and last source frame (inclusive)
@@ -337,7 +343,9 @@ SSYM_API int32_t ssym_spot_queries(ssym_ctx *ctx, const ssym_dict *dict, const s
  * So, without max_cost, occurrence 0 is ssym_dtw_spot's result for the pair bit for bit; costs do not decrease with m and
  * equal costs come in ascending end; spans are pairwise disjoint in frames (touching, end_a + 1 = start_b, is allowed);
  * every occurrence's cost has the bits of the plain DTW cost of (source frames start ... end, target), what
- * ssym_pair_matrix(exact = 1) gives for that cut; a NaN delta(i) is never a candidate.  The cost is NOT normalised by any
+ * ssym_pair_matrix(exact = 1) gives for that cut; a NaN delta(i) is never a candidate.  As for ssym_dtw_spot, a NaN
+ * source frame makes every later end a non-candidate for a target of two or more frames, so occurrences behind it are
+ * not found, and a NaN target frame makes every end NaN or +inf: count 0.  The cost is NOT normalised by any
  * length: without max_cost the later occurrences of a recording that holds the target fewer than K times are spans the
  * target merely fits least badly.
  * ssym_dtw_spot_all: the pair list is ssym_dtw_spot's in every respect (tgt_idx == NULL, repeats, index_base,
@@ -810,7 +818,10 @@ SSYM_API int32_t ssym_stream_reset(ssym_ctx *ctx, ssym_stream *st, uint32_t lane
  * start ... end, target); of a run of mutually overlapping candidates the first least is reported; an event is emitted by
  * the push that consumes the first row i with s(i) > pend.end, or by a flush -- never earlier, never lost.  The rule is
  * causal and is NOT ssym_dtw_spot_all's greedy: it decides with what it has seen, and a later, better span that overlaps a
- * span already emitted is rejected by step 2, not preferred.  The cost is NOT normalised by any length.
+ * span already emitted is rejected by step 2, not preferred.  The cost is NOT normalised by any length.  Features that
+ * are not finite as for ssym_dtw_spot, and the stored row carries them across pushes: after a NaN frame a lane reports
+ * nothing more for targets of two or more frames until ssym_spotter_reset (a one-frame target loses that row alone),
+ * and a NaN target frame makes every end NaN or +inf on every lane: no candidate, no event, no best.
  * ssym_spotter_create: q's resident features are READ BY THE SPOTTER FOR AS LONG AS IT LIVES: destroy the spotter first.
  *   max_cost   HOST memory, n_targets f64, one threshold per target; NULL: none
  *   The state, 12 bytes x (frames of all targets) x n_lanes, is allocated here.  An empty query set is allowed.

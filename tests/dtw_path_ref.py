@@ -4,13 +4,44 @@ INFRASTRUCTURE, the reference the GPU paths of ssym_dtw_align are held to.
 D is formed as oracle.np_dtw forms it: c(i,j) = sum_k (a_ik - b_jk)^2 with k ascending, subtraction, product and sum
 rounded separately in f64, the square root rounded separately unless `squared`; D(i,j) = c(i,j) + min(D(i-1,j),
 D(i,j-1), D(i-1,j-1)), D(0,0) = c(0,0), cells with |i - j| > band are +inf.  (Every operation is elementwise IEEE f64,
-so evaluating a whole anti-diagonal at once gives the bits of the cell-by-cell loop; the minimum of three numbers does
-not depend on the order of the comparisons.)
+so evaluating a whole anti-diagonal at once gives the bits of the cell-by-cell loop.)
+
+The minimum is min3 below, the oracle's comparisons in the oracle's order: best = D(i-1,j); if D(i,j-1) < best, take it;
+if D(i-1,j-1) < best, take it.  Among numbers the order does not matter; with a NaN operand it does, because every
+comparison with NaN is false: a NaN in D(i-1,j) stays, a NaN in D(i,j-1) or D(i-1,j-1) is passed over.  So a NaN feature
+does not simply flood the matrix: a NaN source frame i makes row i NaN and, through `up`, every later row from column 1
+on; a NaN target frame j makes column j NaN and every later column +inf (column j + 1 sees NaN in `lf` and `dg`, passes
+over both, and is left with the +inf above row 0).
 
 The path is found backwards from (Fa-1, Fb-1): at (i,j) != (0,0), with dg = D(i-1,j-1), up = D(i-1,j), lf = D(i,j-1)
-(+inf outside the matrix or the band), go diagonally if dg <= up and dg <= lf, else up if up <= lf, else left.
+(+inf outside the matrix or the band), go diagonally if dg <= up and dg <= lf, else up if up <= lf, else left.  With a
+NaN operand the comparisons that name it are false: a NaN in up or in lf gives left, whatever dg holds (the diagonal
+has to pass both comparisons, up has to pass up <= lf); a NaN dg is never taken and leaves up against lf.  (A path is
+only asked for when the cost is finite, and then no cell on it is NaN; the rule matters for the starts that spot_ref
+carries through every cell.)
 map[j] = the smallest i with (i,j) on the path.  A cost that is not finite gives an empty path and an empty map."""
 import numpy as np
+
+
+def min3(up, lf, dg):
+    """The oracle's minimum of D(i-1,j), D(i,j-1), D(i-1,j-1), elementwise: starts from `up`, replaces it by strict <.
+    Not np.minimum, which returns NaN whenever an operand is NaN."""
+    best = np.where(lf < up, lf, up)
+    return np.where(dg < best, dg, best)
+
+
+def bits(x):
+    return np.asarray(x, dtype=np.float64).view(np.uint64)
+
+
+def same_floats(got, want):
+    """Whether two f64 arrays hold the same values: NaN where the other has NaN (whatever its sign and payload: the
+    default NaN differs between processors), the same bits everywhere else."""
+    got, want = np.asarray(got, dtype=np.float64), np.asarray(want, dtype=np.float64)
+    if got.shape != want.shape or not np.array_equal(np.isnan(got), np.isnan(want)):
+        return False
+    keep = ~np.isnan(want)
+    return np.array_equal(bits(got[keep]), bits(want[keep]))
 
 
 def local_costs(a, b, squared=False):
@@ -18,10 +49,11 @@ def local_costs(a, b, squared=False):
     a = np.asarray(a, dtype=np.float64)
     b = np.asarray(b, dtype=np.float64)
     acc = np.zeros((a.shape[0], b.shape[0]), dtype=np.float64)
-    for k in range(a.shape[1]):
-        df = a[:, k][:, None] - b[:, k][None, :]
-        acc = acc + df * df
-    return acc if squared else np.sqrt(acc)
+    with np.errstate(over="ignore", invalid="ignore"):      # a huge or non-finite feature: +inf or NaN, as IEEE has it
+        for k in range(a.shape[1]):
+            df = a[:, k][:, None] - b[:, k][None, :]
+            acc = acc + df * df
+        return acc if squared else np.sqrt(acc)
 
 
 def cumulative(a, b, band=-1, squared=False):
@@ -37,11 +69,35 @@ def cumulative(a, b, band=-1, squared=False):
             i, j = i[keep], j[keep]
             if i.size == 0:
                 continue
-        best = np.minimum(np.minimum(D[i, j + 1], D[i + 1, j]), D[i, j])
+        best = min3(D[i, j + 1], D[i + 1, j], D[i, j])
         if s == 0:
             best = np.zeros(1)
         D[i + 1, j + 1] = c[i, j] + best
     return D[1:, 1:]
+
+
+def cumulative_loop(c, free_start=False):
+    """D from local costs c, one cell at a time with Python floats, written as oracle/ssym_oracle.c writes its inner loop
+    (no band).  free_start: column 0 restarts in every row (spotting) instead of accumulating (plain DTW).  Slow: what
+    the vectorised forms are checked against."""
+    fa, fb = c.shape
+    inf = float("inf")
+    D = [[inf] * fb for _ in range(fa)]
+    for i in range(fa):
+        for j in range(fb):
+            cij = float(c[i, j])
+            if j == 0 and (free_start or i == 0):
+                D[i][j] = cij
+                continue
+            best = D[i - 1][j] if i > 0 else inf
+            lf = D[i][j - 1] if j > 0 else inf
+            dg = D[i - 1][j - 1] if i > 0 and j > 0 else inf
+            if lf < best:
+                best = lf
+            if dg < best:
+                best = dg
+            D[i][j] = cij + best
+    return np.array(D, dtype=np.float64).reshape(fa, fb)
 
 
 def backtrace(D):

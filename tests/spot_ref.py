@@ -11,10 +11,15 @@ c(i,j) is dtw_path_ref.local_costs' (the oracle's operation order), i a source f
     cost    = D(end,Fb-1);  start = st(end,Fb-1);  nothing to spot: (+inf, NO_MATCH, NO_MATCH)
 
 Every operation is elementwise IEEE f64, so evaluating a whole anti-diagonal at once gives the bits of the cell-by-cell
-loop; the minimum of three numbers does not depend on the order of the comparisons."""
+loop.  min is dtw_path_ref.min3, the oracle's comparisons in the oracle's order (from up, then lf, then dg, strict <),
+which matters as soon as an operand is NaN: a NaN up stays, a NaN lf or dg is passed over.  A NaN source frame i
+therefore makes D(i, .) NaN and D(i', j) NaN for every i' > i and j >= 1 (column 0 restarts, so a one-frame target is
+alive again in row i + 1); a NaN target frame j makes D(., j) NaN and D(., j') = +inf for j' > j.  The predecessor
+rule's <= comparisons are false on NaN: a NaN in up or lf picks left whatever dg holds, a NaN dg is never picked and
+leaves up against lf.  The end rule's strict < keeps NaN and +inf from winning."""
 import numpy as np
 
-from dtw_path_ref import local_costs
+from dtw_path_ref import local_costs, min3
 
 NO_MATCH = 0xFFFFFFFF
 
@@ -29,7 +34,7 @@ def matrices(a, b, squared=False):
         i = np.arange(max(0, s - fb + 1), min(fa - 1, s) + 1)
         j = s - i
         dg, up, lf = D[i, j], D[i, j + 1], D[i + 1, j]
-        cur = c[i, j] + np.minimum(np.minimum(up, lf), dg)
+        cur = c[i, j] + min3(up, lf, dg)
         st = np.where((dg <= up) & (dg <= lf), S[i, j], np.where(up <= lf, S[i, j + 1], S[i + 1, j]))
         first = j == 0
         D[i + 1, j + 1] = np.where(first, c[i, j], cur)

@@ -117,3 +117,77 @@ def test_band_keeps_the_path_inside():
     cost, path, _ = ref.align(a, b, band=1, squared=True)
     ref.check_path(path, 4, 5, 1)
     assert cost == ref.resum(a, b, path, True) and cost > 1.0
+
+
+# ---- the comparison order of min3, which only a NaN can tell apart ------------------------------------------------------
+
+POISON = [float("nan"), float("inf"), float("-inf"), 1e200]          # 1e200: the squared difference overflows to +inf
+
+
+def _cumulative_np_minimum(a, b, band=-1, squared=False):
+    """cumulative() as it was before min3: np.minimum, which is order-free and returns NaN for any NaN operand."""
+    c = ref.local_costs(a, b, squared)
+    fa, fb = c.shape
+    D = np.full((fa + 1, fb + 1), np.inf)
+    for s in range(fa + fb - 1):
+        i = np.arange(max(0, s - fb + 1), min(fa - 1, s) + 1)
+        j = s - i
+        if band >= 0:
+            keep = np.abs(i - j) <= band
+            i, j = i[keep], j[keep]
+            if i.size == 0:
+                continue
+        best = np.minimum(np.minimum(D[i, j + 1], D[i + 1, j]), D[i, j])
+        if s == 0:
+            best = np.zeros(1)
+        D[i + 1, j + 1] = c[i, j] + best
+    return D[1:, 1:]
+
+
+def poisoned(rng, fa, fb, dim, value, side, frame):
+    """A real-valued pair with one poisoned value: in source frame `frame` (side "src") or target frame `frame`."""
+    a, b = rng.standard_normal((fa, dim)), rng.standard_normal((fb, dim))
+    (a if side == "src" else b)[frame, int(rng.integers(0, dim))] = value
+    return a, b
+
+
+def test_min3_orders_its_comparisons_as_the_oracle_does():
+    nan, inf = float("nan"), float("inf")
+    up, lf, dg = np.array([nan, 1.0, 1.0, nan, 2.0, inf]), np.array([1.0, nan, 2.0, nan, nan, nan]), np.array([2.0, 2.0, nan, 0.0, 3.0, nan])
+    got = ref.min3(up, lf, dg)
+    assert ref.same_floats(got, [nan, 1.0, 1.0, nan, 2.0, inf])       # a NaN up stays; a NaN lf or dg is passed over
+    assert np.isnan(np.minimum(np.minimum(up, lf), dg)).all()         # what np.minimum makes of the same operands
+    assert ref.same_floats([nan, 1.0, -0.0], [-nan, 1.0, -0.0]) and not ref.same_floats([0.0], [-0.0])
+    assert not ref.same_floats([nan, 1.0], [1.0, nan]) and not ref.same_floats([1.0], [1.0, 1.0])
+
+
+@pytest.mark.parametrize("squared", [False, True])
+@pytest.mark.parametrize("band", [-1, 0, 3, 8])
+def test_finite_inputs_give_the_bits_np_minimum_gave(band, squared):
+    for a, b in _pairs(0xA11 + band + 100 * squared, 30, 12):
+        assert np.array_equal(ref.bits(ref.cumulative(a, b, band, squared)), ref.bits(_cumulative_np_minimum(a, b, band, squared)))
+
+
+@pytest.mark.parametrize("squared", [False, True])
+@pytest.mark.parametrize("value", POISON)
+def test_non_finite_inputs_against_the_cell_loop_and_the_oracle(oracle, value, squared):
+    rng = np.random.default_rng(0xBAD + squared)
+    differs = nans = infs = 0
+    for side, frame in (("src", 0), ("src", 4), ("src", 9), ("tgt", 0), ("tgt", 2), ("tgt", 5)):
+        a, b = poisoned(rng, 10, 6, 3, value, side, frame)
+        D = ref.cumulative(a, b, squared=squared)
+        loop = ref.cumulative_loop(ref.local_costs(a, b, squared))
+        assert np.array_equal(np.isnan(D), np.isnan(loop)), (side, frame)
+        assert ref.same_floats(D, loop), (side, frame)
+        want = oracle.dtw(a.reshape(-1), b.reshape(-1), 3, -1, squared)
+        assert np.isnan(D[-1, -1]) == np.isnan(want) and ref.same_floats(D[-1, -1], want), (side, frame)
+        cost, path, fmap = ref.align(a, b, squared=squared)
+        assert not np.isfinite(cost) and path.shape == (0, 2) and fmap.size == 0
+        old = _cumulative_np_minimum(a, b, squared=squared)
+        differs += int(not ref.same_floats(D, old))
+        nans += int(np.isnan(D[-1, -1]))
+        infs += int(np.isposinf(D[-1, -1]))
+    if np.isnan(value):
+        assert differs >= 1 and nans >= 1 and infs >= 1               # the order shows: np.minimum gives other matrices
+    else:
+        assert differs == 0 and nans == 0 and infs == 6               # +inf costs: no NaN arises, the order is moot

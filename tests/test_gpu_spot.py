@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 import spot_ref
+import wave_lds
 from soundsym_amd import Engine, Sound, SoundDictionary, SoundSequence, Spot
 from soundsym_amd import _native as nat
 from soundsym_amd.engine import pack_segments
@@ -141,6 +142,25 @@ def test_padding_edges_of_every_dimr(dim):
         s.close()
     if dim <= 2:
         assert end_ties >= 1 and start_ties >= 1, (end_ties, start_ties)
+
+
+_LONG = [c for c in wave_lds.CROSSINGS if c[1] > 130]       # (the dim 64 / 41 crossing at 65 frames: test_padding_edges_of_every_dimr)
+
+
+@pytest.mark.parametrize("dim,fb,above", _LONG)
+def test_both_sides_of_every_lds_crossing(dim, fb, above):
+    """The launch's dynamic LDS goes by the longest listed target: one call per length, on the side of 64 KiB the case
+    names (above it the launch sets MaxDynamicSharedMemorySize first), up to the 116736 bytes of dim 64 x 4096 frames."""
+    need = wave_lds.spot_lds_bytes(dim, fb)
+    assert (need > wave_lds.LIMIT) == above, (dim, fb, need)
+    rng = np.random.default_rng(0x1D5 + 4099 * dim + fb)
+    s = _Sets([_frames(rng, f, dim, "real") for f in (65, 130)], [_frames(rng, fb, dim, "real")], dim)
+    si, ti = _all_pairs(2, 1)
+    out = _raw(s, si, ti)
+    _check(s, si, ti, out)
+    assert np.isfinite(out[1][:2]).all()
+    _check_queries(s, _raw_queries(s))
+    s.close()
 
 
 def test_plants_at_the_edges_and_late_in_a_long_source():

@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 import spot_all_ref
+import wave_lds
 from soundsym_amd import HOP, Engine, Sound, SoundDictionary, SoundSequence
 from soundsym_amd import _native as nat
 from soundsym_amd.engine import pack_segments
@@ -160,6 +161,23 @@ def test_padding_edges_of_every_dimr(dim):
         total, _ = _check(s, [0], [0], _raw(s, [0], [0], k=4), 4)
         assert total >= 2
         s.close()
+
+
+_LONG = [c for c in wave_lds.CROSSINGS if c[1] > 130]
+
+
+@pytest.mark.parametrize("dim,fb,above", _LONG)
+def test_both_sides_of_every_lds_crossing(dim, fb, above):
+    """The launch's dynamic LDS goes by the longest listed target: one call per length, on the side of 64 KiB the case
+    names, up to the 116736 bytes of dim 64 x 4096 frames; K = 3."""
+    need = wave_lds.spot_lds_bytes(dim, fb)
+    assert (need > wave_lds.LIMIT) == above, (dim, fb, need)
+    rng = np.random.default_rng(0x1D5 + 4099 * dim + fb)
+    s = _Sets([_frames(rng, f, dim, "real") for f in (65, 130)], [_frames(rng, fb, dim, "real")], dim)
+    si, ti = _all_pairs(2, 1)
+    total, _ = _check(s, si, ti, _raw(s, si, ti, k=3), 3)
+    assert total >= 2
+    s.close()
 
 
 # ---- 3. identical plants and max_cost ------------------------------------------------------------------------------------

@@ -9,6 +9,7 @@ import pytest
 
 import spot_ref
 import watch_ref
+from dtw_path_ref import same_floats
 from soundsym_amd import Engine, Sound, push_sounds, watch
 from soundsym_amd import _native as nat
 from soundsym_amd.engine import pack_segments
@@ -96,9 +97,11 @@ def _same_events(got, want):
         assert _bits(g[0]) == _bits(w[0]) and g[1:] == w[1:], (g, w)
 
 
-def _check_split(w, lanes, cut_lists, profiles=None, flush_end=True):
+def _check_split(w, lanes, cut_lists, profiles=None, flush_end=True, after_push=None):
     """Feed lane l its frames cut at cut_lists[l] (all lists equally long: push p takes rows cuts[p] ... cuts[p+1] - 1 of
-    every lane) and compare every push with the restatement.  Returns the restatement's Reporters."""
+    every lane) and compare every push with the restatement: the profile by NaN mask and then bit for bit (a NaN's sign
+    and payload are the processor's own), everything else bit for bit.  after_push(p), when given, runs after push p has
+    been compared.  Returns the restatement's Reporters."""
     nT, nL = len(w.tgt), len(lanes)
     prof = profiles if profiles is not None else {}
     want = {}
@@ -119,10 +122,13 @@ def _check_split(w, lanes, cut_lists, profiles=None, flush_end=True):
             lo, hi = cut_lists[l][p], cut_lists[l][p + 1]
             d, s = prof[(l, t)]
             if d.size:
-                assert np.array_equal(_bits(pd[l][t]), _bits(d[lo:hi])), (l, t, p)
+                assert np.array_equal(np.isnan(pd[l][t]), np.isnan(d[lo:hi])), (l, t, p)
+                assert same_floats(pd[l][t], d[lo:hi]), (l, t, p)
                 assert np.array_equal(ps[l][t], s[lo:hi].astype(np.uint32)), (l, t, p)
             _same_events(ev.get((l, t), []), per_push[p])
             assert _bits(cost[l, t]) == _bits(bests[p][0]) and (int(start[l, t]), int(end[l, t])) == bests[p][1:], (l, t, p)
+        if after_push is not None:
+            after_push(p)
     assert np.array_equal(w.sp.counts(), [c[-1] for c in cut_lists])
     if flush_end:
         for l in range(nL):

@@ -121,3 +121,34 @@ def test_identical_plants_come_back_in_ascending_end():
     assert np.isinf(cost[3:]).all() and (start[3:] == NO).all() and (end[3:] == NO).all()
     assert spot_all_ref.spot_all(src, tgt, 2, 0.0, squared=True)[3].tolist() == [15, 55]
     assert spot_all_ref.spot_all(src, tgt, 6, -1.0, squared=True)[0] == 0
+
+
+@pytest.mark.parametrize("value", [float("nan"), float("inf"), float("-inf"), 1e200])
+def test_profile_with_a_non_finite_frame_against_the_cell_loop(value):
+    """The profile is the end column of the cell-by-cell loop in the oracle's comparison order (NaN mask, then bits), and
+    on finite inputs it has the bits np.minimum gave."""
+    rng = np.random.default_rng(0xBAD6)
+    for a, b, squared in CASES:
+        delta, _ = spot_all_ref.profile(a, b, squared)
+        c = dtw_path_ref.local_costs(a, b, squared)
+        D = np.full((c.shape[0] + 1, c.shape[1] + 1), np.inf)
+        for i in range(c.shape[0]):
+            for j in range(c.shape[1]):
+                D[i + 1, j + 1] = c[i, j] + (np.minimum(np.minimum(D[i, j + 1], D[i + 1, j]), D[i, j]) if j else 0.0)
+        assert np.array_equal(_bits(delta), _bits(D[1:, -1]))
+    for squared in (True, False):
+        for side, frame in (("src", 0), ("src", 7), ("src", 23), ("tgt", 0), ("tgt", 3), ("tgt", 5)):
+            a, b = rng.standard_normal((24, 3)), rng.standard_normal((6, 3))
+            (a if side == "src" else b)[frame, 1] = value
+            delta, s = spot_all_ref.profile(a, b, squared)
+            loop = dtw_path_ref.cumulative_loop(dtw_path_ref.local_costs(a, b, squared), free_start=True)[:, -1]
+            assert np.array_equal(np.isnan(delta), np.isnan(loop)) and dtw_path_ref.same_floats(delta, loop)
+            count, cost, start, end = spot_all_ref.spot_all(a, b, 8, None, squared)
+            assert not np.isnan(cost).any() and np.isfinite(cost[:count]).all()
+            if side == "tgt":
+                assert count == 0 and (np.isnan(delta).all() if np.isnan(value) and frame == 5 else np.isposinf(delta).all())
+            elif np.isnan(value):
+                assert np.isnan(delta[frame:]).all() and (end[:count] < frame).all() and (count >= 1) == (frame > 0)
+            else:
+                assert np.isposinf(delta[frame]) and np.isfinite(np.delete(delta, frame)).all()
+                assert frame == 23 or (end[:count] > frame).any()             # an occurrence behind the wall

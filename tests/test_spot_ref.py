@@ -84,3 +84,73 @@ def test_nothing_to_spot():
     assert spot_ref.spot(np.zeros((4, 3)), np.zeros((0, 3))) == none
     assert spot_ref.spot_best([], np.zeros((2, 3))) == (spot_ref.NO_MATCH,) + none
     assert spot_ref.spot_best([np.zeros((0, 3))], np.zeros((2, 3))) == (spot_ref.NO_MATCH,) + none
+
+
+# ---- the comparison order of min3, which only a NaN can tell apart ------------------------------------------------------
+
+def _matrices_np_minimum(a, b, squared):
+    """D of matrices() as it was before min3 (np.minimum: order-free, NaN for any NaN operand)."""
+    c = ref.local_costs(a, b, squared)
+    fa, fb = c.shape
+    D = np.full((fa + 1, fb + 1), np.inf)
+    for s in range(fa + fb - 1):
+        i = np.arange(max(0, s - fb + 1), min(fa - 1, s) + 1)
+        j = s - i
+        cur = c[i, j] + np.minimum(np.minimum(D[i, j + 1], D[i + 1, j]), D[i, j])
+        D[i + 1, j + 1] = np.where(j == 0, c[i, j], cur)
+    return D[1:, 1:]
+
+
+def _starts_loop(D):
+    """st of every cell by the predecessor rule, one cell at a time, from a given D."""
+    fa, fb = D.shape
+    S = np.zeros((fa, fb), dtype=np.int64)
+    inf = float("inf")
+    for i in range(fa):
+        S[i, 0] = i
+        for j in range(1, fb):
+            dg = D[i - 1, j - 1] if i > 0 else inf
+            up = D[i - 1, j] if i > 0 else inf
+            lf = D[i, j - 1]
+            S[i, j] = (S[i - 1, j - 1] if i > 0 else -1) if (dg <= up and dg <= lf) else \
+                      (S[i - 1, j] if i > 0 else -1) if up <= lf else S[i, j - 1]
+    return S
+
+
+@pytest.mark.parametrize("kind", ["int", "real"])
+def test_finite_inputs_give_the_bits_np_minimum_gave(kind):
+    for a, b, squared in _cases(kind, 150, 0x5B07 + (kind == "int")):
+        assert np.array_equal(_bits(spot_ref.matrices(a, b, squared)[0]), _bits(_matrices_np_minimum(a, b, squared)))
+
+
+@pytest.mark.parametrize("squared", [False, True])
+@pytest.mark.parametrize("value", [float("nan"), float("inf"), float("-inf"), 1e200])
+def test_non_finite_inputs_against_the_cell_loop(value, squared):
+    rng = np.random.default_rng(0xBAD5 + squared)
+    for side, frame in (("src", 0), ("src", 4), ("src", 9), ("tgt", 0), ("tgt", 2), ("tgt", 5)):
+        a, b = rng.standard_normal((10, 3)), rng.standard_normal((6, 3))
+        (a if side == "src" else b)[frame, int(rng.integers(0, 3))] = value
+        D, S = spot_ref.matrices(a, b, squared)
+        loop = ref.cumulative_loop(ref.local_costs(a, b, squared), free_start=True)
+        assert np.array_equal(np.isnan(D), np.isnan(loop)), (side, frame)
+        assert ref.same_floats(D, loop), (side, frame)
+        assert np.array_equal(S, _starts_loop(loop)), (side, frame)
+        old = _matrices_np_minimum(a, b, squared)
+        cost, start, end = spot_ref.spot(a, b, squared)
+        if side == "tgt":
+            # a poisoned target frame: NaN in its own column, +inf in every later one -- where np.minimum gave NaN
+            assert (np.isnan(D[:, frame]) if np.isnan(value) else np.isposinf(D[:, frame])).all()
+            assert np.isposinf(D[:, frame + 1:]).all() and (cost, start, end) == (float("inf"), spot_ref.NO_MATCH, spot_ref.NO_MATCH)
+            assert ref.same_floats(D, old) == (not np.isnan(value) or frame == 5)
+        elif np.isnan(value):
+            # a NaN source frame: its row, and through `up` every later row from column 1 on; column 0 restarts
+            assert np.isnan(D[frame]).all() and np.isnan(D[frame + 1:, 1:]).all() and np.isfinite(D[:frame]).all()
+            assert np.isfinite(D[frame + 1:, 0]).all()
+            assert (end < frame) if frame else (end == spot_ref.NO_MATCH)
+        else:
+            # a +inf row is a wall, not a poison: the rows behind it spot again
+            assert np.isposinf(D[frame]).all() and np.isfinite(np.delete(D, frame, axis=0)).all() and np.isfinite(cost)
+            assert ref.same_floats(D, old)
+    a = np.zeros((5, 2))
+    a[2, 0] = np.nan                     # one target frame: column 0 alone, which restarts -- the rows after the NaN live
+    assert ref.same_floats(spot_ref.matrices(a, np.ones((1, 2)), True)[0][:, 0], [2.0, 2.0, np.nan, 2.0, 2.0])

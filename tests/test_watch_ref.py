@@ -130,3 +130,33 @@ def test_a_target_without_frames_and_an_empty_lane():
     assert per_push == [[], []] and flushed == {1: []} and bests[-1] == (np.inf, watch_ref.NO_MATCH, watch_ref.NO_MATCH)
     per_push, bests, flushed, _ = watch_ref.watch(np.zeros((0, 2)), np.zeros((3, 2)), [0, 0], flush_after=(0,))
     assert per_push == [[]] and flushed == {0: []}
+
+
+@pytest.mark.parametrize("value", [float("nan"), float("inf"), float("-inf"), 1e200])
+def test_a_non_finite_frame_in_the_lane_or_the_target(value):
+    """whole_profile is the end column of the cell-by-cell loop in the oracle's comparison order (NaN mask, then bits);
+    neither NaN nor +inf is ever a candidate or a best, however the lane is cut."""
+    from dtw_path_ref import cumulative_loop, same_floats
+    for kind, seed in (("real", 0), ("int", 1)):
+        a0, b0, squared = _case(kind, seed)
+        delta0, _ = watch_ref.whole_profile(a0, b0, squared)
+        assert same_floats(delta0, cumulative_loop(local_costs(a0, b0, squared), free_start=True)[:, -1])
+        for side, frame in (("src", 0), ("src", 100), ("src", FRAMES - 1), ("tgt", 0), ("tgt", b0.shape[0] - 1)):
+            a, b = a0.copy(), b0.copy()
+            (a if side == "src" else b)[frame, 1] = value
+            delta, s = watch_ref.whole_profile(a, b, squared)
+            loop = cumulative_loop(local_costs(a, b, squared), free_start=True)[:, -1]
+            assert np.array_equal(np.isnan(delta), np.isnan(loop)) and same_floats(delta, loop)
+            runs = [watch_ref.drive(delta, s, cuts, None, flush_after=(len(cuts) - 2,)) for cuts in ([0, FRAMES], list(range(FRAMES + 1)))]
+            events = [[e for evs in r[0] for e in evs] + r[2][len(r[0]) - 1] for r in runs]
+            assert events[0] == events[1] and all(np.isfinite(e[0]) for e in events[0])
+            best = runs[1][1][-1]
+            if side == "tgt":
+                assert events[0] == [] and best == (np.inf, watch_ref.NO_MATCH, watch_ref.NO_MATCH)
+                assert np.isnan(delta).all() if np.isnan(value) and frame else np.isposinf(delta).all()
+            elif np.isnan(value):
+                assert np.isnan(delta[frame:]).all() and all(e[2] < frame for e in events[0]) and (len(events[0]) >= 1) == (frame > 0)
+            else:
+                assert np.isposinf(delta[frame]) and np.isfinite(np.delete(delta, frame)).all()
+                assert frame == FRAMES - 1 or any(e[1] > frame for e in events[0])
+                assert same_floats(np.delete(delta, frame)[:frame], delta0[:frame])
