@@ -1,13 +1,16 @@
 """The restatement of WSOLA reconstruction (tests/wsola_ref.py) held to its definition on the CPU: the two consequences
 the contract names (no search = the plain warp; a diagonal map keeps its positions), the tie rule, the source's edges, a
-sample-by-sample reading of the score, and the property the feature exists for -- a sinusoid stays a sinusoid under
-stretching and squeezing maps."""
+sample-by-sample reading of the score, the property the feature exists for -- a sinusoid stays a sinusoid under
+stretching and squeezing maps -- and the inputs the GPU's lag search is held to (tests/wsola_cases.py): every planted
+winner is the restatement's winner, and the odd-sample sources contain the steps they are there for."""
+import collections
 import math
 
 import numpy as np
 import pytest
 
 import warp_ref
+import wsola_cases as wc
 import wsola_ref as ref
 from wsola_ref import BIN, HOP
 
@@ -158,3 +161,70 @@ def test_a_sinusoid_stays_a_sinusoid(freq, kind):
     assert p_wsola >= 0.99
     assert p_plain <= 0.05
     assert all(abs(p - int(m) * HOP) <= 256 for p, m in zip(pos, fmap))
+
+
+# ---- the inputs of tests/test_gpu_wsola_search.py: two statements of every answer, by construction and by the restatement
+
+def _hold(cases, S):
+    for c in cases:
+        assert ref.positions(c.source, c.fmap, S) == c.expected, c.name
+    kinds = collections.Counter(c.kind for c in cases)
+    print("S %d: %d cases %s" % (S, len(cases), dict(kinds)))
+    return kinds
+
+
+@pytest.mark.parametrize("S", wc.PLANT_WIDTHS)
+def test_planted_winners_and_ties_are_the_restatements(S):
+    """Every case of the width, none sampled away (S = 512: 134 cases, 3.5 s)."""
+    L = 2 * S + 1
+    planted_at = set(wc.plant_indices(S))
+    edges = {256 * r + 64 * w + lane for r in range(5) for w in range(4) for lane in (0, 63)}
+    assert planted_at == {i for i in edges | {S, L - 2, L - 1} if i < L}
+    kinds = _hold(wc.plant_cases(S), S)
+    assert kinds["single winner"] == len(planted_at)
+    assert kinds["tie: first against last"] == 1 and kinds["tie: three lags"] >= 1
+    assert kinds["tie: d against -d"] >= 1 or S == 1                            # (S = 1: -1 against +1 is first against last)
+    sets = dict((idx, kind) for kind, idx in wc.tie_sets(S))
+    pairs = [idx for idx in sets if len(idx) == 2]
+    assert (0, L - 1) in pairs and any(a + b == 2 * S and a for a, b in pairs) or S == 1
+    assert any(a // 64 == b // 64 for a, b in pairs)                                            # two lanes of one wave
+    assert any(a // 256 == b // 256 and a // 64 != b // 64 for a, b in pairs) or L <= 64        # two waves, one round
+    assert any(b == a + 256 for a, b in pairs) or L <= 256                                      # one thread, two rounds
+    assert any(a // 256 != b // 256 and (a // 64) % 4 != (b // 64) % 4 for a, b in pairs) or L <= 256
+    assert all(b == a + 256 for a, b in pairs if sets[(a, b)] == "same thread, two rounds")
+    assert all(a // 64 == b // 64 for a, b in pairs if sets[(a, b)] == "two lanes of a wave")
+    assert all(a // 256 == b // 256 and a // 64 != b // 64 for a, b in pairs if sets[(a, b)] == "two waves of a round")
+    assert all(a // 256 != b // 256 and (a // 64) % 4 != (b // 64) % 4 for a, b in pairs
+               if sets[(a, b)] == "another wave and round")
+    if S == 512:                                                                # the pair whose levelling pulse may not sit at lag +S
+        with pytest.raises(ValueError):
+            wc.planted(S, [-512, -511], "no room")
+        assert sum(1 for idx in sets if idx[0] == 0 and idx[-1] != L - 1) >= 5
+
+
+@pytest.mark.parametrize("S", wc.EDGE_WIDTHS)
+def test_planted_edges_and_flat_sources_are_the_restatements(S):
+    kinds = _hold(wc.edge_cases(S) + wc.flat_cases(S), S)
+    for kind in ("lo = -nom", "hi inside the range", "only negative lags, lo", "only negative lags, all tied",
+                 "no admissible lag mid-chain", "template beyond the source", "constant", "silent"):
+        assert kinds[kind] >= 1, kind
+
+
+@pytest.mark.parametrize("S", [s for s in wc.ODD_WIDTHS if s])
+def test_the_odd_sample_sources_contain_the_steps_they_are_for(S):
+    """On the restatement alone, at the seeds the GPU test uses.  Measured: S = 64: 161 searched steps, 28 with every
+    score NaN, 1 with some NaN and a winner off lag 0, 3 with e == 0 on non-zero samples, 27 with e = +inf; S = 512: 14,
+    22, 5, 34; 2 NaN samples of 45 919 at either width."""
+    sounds = wc.odd_call()[0]
+    assert len(sounds) == len(wc.ODD_KINDS) and all(x.size >= 8000 for x in sounds)
+    assert np.isnan(sounds[0]).sum() == 1 and np.isposinf(sounds[1]).sum() == 1 and np.isneginf(sounds[2]).sum() == 1
+    assert np.signbit(sounds[3][sounds[3] == 0.0]).sum() >= 200
+    tiny = np.abs(sounds[4][sounds[4] != 0.0])
+    assert (tiny < np.finfo(np.float64).tiny).sum() >= 200
+    kinds, nans, total = wc.odd_walk(S)
+    print("S %d: %s, %d NaN of %d samples" % (S, dict(kinds), nans, total))
+    for kind in ("every score NaN", "some scores NaN, winner off lag 0", "e == 0 on non-zero samples", "e = +inf"):
+        assert kinds[kind] >= 1, kind
+    assert 2 * nans <= total
+    plain = wc.odd_reference(None)
+    assert 2 * int(np.isnan(plain).sum()) <= plain.size

@@ -26,12 +26,12 @@ def _padded(x, start, count):
     return out
 
 
-def best_lag(x, prev, nom, S):
-    """d* of one step: prev = pos[j-1], nom = map[j] * HOP."""
+def lag_scores(x, prev, nom, S):
+    """(lo, c, e, score) of one step's admissible lags lo, lo + 1, ...; None when no lag is admissible."""
     s_len = int(x.size)
     lo, hi = max(-S, -nom), min(S, s_len - 1 - nom)
     if lo > hi:
-        return 0
+        return None
     tmpl = _padded(x, prev + HOP, BIN)
     span = _padded(x, nom + lo, hi - lo + BIN)
     cand = np.lib.stride_tricks.sliding_window_view(span, BIN)            # [lag, n] = x[nom + lo + lag + n]
@@ -40,6 +40,19 @@ def best_lag(x, prev, nom, S):
         c = np.cumsum(np.concatenate([zero, tmpl[None, :] * cand], axis=1), axis=1)[:, -1]
         e = np.cumsum(np.concatenate([zero, cand * cand], axis=1), axis=1)[:, -1]
         score = np.where(e == 0.0, 0.0, c / np.sqrt(e))
+    return lo, c, e, score
+
+
+def best_lag(x, prev, nom, S):
+    """d* of one step: prev = pos[j-1], nom = map[j] * HOP."""
+    return pick(lag_scores(x, prev, nom, S))
+
+
+def pick(scored):
+    """d* from lag_scores' result."""
+    if scored is None:
+        return 0
+    lo, _, _, score = scored
     best, best_score = None, 0.0
     for i, sc in enumerate(score.tolist()):
         d = lo + i
