@@ -1158,6 +1158,9 @@ int32_t launch_dtw_exact(ssym_ctx *ctx, const SegmentSet &src, const SegmentSet 
     }
     const bool ldsFrames = boundBytes + frameBytes <= 64 * 1024;
     const size_t lds = boundBytes + (ldsFrames ? frameBytes : 0);
+    if (lds > 64 * 1024)        // boundary rows of targets past 4096 frames (the frames are then in global memory)
+        SSYM_HIP_CHECK(ctx, hipFuncSetAttribute((const void *)dtw_exact_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                                (int)lds));
     if (ldsFrames)
         dtw_exact_kernel<true><<<grid, 64, lds, st>>>(src.raw, src.off, tgt.raw, tgt.off, src.n, tgt.n,
                                                      dim, ctx->band, ctx->squared, pairs, count_dev,
