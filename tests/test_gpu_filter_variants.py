@@ -5,9 +5,9 @@ re-score only sees the survivors: a filter value outside its bound, or a (target
 never runs -- the cost matrix is reused scratch, such a pair keeps the previous call's value -- changes an answer with
 no error reported.  Each case below is shaped so that its launches take one particular variant of the short-source
 kernels (dtw_filter_sp_kernel.hpp: multi-pair tasks with KU = 2 or 3 operand planes, single-pair tasks of one to three
-tiles, several pair blocks, few target groups) or the generic kernel beside them, and the launch plan is restated here
-(filter_plan) from the segment lengths, the dim and the device's CU count: the timings' launch and cell counts prove that
-the case ran the variant it names and that the A/B comparisons below compare two different kernels.
+tiles, several pair blocks, few target groups) or the generic kernel beside them, and the launch plan is restated
+(tests/filter_plan.py) from the segment lengths, the dim and the device's CU count: the timings' launch and cell counts
+prove that the case ran the variant it names and that the A/B comparisons below compare two different kernels.
 
 Per case: the whole filter matrix within the per-pair bound of tests/bounds.py after the scratch has been filled with
 another search of the same shape, the exact matrix and the argmin of every target against the oracle, and the same bits
@@ -25,97 +25,12 @@ import pytest
 from soundsym_amd import Engine, synth
 from soundsym_amd.engine import pack_segments
 from bounds import pair_bound_matrix
+from filter_plan import Launch, _cells, filter_ku, filter_plan, plan_cells      # noqa: F401 (the launch plan, restated)
 
 pytestmark = pytest.mark.gpu
 EXACT_RTOL = 1e-12
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
-
-
-# ---- the launch plan, restated (csrc/dtw_filter.hip launch_dtw_filter / launch_one / launch_cells) ---------------------
-REC_HALFS = 48          # kFilterRecHalfs
-WAVES_PER_BLOCK = 4     # kFilterWavesPerBlock
-ROW_BLOCK = 4           # kSpRowBlock
-RING = 4                # kSpRing
-
-Launch = namedtuple("Launch", "nt kernel lo hi blocks cells")      # kernel: "mp", "sp" or "generic"
-
-
-def _ceil(a, b):
-    return -(-a // b)
-
-
-def filter_ku(dim):
-    """Operand planes the unbanded filter multiplies (ssym_internal.hpp filter_pieces / filter_mfmas): up to 13 values
-    record layout 3 (two planes), 14...26 layout 1 in two planes, 27...42 layout 1 in three."""
-    du = min(dim, 42)
-    return 2 if du <= 26 else 3
-
-
-def _cells(pair_len, col_len, lo, hi, origin, rows_pad, pass_rows, row_block, min_cols, per_task=1):
-    """launch_cells for single-pass launches: rows of the pairs [lo, hi) times the columns of every target group."""
-    cols = sum(max(c, min_cols) if row_block else c for c in col_len)
-    rows = 0
-    for sp in range(lo, hi):
-        longer = pair_len[sp]
-        if per_task > 1:                 # every pair of a task starts at the task's first row block
-            first = lo + (sp - lo) // per_task * per_task
-            longer = max(pair_len[first:min(first + per_task, hi)])
-        r0min = rows_pad - longer
-        if row_block:
-            rows += pass_rows - min(max(r0min - origin, 0), 15) // row_block * row_block
-        else:
-            rows += pass_rows            # one pass: its first pass is the only one
-    return rows * cols
-
-
-def filter_plan(src_lens, tgt_lens, dim, num_cus, sp=True, mp=True, pair_blocks=True):
-    """The launches of one unbanded, unpruned filter call over sources of at most 48 frames: per class of source pairs
-    (cut where the longer member of a pair needs more than 16, 32 frames) its tile count, kernel, pair range, pair blocks
-    of the sp kernels' task order and DP cells per lane (n_filter_cells is 64 times their sum).  sp / mp / pair_blocks
-    False: the plan under SSYM_FILTER_SP=0, SSYM_SP_MULTIPAIR=0, SSYM_SP_PAIRBLOCK=0."""
-    ls = sorted(int(x) for x in src_lens)           # record slots are ordered by length
-    lt = sorted(int(x) for x in tgt_lens)
-    n, m = len(ls), len(lt)
-    n_pad, m_pad = _ceil(n, 32) * 32, _ceil(m, 32) * 32
-    ls += [0] * (n_pad - n)
-    lt += [0] * (m_pad - m)
-    top = max(max(ls), 1)
-    assert top <= 48, "single-pass sets only"
-    top_tiles = _ceil(top, 16)
-    rows_pad = 16 * top_tiles
-    n_pairs, n_real = n_pad // 2, (n + 1) // 2
-    pair_len = [max(ls[2 * p], ls[2 * p + 1]) for p in range(n_pairs)]
-    col_len = [max(lt[32 * g:32 * g + 32]) for g in range(m_pad // 32)]
-    n_groups = len(col_len)
-    bound = [0] + [next((p for p in range(n_real) if pair_len[p] > 16 * c), n_real) for c in range(1, top_tiles)]
-    ku = filter_ku(dim)
-    grid_blocks = max(8, num_cus * 2 // 8 * 8)
-    plan = []
-    for c in range(top_tiles):
-        nt, lo = c + 1, bound[c]
-        hi = bound[c + 1] if c + 1 < top_tiles else n_pairs
-        if hi <= lo:
-            continue
-        origin, np_ = rows_pad - 16 * nt, hi - lo
-        mpn = 3 if ku == 2 else 2
-        if nt == 1 and sp and mp and _ceil(np_, mpn) * n_groups >= grid_blocks // 2 * 2 * WAVES_PER_BLOCK:
-            task_pairs = _ceil(np_, mpn)
-            pb = max(16, (1 << 20) // (mpn * 2 * 16 * REC_HALFS * 2)) if pair_blocks else task_pairs
-            plan.append(Launch(nt, "mp", lo, hi, _ceil(task_pairs, min(pb, task_pairs)),
-                               _cells(pair_len, col_len, lo, hi, origin, rows_pad, 16, ROW_BLOCK, RING, mpn)))
-        elif sp and (ku == 2 or nt <= 2):
-            pb = max(16, (1 << 20) // (2 * 16 * nt * REC_HALFS * 2)) if pair_blocks else np_
-            plan.append(Launch(nt, "sp", lo, hi, _ceil(np_, min(pb, np_)),
-                               _cells(pair_len, col_len, lo, hi, origin, rows_pad, 16 * nt, ROW_BLOCK, RING)))
-        else:
-            plan.append(Launch(nt, "generic", lo, hi, 0,
-                               _cells(pair_len, col_len, lo, hi, origin, rows_pad, 16 * nt, 0, 0)))
-    return plan, n_groups
-
-
-def plan_cells(plan):
-    return 64 * sum(x.cells for x in plan)
 
 
 # ---- the cases -------------------------------------------------------------------------------------------------------
