@@ -37,6 +37,8 @@ pub const SSYM_OUT_DEVICE: u32 = 1;
 pub const SSYM_WARP_MAP_DEVICE: u32 = 32;
 pub const SSYM_DTW_FORCE_EXACT: u32 = 2;
 pub const SSYM_DTW_PRUNE: u32 = 4;
+pub const SSYM_STEP_SYMMETRIC: u32 = 0;  // the recurrence of ssym_dtw_spot: the _step calls are then the plain ones
+pub const SSYM_STEP_PACED: u32 = 1;      // one source frame per target frame, at most one skipped or repeated in a row
 pub const SSYM_MFCC_PAD_TAIL: u32 = 4;
 pub const SSYM_TOPK_MAX: u32 = 64;
 pub const SSYM_GMM_STANDARDIZE: u32 = 8;
@@ -138,6 +140,18 @@ extern "C" {
                              tgt_idx: *const u32, n_pairs: u32, index_base: u32, max_spots: u32, max_cost: *const f64,
                              out_count: *mut u32, out_cost: *mut f64, out_start: *mut u32, out_end: *mut u32,
                              flags: u32) -> i32;
+    // the three calls above with a step pattern: SSYM_STEP_PACED bounds the slope (spans of about Fb / 2 to 2 Fb - 1 frames)
+    // and makes cost / Fb a mean per-frame distance; targets of at most 2048 frames; costs and max_cost stay sums
+    pub fn ssym_dtw_spot_step(ctx: *mut SsymCtx, dict: *const SsymDict, q: *const SsymQueries, src_idx: *const u32,
+                              tgt_idx: *const u32, n_pairs: u32, index_base: u32, step: u32, out_cost: *mut f64,
+                              out_start: *mut u32, out_end: *mut u32, flags: u32) -> i32;
+    pub fn ssym_spot_queries_step(ctx: *mut SsymCtx, dict: *const SsymDict, q: *const SsymQueries, index_base: u32,
+                                  step: u32, out_idx: *mut u32, out_cost: *mut f64, out_start: *mut u32,
+                                  out_end: *mut u32, flags: u32) -> i32;
+    pub fn ssym_dtw_spot_all_step(ctx: *mut SsymCtx, dict: *const SsymDict, q: *const SsymQueries, src_idx: *const u32,
+                                  tgt_idx: *const u32, n_pairs: u32, index_base: u32, step: u32, max_spots: u32,
+                                  max_cost: *const f64, out_count: *mut u32, out_cost: *mut f64, out_start: *mut u32,
+                                  out_end: *mut u32, flags: u32) -> i32;
 
     // source-sharded runs, exchange done by the caller (device pointers): filter / all-reduce(MIN) / finish / merge
     pub fn ssym_match_begin(ctx: *mut SsymCtx, dict: *const SsymDict, q: *const SsymQueries, distance: *const f64,

@@ -345,7 +345,10 @@ class SoundDictionary {
         double cost;
         bool empty() const { return end_frame == SSYM_NO_MATCH; }
     };
-    std::vector<Spot> spot(const std::vector<ArcSound> &targets, const std::vector<uint32_t> *indices = nullptr) const
+    // step: SSYM_STEP_SYMMETRIC (the calls above) or SSYM_STEP_PACED (soundsym_amd.h "Paced spotting": spans of about half
+    // to twice the target's frames, and cost / the target's frames a mean per-frame distance)
+    std::vector<Spot> spot(const std::vector<ArcSound> &targets, const std::vector<uint32_t> *indices = nullptr,
+                           uint32_t step = SSYM_STEP_SYMMETRIC) const
     {
         if (sounds.empty())
             throw EmptyDictionary();
@@ -360,11 +363,17 @@ class SoundDictionary {
         int32_t rc;
         if (indices) {
             idx = *indices;
-            rc = idx.size() == n ? ssym_dtw_spot(ctx_->get(), resident(), q, idx.data(), nullptr, n, 0, cost.data(),
-                                                 start.data(), end.data(), 0)
-                                 : (int32_t)SSYM_E_INVALID;
+            rc = idx.size() != n ? (int32_t)SSYM_E_INVALID
+                 : step == SSYM_STEP_SYMMETRIC
+                     ? ssym_dtw_spot(ctx_->get(), resident(), q, idx.data(), nullptr, n, 0, cost.data(), start.data(),
+                                     end.data(), 0)
+                     : ssym_dtw_spot_step(ctx_->get(), resident(), q, idx.data(), nullptr, n, 0, step, cost.data(),
+                                          start.data(), end.data(), 0);
         } else {
-            rc = ssym_spot_queries(ctx_->get(), resident(), q, 0, idx.data(), cost.data(), start.data(), end.data(), 0);
+            rc = step == SSYM_STEP_SYMMETRIC
+                     ? ssym_spot_queries(ctx_->get(), resident(), q, 0, idx.data(), cost.data(), start.data(), end.data(), 0)
+                     : ssym_spot_queries_step(ctx_->get(), resident(), q, 0, step, idx.data(), cost.data(), start.data(),
+                                              end.data(), 0);
         }
         ssym_queries_destroy(ctx_->get(), q);
         ctx_->check(rc);
@@ -377,9 +386,10 @@ class SoundDictionary {
     // every place a target sounds: per target its occurrences by ascending cost, pairwise disjoint within a recording
     // (ssym_dtw_spot_all, one call).  With indices, target t is searched in sounds[indices[t]]; without, in every sound:
     // max_spots (1 ... 64) then applies per sound and a target's list is merged by (cost, source index, end).  max_cost:
-    // an occurrence costs at most that (NULL: no threshold)
+    // an occurrence costs at most that (NULL: no threshold).  step as for spot (ssym_dtw_spot_all_step); max_cost stays a sum
     std::vector<std::vector<Spot>> spot_all(const std::vector<ArcSound> &targets, const std::vector<uint32_t> *indices = nullptr,
-                                            uint32_t max_spots = 8, const double *max_cost = nullptr) const
+                                            uint32_t max_spots = 8, const double *max_cost = nullptr,
+                                            uint32_t step = SSYM_STEP_SYMMETRIC) const
     {
         if (sounds.empty())
             throw EmptyDictionary();
@@ -407,10 +417,14 @@ class SoundDictionary {
         ctx_->check(ssym_queries_create(ctx_->get(), flat.data(), off.data(), m, (uint32_t)NCOEFFS, &q));
         std::vector<uint32_t> count(np), start(np * K), end(np * K);
         std::vector<double> cost(np * K), limit(max_cost ? np : 0, max_cost ? *max_cost : 0.0);
-        const int32_t rc = src.size() == np ? ssym_dtw_spot_all(ctx_->get(), resident(), q, src.data(), tgt.data(), (uint32_t)np,
-                                                                0, max_spots, max_cost ? limit.data() : nullptr, count.data(),
-                                                                cost.data(), start.data(), end.data(), 0)
-                                            : (int32_t)SSYM_E_INVALID;
+        const int32_t rc =
+            src.size() != np ? (int32_t)SSYM_E_INVALID
+            : step == SSYM_STEP_SYMMETRIC
+                ? ssym_dtw_spot_all(ctx_->get(), resident(), q, src.data(), tgt.data(), (uint32_t)np, 0, max_spots,
+                                    max_cost ? limit.data() : nullptr, count.data(), cost.data(), start.data(), end.data(), 0)
+                : ssym_dtw_spot_all_step(ctx_->get(), resident(), q, src.data(), tgt.data(), (uint32_t)np, 0, step, max_spots,
+                                         max_cost ? limit.data() : nullptr, count.data(), cost.data(), start.data(),
+                                         end.data(), 0);
         ssym_queries_destroy(ctx_->get(), q);
         ctx_->check(rc);
         for (size_t p = 0; p < np; ++p)

@@ -366,6 +366,52 @@ SSYM_API int32_t ssym_dtw_spot_all(ssym_ctx *ctx, const ssym_dict *dict, const s
                                    const double *max_cost, uint32_t *out_count, double *out_cost, uint32_t *out_start,
                                    uint32_t *out_end, uint32_t flags);
 
+/* Paced spotting (DESIGN.md section 2 "Paced spotting" and section 5.18): the three calls above with a step pattern.
+ * SSYM_STEP_SYMMETRIC is the recurrence of ssym_dtw_spot: the _step calls are then the calls above, bit for bit.
+ * SSYM_STEP_PACED is the asymmetric pattern with Itakura's rule: every target frame takes exactly one source frame; a
+ * source frame may be skipped, but never two in a row; a source frame may be repeated, but never twice in a row.  Every
+ * admissible path has exactly Fb cells, so cost / Fb is a mean per-frame distance that compares across targets of
+ * different lengths, and every span has between floor((Fb-1)/2) + 1 and 2 Fb - 1 frames.  c, the squared option and the
+ * arithmetic are those of ssym_dtw_spot (f64, k ascending, every operation rounded separately).  Every cell has two
+ * states, N (entered by a source step) and H (entered by repeating the source frame):
+ *   N(i,0) = c(i,0), sN(i,0) = i;   H(i,0) = +inf (no start)
+ *   E(i,j) = the cell's better state: (N, sN); if H(i,j) < N(i,j): (H, sH)        (strict <: a tie keeps N)
+ *   j >= 1:
+ *     P      = E(i-1,j-1); if E(i-2,j-1) < P: E(i-2,j-1)   (strict <: a tie keeps the diagonal; outside the matrix +inf)
+ *     N(i,j) = c(i,j) + P.value,      sN(i,j) = P.start
+ *     H(i,j) = c(i,j) + N(i,j-1),     sH(i,j) = sN(i,j-1)  (a repeat may only follow a source step)
+ *   delta(i) = E(i,Fb-1).value,  s(i) = E(i,Fb-1).start    (the end-column profile)
+ *   end  = the smallest i at which delta(i) is least (i ascending from (none, +inf), strict <: NaN and +inf never win)
+ *   cost = delta(end),  start = s(end);  no spot (Fa = 0, Fb = 0, SSYM_NO_MATCH, no finite delta): (+inf, SSYM_NO_MATCH,
+ *   SSYM_NO_MATCH)
+ * So cost is the least sum of c over all admissible paths of every start and end, summed in path order (acc = c + acc),
+ * and end the first end that reaches it.  A target equal to every second frame of a stretch of the source costs exactly
+ * 0.0 with a span of 2 Fb - 1 frames; one equal to a stretch with each frame doubled costs 0.0 with a span of Fb / 2
+ * frames; the same stretch with each frame tripled costs more than 0, where ssym_dtw_spot gives 0.0.  Features that are
+ * not finite: the strict < comparisons above decide; a span with a NaN or +inf cost is never reported and no read
+ * leaves its buffer.  Occurrences under the paced pattern (ssym_dtw_spot_all_step) use this delta and s; candidates,
+ * picks, kills, the stop, max_cost, the count and the padding are those of "Occurrences" above, word for word.
+ * Costs stay unnormalised sums, and max_cost is a sum: the caller forms per-frame values (cost / Fb, max_cost = x * Fb).
+ * Pair lists, SSYM_NO_MATCH, tgt_idx == NULL, flags, the error codes, outputs unwritten on refusal, n_pairs = 0 and the
+ * timings are those of the three calls above.  An unknown step: SSYM_E_INVALID.
+ * Limits with SSYM_STEP_PACED: targets of at most 2048 frames (two hand-off rows take 24 bytes of LDS per target frame),
+ * dim <= 64, sources as long as a dictionary segment; ssym_dtw_spot_all_step keeps the 2^24 source frames and the
+ * 512 MiB of scratch of ssym_dtw_spot_all.  A longer target, a refcos context, a context with a band:
+ * SSYM_E_UNSUPPORTED before any device work. */
+#define SSYM_STEP_SYMMETRIC 0u
+#define SSYM_STEP_PACED 1u
+SSYM_API int32_t ssym_dtw_spot_step(ssym_ctx *ctx, const ssym_dict *dict, const ssym_queries *q, const uint32_t *src_idx,
+                                    const uint32_t *tgt_idx, uint32_t n_pairs, uint32_t index_base, uint32_t step,
+                                    double *out_cost, uint32_t *out_start, uint32_t *out_end, uint32_t flags);
+SSYM_API int32_t ssym_spot_queries_step(ssym_ctx *ctx, const ssym_dict *dict, const ssym_queries *q, uint32_t index_base,
+                                        uint32_t step, uint32_t *out_idx, double *out_cost, uint32_t *out_start,
+                                        uint32_t *out_end, uint32_t flags);
+SSYM_API int32_t ssym_dtw_spot_all_step(ssym_ctx *ctx, const ssym_dict *dict, const ssym_queries *q,
+                                        const uint32_t *src_idx, const uint32_t *tgt_idx, uint32_t n_pairs,
+                                        uint32_t index_base, uint32_t step, uint32_t max_spots, const double *max_cost,
+                                        uint32_t *out_count, double *out_cost, uint32_t *out_start, uint32_t *out_end,
+                                        uint32_t flags);
+
 /* Source-sharded multi-GPU, dtw metric: the one real exchange the path has.  Each rank's filter gives,
  * per target, an upper bound on the best key in ITS shard; a rank whose shard does not hold a
  * target's neighbour would otherwise re-score ~10^2 of its own pairs per target for nothing.

@@ -34,6 +34,7 @@ OUT_DEVICE = 1
 DTW_FORCE_EXACT = 2
 DTW_PRUNE = 4
 WARP_MAP_DEVICE = 32       # SSYM_WARP_MAP_DEVICE
+STEP_SYMMETRIC, STEP_PACED = 0, 1       # SSYM_STEP_SYMMETRIC, SSYM_STEP_PACED
 
 # every symbol include/soundsym_amd.h declares (tests check the library exports all of them)
 ABI_SYMBOLS = [
@@ -59,6 +60,7 @@ ABI_SYMBOLS = [
     "ssym_spotter_flush", "ssym_spotter_best", "ssym_spotter_counts", "ssym_spotter_reset",
     "ssym_dtw_align_sizes", "ssym_dtw_align",
     "ssym_dtw_spot", "ssym_spot_queries", "ssym_dtw_spot_all",
+    "ssym_dtw_spot_step", "ssym_spot_queries_step", "ssym_dtw_spot_all_step",
     "ssym_reconstruct_warped", "ssym_reconstruct_wsola",
 ]
 COMM_ID_BYTES = 128        # SSYM_COMM_ID_BYTES
@@ -255,6 +257,12 @@ def lib() -> ctypes.CDLL:
     L.ssym_spot_queries.argtypes = [vp, vp, vp, u32, vp, vp, vp, vp, u32]
     L.ssym_dtw_spot_all.restype = i32
     L.ssym_dtw_spot_all.argtypes = [vp, vp, vp, vp, vp, u32, u32, u32, vp, vp, vp, vp, vp, u32]
+    L.ssym_dtw_spot_step.restype = i32
+    L.ssym_dtw_spot_step.argtypes = [vp, vp, vp, vp, vp, u32, u32, u32, vp, vp, vp, u32]
+    L.ssym_spot_queries_step.restype = i32
+    L.ssym_spot_queries_step.argtypes = [vp, vp, vp, u32, u32, vp, vp, vp, vp, u32]
+    L.ssym_dtw_spot_all_step.restype = i32
+    L.ssym_dtw_spot_all_step.argtypes = [vp, vp, vp, vp, vp, u32, u32, u32, u32, vp, vp, vp, vp, vp, u32]
     L.ssym_pair_matrix.restype = i32
     L.ssym_pair_matrix.argtypes = [vp, vp, vp, i32, vp]
     L.ssym_merge_shards.restype = i32

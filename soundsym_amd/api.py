@@ -347,18 +347,38 @@ class Alignment:
         return "Alignment(source_index=%d, cost=%r, cells=%d)" % (self.source_index, self.cost, len(self))
 
 
+def _spot_step(step):
+    if step not in ("symmetric", "paced"):
+        raise ValueError('step must be "symmetric" or "paced"')
+
+
+def _step_kw(step, max_cost_per_frame=None):
+    """The keywords a call passes on for `step`: none at all for the default, so that "symmetric" is the call as it was."""
+    kw = {} if step == "symmetric" else {"step": step}
+    if max_cost_per_frame is not None:
+        kw["max_cost_per_frame"] = max_cost_per_frame
+    return kw
+
+
+def _per_frame(step, cost, frames):
+    return float(cost) / float(frames) if step == "paced" else None
+
+
 class Spot:
     """Where inside a dictionary recording a target sounds (ssym_dtw_spot / ssym_spot_queries; definition in
     include/soundsym_amd.h and DESIGN.md section 2 "Spotting"): `source_index` into the dictionary's sounds, the frames
     `start_frame` ... `end_frame` (INCLUSIVE) of that recording, and `cost`, the DTW cost of (those frames, the target),
     not normalised by any length.  A target without a spot (an empty sound, an empty recording) gives an empty Spot:
-    falsy, no frames, cost +inf."""
+    falsy, no frames, cost +inf.  A spot of the paced step pattern (step="paced"; "Paced spotting") also has
+    `cost_per_frame`, cost / the target's frames: every paced path has one cell per target frame, so this mean compares
+    across targets of different lengths.  It is None for every other spot."""
 
-    __slots__ = ("source_index", "start_frame", "end_frame", "cost")
+    __slots__ = ("source_index", "start_frame", "end_frame", "cost", "cost_per_frame")
 
-    def __init__(self, source_index: int, start_frame: int, end_frame: int, cost: float):
+    def __init__(self, source_index: int, start_frame: int, end_frame: int, cost: float, cost_per_frame=None):
         self.source_index, self.start_frame, self.end_frame = int(source_index), int(start_frame), int(end_frame)
         self.cost = float(cost)
+        self.cost_per_frame = None if cost_per_frame is None else float(cost_per_frame)
         if not self.empty() and not 0 <= self.start_frame <= self.end_frame:
             raise ValueError("a spot spans start_frame ... end_frame with 0 <= start_frame <= end_frame")
 
@@ -679,11 +699,14 @@ class SoundDictionary:
         finally:
             q.close()
 
-    def spot(self, targets: Sequence[Sound], indices=None) -> List["Spot"]:
+    def spot(self, targets: Sequence[Sound], indices=None, step: str = "symmetric") -> List["Spot"]:
         """Where inside the dictionary's (unsegmented) recordings every target sounds: subsequence DTW on the GPU (dtw
         engines without a band).  indices=None: every recording is tried for every target and the best one kept, the
         lower index on a tie -- one ssym_spot_queries call; otherwise indices[t] names the recording target t is
-        spotted in (ssym_dtw_spot).  A target without a spot gives an empty Spot."""
+        spotted in (ssym_dtw_spot).  A target without a spot gives an empty Spot.  step="paced": the paced step pattern
+        (the _step calls with SSYM_STEP_PACED): spans of about half to twice the target's frames, and Spot.cost_per_frame
+        set."""
+        _spot_step(step)
         if not self.sounds:
             raise EmptyDictionaryError(-2, "empty dictionary")
         if getattr(self.engine, "metric", None) != "dtw":
@@ -701,21 +724,32 @@ class SoundDictionary:
         q = self.engine.queries(flat, off, self._dim())
         try:
             if indices is None:
-                indices, cost, start, end = self.engine.spot_queries(self.resident(), q)
+                indices, cost, start, end = self.engine.spot_queries(self.resident(), q, **_step_kw(step))
             else:
-                cost, start, end = self.engine.dtw_spot(self.resident(), q, indices)
+                cost, start, end = self.engine.dtw_spot(self.resident(), q, indices, **_step_kw(step))
         finally:
             q.close()
-        return [Spot(int(indices[t]), int(start[t]), int(end[t]), cost[t]) if int(end[t]) != NO_MATCH else Spot.none()
-                for t in range(len(targets))]
+        frames = np.diff(off.astype(np.int64))
+        return [Spot(int(indices[t]), int(start[t]), int(end[t]), cost[t], _per_frame(step, cost[t], frames[t]))
+                if int(end[t]) != NO_MATCH else Spot.none() for t in range(len(targets))]
 
-    def spot_all(self, targets: Sequence[Sound], indices=None, max_spots: int = 8, max_cost=None) -> List[List["Spot"]]:
+    def spot_all(self, targets: Sequence[Sound], indices=None, max_spots: int = 8, max_cost=None, step: str = "symmetric",
+                 max_cost_per_frame=None) -> List[List["Spot"]]:
         """Every place a target sounds inside the dictionary's recordings: per target its occurrences by ascending cost,
         pairwise disjoint within a recording (ssym_dtw_spot_all, one call; dtw engines without a band).  With indices,
         target t is searched in recording indices[t] and max_cost is a scalar or one value per target; without, in every
         recording -- max_spots then applies per recording, max_cost is a scalar, and a target's list is merged by
         (cost, source index, end).  An occurrence costs at most max_cost; the cost is not normalised by any length, so
-        without max_cost the list goes on with spans the target merely fits least badly."""
+        without max_cost the list goes on with spans the target merely fits least badly.  step="paced": the paced step
+        pattern (ssym_dtw_spot_all_step with SSYM_STEP_PACED), Spot.cost_per_frame set, and max_cost_per_frame (instead
+        of max_cost; a scalar, or with indices one value per target) is a threshold on that mean: target t's occurrences
+        cost at most max_cost_per_frame * its frames, so one value serves targets of every length."""
+        _spot_step(step)
+        if max_cost_per_frame is not None:
+            if max_cost is not None:
+                raise ValueError("max_cost and max_cost_per_frame exclude each other")
+            if step != "paced":
+                raise ValueError('max_cost_per_frame needs step="paced": only there is cost / frames a mean per-frame distance')
         if not self.sounds:
             raise EmptyDictionaryError(-2, "empty dictionary")
         if getattr(self.engine, "metric", None) != "dtw":
@@ -730,6 +764,12 @@ class SoundDictionary:
                 raise ValueError("max_cost must be a scalar, or with indices one value per target")
             if np.isnan(max_cost).any():
                 raise ValueError("max_cost must not be NaN")
+        if max_cost_per_frame is not None:
+            max_cost_per_frame = np.asarray(max_cost_per_frame, dtype=np.float64)
+            if max_cost_per_frame.ndim and (indices is None or max_cost_per_frame.size != m):
+                raise ValueError("max_cost_per_frame must be a scalar, or with indices one value per target")
+            if np.isnan(max_cost_per_frame).any():
+                raise ValueError("max_cost_per_frame must not be NaN")
         if indices is not None:
             indices = np.asarray(indices, dtype=np.int64).reshape(-1)
             if indices.size != m:
@@ -743,15 +783,20 @@ class SoundDictionary:
         else:
             src, tgt = indices, np.arange(m)
         flat, off = pack_segments([t.mfccs() for t in targets], self._dim(), self.engine.np_dtype)
+        frames = np.diff(off.astype(np.int64))
+        if max_cost_per_frame is not None:
+            # a sum per pair, in f64 on the host: max_cost[p] = x * Fb[p]
+            max_cost = np.broadcast_to(max_cost_per_frame.reshape(-1), (m,))[tgt] * frames[tgt].astype(np.float64)
         q = self.engine.queries(flat, off, self._dim())
         try:
             count, cost, start, end = self.engine.dtw_spot_all(self.resident(), q, src, tgt, max_spots=int(max_spots),
-                                                               max_cost=max_cost)
+                                                               max_cost=max_cost, **_step_kw(step))
         finally:
             q.close()
         out: List[List[Spot]] = [[] for _ in range(m)]
         for p in range(src.size):
-            out[int(tgt[p])] += [Spot(int(src[p]), int(start[p, k]), int(end[p, k]), cost[p, k]) for k in range(int(count[p]))]
+            out[int(tgt[p])] += [Spot(int(src[p]), int(start[p, k]), int(end[p, k]), cost[p, k],
+                                      _per_frame(step, cost[p, k], frames[int(tgt[p])])) for k in range(int(count[p]))]
         for spots in out:
             spots.sort(key=lambda sp: (sp.cost, sp.source_index, sp.end_frame))
         return out
@@ -897,17 +942,18 @@ class SoundSequence:
             return []
         return dict_.align(self._sounds)
 
-    def spot_in_dictionary(self, dict_: SoundDictionary) -> List[Spot]:
+    def spot_in_dictionary(self, dict_: SoundDictionary, step: str = "symmetric") -> List[Spot]:
         """Every sound of the sequence located inside dict_'s recordings (SoundDictionary.spot)."""
         if not self._sounds:
             return []
-        return dict_.spot(self._sounds)
+        return dict_.spot(self._sounds, **_step_kw(step))
 
-    def spot_all_in_dictionary(self, dict_: SoundDictionary, max_spots: int = 8, max_cost=None) -> List[List[Spot]]:
+    def spot_all_in_dictionary(self, dict_: SoundDictionary, max_spots: int = 8, max_cost=None, step: str = "symmetric",
+                               max_cost_per_frame=None) -> List[List[Spot]]:
         """Every occurrence of every sound of the sequence inside dict_'s recordings (SoundDictionary.spot_all)."""
         if not self._sounds:
             return []
-        return dict_.spot_all(self._sounds, max_spots=max_spots, max_cost=max_cost)
+        return dict_.spot_all(self._sounds, max_spots=max_spots, max_cost=max_cost, **_step_kw(step, max_cost_per_frame))
 
     def reconstruct_from_dictionary(self, dict_: "SoundDictionary", want_pcm32: bool = False):
         """clone_from_dictionary(dict).to_sound().samples() in one go (src/sound.rs:451-480): match

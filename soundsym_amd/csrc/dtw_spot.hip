@@ -34,6 +34,9 @@ namespace ssym {
 // A source has as many frames as a dictionary segment can (2^31 - 1).
 constexpr int kSpotMaxTargetFrames = 4096;
 constexpr int kSpotMaxDim = 64;
+// Limit of the paced step pattern (the _step entry points with SSYM_STEP_PACED): two hand-off rows take 24 bytes per target
+// frame, and with the ring (66 KiB at DIMR = 64) 4096 frames would need 162 KiB of the 160 KiB of LDS
+constexpr int kPacedMaxTargetFrames = 2048;
 // Limits of ssym_dtw_spot_all: occurrences per pair, and frames of a listed source -- the profile lives in global scratch
 // at 12 bytes per source frame, 192 MiB for one pair at this length.  The scratch of a call stays within
 // kSpotAllScratchBytes: one slot per workgroup, fewer workgroups for longer sources.
@@ -83,6 +86,47 @@ __device__ __forceinline__ void spot_all_pad(const SpotAllArgs &a, uint32_t k, u
         a.end[o] = 0xffffffffu;
     }
 }
+
+// the selection passes of the occurrences, after the end reduction has left the first least end of the
+// profile in (bestD, bestEnd, bestSt): write the pick, kill every end whose span [st(i), i] shares a frame with it, find the
+// first least survivor, until K picks are made or no candidate is left (the least survivor is a candidate or nothing is:
+// bestEnd names a row, so bestD is finite), then the count and the padding.  One text for dtw_spot_kernel and
+// dtw_paced_kernel, as a macro for the reason SSYM_SPOT_FIRST_MIN gives (INF: the kernel's own constant)
+#define SSYM_SPOT_SELECT(a, k, Fa, lane, bestD, bestEnd, bestSt)                                                          \
+    {                                                                                                                     \
+        double *pD = a.profD + (size_t)blockIdx.x * a.slotFrames;                                                         \
+        uint32_t *pS = a.profS + (size_t)blockIdx.x * a.slotFrames;                                                       \
+        const double maxCost = a.maxCost ? a.maxCost[k] : INF;                                                            \
+        const size_t o = (size_t)k * a.maxSpots;                                                                          \
+        uint32_t cnt = 0;                                                                                                 \
+        __threadfence_block();                                                                                            \
+        while (bestEnd != 0xffffffffu && bestD <= maxCost) {                                                              \
+            if (lane == 0) {                                                                                              \
+                a.cost[o + cnt] = bestD;                                                                                  \
+                a.start[o + cnt] = bestSt;                                                                                \
+                a.end[o + cnt] = bestEnd;                                                                                 \
+            }                                                                                                             \
+            if (++cnt == a.maxSpots)                                                                                      \
+                break;                                                                                                    \
+            const uint32_t pickS = bestSt, pickE = bestEnd;                                                               \
+            bestD = INF;                                                                                                  \
+            bestEnd = bestSt = 0xffffffffu;                                                                               \
+            _Pragma("unroll 4")                                                                                           \
+            for (uint32_t i = (uint32_t)lane; i < Fa; i += 64) {                                                          \
+                const double d = pD[i];                                                                                   \
+                const uint32_t s = pS[i];                                                                                 \
+                if (s <= pickE && i >= pickS) {                                                                           \
+                    pD[i] = INF;                                                                                          \
+                } else if (d < bestD) {                                                                                   \
+                    bestD = d;                                                                                            \
+                    bestEnd = i;                                                                                          \
+                    bestSt = s;                                                                                           \
+                }                                                                                                         \
+            }                                                                                                             \
+            SSYM_SPOT_FIRST_MIN(bestD, bestEnd, bestSt)                                                                   \
+        }                                                                                                                 \
+        spot_all_pad(a, k, cnt);                                                                                          \
+    }
 
 // ALL (ssym_dtw_spot_all, Args = SpotAllArgs): keep the end column and pick up to a.maxSpots disjoint spans from it
 template <int DIMR, bool ALL = false, class Args = SpotArgs>
@@ -196,40 +240,163 @@ __global__ __launch_bounds__(64) void dtw_spot_kernel(const Args a)
         // the first minimum of the end column
         SSYM_SPOT_FIRST_MIN(bestD, bestEnd, bestSt)
         if constexpr (ALL) {
-            double *pD = a.profD + (size_t)blockIdx.x * a.slotFrames;
-            uint32_t *pS = a.profS + (size_t)blockIdx.x * a.slotFrames;
-            const double maxCost = a.maxCost ? a.maxCost[k] : INF;
-            const size_t o = (size_t)k * a.maxSpots;
-            uint32_t cnt = 0;
-            __threadfence_block();
-            // the least survivor is a candidate or nothing is (bestEnd names a row: bestD is finite)
-            while (bestEnd != 0xffffffffu && bestD <= maxCost) {
+            SSYM_SPOT_SELECT(a, k, Fa, lane, bestD, bestEnd, bestSt)
+        } else if (lane == 0) {
+            a.cost[k] = bestD;
+            a.start[k] = bestSt;
+            a.end[k] = bestEnd;
+        }
+    }
+}
+
+// Paced spotting (ssym_dtw_spot_step and its kin with SSYM_STEP_PACED; DESIGN.md 2 "Paced spotting", 5.18): the
+// asymmetric step pattern with Itakura's rule.  Every target frame takes exactly one source frame; a source frame may be
+// skipped but never two in a row, and repeated but never twice in a row.  Per cell two states, N (entered by a source
+// step) and H (entered by repeating the source frame), and E, the better of them (strict <: a tie keeps N):
+//   N(i,0) = c(i,0), sN(i,0) = i, H(i,0) = +inf;   j >= 1:  P = E(i-1,j-1), replaced by E(i-2,j-1) if that is < P;
+//   N(i,j) = c(i,j) + P, sN = P's start;   H(i,j) = c(i,j) + N(i,j-1), sH = sN(i,j-1);   outside the matrix +inf.
+// The end column is E(., Fb-1); end, cost, start and the occurrences are taken from it as dtw_spot_kernel takes them.
+//
+// The wavefront is dtw_spot_kernel's.  What differs: the lane keeps (N, sN) of its previous column beside E; what passes
+// between lanes is E.  E(r-1, j-1) is what shfl_up1 brought one step earlier (d1).  E(r-2, j-1) is the d1 lane l - 1 used
+// one step earlier, so every step ends by moving d1 one lane up for the next step (d2): one more DPP triple, and it is taken
+// AFTER lane 0 has put the hand-off row's entry into its d1, because lane 1's second diagonal is row c0 - 1, which only
+// lane 0 read.  Two hand-off rows: lane 63 writes row c0 + 63 (bound1), lane 62 row c0 + 62 (bound2), both in place.
+// In-place order: the lanes of a wave run in lockstep and LDS keeps a wave's accesses in order.  Lane 0 reads entry
+// tau - 1 of both rows at step tau; entry x of bound1 is overwritten at step x + 63 and entry x of bound2 at step x + 62
+// (lane 62 is one column ahead of lane 63), both later than step x + 1.  Only a chunk of 64 rows is followed by another,
+// and it has written every entry of both rows by its last step; a pair's first chunk reads neither row (c0 = 0: +inf),
+// so what the previous pair of the grid stride left there is never seen.
+template <int DIMR, bool ALL = false, class Args = SpotArgs>
+__global__ __launch_bounds__(64) void dtw_paced_kernel(const Args a)
+{
+    extern __shared__ __attribute__((aligned(16))) double smem[];
+    constexpr int LD = wave_ld(DIMR);
+    double *bound1D = smem;                                         // [fbCap]   E of row c0 - 1: value ...
+    double *bound2D = smem + a.fbCap;                               // [fbCap]   E of row c0 - 2: value ...
+    double *ring = smem + 2 * (size_t)a.fbCap;                      // [ringRows][LD]
+    uint32_t *bound1S = reinterpret_cast<uint32_t *>(ring + (size_t)a.ringRows * LD);     // [fbCap]   ... and start
+    uint32_t *bound2S = bound1S + a.fbCap;                          // [fbCap]   ... and start
+    const double INF = __builtin_inf();
+    const int lane = threadIdx.x;
+    const int dim = (int)a.dim;
+    const uint32_t ringMask = a.ringRows - 1;
+
+    for (uint32_t k = blockIdx.x; k < a.nPairs; k += gridDim.x) {
+        uint2 p;
+        if (a.pairs)
+            p = a.pairs[k];
+        else
+            p = make_uint2(k / a.nTgt, k % a.nTgt);
+        uint32_t Fa = 0;
+        int Fb = 0;
+        if (p.x != 0xffffffffu) {
+            Fa = (uint32_t)(a.srcOff[p.x + 1] - a.srcOff[p.x]);
+            Fb = (int)(a.tgtOff[p.y + 1] - a.tgtOff[p.y]);
+        }
+        if (Fa == 0 || Fb == 0) {
+            if constexpr (ALL) {
+                spot_all_pad(a, k, 0u);
+            } else if (lane == 0) {
+                a.cost[k] = INF;
+                a.start[k] = 0xffffffffu;
+                a.end[k] = 0xffffffffu;
+            }
+            continue;
+        }
+        const double *a0 = a.srcRaw + a.srcOff[p.x] * dim;
+        const double *b0 = a.tgtRaw + a.tgtOff[p.y] * dim;
+
+        double bestD = INF;                 // this lane's rows: the least E(r, Fb-1) so far, its row and its start
+        uint32_t bestEnd = 0xffffffffu, bestSt = 0xffffffffu;
+        for (uint32_t c0 = 0; c0 < Fa; c0 += 64) {
+            const uint32_t r = c0 + (uint32_t)lane;
+            const bool rowValid = r < Fa;
+            const int rowsHere = (int)min(64u, Fa - c0);
+            double ar[DIMR];
+            wave_load_frame(ar, a0 + (size_t)(rowValid ? r : c0) * dim, dim);
+            double mineN = INF, mineE = INF;                        // N(r, j-1), E(r, j-1)
+            uint32_t mineNS = 0xffffffffu, mineES = 0xffffffffu;
+            double d1D = INF, d2D = INF;                            // E(r-1, j-1), E(r-2, j-1)
+            uint32_t d1S = 0xffffffffu, d2S = 0xffffffffu;
+            const int tauEnd = Fb - 1 + rowsHere;     // exclusive: lane l works on column tau - l
+            for (int tau = 0; tau < tauEnd; ++tau) {
+                // (the refill's barrier also orders the hand-off rows, as in dtw_spot_kernel)
+                if ((tau & 63) == 0)
+                    wave_refill<DIMR>(ring, ringMask, b0, dim, Fb, tau);
+                const int j = tau - lane;
+                const double c = wave_cell_cost(ar, ring, ringMask, min(max(j, 0), Fb - 1), a.squared);
+                const double upD = shfl_up1(mineE);       // E(r-1, j) and its start, for lanes >= 1: the next step's d1
+                const uint32_t upS = (uint32_t)shfl_up1((int)mineES);
                 if (lane == 0) {
-                    a.cost[o + cnt] = bestD;
-                    a.start[o + cnt] = bestSt;
-                    a.end[o + cnt] = bestEnd;
-                }
-                if (++cnt == a.maxSpots)
-                    break;
-                // kill every end whose span [st(i), i] shares a frame with the pick's, and find the first least survivor
-                const uint32_t pickS = bestSt, pickE = bestEnd;
-                bestD = INF;
-                bestEnd = bestSt = 0xffffffffu;
-#pragma unroll 4
-                for (uint32_t i = (uint32_t)lane; i < Fa; i += 64) {
-                    const double d = pD[i];
-                    const uint32_t s = pS[i];
-                    if (s <= pickE && i >= pickS) {
-                        pD[i] = INF;
-                    } else if (d < bestD) {
-                        bestD = d;
-                        bestEnd = i;
-                        bestSt = s;
+                    d1D = d2D = INF;                      // above row 0 there is nothing
+                    d1S = d2S = 0xffffffffu;
+                    if (c0 != 0 && j >= 1 && j < Fb) {
+                        d1D = bound1D[j - 1];
+                        d1S = bound1S[j - 1];
+                        d2D = bound2D[j - 1];
+                        d2S = bound2S[j - 1];
                     }
                 }
-                SSYM_SPOT_FIRST_MIN(bestD, bestEnd, bestSt)
+                // E(r-2, j) for the next step: the d1 of lane l - 1, lane 0's being what it read from the hand-off row
+                const double nxD = shfl_up1(d1D);
+                const uint32_t nxS = (uint32_t)shfl_up1((int)d1S);
+                const bool active = rowValid && j >= 0 && j < Fb;
+                if (active) {
+                    double nD = c, eD = c;                // column 0: a path may start at any source frame, in state N
+                    uint32_t nS = r, eS = r;
+                    if (j > 0) {
+                        double pD = d1D;
+                        uint32_t pS = d1S;
+                        if (d2D < pD) {
+                            pD = d2D;
+                            pS = d2S;
+                        }
+                        nD = __dadd_rn(c, pD);
+                        nS = pS;
+                        const double hD = __dadd_rn(c, mineN);
+                        eD = nD;
+                        eS = nS;
+                        if (hD < nD) {
+                            eD = hD;
+                            eS = mineNS;
+                        }
+                    }
+                    if (lane == 63) {
+                        bound1D[j] = eD;
+                        bound1S[j] = eS;
+                    }
+                    if (lane == 62) {
+                        bound2D[j] = eD;
+                        bound2S[j] = eS;
+                    }
+                    if (j == Fb - 1 && eD < bestD) {
+                        bestD = eD;
+                        bestEnd = r;
+                        bestSt = eS;
+                    }
+                    mineN = nD;
+                    mineNS = nS;
+                    mineE = eD;
+                    mineES = eS;
+                }
+                d1D = upD;
+                d1S = upS;
+                d2D = nxD;
+                d2S = nxS;
             }
-            spot_all_pad(a, k, cnt);
+            // a valid row's last active step was column Fb - 1: what the lane carries is its entry of the profile
+            if constexpr (ALL) {
+                if (rowValid) {
+                    a.profD[(size_t)blockIdx.x * a.slotFrames + r] = mineE;
+                    a.profS[(size_t)blockIdx.x * a.slotFrames + r] = mineES;
+                }
+            }
+        }
+        // the first minimum of the end column
+        SSYM_SPOT_FIRST_MIN(bestD, bestEnd, bestSt)
+        if constexpr (ALL) {
+            SSYM_SPOT_SELECT(a, k, Fa, lane, bestD, bestEnd, bestSt)
         } else if (lane == 0) {
             a.cost[k] = bestD;
             a.start[k] = bestSt;
@@ -282,9 +449,27 @@ int32_t spot_check_ctx(ssym_ctx *ctx, const char *fn)
     return SSYM_OK;
 }
 
-// the spot kernel on ctx's stream: pairs (device, NULL = every (source, target)) -> cost / start / end (device)
+// what the _step entry points refuse first
+int32_t spot_check_step(ssym_ctx *ctx, const char *fn, uint32_t step)
+{
+    if (step != SSYM_STEP_SYMMETRIC && step != SSYM_STEP_PACED) {
+        ctx->err = std::string(fn) + ": step must be SSYM_STEP_SYMMETRIC or SSYM_STEP_PACED";
+        return SSYM_E_INVALID;
+    }
+    return SSYM_OK;
+}
+
+// dynamic LDS of a launch: the hand-off rows (12 bytes per target frame each: one row, at most 48 KiB, or the paced
+// pattern's two, at most 48 KiB as well) + the ring (at most 66 KiB)
+size_t spot_lds_bytes(uint32_t fbCap, uint32_t ringRows, int dimr, uint32_t step)
+{
+    const size_t rows = step == SSYM_STEP_PACED ? 2 : 1;
+    return rows * fbCap * (sizeof(double) + sizeof(uint32_t)) + wave_ring_bytes(ringRows, dimr);
+}
+
+// the spot kernel of `step` on ctx's stream: pairs (device, NULL = every (source, target)) -> cost / start / end (device)
 int32_t launch_spot(ssym_ctx *ctx, const SegmentSet &src, const SegmentSet &tgt, const uint2 *pairs, uint32_t n_pairs,
-                    uint64_t maxFb, double *cost, uint32_t *start, uint32_t *end)
+                    uint64_t maxFb, double *cost, uint32_t *start, uint32_t *end, uint32_t step)
 {
     SpotArgs a{};
     a.srcRaw = src.raw;
@@ -302,16 +487,18 @@ int32_t launch_spot(ssym_ctx *ctx, const SegmentSet &src, const SegmentSet &tgt,
     a.fbCap = wave_fb_cap(maxFb);
     a.ringRows = wave_ring_rows(maxFb);
     const int dimr = wave_dimr(src.dim);
-    // hand-off row (12 bytes per target frame, at most 48 KiB) + ring (at most 66 KiB)
-    const size_t lds = (size_t)a.fbCap * (sizeof(double) + sizeof(uint32_t)) + wave_ring_bytes(a.ringRows, dimr);
+    const size_t lds = spot_lds_bytes(a.fbCap, a.ringRows, dimr, step);
     const unsigned grid = (unsigned)std::min<uint64_t>(n_pairs, (uint64_t)ctx->num_cus * 8);
+    if (step == SSYM_STEP_PACED)
+        return wave_launch(ctx, SSYM_WAVE_KERNEL(dtw_paced_kernel, dimr), grid, lds, a);
     return wave_launch(ctx, SSYM_WAVE_KERNEL(dtw_spot_kernel, dimr), grid, lds, a);
 }
 
-int32_t spot_limits(ssym_ctx *ctx, const char *fn, uint64_t maxFb, uint32_t dim)
+int32_t spot_limits(ssym_ctx *ctx, const char *fn, uint64_t maxFb, uint32_t dim, uint32_t step = SSYM_STEP_SYMMETRIC)
 {
-    if (maxFb > (uint64_t)kSpotMaxTargetFrames || dim > (uint32_t)kSpotMaxDim) {
-        ctx->err = std::string(fn) + ": a target has more than " + std::to_string(kSpotMaxTargetFrames) +
+    const int maxFrames = step == SSYM_STEP_PACED ? kPacedMaxTargetFrames : kSpotMaxTargetFrames;
+    if (maxFb > (uint64_t)maxFrames || dim > (uint32_t)kSpotMaxDim) {
+        ctx->err = std::string(fn) + ": a target has more than " + std::to_string(maxFrames) +
                    " frames, or frames have more than " + std::to_string(kSpotMaxDim) + " values";
         return SSYM_E_UNSUPPORTED;
     }
@@ -320,18 +507,20 @@ int32_t spot_limits(ssym_ctx *ctx, const char *fn, uint64_t maxFb, uint32_t dim)
 
 int32_t dtw_spot(ssym_ctx *ctx, const ssym_dict *dict, const ssym_queries *q, const uint32_t *src_idx,
                  const uint32_t *tgt_idx, uint32_t n_pairs, uint32_t index_base, double *out_cost, uint32_t *out_start,
-                 uint32_t *out_end, uint32_t flags)
+                 uint32_t *out_end, uint32_t flags, uint32_t step = SSYM_STEP_SYMMETRIC, const char *fn = "ssym_dtw_spot")
 {
     if (!ctx)
         return SSYM_E_INVALID;
-    int32_t rc = spot_check_ctx(ctx, "ssym_dtw_spot");
+    int32_t rc = spot_check_step(ctx, fn, step);
+    if (rc == SSYM_OK)
+        rc = spot_check_ctx(ctx, fn);
     if (rc != SSYM_OK)
         return rc;
-    rc = check_pair_list(ctx->err, "ssym_dtw_spot", dict, q, src_idx, tgt_idx, n_pairs, index_base);
+    rc = check_pair_list(ctx->err, fn, dict, q, src_idx, tgt_idx, n_pairs, index_base);
     if (rc != SSYM_OK || n_pairs == 0)
         return rc;
     if (!out_cost || !out_start || !out_end) {
-        ctx->err = "ssym_dtw_spot: out_cost, out_start and out_end must not be NULL";
+        ctx->err = std::string(fn) + ": out_cost, out_start and out_end must not be NULL";
         return SSYM_E_INVALID;
     }
     const SegmentSet &src = dict->set, &tgt = q->set;
@@ -344,7 +533,7 @@ int32_t dtw_spot(ssym_ctx *ctx, const ssym_dict *dict, const ssym_queries *q, co
         if (s != SSYM_NO_MATCH && src.h_off[s + 1] > src.h_off[s])
             maxFb = std::max(maxFb, tgt.h_off[t + 1] - tgt.h_off[t]);
     }
-    rc = spot_limits(ctx, "ssym_dtw_spot", maxFb, src.dim);
+    rc = spot_limits(ctx, fn, maxFb, src.dim, step);
     if (rc != SSYM_OK)
         return rc;
     SSYM_HIP_CHECK(ctx, hipSetDevice(ctx->device));
@@ -367,7 +556,7 @@ int32_t dtw_spot(ssym_ctx *ctx, const ssym_dict *dict, const ssym_queries *q, co
         return rc;
     SSYM_HIP_CHECK(ctx, hipMemcpyAsync(dPairs, pairs.data(), sizeof(uint2) * n_pairs, hipMemcpyHostToDevice, st));
     SSYM_HIP_CHECK(ctx, hipEventRecord(ctx->ev[0], st));
-    rc = launch_spot(ctx, src, tgt, dPairs, n_pairs, maxFb, dCost, dStart, dEnd);
+    rc = launch_spot(ctx, src, tgt, dPairs, n_pairs, maxFb, dCost, dStart, dEnd, step);
     if (rc != SSYM_OK)
         return rc;
     SSYM_HIP_CHECK(ctx, hipEventRecord(ctx->ev[1], st));
@@ -393,12 +582,13 @@ int32_t dtw_spot(ssym_ctx *ctx, const ssym_dict *dict, const ssym_queries *q, co
 int32_t dtw_spot_all(ssym_ctx *ctx, const ssym_dict *dict, const ssym_queries *q, const uint32_t *src_idx,
                      const uint32_t *tgt_idx, uint32_t n_pairs, uint32_t index_base, uint32_t max_spots,
                      const double *max_cost, uint32_t *out_count, double *out_cost, uint32_t *out_start, uint32_t *out_end,
-                     uint32_t flags)
+                     uint32_t flags, uint32_t step = SSYM_STEP_SYMMETRIC, const char *fn = "ssym_dtw_spot_all")
 {
-    const char *fn = "ssym_dtw_spot_all";
     if (!ctx)
         return SSYM_E_INVALID;
-    int32_t rc = spot_check_ctx(ctx, fn);
+    int32_t rc = spot_check_step(ctx, fn, step);
+    if (rc == SSYM_OK)
+        rc = spot_check_ctx(ctx, fn);
     if (rc != SSYM_OK)
         return rc;
     rc = check_pair_list(ctx->err, fn, dict, q, src_idx, tgt_idx, n_pairs, index_base);
@@ -430,7 +620,7 @@ int32_t dtw_spot_all(ssym_ctx *ctx, const ssym_dict *dict, const ssym_queries *q
         if (fa)
             maxFb = std::max(maxFb, fb);
     }
-    rc = spot_limits(ctx, fn, maxFb, src.dim);
+    rc = spot_limits(ctx, fn, maxFb, src.dim, step);
     if (rc != SSYM_OK)
         return rc;
     if (maxFa > kSpotAllMaxSourceFrames) {
@@ -492,14 +682,22 @@ int32_t dtw_spot_all(ssym_ctx *ctx, const ssym_dict *dict, const ssym_queries *q
     a.count = dCount;
     a.maxCost = dMax;
     const int dimr = wave_dimr(src.dim);
-    const size_t lds = (size_t)a.fbCap * (sizeof(double) + sizeof(uint32_t)) + wave_ring_bytes(a.ringRows, dimr);
+    const size_t lds = spot_lds_bytes(a.fbCap, a.ringRows, dimr, step);
     SSYM_HIP_CHECK(ctx, hipEventRecord(ctx->ev[0], st));
-    rc = wave_launch(ctx,
-                     dimr == 14   ? dtw_spot_kernel<14, true, SpotAllArgs>
-                     : dimr == 16 ? dtw_spot_kernel<16, true, SpotAllArgs>
-                     : dimr == 40 ? dtw_spot_kernel<40, true, SpotAllArgs>
-                                  : dtw_spot_kernel<64, true, SpotAllArgs>,
-                     grid, lds, a);
+    if (step == SSYM_STEP_PACED)
+        rc = wave_launch(ctx,
+                         dimr == 14   ? dtw_paced_kernel<14, true, SpotAllArgs>
+                         : dimr == 16 ? dtw_paced_kernel<16, true, SpotAllArgs>
+                         : dimr == 40 ? dtw_paced_kernel<40, true, SpotAllArgs>
+                                      : dtw_paced_kernel<64, true, SpotAllArgs>,
+                         grid, lds, a);
+    else
+        rc = wave_launch(ctx,
+                         dimr == 14   ? dtw_spot_kernel<14, true, SpotAllArgs>
+                         : dimr == 16 ? dtw_spot_kernel<16, true, SpotAllArgs>
+                         : dimr == 40 ? dtw_spot_kernel<40, true, SpotAllArgs>
+                                      : dtw_spot_kernel<64, true, SpotAllArgs>,
+                         grid, lds, a);
     if (rc != SSYM_OK)
         return rc;
     SSYM_HIP_CHECK(ctx, hipEventRecord(ctx->ev[1], st));
@@ -524,14 +722,17 @@ int32_t dtw_spot_all(ssym_ctx *ctx, const ssym_dict *dict, const ssym_queries *q
 }
 
 int32_t spot_queries(ssym_ctx *ctx, const ssym_dict *dict, const ssym_queries *q, uint32_t index_base, uint32_t *out_idx,
-                     double *out_cost, uint32_t *out_start, uint32_t *out_end, uint32_t flags)
+                     double *out_cost, uint32_t *out_start, uint32_t *out_end, uint32_t flags,
+                     uint32_t step = SSYM_STEP_SYMMETRIC, const char *fn = "ssym_spot_queries")
 {
     if (!ctx)
         return SSYM_E_INVALID;
-    int32_t rc = spot_check_ctx(ctx, "ssym_spot_queries");
+    int32_t rc = spot_check_step(ctx, fn, step);
+    if (rc == SSYM_OK)
+        rc = spot_check_ctx(ctx, fn);
     if (rc != SSYM_OK)
         return rc;
-    rc = check_handles(ctx->err, "ssym_spot_queries", dict, q);
+    rc = check_handles(ctx->err, fn, dict, q);
     if (rc != SSYM_OK)
         return rc;
     const SegmentSet &src = dict->set, &tgt = q->set;
@@ -542,15 +743,15 @@ int32_t spot_queries(ssym_ctx *ctx, const ssym_dict *dict, const ssym_queries *q
     if (rc != SSYM_OK)
         return rc;
     if (!out_idx || !out_cost || !out_start || !out_end) {
-        ctx->err = "ssym_spot_queries: out_idx, out_cost, out_start and out_end must not be NULL";
+        ctx->err = std::string(fn) + ": out_idx, out_cost, out_start and out_end must not be NULL";
         return SSYM_E_INVALID;
     }
     if ((uint64_t)N * M > 0xffffffffull) {
-        ctx->err = "ssym_spot_queries: more than 2^32 - 1 (source, target) pairs in one call";
+        ctx->err = std::string(fn) + ": more than 2^32 - 1 (source, target) pairs in one call";
         return SSYM_E_UNSUPPORTED;
     }
     const uint64_t maxFb = src.max_frames ? tgt.max_frames : 0;      // (sources without frames: nothing to run)
-    rc = spot_limits(ctx, "ssym_spot_queries", maxFb, src.dim);
+    rc = spot_limits(ctx, fn, maxFb, src.dim, step);
     if (rc != SSYM_OK)
         return rc;
     SSYM_HIP_CHECK(ctx, hipSetDevice(ctx->device));
@@ -575,7 +776,7 @@ int32_t spot_queries(ssym_ctx *ctx, const ssym_dict *dict, const ssym_queries *q
     if (rc != SSYM_OK)
         return rc;
     SSYM_HIP_CHECK(ctx, hipEventRecord(ctx->ev[0], st));
-    rc = launch_spot(ctx, src, tgt, nullptr, nPairs, maxFb, mCost, mSpan, mSpan + nPairs);
+    rc = launch_spot(ctx, src, tgt, nullptr, nPairs, maxFb, mCost, mSpan, mSpan + nPairs, step);
     if (rc != SSYM_OK)
         return rc;
     SSYM_HIP_CHECK(ctx, hipEventRecord(ctx->ev[1], st));
@@ -637,6 +838,38 @@ int32_t ssym_spot_queries(ssym_ctx *ctx, const ssym_dict *dict, const ssym_queri
 {
     return guarded(ctx, [&]() -> int32_t {
         return spot_queries(ctx, dict, q, index_base, out_idx, out_cost, out_start, out_end, flags);
+    });
+}
+
+// the three calls above with the step pattern as an argument: SSYM_STEP_SYMMETRIC is the call above itself
+int32_t ssym_dtw_spot_step(ssym_ctx *ctx, const ssym_dict *dict, const ssym_queries *q, const uint32_t *src_idx,
+                           const uint32_t *tgt_idx, uint32_t n_pairs, uint32_t index_base, uint32_t step, double *out_cost,
+                           uint32_t *out_start, uint32_t *out_end, uint32_t flags)
+{
+    return guarded(ctx, [&]() -> int32_t {
+        return dtw_spot(ctx, dict, q, src_idx, tgt_idx, n_pairs, index_base, out_cost, out_start, out_end, flags, step,
+                        "ssym_dtw_spot_step");
+    });
+}
+
+int32_t ssym_spot_queries_step(ssym_ctx *ctx, const ssym_dict *dict, const ssym_queries *q, uint32_t index_base,
+                               uint32_t step, uint32_t *out_idx, double *out_cost, uint32_t *out_start, uint32_t *out_end,
+                               uint32_t flags)
+{
+    return guarded(ctx, [&]() -> int32_t {
+        return spot_queries(ctx, dict, q, index_base, out_idx, out_cost, out_start, out_end, flags, step,
+                            "ssym_spot_queries_step");
+    });
+}
+
+int32_t ssym_dtw_spot_all_step(ssym_ctx *ctx, const ssym_dict *dict, const ssym_queries *q, const uint32_t *src_idx,
+                               const uint32_t *tgt_idx, uint32_t n_pairs, uint32_t index_base, uint32_t step,
+                               uint32_t max_spots, const double *max_cost, uint32_t *out_count, double *out_cost,
+                               uint32_t *out_start, uint32_t *out_end, uint32_t flags)
+{
+    return guarded(ctx, [&]() -> int32_t {
+        return dtw_spot_all(ctx, dict, q, src_idx, tgt_idx, n_pairs, index_base, max_spots, max_cost, out_count, out_cost,
+                            out_start, out_end, flags, step, "ssym_dtw_spot_all_step");
     });
 }
 

@@ -43,6 +43,15 @@ def _align_indices(src_idx, tgt_idx):
     return src, tgt
 
 
+def _spot_step(step):
+    """SSYM_STEP_* of step="symmetric" | "paced", checked before the library is asked."""
+    if step == "symmetric":
+        return nat.STEP_SYMMETRIC
+    if step == "paced":
+        return nat.STEP_PACED
+    raise ValueError('step must be "symmetric" or "paced"')
+
+
 def _spot_all_args(src, max_spots, max_cost):
     """(K, per-pair thresholds as a contiguous f64 array or None) of dtw_spot_all, checked before the library is asked."""
     k = int(max_spots)
@@ -834,25 +843,34 @@ class Engine:
                                            fmap.data_ptr(), nat.OUT_DEVICE), self.ctx)
         return cost[:n], length[:n], path[:2 * int(p_off[-1])], fmap[:int(m_off[-1])], p_off, m_off
 
-    def dtw_spot(self, d: _Handle, q: _Handle, src_idx, tgt_idx=None, index_base: int = 0):
+    def dtw_spot(self, d: _Handle, q: _Handle, src_idx, tgt_idx=None, index_base: int = 0, step: str = "symmetric"):
         """ssym_dtw_spot (subsequence DTW; dtw engines without a band): for every listed pair (source src_idx[p] -
         index_base, target tgt_idx[p], or target p without tgt_idx) the span of the source's frames the target aligns
         with best, by the definition in include/soundsym_amd.h.  Returns (cost f64 [n], start uint32 [n], end uint32
         [n]); end is inclusive; a pair without a spot has cost +inf and start = end = NO_MATCH.  The cost is not
-        normalised by any length."""
+        normalised by any length.  step="paced": ssym_dtw_spot_step with SSYM_STEP_PACED ("Paced spotting": every path
+        has as many cells as the target has frames, so cost / frames is a mean per-frame distance); "symmetric" is
+        ssym_dtw_spot itself."""
+        which = _spot_step(step)
         src, tgt = _align_indices(src_idx, tgt_idx)
         n = src.size
         cost = np.zeros(n, dtype=np.float64)
         start = np.zeros(n, dtype=np.uint32)
         end = np.zeros(n, dtype=np.uint32)
-        rc = nat.lib().ssym_dtw_spot(self.ctx, d.ptr, q.ptr, src.ctypes.data, tgt.ctypes.data if tgt is not None else None,
-                                     n, index_base, cost.ctypes.data, start.ctypes.data, end.ctypes.data, 0)
+        tp = tgt.ctypes.data if tgt is not None else None
+        if which == nat.STEP_SYMMETRIC:
+            rc = nat.lib().ssym_dtw_spot(self.ctx, d.ptr, q.ptr, src.ctypes.data, tp, n, index_base, cost.ctypes.data,
+                                         start.ctypes.data, end.ctypes.data, 0)
+        else:
+            rc = nat.lib().ssym_dtw_spot_step(self.ctx, d.ptr, q.ptr, src.ctypes.data, tp, n, index_base, which,
+                                              cost.ctypes.data, start.ctypes.data, end.ctypes.data, 0)
         nat.check(rc, self.ctx)
         return cost, start, end
 
-    def dtw_spot_device(self, d: _Handle, q: _Handle, src_idx, tgt_idx=None, index_base: int = 0):
+    def dtw_spot_device(self, d: _Handle, q: _Handle, src_idx, tgt_idx=None, index_base: int = 0, step: str = "symmetric"):
         """ssym_dtw_spot with SSYM_OUT_DEVICE: (cost f64 [n], start i32 [n], end i32 [n]) as torch tensors in device
-        memory (torch only owns the memory; the 32-bit tensors hold the call's u32 values)."""
+        memory (torch only owns the memory; the 32-bit tensors hold the call's u32 values).  step as for dtw_spot."""
+        which = _spot_step(step)
         import torch
         src, tgt = _align_indices(src_idx, tgt_idx)
         n = src.size
@@ -860,17 +878,25 @@ class Engine:
         cost = torch.empty(max(n, 1), dtype=torch.float64, device=dev)
         start = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
         end = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
-        nat.check(nat.lib().ssym_dtw_spot(self.ctx, d.ptr, q.ptr, src.ctypes.data,
-                                          tgt.ctypes.data if tgt is not None else None, n, index_base, cost.data_ptr(),
-                                          start.data_ptr(), end.data_ptr(), nat.OUT_DEVICE), self.ctx)
+        tp = tgt.ctypes.data if tgt is not None else None
+        if which == nat.STEP_SYMMETRIC:
+            rc = nat.lib().ssym_dtw_spot(self.ctx, d.ptr, q.ptr, src.ctypes.data, tp, n, index_base, cost.data_ptr(),
+                                         start.data_ptr(), end.data_ptr(), nat.OUT_DEVICE)
+        else:
+            rc = nat.lib().ssym_dtw_spot_step(self.ctx, d.ptr, q.ptr, src.ctypes.data, tp, n, index_base, which,
+                                              cost.data_ptr(), start.data_ptr(), end.data_ptr(), nat.OUT_DEVICE)
+        nat.check(rc, self.ctx)
         return cost[:n], start[:n], end[:n]
 
     def dtw_spot_all(self, d: _Handle, q: _Handle, src_idx, tgt_idx=None, index_base: int = 0, max_spots: int = 8,
-                     max_cost=None):
+                     max_cost=None, step: str = "symmetric"):
         """ssym_dtw_spot_all: for every listed pair (as in dtw_spot) up to max_spots (1 ... 64) pairwise disjoint spans
         of the source the target aligns with, best first, by the definition in include/soundsym_amd.h ("Occurrences").
         max_cost: a scalar or one value per pair; an occurrence costs at most that.  Returns (count uint32 [n], cost f64
-        [n, K], start uint32 [n, K], end uint32 [n, K]); slots from count[p] on hold +inf and NO_MATCH."""
+        [n, K], start uint32 [n, K], end uint32 [n, K]); slots from count[p] on hold +inf and NO_MATCH.  step="paced":
+        ssym_dtw_spot_all_step with SSYM_STEP_PACED (costs and max_cost stay sums); "symmetric" is ssym_dtw_spot_all
+        itself."""
+        which = _spot_step(step)
         src, tgt = _align_indices(src_idx, tgt_idx)
         k, mc = _spot_all_args(src, max_spots, max_cost)
         n = src.size
@@ -878,16 +904,22 @@ class Engine:
         cost = np.zeros((n, k), dtype=np.float64)
         start = np.zeros((n, k), dtype=np.uint32)
         end = np.zeros((n, k), dtype=np.uint32)
-        rc = nat.lib().ssym_dtw_spot_all(self.ctx, d.ptr, q.ptr, src.ctypes.data, tgt.ctypes.data if tgt is not None else None,
-                                         n, index_base, k, mc.ctypes.data if mc is not None else None, count.ctypes.data,
-                                         cost.ctypes.data, start.ctypes.data, end.ctypes.data, 0)
+        head = (self.ctx, d.ptr, q.ptr, src.ctypes.data, tgt.ctypes.data if tgt is not None else None, n, index_base)
+        tail = (k, mc.ctypes.data if mc is not None else None, count.ctypes.data, cost.ctypes.data, start.ctypes.data,
+                end.ctypes.data, 0)
+        if which == nat.STEP_SYMMETRIC:
+            rc = nat.lib().ssym_dtw_spot_all(*head, *tail)
+        else:
+            rc = nat.lib().ssym_dtw_spot_all_step(*head, which, *tail)
         nat.check(rc, self.ctx)
         return count, cost, start, end
 
     def dtw_spot_all_device(self, d: _Handle, q: _Handle, src_idx, tgt_idx=None, index_base: int = 0, max_spots: int = 8,
-                            max_cost=None):
+                            max_cost=None, step: str = "symmetric"):
         """ssym_dtw_spot_all with SSYM_OUT_DEVICE: (count i32 [n], cost f64 [n, K], start i32 [n, K], end i32 [n, K]) as
-        torch tensors in device memory (torch only owns the memory; the 32-bit tensors hold the call's u32 values)."""
+        torch tensors in device memory (torch only owns the memory; the 32-bit tensors hold the call's u32 values).  step as
+        for dtw_spot_all."""
+        which = _spot_step(step)
         src, tgt = _align_indices(src_idx, tgt_idx)
         k, mc = _spot_all_args(src, max_spots, max_cost)
         import torch
@@ -897,23 +929,33 @@ class Engine:
         cost = torch.empty((max(n, 1), k), dtype=torch.float64, device=dev)
         start = torch.empty((max(n, 1), k), dtype=torch.int32, device=dev)
         end = torch.empty((max(n, 1), k), dtype=torch.int32, device=dev)
-        nat.check(nat.lib().ssym_dtw_spot_all(self.ctx, d.ptr, q.ptr, src.ctypes.data,
-                                              tgt.ctypes.data if tgt is not None else None, n, index_base, k,
-                                              mc.ctypes.data if mc is not None else None, count.data_ptr(),
-                                              cost.data_ptr(), start.data_ptr(), end.data_ptr(), nat.OUT_DEVICE), self.ctx)
+        head = (self.ctx, d.ptr, q.ptr, src.ctypes.data, tgt.ctypes.data if tgt is not None else None, n, index_base)
+        tail = (k, mc.ctypes.data if mc is not None else None, count.data_ptr(), cost.data_ptr(), start.data_ptr(),
+                end.data_ptr(), nat.OUT_DEVICE)
+        if which == nat.STEP_SYMMETRIC:
+            rc = nat.lib().ssym_dtw_spot_all(*head, *tail)
+        else:
+            rc = nat.lib().ssym_dtw_spot_all_step(*head, which, *tail)
+        nat.check(rc, self.ctx)
         return count[:n], cost[:n], start[:n], end[:n]
 
-    def spot_queries(self, d: _Handle, q: _Handle, index_base: int = 0):
+    def spot_queries(self, d: _Handle, q: _Handle, index_base: int = 0, step: str = "symmetric"):
         """ssym_spot_queries: every dictionary segment spotted against every target, then the first least cost per
         target over ascending segment index.  Returns (idx uint32 [m] (+ index_base; NO_MATCH where no segment has a
-        spot), cost f64 [m], start uint32 [m], end uint32 [m]) -- the span is the winning segment's."""
+        spot), cost f64 [m], start uint32 [m], end uint32 [m]) -- the span is the winning segment's.  step="paced":
+        ssym_spot_queries_step with SSYM_STEP_PACED; "symmetric" is ssym_spot_queries itself."""
+        which = _spot_step(step)
         m = q.n
         idx = np.zeros(m, dtype=np.uint32)
         cost = np.zeros(m, dtype=np.float64)
         start = np.zeros(m, dtype=np.uint32)
         end = np.zeros(m, dtype=np.uint32)
-        rc = nat.lib().ssym_spot_queries(self.ctx, d.ptr, q.ptr, index_base, idx.ctypes.data, cost.ctypes.data,
-                                         start.ctypes.data, end.ctypes.data, 0)
+        if which == nat.STEP_SYMMETRIC:
+            rc = nat.lib().ssym_spot_queries(self.ctx, d.ptr, q.ptr, index_base, idx.ctypes.data, cost.ctypes.data,
+                                             start.ctypes.data, end.ctypes.data, 0)
+        else:
+            rc = nat.lib().ssym_spot_queries_step(self.ctx, d.ptr, q.ptr, index_base, which, idx.ctypes.data,
+                                                  cost.ctypes.data, start.ctypes.data, end.ctypes.data, 0)
         nat.check(rc, self.ctx)
         return idx, cost, start, end
 
