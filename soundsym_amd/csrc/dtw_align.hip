@@ -256,12 +256,11 @@ int32_t dtw_align(ssym_ctx *ctx, const ssym_dict *dict, const ssym_queries *q, c
     }
     const SegmentSet &src = dict->set, &tgt = q->set;
     // the pair list, the offsets against the capacities, the shape limits: all on the host, before any device work
-    std::vector<uint2> pairs(n_pairs);
+    PairList pairs(src_idx, tgt_idx, index_base, n_pairs);
     uint64_t maxFa = 0, maxFb = 0, maxSlab = 0;
     for (uint32_t p = 0; p < n_pairs; ++p) {
-        pairs[p] = pair_at(src_idx, tgt_idx, index_base, p);
         uint64_t steps, frames;
-        align_capacity(src, tgt, pairs[p].x, pairs[p].y, &steps, &frames);
+        align_capacity(src, tgt, pairs.host[p].x, pairs.host[p].y, &steps, &frames);
         if (path_offsets[p + 1] < path_offsets[p] || path_offsets[p + 1] - path_offsets[p] < steps ||
             (out_map && (map_offsets[p + 1] < map_offsets[p] || map_offsets[p + 1] - map_offsets[p] < frames))) {
             ctx->err = "ssym_dtw_align: offsets of pair " + std::to_string(p) +
@@ -290,11 +289,8 @@ int32_t dtw_align(ssym_ctx *ctx, const ssym_dict *dict, const ssym_queries *q, c
 
     Blocks bl(ctx);
     AlignArgs a{};
-    uint2 *dPairs = nullptr;
     uint64_t *dOff = nullptr;        // path offsets, then map offsets, both rebased to the first pair's
-    rc = bl.get(&dPairs, n_pairs);
-    if (rc == SSYM_OK)
-        rc = bl.get(&dOff, 2 * ((size_t)n_pairs + 1));
+    rc = bl.get(&dOff, 2 * ((size_t)n_pairs + 1));
     std::vector<uint64_t> hOff(2 * ((size_t)n_pairs + 1));
     for (uint32_t p = 0; p <= n_pairs; ++p) {
         hOff[p] = path_offsets[p] - path_offsets[0];
@@ -312,13 +308,13 @@ int32_t dtw_align(ssym_ctx *ctx, const ssym_dict *dict, const ssym_queries *q, c
         if (rc == SSYM_OK && out_map)
             rc = bl.get(&dMap, (size_t)mapTotal);
     }
-    const int dimr = wave_dimr(src.dim);
-    a.fbCap = wave_fb_cap(maxFb);
-    a.ringRows = wave_ring_rows(maxFb);
+    const WaveGeom g = wave_geom(ctx, maxFb, src.dim, n_pairs);
+    a.fbCap = g.fbCap;
+    a.ringRows = g.ringRows;
     a.codeCap = ((uint32_t)(maxFa + maxFb) + 15) & ~15u;
     a.dirLdsBytes = (uint32_t)std::min<uint64_t>((uint64_t)kAlignDirLdsBytes, (maxFa * ((maxFb + 15) / 16) * 4 + 15) & ~15ull);
-    const size_t lds = (size_t)a.fbCap * sizeof(double) + wave_ring_bytes(a.ringRows, dimr) + a.codeCap + a.dirLdsBytes;
-    unsigned grid = (unsigned)std::min<uint64_t>(n_pairs, (uint64_t)ctx->num_cus * 8);
+    const size_t lds = (size_t)a.fbCap * sizeof(double) + g.ringBytes + a.codeCap + a.dirLdsBytes;
+    unsigned grid = g.grid;
     if (maxSlab) {
         // one slab per workgroup, as many workgroups as kAlignScratchBytes holds (128 for a 4096 x 4096 pair)
         a.slabWords = (maxSlab + 3) / 4;
@@ -326,9 +322,10 @@ int32_t dtw_align(ssym_ctx *ctx, const ssym_dict *dict, const ssym_queries *q, c
         if (rc == SSYM_OK)
             rc = bl.get(&a.slabs, (size_t)grid * a.slabWords);
     }
+    if (rc == SSYM_OK)
+        rc = pairs.upload(ctx, bl);
     if (rc != SSYM_OK)
         return rc;
-    SSYM_HIP_CHECK(ctx, hipMemcpyAsync(dPairs, pairs.data(), sizeof(uint2) * n_pairs, hipMemcpyHostToDevice, st));
     SSYM_HIP_CHECK(ctx, hipMemcpyAsync(dOff, hOff.data(), sizeof(uint64_t) * hOff.size(), hipMemcpyHostToDevice, st));
     a.srcRaw = src.raw;
     a.srcOff = src.off;
@@ -337,7 +334,7 @@ int32_t dtw_align(ssym_ctx *ctx, const ssym_dict *dict, const ssym_queries *q, c
     a.dim = src.dim;
     a.band = ctx->band;
     a.squared = ctx->squared;
-    a.pairs = dPairs;
+    a.pairs = pairs.dev;
     a.nPairs = n_pairs;
     a.pathOff = dOff;
     a.mapOff = dOff + n_pairs + 1;
@@ -345,7 +342,7 @@ int32_t dtw_align(ssym_ctx *ctx, const ssym_dict *dict, const ssym_queries *q, c
     a.len = dLen;
     a.path = reinterpret_cast<uint2 *>(dPath);
     a.map = dMap;
-    rc = wave_launch(ctx, SSYM_WAVE_KERNEL(dtw_align_kernel, dimr), grid, lds, a);
+    rc = wave_launch(ctx, SSYM_WAVE_KERNEL(dtw_align_kernel, g.dimr), grid, lds, a);
     if (rc != SSYM_OK)
         return rc;
     if (outDev) {
@@ -369,7 +366,7 @@ int32_t dtw_align(ssym_ctx *ctx, const ssym_dict *dict, const ssym_queries *q, c
             continue;
         std::copy(hPath.begin() + 2 * hOff[p], hPath.begin() + 2 * (hOff[p] + hLen[p]), out_path + 2 * path_offsets[p]);
         if (out_map) {
-            const uint64_t m0 = hOff[(size_t)n_pairs + 1 + p], fb = tgt.h_off[pairs[p].y + 1] - tgt.h_off[pairs[p].y];
+            const uint64_t m0 = hOff[(size_t)n_pairs + 1 + p], fb = tgt.h_off[pairs.host[p].y + 1] - tgt.h_off[pairs.host[p].y];
             std::copy(hMap.begin() + m0, hMap.begin() + m0 + fb, out_map + map_offsets[p]);
         }
     }

@@ -27,6 +27,7 @@
 #include "dtw_wave.hpp"
 
 #include <algorithm>
+#include <type_traits>
 
 namespace ssym {
 
@@ -435,43 +436,29 @@ __global__ __launch_bounds__(256) void spot_fold_kernel(const double *cost, cons
     outEnd[t] = en;
 }
 
-// what both entry points refuse before anything else (err: where the message goes)
-int32_t spot_check_ctx(ssym_ctx *ctx, const char *fn)
+// what every driver refuses first, in this order: no context, an unknown step, the context's metric, its band
+int32_t spot_check_entry(ssym_ctx *ctx, const char *fn, uint32_t step)
 {
-    if (ctx->metric != SSYM_METRIC_DTW) {
-        ctx->err = std::string(fn) + ": the context's metric is refcos, which has no alignment to spot";
-        return SSYM_E_UNSUPPORTED;
-    }
-    if (ctx->band >= 0) {
-        ctx->err = std::string(fn) + ": a Sakoe-Chiba band has no meaning with a free start; use a context without one";
-        return SSYM_E_UNSUPPORTED;
-    }
-    return SSYM_OK;
-}
-
-// what the _step entry points refuse first
-int32_t spot_check_step(ssym_ctx *ctx, const char *fn, uint32_t step)
-{
+    if (!ctx)
+        return SSYM_E_INVALID;
     if (step != SSYM_STEP_SYMMETRIC && step != SSYM_STEP_PACED) {
         ctx->err = std::string(fn) + ": step must be SSYM_STEP_SYMMETRIC or SSYM_STEP_PACED";
         return SSYM_E_INVALID;
     }
-    return SSYM_OK;
+    return check_spot_ctx(ctx, fn);
 }
 
-// dynamic LDS of a launch: the hand-off rows (12 bytes per target frame each: one row, at most 48 KiB, or the paced
-// pattern's two, at most 48 KiB as well) + the ring (at most 66 KiB)
-size_t spot_lds_bytes(uint32_t fbCap, uint32_t ringRows, int dimr, uint32_t step)
+int32_t spot_limits(ssym_ctx *ctx, const char *fn, uint64_t maxFb, uint32_t dim, uint32_t step)
 {
-    const size_t rows = step == SSYM_STEP_PACED ? 2 : 1;
-    return rows * fbCap * (sizeof(double) + sizeof(uint32_t)) + wave_ring_bytes(ringRows, dimr);
+    return check_spot_limits(ctx, fn, maxFb, dim, step == SSYM_STEP_PACED ? kPacedMaxTargetFrames : kSpotMaxTargetFrames,
+                             kSpotMaxDim);
 }
 
-// the spot kernel of `step` on ctx's stream: pairs (device, NULL = every (source, target)) -> cost / start / end (device)
-int32_t launch_spot(ssym_ctx *ctx, const SegmentSet &src, const SegmentSet &tgt, const uint2 *pairs, uint32_t n_pairs,
-                    uint64_t maxFb, double *cost, uint32_t *start, uint32_t *end, uint32_t step)
+// the SpotArgs of a launch (SpotAllArgs' base too): pairs (device, NULL = every (source, target)) -> cost / start / end
+// (device)
+void spot_fill(SpotArgs &a, const ssym_ctx *ctx, const SegmentSet &src, const SegmentSet &tgt, const uint2 *pairs,
+               uint32_t n_pairs, const WaveGeom &g, double *cost, uint32_t *start, uint32_t *end)
 {
-    SpotArgs a{};
     a.srcRaw = src.raw;
     a.srcOff = src.off;
     a.tgtRaw = tgt.raw;
@@ -484,24 +471,42 @@ int32_t launch_spot(ssym_ctx *ctx, const SegmentSet &src, const SegmentSet &tgt,
     a.cost = cost;
     a.start = start;
     a.end = end;
-    a.fbCap = wave_fb_cap(maxFb);
-    a.ringRows = wave_ring_rows(maxFb);
-    const int dimr = wave_dimr(src.dim);
-    const size_t lds = spot_lds_bytes(a.fbCap, a.ringRows, dimr, step);
-    const unsigned grid = (unsigned)std::min<uint64_t>(n_pairs, (uint64_t)ctx->num_cus * 8);
-    if (step == SSYM_STEP_PACED)
-        return wave_launch(ctx, SSYM_WAVE_KERNEL(dtw_paced_kernel, dimr), grid, lds, a);
-    return wave_launch(ctx, SSYM_WAVE_KERNEL(dtw_spot_kernel, dimr), grid, lds, a);
+    a.fbCap = g.fbCap;
+    a.ringRows = g.ringRows;
 }
 
-int32_t spot_limits(ssym_ctx *ctx, const char *fn, uint64_t maxFb, uint32_t dim, uint32_t step = SSYM_STEP_SYMMETRIC)
+// the kernel of `step` for a (SpotAllArgs: the one that keeps the end column) on ctx's stream, between ev[0] and ev[1]
+template <class Args>
+int32_t launch_spot(ssym_ctx *ctx, const Args &a, const WaveGeom &g, unsigned grid, uint32_t step)
 {
-    const int maxFrames = step == SSYM_STEP_PACED ? kPacedMaxTargetFrames : kSpotMaxTargetFrames;
-    if (maxFb > (uint64_t)maxFrames || dim > (uint32_t)kSpotMaxDim) {
-        ctx->err = std::string(fn) + ": a target has more than " + std::to_string(maxFrames) +
-                   " frames, or frames have more than " + std::to_string(kSpotMaxDim) + " values";
-        return SSYM_E_UNSUPPORTED;
+    constexpr bool ALL = std::is_same<Args, SpotAllArgs>::value;
+    const size_t lds = spot_lds_bytes(g, step);
+    SSYM_HIP_CHECK(ctx, hipEventRecord(ctx->ev[0], ctx->stream));
+    const int32_t rc = step == SSYM_STEP_PACED
+                           ? wave_launch(ctx, SSYM_WAVE_KERNEL(dtw_paced_kernel, g.dimr, ALL, Args), grid, lds, a)
+                           : wave_launch(ctx, SSYM_WAVE_KERNEL(dtw_spot_kernel, g.dimr, ALL, Args), grid, lds, a);
+    if (rc != SSYM_OK)
+        return rc;
+    SSYM_HIP_CHECK(ctx, hipEventRecord(ctx->ev[1], ctx->stream));
+    return SSYM_OK;
+}
+
+// what ends a call: the outputs back (the call's one synchronisation) and the timings (folded: spot_queries' fold ran
+// between ev[1] and ev[2])
+int32_t spot_finish(ssym_ctx *ctx, SpotOut &out, uint32_t n_pairs, bool folded = false)
+{
+    const int32_t rc = out.finish(ctx);
+    if (rc != SSYM_OK)
+        return rc;
+    ssym_timings tm{};
+    tm.main_ms = tm.total_ms = ev_ms(ctx->ev[0], ctx->ev[1]);
+    if (folded) {
+        tm.reduce_ms = ev_ms(ctx->ev[1], ctx->ev[2]);
+        tm.total_ms = ev_ms(ctx->ev[0], ctx->ev[2]);
     }
+    tm.main_launches = 1;
+    tm.n_pairs = n_pairs;
+    ctx->timings = tm;
     return SSYM_OK;
 }
 
@@ -509,11 +514,7 @@ int32_t dtw_spot(ssym_ctx *ctx, const ssym_dict *dict, const ssym_queries *q, co
                  const uint32_t *tgt_idx, uint32_t n_pairs, uint32_t index_base, double *out_cost, uint32_t *out_start,
                  uint32_t *out_end, uint32_t flags, uint32_t step = SSYM_STEP_SYMMETRIC, const char *fn = "ssym_dtw_spot")
 {
-    if (!ctx)
-        return SSYM_E_INVALID;
-    int32_t rc = spot_check_step(ctx, fn, step);
-    if (rc == SSYM_OK)
-        rc = spot_check_ctx(ctx, fn);
+    int32_t rc = spot_check_entry(ctx, fn, step);
     if (rc != SSYM_OK)
         return rc;
     rc = check_pair_list(ctx->err, fn, dict, q, src_idx, tgt_idx, n_pairs, index_base);
@@ -525,58 +526,30 @@ int32_t dtw_spot(ssym_ctx *ctx, const ssym_dict *dict, const ssym_queries *q, co
     }
     const SegmentSet &src = dict->set, &tgt = q->set;
     // the pair list and the shape limits: on the host, before any device work
-    std::vector<uint2> pairs(n_pairs);
+    PairList pairs(src_idx, tgt_idx, index_base, n_pairs);
     uint64_t maxFb = 0;
-    for (uint32_t p = 0; p < n_pairs; ++p) {
-        pairs[p] = pair_at(src_idx, tgt_idx, index_base, p);
-        const uint32_t s = pairs[p].x, t = pairs[p].y;
-        if (s != SSYM_NO_MATCH && src.h_off[s + 1] > src.h_off[s])
-            maxFb = std::max(maxFb, tgt.h_off[t + 1] - tgt.h_off[t]);
-    }
+    for (const uint2 &p : pairs.host)
+        if (p.x != SSYM_NO_MATCH && src.h_off[p.x + 1] > src.h_off[p.x])
+            maxFb = std::max(maxFb, tgt.h_off[p.y + 1] - tgt.h_off[p.y]);
     rc = spot_limits(ctx, fn, maxFb, src.dim, step);
     if (rc != SSYM_OK)
         return rc;
     SSYM_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-    hipStream_t st = ctx->stream;
-    const bool outDev = (flags & SSYM_OUT_DEVICE) != 0;
 
     Blocks bl(ctx);
-    uint2 *dPairs = nullptr;
-    double *dCost = out_cost;
-    uint32_t *dStart = out_start, *dEnd = out_end;
-    rc = bl.get(&dPairs, n_pairs);
-    if (!outDev) {
-        if (rc == SSYM_OK)
-            rc = bl.get(&dCost, n_pairs);
-        if (rc == SSYM_OK)
-            rc = bl.get(&dStart, 2 * (size_t)n_pairs);
-        dEnd = dStart + n_pairs;
-    }
+    SpotOut out(flags, out_cost, n_pairs, {{out_start, n_pairs}, {out_end, n_pairs}});
+    rc = out.alloc(bl);
+    if (rc == SSYM_OK)
+        rc = pairs.upload(ctx, bl);
     if (rc != SSYM_OK)
         return rc;
-    SSYM_HIP_CHECK(ctx, hipMemcpyAsync(dPairs, pairs.data(), sizeof(uint2) * n_pairs, hipMemcpyHostToDevice, st));
-    SSYM_HIP_CHECK(ctx, hipEventRecord(ctx->ev[0], st));
-    rc = launch_spot(ctx, src, tgt, dPairs, n_pairs, maxFb, dCost, dStart, dEnd, step);
+    const WaveGeom g = wave_geom(ctx, maxFb, src.dim, n_pairs);
+    SpotArgs a{};
+    spot_fill(a, ctx, src, tgt, pairs.dev, n_pairs, g, out.cost, out.words[0].dev, out.words[1].dev);
+    rc = launch_spot(ctx, a, g, g.grid, step);
     if (rc != SSYM_OK)
         return rc;
-    SSYM_HIP_CHECK(ctx, hipEventRecord(ctx->ev[1], st));
-    std::vector<uint32_t> hSpan;
-    if (!outDev) {
-        hSpan.resize(2 * (size_t)n_pairs);
-        SSYM_HIP_CHECK(ctx, hipMemcpyAsync(out_cost, dCost, sizeof(double) * n_pairs, hipMemcpyDeviceToHost, st));
-        SSYM_HIP_CHECK(ctx, hipMemcpyAsync(hSpan.data(), dStart, sizeof(uint32_t) * 2 * n_pairs, hipMemcpyDeviceToHost, st));
-    }
-    SSYM_HIP_CHECK(ctx, hipStreamSynchronize(st));
-    if (!outDev) {
-        std::copy(hSpan.begin(), hSpan.begin() + n_pairs, out_start);
-        std::copy(hSpan.begin() + n_pairs, hSpan.end(), out_end);
-    }
-    ssym_timings tm{};
-    tm.main_ms = tm.total_ms = ev_ms(ctx->ev[0], ctx->ev[1]);
-    tm.main_launches = 1;
-    tm.n_pairs = n_pairs;
-    ctx->timings = tm;
-    return SSYM_OK;
+    return spot_finish(ctx, out, n_pairs);
 }
 
 int32_t dtw_spot_all(ssym_ctx *ctx, const ssym_dict *dict, const ssym_queries *q, const uint32_t *src_idx,
@@ -584,11 +557,7 @@ int32_t dtw_spot_all(ssym_ctx *ctx, const ssym_dict *dict, const ssym_queries *q
                      const double *max_cost, uint32_t *out_count, double *out_cost, uint32_t *out_start, uint32_t *out_end,
                      uint32_t flags, uint32_t step = SSYM_STEP_SYMMETRIC, const char *fn = "ssym_dtw_spot_all")
 {
-    if (!ctx)
-        return SSYM_E_INVALID;
-    int32_t rc = spot_check_step(ctx, fn, step);
-    if (rc == SSYM_OK)
-        rc = spot_check_ctx(ctx, fn);
+    int32_t rc = spot_check_entry(ctx, fn, step);
     if (rc != SSYM_OK)
         return rc;
     rc = check_pair_list(ctx->err, fn, dict, q, src_idx, tgt_idx, n_pairs, index_base);
@@ -604,15 +573,14 @@ int32_t dtw_spot_all(ssym_ctx *ctx, const ssym_dict *dict, const ssym_queries *q
     }
     const SegmentSet &src = dict->set, &tgt = q->set;
     // the pair list, the thresholds and the shape limits: on the host, before any device work
-    std::vector<uint2> pairs(n_pairs);
+    PairList pairs(src_idx, tgt_idx, index_base, n_pairs);
     uint64_t maxFa = 0, maxFb = 0;
     for (uint32_t p = 0; p < n_pairs; ++p) {
         if (max_cost && max_cost[p] != max_cost[p]) {
             ctx->err = std::string(fn) + ": max_cost[" + std::to_string(p) + "] is NaN";
             return SSYM_E_INVALID;
         }
-        pairs[p] = pair_at(src_idx, tgt_idx, index_base, p);
-        const uint32_t s = pairs[p].x, t = pairs[p].y;
+        const uint32_t s = pairs.host[p].x, t = pairs.host[p].y;
         if (s == SSYM_NO_MATCH)
             continue;
         const uint64_t fa = src.h_off[s + 1] - src.h_off[s], fb = tgt.h_off[t + 1] - tgt.h_off[t];
@@ -629,107 +597,47 @@ int32_t dtw_spot_all(ssym_ctx *ctx, const ssym_dict *dict, const ssym_queries *q
         return SSYM_E_UNSUPPORTED;
     }
     SSYM_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-    hipStream_t st = ctx->stream;
-    const bool outDev = (flags & SSYM_OUT_DEVICE) != 0;
-    const size_t K = max_spots, nOut = (size_t)n_pairs * K;
+    const size_t nOut = (size_t)n_pairs * max_spots;
 
     // one profile slot per workgroup, as many workgroups as kSpotAllScratchBytes holds (2 for a 2^24-frame source)
+    const WaveGeom g = wave_geom(ctx, maxFb, src.dim, n_pairs);
     SpotAllArgs a{};
     a.slotFrames = std::max<uint64_t>(maxFa, 1);
     const unsigned grid = (unsigned)std::min<uint64_t>(
-        std::min<uint64_t>(n_pairs, (uint64_t)ctx->num_cus * 8),
-        std::max<uint64_t>(1, kSpotAllScratchBytes / (a.slotFrames * (sizeof(double) + sizeof(uint32_t)))));
+        g.grid, std::max<uint64_t>(1, kSpotAllScratchBytes / (a.slotFrames * (sizeof(double) + sizeof(uint32_t)))));
 
     Blocks bl(ctx);
-    uint2 *dPairs = nullptr;
-    double *dMax = nullptr, *dCost = out_cost;
-    uint32_t *dCount = out_count, *dStart = out_start, *dEnd = out_end;
-    rc = bl.get(&dPairs, n_pairs);
-    if (rc == SSYM_OK && max_cost)
+    SpotOut out(flags, out_cost, nOut, {{out_start, nOut}, {out_end, nOut}, {out_count, n_pairs}});
+    double *dMax = nullptr;
+    if (max_cost)
         rc = bl.get(&dMax, n_pairs);
     if (rc == SSYM_OK)
         rc = bl.get(&a.profD, (size_t)grid * a.slotFrames);
     if (rc == SSYM_OK)
         rc = bl.get(&a.profS, (size_t)grid * a.slotFrames);
-    if (!outDev) {
-        if (rc == SSYM_OK)
-            rc = bl.get(&dCost, nOut);
-        if (rc == SSYM_OK)
-            rc = bl.get(&dStart, 2 * nOut + n_pairs);          // start, end, count: one copy back
-        dEnd = dStart + nOut;
-        dCount = dStart + 2 * nOut;
-    }
+    if (rc == SSYM_OK)
+        rc = out.alloc(bl);
+    if (rc == SSYM_OK)
+        rc = pairs.upload(ctx, bl);
     if (rc != SSYM_OK)
         return rc;
-    SSYM_HIP_CHECK(ctx, hipMemcpyAsync(dPairs, pairs.data(), sizeof(uint2) * n_pairs, hipMemcpyHostToDevice, st));
     if (max_cost)
-        SSYM_HIP_CHECK(ctx, hipMemcpyAsync(dMax, max_cost, sizeof(double) * n_pairs, hipMemcpyHostToDevice, st));
-    a.srcRaw = src.raw;
-    a.srcOff = src.off;
-    a.tgtRaw = tgt.raw;
-    a.tgtOff = tgt.off;
-    a.dim = src.dim;
-    a.squared = ctx->squared;
-    a.pairs = dPairs;
-    a.nTgt = tgt.n;
-    a.nPairs = n_pairs;
-    a.cost = dCost;
-    a.start = dStart;
-    a.end = dEnd;
-    a.fbCap = wave_fb_cap(maxFb);
-    a.ringRows = wave_ring_rows(maxFb);
+        SSYM_HIP_CHECK(ctx, hipMemcpyAsync(dMax, max_cost, sizeof(double) * n_pairs, hipMemcpyHostToDevice, ctx->stream));
+    spot_fill(a, ctx, src, tgt, pairs.dev, n_pairs, g, out.cost, out.words[0].dev, out.words[1].dev);
     a.maxSpots = max_spots;
-    a.count = dCount;
+    a.count = out.words[2].dev;
     a.maxCost = dMax;
-    const int dimr = wave_dimr(src.dim);
-    const size_t lds = spot_lds_bytes(a.fbCap, a.ringRows, dimr, step);
-    SSYM_HIP_CHECK(ctx, hipEventRecord(ctx->ev[0], st));
-    if (step == SSYM_STEP_PACED)
-        rc = wave_launch(ctx,
-                         dimr == 14   ? dtw_paced_kernel<14, true, SpotAllArgs>
-                         : dimr == 16 ? dtw_paced_kernel<16, true, SpotAllArgs>
-                         : dimr == 40 ? dtw_paced_kernel<40, true, SpotAllArgs>
-                                      : dtw_paced_kernel<64, true, SpotAllArgs>,
-                         grid, lds, a);
-    else
-        rc = wave_launch(ctx,
-                         dimr == 14   ? dtw_spot_kernel<14, true, SpotAllArgs>
-                         : dimr == 16 ? dtw_spot_kernel<16, true, SpotAllArgs>
-                         : dimr == 40 ? dtw_spot_kernel<40, true, SpotAllArgs>
-                                      : dtw_spot_kernel<64, true, SpotAllArgs>,
-                         grid, lds, a);
+    rc = launch_spot(ctx, a, g, grid, step);
     if (rc != SSYM_OK)
         return rc;
-    SSYM_HIP_CHECK(ctx, hipEventRecord(ctx->ev[1], st));
-    std::vector<uint32_t> hWords;
-    if (!outDev) {
-        hWords.resize(2 * nOut + n_pairs);
-        SSYM_HIP_CHECK(ctx, hipMemcpyAsync(out_cost, dCost, sizeof(double) * nOut, hipMemcpyDeviceToHost, st));
-        SSYM_HIP_CHECK(ctx, hipMemcpyAsync(hWords.data(), dStart, sizeof(uint32_t) * hWords.size(), hipMemcpyDeviceToHost, st));
-    }
-    SSYM_HIP_CHECK(ctx, hipStreamSynchronize(st));
-    if (!outDev) {
-        std::copy(hWords.begin(), hWords.begin() + nOut, out_start);
-        std::copy(hWords.begin() + nOut, hWords.begin() + 2 * nOut, out_end);
-        std::copy(hWords.begin() + 2 * nOut, hWords.end(), out_count);
-    }
-    ssym_timings tm{};
-    tm.main_ms = tm.total_ms = ev_ms(ctx->ev[0], ctx->ev[1]);
-    tm.main_launches = 1;
-    tm.n_pairs = n_pairs;
-    ctx->timings = tm;
-    return SSYM_OK;
+    return spot_finish(ctx, out, n_pairs);
 }
 
 int32_t spot_queries(ssym_ctx *ctx, const ssym_dict *dict, const ssym_queries *q, uint32_t index_base, uint32_t *out_idx,
                      double *out_cost, uint32_t *out_start, uint32_t *out_end, uint32_t flags,
                      uint32_t step = SSYM_STEP_SYMMETRIC, const char *fn = "ssym_spot_queries")
 {
-    if (!ctx)
-        return SSYM_E_INVALID;
-    int32_t rc = spot_check_step(ctx, fn, step);
-    if (rc == SSYM_OK)
-        rc = spot_check_ctx(ctx, fn);
+    int32_t rc = spot_check_entry(ctx, fn, step);
     if (rc != SSYM_OK)
         return rc;
     rc = check_handles(ctx->err, fn, dict, q);
@@ -756,54 +664,31 @@ int32_t spot_queries(ssym_ctx *ctx, const ssym_dict *dict, const ssym_queries *q
         return rc;
     SSYM_HIP_CHECK(ctx, hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
-    const bool outDev = (flags & SSYM_OUT_DEVICE) != 0;
     const uint32_t nPairs = N * M;
 
+    // every (source, target) into scratch, then the fold into the outputs
     Blocks bl(ctx);
-    double *mCost = nullptr, *dCost = out_cost;
-    uint32_t *mSpan = nullptr, *dIdx = out_idx, *dStart = out_start, *dEnd = out_end;
+    SpotOut out(flags, out_cost, M, {{out_idx, M}, {out_start, M}, {out_end, M}});
+    double *mCost = nullptr;
+    uint32_t *mSpan = nullptr;
     rc = bl.get(&mCost, nPairs);
     if (rc == SSYM_OK)
         rc = bl.get(&mSpan, 2 * (size_t)nPairs);
-    if (!outDev) {
-        if (rc == SSYM_OK)
-            rc = bl.get(&dCost, M);
-        if (rc == SSYM_OK)
-            rc = bl.get(&dIdx, 3 * (size_t)M);
-        dStart = dIdx + M;
-        dEnd = dIdx + 2 * (size_t)M;
-    }
+    if (rc == SSYM_OK)
+        rc = out.alloc(bl);
     if (rc != SSYM_OK)
         return rc;
-    SSYM_HIP_CHECK(ctx, hipEventRecord(ctx->ev[0], st));
-    rc = launch_spot(ctx, src, tgt, nullptr, nPairs, maxFb, mCost, mSpan, mSpan + nPairs, step);
+    const WaveGeom g = wave_geom(ctx, maxFb, src.dim, nPairs);
+    SpotArgs a{};
+    spot_fill(a, ctx, src, tgt, nullptr, nPairs, g, mCost, mSpan, mSpan + nPairs);
+    rc = launch_spot(ctx, a, g, g.grid, step);
     if (rc != SSYM_OK)
         return rc;
-    SSYM_HIP_CHECK(ctx, hipEventRecord(ctx->ev[1], st));
-    spot_fold_kernel<<<(M + 255) / 256, 256, 0, st>>>(mCost, mSpan, mSpan + nPairs, N, M, index_base, dIdx, dCost, dStart,
-                                                      dEnd);
+    spot_fold_kernel<<<(M + 255) / 256, 256, 0, st>>>(mCost, mSpan, mSpan + nPairs, N, M, index_base, out.words[0].dev, out.cost,
+                                                      out.words[1].dev, out.words[2].dev);
     SSYM_HIP_CHECK(ctx, hipGetLastError());
     SSYM_HIP_CHECK(ctx, hipEventRecord(ctx->ev[2], st));
-    std::vector<uint32_t> hWords;
-    if (!outDev) {
-        hWords.resize(3 * (size_t)M);
-        SSYM_HIP_CHECK(ctx, hipMemcpyAsync(out_cost, dCost, sizeof(double) * M, hipMemcpyDeviceToHost, st));
-        SSYM_HIP_CHECK(ctx, hipMemcpyAsync(hWords.data(), dIdx, sizeof(uint32_t) * 3 * M, hipMemcpyDeviceToHost, st));
-    }
-    SSYM_HIP_CHECK(ctx, hipStreamSynchronize(st));
-    if (!outDev) {
-        std::copy(hWords.begin(), hWords.begin() + M, out_idx);
-        std::copy(hWords.begin() + M, hWords.begin() + 2 * (size_t)M, out_start);
-        std::copy(hWords.begin() + 2 * (size_t)M, hWords.end(), out_end);
-    }
-    ssym_timings tm{};
-    tm.main_ms = ev_ms(ctx->ev[0], ctx->ev[1]);
-    tm.reduce_ms = ev_ms(ctx->ev[1], ctx->ev[2]);
-    tm.total_ms = ev_ms(ctx->ev[0], ctx->ev[2]);
-    tm.main_launches = 1;
-    tm.n_pairs = nPairs;
-    ctx->timings = tm;
-    return SSYM_OK;
+    return spot_finish(ctx, out, nPairs, true);
 }
 
 }  // namespace

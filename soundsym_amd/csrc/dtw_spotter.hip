@@ -25,8 +25,8 @@
 
 namespace ssym {
 
-// ssym_dtw_spot's limits (dtw_spot.hip): frames of a target, values per frame; frames a lane may consume (st is u32 and
-// 0xffffffff means none: the dictionary's own limit)
+// Limits (soundsym_amd.h "Watching"; ssym_dtw_spot's for a target, refused by the same check_spot_limits): frames of a
+// target, values per frame; frames a lane may consume (st is u32 and 0xffffffff means none: the dictionary's own limit)
 constexpr uint64_t kSpotterMaxTargetFrames = 4096;
 constexpr uint32_t kSpotterMaxDim = 64;
 constexpr uint64_t kSpotterMaxLaneFrames = 2147483647;           // 2^31 - 1
@@ -421,14 +421,9 @@ int32_t spotter_create(ssym_ctx *ctx, const ssym_queries *q, uint32_t n_lanes, c
         return SSYM_E_INVALID;
     }
     *out = nullptr;
-    if (ctx->metric != SSYM_METRIC_DTW) {
-        ctx->err = std::string(fn) + ": the context's metric is refcos, which has no alignment to spot";
-        return SSYM_E_UNSUPPORTED;
-    }
-    if (ctx->band >= 0) {
-        ctx->err = std::string(fn) + ": a Sakoe-Chiba band has no meaning with a free start; use a context without one";
-        return SSYM_E_UNSUPPORTED;
-    }
+    int32_t rc = check_spot_ctx(ctx, fn);
+    if (rc != SSYM_OK)
+        return rc;
     if (!q || n_lanes == 0) {
         ctx->err = std::string(fn) + ": the queries handle is NULL or n_lanes is 0";
         return SSYM_E_INVALID;
@@ -440,11 +435,9 @@ int32_t spotter_create(ssym_ctx *ctx, const ssym_queries *q, uint32_t n_lanes, c
                 ctx->err = std::string(fn) + ": max_cost[" + std::to_string(t) + "] is NaN";
                 return SSYM_E_INVALID;
             }
-    if ((tgt.n && (uint64_t)tgt.max_frames > kSpotterMaxTargetFrames) || tgt.dim > kSpotterMaxDim) {
-        ctx->err = std::string(fn) + ": a target has more than " + std::to_string(kSpotterMaxTargetFrames) +
-                   " frames, or frames have more than " + std::to_string(kSpotterMaxDim) + " values";
-        return SSYM_E_UNSUPPORTED;
-    }
+    rc = check_spot_limits(ctx, fn, tgt.n ? tgt.max_frames : 0, tgt.dim, kSpotterMaxTargetFrames, kSpotterMaxDim);
+    if (rc != SSYM_OK)
+        return rc;
     if ((uint64_t)n_lanes * tgt.n > 0xfffffffeull) {
         ctx->err = std::string(fn) + ": more than 2^32 - 2 (lane, target) pairs";
         return SSYM_E_UNSUPPORTED;
@@ -459,7 +452,7 @@ int32_t spotter_create(ssym_ctx *ctx, const ssym_queries *q, uint32_t n_lanes, c
     sp->consumed.assign(n_lanes, 0);
     sp->hSteps.resize(n_lanes);
     const size_t nState = (size_t)n_lanes * tgt.total_frames, nP = sp->nPairs;
-    int32_t rc = alloc_n(ctx, &sp->stateD, nState);
+    rc = alloc_n(ctx, &sp->stateD, nState);
     if (rc == SSYM_OK)
         rc = alloc_n(ctx, &sp->stateS, nState);
     if (rc == SSYM_OK)
@@ -632,12 +625,10 @@ int32_t spotter_run(ssym_ctx *ctx, ssym_spotter *sp, const std::vector<const dou
     wa.bestS = ia.bestS;
     wa.profD = profD;
     wa.profS = profS;
-    wa.fbCap = wave_fb_cap(tgt.max_frames);
-    wa.ringRows = wave_ring_rows(tgt.max_frames);
-    const int dimr = wave_dimr(tgt.dim);
-    // hand-off row (12 bytes per target frame, at most 48 KiB) + ring (at most 66 KiB)
-    const size_t lds = (size_t)wa.fbCap * (sizeof(double) + sizeof(uint32_t)) + wave_ring_bytes(wa.ringRows, dimr);
-    const unsigned grid = (unsigned)std::min<uint64_t>(nP, (uint64_t)ctx->num_cus * 8);
+    const WaveGeom g = wave_geom(ctx, tgt.max_frames, tgt.dim, nP);
+    wa.fbCap = g.fbCap;
+    wa.ringRows = g.ringRows;
+    const size_t lds = spot_lds_bytes(g, SSYM_STEP_SYMMETRIC);       // one hand-off row
     const unsigned repGrid = (unsigned)((nP + kRepPairs - 1) / kRepPairs);
 
     ReportArgs ra{};
@@ -676,7 +667,7 @@ int32_t spotter_run(ssym_ctx *ctx, ssym_spotter *sp, const std::vector<const dou
         SSYM_HIP_CHECK(ctx, hipMemcpyAsync(sp->dSteps, sp->hSteps.data(), sizeof(LaneStep) * nL, hipMemcpyHostToDevice, st));
         SSYM_HIP_CHECK(ctx, hipEventRecord(ctx->ev[0], st));
         if (any) {
-            rc = wave_launch(ctx, SSYM_WAVE_KERNEL(dtw_watch_kernel, dimr), grid, lds, wa);
+            rc = wave_launch(ctx, SSYM_WAVE_KERNEL(dtw_watch_kernel, g.dimr), g.grid, lds, wa);
             if (rc != SSYM_OK)
                 return rc;
         }

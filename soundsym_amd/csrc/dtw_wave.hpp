@@ -1,6 +1,7 @@
 // dtw_wave.hpp -- the anti-diagonal wavefront forward pass dtw_align.hip and dtw_spot.hip share (and the lane - 1 move
-// and ring stride dtw_exact.hip shares with them), each piece written once, plus the pair-list checks of their entry
-// points.  Each kernel keeps its own step loop; what is here is what must not differ between them.  (dtw_align_kernel
+// and ring stride dtw_exact.hip shares with them), each piece written once, plus the host side their drivers and
+// dtw_spotter.hip's share: launch geometry, the pair-list checks and upload, and the spot family's refusals, LDS size and
+// output rule.  Each kernel keeps its own step loop; what is here is what must not differ between them.  (dtw_align_kernel
 // still carries the text of wave_load_frame and wave_refill in its body, for the reason given there: change them together.)
 //
 // The pass: one wave per pair, grid-stride over the list.  Lane l owns source row c0 + l of a 64-row chunk and works on
@@ -19,6 +20,8 @@
 #include "ssym_internal.hpp"
 
 #include <algorithm>
+#include <initializer_list>
+#include <utility>
 
 namespace ssym {
 
@@ -130,9 +133,33 @@ inline uint32_t wave_fb_cap(uint64_t maxFb) { return ((uint32_t)std::max<uint64_
 inline uint32_t wave_ring_rows(uint64_t maxFb) { return maxFb <= 64 ? 64 : kWaveRing; }
 inline size_t wave_ring_bytes(uint32_t ringRows, int dimr) { return (size_t)ringRows * wave_ld(dimr) * sizeof(double); }
 
-// the instantiation of kernel template K_ (one wave per workgroup, one argument struct) for wave_dimr's value
-#define SSYM_WAVE_KERNEL(K_, dimr_) \
-    ((dimr_) == 14 ? K_<14> : (dimr_) == 16 ? K_<16> : (dimr_) == 40 ? K_<40> : K_<64>)
+// what every launch of the wavefront derives from (context, longest listed target, dim, pairs).  The caller adds its own
+// LDS terms to ringBytes: dtw_align the code row and the direction matrix, the spot family spot_lds_bytes' hand-off rows
+struct WaveGeom {
+    uint32_t fbCap, ringRows;
+    int dimr;
+    size_t ringBytes;
+    unsigned grid;               // one wave per pair, 8 x CUs at most
+};
+inline WaveGeom wave_geom(const ssym_ctx *ctx, uint64_t maxFb, uint32_t dim, uint64_t n_pairs)
+{
+    WaveGeom g;
+    g.fbCap = wave_fb_cap(maxFb);
+    g.ringRows = wave_ring_rows(maxFb);
+    g.dimr = wave_dimr(dim);
+    g.ringBytes = wave_ring_bytes(g.ringRows, g.dimr);
+    g.grid = (unsigned)std::min<uint64_t>(n_pairs, (uint64_t)ctx->num_cus * 8);
+    return g;
+}
+
+// the instantiation of kernel template K_ (one wave per workgroup, one argument struct) for wave_dimr's value; what
+// follows dimr_ goes behind DIMR in the template's argument list (", ##__VA_ARGS__" is the GNU extension that drops the
+// comma when nothing follows; hipcc is clang and takes it, C++17 has no __VA_OPT__)
+#define SSYM_WAVE_KERNEL(K_, dimr_, ...)                                                                                  \
+    ((dimr_) == 14   ? K_<14, ##__VA_ARGS__>                                                                              \
+     : (dimr_) == 16 ? K_<16, ##__VA_ARGS__>                                                                              \
+     : (dimr_) == 40 ? K_<40, ##__VA_ARGS__>                                                                              \
+                     : K_<64, ##__VA_ARGS__>)
 
 template <class Args>
 inline int32_t wave_launch(ssym_ctx *ctx, void (*kern)(Args), unsigned grid, size_t lds, const Args &a)
@@ -207,5 +234,118 @@ inline uint2 pair_at(const uint32_t *src_idx, const uint32_t *tgt_idx, uint32_t 
 {
     return make_uint2(src_idx[p] == SSYM_NO_MATCH ? SSYM_NO_MATCH : src_idx[p] - index_base, tgt_idx ? tgt_idx[p] : p);
 }
+
+// a checked list as the kernels read it: on the host from the start, in a block of bl once upload has enqueued the copy
+// on ctx's stream (the list outlives the call's synchronisation)
+struct PairList {
+    std::vector<uint2> host;
+    uint2 *dev = nullptr;
+    PairList(const uint32_t *src_idx, const uint32_t *tgt_idx, uint32_t index_base, uint32_t n_pairs) : host(n_pairs)
+    {
+        for (uint32_t p = 0; p < n_pairs; ++p)
+            host[p] = pair_at(src_idx, tgt_idx, index_base, p);
+    }
+    int32_t upload(ssym_ctx *ctx, Blocks &bl)
+    {
+        const int32_t rc = bl.get(&dev, host.size());
+        if (rc != SSYM_OK)
+            return rc;
+        SSYM_HIP_CHECK(ctx, hipMemcpyAsync(dev, host.data(), sizeof(uint2) * host.size(), hipMemcpyHostToDevice, ctx->stream));
+        return SSYM_OK;
+    }
+};
+
+// ---- host: the spot family (dtw_spot.hip, dtw_spotter.hip) --------------------------------------------------------------
+
+// what spotting refuses of a context
+inline int32_t check_spot_ctx(ssym_ctx *ctx, const char *fn)
+{
+    if (ctx->metric != SSYM_METRIC_DTW) {
+        ctx->err = std::string(fn) + ": the context's metric is refcos, which has no alignment to spot";
+        return SSYM_E_UNSUPPORTED;
+    }
+    if (ctx->band >= 0) {
+        ctx->err = std::string(fn) + ": a Sakoe-Chiba band has no meaning with a free start; use a context without one";
+        return SSYM_E_UNSUPPORTED;
+    }
+    return SSYM_OK;
+}
+
+// ... and of the shapes: the longest target that will run against the caller's limit for its step pattern, values per frame
+inline int32_t check_spot_limits(ssym_ctx *ctx, const char *fn, uint64_t maxFb, uint32_t dim, uint64_t maxFrames,
+                                 uint32_t maxDim)
+{
+    if (maxFb > maxFrames || dim > maxDim) {
+        ctx->err = std::string(fn) + ": a target has more than " + std::to_string(maxFrames) +
+                   " frames, or frames have more than " + std::to_string(maxDim) + " values";
+        return SSYM_E_UNSUPPORTED;
+    }
+    return SSYM_OK;
+}
+
+// dynamic LDS of a launch: the hand-off rows (12 bytes per target frame each: one row, at most 48 KiB, or the paced
+// pattern's two, at most 48 KiB as well) + the ring (at most 66 KiB)
+inline size_t spot_lds_bytes(const WaveGeom &g, uint32_t step)
+{
+    const size_t rows = step == SSYM_STEP_PACED ? 2 : 1;
+    return rows * g.fbCap * (sizeof(double) + sizeof(uint32_t)) + g.ringBytes;
+}
+
+// The output rule of the spot drivers: one f64 array and up to three u32 arrays.  Host outputs: the kernel writes device
+// scratch (alloc) -- the f64 array a block of its own, the u32 arrays packed into ONE block in the order given -- and
+// finish enqueues one copy back of each, synchronises and hands the words to the caller's arrays.  SSYM_OUT_DEVICE: the
+// kernel writes the caller's arrays in place and finish only synchronises.  Either way: the call's one synchronisation.
+struct SpotOut {
+    struct Words {
+        uint32_t *out;           // the caller's array
+        size_t n;
+        uint32_t *dev;           // where the kernel writes
+    };
+    bool inPlace;
+    double *outCost, *cost;      // the caller's array, and where the kernel writes
+    size_t nCost;
+    Words words[3];
+    size_t nArrays = 0, nWords = 0;
+
+    SpotOut(uint32_t flags, double *out_cost, size_t n_cost, std::initializer_list<std::pair<uint32_t *, size_t>> list)
+        : inPlace((flags & SSYM_OUT_DEVICE) != 0), outCost(out_cost), cost(out_cost), nCost(n_cost)
+    {
+        for (const auto &w : list) {
+            words[nArrays++] = Words{w.first, w.second, w.first};
+            nWords += w.second;
+        }
+    }
+    int32_t alloc(Blocks &bl)
+    {
+        if (inPlace)
+            return SSYM_OK;
+        uint32_t *block = nullptr;
+        int32_t rc = bl.get(&cost, nCost);
+        if (rc == SSYM_OK)
+            rc = bl.get(&block, nWords);
+        for (size_t i = 0; rc == SSYM_OK && i < nArrays; ++i) {
+            words[i].dev = block;
+            block += words[i].n;
+        }
+        return rc;
+    }
+    int32_t finish(ssym_ctx *ctx)
+    {
+        if (inPlace) {
+            SSYM_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+            return SSYM_OK;
+        }
+        std::vector<uint32_t> host(nWords);
+        SSYM_HIP_CHECK(ctx, hipMemcpyAsync(outCost, cost, sizeof(double) * nCost, hipMemcpyDeviceToHost, ctx->stream));
+        SSYM_HIP_CHECK(ctx, hipMemcpyAsync(host.data(), words[0].dev, sizeof(uint32_t) * nWords, hipMemcpyDeviceToHost, ctx->stream));
+        SSYM_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+        const uint32_t *from = host.data();
+        for (size_t i = 0; i < nArrays; ++i) {
+            std::copy(from, from + words[i].n, words[i].out);
+            from += words[i].n;
+        }
+        return SSYM_OK;
+    }
+};
 
 }  // namespace ssym

@@ -70,6 +70,19 @@ def _spot_all_args(src, max_spots, max_cost):
     return k, mc
 
 
+def _output(device, shape, dtype):
+    """One output array of a call as (array, address): a zeroed numpy array, or with a device number (SSYM_OUT_DEVICE) a
+    torch tensor in that device's memory, float64 or -- for the call's u32 values -- int32.  The tensor has room for at
+    least one row, so it has an address when shape[0] is 0; what is returned is its first shape[0] rows."""
+    if device is None:
+        x = np.zeros(shape, dtype=dtype)
+        return x, x.ctypes.data
+    import torch
+    x = torch.empty((max(shape[0], 1),) + tuple(shape[1:]), dtype=torch.float64 if dtype == np.float64 else torch.int32,
+                    device=torch.device("cuda", device))
+    return x[:shape[0]], x.data_ptr()
+
+
 def _device_words(x, what: str):
     """(pointer, count) of 32-bit words in device memory: a torch CUDA tensor of a 4-byte integer type, or a
     DeviceFrames-style object (data_ptr / numel) whose owner vouches for the content."""
@@ -828,20 +841,50 @@ class Engine:
         memory).  Returns (cost f64 [n], lengths i32 [n], paths i32 [cells * 2], maps i32 [map entries], path_offsets,
         map_offsets); the 32-bit tensors hold the call's u32 values.  maps, lengths and map_offsets are what
         reconstruct_warped takes."""
-        import torch
         src, tgt = _align_indices(src_idx, tgt_idx)
         n = src.size
         p_off, m_off = self.dtw_align_sizes(d, q, src, tgt, index_base)
-        dev = torch.device("cuda", self.device)
-        cost = torch.empty(max(n, 1), dtype=torch.float64, device=dev)
-        length = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
-        path = torch.empty(max(2 * int(p_off[-1]), 1), dtype=torch.int32, device=dev)
-        fmap = torch.empty(max(int(m_off[-1]), 1), dtype=torch.int32, device=dev)
+        (cost, pc), (length, pl), (path, pp), (fmap, pm) = (
+            _output(self.device, (rows,), t) for rows, t in ((n, np.float64), (n, np.uint32), (2 * int(p_off[-1]), np.uint32),
+                                                            (int(m_off[-1]), np.uint32)))
         nat.check(nat.lib().ssym_dtw_align(self.ctx, d.ptr, q.ptr, src.ctypes.data,
-                                           tgt.ctypes.data if tgt is not None else None, n, index_base, cost.data_ptr(),
-                                           length.data_ptr(), p_off.ctypes.data, path.data_ptr(), m_off.ctypes.data,
-                                           fmap.data_ptr(), nat.OUT_DEVICE), self.ctx)
-        return cost[:n], length[:n], path[:2 * int(p_off[-1])], fmap[:int(m_off[-1])], p_off, m_off
+                                           tgt.ctypes.data if tgt is not None else None, n, index_base, pc, pl,
+                                           p_off.ctypes.data, pp, m_off.ctypes.data, pm, nat.OUT_DEVICE), self.ctx)
+        return cost, length, path, fmap, p_off, m_off
+
+    def _dtw_spot(self, d, q, src_idx, tgt_idx, index_base, step, on_device):
+        """dtw_spot and, with on_device, dtw_spot_device.  The argument checks come before self is touched, and the public
+        methods call this through the class: a call with bad arguments fails as ValueError whatever self is."""
+        which = _spot_step(step)
+        src, tgt = _align_indices(src_idx, tgt_idx)
+        n, device = src.size, self.device if on_device else None
+        (cost, pc), (start, ps), (end, pe) = (_output(device, (n,), t) for t in (np.float64, np.uint32, np.uint32))
+        head = (self.ctx, d.ptr, q.ptr, src.ctypes.data, tgt.ctypes.data if tgt is not None else None, n, index_base)
+        tail = (pc, ps, pe, 0 if device is None else nat.OUT_DEVICE)
+        if which == nat.STEP_SYMMETRIC:
+            rc = nat.lib().ssym_dtw_spot(*head, *tail)
+        else:
+            rc = nat.lib().ssym_dtw_spot_step(*head, which, *tail)
+        nat.check(rc, self.ctx)
+        return cost, start, end
+
+    def _dtw_spot_all(self, d, q, src_idx, tgt_idx, index_base, max_spots, max_cost, step, on_device):
+        """dtw_spot_all and, with on_device, dtw_spot_all_device; called as _dtw_spot is."""
+        which = _spot_step(step)
+        src, tgt = _align_indices(src_idx, tgt_idx)
+        k, mc = _spot_all_args(src, max_spots, max_cost)
+        n, device = src.size, self.device if on_device else None
+        (count, pn), (cost, pc), (start, ps), (end, pe) = (
+            _output(device, shape, t) for shape, t in (((n,), np.uint32), ((n, k), np.float64), ((n, k), np.uint32),
+                                                       ((n, k), np.uint32)))
+        head = (self.ctx, d.ptr, q.ptr, src.ctypes.data, tgt.ctypes.data if tgt is not None else None, n, index_base)
+        tail = (k, mc.ctypes.data if mc is not None else None, pn, pc, ps, pe, 0 if device is None else nat.OUT_DEVICE)
+        if which == nat.STEP_SYMMETRIC:
+            rc = nat.lib().ssym_dtw_spot_all(*head, *tail)
+        else:
+            rc = nat.lib().ssym_dtw_spot_all_step(*head, which, *tail)
+        nat.check(rc, self.ctx)
+        return count, cost, start, end
 
     def dtw_spot(self, d: _Handle, q: _Handle, src_idx, tgt_idx=None, index_base: int = 0, step: str = "symmetric"):
         """ssym_dtw_spot (subsequence DTW; dtw engines without a band): for every listed pair (source src_idx[p] -
@@ -851,42 +894,12 @@ class Engine:
         normalised by any length.  step="paced": ssym_dtw_spot_step with SSYM_STEP_PACED ("Paced spotting": every path
         has as many cells as the target has frames, so cost / frames is a mean per-frame distance); "symmetric" is
         ssym_dtw_spot itself."""
-        which = _spot_step(step)
-        src, tgt = _align_indices(src_idx, tgt_idx)
-        n = src.size
-        cost = np.zeros(n, dtype=np.float64)
-        start = np.zeros(n, dtype=np.uint32)
-        end = np.zeros(n, dtype=np.uint32)
-        tp = tgt.ctypes.data if tgt is not None else None
-        if which == nat.STEP_SYMMETRIC:
-            rc = nat.lib().ssym_dtw_spot(self.ctx, d.ptr, q.ptr, src.ctypes.data, tp, n, index_base, cost.ctypes.data,
-                                         start.ctypes.data, end.ctypes.data, 0)
-        else:
-            rc = nat.lib().ssym_dtw_spot_step(self.ctx, d.ptr, q.ptr, src.ctypes.data, tp, n, index_base, which,
-                                              cost.ctypes.data, start.ctypes.data, end.ctypes.data, 0)
-        nat.check(rc, self.ctx)
-        return cost, start, end
+        return Engine._dtw_spot(self, d, q, src_idx, tgt_idx, index_base, step, on_device=False)
 
     def dtw_spot_device(self, d: _Handle, q: _Handle, src_idx, tgt_idx=None, index_base: int = 0, step: str = "symmetric"):
         """ssym_dtw_spot with SSYM_OUT_DEVICE: (cost f64 [n], start i32 [n], end i32 [n]) as torch tensors in device
         memory (torch only owns the memory; the 32-bit tensors hold the call's u32 values).  step as for dtw_spot."""
-        which = _spot_step(step)
-        import torch
-        src, tgt = _align_indices(src_idx, tgt_idx)
-        n = src.size
-        dev = torch.device("cuda", self.device)
-        cost = torch.empty(max(n, 1), dtype=torch.float64, device=dev)
-        start = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
-        end = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
-        tp = tgt.ctypes.data if tgt is not None else None
-        if which == nat.STEP_SYMMETRIC:
-            rc = nat.lib().ssym_dtw_spot(self.ctx, d.ptr, q.ptr, src.ctypes.data, tp, n, index_base, cost.data_ptr(),
-                                         start.data_ptr(), end.data_ptr(), nat.OUT_DEVICE)
-        else:
-            rc = nat.lib().ssym_dtw_spot_step(self.ctx, d.ptr, q.ptr, src.ctypes.data, tp, n, index_base, which,
-                                              cost.data_ptr(), start.data_ptr(), end.data_ptr(), nat.OUT_DEVICE)
-        nat.check(rc, self.ctx)
-        return cost[:n], start[:n], end[:n]
+        return Engine._dtw_spot(self, d, q, src_idx, tgt_idx, index_base, step, on_device=True)
 
     def dtw_spot_all(self, d: _Handle, q: _Handle, src_idx, tgt_idx=None, index_base: int = 0, max_spots: int = 8,
                      max_cost=None, step: str = "symmetric"):
@@ -896,48 +909,14 @@ class Engine:
         [n, K], start uint32 [n, K], end uint32 [n, K]); slots from count[p] on hold +inf and NO_MATCH.  step="paced":
         ssym_dtw_spot_all_step with SSYM_STEP_PACED (costs and max_cost stay sums); "symmetric" is ssym_dtw_spot_all
         itself."""
-        which = _spot_step(step)
-        src, tgt = _align_indices(src_idx, tgt_idx)
-        k, mc = _spot_all_args(src, max_spots, max_cost)
-        n = src.size
-        count = np.zeros(n, dtype=np.uint32)
-        cost = np.zeros((n, k), dtype=np.float64)
-        start = np.zeros((n, k), dtype=np.uint32)
-        end = np.zeros((n, k), dtype=np.uint32)
-        head = (self.ctx, d.ptr, q.ptr, src.ctypes.data, tgt.ctypes.data if tgt is not None else None, n, index_base)
-        tail = (k, mc.ctypes.data if mc is not None else None, count.ctypes.data, cost.ctypes.data, start.ctypes.data,
-                end.ctypes.data, 0)
-        if which == nat.STEP_SYMMETRIC:
-            rc = nat.lib().ssym_dtw_spot_all(*head, *tail)
-        else:
-            rc = nat.lib().ssym_dtw_spot_all_step(*head, which, *tail)
-        nat.check(rc, self.ctx)
-        return count, cost, start, end
+        return Engine._dtw_spot_all(self, d, q, src_idx, tgt_idx, index_base, max_spots, max_cost, step, on_device=False)
 
     def dtw_spot_all_device(self, d: _Handle, q: _Handle, src_idx, tgt_idx=None, index_base: int = 0, max_spots: int = 8,
                             max_cost=None, step: str = "symmetric"):
         """ssym_dtw_spot_all with SSYM_OUT_DEVICE: (count i32 [n], cost f64 [n, K], start i32 [n, K], end i32 [n, K]) as
         torch tensors in device memory (torch only owns the memory; the 32-bit tensors hold the call's u32 values).  step as
         for dtw_spot_all."""
-        which = _spot_step(step)
-        src, tgt = _align_indices(src_idx, tgt_idx)
-        k, mc = _spot_all_args(src, max_spots, max_cost)
-        import torch
-        n = src.size
-        dev = torch.device("cuda", self.device)
-        count = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
-        cost = torch.empty((max(n, 1), k), dtype=torch.float64, device=dev)
-        start = torch.empty((max(n, 1), k), dtype=torch.int32, device=dev)
-        end = torch.empty((max(n, 1), k), dtype=torch.int32, device=dev)
-        head = (self.ctx, d.ptr, q.ptr, src.ctypes.data, tgt.ctypes.data if tgt is not None else None, n, index_base)
-        tail = (k, mc.ctypes.data if mc is not None else None, count.data_ptr(), cost.data_ptr(), start.data_ptr(),
-                end.data_ptr(), nat.OUT_DEVICE)
-        if which == nat.STEP_SYMMETRIC:
-            rc = nat.lib().ssym_dtw_spot_all(*head, *tail)
-        else:
-            rc = nat.lib().ssym_dtw_spot_all_step(*head, which, *tail)
-        nat.check(rc, self.ctx)
-        return count[:n], cost[:n], start[:n], end[:n]
+        return Engine._dtw_spot_all(self, d, q, src_idx, tgt_idx, index_base, max_spots, max_cost, step, on_device=True)
 
     def spot_queries(self, d: _Handle, q: _Handle, index_base: int = 0, step: str = "symmetric"):
         """ssym_spot_queries: every dictionary segment spotted against every target, then the first least cost per
