@@ -496,6 +496,11 @@ int32_t launch_dtw_filter(ssym_ctx *ctx, const SegmentSet &src, const SegmentSet
         ctx->err = "dtw filter: segment set not padded for the filter kernel";
         return SSYM_E_UNSUPPORTED;
     }
+    // the kernel addresses a wave's hand-off row as a buffer: 32-bit byte offsets, a signed extent in the descriptor
+    if (((size_t)tgt.frames_pad + 3) / 4 * 1024 >= ((size_t)1 << 31)) {
+        ctx->err = "dtw filter: targets too long for the hand-off rows";
+        return SSYM_E_UNSUPPORTED;
+    }
     // Early abandoning: the work of a pruned task is about the area where D <= threshold, counted in whole
     // row passes x columns, so lower passes waste less: with 32-row passes the headline grid takes 3.1 ms
     // instead of 4.6.  But a task that cannot be cut short pays two more hand-offs per 128 rows (+17 % on

@@ -33,14 +33,27 @@
 //   * a wave keeps 16*NT rows of the column in registers; longer sources are processed in row-block
 //     PASSES by the same wave: pass p sweeps all columns for rows [p*16*NT, (p+1)*16*NT) and leaves
 //     the bottom row of its block, D(last row, j), in a per-wave hand-off row in global memory
-//     (1 KB per four columns, L2 / Infinity-Cache resident because the grid is
-//     persistent); pass p+1 reads it back as its top boundary.  Waves never synchronise with each
+//     (1 KB per four columns, column-major: 256 contiguous bytes per column, L2 / Infinity-Cache resident because the
+//     grid is persistent); pass p+1 reads it back as its top boundary.  Waves never synchronise with each
 //     other -- a first version that pipelined row blocks across waves with one workgroup barrier
 //     per column spent half of its wave-cycles waiting (profiles/);
 //   * target records (group-major, 1 KB per MFMA operand plane per column) reach the wave through a
-//     per-wave LDS ring filled by global_load_lds DMA three columns ahead of use, the hand-off row
-//     four columns per 16-byte access (one store and one DMA per FOUR columns): loads in flight hold no registers (the kernel sits at the 256-VGPR limit of two
-//     waves per SIMD) and s_waitcnt vmcnt(6) at the top of a column never waits for a young load;
+//     per-wave LDS ring filled by global_load_lds DMA three columns ahead of use, the hand-off row by one 4-byte store per
+//     column and one 16-byte DMA per FOUR columns: loads in flight hold no registers (the kernel sits at the 256-VGPR
+//     limit of two waves per SIMD).  The wait at the top of a column, s_waitcnt vmcnt(2 KU), counts the DMAs of the two
+//     columns staged last; the hand-off stores (one per column in every pass but the last) and the hand-off DMA are
+//     younger operations it does not count, so in those passes it also waits for up to three operations more -- the
+//     DMAs of the column staged two columns ago and the store before them: a lead of about two columns where the last
+//     pass has three.  More operations in flight only make the wait stricter, never too lenient; the shorter lead is
+//     inside the measured -1.2 % below;
+//   * the column loop's bookkeeping stays off the VALU: the staging DMAs take (the task's group base + the column's scalar
+//     offset) in SGPRs and the lane's constant offset in one VGPR, the hand-off row is a buffer (descriptor + scalar byte
+//     offset + constant lane offset) whose stores read a bottom from the register the column array ends in, a pass
+//     without a row above it fills its top buffers with +inf once instead of selecting per column, and column 0 starts
+//     from prevTop.  Per four columns 5 vector instructions beside the cells and MFMAs are left (the address of the top
+//     read, the last-pass test), where there were 19 -- 64-bit vector address arithmetic, selects, packing moves for a
+//     16-byte store (LAB.md 5.1): -1.2 % on the headline, 3.25 -> 3.19 VALU instructions and 17.47 -> 17.18 elapsed
+//     SIMD cycles per wave-cell (floor 3.125 and 17.0);
 //   * measured on MI355X (rocprofv3 PMC): plain VALU instructions occupy the SIMD for 4 cycles,
 //     v_sqrt_f32 for 8, whatever the occupancy -- 16 cycles per cell is the floor of this
 //     recurrence, and the kernel is VALU-bound, not MFMA- or HBM-bound.  Ablations (tools/
@@ -166,6 +179,13 @@ __device__ __forceinline__ float dp_column(const half8 (&A)[NT][KU], const half8
 }
 
 constexpr int kFilterWavesPerBlock = 4;
+
+// Column addressing: every global address of the column loop is (a wave-uniform base in scalar registers) + (the lane's
+// constant 16-byte offset) + (an instruction offset).  The base is made opaque so that it stays scalar: left alone, the
+// optimiser folds the lane offset into it and re-forms a 64-bit VECTOR address per access (a v_mad_i64_i32 per staged
+// column, a v_lshl_add_u64 per hand-off access).  (Macros, as in dtw_filter_sp_kernel.hpp: the constraints are device-only.)
+#define SSYM_FILTER_SBASE(P_) asm volatile("" : "+s"(P_))
+#define SSYM_FILTER_LANEOFF(V_) asm volatile("" : "+v"(V_))
 #ifndef SSYM_PRUNE_EVERY
 #define SSYM_PRUNE_EVERY 8
 #endif
@@ -229,11 +249,15 @@ __global__ __launch_bounds__(64 * kFilterWavesPerBlock, OCC) void dtw_filter_ker
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int col = lane & 31;         // output column: target 32*tg + col
     const int half = lane >> 5;        // operand role: K half; output role: source 2*sp + half
-    // this wave's hand-off row, [ceil(tgtFramesPad / 4)][64 lanes][4 columns] floats: one 16-byte
-    // access per lane moves FOUR columns (a store and a DMA per column cost ~6 % of the kernel)
+    // this wave's hand-off row, [ceil(tgtFramesPad / 4)][4 columns][64 lanes] floats: a column is stored as 256 contiguous
+    // bytes, one 16-byte DMA per lane brings FOUR columns back (a DMA per column cost several % of the kernel)
     const size_t handGroups = ((size_t)tgtFramesPad + 3) / 4;
     char *const handRow = reinterpret_cast<char *>(handoff + ((size_t)blockIdx.x * kFilterWavesPerBlock + wave) * handGroups * 256);
-    const uint32_t laneOff16 = lane * 16;
+    uint32_t laneOff16 = lane * 16;
+    // the hand-off row as a buffer: its accesses are (descriptor, scalar byte offset of the column group, the lane's constant
+    // offset) -- no address arithmetic on the VALU.  (The descriptor's range check covers the lane offset, not the scalar
+    // one: what keeps an access inside the row are the clamps, gg <= (nCols - 1) >> 2 and j < nCols <= tgtFramesPad.)
+    const __amdgpu_buffer_rsrc_t handBuf = __builtin_amdgcn_make_buffer_rsrc(handRow, 0, (int)(handGroups * 1024), 0x00020000);
     // OCC >= 3 is only instantiated for single-pass shapes: no hand-off traffic is in flight, so the waits
     // below count column groups of exactly KU DMAs
     constexpr int kFilterRing = filter_ring(OCC);
@@ -296,7 +320,7 @@ __global__ __launch_bounds__(64 * kFilterWavesPerBlock, OCC) void dtw_filter_ker
         }
         nCols = __builtin_amdgcn_readfirstlane(nCols);
         r0min = __builtin_amdgcn_readfirstlane(r0min);
-        // (a source that begins exactly on a pass boundary needs nothing of the pass above: diagCol0 starts it)
+        // (a source that begins exactly on a pass boundary needs nothing of the pass above: prevTop starts it, at D(rowBase-1, -1) = 0)
         const int firstPass = min(max(r0min - rowOrigin, 0) / BR, nPasses - 1);
 
         float res = INF;
@@ -334,8 +358,10 @@ __global__ __launch_bounds__(64 * kFilterWavesPerBlock, OCC) void dtw_filter_ker
                 char *slot = myRing + (c & (kFilterRing - 1)) * kFilterSlotBytes;
                 // one LDS base (M0) per column; the instruction offset moves the global and the LDS
                 // address together, which the group-major record layout is made for
-                const char *gb = tgtGroup + (size_t)cc * (kTgtFrameHalfs * 2);       // wave-uniform
+                const char *gb = tgtGroup + (size_t)(unsigned)cc * (kTgtFrameHalfs * 2);       // wave-uniform, kept scalar
                 static_assert(KU == 2 || KU == 3, "two or three operand planes per column");
+                SSYM_FILTER_SBASE(gb);
+                SSYM_FILTER_LANEOFF(laneOff16);
                 const __attribute__((address_space(1))) void *gp =
                     (const __attribute__((address_space(1))) void *)(gb + laneOff16);
                 __attribute__((address_space(3))) void *lp = (__attribute__((address_space(3))) void *)slot;
@@ -344,20 +370,19 @@ __global__ __launch_bounds__(64 * kFilterWavesPerBlock, OCC) void dtw_filter_ker
                 if (KU == 3)
                     __builtin_amdgcn_global_load_lds(gp, lp, 16, 2048, 0);
             };
-            // hand-off values of column group g (4 columns) -> top buffer g & 1
+            // hand-off values of column group g (4 columns x 64 lanes, as stored) -> top buffer g & 1
             auto stageTop = [&](int g) {
                 const int gg = min(g, (nCols - 1) >> 2);
-                __builtin_amdgcn_global_load_lds(
-                    (const __attribute__((address_space(1))) void *)(handRow + (size_t)gg * 1024 + laneOff16),
-                    (__attribute__((address_space(3))) void *)(myTop + (g & 1) * 1024), 16, 0, 0);
+                __builtin_amdgcn_raw_ptr_buffer_load_lds(handBuf, (__attribute__((address_space(3))) void *)(myTop + (g & 1) * 1024),
+                                                         16, laneOff16, gg * 1024, 0, 0);
             };
             auto fetch = [&](int c, half8 (&B)[KU], float &top) {
                 const char *slot = myRing + (c & (kFilterRing - 1)) * kFilterSlotBytes;
 #pragma unroll
                 for (int m = 0; m < KU; ++m)
                     B[m] = *reinterpret_cast<const half8 *>(slot + m * 1024 + lane * 16);
-                // read unconditionally (no branch, no wait at a block end); unused when !haveTop
-                top = *reinterpret_cast<const float *>(myTop + ((c >> 2) & 1) * 1024 + lane * 16 + (c & 3) * 4);
+                // read unconditionally (no branch, no wait at a block end); +inf when !haveTop (filled once per pass)
+                top = *reinterpret_cast<const float *>(myTop + ((c >> 2) & 1) * 1024 + (c & 3) * 256 + lane * 4);
             };
             // A operands of this pass: the pad rows above a source carry |a|^2 = +inf
             half8 A[NT][KU];
@@ -385,8 +410,8 @@ __global__ __launch_bounds__(64 * kFilterWavesPerBlock, OCC) void dtw_filter_ker
                 L0[i] = (rowBase + i == r0 - 1) ? 0.0f : INF;
                 L1[i] = L0[i];
             }
-            const float diagCol0 = (rowBase == r0) ? 0.0f : INF;   // D(rowBase-1, -1)
-            float prevTop = INF;                                    // D(rowBase-1, j-1)
+            // D(rowBase-1, j-1): D(rowBase-1, -1) before column 0, which so needs no case of its own
+            float prevTop = (rowBase == r0) ? 0.0f : INF;
 
             // B operands of the current and the next column swap roles every column (no copies)
             half8 B0[KU], B1[KU];
@@ -395,10 +420,17 @@ __global__ __launch_bounds__(64 * kFilterWavesPerBlock, OCC) void dtw_filter_ker
             // (a group is KU or KU + 1 DMAs; the A loads are older): column 0 is in its slot
             __builtin_amdgcn_s_waitcnt(kWaitFirst);
             asm volatile("" ::: "memory");
+            // a pass without a row above it reads +inf as its top values: both top buffers are filled once here (the wait
+            // above has landed every hand-off DMA an earlier pass of this wave left in flight), and the column loop reads
+            // `up` without a select.  (PRUNE keeps its select -- the row above may end early -- and needs no fill.)
+            if (!PRUNE && !haveTop) {
+                typedef float f32x4 __attribute__((ext_vector_type(4)));
+                *reinterpret_cast<f32x4 *>(myTop + lane * 16) = f32x4{INF, INF, INF, INF};
+                *reinterpret_cast<f32x4 *>(myTop + 1024 + lane * 16) = f32x4{INF, INF, INF, INF};
+            }
             fetch(0, B0, topN);
             f32x16 acc = mfma_tile<KU>(A[0], B0);
 
-            float bq[4] = {INF, INF, INF, INF};                     // bottoms of the current group of 4 columns
             float runBot = INF;                                     // PRUNE: min of this pass's bottoms so far
             bool passOver = false;                                  // PRUNE: nothing at or below a threshold is left in this pass
             int lastCol = nCols - 1;
@@ -410,8 +442,8 @@ __global__ __launch_bounds__(64 * kFilterWavesPerBlock, OCC) void dtw_filter_ker
                     const int j = j0 + q;
                     if (j < nCols) {                                // wave-uniform
                         // (PRUNE: the previous pass may have stopped early; beyond its last column nothing enters from above)
-                        const float up = (haveTop && (!PRUNE || j <= lastTop)) ? topN : INF;
-                        const float diag = (j == 0) ? diagCol0 : prevTop;
+                        const float up = (!PRUNE || (haveTop && j <= lastTop)) ? topN : INF;
+                        const float diag = prevTop;
                         prevTop = up;
                         // column j+1 was staged kFilterRing - 1 columns ago; at least the two
                         // groups after it (>= 2 KU DMAs) are younger, so vmcnt(2 KU) covers it -- and the
@@ -432,14 +464,11 @@ __global__ __launch_bounds__(64 * kFilterWavesPerBlock, OCC) void dtw_filter_ker
                             bottom = dp_column<NT, SQ, KU, SKIP0>(A, B0, B1, acc, up, diag, L0, L1, skip0);
                         else
                             bottom = dp_column<NT, SQ, KU, SKIP0>(A, B1, B0, acc, up, diag, L1, L0, skip0);
-                        bq[q] = bottom;
                         if (!lastPass) {
 #ifndef SSYM_ABL_NOHAND
-                            if (q == 3 || j == nCols - 1) {         // top boundary of the next pass, 4 columns at a time
-                                typedef float f32x4 __attribute__((ext_vector_type(4)));
-                                *reinterpret_cast<f32x4 *>(handRow + (size_t)(j >> 2) * 1024 + laneOff16) =
-                                    f32x4{bq[0], bq[1], bq[2], bq[3]};
-                            }
+                            // top boundary of the next pass: a column's bottoms are 256 contiguous bytes, stored straight
+                            // from the register the column array ends in
+                            __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(bottom), handBuf, lane * 4, (j >> 2) * 1024 + q * 256, 0);
 #else
                             res = (j == fb_m1 - 1) ? bottom : res;
 #endif
@@ -481,5 +510,8 @@ __global__ __launch_bounds__(64 * kFilterWavesPerBlock, OCC) void dtw_filter_ker
     if (PRUNE && colCtr && lane == 0)
         atomicAdd(colCtr, (unsigned long long)colSteps * BR);
 }
+
+#undef SSYM_FILTER_SBASE
+#undef SSYM_FILTER_LANEOFF
 
 }  // namespace ssym
