@@ -152,6 +152,12 @@ extern "C" {
                                   tgt_idx: *const u32, n_pairs: u32, index_base: u32, step: u32, max_spots: u32,
                                   max_cost: *const f64, out_count: *mut u32, out_cost: *mut f64, out_start: *mut u32,
                                   out_end: *mut u32, flags: u32) -> i32;
+    // ssym_dtw_align with a step pattern: SSYM_STEP_PACED gives the path of the paced pattern between pinned ends (one cell
+    // per target frame: out_len = Fb, or 0 without a finite cost); targets of at most 2048, sources of at most 4096 frames
+    pub fn ssym_dtw_align_step(ctx: *mut SsymCtx, dict: *const SsymDict, q: *const SsymQueries, src_idx: *const u32,
+                               tgt_idx: *const u32, n_pairs: u32, index_base: u32, step: u32, out_cost: *mut f64,
+                               out_len: *mut u32, path_offsets: *const u64, out_path: *mut u32, map_offsets: *const u64,
+                               out_map: *mut u32, flags: u32) -> i32;
 
     // source-sharded runs, exchange done by the caller (device pointers): filter / all-reduce(MIN) / finish / merge
     pub fn ssym_match_begin(ctx: *mut SsymCtx, dict: *const SsymDict, q: *const SsymQueries, distance: *const f64,

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """examples/spot.py -- a reconstruction from recordings that were never cut.
 
-    python examples/spot.py -s TARGET.wav -d DICT.wav|DIR -o OUT.wav [--search 0] [--depth 5] [--threshold 4] [--seed 0]
+    python examples/spot.py -s TARGET.wav -d DICT.wav|DIR -o OUT.wav [--paced] [--search 0] [--depth 5] [--threshold 4] [--seed 0]
 
 The target is cut by a Partitioner as examples/warp.py cuts it (trained on the first dictionary recording); the dictionary
 recordings stay whole.  Every target segment is located inside the recordings by subsequence DTW
@@ -9,6 +9,11 @@ recordings stay whole.  Every target segment is located inside the recordings by
 its target's timing (SoundDictionary.warp with the given indices: ssym_dtw_align and ssym_reconstruct_warped, or
 ssym_reconstruct_wsola with --search N).  The recording, span and cost of every target segment are printed; the cost is
 a sum along the path, not normalised by any length.
+
+--paced: the whole flow under the paced step pattern (step="paced": ssym_spot_queries_step, ssym_dtw_align_step) -- every
+target frame takes one source frame, at most one source frame in a row is skipped or repeated.  The span of a segment then
+has about half to twice its frames, the alignment of the cut span has the cost the spot reported, and cost / frames is a
+mean per-frame distance: it is printed per segment, and its mean over the segments at the end.
 """
 import argparse
 import os
@@ -27,6 +32,7 @@ def main(argv=None):
     ap.add_argument("-s", required=True, help="target recording")
     ap.add_argument("-d", required=True, help="dictionary recording, or a directory of recordings")
     ap.add_argument("-o", required=True, help="output path of the reconstruction")
+    ap.add_argument("--paced", action="store_true", help="spot, align and warp under the paced step pattern")
     ap.add_argument("--search", type=int, default=0, help="WSOLA search width in samples (0: plain overlap-add)")
     ap.add_argument("--depth", type=int, default=5)
     ap.add_argument("--threshold", type=int, default=4)
@@ -46,16 +52,21 @@ def main(argv=None):
     pieces = SoundDictionary.from_segments(target, partitioner.partition_other(target), engine=engine)
     targets = [s for s in pieces.sounds if s.num_frames() > 0]
 
-    spots = dictionary.spot(targets)
+    step = {"step": "paced"} if args.paced else {}
+    spots = dictionary.spot(targets, **step)
     for t, sp in enumerate(spots):
         if not sp:
             print(f"segment {t:4d} ({targets[t].num_frames():3d} frames): no spot")
             continue
         name = dictionary.sounds[sp.source_index].name or str(sp.source_index)
+        per_frame = f", per frame {sp.cost_per_frame:.6g}" if args.paced else ""
         print(f"segment {t:4d} ({targets[t].num_frames():3d} frames): {name} frames {sp.start_frame}...{sp.end_frame} "
-              f"({sp.num_frames()} frames), cost {sp.cost:.6g}")
+              f"({sp.num_frames()} frames), cost {sp.cost:.6g}{per_frame}")
     found = dictionary.cut(spots)
-    samples, pcm = found.warp(targets, indices=np.arange(len(targets)), want_pcm32=True, search=args.search)
+    samples, pcm = found.warp(targets, indices=np.arange(len(targets)), want_pcm32=True, search=args.search, **step)
+    if args.paced:
+        means = [sp.cost_per_frame for sp in spots if sp]
+        print(f"mean cost_per_frame over {len(means)} spotted segments: {np.mean(means) if means else float('nan'):.6g}")
     write_wav32(args.o, sample_rate=target.sample_rate(), pcm=pcm)
     print(f"{len(dictionary.sounds)} recordings, {len(targets)} target segments, {samples.size} samples -> {args.o}")
     return samples

@@ -250,7 +250,10 @@ class SoundDictionary {
         std::vector<uint32_t> frame_map;
         uint32_t source_index;
     };
-    std::vector<Alignment> align(const std::vector<ArcSound> &targets, const std::vector<uint32_t> &indices) const
+    // step: SSYM_STEP_SYMMETRIC (ssym_dtw_align) or SSYM_STEP_PACED (ssym_dtw_align_step; soundsym_amd.h "Paced
+    // alignment": one cell per target frame, the alignment of a span a paced spot found)
+    std::vector<Alignment> align(const std::vector<ArcSound> &targets, const std::vector<uint32_t> &indices,
+                                 uint32_t step = SSYM_STEP_SYMMETRIC) const
     {
         if (sounds.empty())
             throw EmptyDictionary();
@@ -269,8 +272,11 @@ class SoundDictionary {
         if (rc == SSYM_OK) {
             path.resize(2 * poff[n]);
             map.resize(moff[n]);
-            rc = ssym_dtw_align(ctx_->get(), resident(), q, indices.data(), nullptr, n, 0, cost.data(), len.data(),
-                                poff.data(), path.data(), moff.data(), map.data(), 0);
+            rc = step == SSYM_STEP_SYMMETRIC
+                     ? ssym_dtw_align(ctx_->get(), resident(), q, indices.data(), nullptr, n, 0, cost.data(), len.data(),
+                                      poff.data(), path.data(), moff.data(), map.data(), 0)
+                     : ssym_dtw_align_step(ctx_->get(), resident(), q, indices.data(), nullptr, n, 0, step, cost.data(),
+                                           len.data(), poff.data(), path.data(), moff.data(), map.data(), 0);
         }
         ssym_queries_destroy(ctx_->get(), q);
         ctx_->check(rc);

@@ -412,6 +412,43 @@ SSYM_API int32_t ssym_dtw_spot_all_step(ssym_ctx *ctx, const ssym_dict *dict, co
                                         uint32_t *out_count, double *out_cost, uint32_t *out_start, uint32_t *out_end,
                                         uint32_t flags);
 
+/* Paced alignment (DESIGN.md section 2 "Paced alignment" and section 5.19): ssym_dtw_align with a step pattern.
+ * SSYM_STEP_SYMMETRIC is ssym_dtw_align itself: one host path, the same kernel, the same bits.  SSYM_STEP_PACED is the path
+ * of the paced pattern above between pinned ends -- the alignment that goes with a paced spot: cut the span out of the
+ * recording, align it with the target under the same pattern, warp along the map.  c, the squared option and the
+ * arithmetic are those of "Paced spotting" (f64, k ascending, every sub, mul, add and sqrt rounded separately, no
+ * contraction); i is a source frame 0 ... Fa - 1, j a target frame 0 ... Fb - 1:
+ *   shape   : Fa = 0, Fb = 0, SSYM_NO_MATCH, or Fa outside floor((Fb-1)/2) + 1 ... 2 Fb - 1  ->  cost +inf, L = 0, decided
+ *             before the recurrence
+ *   N(0,0) = c(0,0);  N(i,0) = +inf for i >= 1;  H(i,0) = +inf
+ *   E(i,j) = N(i,j); if H(i,j) < N(i,j): H(i,j)                       (strict <: a tie keeps N)
+ *   j >= 1:  P = E(i-1,j-1); if E(i-2,j-1) < P: E(i-2,j-1)             (strict <; outside the matrix = +inf)
+ *            N(i,j) = c(i,j) + P;   H(i,j) = c(i,j) + N(i,j-1)
+ *   cost    = E(Fa-1,Fb-1);  L = Fb if the cost is finite, else 0 (no path, no map, slots unwritten)
+ *   backward: at (Fa-1,Fb-1) the state is H if H < N there, else N.
+ *             state H at (i,j): the cell before is (i, j-1), in state N.
+ *             state N at (i,j): the cell before is (i-2,j-1) if E(i-2,j-1) < E(i-1,j-1), else (i-1,j-1); its state is H
+ *             if H < N there, else N.
+ *   path[j] = (i_j, j);  map[j] = i_j
+ * So map[0] = 0 and map[Fb-1] = Fa - 1, every map[j+1] - map[j] is 0, 1 or 2 and never 0 twice in a row; acc = c(p_0),
+ * acc = c(p_j) + acc along the path reproduces cost bit for bit; cost is the least such sum over all admissible pinned
+ * paths; and for a span [start, end] that ssym_dtw_spot_step or ssym_dtw_spot_all_step reports under SSYM_STEP_PACED, the
+ * cost of (source frames start ... end, target) has that spot's cost bits.  Path and map are the same thing here (one
+ * source frame per target frame), and the map is what ssym_reconstruct_warped and ssym_reconstruct_wsola take.  Features
+ * that are not finite: the strict < comparisons above decide over the whole matrix.  A value that is not finite in a
+ * target frame or in the first or last source frame is on every path, and a NaN in any source frame spreads down the
+ * diagonals: the cost is NaN or +inf and L = 0.  A source frame in between whose local costs are +inf is stepped over
+ * where the pattern allows a skip, as paced spotting finds spans behind such a frame.  No read leaves its buffer.
+ * Parameters, pair lists, SSYM_NO_MATCH, flags, error codes, n_pairs = 0 and outputs unwritten on refusal are
+ * ssym_dtw_align's.  A paced pair needs room for Fb cells and Fb map entries; ssym_dtw_align_sizes leaves at least that.
+ * An unknown step: SSYM_E_INVALID.  Limits with SSYM_STEP_PACED: targets of at most 2048 frames (two hand-off rows take 16
+ * bytes of LDS per target frame), sources of at most 4096 frames, dim <= 64; beyond them, on a refcos context and on a
+ * context with a band (the pattern bounds the slope itself): SSYM_E_UNSUPPORTED before any device work. */
+SSYM_API int32_t ssym_dtw_align_step(ssym_ctx *ctx, const ssym_dict *dict, const ssym_queries *q, const uint32_t *src_idx,
+                                     const uint32_t *tgt_idx, uint32_t n_pairs, uint32_t index_base, uint32_t step,
+                                     double *out_cost, uint32_t *out_len, const uint64_t *path_offsets, uint32_t *out_path,
+                                     const uint64_t *map_offsets, uint32_t *out_map, uint32_t flags);
+
 /* Source-sharded multi-GPU, dtw metric: the one real exchange the path has.  Each rank's filter gives,
  * per target, an upper bound on the best key in ITS shard; a rank whose shard does not hold a
  * target's neighbour would otherwise re-score ~10^2 of its own pairs per target for nothing.

@@ -61,6 +61,7 @@ ABI_SYMBOLS = [
     "ssym_dtw_align_sizes", "ssym_dtw_align",
     "ssym_dtw_spot", "ssym_spot_queries", "ssym_dtw_spot_all",
     "ssym_dtw_spot_step", "ssym_spot_queries_step", "ssym_dtw_spot_all_step",
+    "ssym_dtw_align_step",
     "ssym_reconstruct_warped", "ssym_reconstruct_wsola",
 ]
 COMM_ID_BYTES = 128        # SSYM_COMM_ID_BYTES
@@ -251,6 +252,8 @@ def lib() -> ctypes.CDLL:
     L.ssym_dtw_align_sizes.argtypes = [vp, vp, vp, vp, u32, u32, vp, vp]
     L.ssym_dtw_align.restype = i32
     L.ssym_dtw_align.argtypes = [vp, vp, vp, vp, vp, u32, u32, vp, vp, vp, vp, vp, vp, u32]
+    L.ssym_dtw_align_step.restype = i32
+    L.ssym_dtw_align_step.argtypes = [vp, vp, vp, vp, vp, u32, u32, u32, vp, vp, vp, vp, vp, vp, u32]
     L.ssym_dtw_spot.restype = i32
     L.ssym_dtw_spot.argtypes = [vp, vp, vp, vp, vp, u32, u32, vp, vp, vp, u32]
     L.ssym_spot_queries.restype = i32

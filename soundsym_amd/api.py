@@ -630,10 +630,15 @@ class SoundDictionary:
         return self.engine.match_batch(self.resident(), flat, off, distances)
 
 
-    def align(self, targets: Sequence[Sound], indices=None) -> List["Alignment"]:
+    def align(self, targets: Sequence[Sound], indices=None, step: str = "symmetric") -> List["Alignment"]:
         """The warping path of every target onto a dictionary sound (dtw engines; ssym_dtw_align).  indices=None:
         every target is matched first (match_indices) and aligned with its match -- two library calls in all;
-        otherwise indices[t] is the dictionary sound target t is aligned with."""
+        otherwise indices[t] is the dictionary sound target t is aligned with.  step="paced": the paced step pattern
+        (ssym_dtw_align_step with SSYM_STEP_PACED) -- the alignment of a span that spot(step="paced") found and cut()
+        took out: one source frame per target frame, so the path has as many cells as the target has frames and
+        frame_map is its first column; a sound too short or too long for the target (outside about half to twice its
+        frames) has no such path and gives an empty Alignment."""
+        _spot_step(step)
         if not self.sounds:
             raise EmptyDictionaryError(-2, "empty dictionary")
         targets = list(targets)
@@ -650,13 +655,13 @@ class SoundDictionary:
         try:
             if indices is None:
                 indices, _ = self.engine.match(self.resident(), q)
-            cost, _, paths, maps = self.engine.dtw_align(self.resident(), q, indices)
+            cost, _, paths, maps = self.engine.dtw_align(self.resident(), q, indices, **_step_kw(step))
         finally:
             q.close()
         return [Alignment(cost[t], paths[t], maps[t], int(indices[t])) for t in range(len(targets))]
 
     def warp(self, targets: Sequence[Sound], indices=None, want_pcm32: bool = False, search: int = 0,
-             want_pos: bool = False):
+             want_pos: bool = False, step: str = "symmetric"):
         """The reconstruction of the targets with every match warped onto its target's timing (dtw engines): match
         (unless indices[t] names the dictionary sound of target t), align with the outputs left on the device, and
         resynthesise along the maps -- ssym_match_queries, ssym_dtw_align, ssym_reconstruct_warped; the maps never
@@ -664,7 +669,10 @@ class SoundDictionary:
         want_pcm32 also their 32-bit conversion).  A target without a finite alignment takes the length fit of
         reconstruct_from_dictionary.  search > 0 (at most 512 samples): ssym_reconstruct_wsola in place of the last
         call -- every source frame may move that far to continue the frame before it in phase; want_pos then also
-        returns the frames' sample starts and the map offsets they are laid out by (Engine.reconstruct_wsola)."""
+        returns the frames' sample starts and the map offsets they are laid out by (Engine.reconstruct_wsola).
+        step="paced": the alignment is the paced one (align), whose maps move by 0, 1 or 2 source frames per target frame
+        and never stand still twice in a row; a pair whose shape admits no paced path takes the length fit."""
+        _spot_step(step)
         if not self.sounds:
             raise EmptyDictionaryError(-2, "empty dictionary")
         if getattr(self.engine, "metric", None) != "dtw":
@@ -689,7 +697,7 @@ class SoundDictionary:
         try:
             if indices is None:
                 indices, _ = self.engine.match(self.resident(), q)
-            _, lengths, _, maps, _, m_off = self.engine.dtw_align_device(self.resident(), q, indices)
+            _, lengths, _, maps, _, m_off = self.engine.dtw_align_device(self.resident(), q, indices, **_step_kw(step))
             if not search:
                 return self.engine.reconstruct_warped(self.resident_samples(), indices, out_off, maps, m_off,
                                                       np.diff(m_off.astype(np.int64)), lengths, want_pcm32)
@@ -936,11 +944,11 @@ class SoundSequence:
                                  None, None, s.ncoeffs))
         return SoundSequence(out)
 
-    def align_to_dictionary(self, dict_: SoundDictionary) -> List[Alignment]:
+    def align_to_dictionary(self, dict_: SoundDictionary, step: str = "symmetric") -> List[Alignment]:
         """Every sound of the sequence matched against dict_ and aligned with its match (SoundDictionary.align)."""
         if not self._sounds:
             return []
-        return dict_.align(self._sounds)
+        return dict_.align(self._sounds, **_step_kw(step))
 
     def spot_in_dictionary(self, dict_: SoundDictionary, step: str = "symmetric") -> List[Spot]:
         """Every sound of the sequence located inside dict_'s recordings (SoundDictionary.spot)."""
@@ -966,14 +974,17 @@ class SoundSequence:
         out_off = np.concatenate([[0], np.cumsum(lens)]).astype(np.uint64)
         return dict_.engine.reconstruct(dict_.resident_samples(), idx, out_off, want_pcm32)
 
-    def reconstruct_warped_from_dictionary(self, dict_: "SoundDictionary", want_pcm32: bool = False, search: int = 0):
+    def reconstruct_warped_from_dictionary(self, dict_: "SoundDictionary", want_pcm32: bool = False, search: int = 0,
+                                           step: str = "symmetric"):
         """reconstruct_from_dictionary with every match warped onto its target's timing instead of cut off or padded
         (SoundDictionary.warp: match, align, resynthesise along the alignment, all on the GPU; dtw engines).
-        search > 0: with the waveform-similarity search of that width in samples (at most 512)."""
+        search > 0: with the waveform-similarity search of that width in samples (at most 512).  step as for
+        SoundDictionary.warp."""
         search = _wsola_search(search)
+        _spot_step(step)
         if not self._sounds:
             return (np.zeros(0), np.zeros(0, dtype=np.int32)) if want_pcm32 else np.zeros(0)
-        return dict_.warp(self._sounds, None, want_pcm32, search)
+        return dict_.warp(self._sounds, None, want_pcm32, search, **_step_kw(step))
 
     def to_sound(self) -> Sound:                                        # src/sound.rs:475-483
         parts = [s.samples() for s in self._sounds]

@@ -26,6 +26,9 @@ namespace ssym {
 // Limits of ssym_dtw_align (soundsym_amd.h): frames per segment of a listed pair, values per frame
 constexpr int kAlignMaxFrames = 4096;
 constexpr int kAlignMaxDim = 64;
+// Limit of ssym_dtw_align_step with SSYM_STEP_PACED: frames of a listed target (two f64 hand-off rows, 16 bytes per target
+// frame; the paced spot kernels' limit, so that every span they report can be aligned); a source keeps kAlignMaxFrames
+constexpr int kAlignPacedMaxTargetFrames = 2048;
 // a pair whose direction matrix (Fa * ceil(Fb / 16) * 4 bytes) is at most this keeps it in LDS, a larger one uses global scratch
 constexpr int kAlignDirLdsBytes = 16384;
 // global scratch of one call: at most this many bytes of direction slabs (one per workgroup)
@@ -50,7 +53,7 @@ struct AlignArgs {
     uint32_t *map;               // nullable
     uint32_t fbCap;              // even, >= the longest listed target
     uint32_t ringRows;           // 64 or 128
-    uint32_t codeCap;            // bytes of the code string (>= longest Fa + Fb - 1, a multiple of 16)
+    uint32_t codeCap;            // bytes of the code string (>= longest Fa + Fb - 1, a multiple of 16); paced: of the row of i_j (4 fbCap)
     uint32_t dirLdsBytes;        // LDS room of the direction matrix
     uint32_t *slabs;             // global direction slabs, slabWords each (NULL: every listed pair fits LDS)
     uint64_t slabWords;
@@ -220,65 +223,259 @@ __global__ __launch_bounds__(64) void dtw_align_kernel(const AlignArgs a)
     }
 }
 
+// Paced alignment (ssym_dtw_align_step with SSYM_STEP_PACED; DESIGN.md 2 "Paced alignment", 5.19): the path of the paced
+// step pattern between pinned ends.  N, H, E and the arithmetic are dtw_paced_kernel's (dtw_spot.hip); what differs is
+// column 0 (N(0,0) = c(0,0), every other row +inf: the path starts at source frame 0) and what a cell leaves behind: no
+// start word, but two bits -- skip (P came from row i - 2) and rep (H < N) -- packed 16 per dword like dtw_align_kernel's
+// codes, in LDS up to dirLdsBytes and in the workgroup's global slab beyond.
+//   forward   dtw_paced_kernel's wavefront: N and E of the previous column per lane, d1 = E(r-1, j-1) and d2 = E(r-2, j-1)
+//             by DPP, two f64 hand-off rows written in place by lanes 63 and 62 (the order argument is the one given there)
+//   backward  lane 0 walks Fb - 1 steps from (Fa-1, Fb-1) with the wanted state in a register: E (the cell's better state:
+//             H if rep, else N) or N (the cell was left by a repeat, which may only follow a source step).  State H: the cell
+//             before is (i, j-1), wanted in state N.  State N: the cell before is (i-2, j-1) if skip, else (i-1, j-1),
+//             wanted in state E.  One dependent read and one LDS word (the row of column j) per step; the row is clamped at 0.
+//   output    every admissible path has one cell per target frame: path[j] = (i_j, j), map[j] = i_j, len = Fb, stored
+//             coalesced from the LDS row.  A pair whose shape admits no path (Fa outside floor((Fb-1)/2)+1 ... 2 Fb - 1) is
+//             decided before the recurrence; a cost that is not finite writes cost and len = 0 alone.
+template <int DIMR>
+__global__ __launch_bounds__(64) void dtw_align_paced_kernel(const AlignArgs a)
+{
+    extern __shared__ __attribute__((aligned(16))) double smem[];
+    constexpr int LD = wave_ld(DIMR);
+    double *bound1 = smem;                                          // [fbCap]   E of row c0 - 1
+    double *bound2 = smem + a.fbCap;                                // [fbCap]   E of row c0 - 2
+    double *ring = smem + 2 * (size_t)a.fbCap;                      // [ringRows][LD]
+    uint32_t *rows = reinterpret_cast<uint32_t *>(ring + (size_t)a.ringRows * LD);                // [codeCap / 4]  i_j
+    uint32_t *dirLds = rows + a.codeCap / 4;                                                    // [dirLdsBytes / 4]
+    const double INF = __builtin_inf();
+    const int lane = threadIdx.x;
+    const int dim = (int)a.dim;
+    const uint32_t ringMask = a.ringRows - 1;
+
+    for (uint32_t k = blockIdx.x; k < a.nPairs; k += gridDim.x) {
+        const uint2 p = a.pairs[k];
+        int Fa = 0, Fb = 0;
+        if (p.x != 0xffffffffu) {
+            Fa = (int)(a.srcOff[p.x + 1] - a.srcOff[p.x]);
+            Fb = (int)(a.tgtOff[p.y + 1] - a.tgtOff[p.y]);
+        }
+        // nothing to align, or a shape no admissible path fits: one source frame per target frame, steps of 0, 1 or 2
+        if (Fa == 0 || Fb == 0 || Fa < (Fb - 1) / 2 + 1 || Fa > 2 * Fb - 1) {
+            if (lane == 0) {
+                a.cost[k] = INF;
+                a.len[k] = 0;
+            }
+            continue;
+        }
+        const double *a0 = a.srcRaw + a.srcOff[p.x] * dim;
+        const double *b0 = a.tgtRaw + a.tgtOff[p.y] * dim;
+        const uint32_t rowWords = ((uint32_t)Fb + 15) >> 4;
+        const bool dirInLds = (uint64_t)Fa * rowWords * 4 <= a.dirLdsBytes;
+        uint32_t *dirG = a.slabs + (size_t)blockIdx.x * a.slabWords;     // only touched when !dirInLds (then slabs != NULL)
+
+        double result = INF;
+        for (int c0 = 0; c0 < Fa; c0 += 64) {
+            const int r = c0 + lane;
+            const bool rowValid = r < Fa;
+            const int rowsHere = min(64, Fa - c0);
+            double ar[DIMR];
+            wave_load_frame(ar, a0 + (size_t)(rowValid ? r : c0) * dim, dim);
+            double mineN = INF, mineE = INF;                        // N(r, j-1), E(r, j-1)
+            double d1 = INF, d2 = INF;                              // E(r-1, j-1), E(r-2, j-1)
+            uint32_t pack = 0;                                      // codes of this row's current group of 16 columns
+            const int tauEnd = Fb - 1 + rowsHere;     // exclusive: lane l works on column tau - l
+            for (int tau = 0; tau < tauEnd; ++tau) {
+                // (the refill's barrier also orders the hand-off rows, the row of i_j and the codes in LDS: the previous
+                // chunk's writes, and the previous pair's reads, are done before tau = 0 goes on)
+                if ((tau & 63) == 0)
+                    wave_refill<DIMR>(ring, ringMask, b0, dim, Fb, tau);
+                const int j = tau - lane;
+                const double c = wave_cell_cost(ar, ring, ringMask, min(max(j, 0), Fb - 1), a.squared);
+                const double up = shfl_up1(mineE);        // E(r-1, j) for lanes >= 1: the next step's d1
+                if (lane == 0) {
+                    d1 = d2 = INF;                        // above row 0 there is nothing
+                    if (c0 != 0 && j >= 1 && j < Fb) {
+                        d1 = bound1[j - 1];
+                        d2 = bound2[j - 1];
+                    }
+                }
+                // E(r-2, j) for the next step: the d1 of lane l - 1, lane 0's being what it read from the hand-off row
+                const double nx = shfl_up1(d1);
+                const bool active = rowValid && j >= 0 && j < Fb;
+                if (active) {
+                    double nD = r == 0 ? c : INF;         // column 0: the path starts at source frame 0, in state N
+                    double eD = nD;
+                    if (j > 0) {
+                        double pD = d1;
+                        uint32_t code = 0;
+                        if (d2 < pD) {
+                            pD = d2;
+                            code = 1u;                    // skip
+                        }
+                        nD = __dadd_rn(c, pD);
+                        const double hD = __dadd_rn(c, mineN);
+                        eD = nD;
+                        if (hD < nD) {
+                            eD = hD;
+                            code |= 2u;                   // rep
+                        }
+                        pack |= code << (2 * (j & 15));
+                    }
+                    if ((j & 15) == 15 || j == Fb - 1) {
+                        const size_t w = (size_t)r * rowWords + ((uint32_t)j >> 4);
+                        if (dirInLds)
+                            dirLds[w] = pack;
+                        else
+                            dirG[w] = pack;
+                        pack = 0;
+                    }
+                    if (lane == 63)
+                        bound1[j] = eD;
+                    if (lane == 62)
+                        bound2[j] = eD;
+                    if (r == Fa - 1 && j == Fb - 1)
+                        result = eD;
+                    mineN = nD;
+                    mineE = eD;
+                }
+                d1 = up;
+                d2 = nx;
+            }
+        }
+        const double total = __shfl(result, (Fa - 1) & 63);
+        if (lane == 0)
+            a.cost[k] = total;
+        if (!(total < INF)) {      // +inf or NaN: no path
+            if (lane == 0)
+                a.len[k] = 0;
+            continue;
+        }
+        // the codes are read back by lane 0 as dtw_align_kernel reads its own: LDS after a barrier, the slab after a release
+        // and by loads that bypass this CU's L1
+        if (!dirInLds)
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+        __syncthreads();
+        if (lane == 0) {
+            int i = Fa - 1;
+            bool wantE = true;
+            for (int j = Fb - 1; j >= 1; --j) {
+                rows[j] = (uint32_t)i;
+                const size_t w = (size_t)i * rowWords + ((uint32_t)j >> 4);
+                const uint32_t word = dirInLds ? dirLds[w] : __hip_atomic_load(dirG + w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                const uint32_t code = (word >> (2 * (j & 15))) & 3u;
+                if (wantE && (code & 2u)) {
+                    wantE = false;                        // state H: (i, j-1), in state N
+                } else {
+                    i = max(i - ((code & 1u) ? 2 : 1), 0);      // (a finite cost's codes never lead above row 0)
+                    wantE = true;
+                }
+            }
+            rows[0] = (uint32_t)i;
+        }
+        __syncthreads();
+        if (lane == 0)
+            a.len[k] = (uint32_t)Fb;
+        uint2 *path = a.path + a.pathOff[k];
+        uint32_t *map = a.map ? a.map + a.mapOff[k] : nullptr;
+        for (int j = lane; j < Fb; j += 64) {
+            const uint32_t i = rows[j];
+            path[j] = make_uint2(i, (uint32_t)j);
+            if (map)
+                map[j] = i;
+        }
+    }
+}
+
+// the frames of a listed pair, (0, 0) for a pair without a source or with an empty segment
+inline void align_shape(const SegmentSet &src, const SegmentSet &tgt, uint32_t s, uint32_t t, uint64_t *fa, uint64_t *fb)
+{
+    *fa = *fb = 0;
+    if (s == SSYM_NO_MATCH)
+        return;
+    const uint64_t a = src.h_off[s + 1] - src.h_off[s], b = tgt.h_off[t + 1] - tgt.h_off[t];
+    if (a == 0 || b == 0)
+        return;
+    *fa = a;
+    *fb = b;
+}
+
 // Fa + Fb - 1 steps and Fb map entries per pair, 0 for a pair without a source or with an empty segment
 inline void align_capacity(const SegmentSet &src, const SegmentSet &tgt, uint32_t s, uint32_t t, uint64_t *steps,
                            uint64_t *frames)
 {
-    *steps = *frames = 0;
-    if (s == SSYM_NO_MATCH)
-        return;
-    const uint64_t fa = src.h_off[s + 1] - src.h_off[s], fb = tgt.h_off[t + 1] - tgt.h_off[t];
-    if (fa == 0 || fb == 0)
-        return;
-    *steps = fa + fb - 1;
+    uint64_t fa, fb;
+    align_shape(src, tgt, s, t, &fa, &fb);
+    *steps = fb ? fa + fb - 1 : 0;
     *frames = fb;
 }
 
 int32_t dtw_align(ssym_ctx *ctx, const ssym_dict *dict, const ssym_queries *q, const uint32_t *src_idx,
                   const uint32_t *tgt_idx, uint32_t n_pairs, uint32_t index_base, double *out_cost, uint32_t *out_len,
                   const uint64_t *path_offsets, uint32_t *out_path, const uint64_t *map_offsets, uint32_t *out_map,
-                  uint32_t flags)
+                  uint32_t flags, uint32_t step = SSYM_STEP_SYMMETRIC, const char *fn = "ssym_dtw_align")
 {
     if (!ctx)
         return SSYM_E_INVALID;
+    const std::string name(fn);
+    const bool paced = step == SSYM_STEP_PACED;
+    if (step != SSYM_STEP_SYMMETRIC && !paced) {
+        ctx->err = name + ": step must be SSYM_STEP_SYMMETRIC or SSYM_STEP_PACED";
+        return SSYM_E_INVALID;
+    }
     if (ctx->metric != SSYM_METRIC_DTW) {
-        ctx->err = "ssym_dtw_align: the context's metric is refcos, which has no alignment";
+        ctx->err = name + ": the context's metric is refcos, which has no alignment";
         return SSYM_E_UNSUPPORTED;
     }
-    int32_t rc = check_pair_list(ctx->err, "ssym_dtw_align", dict, q, src_idx, tgt_idx, n_pairs, index_base);
+    if (paced && ctx->band >= 0) {
+        ctx->err = name + ": the paced step pattern bounds the slope itself and takes no Sakoe-Chiba band; use a context without one";
+        return SSYM_E_UNSUPPORTED;
+    }
+    int32_t rc = check_pair_list(ctx->err, fn, dict, q, src_idx, tgt_idx, n_pairs, index_base);
     if (rc != SSYM_OK)
         return rc;
     if (n_pairs == 0)
         return SSYM_OK;
     if (!out_cost || !out_len || !path_offsets || !out_path || (out_map && !map_offsets)) {
-        ctx->err = "ssym_dtw_align: out_cost, out_len, path_offsets, out_path (and map_offsets with out_map) must not be NULL";
+        ctx->err = name + ": out_cost, out_len, path_offsets, out_path (and map_offsets with out_map) must not be NULL";
         return SSYM_E_INVALID;
     }
     const SegmentSet &src = dict->set, &tgt = q->set;
     // the pair list, the offsets against the capacities, the shape limits: all on the host, before any device work
     PairList pairs(src_idx, tgt_idx, index_base, n_pairs);
-    uint64_t maxFa = 0, maxFb = 0, maxSlab = 0;
+    uint64_t listedFa = 0, listedFb = 0;               // what the limits hold: every listed pair with frames
+    uint64_t maxFa = 0, maxFb = 0, maxSlab = 0;        // what sizes LDS and the slabs: the pairs the kernel runs
     for (uint32_t p = 0; p < n_pairs; ++p) {
-        uint64_t steps, frames;
-        align_capacity(src, tgt, pairs.host[p].x, pairs.host[p].y, &steps, &frames);
+        uint64_t fa, fb;
+        align_shape(src, tgt, pairs.host[p].x, pairs.host[p].y, &fa, &fb);
+        // a paced path has one cell per target frame
+        const uint64_t steps = fb == 0 ? 0 : paced ? fb : fa + fb - 1;
         if (path_offsets[p + 1] < path_offsets[p] || path_offsets[p + 1] - path_offsets[p] < steps ||
-            (out_map && (map_offsets[p + 1] < map_offsets[p] || map_offsets[p + 1] - map_offsets[p] < frames))) {
-            ctx->err = "ssym_dtw_align: offsets of pair " + std::to_string(p) +
-                       " decrease or leave less room than ssym_dtw_align_sizes asks for";
+            (out_map && (map_offsets[p + 1] < map_offsets[p] || map_offsets[p + 1] - map_offsets[p] < fb))) {
+            ctx->err = name + ": offsets of pair " + std::to_string(p) + " decrease or leave less room than " +
+                       (paced ? "the target's frames" : "ssym_dtw_align_sizes asks for");
             return SSYM_E_INVALID;
         }
         if (steps == 0)
             continue;
-        const uint64_t fa = steps + 1 - frames, fb = frames;
+        listedFa = std::max(listedFa, fa);
+        listedFb = std::max(listedFb, fb);
+        // a shape without a paced path is decided before the recurrence: it takes no LDS and no slab, so it sizes none
+        if (paced && (fa < (fb - 1) / 2 + 1 || fa > 2 * fb - 1))
+            continue;
         maxFa = std::max(maxFa, fa);
         maxFb = std::max(maxFb, fb);
         const uint64_t dirBytes = fa * ((fb + 15) / 16) * 4;
         if (dirBytes > (uint64_t)kAlignDirLdsBytes)
             maxSlab = std::max(maxSlab, dirBytes);
     }
-    if (maxFa > (uint64_t)kAlignMaxFrames || maxFb > (uint64_t)kAlignMaxFrames || src.dim > (uint32_t)kAlignMaxDim) {
-        ctx->err = "ssym_dtw_align: a listed segment has more than " + std::to_string(kAlignMaxFrames) +
+    if (listedFa > (uint64_t)kAlignMaxFrames || listedFb > (uint64_t)kAlignMaxFrames || src.dim > (uint32_t)kAlignMaxDim) {
+        ctx->err = name + ": a listed segment has more than " + std::to_string(kAlignMaxFrames) +
                    " frames, or frames have more than " + std::to_string(kAlignMaxDim) + " values";
+        return SSYM_E_UNSUPPORTED;
+    }
+    if (paced && listedFb > (uint64_t)kAlignPacedMaxTargetFrames) {
+        ctx->err = name + ": a listed target has more than " + std::to_string(kAlignPacedMaxTargetFrames) +
+                   " frames, the limit of SSYM_STEP_PACED";
         return SSYM_E_UNSUPPORTED;
     }
     SSYM_HIP_CHECK(ctx, hipSetDevice(ctx->device));
@@ -311,9 +508,10 @@ int32_t dtw_align(ssym_ctx *ctx, const ssym_dict *dict, const ssym_queries *q, c
     const WaveGeom g = wave_geom(ctx, maxFb, src.dim, n_pairs);
     a.fbCap = g.fbCap;
     a.ringRows = g.ringRows;
-    a.codeCap = ((uint32_t)(maxFa + maxFb) + 15) & ~15u;
+    // symmetric: the code string, one byte per step; paced: the source frame of every target frame, one word each
+    a.codeCap = paced ? 4 * g.fbCap : ((uint32_t)(maxFa + maxFb) + 15) & ~15u;
     a.dirLdsBytes = (uint32_t)std::min<uint64_t>((uint64_t)kAlignDirLdsBytes, (maxFa * ((maxFb + 15) / 16) * 4 + 15) & ~15ull);
-    const size_t lds = (size_t)a.fbCap * sizeof(double) + g.ringBytes + a.codeCap + a.dirLdsBytes;
+    const size_t lds = (paced ? 2 : 1) * (size_t)a.fbCap * sizeof(double) + g.ringBytes + a.codeCap + a.dirLdsBytes;
     unsigned grid = g.grid;
     if (maxSlab) {
         // one slab per workgroup, as many workgroups as kAlignScratchBytes holds (128 for a 4096 x 4096 pair)
@@ -342,7 +540,8 @@ int32_t dtw_align(ssym_ctx *ctx, const ssym_dict *dict, const ssym_queries *q, c
     a.len = dLen;
     a.path = reinterpret_cast<uint2 *>(dPath);
     a.map = dMap;
-    rc = wave_launch(ctx, SSYM_WAVE_KERNEL(dtw_align_kernel, g.dimr), grid, lds, a);
+    rc = paced ? wave_launch(ctx, SSYM_WAVE_KERNEL(dtw_align_paced_kernel, g.dimr), grid, lds, a)
+               : wave_launch(ctx, SSYM_WAVE_KERNEL(dtw_align_kernel, g.dimr), grid, lds, a);
     if (rc != SSYM_OK)
         return rc;
     if (outDev) {
@@ -411,6 +610,18 @@ int32_t ssym_dtw_align(ssym_ctx *ctx, const ssym_dict *dict, const ssym_queries 
     return guarded(ctx, [&]() -> int32_t {
         return dtw_align(ctx, dict, q, src_idx, tgt_idx, n_pairs, index_base, out_cost, out_len, path_offsets, out_path,
                          map_offsets, out_map, flags);
+    });
+}
+
+// the call above with the step pattern as an argument: SSYM_STEP_SYMMETRIC is the call above itself
+int32_t ssym_dtw_align_step(ssym_ctx *ctx, const ssym_dict *dict, const ssym_queries *q, const uint32_t *src_idx,
+                            const uint32_t *tgt_idx, uint32_t n_pairs, uint32_t index_base, uint32_t step, double *out_cost,
+                            uint32_t *out_len, const uint64_t *path_offsets, uint32_t *out_path,
+                            const uint64_t *map_offsets, uint32_t *out_map, uint32_t flags)
+{
+    return guarded(ctx, [&]() -> int32_t {
+        return dtw_align(ctx, dict, q, src_idx, tgt_idx, n_pairs, index_base, out_cost, out_len, path_offsets, out_path,
+                         map_offsets, out_map, flags, step, "ssym_dtw_align_step");
     });
 }
 

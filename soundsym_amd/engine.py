@@ -811,13 +811,23 @@ class Engine:
             raise nat.SsymError(rc, "ssym_dtw_align_sizes: an index is outside its set, or the sets do not go together")
         return p_off, m_off
 
-    def dtw_align(self, d: _Handle, q: _Handle, src_idx, tgt_idx=None, index_base: int = 0, want_map: bool = True):
+    def _align_call(self, which, head, tail):
+        """ssym_dtw_align for the symmetric pattern, ssym_dtw_align_step for any other."""
+        if which == nat.STEP_SYMMETRIC:
+            return nat.lib().ssym_dtw_align(*head, *tail)
+        return nat.lib().ssym_dtw_align_step(*head, which, *tail)
+
+    def dtw_align(self, d: _Handle, q: _Handle, src_idx, tgt_idx=None, index_base: int = 0, want_map: bool = True,
+                  step: str = "symmetric"):
         """ssym_dtw_align: the optimal warping path of every listed pair (source src_idx[p] - index_base, target
         tgt_idx[p], or target p without tgt_idx), by the definition in include/soundsym_amd.h.  Returns (cost f64
         [n], lengths uint32 [n], paths, maps): paths[p] is an (L, 2) uint32 array of (source frame, target frame)
         cells in forward order, maps[p] a (Fb,) uint32 array with the smallest source frame of every target frame (or
         None without want_map).  A pair without a finite cost has length 0, an empty path and an empty map.  The
-        arrays are views into one buffer each."""
+        arrays are views into one buffer each.  step="paced": ssym_dtw_align_step with SSYM_STEP_PACED ("Paced
+        alignment": one cell per target frame, steps of 0, 1 or 2 source frames, never two 0 steps in a row; a pair
+        whose shape admits no such path has length 0); "symmetric" is ssym_dtw_align itself."""
+        which = _spot_step(step)
         src, tgt = _align_indices(src_idx, tgt_idx)
         n = src.size
         p_off, m_off = self.dtw_align_sizes(d, q, src, tgt, index_base)
@@ -825,31 +835,31 @@ class Engine:
         length = np.zeros(n, dtype=np.uint32)
         path = np.zeros((int(p_off[-1]), 2), dtype=np.uint32)
         fmap = np.zeros(int(m_off[-1]), dtype=np.uint32) if want_map else None
-        rc = nat.lib().ssym_dtw_align(self.ctx, d.ptr, q.ptr, src.ctypes.data, tgt.ctypes.data if tgt is not None else None,
-                                      n, index_base, cost.ctypes.data, length.ctypes.data, p_off.ctypes.data,
-                                      path.ctypes.data, m_off.ctypes.data if want_map else None,
-                                      fmap.ctypes.data if want_map else None, 0)
-        nat.check(rc, self.ctx)
+        head = (self.ctx, d.ptr, q.ptr, src.ctypes.data, tgt.ctypes.data if tgt is not None else None, n, index_base)
+        tail = (cost.ctypes.data, length.ctypes.data, p_off.ctypes.data, path.ctypes.data,
+                m_off.ctypes.data if want_map else None, fmap.ctypes.data if want_map else None, 0)
+        nat.check(Engine._align_call(self, which, head, tail), self.ctx)
         paths = [path[int(p_off[p]):int(p_off[p]) + int(length[p])] for p in range(n)]
         maps = None
         if want_map:
             maps = [fmap[int(m_off[p]):int(m_off[p + 1])] if length[p] else fmap[0:0] for p in range(n)]
         return cost, length, paths, maps
 
-    def dtw_align_device(self, d: _Handle, q: _Handle, src_idx, tgt_idx=None, index_base: int = 0):
+    def dtw_align_device(self, d: _Handle, q: _Handle, src_idx, tgt_idx=None, index_base: int = 0, step: str = "symmetric"):
         """ssym_dtw_align with SSYM_OUT_DEVICE: the outputs stay in device memory (torch tensors; torch only owns the
         memory).  Returns (cost f64 [n], lengths i32 [n], paths i32 [cells * 2], maps i32 [map entries], path_offsets,
         map_offsets); the 32-bit tensors hold the call's u32 values.  maps, lengths and map_offsets are what
-        reconstruct_warped takes."""
+        reconstruct_warped takes.  step as for dtw_align."""
+        which = _spot_step(step)
         src, tgt = _align_indices(src_idx, tgt_idx)
         n = src.size
         p_off, m_off = self.dtw_align_sizes(d, q, src, tgt, index_base)
         (cost, pc), (length, pl), (path, pp), (fmap, pm) = (
             _output(self.device, (rows,), t) for rows, t in ((n, np.float64), (n, np.uint32), (2 * int(p_off[-1]), np.uint32),
                                                             (int(m_off[-1]), np.uint32)))
-        nat.check(nat.lib().ssym_dtw_align(self.ctx, d.ptr, q.ptr, src.ctypes.data,
-                                           tgt.ctypes.data if tgt is not None else None, n, index_base, pc, pl,
-                                           p_off.ctypes.data, pp, m_off.ctypes.data, pm, nat.OUT_DEVICE), self.ctx)
+        head = (self.ctx, d.ptr, q.ptr, src.ctypes.data, tgt.ctypes.data if tgt is not None else None, n, index_base)
+        tail = (pc, pl, p_off.ctypes.data, pp, m_off.ctypes.data, pm, nat.OUT_DEVICE)
+        nat.check(Engine._align_call(self, which, head, tail), self.ctx)
         return cost, length, path, fmap, p_off, m_off
 
     def _dtw_spot(self, d, q, src_idx, tgt_idx, index_base, step, on_device):
