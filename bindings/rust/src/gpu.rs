@@ -286,6 +286,10 @@ extern "C" {
                              out_end: *mut u32, flags: u32) -> i32;
     pub fn ssym_spotter_counts(sp: *const SsymSpotter, out_frames: *mut u64) -> i32;
     pub fn ssym_spotter_reset(ctx: *mut SsymCtx, sp: *mut SsymSpotter, lane: u32) -> i32;
+    // ssym_spotter_create with a step pattern: under SSYM_STEP_PACED the spotter's spans keep the paced slope bounds, a NaN
+    // frame costs a bounded stretch of a lane, and the state is two rows per (lane, target); max_cost stays a sum
+    pub fn ssym_spotter_create_step(ctx: *mut SsymCtx, q: *const SsymQueries, n_lanes: u32, max_cost: *const f64,
+                                    step: u32, out: *mut *mut SsymSpotter) -> i32;
 }
 
 /// `Err(message)` for any status but SSYM_OK; SSYM_E_EMPTY_DICT keeps the crate's behaviour (a panic, :369).

@@ -2,6 +2,7 @@
 """examples/watch.py -- watch for known sounds in a recording that arrives block by block.
 
     python examples/watch.py -s RECORDING.wav -d TARGETS.wav|DIR [--block 4096] [--max-cost X]
+                             [--paced [--max-cost-per-frame X]]
 
 The recording is fed --block samples at a time, as a microphone would deliver it (Sound.push_samples: only the new
 samples are uploaded and analysed).  A Watch (streaming DTW spotting: ssym_spotter_*) consumes the new frames of every
@@ -10,7 +11,9 @@ soon as the frames that follow it no longer overlap it: the block, the target, t
 as each event is emitted.  The rule is causal: a span once reported is never revised, unlike examples/occurrences.py, which
 sees the whole recording.  The cost is a sum along the warping path, not normalised by any length; without --max-cost
 every stretch of the recording is reported as the occurrence it resembles most, and the printed costs show where to put the
-threshold.
+threshold.  With --paced the paced step pattern is used (ssym_spotter_create_step): a reported span has between about half
+and twice the target's frames, the cost per target frame is printed beside the sum, and --max-cost-per-frame puts the
+threshold on that mean -- one value for targets of every length.
 """
 import argparse
 import os
@@ -27,7 +30,12 @@ def main(argv=None):
     ap.add_argument("-d", required=True, help="a target sound, or a directory of them")
     ap.add_argument("--block", type=int, default=4096, help="samples per block")
     ap.add_argument("--max-cost", type=float, default=None, help="an occurrence costs at most this")
+    ap.add_argument("--paced", action="store_true", help="the paced step pattern: slope-bounded spans, costs per frame")
+    ap.add_argument("--max-cost-per-frame", type=float, default=None,
+                    help="with --paced: an occurrence costs at most this per target frame")
     args = ap.parse_args(argv)
+    if args.max_cost_per_frame is not None and not args.paced:
+        ap.error("--max-cost-per-frame needs --paced")
 
     engine = Engine(metric="dtw", dtype="f64")
     whole = Sound.from_path(args.s, engine=engine)
@@ -40,14 +48,19 @@ def main(argv=None):
     head = min(BIN, samples.size)                       # the first window, analysed as a sound of its own
     live = Sound.from_samples(samples[:head], rate, engine=engine)
     live.push_samples(samples[head:head], engine)       # makes the sound resident: the stream a Watch follows
-    w = watch([live], targets, max_cost=args.max_cost, engine=engine)
+    if args.paced:
+        w = watch([live], targets, max_cost=args.max_cost, engine=engine, step="paced",
+                  max_cost_per_frame=args.max_cost_per_frame)
+    else:
+        w = watch([live], targets, max_cost=args.max_cost, engine=engine)
     found = []
 
     def report(block, events):
         for _, t, sp in events:
             a, b = sp.sample_span(live.samples().size)
             print(f"block {block:5d}: {targets[t].name or t} {a / rate:9.3f} s ... {b / rate:9.3f} s "
-                  f"(frames {sp.start_frame}...{sp.end_frame}), cost {sp.cost:.6g}")
+                  f"(frames {sp.start_frame}...{sp.end_frame}), cost {sp.cost:.6g}"
+                  + (f", per frame {sp.cost_per_frame:.6g}" if sp.cost_per_frame is not None else ""))
         found.extend(events)
 
     block = 0

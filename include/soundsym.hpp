@@ -489,6 +489,8 @@ class SoundDictionary {
 // The targets of one query set watched in n_lanes growing sources (ssym_spotter; soundsym_amd.h "Watching"): a push costs
 // the new frames alone, best() is SoundDictionary::spot's answer for what a lane has consumed, and occurrences come as
 // events under a causal rule (not spot_all's greedy: a span once emitted is never revised).
+// step: SSYM_STEP_SYMMETRIC (ssym_spotter_create) or SSYM_STEP_PACED (ssym_spotter_create_step; soundsym_amd.h "Paced
+// watching": spans of about half to twice the target's frames, max_cost stays a sum, targets of at most 2048 frames).
 class Spotter {
   public:
     using Spot = SoundDictionary::Spot;
@@ -497,7 +499,7 @@ class Spotter {
         Spot spot;                  // source_index = the lane
     };
     Spotter(std::shared_ptr<Context> ctx, const std::vector<ArcSound> &targets, uint32_t n_lanes = 1,
-            const std::vector<double> *max_cost = nullptr)
+            const std::vector<double> *max_cost = nullptr, uint32_t step = SSYM_STEP_SYMMETRIC)
         : ctx_(std::move(ctx)), lanes_(n_lanes), targets_((uint32_t)targets.size())
     {
         if (max_cost && max_cost->size() != targets.size())
@@ -506,7 +508,9 @@ class Spotter {
         std::vector<uint64_t> off;
         pack_features(targets, flat, off);
         ctx_->check(ssym_queries_create(ctx_->get(), flat.data(), off.data(), targets_, (uint32_t)NCOEFFS, &q_));
-        const int32_t rc = ssym_spotter_create(ctx_->get(), q_, n_lanes, max_cost ? max_cost->data() : nullptr, &sp_);
+        const double *limits = max_cost ? max_cost->data() : nullptr;
+        const int32_t rc = step == SSYM_STEP_SYMMETRIC ? ssym_spotter_create(ctx_->get(), q_, n_lanes, limits, &sp_)
+                                                       : ssym_spotter_create_step(ctx_->get(), q_, n_lanes, limits, step, &sp_);
         if (rc != SSYM_OK) {
             ssym_queries_destroy(ctx_->get(), q_);
             ctx_->check(rc);

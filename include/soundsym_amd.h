@@ -948,6 +948,35 @@ SSYM_API int32_t ssym_spotter_best(ssym_ctx *ctx, const ssym_spotter *sp, double
 SSYM_API int32_t ssym_spotter_counts(const ssym_spotter *sp, uint64_t *out_frames);
 SSYM_API int32_t ssym_spotter_reset(ssym_ctx *ctx, ssym_spotter *sp, uint32_t lane);
 
+/* Paced watching (DESIGN.md section 2 "Paced watching" and section 5.20): ssym_spotter_create with a step pattern.
+ * SSYM_STEP_SYMMETRIC is ssym_spotter_create itself: one host path, the same kernels, the same bits.  With SSYM_STEP_PACED
+ * the spotter watches under the pattern of "Paced spotting": c, the squared option, the arithmetic and the states N, H,
+ * E, P are those, word for word; i is the absolute frame number within everything the lane has consumed;
+ * delta(i) = E(i,Fb-1).value and s(i) = E(i,Fb-1).start.
+ *   resume  : after consuming n frames the spotter holds, per (l,t): n, rows n-1 and n-2 of E (value f64, start u32; Fb
+ *             entries each; a row that does not exist yet is (+inf, none)), the running best, pend, last.  Consuming
+ *             frames n ... n+m-1 computes rows n ... n+m-1 from those two rows.
+ *   best    : the first least delta(i), i ascending from (none, +inf), strict < -- after any push it is
+ *             ssym_dtw_spot_step(SSYM_STEP_PACED)'s result for (the frames consumed so far, target), bit for bit
+ *   report, flush, nothing : those of "Watching" above, unchanged, on this (delta, s)
+ * So: however a lane is cut into pushes, the profile, the best after every push and the events (with the push that emits
+ * each) are bit for bit those of one push; every emitted span has between floor((Fb-1)/2) + 1 and 2 Fb - 1 frames, the
+ * spans of one (l,t) are pairwise disjoint and their ends ascend; every emitted cost has the bits
+ * ssym_dtw_align_step(SSYM_STEP_PACED) gives for (frames start ... end, target), so a span goes straight into that call.
+ * Every path has Fb cells: a caller that wants one per-frame threshold x for targets of every length passes
+ * max_cost[t] = x * Fb[t] (max_cost stays a sum here, as costs do) and +inf for a target without frames.
+ * Features that are not finite as for "Paced spotting", carried across pushes by the two stored rows: the recurrence has
+ * no edge from row i to row i in the next column but through N, so a NaN or infinite source frame poisons a bounded
+ * stretch of rows only, after which the lane spots again WITHOUT ssym_spotter_reset; a poisoned target frame is on every
+ * path, so that target never has a candidate on any lane.  No read leaves its buffer.
+ * The spotter remembers its step: push, follow, events, flush, best, counts, reset and destroy act by it.
+ * An unknown step: SSYM_E_INVALID.  Limits with SSYM_STEP_PACED: targets of at most 2048 frames (two hand-off rows
+ * take 24 bytes of LDS per target frame): a longer one is SSYM_E_UNSUPPORTED at creation, before any device work.
+ * Every other limit, refusal and output is that of "Watching".  The state is
+ * 24 bytes x (frames of all targets) x n_lanes under SSYM_STEP_PACED and stays 12 under SSYM_STEP_SYMMETRIC. */
+SSYM_API int32_t ssym_spotter_create_step(ssym_ctx *ctx, const ssym_queries *q, uint32_t n_lanes, const double *max_cost,
+                                          uint32_t step, ssym_spotter **out);
+
 #ifdef __cplusplus
 }
 #endif

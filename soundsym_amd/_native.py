@@ -62,6 +62,7 @@ ABI_SYMBOLS = [
     "ssym_dtw_spot", "ssym_spot_queries", "ssym_dtw_spot_all",
     "ssym_dtw_spot_step", "ssym_spot_queries_step", "ssym_dtw_spot_all_step",
     "ssym_dtw_align_step",
+    "ssym_spotter_create_step",
     "ssym_reconstruct_warped", "ssym_reconstruct_wsola",
 ]
 COMM_ID_BYTES = 128        # SSYM_COMM_ID_BYTES
@@ -350,6 +351,8 @@ def lib() -> ctypes.CDLL:
     L.ssym_stream_reset.argtypes = [vp, vp, u32]
     L.ssym_spotter_create.restype = i32
     L.ssym_spotter_create.argtypes = [vp, vp, u32, vp, pvp]
+    L.ssym_spotter_create_step.restype = i32
+    L.ssym_spotter_create_step.argtypes = [vp, vp, u32, vp, u32, pvp]
     L.ssym_spotter_destroy.restype = i32
     L.ssym_spotter_destroy.argtypes = [vp, vp]
     L.ssym_spotter_push.restype = i32

@@ -413,14 +413,20 @@ class Spot:
 class Watch:
     """Targets watched in growing Sounds (`watch`): the sounds' shared stream followed by a Spotter.  Events are
     (sound index, target index, Spot) with Spot.source_index the sound index; frames are those of the sound, so
-    Spot.sample_span applies as it is."""
+    Spot.sample_span applies as it is.  Under step="paced" every Spot carries cost_per_frame, cost / the target's
+    frames."""
 
-    def __init__(self, sounds, stream, spotter, queries):
+    def __init__(self, sounds, stream, spotter, queries, frames=None):
         self.sounds, self.stream, self.spotter, self._queries = sounds, stream, spotter, queries
+        self._frames = frames                 # per target, for cost_per_frame
+
+    def _spot(self, lane, t, start, end, cost):
+        step = getattr(self.spotter, "step", "symmetric")
+        return Spot(lane, start, end, cost, _per_frame(step, cost, self._frames[t]) if step == "paced" else None)
 
     def _events(self):
         lane, tgt, cost, start, end = self.spotter.events()
-        return [(int(lane[k]), int(tgt[k]), Spot(int(lane[k]), int(start[k]), int(end[k]), cost[k]))
+        return [(int(lane[k]), int(tgt[k]), self._spot(int(lane[k]), int(tgt[k]), int(start[k]), int(end[k]), cost[k]))
                 for k in range(lane.size)]
 
     def poll(self):
@@ -440,7 +446,7 @@ class Watch:
     def best(self):
         """[sound][target] the best span so far as a Spot (SoundDictionary.spot's for what was consumed)."""
         cost, start, end = self.spotter.best()
-        return [[Spot(l, int(start[l, t]), int(end[l, t]), cost[l, t]) if int(end[l, t]) != NO_MATCH else Spot.none()
+        return [[self._spot(l, t, int(start[l, t]), int(end[l, t]), cost[l, t]) if int(end[l, t]) != NO_MATCH else Spot.none()
                  for t in range(cost.shape[1])] for l in range(cost.shape[0])]
 
     def close(self):
@@ -448,11 +454,22 @@ class Watch:
         self._queries.close()
 
 
-def watch(sounds: Sequence[Sound], targets: Sequence[Sound], max_cost=None, engine: Optional[Engine] = None) -> Watch:
+def watch(sounds: Sequence[Sound], targets: Sequence[Sound], max_cost=None, engine: Optional[Engine] = None,
+          step: str = "symmetric", max_cost_per_frame=None) -> Watch:
     """Watch for `targets` in Sounds that are fed with push_samples / push_sounds (streaming DTW spotting, DESIGN.md
     section 2 "Watching"; dtw engines without a band).  The sounds must be resident and share one stream, sound i in lane
     i -- what one push_sounds(sounds, ...) leaves -- ValueError otherwise, before any device work.  max_cost: a scalar or
-    one value per target.  The first poll consumes everything the sounds hold."""
+    one value per target.  The first poll consumes everything the sounds hold.  step="paced": the paced step pattern
+    ("Paced watching": spans of about half to twice the target's frames, Spot.cost_per_frame set, and a NaN frame in a
+    sound costs a bounded stretch, not the rest of the lane); max_cost_per_frame (instead of max_cost; a scalar or one
+    value per target) is then a threshold on that mean: target t's events cost at most max_cost_per_frame * its frames, so
+    one value serves targets of every length."""
+    _spot_step(step)
+    if max_cost_per_frame is not None:
+        if max_cost is not None:
+            raise ValueError("max_cost and max_cost_per_frame exclude each other")
+        if step != "paced":
+            raise ValueError('max_cost_per_frame needs step="paced": only there is cost / frames a mean per-frame distance')
     sounds, targets = list(sounds), list(targets)
     first = sounds[0]._stream if sounds else None
     if first is None or not first[0].ptr or first[0].n_lanes != len(sounds) or \
@@ -472,14 +489,26 @@ def watch(sounds: Sequence[Sound], targets: Sequence[Sound], max_cost=None, engi
             raise ValueError("max_cost must be a scalar or one value per target")
         if np.isnan(mc).any():
             raise ValueError("max_cost must not be NaN")
+    if max_cost_per_frame is not None:
+        max_cost_per_frame = np.asarray(max_cost_per_frame, dtype=np.float64)
+        if max_cost_per_frame.ndim and max_cost_per_frame.size != len(targets):
+            raise ValueError("max_cost_per_frame must be a scalar or one value per target")
+        if np.isnan(max_cost_per_frame).any():
+            raise ValueError("max_cost_per_frame must not be NaN")
     flat, off = pack_segments([t.mfccs() for t in targets], st.ncoeffs, e.np_dtype)
+    frames = np.diff(off.astype(np.int64))
+    if max_cost_per_frame is not None:
+        # a sum per target, in f64 on the host: max_cost[t] = x * Fb[t]; a target without frames has no candidate anyway,
+        # and +inf * 0 would be the NaN that creation refuses
+        x = np.broadcast_to(max_cost_per_frame.reshape(-1), (len(targets),))
+        max_cost = np.where(frames >= 1, x * np.maximum(frames, 1).astype(np.float64), np.inf)
     q = e.queries(flat, off, st.ncoeffs)
     try:
-        sp = e.spotter(q, len(sounds), max_cost)
+        sp = e.spotter(q, len(sounds), max_cost, **_step_kw(step))
     except Exception:
         q.close()
         raise
-    return Watch(sounds, st, sp, q)
+    return Watch(sounds, st, sp, q, frames)
 
 
 class SoundDictionary:

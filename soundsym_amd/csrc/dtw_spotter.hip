@@ -18,6 +18,22 @@
 // tile.  Events reach the caller without a capacity that could drop one: a first pass that mutates nothing counts the
 // events per pair, an exclusive scan turns counts into places, the second pass writes into a log the spotter owns and
 // grows, ordered by (lane, target, end).
+//
+// Paced watching (ssym_spotter_create_step with SSYM_STEP_PACED; DESIGN.md 2 "Paced watching", 5.20):
+// dtw_watch_paced_kernel is to dtw_paced_kernel what dtw_watch_kernel is to dtw_spot_kernel.  Row i of the paced
+// recurrence needs rows i - 1 and i - 2 of E alone, so the state is TWO hand-off rows per pair (24 bytes per target frame)
+// and the step loop is dtw_paced_kernel's.  The reporting kernels, the log and the slices do not know the step.
+// In-place order of the two LDS rows (bound1 = the row above the chunk, bound2 = the one above that).  A chunk of R rows
+// (R = rowsHere, 1 ... 64; only R = 64 is followed by another chunk) has its bottom row in lane R - 1, which writes
+// bound1[x] at step x + R - 1, and the row above it in lane R - 2, which writes bound2[x] at step x + R - 2; for R = 1
+// the second row above is the OLD bound1, which lane 0 copies into bound2[x] at step x.  So entry x of either row is
+// overwritten at step x at the earliest, and at step x only by lane 0 itself (bound1: R = 1; bound2: R = 1 or 2).  Lane 0
+// reads entry tau of both rows at step tau, in program order BEFORE that step's stores, and uses it one step later
+// (its diagonals are column j - 1 = tau - 1), carried in registers.  The lanes of a wave run in lockstep and LDS keeps a
+// wave's accesses in order, so every read sees the row as the previous chunk (or the state load) left it.  Every valid
+// lane is active for every column, so after a chunk both rows hold Fb fresh entries: bound1 = row c0 + R - 1, bound2 = row
+// c0 + R - 2 (for first + c0 + R = 1 a row that does not exist, written as (+inf, none) and never read: "second row above
+// exists" is first + c0 >= 2).  A row that does not exist yet is neither loaded from the state nor read from LDS.
 #include "dtw_wave.hpp"
 
 #include <algorithm>
@@ -29,6 +45,8 @@ namespace ssym {
 // target, values per frame; frames a lane may consume (st is u32 and 0xffffffff means none: the dictionary's own limit)
 constexpr uint64_t kSpotterMaxTargetFrames = 4096;
 constexpr uint32_t kSpotterMaxDim = 64;
+// under SSYM_STEP_PACED: dtw_spot.hip's kPacedMaxTargetFrames, for its reason (two hand-off rows and the ring within LDS)
+constexpr uint64_t kSpotterPacedMaxTargetFrames = 2048;
 constexpr uint64_t kSpotterMaxLaneFrames = 2147483647;           // 2^31 - 1
 // the profile of one forward launch stays within ssym_dtw_spot_all's scratch limit: a longer push runs as several slices
 // of rows, which the carried state makes exact
@@ -178,9 +196,175 @@ __global__ __launch_bounds__(64) void dtw_watch_kernel(const WatchArgs a)
     }
 }
 
+// dtw_watch_paced_kernel's arguments: WatchArgs, with stateD / stateS holding TWO rows per (lane, target).  A struct of its
+// own: dtw_watch_kernel's arguments, and with them its register figures, stay what they were.
+struct WatchPacedArgs : WatchArgs {
+    uint64_t rowStride;          // entries from a pair's row n - 1 to its row n - 2: nLanes * sumFb
+};
+
+// Paced watching (the file header has the order argument of the two hand-off rows).
+template <int DIMR>
+__global__ __launch_bounds__(64) void dtw_watch_paced_kernel(const WatchPacedArgs a)
+{
+    extern __shared__ __attribute__((aligned(16))) double smem[];
+    constexpr int LD = wave_ld(DIMR);
+    double *bound1D = smem;                                         // [fbCap]   E of the row above the chunk: value ...
+    double *bound2D = smem + a.fbCap;                               // [fbCap]   E of the row above that: value ...
+    double *ring = smem + 2 * (size_t)a.fbCap;                      // [ringRows][LD]
+    uint32_t *bound1S = reinterpret_cast<uint32_t *>(ring + (size_t)a.ringRows * LD);     // [fbCap]   ... and start
+    uint32_t *bound2S = bound1S + a.fbCap;                          // [fbCap]   ... and start
+    const double INF = __builtin_inf();
+    const int lane = threadIdx.x;
+    const int dim = (int)a.dim;
+    const uint32_t ringMask = a.ringRows - 1;
+
+    for (uint32_t k = blockIdx.x; k < a.nPairs; k += gridDim.x) {
+        const uint32_t l = k / a.nTgt, t = k % a.nTgt;
+        const LaneStep s = a.steps[l];
+        const int Fb = (int)(a.tgtOff[t + 1] - a.tgtOff[t]);
+        if (s.m == 0 || Fb == 0)
+            continue;                       // nothing new, or a target without frames: the state stays what it is
+        const double *b0 = a.tgtRaw + a.tgtOff[t] * dim;
+        const size_t sBase = (size_t)l * a.sumFb + a.tgtOff[t];
+        const size_t pBase = s.profOff + (size_t)t * s.m;
+
+        // hand-off rows in, those that exist (the barrier: the previous pair's store-back has read the rows)
+        __syncthreads();
+        for (int j = lane; j < Fb; j += 64) {
+            if (s.first >= 1) {
+                bound1D[j] = a.stateD[sBase + j];
+                bound1S[j] = a.stateS[sBase + j];
+            }
+            if (s.first >= 2) {
+                bound2D[j] = a.stateD[a.rowStride + sBase + j];
+                bound2S[j] = a.stateS[a.rowStride + sBase + j];
+            }
+        }
+        // every lane starts from the stored best, as in dtw_watch_kernel
+        double bestD = a.bestD[k];
+        uint32_t bestEnd = a.bestE[k], bestSt = a.bestS[k];
+        for (uint32_t c0 = 0; c0 < s.m; c0 += 64) {
+            const uint32_t rl = c0 + (uint32_t)lane;
+            const bool rowValid = rl < s.m;
+            const uint32_t r = s.first + rl;          // the absolute row: what the starts and the best's end hold
+            const int rowsHere = (int)min(64u, s.m - c0);
+            const bool row1 = s.first + c0 >= 1;      // the row above the chunk exists ...
+            const bool row2 = s.first + c0 >= 2;      // ... and the one above that
+            double ar[DIMR];
+            wave_load_frame(ar, s.rows + (size_t)(rowValid ? rl : c0) * dim, dim);
+            double mineN = INF, mineE = INF;                        // N(r, j-1), E(r, j-1)
+            uint32_t mineNS = kNone, mineES = kNone;
+            double d1D = INF, d2D = INF;                            // E(r-1, j-1), E(r-2, j-1)
+            uint32_t d1S = kNone, d2S = kNone;
+            double in1D = INF, in2D = INF;                          // lane 0: entry tau - 1 of the two hand-off rows
+            uint32_t in1S = kNone, in2S = kNone;
+            const int tauEnd = Fb - 1 + rowsHere;     // exclusive: lane l works on column tau - l
+            for (int tau = 0; tau < tauEnd; ++tau) {
+                // (the refill's barrier also orders the hand-off rows: the loads above and the previous chunk's writes
+                // are done before tau = 0 goes on)
+                if ((tau & 63) == 0)
+                    wave_refill<DIMR>(ring, ringMask, b0, dim, Fb, tau);
+                const int j = tau - lane;
+                const double c = wave_cell_cost(ar, ring, ringMask, min(max(j, 0), Fb - 1), a.squared);
+                const double upD = shfl_up1(mineE);       // E(r-1, j) and its start, for lanes >= 1: the next step's d1
+                const uint32_t upS = (uint32_t)shfl_up1((int)mineES);
+                if (lane == 0) {
+                    // its diagonals are entry tau - 1 of the hand-off rows, read one step ago; entry tau is read now,
+                    // BEFORE this step's stores, which may overwrite it
+                    d1D = in1D;
+                    d1S = in1S;
+                    d2D = in2D;
+                    d2S = in2S;
+                    in1D = in2D = INF;
+                    in1S = in2S = kNone;
+                    if (j < Fb) {
+                        if (row1) {
+                            in1D = bound1D[j];
+                            in1S = bound1S[j];
+                        }
+                        if (row2) {
+                            in2D = bound2D[j];
+                            in2S = bound2S[j];
+                        }
+                    }
+                }
+                // E(r-2, j) for the next step: the d1 of lane l - 1, lane 0's being what it took from the hand-off row
+                const double nxD = shfl_up1(d1D);
+                const uint32_t nxS = (uint32_t)shfl_up1((int)d1S);
+                const bool active = rowValid && j >= 0 && j < Fb;
+                if (active) {
+                    double nD = c, eD = c;                // column 0: a path may start at any source frame, in state N
+                    uint32_t nS = r, eS = r;
+                    if (j > 0) {
+                        double pD = d1D;
+                        uint32_t pS = d1S;
+                        if (d2D < pD) {
+                            pD = d2D;
+                            pS = d2S;
+                        }
+                        nD = __dadd_rn(c, pD);
+                        nS = pS;
+                        const double hD = __dadd_rn(c, mineN);
+                        eD = nD;
+                        eS = nS;
+                        if (hD < nD) {
+                            eD = hD;
+                            eS = mineNS;
+                        }
+                    }
+                    if (rowsHere == 1) {                  // (lane 0) the row that was above becomes the second row above
+                        bound2D[j] = in1D;
+                        bound2S[j] = in1S;
+                    }
+                    if (lane == rowsHere - 1) {           // the chunk's bottom row
+                        bound1D[j] = eD;
+                        bound1S[j] = eS;
+                    }
+                    if (lane == rowsHere - 2) {           // and the row above it
+                        bound2D[j] = eD;
+                        bound2S[j] = eS;
+                    }
+                    if (j == Fb - 1 && eD < bestD) {
+                        bestD = eD;
+                        bestEnd = r;
+                        bestSt = eS;
+                    }
+                    mineN = nD;
+                    mineNS = nS;
+                    mineE = eD;
+                    mineES = eS;
+                }
+                d1D = upD;
+                d1S = upS;
+                d2D = nxD;
+                d2S = nxS;
+            }
+            // a valid row's last active step was column Fb - 1: what the lane carries is its entry of the profile
+            if (rowValid) {
+                a.profD[pBase + rl] = mineE;
+                a.profS[pBase + rl] = mineES;
+            }
+        }
+        // hand-off rows out: the last chunk's two bottom rows, whichever lanes wrote them
+        __syncthreads();
+        for (int j = lane; j < Fb; j += 64) {
+            a.stateD[sBase + j] = bound1D[j];
+            a.stateS[sBase + j] = bound1S[j];
+            a.stateD[a.rowStride + sBase + j] = bound2D[j];
+            a.stateS[a.rowStride + sBase + j] = bound2S[j];
+        }
+        SSYM_SPOT_FIRST_MIN(bestD, bestEnd, bestSt)
+        if (lane == 0) {
+            a.bestD[k] = bestD;
+            a.bestE[k] = bestEnd;
+            a.bestS[k] = bestSt;
+        }
+    }
+}
+
 // ---- reporting ----------------------------------------------------------------------------------------------------------
 
-constexpr int kRepPairs = 4;                // pairs per workgroup: few, so that many workgroups hide each other's latency
+constexpr int kRepPairs = 4;               // pairs per workgroup: few, so that many workgroups hide each other's latency
 constexpr int kRepLd = 65;                  // LDS stride of a pair's 64-row tile: the walking lanes read distinct banks
 
 struct ReportArgs {
@@ -359,9 +543,10 @@ struct ssym_spotter {
     ssym_ctx *ctx = nullptr;
     const ssym_queries *q = nullptr;
     uint32_t nLanes = 0, nTgt = 0, nPairs = 0;
+    uint32_t step = SSYM_STEP_SYMMETRIC;     // what the forward launch and the state's size go by
     std::vector<uint64_t> consumed;          // frames per lane
     // device, allocated at creation
-    double *stateD = nullptr;                // [nLanes][sumFb]
+    double *stateD = nullptr;                // [nLanes][sumFb]; paced: [2][nLanes][sumFb], row n - 1 then row n - 2
     uint32_t *stateS = nullptr;
     double *pairD = nullptr;                 // [2][nPairs]: bestD, pendD
     uint32_t *pairW = nullptr;               // [5][nPairs]: bestE, bestS, pendS, pendE, last
@@ -413,14 +598,19 @@ int32_t check_handle(ssym_ctx *ctx, const ssym_spotter *sp, const char *fn)
     return SSYM_OK;
 }
 
-int32_t spotter_create(ssym_ctx *ctx, const ssym_queries *q, uint32_t n_lanes, const double *max_cost, ssym_spotter **out)
+// fn: ssym_spotter_create (step = SSYM_STEP_SYMMETRIC) or ssym_spotter_create_step
+int32_t spotter_create(ssym_ctx *ctx, const ssym_queries *q, uint32_t n_lanes, const double *max_cost, uint32_t step,
+                       ssym_spotter **out, const char *fn)
 {
-    const char *fn = "ssym_spotter_create";
     if (!out) {
         ctx->err = std::string(fn) + ": out is NULL";
         return SSYM_E_INVALID;
     }
     *out = nullptr;
+    if (step != SSYM_STEP_SYMMETRIC && step != SSYM_STEP_PACED) {
+        ctx->err = std::string(fn) + ": step must be SSYM_STEP_SYMMETRIC or SSYM_STEP_PACED";
+        return SSYM_E_INVALID;
+    }
     int32_t rc = check_spot_ctx(ctx, fn);
     if (rc != SSYM_OK)
         return rc;
@@ -435,7 +625,8 @@ int32_t spotter_create(ssym_ctx *ctx, const ssym_queries *q, uint32_t n_lanes, c
                 ctx->err = std::string(fn) + ": max_cost[" + std::to_string(t) + "] is NaN";
                 return SSYM_E_INVALID;
             }
-    rc = check_spot_limits(ctx, fn, tgt.n ? tgt.max_frames : 0, tgt.dim, kSpotterMaxTargetFrames, kSpotterMaxDim);
+    rc = check_spot_limits(ctx, fn, tgt.n ? tgt.max_frames : 0, tgt.dim,
+                           step == SSYM_STEP_PACED ? kSpotterPacedMaxTargetFrames : kSpotterMaxTargetFrames, kSpotterMaxDim);
     if (rc != SSYM_OK)
         return rc;
     if ((uint64_t)n_lanes * tgt.n > 0xfffffffeull) {
@@ -449,9 +640,10 @@ int32_t spotter_create(ssym_ctx *ctx, const ssym_queries *q, uint32_t n_lanes, c
     sp->nLanes = n_lanes;
     sp->nTgt = tgt.n;
     sp->nPairs = n_lanes * tgt.n;
+    sp->step = step;
     sp->consumed.assign(n_lanes, 0);
     sp->hSteps.resize(n_lanes);
-    const size_t nState = (size_t)n_lanes * tgt.total_frames, nP = sp->nPairs;
+    const size_t nState = (size_t)n_lanes * tgt.total_frames * (step == SSYM_STEP_PACED ? 2 : 1), nP = sp->nPairs;
     rc = alloc_n(ctx, &sp->stateD, nState);
     if (rc == SSYM_OK)
         rc = alloc_n(ctx, &sp->stateS, nState);
@@ -609,7 +801,7 @@ int32_t spotter_run(ssym_ctx *ctx, ssym_spotter *sp, const std::vector<const dou
     const size_t nP = sp->nPairs;
     const InitArgs ia = init_args(sp);
 
-    WatchArgs wa{};
+    WatchPacedArgs wa{};                     // (the symmetric launch takes its WatchArgs base)
     wa.steps = sp->dSteps;
     wa.tgtRaw = tgt.raw;
     wa.tgtOff = tgt.off;
@@ -628,7 +820,8 @@ int32_t spotter_run(ssym_ctx *ctx, ssym_spotter *sp, const std::vector<const dou
     const WaveGeom g = wave_geom(ctx, tgt.max_frames, tgt.dim, nP);
     wa.fbCap = g.fbCap;
     wa.ringRows = g.ringRows;
-    const size_t lds = spot_lds_bytes(g, SSYM_STEP_SYMMETRIC);       // one hand-off row
+    wa.rowStride = (uint64_t)nL * tgt.total_frames;
+    const size_t lds = spot_lds_bytes(g, sp->step);                  // one hand-off row, or the paced pattern's two
     const unsigned repGrid = (unsigned)((nP + kRepPairs - 1) / kRepPairs);
 
     ReportArgs ra{};
@@ -667,7 +860,9 @@ int32_t spotter_run(ssym_ctx *ctx, ssym_spotter *sp, const std::vector<const dou
         SSYM_HIP_CHECK(ctx, hipMemcpyAsync(sp->dSteps, sp->hSteps.data(), sizeof(LaneStep) * nL, hipMemcpyHostToDevice, st));
         SSYM_HIP_CHECK(ctx, hipEventRecord(ctx->ev[0], st));
         if (any) {
-            rc = wave_launch(ctx, SSYM_WAVE_KERNEL(dtw_watch_kernel, g.dimr), g.grid, lds, wa);
+            rc = sp->step == SSYM_STEP_PACED
+                     ? wave_launch(ctx, SSYM_WAVE_KERNEL(dtw_watch_paced_kernel, g.dimr), g.grid, lds, wa)
+                     : wave_launch<WatchArgs>(ctx, SSYM_WAVE_KERNEL(dtw_watch_kernel, g.dimr), g.grid, lds, wa);
             if (rc != SSYM_OK)
                 return rc;
         }
@@ -935,7 +1130,19 @@ int32_t ssym_spotter_create(ssym_ctx *ctx, const ssym_queries *q, uint32_t n_lan
 {
     if (!ctx)
         return SSYM_E_INVALID;
-    return guarded(ctx, [&]() -> int32_t { return spotter_create(ctx, q, n_lanes, max_cost, out); });
+    return guarded(ctx, [&]() -> int32_t {
+        return spotter_create(ctx, q, n_lanes, max_cost, SSYM_STEP_SYMMETRIC, out, "ssym_spotter_create");
+    });
+}
+
+int32_t ssym_spotter_create_step(ssym_ctx *ctx, const ssym_queries *q, uint32_t n_lanes, const double *max_cost,
+                                 uint32_t step, ssym_spotter **out)
+{
+    if (!ctx)
+        return SSYM_E_INVALID;
+    return guarded(ctx, [&]() -> int32_t {
+        return spotter_create(ctx, q, n_lanes, max_cost, step, out, "ssym_spotter_create_step");
+    });
 }
 
 int32_t ssym_spotter_destroy(ssym_ctx *ctx, ssym_spotter *sp)

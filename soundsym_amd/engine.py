@@ -376,10 +376,12 @@ class Spotter:
     """The targets of a query set watched in `n_lanes` growing sources (ssym_spotter; definition in
     include/soundsym_amd.h and DESIGN.md section 2 "Watching"): a push costs the new frames alone, the best span so far is
     ssym_dtw_spot's for everything consumed, and occurrences are reported as events by a causal rule.  The spotter reads
-    the query set's resident features for as long as it lives: it keeps `q` alive and must be closed before it."""
+    the query set's resident features for as long as it lives: it keeps `q` alive and must be closed before it.
+    `step` is the pattern it was created with ("Paced watching" for "paced": the best is ssym_dtw_spot_step's)."""
 
-    def __init__(self, engine: "Engine", ptr: int, q: _Handle, n_lanes: int):
+    def __init__(self, engine: "Engine", ptr: int, q: _Handle, n_lanes: int, step: str = "symmetric"):
         self.engine, self.ptr, self.q, self.n_lanes, self.n_targets, self.dim = engine, ptr, q, n_lanes, q.n, q.dim
+        self.step = step
         self.n_events = 0
 
     def _run(self, call, new_rows, want_profile: bool):
@@ -1002,14 +1004,21 @@ class Engine:
                                                float(f_hi), int(capacity), ctypes.byref(out)), self.ctx)
         return Stream(self, out.value, int(n_lanes), int(ncoeffs), float(sample_rate))
 
-    def spotter(self, q: _Handle, n_lanes: int = 1, max_cost=None) -> Spotter:
+    def spotter(self, q: _Handle, n_lanes: int = 1, max_cost=None, step: str = "symmetric") -> Spotter:
         """ssym_spotter_create: the targets of `q` watched in `n_lanes` growing sources (dtw engines without a band).
-        max_cost: a scalar or one value per target; an event costs at most that."""
+        max_cost: a scalar or one value per target; an event costs at most that (a sum, whatever the step).
+        step="paced": ssym_spotter_create_step with SSYM_STEP_PACED ("Paced watching": slope-bounded spans, targets of
+        at most 2048 frames); "symmetric" is ssym_spotter_create itself."""
+        which = _spot_step(step)
         lanes, mc = _spotter_args(q, n_lanes, max_cost)
         out = ctypes.c_void_p()
-        nat.check(nat.lib().ssym_spotter_create(self.ctx, q.ptr, lanes, mc.ctypes.data if mc is not None else None,
-                                                ctypes.byref(out)), self.ctx)
-        return Spotter(self, out.value, q, lanes)
+        head = (self.ctx, q.ptr, lanes, mc.ctypes.data if mc is not None else None)
+        if which == nat.STEP_SYMMETRIC:
+            rc = nat.lib().ssym_spotter_create(*head, ctypes.byref(out))
+        else:
+            rc = nat.lib().ssym_spotter_create_step(*head, which, ctypes.byref(out))
+        nat.check(rc, self.ctx)
+        return Spotter(self, out.value, q, lanes, step)
 
     @staticmethod
     def mfcc_num_frames(n_samples: int, pad_tail: bool = False) -> int:
