@@ -895,6 +895,7 @@ SSYM_API int32_t ssym_stream_reset(ssym_ctx *ctx, ssym_stream *st, uint32_t lane
  *               3. if candidate and (pend = none or d < pend.cost):   pend = (d, s, i)
  *   flush   : if pend: emit pend; last = pend.end; pend = none        (an explicit call: "the lane has ended")
  *   nothing : a target without frames never has a candidate; its best is (+inf, SSYM_NO_MATCH, SSYM_NO_MATCH)
+ *             and every row of its profile outputs is (+inf, SSYM_NO_MATCH)
  * So: however the frames of a lane are cut into pushes, the profile, the best after every push and the events (with the
  * push that emits each) are bit for bit those of one push of the whole; the emitted spans of one (l,t) are pairwise
  * disjoint in frames and their ends ascend; every emitted cost has the bits ssym_pair_matrix(exact = 1) gives for (frames

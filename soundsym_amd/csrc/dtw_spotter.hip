@@ -491,6 +491,28 @@ __global__ __launch_bounds__(64) void spotter_report_kernel(const ReportArgs a)
     }
 }
 
+// The profile rows of the targets without frames, the workgroups taking the pairs in turn: (+inf, none).  The watch kernels skip such a
+// pair, and the profile scratch is a cached block that goes to the caller's profile outputs as it stands: without this
+// those rows held whatever the context ran before.  Launched only for a query set that has such a target, and only
+// when a profile output is asked for (the reporting pass never reads these rows).
+__global__ __launch_bounds__(64) void spotter_no_frames_kernel(const LaneStep *__restrict__ steps,
+                                                               const uint64_t *__restrict__ tgtOff, uint32_t nTgt,
+                                                               uint32_t nPairs, double *__restrict__ profD,
+                                                               uint32_t *__restrict__ profS)
+{
+    for (uint32_t k = blockIdx.x; k < nPairs; k += gridDim.x) {
+        const uint32_t l = k / nTgt, t = k % nTgt;
+        if (tgtOff[t + 1] != tgtOff[t])
+            continue;
+        const LaneStep s = steps[l];
+        const size_t pBase = s.profOff + (size_t)t * s.m;
+        for (uint32_t rl = threadIdx.x; rl < s.m; rl += 64) {
+            profD[pBase + rl] = __builtin_inf();
+            profS[pBase + rl] = kNone;
+        }
+    }
+}
+
 // cnt[0 ... n - 1] -> its exclusive prefix sums in place, the total in cnt[n].  One workgroup: thread i sums a run of
 // consecutive entries, the 1024 sums are scanned in LDS, the run is rewritten.
 __global__ __launch_bounds__(1024) void spotter_scan_kernel(uint32_t *cnt, uint32_t n)
@@ -838,6 +860,9 @@ int32_t spotter_run(ssym_ctx *ctx, ssym_spotter *sp, const std::vector<const dou
     ra.last = ia.last;
     ra.cnt = sp->dCnt;
 
+    bool emptyTarget = false;                // a target without frames: no kernel writes its rows of the profile
+    for (uint32_t t = 0; t < nT; ++t)
+        emptyTarget = emptyTarget || tgt.h_off[t + 1] == tgt.h_off[t];
     uint64_t outLane = 0;                    // where a lane's profile starts in the outputs: [lane][target][new row]
     std::vector<uint64_t> outOff(nL);
     for (uint32_t l = 0; l < nL; ++l) {
@@ -892,6 +917,11 @@ int32_t spotter_run(ssym_ctx *ctx, ssym_spotter *sp, const std::vector<const dou
         sp->nEvents += total;
         // the slice's profile into the outputs: one piece when the call is one slice, else per lane a strided copy
         if (any && (out_prof_d || out_prof_s)) {
+            if (emptyTarget) {
+                spotter_no_frames_kernel<<<(unsigned)std::min<size_t>(nP, 65536), 64, 0, st>>>(sp->dSteps, tgt.off, nT, sp->nPairs,
+                                                                                              profD, profS);
+                SSYM_HIP_CHECK(ctx, hipGetLastError());
+            }
             if (nSlices == 1) {
                 if (out_prof_d)
                     SSYM_HIP_CHECK(ctx, hipMemcpyAsync(out_prof_d, profD, sizeof(double) * off, outKind, st));

@@ -125,6 +125,8 @@ def _check_split(w, lanes, cut_lists, profiles=None, flush_end=True, after_push=
                 assert np.array_equal(np.isnan(pd[l][t]), np.isnan(d[lo:hi])), (l, t, p)
                 assert same_floats(pd[l][t], d[lo:hi]), (l, t, p)
                 assert np.array_equal(ps[l][t], s[lo:hi].astype(np.uint32)), (l, t, p)
+            else:                                               # a target without frames: "no path" in every new row
+                assert (pd[l][t] == np.inf).all() and (ps[l][t] == NO).all(), (l, t, p)
             _same_events(ev.get((l, t), []), per_push[p])
             assert _bits(cost[l, t]) == _bits(bests[p][0]) and (int(start[l, t]), int(end[l, t])) == bests[p][1:], (l, t, p)
         if after_push is not None:
