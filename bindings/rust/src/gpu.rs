@@ -158,6 +158,12 @@ extern "C" {
                                tgt_idx: *const u32, n_pairs: u32, index_base: u32, step: u32, out_cost: *mut f64,
                                out_len: *mut u32, path_offsets: *const u64, out_path: *mut u32, map_offsets: *const u64,
                                out_map: *mut u32, flags: u32) -> i32;
+    // ssym_match_queries / ssym_pair_matrix with a step pattern: SSYM_STEP_PACED searches under the paced pattern (the cost of
+    // a pair is ssym_dtw_align_step's paced cost, +inf without a paced shape; costs are sums over the target's frames)
+    pub fn ssym_match_queries_step(ctx: *mut SsymCtx, dict: *const SsymDict, q: *const SsymQueries, distance: *const f64,
+                                   index_base: u32, step: u32, out_idx: *mut u32, out_cost: *mut f64, flags: u32) -> i32;
+    pub fn ssym_pair_matrix_step(ctx: *mut SsymCtx, dict: *const SsymDict, q: *const SsymQueries, step: u32,
+                                 out_matrix: *mut f64) -> i32;
 
     // source-sharded runs, exchange done by the caller (device pointers): filter / all-reduce(MIN) / finish / merge
     pub fn ssym_match_begin(ctx: *mut SsymCtx, dict: *const SsymDict, q: *const SsymQueries, distance: *const f64,

@@ -2,7 +2,7 @@
 """examples/warp.py -- a reconstruction whose matches follow the target's timing.
 
     python examples/warp.py -s TARGET.wav -d DICT.wav -o OUT.wav [--plain PLAIN.wav] [--search 0] [--depth 5] [--threshold 4]
-                            [--seed 0]
+                            [--seed 0] [--paced]
 
 Both recordings are cut by a Partitioner trained on the dictionary recording, as examples/reconstruction.py --partition
 cuts them.  Every target segment is matched against the dictionary's segments under DTW, aligned with its match, and the
@@ -12,6 +12,10 @@ reconstruction (reconstruct_from_dictionary: matches cut off or padded with sile
 --search N (at most 512 samples) resynthesises with the waveform-similarity search instead (ssym_reconstruct_wsola): every
 source frame may move up to N samples to where it continues the frame before it in phase; the share of frames that did
 move is printed.
+--paced matches, aligns and warps under the paced step pattern (match_step="paced", step="paced": ssym_match_queries_step
+and ssym_dtw_align_step with SSYM_STEP_PACED): every target frame takes one source frame, the match is the segment with the
+least such cost, and no target falls back to the length fit because the symmetric search chose a segment the pattern cannot
+align.  Beside the output it prints how many targets the symmetric search would have handed such a pair.
 """
 import argparse
 import os
@@ -35,6 +39,7 @@ def main(argv=None):
     ap.add_argument("--depth", type=int, default=5)
     ap.add_argument("--threshold", type=int, default=4)
     ap.add_argument("--seed", type=int, default=0, help="draws the mixture's starting frames")
+    ap.add_argument("--paced", action="store_true", help="match, align and warp under the paced step pattern")
     args = ap.parse_args(argv)
 
     engine = Engine(metric="dtw", dtype="f64")
@@ -46,9 +51,16 @@ def main(argv=None):
     cut = SoundDictionary.from_segments(target, partitioner.partition_other(target), engine=engine)
     sequence = SoundSequence.new([s for s in cut.sounds if s.num_frames() > 0])
 
+    step = {"step": "paced", "match_step": "paced"} if args.paced else {}
+    if args.paced:
+        paced_idx, paced_cost = dictionary.match_indices(sequence.sounds(), step="paced", per_frame=True)
+        lost = sum(len(a) == 0 for a in dictionary.align(sequence.sounds(), step="paced"))
+        print(f"paced: {int(np.isfinite(paced_cost).sum())} of {len(paced_cost)} targets matched, mean cost per frame "
+              f"{float(np.mean(paced_cost[np.isfinite(paced_cost)])) if np.isfinite(paced_cost).any() else float('nan'):.4f}; "
+              f"the symmetric search would have handed {lost} of them a pair with no paced path")
     if args.search:
-        samples, pcm, pos, m_off = dictionary.warp(sequence.sounds(), want_pcm32=True, search=args.search, want_pos=True)
-        aligned = dictionary.align(sequence.sounds())
+        samples, pcm, pos, m_off = dictionary.warp(sequence.sounds(), want_pcm32=True, search=args.search, want_pos=True, **step)
+        aligned = dictionary.align(sequence.sounds(), **step)
         moved = frames = 0
         for t, al in enumerate(aligned):
             nominal = np.asarray(al.frame_map, dtype=np.uint64) * np.uint64(256)
@@ -56,7 +68,7 @@ def main(argv=None):
             frames += nominal.size
         print(f"search {args.search}: {moved} of {frames} frames ({100.0 * moved / max(frames, 1):.1f} %) moved off their nominal place")
     else:
-        samples, pcm = sequence.reconstruct_warped_from_dictionary(dictionary, want_pcm32=True)
+        samples, pcm = sequence.reconstruct_warped_from_dictionary(dictionary, want_pcm32=True, **step)
     write_wav32(args.o, sample_rate=target.sample_rate(), pcm=pcm)
     print(f"{len(dictionary.sounds)} dictionary segments, {len(sequence.sounds())} target segments, "
           f"{samples.size} samples -> {args.o}")

@@ -216,6 +216,46 @@ class SoundDictionary {
                                      distances, idx.data(), nullptr));
         return idx;
     }
+    // match_indices under a step pattern (ssym_match_queries_step): SSYM_STEP_PACED searches under the paced pattern of
+    // soundsym_amd.h "Paced matching" -- the cost of a pair is its paced alignment's (+inf where the shapes admit no paced
+    // path), costs[t] (if asked for) the winner's, a sum over the target's frames; a target nothing fits gets 0 and +inf
+    std::vector<uint32_t> match_indices_step(const std::vector<ArcSound> &targets, const double *distances, uint32_t step,
+                                             std::vector<double> *costs = nullptr) const
+    {
+        if (sounds.empty())
+            throw EmptyDictionary();
+        std::vector<double> flat;
+        std::vector<uint64_t> off;
+        pack_features(targets, flat, off);
+        ssym_queries *q = nullptr;
+        ctx_->check(ssym_queries_create(ctx_->get(), flat.data(), off.data(), (uint32_t)targets.size(),
+                                        (uint32_t)NCOEFFS, &q));
+        std::vector<uint32_t> idx(targets.size());
+        if (costs)
+            costs->assign(targets.size(), 0.0);
+        int32_t rc = ssym_match_queries_step(ctx_->get(), resident(), q, distances, 0, step, idx.data(),
+                                             costs ? costs->data() : nullptr, 0);
+        ssym_queries_destroy(ctx_->get(), q);
+        ctx_->check(rc);
+        return idx;
+    }
+    // the [sounds][targets] costs of a step pattern (ssym_pair_matrix_step), row-major
+    std::vector<double> pair_matrix_step(const std::vector<ArcSound> &targets, uint32_t step) const
+    {
+        if (sounds.empty())
+            throw EmptyDictionary();
+        std::vector<double> flat;
+        std::vector<uint64_t> off;
+        pack_features(targets, flat, off);
+        ssym_queries *q = nullptr;
+        ctx_->check(ssym_queries_create(ctx_->get(), flat.data(), off.data(), (uint32_t)targets.size(),
+                                        (uint32_t)NCOEFFS, &q));
+        std::vector<double> out(sounds.size() * targets.size());
+        int32_t rc = ssym_pair_matrix_step(ctx_->get(), resident(), q, step, out.data());
+        ssym_queries_destroy(ctx_->get(), q);
+        ctx_->check(rc);
+        return out;
+    }
 
     // the k best sounds per target, best first (ssym_match_topk; the crate has no counterpart:
     // at_distance keeps only the first minimum, :361-367)

@@ -449,6 +449,34 @@ SSYM_API int32_t ssym_dtw_align_step(ssym_ctx *ctx, const ssym_dict *dict, const
                                      double *out_cost, uint32_t *out_len, const uint64_t *path_offsets, uint32_t *out_path,
                                      const uint64_t *map_offsets, uint32_t *out_map, uint32_t flags);
 
+/* Paced matching (DESIGN.md section 2 "Paced matching" and section 5.21): ssym_match_queries and ssym_pair_matrix with a
+ * step pattern.  SSYM_STEP_SYMMETRIC makes them the existing calls: one host path, the same kernels, the same bits
+ * (ssym_pair_matrix_step is then ssym_pair_matrix with exact = 1).  Under SSYM_STEP_PACED, for source s (Fa frames) and
+ * target t (Fb frames), cost(s, t) is EXACTLY the cost of "Paced alignment" above: the shape rule decided before the
+ * recurrence (Fa = 0, Fb = 0 or Fa outside floor((Fb-1)/2) + 1 ... 2 Fb - 1 gives +inf), column 0 pinned at source frame 0,
+ * the states N, H, E, P with their strict < comparisons, the same arithmetic (f64, k ascending, every sub, mul, add and
+ * sqrt rounded separately, no contraction) over the whole matrix, the context's squared option.  So a matrix entry has the
+ * bits ssym_dtw_align_step(SSYM_STEP_PACED) returns in out_cost for that pair, and is not finite exactly where that is not.
+ * Per target the result follows ssym_match_queries' dtw rule: idx[t] = argmin_s |cost(s,t) - distance[t]| (distance NULL
+ * = 0), the first minimum wins, the fold starts at (0, +inf), a NaN or +inf key never wins, out_cost (nullable) is the
+ * winner's cost, and a target nothing beats gets 0 + index_base and +inf.  Whenever out_cost[t] is finite,
+ * ssym_dtw_align_step(SSYM_STEP_PACED) on (out_idx[t], t) gives out_len = Fb and that cost, bit for bit.  Every admissible
+ * path has Fb cells, so cost / Fb is a true mean per frame; costs stay sums here and the caller divides.  Neither cost
+ * bounds the other (a paced step that skips a source frame is no symmetric step), so no filter runs in front: every
+ * shape-feasible pair is evaluated in f64, and SSYM_DTW_FORCE_EXACT and SSYM_DTW_PRUNE mean nothing under SSYM_STEP_PACED
+ * and are ignored there.  SSYM_OUT_DEVICE is honoured.  index_base is honoured, so the results of dictionary shards go
+ * through ssym_merge_shards as they are.  out_matrix: [n_sources][n_targets] f64, HOST memory.
+ * Limits with SSYM_STEP_PACED: a dtw context without a band, dim <= 64, every target of at most 2048 and every source of at
+ * most 4096 frames (ssym_dtw_align_step's, so every reported match can be aligned); beyond them and on a refcos context:
+ * SSYM_E_UNSUPPORTED before any device work, with the outputs unwritten.  An unknown step: SSYM_E_INVALID.  An empty
+ * dictionary: SSYM_E_EMPTY_DICT.  n_targets = 0 succeeds and does nothing.  One synchronisation per call.
+ * ssym_get_timings afterwards: main_ms = the forward kernel, reduce_ms = the fold, n_pairs = n_sources x n_targets. */
+SSYM_API int32_t ssym_match_queries_step(ssym_ctx *ctx, const ssym_dict *dict, const ssym_queries *q, const double *distance,
+                                         uint32_t index_base, uint32_t step, uint32_t *out_idx, double *out_cost,
+                                         uint32_t flags);
+SSYM_API int32_t ssym_pair_matrix_step(ssym_ctx *ctx, const ssym_dict *dict, const ssym_queries *q, uint32_t step,
+                                       double *out_matrix);
+
 /* Source-sharded multi-GPU, dtw metric: the one real exchange the path has.  Each rank's filter gives,
  * per target, an upper bound on the best key in ITS shard; a rank whose shard does not hold a
  * target's neighbour would otherwise re-score ~10^2 of its own pairs per target for nothing.

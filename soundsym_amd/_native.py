@@ -62,6 +62,7 @@ ABI_SYMBOLS = [
     "ssym_dtw_spot", "ssym_spot_queries", "ssym_dtw_spot_all",
     "ssym_dtw_spot_step", "ssym_spot_queries_step", "ssym_dtw_spot_all_step",
     "ssym_dtw_align_step",
+    "ssym_match_queries_step", "ssym_pair_matrix_step",
     "ssym_spotter_create_step",
     "ssym_reconstruct_warped", "ssym_reconstruct_wsola",
 ]
@@ -253,6 +254,10 @@ def lib() -> ctypes.CDLL:
     L.ssym_dtw_align_sizes.argtypes = [vp, vp, vp, vp, u32, u32, vp, vp]
     L.ssym_dtw_align.restype = i32
     L.ssym_dtw_align.argtypes = [vp, vp, vp, vp, vp, u32, u32, vp, vp, vp, vp, vp, vp, u32]
+    L.ssym_match_queries_step.restype = i32
+    L.ssym_match_queries_step.argtypes = [vp, vp, vp, vp, u32, u32, vp, vp, u32]
+    L.ssym_pair_matrix_step.restype = i32
+    L.ssym_pair_matrix_step.argtypes = [vp, vp, vp, u32, vp]
     L.ssym_dtw_align_step.restype = i32
     L.ssym_dtw_align_step.argtypes = [vp, vp, vp, vp, vp, u32, u32, u32, vp, vp, vp, vp, vp, vp, u32]
     L.ssym_dtw_spot.restype = i32

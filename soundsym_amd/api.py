@@ -364,6 +364,17 @@ def _per_frame(step, cost, frames):
     return float(cost) / float(frames) if step == "paced" else None
 
 
+def _match_kw(step, match_step):
+    """The keywords the match of an align / warp passes on for `match_step`: none at all for None (the symmetric search,
+    the call as it was) and for "symmetric"; "paced" searches under the paced pattern and needs the alignment to be paced."""
+    if match_step is None:
+        return {}
+    _spot_step(match_step)
+    if match_step == "paced" and step != "paced":
+        raise ValueError('match_step="paced" needs step="paced": the match it picks is one the paced alignment can align')
+    return {} if match_step == "symmetric" else {"step": match_step}
+
+
 class Spot:
     """Where inside a dictionary recording a target sounds (ssym_dtw_spot / ssym_spot_queries; definition in
     include/soundsym_amd.h and DESIGN.md section 2 "Spotting"): `source_index` into the dictionary's sounds, the frames
@@ -651,23 +662,49 @@ class SoundDictionary:
         idx, _ = self.engine.match_one(self.resident(), other.mfccs(), distance)
         return self.sounds[idx]              # Some(self.sounds[min_idx].clone())
 
-    def match_indices(self, targets: Sequence[Sound], distances=None):
-        """Batched form of the loops at src/sound.rs:442-446 and :453-454."""
+    def match_indices(self, targets: Sequence[Sound], distances=None, step: str = "symmetric", per_frame: bool = False):
+        """Batched form of the loops at src/sound.rs:442-446 and :453-454.  step="paced": the search runs under the paced
+        step pattern (ssym_match_queries_step with SSYM_STEP_PACED, dtw engines): the cost of a pair is its paced
+        alignment's, +inf where the shapes admit no paced path, so the match is one align(step="paced") can align, at the
+        same cost; a target nothing fits gets index 0 and +inf.  Every paced path has one cell per target frame, so with
+        per_frame=True the distances are means per frame (multiplied by the target's frames before the call) and the
+        returned costs are divided by them: values that compare across targets of every length."""
+        _spot_step(step)
+        if per_frame and step != "paced":
+            raise ValueError('per_frame needs step="paced": only there is cost / frames a mean per-frame distance')
         if not self.sounds:
             raise EmptyDictionaryError(-2, "empty dictionary")
         flat, off = pack_segments([t.mfccs() for t in targets], self._dim(), self.engine.np_dtype)
-        return self.engine.match_batch(self.resident(), flat, off, distances)
+        if step == "symmetric":
+            return self.engine.match_batch(self.resident(), flat, off, distances)
+        frames = np.diff(np.asarray(off, dtype=np.int64)).astype(np.float64)
+        if distances is not None:
+            distances = np.asarray(distances, dtype=np.float64).reshape(-1)
+            if per_frame:
+                distances = distances * frames
+        q = self.engine.queries(flat, off, self._dim())
+        try:
+            idx, cost = self.engine.match(self.resident(), q, distances, step=step)
+        finally:
+            q.close()
+        if per_frame:
+            with np.errstate(divide="ignore", invalid="ignore"):
+                cost = cost / frames
+        return idx, cost
 
 
-    def align(self, targets: Sequence[Sound], indices=None, step: str = "symmetric") -> List["Alignment"]:
+    def align(self, targets: Sequence[Sound], indices=None, step: str = "symmetric", match_step=None) -> List["Alignment"]:
         """The warping path of every target onto a dictionary sound (dtw engines; ssym_dtw_align).  indices=None:
         every target is matched first (match_indices) and aligned with its match -- two library calls in all;
         otherwise indices[t] is the dictionary sound target t is aligned with.  step="paced": the paced step pattern
         (ssym_dtw_align_step with SSYM_STEP_PACED) -- the alignment of a span that spot(step="paced") found and cut()
         took out: one source frame per target frame, so the path has as many cells as the target has frames and
         frame_map is its first column; a sound too short or too long for the target (outside about half to twice its
-        frames) has no such path and gives an empty Alignment."""
+        frames) has no such path and gives an empty Alignment.  match_step (looked at with indices=None): None keeps the
+        symmetric search, which may pick such a sound; "paced" (with step="paced" only) searches under the paced pattern
+        (match_indices(step="paced")), so every match that has a finite cost is aligned at that cost."""
         _spot_step(step)
+        match_kw = _match_kw(step, match_step)
         if not self.sounds:
             raise EmptyDictionaryError(-2, "empty dictionary")
         targets = list(targets)
@@ -683,14 +720,14 @@ class SoundDictionary:
         q = self.engine.queries(flat, off, self._dim())
         try:
             if indices is None:
-                indices, _ = self.engine.match(self.resident(), q)
+                indices, _ = self.engine.match(self.resident(), q, **match_kw)
             cost, _, paths, maps = self.engine.dtw_align(self.resident(), q, indices, **_step_kw(step))
         finally:
             q.close()
         return [Alignment(cost[t], paths[t], maps[t], int(indices[t])) for t in range(len(targets))]
 
     def warp(self, targets: Sequence[Sound], indices=None, want_pcm32: bool = False, search: int = 0,
-             want_pos: bool = False, step: str = "symmetric"):
+             want_pos: bool = False, step: str = "symmetric", match_step=None):
         """The reconstruction of the targets with every match warped onto its target's timing (dtw engines): match
         (unless indices[t] names the dictionary sound of target t), align with the outputs left on the device, and
         resynthesise along the maps -- ssym_match_queries, ssym_dtw_align, ssym_reconstruct_warped; the maps never
@@ -700,8 +737,11 @@ class SoundDictionary:
         call -- every source frame may move that far to continue the frame before it in phase; want_pos then also
         returns the frames' sample starts and the map offsets they are laid out by (Engine.reconstruct_wsola).
         step="paced": the alignment is the paced one (align), whose maps move by 0, 1 or 2 source frames per target frame
-        and never stand still twice in a row; a pair whose shape admits no paced path takes the length fit."""
+        and never stand still twice in a row; a pair whose shape admits no paced path takes the length fit.  match_step
+        as for align: "paced" (with step="paced") matches under the paced pattern too, so that no target falls back to the
+        length fit because the symmetric search chose a sound of the wrong length."""
         _spot_step(step)
+        match_kw = _match_kw(step, match_step)
         if not self.sounds:
             raise EmptyDictionaryError(-2, "empty dictionary")
         if getattr(self.engine, "metric", None) != "dtw":
@@ -725,7 +765,7 @@ class SoundDictionary:
         q = self.engine.queries(flat, off, self._dim())
         try:
             if indices is None:
-                indices, _ = self.engine.match(self.resident(), q)
+                indices, _ = self.engine.match(self.resident(), q, **match_kw)
             _, lengths, _, maps, _, m_off = self.engine.dtw_align_device(self.resident(), q, indices, **_step_kw(step))
             if not search:
                 return self.engine.reconstruct_warped(self.resident_samples(), indices, out_off, maps, m_off,
@@ -947,19 +987,27 @@ class SoundSequence:
         idx, _ = dict_.engine.chain(dict_.resident(), start.mfccs(), distances)
         return SoundSequence([start] + [dict_.sounds[int(i)] for i in idx])
 
-    def morph_to(self, distances: Sequence[float], dict_: SoundDictionary) -> "SoundSequence":
-        """src/sound.rs:440-449: zip(sounds, distances) -> at_distance, here as ONE batch."""
+    def morph_to(self, distances: Sequence[float], dict_: SoundDictionary, step: str = "symmetric",
+                 per_frame: bool = False) -> "SoundSequence":
+        """src/sound.rs:440-449: zip(sounds, distances) -> at_distance, here as ONE batch.  step="paced", per_frame: as for
+        SoundDictionary.match_indices -- with both, a distance is a mean per frame and means the same for every sound."""
+        _spot_step(step)
+        if per_frame and step != "paced":
+            raise ValueError('per_frame needs step="paced": only there is cost / frames a mean per-frame distance')
         n = min(len(self._sounds), len(distances))
         if n == 0:
             return SoundSequence([])
-        idx, _ = dict_.match_indices(self._sounds[:n], np.asarray(distances[:n], dtype=np.float64))
+        kw = dict(_step_kw(step), **({"per_frame": True} if per_frame else {}))
+        idx, _ = dict_.match_indices(self._sounds[:n], np.asarray(distances[:n], dtype=np.float64), **kw)
         return SoundSequence([dict_.sounds[int(i)] for i in idx])
 
-    def clone_from_dictionary(self, dict_: SoundDictionary) -> "SoundSequence":
-        """src/sound.rs:451-472: match every sound, then fit the match to the target's length."""
+    def clone_from_dictionary(self, dict_: SoundDictionary, step: str = "symmetric") -> "SoundSequence":
+        """src/sound.rs:451-472: match every sound, then fit the match to the target's length.  step="paced": the match
+        is SoundDictionary.match_indices(step="paced")'s."""
+        _spot_step(step)
         if not self._sounds:
             return SoundSequence([])
-        idx, _ = dict_.match_indices(self._sounds, None)
+        idx, _ = dict_.match_indices(self._sounds, None, **_step_kw(step))
         out = []
         for sound, i in zip(self._sounds, idx):
             s = dict_.sounds[int(i)]
@@ -973,11 +1021,14 @@ class SoundSequence:
                                  None, None, s.ncoeffs))
         return SoundSequence(out)
 
-    def align_to_dictionary(self, dict_: SoundDictionary, step: str = "symmetric") -> List[Alignment]:
+    def align_to_dictionary(self, dict_: SoundDictionary, step: str = "symmetric", match_step=None) -> List[Alignment]:
         """Every sound of the sequence matched against dict_ and aligned with its match (SoundDictionary.align)."""
+        _spot_step(step)
+        match_kw = {} if match_step is None else {"match_step": match_step}
+        _match_kw(step, match_step)
         if not self._sounds:
             return []
-        return dict_.align(self._sounds, **_step_kw(step))
+        return dict_.align(self._sounds, **_step_kw(step), **match_kw)
 
     def spot_in_dictionary(self, dict_: SoundDictionary, step: str = "symmetric") -> List[Spot]:
         """Every sound of the sequence located inside dict_'s recordings (SoundDictionary.spot)."""
@@ -1004,16 +1055,18 @@ class SoundSequence:
         return dict_.engine.reconstruct(dict_.resident_samples(), idx, out_off, want_pcm32)
 
     def reconstruct_warped_from_dictionary(self, dict_: "SoundDictionary", want_pcm32: bool = False, search: int = 0,
-                                           step: str = "symmetric"):
+                                           step: str = "symmetric", match_step=None):
         """reconstruct_from_dictionary with every match warped onto its target's timing instead of cut off or padded
         (SoundDictionary.warp: match, align, resynthesise along the alignment, all on the GPU; dtw engines).
-        search > 0: with the waveform-similarity search of that width in samples (at most 512).  step as for
-        SoundDictionary.warp."""
+        search > 0: with the waveform-similarity search of that width in samples (at most 512).  step and match_step as
+        for SoundDictionary.warp."""
         search = _wsola_search(search)
         _spot_step(step)
+        match_kw = {} if match_step is None else {"match_step": match_step}
+        _match_kw(step, match_step)
         if not self._sounds:
             return (np.zeros(0), np.zeros(0, dtype=np.int32)) if want_pcm32 else np.zeros(0)
-        return dict_.warp(self._sounds, None, want_pcm32, search, **_step_kw(step))
+        return dict_.warp(self._sounds, None, want_pcm32, search, **_step_kw(step), **match_kw)
 
     def to_sound(self) -> Sound:                                        # src/sound.rs:475-483
         parts = [s.samples() for s in self._sounds]

@@ -139,7 +139,7 @@ int32_t ssym_ctx_destroy(ssym_ctx *ctx)
     (void)hipStreamSynchronize(ctx->stream);
     DeviceBuf *bufs[] = {&ctx->handoff, &ctx->cmat, &ctx->tmin, &ctx->cand, &ctx->cand2, &ctx->cand_xmin,
                          &ctx->cand_cost, &ctx->best, &ctx->selmask, &ctx->selcnt, &ctx->topk,
-                         &ctx->abandon, &ctx->prune_pairs, &ctx->prune_cost, &ctx->one_ticket, &ctx->dist, &ctx->part, &ctx->out_idx, &ctx->out_cost,
+                         &ctx->abandon, &ctx->prune_pairs, &ctx->prune_cost, &ctx->one_ticket, &ctx->dist, &ctx->part, &ctx->paced_part, &ctx->out_idx, &ctx->out_cost,
                          &ctx->pipe_flag, &ctx->tmin2, &ctx->zeros, &ctx->stamps};
     for (DeviceBuf *b : bufs)
         if (b->ptr)
@@ -271,6 +271,23 @@ int32_t ssym_match_queries(ssym_ctx *ctx, const ssym_dict *dict, const ssym_quer
 {
     return guarded(ctx, [&]() -> int32_t {
     return match(ctx, dict, q, distance, index_base, 1, out_idx, out_cost, flags);
+    });
+}
+
+// the call above with the step pattern as an argument: SSYM_STEP_SYMMETRIC is the call above itself
+int32_t ssym_match_queries_step(ssym_ctx *ctx, const ssym_dict *dict, const ssym_queries *q, const double *distance,
+                                uint32_t index_base, uint32_t step, uint32_t *out_idx, double *out_cost, uint32_t flags)
+{
+    return guarded(ctx, [&]() -> int32_t {
+    if (!ctx)
+        return SSYM_E_INVALID;
+    if (step == SSYM_STEP_SYMMETRIC)
+        return match(ctx, dict, q, distance, index_base, 1, out_idx, out_cost, flags);
+    if (step != SSYM_STEP_PACED) {
+        ctx->err = "ssym_match_queries_step: step must be SSYM_STEP_SYMMETRIC or SSYM_STEP_PACED";
+        return SSYM_E_INVALID;
+    }
+    return match_paced(ctx, dict, q, distance, index_base, out_idx, out_cost, flags, "ssym_match_queries_step");
     });
 }
 
@@ -543,10 +560,10 @@ int32_t ssym_chain(ssym_ctx *ctx, ssym_dict *dict, const void *start_feats, uint
     });
 }
 
-int32_t ssym_pair_matrix(ssym_ctx *ctx, const ssym_dict *dict, const ssym_queries *q, int32_t exact,
-                         double *out_matrix)
+}  // extern "C"
+
+static int32_t pair_matrix(ssym_ctx *ctx, const ssym_dict *dict, const ssym_queries *q, int32_t exact, double *out_matrix)
 {
-    return guarded(ctx, [&]() -> int32_t {
     int32_t rc = check_match_args(ctx, dict, q);
     if (rc != SSYM_OK)
         return rc;
@@ -597,6 +614,31 @@ int32_t ssym_pair_matrix(ssym_ctx *ctx, const ssym_dict *dict, const ssym_querie
                                        hipMemcpyDeviceToHost, st));
     SSYM_HIP_CHECK(ctx, hipStreamSynchronize(st));
     return SSYM_OK;
+}
+
+extern "C" {
+
+int32_t ssym_pair_matrix(ssym_ctx *ctx, const ssym_dict *dict, const ssym_queries *q, int32_t exact,
+                         double *out_matrix)
+{
+    return guarded(ctx, [&]() -> int32_t {
+    return pair_matrix(ctx, dict, q, exact, out_matrix);
+    });
+}
+
+// the call above with the step pattern in place of the mode: SSYM_STEP_SYMMETRIC is the call above with exact = 1
+int32_t ssym_pair_matrix_step(ssym_ctx *ctx, const ssym_dict *dict, const ssym_queries *q, uint32_t step, double *out_matrix)
+{
+    return guarded(ctx, [&]() -> int32_t {
+    if (!ctx)
+        return SSYM_E_INVALID;
+    if (step == SSYM_STEP_SYMMETRIC)
+        return pair_matrix(ctx, dict, q, 1, out_matrix);
+    if (step != SSYM_STEP_PACED) {
+        ctx->err = "ssym_pair_matrix_step: step must be SSYM_STEP_SYMMETRIC or SSYM_STEP_PACED";
+        return SSYM_E_INVALID;
+    }
+    return pair_matrix_paced(ctx, dict, q, out_matrix, "ssym_pair_matrix_step");
     });
 }
 

@@ -145,6 +145,7 @@ struct ssym_ctx {
     ssym::DeviceBuf abandon;    // SSYM_DTW_PRUNE: per-target-slot thresholds (f32, accumulator units) + cell counter
     ssym::DeviceBuf dist;       // per-target distance (f64)
     ssym::DeviceBuf part;       // refcos partial argmin
+    ssym::DeviceBuf paced_part; // paced matching: per (source block, target) first minimum -- keys, costs, indices
     ssym::DeviceBuf one_ticket; // refcos_match_one_kernel: the "last workgroup" counter (zero between calls)
     ssym::DeviceBuf out_idx, out_cost;  // staging for host outputs
     ssym::DeviceBuf zeros;      // 256 bytes of 0.0: what refcos_mfma_kernel's staging DMA reads beyond a segment's end
@@ -420,6 +421,11 @@ int32_t match_candidates_impl(ssym_ctx *ctx, const ssym_dict *dict, const ssym_q
 int32_t match_begin_impl(ssym_ctx *ctx, const ssym_dict *dict, const ssym_queries *q, const double *distance,
                          uint32_t index_base, double *bounds_dev, const double *prune_cost_dev);
 int32_t match_finish_impl(ssym_ctx *ctx, const double *bounds_dev, uint32_t *out_idx, double *out_cost, uint32_t flags);
+
+// dtw_match_paced.hip: the search and the cost matrix under the paced step pattern (fn: the entry point's name, for messages)
+int32_t match_paced(ssym_ctx *ctx, const ssym_dict *dict, const ssym_queries *q, const double *distance, uint32_t index_base,
+                    uint32_t *out_idx, double *out_cost, uint32_t flags, const char *fn);
+int32_t pair_matrix_paced(ssym_ctx *ctx, const ssym_dict *dict, const ssym_queries *q, double *out_matrix, const char *fn);
 
 // chain.hip
 int32_t launch_chain_argmin(ssym_ctx *ctx, const double *base, size_t row_stride, const uint32_t *row_sel,

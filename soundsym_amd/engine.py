@@ -637,11 +637,15 @@ class Engine:
 
     # -- the hot path ------------------------------------------------------------------------
     def match(self, d: _Handle, q: _Handle, distance=None, index_base: int = 0,
-              force_exact: bool = False, out_idx=None, out_cost=None, prune: bool = False
-              ) -> Tuple[np.ndarray, np.ndarray]:
+              force_exact: bool = False, out_idx=None, out_cost=None, prune: bool = False,
+              step: str = "symmetric") -> Tuple[np.ndarray, np.ndarray]:
         """argmin per target.  With torch CUDA tensors in out_idx (int32/uint32 storage, n
         entries) and out_cost (float64) the results stay on the device.  prune=True asks for
-        early abandoning (SSYM_DTW_PRUNE): same results, data-dependent time."""
+        early abandoning (SSYM_DTW_PRUNE): same results, data-dependent time.  step="paced":
+        ssym_match_queries_step with SSYM_STEP_PACED ("Paced matching": the cost is ssym_dtw_align_step's paced cost,
+        +inf for a pair whose shape has no paced path; costs stay sums; force_exact and prune mean nothing there);
+        "symmetric" is ssym_match_queries itself."""
+        which = _spot_step(step)
         L = nat.lib()
         m = q.n
         dist_p = None
@@ -651,16 +655,18 @@ class Engine:
                 raise ValueError("distance must have one entry per target")
             dist_p = dist.ctypes.data
         flags = (nat.DTW_FORCE_EXACT if force_exact else 0) | (nat.DTW_PRUNE if prune else 0)
+        if which == nat.STEP_SYMMETRIC:
+            call = lambda oi, oc, fl: L.ssym_match_queries(self.ctx, d.ptr, q.ptr, dist_p, index_base, oi, oc, fl)
+        else:
+            call = lambda oi, oc, fl: L.ssym_match_queries_step(self.ctx, d.ptr, q.ptr, dist_p, index_base, which, oi, oc, fl)
         if out_idx is not None and _is_device_tensor(out_idx):
             flags |= nat.OUT_DEVICE
-            rc = L.ssym_match_queries(self.ctx, d.ptr, q.ptr, dist_p, index_base, out_idx.data_ptr(),
-                                      out_cost.data_ptr() if out_cost is not None else None, flags)
+            rc = call(out_idx.data_ptr(), out_cost.data_ptr() if out_cost is not None else None, flags)
             nat.check(rc, self.ctx)
             return out_idx, out_cost
         idx = np.zeros(m, dtype=np.uint32)
         cost = np.zeros(m, dtype=np.float64)
-        rc = L.ssym_match_queries(self.ctx, d.ptr, q.ptr, dist_p, index_base, idx.ctypes.data,
-                                  cost.ctypes.data, flags)
+        rc = call(idx.ctypes.data, cost.ctypes.data, flags)
         nat.check(rc, self.ctx)
         return idx, cost
 
@@ -793,10 +799,16 @@ class Engine:
         nat.check(rc, self.ctx)
         return idx, cost
 
-    def pair_matrix(self, d: _Handle, q: _Handle, exact: bool = False) -> np.ndarray:
+    def pair_matrix(self, d: _Handle, q: _Handle, exact: bool = False, step: str = "symmetric") -> np.ndarray:
+        """ssym_pair_matrix; step="paced": ssym_pair_matrix_step with SSYM_STEP_PACED, the [n_sources][n_targets] costs
+        of "Paced matching" (always exact: `exact` is not looked at)."""
+        which = _spot_step(step)
         out = np.zeros((d.n, q.n), dtype=np.float64)
-        nat.check(nat.lib().ssym_pair_matrix(self.ctx, d.ptr, q.ptr, 1 if exact else 0,
-                                             out.ctypes.data), self.ctx)
+        if which == nat.STEP_SYMMETRIC:
+            rc = nat.lib().ssym_pair_matrix(self.ctx, d.ptr, q.ptr, 1 if exact else 0, out.ctypes.data)
+        else:
+            rc = nat.lib().ssym_pair_matrix_step(self.ctx, d.ptr, q.ptr, which, out.ctypes.data)
+        nat.check(rc, self.ctx)
         return out
 
     def dtw_align_sizes(self, d: _Handle, q: _Handle, src_idx, tgt_idx=None, index_base: int = 0):
