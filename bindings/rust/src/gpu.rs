@@ -158,6 +158,15 @@ extern "C" {
                                tgt_idx: *const u32, n_pairs: u32, index_base: u32, step: u32, out_cost: *mut f64,
                                out_len: *mut u32, path_offsets: *const u64, out_path: *mut u32, map_offsets: *const u64,
                                out_map: *mut u32, flags: u32) -> i32;
+    // ssym_dtw_align / ssym_dtw_align_step with a span of source frames per pair (span_first ..= span_last inside segment
+    // src_idx[p] - index_base, HOST): what the spot calls report, aligned where it lies; cells and maps count from the span
+    pub fn ssym_dtw_align_spans_sizes(dict: *const SsymDict, q: *const SsymQueries, src_idx: *const u32, tgt_idx: *const u32,
+                                      span_first: *const u32, span_last: *const u32, n_pairs: u32, index_base: u32,
+                                      path_offsets: *mut u64, map_offsets: *mut u64) -> i32;
+    pub fn ssym_dtw_align_spans(ctx: *mut SsymCtx, dict: *const SsymDict, q: *const SsymQueries, src_idx: *const u32,
+                                tgt_idx: *const u32, span_first: *const u32, span_last: *const u32, n_pairs: u32,
+                                index_base: u32, step: u32, out_cost: *mut f64, out_len: *mut u32, path_offsets: *const u64,
+                                out_path: *mut u32, map_offsets: *const u64, out_map: *mut u32, flags: u32) -> i32;
     // ssym_match_queries / ssym_pair_matrix with a step pattern: SSYM_STEP_PACED searches under the paced pattern (the cost of
     // a pair is ssym_dtw_align_step's paced cost, +inf without a paced shape; costs are sums over the target's frames)
     pub fn ssym_match_queries_step(ctx: *mut SsymCtx, dict: *const SsymDict, q: *const SsymQueries, distance: *const f64,
@@ -220,6 +229,16 @@ extern "C" {
                                   n_targets: u32, frame_map: *const u32, map_offsets: *const u64, map_frames: *const u32,
                                   pair_len: *const u32, search: u32, flags: u32, out_pos: *mut u64, out_samples: *mut f64,
                                   out_pcm32: *mut i32) -> i32;
+    // the two calls above with a window of samples per target (win_first, win_len: HOST, in samples): sound idx[t] is only
+    // that window, and the map counts frames from its start -- what ssym_dtw_align_spans returns
+    pub fn ssym_reconstruct_warped_spans(ctx: *mut SsymCtx, s: *const SsymSamples, idx: *const u32, win_first: *const u64,
+                                         win_len: *const u64, out_offsets: *const u64, n_targets: u32, frame_map: *const u32,
+                                         map_offsets: *const u64, map_frames: *const u32, pair_len: *const u32, flags: u32,
+                                         out_samples: *mut f64, out_pcm32: *mut i32) -> i32;
+    pub fn ssym_reconstruct_wsola_spans(ctx: *mut SsymCtx, s: *const SsymSamples, idx: *const u32, win_first: *const u64,
+                                        win_len: *const u64, out_offsets: *const u64, n_targets: u32, frame_map: *const u32,
+                                        map_offsets: *const u64, map_frames: *const u32, pair_len: *const u32, search: u32,
+                                        flags: u32, out_pos: *mut u64, out_samples: *mut f64, out_pcm32: *mut i32) -> i32;
 
     // feature front-end (own MFCC definition -- parity with vox_box unpinned)
     pub fn ssym_mfcc_num_frames(n_samples: u64, flags: u32, out_frames: *mut u64) -> i32;

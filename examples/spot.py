@@ -5,14 +5,15 @@
 
 The target is cut by a Partitioner as examples/warp.py cuts it (trained on the first dictionary recording); the dictionary
 recordings stay whole.  Every target segment is located inside the recordings by subsequence DTW
-(SoundDictionary.spot: one ssym_spot_queries call), the spans are cut out (SoundDictionary.cut) and each is warped onto
-its target's timing (SoundDictionary.warp with the given indices: ssym_dtw_align and ssym_reconstruct_warped, or
-ssym_reconstruct_wsola with --search N).  The recording, span and cost of every target segment are printed; the cost is
-a sum along the path, not normalised by any length.
+(SoundDictionary.spot: one ssym_spot_queries call), and each span is warped onto its target's timing where it lies, from
+the dictionary and the samples that are resident already (SoundDictionary.warp with spans=: ssym_dtw_align_spans and
+ssym_reconstruct_warped_spans, or ssym_reconstruct_wsola_spans with --search N) -- nothing is cut and nothing is uploaded a
+second time.  The recording, span and cost of every target segment are printed; the cost is a sum along the path, not
+normalised by any length.
 
---paced: the whole flow under the paced step pattern (step="paced": ssym_spot_queries_step, ssym_dtw_align_step) -- every
+--paced: the whole flow under the paced step pattern (step="paced": ssym_spot_queries_step, SSYM_STEP_PACED) -- every
 target frame takes one source frame, at most one source frame in a row is skipped or repeated.  The span of a segment then
-has about half to twice its frames, the alignment of the cut span has the cost the spot reported, and cost / frames is a
+has about half to twice its frames, the alignment of the span has the cost the spot reported, and cost / frames is a
 mean per-frame distance: it is printed per segment, and its mean over the segments at the end.
 """
 import argparse
@@ -62,8 +63,7 @@ def main(argv=None):
         per_frame = f", per frame {sp.cost_per_frame:.6g}" if args.paced else ""
         print(f"segment {t:4d} ({targets[t].num_frames():3d} frames): {name} frames {sp.start_frame}...{sp.end_frame} "
               f"({sp.num_frames()} frames), cost {sp.cost:.6g}{per_frame}")
-    found = dictionary.cut(spots)
-    samples, pcm = found.warp(targets, indices=np.arange(len(targets)), want_pcm32=True, search=args.search, **step)
+    samples, pcm = dictionary.warp(targets, spans=spots, want_pcm32=True, search=args.search, **step)
     if args.paced:
         means = [sp.cost_per_frame for sp in spots if sp]
         print(f"mean cost_per_frame over {len(means)} spotted segments: {np.mean(means) if means else float('nan'):.6g}")

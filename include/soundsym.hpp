@@ -429,6 +429,94 @@ class SoundDictionary {
                                              : Spot{idx[t], start[t], end[t], cost[t]};
         return out;
     }
+    // align with a Spot per target instead of an index: target t against frames start_frame ... end_frame of
+    // sounds[source_index], where they lie in the resident dictionary (ssym_dtw_align_spans; soundsym_amd.h "Span
+    // alignment").  path and frame_map count from the span's first frame; an empty Spot gives an empty Alignment
+    std::vector<Alignment> align_spans(const std::vector<ArcSound> &targets, const std::vector<Spot> &spots,
+                                       uint32_t step = SSYM_STEP_SYMMETRIC) const
+    {
+        if (sounds.empty())
+            throw EmptyDictionary();
+        const uint32_t n = (uint32_t)targets.size();
+        std::vector<double> flat;
+        std::vector<uint64_t> off;
+        pack_features(targets, flat, off);
+        ssym_queries *q = nullptr;
+        ctx_->check(ssym_queries_create(ctx_->get(), flat.data(), off.data(), n, (uint32_t)NCOEFFS, &q));
+        std::vector<uint64_t> poff(n + 1), moff(n + 1);
+        std::vector<double> cost(n);
+        std::vector<uint32_t> len(n), path, map, src(n), first(n), last(n);
+        for (uint32_t t = 0; t < n && t < spots.size(); ++t) {
+            src[t] = spots[t].empty() ? SSYM_NO_MATCH : spots[t].source_index;
+            first[t] = spots[t].empty() ? SSYM_NO_MATCH : spots[t].start_frame;
+            last[t] = spots[t].empty() ? SSYM_NO_MATCH : spots[t].end_frame;
+        }
+        int32_t rc = spots.size() == n ? ssym_dtw_align_spans_sizes(resident(), q, src.data(), nullptr, first.data(),
+                                                                    last.data(), n, 0, poff.data(), moff.data())
+                                       : (int32_t)SSYM_E_INVALID;
+        if (rc == SSYM_OK) {
+            path.resize(2 * poff[n]);
+            map.resize(moff[n]);
+            rc = ssym_dtw_align_spans(ctx_->get(), resident(), q, src.data(), nullptr, first.data(), last.data(), n, 0, step,
+                                      cost.data(), len.data(), poff.data(), path.data(), moff.data(), map.data(), 0);
+        }
+        ssym_queries_destroy(ctx_->get(), q);
+        ctx_->check(rc);
+        std::vector<Alignment> out(n);
+        for (uint32_t t = 0; t < n; ++t) {
+            out[t].cost = cost[t];
+            out[t].source_index = src[t];
+            for (uint32_t s = 0; s < len[t]; ++s)
+                out[t].path.push_back({path[2 * (poff[t] + s)], path[2 * (poff[t] + s) + 1]});
+            if (len[t])
+                out[t].frame_map.assign(map.begin() + moff[t], map.begin() + moff[t + 1]);
+        }
+        return out;
+    }
+    // warp with a Spot per target: every span aligned and resynthesised where it lies, the sample window being frame
+    // start_frame's first sample up to where frame end_frame + 1 would start, or the recording's end
+    // (ssym_dtw_align_spans + ssym_reconstruct_warped_spans, or with search > 0 ssym_reconstruct_wsola_spans).  An empty
+    // Spot gives zeros
+    std::vector<double> warp_spans(const std::vector<ArcSound> &targets, const std::vector<Spot> &spots, uint32_t search = 0,
+                                   uint32_t step = SSYM_STEP_SYMMETRIC) const
+    {
+        const std::vector<Alignment> al = align_spans(targets, spots, step);
+        const uint32_t n = (uint32_t)targets.size();
+        std::vector<uint64_t> moff(n + 1, 0), ooff(n + 1, 0), soff(sounds.size() + 1, 0), wfirst(n, 0), wlen(n, 0);
+        std::vector<uint32_t> map, frames(n), len(n), idx(n, 0);
+        std::vector<double> samples, out;
+        for (std::size_t i = 0; i < sounds.size(); ++i) {
+            samples.insert(samples.end(), sounds[i]->samples().begin(), sounds[i]->samples().end());
+            soff[i + 1] = samples.size();
+        }
+        for (uint32_t t = 0; t < n; ++t) {
+            map.insert(map.end(), al[t].frame_map.begin(), al[t].frame_map.end());
+            frames[t] = (uint32_t)al[t].frame_map.size();
+            len[t] = (uint32_t)al[t].path.size();
+            moff[t + 1] = map.size();
+            ooff[t + 1] = ooff[t] + targets[t]->samples().size();
+            if (spots[t].empty())
+                continue;
+            idx[t] = spots[t].source_index;
+            const uint64_t size = soff[idx[t] + 1] - soff[idx[t]];
+            const uint64_t a = std::min<uint64_t>((uint64_t)spots[t].start_frame * SSYM_MFCC_HOP, size);
+            const uint64_t b = std::min<uint64_t>(((uint64_t)spots[t].end_frame + 1) * SSYM_MFCC_HOP, size);
+            wfirst[t] = a;
+            wlen[t] = b > a ? b - a : 0;
+        }
+        ssym_samples *smp = nullptr;
+        ctx_->check(ssym_samples_create(ctx_->get(), samples.data(), soff.data(), (uint32_t)sounds.size(), &smp));
+        out.resize(ooff[n]);
+        const int32_t rc =
+            search ? ssym_reconstruct_wsola_spans(ctx_->get(), smp, idx.data(), wfirst.data(), wlen.data(), ooff.data(), n,
+                                                  map.data(), moff.data(), frames.data(), len.data(), search, 0, nullptr,
+                                                  out.data(), nullptr)
+                   : ssym_reconstruct_warped_spans(ctx_->get(), smp, idx.data(), wfirst.data(), wlen.data(), ooff.data(), n,
+                                                   map.data(), moff.data(), frames.data(), len.data(), 0, out.data(), nullptr);
+        ssym_samples_destroy(ctx_->get(), smp);
+        ctx_->check(rc);
+        return out;
+    }
     // every place a target sounds: per target its occurrences by ascending cost, pairwise disjoint within a recording
     // (ssym_dtw_spot_all, one call).  With indices, target t is searched in sounds[indices[t]]; without, in every sound:
     // max_spots (1 ... 64) then applies per sound and a target's list is merged by (cost, source index, end).  max_cost:

@@ -449,6 +449,37 @@ SSYM_API int32_t ssym_dtw_align_step(ssym_ctx *ctx, const ssym_dict *dict, const
                                      double *out_cost, uint32_t *out_len, const uint64_t *path_offsets, uint32_t *out_path,
                                      const uint64_t *map_offsets, uint32_t *out_map, uint32_t flags);
 
+/* Span alignment (DESIGN.md section 2 "Spans" and section 5.22): ssym_dtw_align and ssym_dtw_align_step with a span of
+ * source frames per pair, so that what ssym_dtw_spot, ssym_dtw_spot_all and their _step forms report is aligned where it
+ * lies, in the resident dictionary, without cutting the recording.
+ *   span_first, span_last   n_pairs u32 each (HOST): inclusive source frames inside segment src_idx[p] - index_base
+ *   step                    SSYM_STEP_SYMMETRIC or SSYM_STEP_PACED
+ * Definition by reduction: pair p gives exactly what the existing call gives for the pair (S', target), S' a dictionary
+ * segment that holds frames span_first[p] ... span_last[p] of that segment -- with SSYM_STEP_SYMMETRIC ssym_dtw_align
+ * (the context's band and squared option included), with SSYM_STEP_PACED ssym_dtw_align_step(SSYM_STEP_PACED).  out_cost,
+ * out_len, the path and the map are those bits; the NaN and +-inf rules and the tie rules are those; the paced shape rule is
+ * applied to Fa' = last - first + 1.  Path cells and out_map are RELATIVE TO THE SPAN: map[0] = 0, and source frame
+ * first + map[j] of the recording goes with target frame j, so the map feeds ssym_reconstruct_warped_spans and
+ * ssym_reconstruct_wsola_spans unchanged.  ssym_dtw_align_spans_sizes leaves Fa' + Fb - 1 cells and Fb map entries per
+ * pair.  span_first[p] == span_last[p] == SSYM_NO_MATCH -- what a spot without a span returns -- is "no path", like
+ * src_idx[p] == SSYM_NO_MATCH: cost +inf, out_len 0, slots unwritten (nothing else of the pair's span is looked at when
+ * src_idx[p] is SSYM_NO_MATCH).  Frames outside the span are never read.
+ * Errors: first > last, last >= the segment's frames, exactly one of the two SSYM_NO_MATCH, a NULL span array with
+ * n_pairs > 0: SSYM_E_INVALID; every error case of the existing calls keeps its code.  Limits hold for the SPAN, not the
+ * segment: Fa' <= 4096, targets <= 4096 frames (<= 2048 under SSYM_STEP_PACED), dim <= 64, dtw contexts only, no band under
+ * SSYM_STEP_PACED, fewer than 2^31 pairs; beyond them SSYM_E_UNSUPPORTED.  The segment itself may be as long as a
+ * dictionary holds.  Every error comes with a message, before any device work, with the outputs unwritten.
+ * SSYM_OUT_DEVICE, n_pairs = 0, the one synchronisation per call and ssym_get_timings are ssym_dtw_align's. */
+SSYM_API int32_t ssym_dtw_align_spans_sizes(const ssym_dict *dict, const ssym_queries *q, const uint32_t *src_idx,
+                                            const uint32_t *tgt_idx, const uint32_t *span_first, const uint32_t *span_last,
+                                            uint32_t n_pairs, uint32_t index_base, uint64_t *path_offsets,
+                                            uint64_t *map_offsets);
+SSYM_API int32_t ssym_dtw_align_spans(ssym_ctx *ctx, const ssym_dict *dict, const ssym_queries *q, const uint32_t *src_idx,
+                                      const uint32_t *tgt_idx, const uint32_t *span_first, const uint32_t *span_last,
+                                      uint32_t n_pairs, uint32_t index_base, uint32_t step, double *out_cost,
+                                      uint32_t *out_len, const uint64_t *path_offsets, uint32_t *out_path,
+                                      const uint64_t *map_offsets, uint32_t *out_map, uint32_t flags);
+
 /* Paced matching (DESIGN.md section 2 "Paced matching" and section 5.21): ssym_match_queries and ssym_pair_matrix with a
  * step pattern.  SSYM_STEP_SYMMETRIC makes them the existing calls: one host path, the same kernels, the same bits
  * (ssym_pair_matrix_step is then ssym_pair_matrix with exact = 1).  Under SSYM_STEP_PACED, for source s (Fa frames) and
@@ -722,6 +753,33 @@ SSYM_API int32_t ssym_reconstruct_wsola(ssym_ctx *ctx, const ssym_samples *s, co
                                         const uint64_t *map_offsets, const uint32_t *map_frames,
                                         const uint32_t *pair_len, uint32_t search, uint32_t flags, uint64_t *out_pos,
                                         double *out_samples, int32_t *out_pcm32);
+
+/* Sample windows (DESIGN.md section 2 "Spans" and section 5.22): ssym_reconstruct_warped and ssym_reconstruct_wsola with a
+ * window of samples per target, so that a spotted span is resynthesised from the resident sample store without cutting
+ * the recording.
+ *   win_first, win_len   n_targets u64 each (HOST), in samples
+ * The two calls are the calls above with "x[0 .. sLen) = the samples of dictionary sound idx[t]" replaced by "x[0 .. sLen)
+ * = samples win_first[t] ... win_first[t] + win_len[t] - 1 of sound idx[t]" (sLen = win_len[t]).  Everything else is word
+ * for word the same: the taps and their validity p < sLen, WSOLA's admissible lags 0 <= nom + d < sLen, templates and
+ * candidates reading +0.0 at or beyond sLen, pos[] and out_pos relative to the window, the length-fit fallback taken over
+ * the window's samples, out_pcm32, the flags, the no-op cases.  So the output has the bits of the existing call on a store
+ * whose sound t is that slice.  win_len[t] = 0 is allowed: the window is an empty sound.  No map content and no window
+ * can cause a read outside the window, and samples outside the window never influence an output.
+ * Errors: win_first[t] + win_len[t] beyond the sound's samples, a NULL window array: SSYM_E_INVALID; 2^31 targets or more:
+ * SSYM_E_UNSUPPORTED; every error case of the existing calls keeps its code -- all with a message, before any device work,
+ * with the outputs unwritten.  One synchronisation per call; ssym_get_timings as for the existing calls. */
+SSYM_API int32_t ssym_reconstruct_warped_spans(ssym_ctx *ctx, const ssym_samples *s, const uint32_t *idx,
+                                               const uint64_t *win_first, const uint64_t *win_len,
+                                               const uint64_t *out_offsets, uint32_t n_targets, const uint32_t *frame_map,
+                                               const uint64_t *map_offsets, const uint32_t *map_frames,
+                                               const uint32_t *pair_len, uint32_t flags, double *out_samples,
+                                               int32_t *out_pcm32);
+SSYM_API int32_t ssym_reconstruct_wsola_spans(ssym_ctx *ctx, const ssym_samples *s, const uint32_t *idx,
+                                              const uint64_t *win_first, const uint64_t *win_len,
+                                              const uint64_t *out_offsets, uint32_t n_targets, const uint32_t *frame_map,
+                                              const uint64_t *map_offsets, const uint32_t *map_frames,
+                                              const uint32_t *pair_len, uint32_t search, uint32_t flags, uint64_t *out_pos,
+                                              double *out_samples, int32_t *out_pcm32);
 
 /* Feature front-end, the step before the hot path: what
  * Sound::from_samples(.., None, ..) computes through analyze_mfccs (src/sound.rs:215-242) --

@@ -65,6 +65,7 @@ ABI_SYMBOLS = [
     "ssym_match_queries_step", "ssym_pair_matrix_step",
     "ssym_spotter_create_step",
     "ssym_reconstruct_warped", "ssym_reconstruct_wsola",
+    "ssym_dtw_align_spans_sizes", "ssym_dtw_align_spans", "ssym_reconstruct_warped_spans", "ssym_reconstruct_wsola_spans",
 ]
 COMM_ID_BYTES = 128        # SSYM_COMM_ID_BYTES
 
@@ -286,6 +287,15 @@ def lib() -> ctypes.CDLL:
     L.ssym_reconstruct_warped.argtypes = [vp, vp, vp, vp, u32, vp, vp, vp, vp, u32, vp, vp]
     L.ssym_reconstruct_wsola.restype = i32
     L.ssym_reconstruct_wsola.argtypes = [vp, vp, vp, vp, u32, vp, vp, vp, vp, u32, u32, vp, vp, vp]
+    # the align and reconstruction calls with a span of source frames / a window of samples behind the indices
+    L.ssym_dtw_align_spans_sizes.restype = i32
+    L.ssym_dtw_align_spans_sizes.argtypes = [vp, vp, vp, vp, vp, vp, u32, u32, vp, vp]
+    L.ssym_dtw_align_spans.restype = i32
+    L.ssym_dtw_align_spans.argtypes = [vp, vp, vp, vp, vp, vp, vp, u32, u32, u32, vp, vp, vp, vp, vp, vp, u32]
+    L.ssym_reconstruct_warped_spans.restype = i32
+    L.ssym_reconstruct_warped_spans.argtypes = [vp, vp, vp, vp, vp, vp, u32, vp, vp, vp, vp, u32, vp, vp]
+    L.ssym_reconstruct_wsola_spans.restype = i32
+    L.ssym_reconstruct_wsola_spans.argtypes = [vp, vp, vp, vp, vp, vp, u32, vp, vp, vp, vp, u32, u32, vp, vp, vp]
     L.ssym_comm_unique_id.restype = i32
     L.ssym_comm_unique_id.argtypes = [vp]
     L.ssym_comm_create.restype = i32

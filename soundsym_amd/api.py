@@ -320,11 +320,13 @@ class Alignment:
     section 2): `source_index` into the dictionary's sounds, the DTW `cost` of the pair, `path` an (L, 2) uint32 array
     of (source frame, target frame) cells from (0, 0) to the last frames, and `frame_map` a (target frames,) uint32
     array with the smallest source frame aligned with every target frame.  A pair without a finite cost (an empty
-    sound, a band that cuts every path) has an empty path and an empty map."""
+    sound, a band that cuts every path) has an empty path and an empty map.  An alignment of a spotted span
+    (SoundDictionary.align(spans=)) counts source frames from the span's first frame: `span_start` is that frame, so
+    span_start + frame_map are frames of the recording; it is 0 for every other alignment."""
 
-    __slots__ = ("cost", "path", "frame_map", "source_index")
+    __slots__ = ("cost", "path", "frame_map", "source_index", "span_start")
 
-    def __init__(self, cost: float, path, frame_map, source_index: int):
+    def __init__(self, cost: float, path, frame_map, source_index: int, span_start: int = 0):
         path = np.asarray(path, dtype=np.uint32)
         if path.ndim != 2 or path.shape[1] != 2:
             raise ValueError("path must be an (L, 2) array of (source frame, target frame) cells")
@@ -332,6 +334,7 @@ class Alignment:
         if frame_map.ndim != 1:
             raise ValueError("frame_map must hold one source frame per target frame")
         self.cost, self.path, self.frame_map, self.source_index = float(cost), path, frame_map, int(source_index)
+        self.span_start = int(span_start)
 
     def __len__(self) -> int:
         return int(self.path.shape[0])
@@ -373,6 +376,36 @@ def _match_kw(step, match_step):
     if match_step == "paced" and step != "paced":
         raise ValueError('match_step="paced" needs step="paced": the match it picks is one the paced alignment can align')
     return {} if match_step == "symmetric" else {"step": match_step}
+
+
+def _span_args(sounds, spots, targets, indices, match_step, context=False):
+    """What align(spans=) and warp(spans=) hand the engine, checked before any library call: (source indices u32, (first,
+    last) frames u32, sound indices u32, (first, len) sample windows u64).  An empty Spot is a pair without a source and
+    without a span, and an empty window of sound 0.  context: every window runs on to the end of its recording."""
+    if indices is not None or match_step is not None:
+        raise ValueError("spans name the source of every target themselves: indices and match_step do not go with them")
+    spots = list(spots)
+    if len(spots) != len(targets):
+        raise ValueError("spans must hold one Spot per target")
+    n = len(spots)
+    src, first, last = (np.full(n, NO_MATCH, dtype=np.uint32) for _ in range(3))
+    snd, w_first, w_len = np.zeros(n, dtype=np.uint32), np.zeros(n, dtype=np.uint64), np.zeros(n, dtype=np.uint64)
+    for t, sp in enumerate(spots):
+        if not isinstance(sp, Spot):
+            raise ValueError("spans must hold one Spot per target")
+        if not sp:
+            continue
+        if not 0 <= sp.source_index < len(sounds):
+            raise ValueError("a spot names a sound outside the dictionary")
+        s = sounds[sp.source_index]
+        if sp.end_frame >= s.num_frames():
+            raise ValueError("a spot ends beyond its sound's frames")
+        size = s.samples().size
+        a, b = sp.sample_span(size)
+        a = min(a, size)
+        src[t], first[t], last[t], snd[t] = sp.source_index, sp.start_frame, sp.end_frame, sp.source_index
+        w_first[t], w_len[t] = a, (size if context else max(a, b)) - a
+    return src, (first, last), snd, (w_first, w_len)
 
 
 class Spot:
@@ -693,7 +726,8 @@ class SoundDictionary:
         return idx, cost
 
 
-    def align(self, targets: Sequence[Sound], indices=None, step: str = "symmetric", match_step=None) -> List["Alignment"]:
+    def align(self, targets: Sequence[Sound], indices=None, step: str = "symmetric", match_step=None,
+              spans=None) -> List["Alignment"]:
         """The warping path of every target onto a dictionary sound (dtw engines; ssym_dtw_align).  indices=None:
         every target is matched first (match_indices) and aligned with its match -- two library calls in all;
         otherwise indices[t] is the dictionary sound target t is aligned with.  step="paced": the paced step pattern
@@ -702,12 +736,31 @@ class SoundDictionary:
         frame_map is its first column; a sound too short or too long for the target (outside about half to twice its
         frames) has no such path and gives an empty Alignment.  match_step (looked at with indices=None): None keeps the
         symmetric search, which may pick such a sound; "paced" (with step="paced" only) searches under the paced pattern
-        (match_indices(step="paced")), so every match that has a finite cost is aligned at that cost."""
+        (match_indices(step="paced")), so every match that has a finite cost is aligned at that cost.  spans: one Spot per
+        target (what spot and spot_all return; not with indices or match_step) -- target t is aligned with frames
+        start_frame ... end_frame of recording source_index where they lie, in the resident dictionary
+        (ssym_dtw_align_spans): the results of cut(spots).align(targets, indices=arange) bit for bit, with
+        Alignment.source_index the recording, path and frame_map counted from Alignment.span_start = start_frame, and an
+        empty Alignment for an empty Spot."""
         _spot_step(step)
+        targets = list(targets)
+        if spans is not None:
+            src, frames, _, _ = _span_args(self.sounds, spans, targets, indices, match_step)
+            if not self.sounds:
+                raise EmptyDictionaryError(-2, "empty dictionary")
+            if not targets:
+                return []
+            flat, off = pack_segments([t.mfccs() for t in targets], self._dim(), self.engine.np_dtype)
+            q = self.engine.queries(flat, off, self._dim())
+            try:
+                cost, _, paths, maps = self.engine.dtw_align(self.resident(), q, src, spans=frames, **_step_kw(step))
+            finally:
+                q.close()
+            return [Alignment(cost[t], paths[t], maps[t], int(src[t]), 0 if src[t] == NO_MATCH else int(frames[0][t]))
+                    for t in range(len(targets))]
         match_kw = _match_kw(step, match_step)
         if not self.sounds:
             raise EmptyDictionaryError(-2, "empty dictionary")
-        targets = list(targets)
         if indices is not None:
             indices = np.asarray(indices, dtype=np.int64).reshape(-1)
             if indices.size != len(targets):
@@ -727,7 +780,7 @@ class SoundDictionary:
         return [Alignment(cost[t], paths[t], maps[t], int(indices[t])) for t in range(len(targets))]
 
     def warp(self, targets: Sequence[Sound], indices=None, want_pcm32: bool = False, search: int = 0,
-             want_pos: bool = False, step: str = "symmetric", match_step=None):
+             want_pos: bool = False, step: str = "symmetric", match_step=None, spans=None, context: bool = False):
         """The reconstruction of the targets with every match warped onto its target's timing (dtw engines): match
         (unless indices[t] names the dictionary sound of target t), align with the outputs left on the device, and
         resynthesise along the maps -- ssym_match_queries, ssym_dtw_align, ssym_reconstruct_warped; the maps never
@@ -739,8 +792,20 @@ class SoundDictionary:
         step="paced": the alignment is the paced one (align), whose maps move by 0, 1 or 2 source frames per target frame
         and never stand still twice in a row; a pair whose shape admits no paced path takes the length fit.  match_step
         as for align: "paced" (with step="paced") matches under the paced pattern too, so that no target falls back to the
-        length fit because the symmetric search chose a sound of the wrong length."""
+        length fit because the symmetric search chose a sound of the wrong length.  spans: one Spot per target (not with
+        indices or match_step) -- every span is aligned and resynthesised where it lies, from the resident dictionary and
+        the resident samples (ssym_dtw_align_spans, then ssym_reconstruct_warped_spans or ssym_reconstruct_wsola_spans over
+        the samples of spot.sample_span()): the results of cut(spots).warp(targets, indices=arange) bit for bit, zeros for an
+        empty Spot, with no second dictionary and no second sample store.  context=True (with spans) lets every window run
+        on to the end of its recording: look-ahead taps and WSOLA candidates past the span's end then read the
+        recording's real continuation instead of dropping out; nothing else changes."""
         _spot_step(step)
+        targets = list(targets)
+        span_args = None
+        if spans is not None:
+            span_args = _span_args(self.sounds, spans, targets, indices, match_step, bool(context))
+        elif context:
+            raise ValueError("context widens the sample windows of spans: it needs spans")
         match_kw = _match_kw(step, match_step)
         if not self.sounds:
             raise EmptyDictionaryError(-2, "empty dictionary")
@@ -749,7 +814,6 @@ class SoundDictionary:
         search = _wsola_search(search)
         if want_pos and not search:
             raise ValueError("want_pos needs search > 0: without a search the positions are the map times 256")
-        targets = list(targets)
         if indices is not None:
             indices = np.asarray(indices, dtype=np.int64).reshape(-1)
             if indices.size != len(targets):
@@ -764,6 +828,8 @@ class SoundDictionary:
         out_off = np.concatenate([[0], np.cumsum([t.samples().size for t in targets])]).astype(np.uint64)
         q = self.engine.queries(flat, off, self._dim())
         try:
+            if span_args is not None:
+                return self._warp_spans(q, span_args, out_off, step, search, want_pcm32, want_pos)
             if indices is None:
                 indices, _ = self.engine.match(self.resident(), q, **match_kw)
             _, lengths, _, maps, _, m_off = self.engine.dtw_align_device(self.resident(), q, indices, **_step_kw(step))
@@ -775,6 +841,49 @@ class SoundDictionary:
             return res + (m_off,) if want_pos else res
         finally:
             q.close()
+
+    def _warp_spans(self, q, span_args, out_off, step, search, want_pcm32, want_pos):
+        """The tail of warp(spans=) and reconstruct_spotted: span alignment with the outputs left on the device, then the
+        window reconstruction -- two library calls on the resident query set q; maps and lengths never visit the host."""
+        src, frames, snd, windows = span_args
+        _, lengths, _, maps, _, m_off = self.engine.dtw_align_device(self.resident(), q, src, spans=frames, **_step_kw(step))
+        if not search:
+            return self.engine.reconstruct_warped(self.resident_samples(), snd, out_off, maps, m_off,
+                                                  np.diff(m_off.astype(np.int64)), lengths, want_pcm32, windows=windows)
+        res = self.engine.reconstruct_wsola(self.resident_samples(), snd, out_off, maps, m_off,
+                                            np.diff(m_off.astype(np.int64)), lengths, search, want_pcm32, want_pos,
+                                            windows=windows)
+        return res + (m_off,) if want_pos else res
+
+    def reconstruct_spotted(self, targets: Sequence[Sound], step: str = "symmetric", search: int = 0,
+                            want_pcm32: bool = False):
+        """spot, then warp(spans=) on one upload of the targets: every target is located in the dictionary's recordings
+        (ssym_spot_queries), its span aligned with the outputs left on the device (ssym_dtw_align_spans) and
+        resynthesised from the resident samples (ssym_reconstruct_warped_spans, or with search > 0
+        ssym_reconstruct_wsola_spans) -- three library calls, one query set, no cut.  Returns (spots, samples), with
+        want_pcm32 (spots, samples, pcm)."""
+        _spot_step(step)
+        if not self.sounds:
+            raise EmptyDictionaryError(-2, "empty dictionary")
+        if getattr(self.engine, "metric", None) != "dtw":
+            raise SsymError(SSYM_E_UNSUPPORTED, "reconstruct_spotted aligns with dtw: a refcos engine has no alignment")
+        search = _wsola_search(search)
+        targets = list(targets)
+        if not targets:
+            return ([], np.zeros(0)) + ((np.zeros(0, dtype=np.int32),) if want_pcm32 else ())
+        flat, off = pack_segments([t.mfccs() for t in targets], self._dim(), self.engine.np_dtype)
+        out_off = np.concatenate([[0], np.cumsum([t.samples().size for t in targets])]).astype(np.uint64)
+        frames = np.diff(off.astype(np.int64))
+        q = self.engine.queries(flat, off, self._dim())
+        try:
+            indices, cost, start, end = self.engine.spot_queries(self.resident(), q, **_step_kw(step))
+            spots = [Spot(int(indices[t]), int(start[t]), int(end[t]), cost[t], _per_frame(step, cost[t], frames[t]))
+                     if int(end[t]) != NO_MATCH else Spot.none() for t in range(len(targets))]
+            res = self._warp_spans(q, _span_args(self.sounds, spots, targets, None, None), out_off, step, search,
+                                   want_pcm32, False)
+        finally:
+            q.close()
+        return (spots,) + (res if isinstance(res, tuple) else (res,))
 
     def spot(self, targets: Sequence[Sound], indices=None, step: str = "symmetric") -> List["Spot"]:
         """Where inside the dictionary's (unsegmented) recordings every target sounds: subsequence DTW on the GPU (dtw
@@ -1067,6 +1176,11 @@ class SoundSequence:
         if not self._sounds:
             return (np.zeros(0), np.zeros(0, dtype=np.int32)) if want_pcm32 else np.zeros(0)
         return dict_.warp(self._sounds, None, want_pcm32, search, **_step_kw(step), **match_kw)
+
+    def reconstruct_spotted_from_dictionary(self, dict_: "SoundDictionary", step: str = "symmetric", search: int = 0,
+                                            want_pcm32: bool = False):
+        """dict_.reconstruct_spotted of this sequence's sounds: (spots, samples[, pcm])."""
+        return dict_.reconstruct_spotted(self._sounds, step, search, want_pcm32)
 
     def to_sound(self) -> Sound:                                        # src/sound.rs:475-483
         parts = [s.samples() for s in self._sounds]

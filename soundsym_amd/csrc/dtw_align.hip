@@ -386,13 +386,40 @@ __global__ __launch_bounds__(64) void dtw_align_paced_kernel(const AlignArgs a)
     }
 }
 
-// the frames of a listed pair, (0, 0) for a pair without a source or with an empty segment
-inline void align_shape(const SegmentSet &src, const SegmentSet &tgt, uint32_t s, uint32_t t, uint64_t *fa, uint64_t *fb)
+// Spans (ssym_dtw_align_spans; DESIGN.md 2 "Spans", 5.22): a listed source is frames first[p] ... last[p] of its segment.
+// The kernels are untouched: they find a source through srcOff[s] and srcOff[s + 1], so a spans call hands them a per-call
+// offset table with two entries per pair -- the span's first frame and the frame after its last, both counted from the
+// dictionary's first frame -- and lists pair p with source 2 p.
+struct AlignSpans {
+    const uint32_t *first = nullptr, *last = nullptr;     // HOST, n_pairs each; both NULL: whole segments
+    explicit operator bool() const { return first != nullptr; }
+};
+
+// the span of listed pair p against its segment (s: the set's own index, SSYM_NO_MATCH stays): *none = a spot without a span
+inline int32_t check_span(std::string &err, const std::string &name, const SegmentSet &src, uint32_t s, const AlignSpans &sp,
+                          uint32_t p, bool *none)
+{
+    const uint32_t f = sp.first[p], l = sp.last[p];
+    *none = f == SSYM_NO_MATCH && l == SSYM_NO_MATCH;
+    if (*none || s == SSYM_NO_MATCH)
+        return SSYM_OK;
+    if (f == SSYM_NO_MATCH || l == SSYM_NO_MATCH || f > l || (uint64_t)l >= src.h_off[s + 1] - src.h_off[s]) {
+        err = name + ": span " + std::to_string(p) + " is not first <= last < the segment's frames (or only one end is SSYM_NO_MATCH)";
+        return SSYM_E_INVALID;
+    }
+    return SSYM_OK;
+}
+
+// the frames of a listed pair, (0, 0) for a pair without a source or with an empty segment; with spans (checked) the
+// source's frames are the span's, and a spot without a span is a pair without a source
+inline void align_shape(const SegmentSet &src, const SegmentSet &tgt, uint32_t s, uint32_t t, uint64_t *fa, uint64_t *fb,
+                        const AlignSpans &sp = AlignSpans(), uint32_t p = 0)
 {
     *fa = *fb = 0;
-    if (s == SSYM_NO_MATCH)
+    if (s == SSYM_NO_MATCH || (sp && sp.first[p] == SSYM_NO_MATCH))
         return;
-    const uint64_t a = src.h_off[s + 1] - src.h_off[s], b = tgt.h_off[t + 1] - tgt.h_off[t];
+    const uint64_t a = sp ? (uint64_t)sp.last[p] - sp.first[p] + 1 : src.h_off[s + 1] - src.h_off[s];
+    const uint64_t b = tgt.h_off[t + 1] - tgt.h_off[t];
     if (a == 0 || b == 0)
         return;
     *fa = a;
@@ -401,10 +428,10 @@ inline void align_shape(const SegmentSet &src, const SegmentSet &tgt, uint32_t s
 
 // Fa + Fb - 1 steps and Fb map entries per pair, 0 for a pair without a source or with an empty segment
 inline void align_capacity(const SegmentSet &src, const SegmentSet &tgt, uint32_t s, uint32_t t, uint64_t *steps,
-                           uint64_t *frames)
+                           uint64_t *frames, const AlignSpans &sp = AlignSpans(), uint32_t p = 0)
 {
     uint64_t fa, fb;
-    align_shape(src, tgt, s, t, &fa, &fb);
+    align_shape(src, tgt, s, t, &fa, &fb, sp, p);
     *steps = fb ? fa + fb - 1 : 0;
     *frames = fb;
 }
@@ -412,7 +439,8 @@ inline void align_capacity(const SegmentSet &src, const SegmentSet &tgt, uint32_
 int32_t dtw_align(ssym_ctx *ctx, const ssym_dict *dict, const ssym_queries *q, const uint32_t *src_idx,
                   const uint32_t *tgt_idx, uint32_t n_pairs, uint32_t index_base, double *out_cost, uint32_t *out_len,
                   const uint64_t *path_offsets, uint32_t *out_path, const uint64_t *map_offsets, uint32_t *out_map,
-                  uint32_t flags, uint32_t step = SSYM_STEP_SYMMETRIC, const char *fn = "ssym_dtw_align")
+                  uint32_t flags, uint32_t step = SSYM_STEP_SYMMETRIC, const char *fn = "ssym_dtw_align",
+                  const AlignSpans &sp = AlignSpans())
 {
     if (!ctx)
         return SSYM_E_INVALID;
@@ -439,14 +467,35 @@ int32_t dtw_align(ssym_ctx *ctx, const ssym_dict *dict, const ssym_queries *q, c
         ctx->err = name + ": out_cost, out_len, path_offsets, out_path (and map_offsets with out_map) must not be NULL";
         return SSYM_E_INVALID;
     }
+    if (sp && n_pairs > 0x7fffffffu) {
+        ctx->err = name + ": more than 2^31 - 1 spans in one call";
+        return SSYM_E_UNSUPPORTED;
+    }
     const SegmentSet &src = dict->set, &tgt = q->set;
     // the pair list, the offsets against the capacities, the shape limits: all on the host, before any device work
     PairList pairs(src_idx, tgt_idx, index_base, n_pairs);
     uint64_t listedFa = 0, listedFb = 0;               // what the limits hold: every listed pair with frames
     uint64_t maxFa = 0, maxFb = 0, maxSlab = 0;        // what sizes LDS and the slabs: the pairs the kernel runs
+    std::vector<uint64_t> hSpan(sp ? 2 * (size_t)n_pairs : 0);     // the kernels' source offsets of a spans call
     for (uint32_t p = 0; p < n_pairs; ++p) {
         uint64_t fa, fb;
-        align_shape(src, tgt, pairs.host[p].x, pairs.host[p].y, &fa, &fb);
+        if (sp) {
+            bool none;
+            rc = check_span(ctx->err, name, src, pairs.host[p].x, sp, p, &none);
+            if (rc != SSYM_OK)
+                return rc;
+        }
+        align_shape(src, tgt, pairs.host[p].x, pairs.host[p].y, &fa, &fb, sp, p);
+        if (sp) {
+            // the source the kernel sees: entries 2 p and 2 p + 1 of the span table, or none
+            const uint32_t s = pairs.host[p].x;
+            const bool has = s != SSYM_NO_MATCH && sp.first[p] != SSYM_NO_MATCH;
+            if (has) {
+                hSpan[2 * (size_t)p] = src.h_off[s] + sp.first[p];
+                hSpan[2 * (size_t)p + 1] = src.h_off[s] + sp.last[p] + 1;
+            }
+            pairs.host[p].x = has ? 2 * p : SSYM_NO_MATCH;
+        }
         // a paced path has one cell per target frame
         const uint64_t steps = fb == 0 ? 0 : paced ? fb : fa + fb - 1;
         if (path_offsets[p + 1] < path_offsets[p] || path_offsets[p + 1] - path_offsets[p] < steps ||
@@ -469,7 +518,7 @@ int32_t dtw_align(ssym_ctx *ctx, const ssym_dict *dict, const ssym_queries *q, c
             maxSlab = std::max(maxSlab, dirBytes);
     }
     if (listedFa > (uint64_t)kAlignMaxFrames || listedFb > (uint64_t)kAlignMaxFrames || src.dim > (uint32_t)kAlignMaxDim) {
-        ctx->err = name + ": a listed segment has more than " + std::to_string(kAlignMaxFrames) +
+        ctx->err = name + ": a listed " + (sp ? "span or target" : "segment") + " has more than " + std::to_string(kAlignMaxFrames) +
                    " frames, or frames have more than " + std::to_string(kAlignMaxDim) + " values";
         return SSYM_E_UNSUPPORTED;
     }
@@ -486,13 +535,14 @@ int32_t dtw_align(ssym_ctx *ctx, const ssym_dict *dict, const ssym_queries *q, c
 
     Blocks bl(ctx);
     AlignArgs a{};
-    uint64_t *dOff = nullptr;        // path offsets, then map offsets, both rebased to the first pair's
-    rc = bl.get(&dOff, 2 * ((size_t)n_pairs + 1));
-    std::vector<uint64_t> hOff(2 * ((size_t)n_pairs + 1));
+    uint64_t *dOff = nullptr;        // path offsets, then map offsets, both rebased to the first pair's; then the span table
+    rc = bl.get(&dOff, 2 * ((size_t)n_pairs + 1) + hSpan.size());
+    std::vector<uint64_t> hOff(2 * ((size_t)n_pairs + 1) + hSpan.size());
     for (uint32_t p = 0; p <= n_pairs; ++p) {
         hOff[p] = path_offsets[p] - path_offsets[0];
         hOff[(size_t)n_pairs + 1 + p] = out_map ? map_offsets[p] - map_offsets[0] : 0;
     }
+    std::copy(hSpan.begin(), hSpan.end(), hOff.begin() + 2 * ((size_t)n_pairs + 1));
     double *dCost = out_cost;
     uint32_t *dLen = out_len, *dPath = out_path + 2 * path_offsets[0], *dMap = out_map ? out_map + map_offsets[0] : nullptr;
     if (!outDev) {
@@ -526,7 +576,7 @@ int32_t dtw_align(ssym_ctx *ctx, const ssym_dict *dict, const ssym_queries *q, c
         return rc;
     SSYM_HIP_CHECK(ctx, hipMemcpyAsync(dOff, hOff.data(), sizeof(uint64_t) * hOff.size(), hipMemcpyHostToDevice, st));
     a.srcRaw = src.raw;
-    a.srcOff = src.off;
+    a.srcOff = sp ? dOff + 2 * ((size_t)n_pairs + 1) : src.off;
     a.tgtRaw = tgt.raw;
     a.tgtOff = tgt.off;
     a.dim = src.dim;
@@ -572,6 +622,34 @@ int32_t dtw_align(ssym_ctx *ctx, const ssym_dict *dict, const ssym_queries *q, c
     return SSYM_OK;
 }
 
+// ssym_dtw_align_sizes, and with spans ssym_dtw_align_spans_sizes: nothing is written before every pair is checked
+int32_t dtw_align_sizes(const char *fn, const ssym_dict *dict, const ssym_queries *q, const uint32_t *src_idx,
+                        const uint32_t *tgt_idx, uint32_t n_pairs, uint32_t index_base, uint64_t *path_offsets,
+                        uint64_t *map_offsets, const AlignSpans &sp = AlignSpans())
+{
+    std::string err;
+    int32_t rc = check_pair_list(err, fn, dict, q, src_idx, tgt_idx, n_pairs, index_base);
+    if (rc != SSYM_OK)
+        return rc;
+    if (!path_offsets || !map_offsets)
+        return SSYM_E_INVALID;
+    for (uint32_t p = 0; sp && p < n_pairs; ++p) {
+        bool none;
+        rc = check_span(err, fn, dict->set, pair_at(src_idx, tgt_idx, index_base, p).x, sp, p, &none);
+        if (rc != SSYM_OK)
+            return rc;
+    }
+    path_offsets[0] = map_offsets[0] = 0;
+    for (uint32_t p = 0; p < n_pairs; ++p) {
+        const uint2 pr = pair_at(src_idx, tgt_idx, index_base, p);
+        uint64_t steps, frames;
+        align_capacity(dict->set, q->set, pr.x, pr.y, &steps, &frames, sp, p);
+        path_offsets[p + 1] = path_offsets[p] + steps;
+        map_offsets[p + 1] = map_offsets[p] + frames;
+    }
+    return SSYM_OK;
+}
+
 }  // namespace
 }  // namespace ssym
 
@@ -584,21 +662,42 @@ int32_t ssym_dtw_align_sizes(const ssym_dict *dict, const ssym_queries *q, const
                              uint64_t *map_offsets)
 {
     return guarded(nullptr, [&]() -> int32_t {
-        std::string err;
-        const int32_t rc = check_pair_list(err, "ssym_dtw_align", dict, q, src_idx, tgt_idx, n_pairs, index_base);
-        if (rc != SSYM_OK)
-            return rc;
-        if (!path_offsets || !map_offsets)
+        return dtw_align_sizes("ssym_dtw_align", dict, q, src_idx, tgt_idx, n_pairs, index_base, path_offsets, map_offsets);
+    });
+}
+
+// the two calls above with a span of source frames per pair: the same drivers, the kernels untouched (AlignSpans)
+int32_t ssym_dtw_align_spans_sizes(const ssym_dict *dict, const ssym_queries *q, const uint32_t *src_idx,
+                                   const uint32_t *tgt_idx, const uint32_t *span_first, const uint32_t *span_last,
+                                   uint32_t n_pairs, uint32_t index_base, uint64_t *path_offsets, uint64_t *map_offsets)
+{
+    return guarded(nullptr, [&]() -> int32_t {
+        if (n_pairs && (!span_first || !span_last))
             return SSYM_E_INVALID;
-        path_offsets[0] = map_offsets[0] = 0;
-        for (uint32_t p = 0; p < n_pairs; ++p) {
-            const uint2 pr = pair_at(src_idx, tgt_idx, index_base, p);
-            uint64_t steps, frames;
-            align_capacity(dict->set, q->set, pr.x, pr.y, &steps, &frames);
-            path_offsets[p + 1] = path_offsets[p] + steps;
-            map_offsets[p + 1] = map_offsets[p] + frames;
+        AlignSpans sp;
+        sp.first = span_first;
+        sp.last = span_last;
+        return dtw_align_sizes("ssym_dtw_align_spans", dict, q, src_idx, tgt_idx, n_pairs, index_base, path_offsets,
+                               map_offsets, sp);
+    });
+}
+
+int32_t ssym_dtw_align_spans(ssym_ctx *ctx, const ssym_dict *dict, const ssym_queries *q, const uint32_t *src_idx,
+                             const uint32_t *tgt_idx, const uint32_t *span_first, const uint32_t *span_last,
+                             uint32_t n_pairs, uint32_t index_base, uint32_t step, double *out_cost, uint32_t *out_len,
+                             const uint64_t *path_offsets, uint32_t *out_path, const uint64_t *map_offsets,
+                             uint32_t *out_map, uint32_t flags)
+{
+    return guarded(ctx, [&]() -> int32_t {
+        if (ctx && n_pairs && (!span_first || !span_last)) {
+            ctx->err = "ssym_dtw_align_spans: span_first and span_last must not be NULL";
+            return SSYM_E_INVALID;
         }
-        return SSYM_OK;
+        AlignSpans sp;
+        sp.first = span_first;
+        sp.last = span_last;
+        return dtw_align(ctx, dict, q, src_idx, tgt_idx, n_pairs, index_base, out_cost, out_len, path_offsets, out_path,
+                         map_offsets, out_map, flags, step, "ssym_dtw_align_spans", sp);
     });
 }
 

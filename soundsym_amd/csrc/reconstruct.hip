@@ -86,6 +86,7 @@ int32_t ssym_samples_create(ssym_ctx *ctx, const double *samples, const uint64_t
         return SSYM_E_NOMEM;
     h->n = n_sounds;
     h->total = sample_offsets[n_sounds];
+    h->h_off.assign(sample_offsets, sample_offsets + n_sounds + 1);
     if (h->total && !samples) {
         delete h;
         ctx->err = "samples is NULL";

@@ -218,9 +218,48 @@ struct ssym_queries {
 struct ssym_samples {
     double *samples = nullptr;      // device, [total]
     uint64_t *off = nullptr;        // device, [n + 1] sample offsets
+    std::vector<uint64_t> h_off;    // host copy (the window calls check against it and build their window tables from it)
     uint32_t n = 0;
     uint64_t total = 0;
 };
+
+namespace ssym {
+
+// Sample windows (ssym_reconstruct_warped_spans / _wsola_spans; DESIGN.md 2 "Spans", 5.22): target t's sound is samples
+// first[t] ... first[t] + len[t] - 1 of sound idx[t].  The kernels are untouched: they find a sound through srcOff[s] and
+// srcOff[s + 1], so a window call hands them a per-call offset table with two entries per target -- where the window starts
+// in the store and where it ends -- and lists target t with sound 2 t.
+struct SampleWindows {
+    const uint64_t *first = nullptr, *len = nullptr;      // HOST, n_targets each; both NULL: whole sounds
+    explicit operator bool() const { return first != nullptr; }
+    // the checks of a window call, after the plain call's own (every idx[t] < s->n)
+    int32_t check(std::string &err, const char *fn, const ssym_samples *s, const uint32_t *idx, uint32_t n_targets) const
+    {
+        if (n_targets > 0x7fffffffu) {
+            err = std::string(fn) + ": more than 2^31 - 1 windows in one call";
+            return SSYM_E_UNSUPPORTED;
+        }
+        for (uint32_t t = 0; t < n_targets; ++t) {
+            const uint64_t sLen = s->h_off[idx[t] + 1] - s->h_off[idx[t]];
+            if (first[t] > sLen || len[t] > sLen - first[t]) {
+                err = std::string(fn) + ": window " + std::to_string(t) + " reaches beyond its sound's samples";
+                return SSYM_E_INVALID;
+            }
+        }
+        return SSYM_OK;
+    }
+    // the table (2 n_targets u64) and the indices into it (n_targets u32)
+    void fill(const ssym_samples *s, const uint32_t *idx, uint32_t n_targets, uint64_t *table, uint32_t *tabIdx) const
+    {
+        for (uint32_t t = 0; t < n_targets; ++t) {
+            table[2 * (size_t)t] = s->h_off[idx[t]] + first[t];
+            table[2 * (size_t)t + 1] = table[2 * (size_t)t] + len[t];
+            tabIdx[t] = 2 * t;
+        }
+    }
+};
+
+}  // namespace ssym
 
 namespace ssym {
 

@@ -282,24 +282,26 @@ __global__ __launch_bounds__(256) void wsola_synth_kernel(const WsolaArgs a)
 int32_t reconstruct_wsola(ssym_ctx *ctx, const ssym_samples *s, const uint32_t *idx, const uint64_t *out_offsets,
                           uint32_t n_targets, const uint32_t *frame_map, const uint64_t *map_offsets,
                           const uint32_t *map_frames, const uint32_t *pair_len, uint32_t search, uint32_t flags,
-                          uint64_t *out_pos, double *out_samples, int32_t *out_pcm32)
+                          uint64_t *out_pos, double *out_samples, int32_t *out_pcm32,
+                          const SampleWindows &wn = SampleWindows(), const char *fn = "ssym_reconstruct_wsola")
 {
     if (!ctx)
         return SSYM_E_INVALID;
+    const std::string name(fn);
     if (!s || !idx || !out_offsets || !map_offsets || !map_frames) {
-        ctx->err = "ssym_reconstruct_wsola: s, idx, out_offsets, map_offsets and map_frames must not be NULL";
+        ctx->err = name + ": s, idx, out_offsets, map_offsets and map_frames must not be NULL";
         return SSYM_E_INVALID;
     }
     if (search > kWsolaMaxSearch) {
-        ctx->err = "ssym_reconstruct_wsola: search must not exceed 512 samples";
+        ctx->err = name + ": search must not exceed 512 samples";
         return SSYM_E_INVALID;
     }
     if (out_offsets[0] != 0) {
-        ctx->err = "ssym_reconstruct_wsola: out_offsets must start at 0";
+        ctx->err = name + ": out_offsets must start at 0";
         return SSYM_E_INVALID;
     }
     if (flags & ~(uint32_t)(SSYM_OUT_DEVICE | SSYM_WARP_MAP_DEVICE)) {
-        ctx->err = "ssym_reconstruct_wsola: unknown flag bits";
+        ctx->err = name + ": unknown flag bits";
         return SSYM_E_INVALID;
     }
     if (s->n == 0) {
@@ -310,12 +312,12 @@ int32_t reconstruct_wsola(ssym_ctx *ctx, const ssym_samples *s, const uint32_t *
     bool anyMap = false;
     for (uint32_t t = 0; t < n_targets; ++t) {
         if (out_offsets[t + 1] < out_offsets[t] || idx[t] >= s->n) {
-            ctx->err = "ssym_reconstruct_wsola: out_offsets decrease or an index is outside the sample store (target " +
+            ctx->err = name + ": out_offsets decrease or an index is outside the sample store (target " +
                        std::to_string(t) + ")";
             return SSYM_E_INVALID;
         }
         if (map_offsets[t + 1] < map_offsets[t] || map_offsets[t + 1] - map_offsets[t] < map_frames[t]) {
-            ctx->err = "ssym_reconstruct_wsola: map_offsets decrease or leave less room than map_frames (target " +
+            ctx->err = name + ": map_offsets decrease or leave less room than map_frames (target " +
                        std::to_string(t) + ")";
             return SSYM_E_INVALID;
         }
@@ -323,8 +325,13 @@ int32_t reconstruct_wsola(ssym_ctx *ctx, const ssym_samples *s, const uint32_t *
         maxLen = std::max<uint64_t>(maxLen, out_offsets[t + 1] - out_offsets[t]);
     }
     if (anyMap && !frame_map) {
-        ctx->err = "ssym_reconstruct_wsola: frame_map is NULL although a target has map frames";
+        ctx->err = name + ": frame_map is NULL although a target has map frames";
         return SSYM_E_INVALID;
+    }
+    if (wn) {
+        const int32_t wrc = wn.check(ctx->err, fn, s, idx, n_targets);
+        if (wrc != SSYM_OK)
+            return wrc;
     }
     const uint64_t total = out_offsets[n_targets];
     if (n_targets == 0 || total == 0 || (!out_samples && !out_pcm32))
@@ -342,7 +349,7 @@ int32_t reconstruct_wsola(ssym_ctx *ctx, const ssym_samples *s, const uint32_t *
     // pair_len] u32 -- one block, uploaded in one copy; behind it the caller's map and the positions, unless they are
     // device memory of the caller's
     const size_t n1 = (size_t)n_targets + 1;
-    const size_t words64 = 2 * n1 + kWarpBin;
+    const size_t words64 = 2 * n1 + kWarpBin + (wn ? 2 * (size_t)n_targets : 0);     // ... | window table] with windows
     const size_t words32 = (size_t)n_targets * (upLen ? 3 : 2);
     std::vector<uint64_t> host(words64 + (words32 + 1) / 2);
     std::copy(out_offsets, out_offsets + n1, host.begin());
@@ -351,7 +358,10 @@ int32_t reconstruct_wsola(ssym_ctx *ctx, const ssym_samples *s, const uint32_t *
     static_assert(sizeof(double) == sizeof(uint64_t), "one staging block");
     std::copy(warp_window().begin(), warp_window().end(), reinterpret_cast<double *>(host.data() + 2 * n1));
     uint32_t *h32 = reinterpret_cast<uint32_t *>(host.data() + words64);
-    std::copy(idx, idx + n_targets, h32);
+    if (wn)
+        wn.fill(s, idx, n_targets, host.data() + 2 * n1 + kWarpBin, h32);
+    else
+        std::copy(idx, idx + n_targets, h32);
     std::copy(map_frames, map_frames + n_targets, h32 + n_targets);
     if (upLen)
         std::copy(pair_len, pair_len + n_targets, h32 + 2 * (size_t)n_targets);
@@ -382,8 +392,8 @@ int32_t reconstruct_wsola(ssym_ctx *ctx, const ssym_samples *s, const uint32_t *
     }
     WsolaArgs a{};
     a.src = s->samples;
-    a.srcOff = s->off;
-    a.nSounds = s->n;
+    a.srcOff = wn ? d64 + 2 * n1 + kWarpBin : s->off;
+    a.nSounds = wn ? 2 * n_targets : s->n;
     a.nTargets = n_targets;
     a.search = search;
     a.idx = d32;
@@ -444,6 +454,26 @@ int32_t ssym_reconstruct_wsola(ssym_ctx *ctx, const ssym_samples *s, const uint3
     return guarded(ctx, [&]() -> int32_t {
         return reconstruct_wsola(ctx, s, idx, out_offsets, n_targets, frame_map, map_offsets, map_frames, pair_len, search,
                                  flags, out_pos, out_samples, out_pcm32);
+    });
+}
+
+// the call above with a window of samples per target: the same driver, the kernels untouched (SampleWindows)
+int32_t ssym_reconstruct_wsola_spans(ssym_ctx *ctx, const ssym_samples *s, const uint32_t *idx, const uint64_t *win_first,
+                                     const uint64_t *win_len, const uint64_t *out_offsets, uint32_t n_targets,
+                                     const uint32_t *frame_map, const uint64_t *map_offsets, const uint32_t *map_frames,
+                                     const uint32_t *pair_len, uint32_t search, uint32_t flags, uint64_t *out_pos,
+                                     double *out_samples, int32_t *out_pcm32)
+{
+    return guarded(ctx, [&]() -> int32_t {
+        if (ctx && (!win_first || !win_len)) {
+            ctx->err = "ssym_reconstruct_wsola_spans: win_first and win_len must not be NULL";
+            return SSYM_E_INVALID;
+        }
+        SampleWindows wn;
+        wn.first = win_first;
+        wn.len = win_len;
+        return reconstruct_wsola(ctx, s, idx, out_offsets, n_targets, frame_map, map_offsets, map_frames, pair_len, search,
+                                 flags, out_pos, out_samples, out_pcm32, wn, "ssym_reconstruct_wsola_spans");
     });
 }
 

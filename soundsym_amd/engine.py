@@ -43,6 +43,27 @@ def _align_indices(src_idx, tgt_idx):
     return src, tgt
 
 
+def _align_spans(spans, n):
+    """spans=(first, last) of dtw_align as two contiguous uint32 arrays of n inclusive source frames, or None."""
+    if spans is None:
+        return None
+    first, last = (np.ascontiguousarray(x, dtype=np.uint32).reshape(-1) for x in spans)
+    if first.size != n or last.size != n:
+        raise ValueError("spans must give one first and one last source frame per pair")
+    return first, last
+
+
+def _warp_windows(windows, n):
+    """windows=(first, len) of reconstruct_warped / reconstruct_wsola as two contiguous uint64 arrays of n sample counts, or
+    None."""
+    if windows is None:
+        return None
+    first, length = (np.ascontiguousarray(x, dtype=np.uint64).reshape(-1) for x in windows)
+    if first.size != n or length.size != n:
+        raise ValueError("windows must give one first sample and one length per target")
+    return first, length
+
+
 def _spot_step(step):
     """SSYM_STEP_* of step="symmetric" | "paced", checked before the library is asked."""
     if step == "symmetric":
@@ -811,28 +832,39 @@ class Engine:
         nat.check(rc, self.ctx)
         return out
 
-    def dtw_align_sizes(self, d: _Handle, q: _Handle, src_idx, tgt_idx=None, index_base: int = 0):
+    def dtw_align_sizes(self, d: _Handle, q: _Handle, src_idx, tgt_idx=None, index_base: int = 0, spans=None):
         """ssym_dtw_align_sizes: (path_offsets, map_offsets), n_pairs + 1 uint64 each -- the room a pair's path
-        (Fa + Fb - 1 cells) and map (Fb entries) can need.  Host arithmetic."""
+        (Fa + Fb - 1 cells) and map (Fb entries) can need.  Host arithmetic.  spans=(first, last):
+        ssym_dtw_align_spans_sizes, Fa the span's frames."""
         src, tgt = _align_indices(src_idx, tgt_idx)
+        spans = _align_spans(spans, src.size)
         p_off = np.zeros(src.size + 1, dtype=np.uint64)
         m_off = np.zeros(src.size + 1, dtype=np.uint64)
-        rc = nat.lib().ssym_dtw_align_sizes(d.ptr, q.ptr, src.ctypes.data, tgt.ctypes.data if tgt is not None else None,
-                                            src.size, index_base, p_off.ctypes.data, m_off.ctypes.data)
+        if spans is None:
+            rc = nat.lib().ssym_dtw_align_sizes(d.ptr, q.ptr, src.ctypes.data, tgt.ctypes.data if tgt is not None else None,
+                                                src.size, index_base, p_off.ctypes.data, m_off.ctypes.data)
+        else:
+            rc = nat.lib().ssym_dtw_align_spans_sizes(d.ptr, q.ptr, src.ctypes.data, tgt.ctypes.data if tgt is not None else None,
+                                                      spans[0].ctypes.data, spans[1].ctypes.data, src.size, index_base,
+                                                      p_off.ctypes.data, m_off.ctypes.data)
         if rc == nat.SSYM_E_EMPTY_DICT:
             raise nat.EmptyDictionaryError(rc, "empty dictionary")
         if rc != nat.SSYM_OK:
-            raise nat.SsymError(rc, "ssym_dtw_align_sizes: an index is outside its set, or the sets do not go together")
+            raise nat.SsymError(rc, "ssym_dtw_align_sizes: an index is outside its set, the sets do not go together, or a "
+                                    "span is not inside its segment")
         return p_off, m_off
 
-    def _align_call(self, which, head, tail):
-        """ssym_dtw_align for the symmetric pattern, ssym_dtw_align_step for any other."""
+    def _align_call(self, which, head, tail, spans=None):
+        """ssym_dtw_align for the symmetric pattern, ssym_dtw_align_step for any other; with spans ssym_dtw_align_spans,
+        which takes the spans behind the indices and the step behind index_base."""
+        if spans is not None:
+            return nat.lib().ssym_dtw_align_spans(*head[:5], spans[0].ctypes.data, spans[1].ctypes.data, *head[5:], which, *tail)
         if which == nat.STEP_SYMMETRIC:
             return nat.lib().ssym_dtw_align(*head, *tail)
         return nat.lib().ssym_dtw_align_step(*head, which, *tail)
 
     def dtw_align(self, d: _Handle, q: _Handle, src_idx, tgt_idx=None, index_base: int = 0, want_map: bool = True,
-                  step: str = "symmetric"):
+                  step: str = "symmetric", spans=None):
         """ssym_dtw_align: the optimal warping path of every listed pair (source src_idx[p] - index_base, target
         tgt_idx[p], or target p without tgt_idx), by the definition in include/soundsym_amd.h.  Returns (cost f64
         [n], lengths uint32 [n], paths, maps): paths[p] is an (L, 2) uint32 array of (source frame, target frame)
@@ -840,11 +872,15 @@ class Engine:
         None without want_map).  A pair without a finite cost has length 0, an empty path and an empty map.  The
         arrays are views into one buffer each.  step="paced": ssym_dtw_align_step with SSYM_STEP_PACED ("Paced
         alignment": one cell per target frame, steps of 0, 1 or 2 source frames, never two 0 steps in a row; a pair
-        whose shape admits no such path has length 0); "symmetric" is ssym_dtw_align itself."""
+        whose shape admits no such path has length 0); "symmetric" is ssym_dtw_align itself.  spans=(first, last), one
+        inclusive range of source frames per pair: ssym_dtw_align_spans -- the pair is (those frames of the segment,
+        target), cells and maps count from the span's first frame, and first = last = NO_MATCH is a pair without a path."""
         which = _spot_step(step)
         src, tgt = _align_indices(src_idx, tgt_idx)
         n = src.size
-        p_off, m_off = self.dtw_align_sizes(d, q, src, tgt, index_base)
+        spans = _align_spans(spans, n)
+        p_off, m_off = (self.dtw_align_sizes(d, q, src, tgt, index_base) if spans is None else
+                        self.dtw_align_sizes(d, q, src, tgt, index_base, spans))
         cost = np.zeros(n, dtype=np.float64)
         length = np.zeros(n, dtype=np.uint32)
         path = np.zeros((int(p_off[-1]), 2), dtype=np.uint32)
@@ -852,28 +888,31 @@ class Engine:
         head = (self.ctx, d.ptr, q.ptr, src.ctypes.data, tgt.ctypes.data if tgt is not None else None, n, index_base)
         tail = (cost.ctypes.data, length.ctypes.data, p_off.ctypes.data, path.ctypes.data,
                 m_off.ctypes.data if want_map else None, fmap.ctypes.data if want_map else None, 0)
-        nat.check(Engine._align_call(self, which, head, tail), self.ctx)
+        nat.check(Engine._align_call(self, which, head, tail, spans), self.ctx)
         paths = [path[int(p_off[p]):int(p_off[p]) + int(length[p])] for p in range(n)]
         maps = None
         if want_map:
             maps = [fmap[int(m_off[p]):int(m_off[p + 1])] if length[p] else fmap[0:0] for p in range(n)]
         return cost, length, paths, maps
 
-    def dtw_align_device(self, d: _Handle, q: _Handle, src_idx, tgt_idx=None, index_base: int = 0, step: str = "symmetric"):
+    def dtw_align_device(self, d: _Handle, q: _Handle, src_idx, tgt_idx=None, index_base: int = 0, step: str = "symmetric",
+                         spans=None):
         """ssym_dtw_align with SSYM_OUT_DEVICE: the outputs stay in device memory (torch tensors; torch only owns the
         memory).  Returns (cost f64 [n], lengths i32 [n], paths i32 [cells * 2], maps i32 [map entries], path_offsets,
         map_offsets); the 32-bit tensors hold the call's u32 values.  maps, lengths and map_offsets are what
-        reconstruct_warped takes.  step as for dtw_align."""
+        reconstruct_warped takes.  step and spans as for dtw_align; the maps of a spans call go with windows= there."""
         which = _spot_step(step)
         src, tgt = _align_indices(src_idx, tgt_idx)
         n = src.size
-        p_off, m_off = self.dtw_align_sizes(d, q, src, tgt, index_base)
+        spans = _align_spans(spans, n)
+        p_off, m_off = (self.dtw_align_sizes(d, q, src, tgt, index_base) if spans is None else
+                        self.dtw_align_sizes(d, q, src, tgt, index_base, spans))
         (cost, pc), (length, pl), (path, pp), (fmap, pm) = (
             _output(self.device, (rows,), t) for rows, t in ((n, np.float64), (n, np.uint32), (2 * int(p_off[-1]), np.uint32),
                                                             (int(m_off[-1]), np.uint32)))
         head = (self.ctx, d.ptr, q.ptr, src.ctypes.data, tgt.ctypes.data if tgt is not None else None, n, index_base)
         tail = (pc, pl, p_off.ctypes.data, pp, m_off.ctypes.data, pm, nat.OUT_DEVICE)
-        nat.check(Engine._align_call(self, which, head, tail), self.ctx)
+        nat.check(Engine._align_call(self, which, head, tail, spans), self.ctx)
         return cost, length, path, fmap, p_off, m_off
 
     def _dtw_spot(self, d, q, src_idx, tgt_idx, index_base, step, on_device):
@@ -1226,34 +1265,43 @@ class Engine:
         return (out, pcm) if want_pcm32 else out
 
     def reconstruct_warped(self, smp, idx, out_offsets, maps, map_offsets, map_frames, pair_len=None,
-                           want_pcm32: bool = False):
+                           want_pcm32: bool = False, windows=None):
         """ssym_reconstruct_warped: the matched sounds resynthesised along target-frame -> source-frame maps
         (definition in include/soundsym_amd.h), concatenated.  maps: u32 source frame per target frame, target t from
         map_offsets[t] on, map_frames[t] of them; pair_len: optional, 0 marks a target that takes reconstruct's
         length fit (dtw_align's lengths).  maps and pair_len are numpy arrays, or both device memory (torch CUDA
         tensors of a 32-bit integer type, DeviceFrames-style pointers): dtw_align_device's maps and lengths pass
-        straight in.  dtw engines only."""
+        straight in.  windows=(first, len), in samples, one per target: ssym_reconstruct_warped_spans -- sound idx[t] is
+        only its samples first[t] ... first[t] + len[t] - 1, and the map counts frames from the window's start (what
+        dtw_align(spans=) returns).  dtw engines only."""
         if self.metric != "dtw":
             raise nat.SsymError(nat.SSYM_E_UNSUPPORTED, "reconstruct_warped follows dtw alignments: a refcos engine has none")
         idx, off, m_off, frames, map_ptr, len_ptr, device, keep = _warp_inputs(idx, out_offsets, maps, map_offsets,
                                                                                map_frames, pair_len)
+        windows = _warp_windows(windows, idx.size)
         total = int(off[-1])
         out = np.zeros(total, dtype=np.float64)
         pcm = np.zeros(total, dtype=np.int32) if want_pcm32 else None
-        nat.check(nat.lib().ssym_reconstruct_warped(self.ctx, smp.ptr, idx.ctypes.data, off.ctypes.data, idx.size,
-                                                    map_ptr, m_off.ctypes.data, frames.ctypes.data, len_ptr,
-                                                    nat.WARP_MAP_DEVICE if device else 0, out.ctypes.data,
-                                                    pcm.ctypes.data if pcm is not None else None), self.ctx)
+        tail = (off.ctypes.data, idx.size, map_ptr, m_off.ctypes.data, frames.ctypes.data, len_ptr,
+                nat.WARP_MAP_DEVICE if device else 0, out.ctypes.data, pcm.ctypes.data if pcm is not None else None)
+        if windows is None:
+            rc = nat.lib().ssym_reconstruct_warped(self.ctx, smp.ptr, idx.ctypes.data, *tail)
+        else:
+            rc = nat.lib().ssym_reconstruct_warped_spans(self.ctx, smp.ptr, idx.ctypes.data, windows[0].ctypes.data,
+                                                         windows[1].ctypes.data, *tail)
+        nat.check(rc, self.ctx)
         del keep
         return (out, pcm) if want_pcm32 else out
 
     def reconstruct_wsola(self, smp, idx, out_offsets, maps, map_offsets, map_frames, pair_len=None, search: int = 0,
-                          want_pcm32: bool = False, want_pos: bool = False):
+                          want_pcm32: bool = False, want_pos: bool = False, windows=None):
         """ssym_reconstruct_wsola: reconstruct_warped with every source frame moved by up to `search` samples (0 ... 512)
         to where it continues the frame before it best (definition in include/soundsym_amd.h).  Arguments as
         reconstruct_warped.  Returns the samples, with want_pcm32 also their 32-bit conversion, with want_pos also the
         u64 sample start of every source frame, laid out by map_offsets (slots of targets without a path and slack
-        slots hold 2^64 - 1).  search = 0 gives reconstruct_warped's samples bit for bit.  dtw engines only."""
+        slots hold 2^64 - 1).  search = 0 gives reconstruct_warped's samples bit for bit.  windows as for
+        reconstruct_warped (ssym_reconstruct_wsola_spans): lags stay inside the window and the positions count from its
+        first sample.  dtw engines only."""
         if self.metric != "dtw":
             raise nat.SsymError(nat.SSYM_E_UNSUPPORTED, "reconstruct_wsola follows dtw alignments: a refcos engine has none")
         search = _wsola_search(search)
@@ -1263,12 +1311,16 @@ class Engine:
         out = np.zeros(total, dtype=np.float64)
         pcm = np.zeros(total, dtype=np.int32) if want_pcm32 else None
         pos = np.full(int(m_off[-1]), np.iinfo(np.uint64).max, dtype=np.uint64) if want_pos else None
-        nat.check(nat.lib().ssym_reconstruct_wsola(self.ctx, smp.ptr, idx.ctypes.data, off.ctypes.data, idx.size,
-                                                   map_ptr, m_off.ctypes.data, frames.ctypes.data, len_ptr, search,
-                                                   nat.WARP_MAP_DEVICE if device else 0,
-                                                   pos.ctypes.data if pos is not None and pos.size else None,
-                                                   out.ctypes.data, pcm.ctypes.data if pcm is not None else None),
-                  self.ctx)
+        windows = _warp_windows(windows, idx.size)
+        tail = (off.ctypes.data, idx.size, map_ptr, m_off.ctypes.data, frames.ctypes.data, len_ptr, search,
+                nat.WARP_MAP_DEVICE if device else 0, pos.ctypes.data if pos is not None and pos.size else None,
+                out.ctypes.data, pcm.ctypes.data if pcm is not None else None)
+        if windows is None:
+            rc = nat.lib().ssym_reconstruct_wsola(self.ctx, smp.ptr, idx.ctypes.data, *tail)
+        else:
+            rc = nat.lib().ssym_reconstruct_wsola_spans(self.ctx, smp.ptr, idx.ctypes.data, windows[0].ctypes.data,
+                                                        windows[1].ctypes.data, *tail)
+        nat.check(rc, self.ctx)
         del keep
         res = (out,) + ((pcm,) if want_pcm32 else ()) + ((pos,) if want_pos else ())
         return res if len(res) > 1 else out
