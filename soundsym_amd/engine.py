@@ -174,6 +174,36 @@ def _wsola_search(search) -> int:
     return int(search)
 
 
+def _warp_call(engine, name, smp, idx, out_offsets, maps, map_offsets, map_frames, pair_len, search, want_pcm32, want_pos,
+               windows):
+    """Engine.reconstruct_warped (search None) and reconstruct_wsola: the checks -- the metric, the search width, the inputs,
+    all before anything touches the context -- the output arrays and the call of ssym_<name> or, with windows, of
+    ssym_<name>_spans.  Returns (samples, pcm or None, positions or None)."""
+    if engine.metric != "dtw":
+        raise nat.SsymError(nat.SSYM_E_UNSUPPORTED, name + " follows dtw alignments: a refcos engine has none")
+    if search is not None:
+        search = _wsola_search(search)
+    idx, off, m_off, frames, map_ptr, len_ptr, device, keep = _warp_inputs(idx, out_offsets, maps, map_offsets,
+                                                                           map_frames, pair_len)
+    windows = _warp_windows(windows, idx.size)
+    total = int(off[-1])
+    out = np.zeros(total, dtype=np.float64)
+    pcm = np.zeros(total, dtype=np.int32) if want_pcm32 else None
+    pos = np.full(int(m_off[-1]), np.iinfo(np.uint64).max, dtype=np.uint64) if want_pos else None
+    flags = nat.WARP_MAP_DEVICE if device else 0
+    mid = (flags,) if search is None else (search, flags, pos.ctypes.data if pos is not None and pos.size else None)
+    args = (off.ctypes.data, idx.size, map_ptr, m_off.ctypes.data, frames.ctypes.data, len_ptr) + mid + (
+        out.ctypes.data, pcm.ctypes.data if pcm is not None else None)
+    if windows is None:
+        rc = getattr(nat.lib(), "ssym_" + name)(engine.ctx, smp.ptr, idx.ctypes.data, *args)
+    else:
+        rc = getattr(nat.lib(), "ssym_" + name + "_spans")(engine.ctx, smp.ptr, idx.ctypes.data, windows[0].ctypes.data,
+                                                          windows[1].ctypes.data, *args)
+    nat.check(rc, engine.ctx)
+    del keep
+    return out, pcm, pos
+
+
 class _Handle:
     def __init__(self, engine: "Engine", ptr: int, n: int, dim: int, kind: str):
         self.engine, self.ptr, self.n, self.dim, self.kind = engine, ptr, n, dim, kind
@@ -1274,23 +1304,8 @@ class Engine:
         straight in.  windows=(first, len), in samples, one per target: ssym_reconstruct_warped_spans -- sound idx[t] is
         only its samples first[t] ... first[t] + len[t] - 1, and the map counts frames from the window's start (what
         dtw_align(spans=) returns).  dtw engines only."""
-        if self.metric != "dtw":
-            raise nat.SsymError(nat.SSYM_E_UNSUPPORTED, "reconstruct_warped follows dtw alignments: a refcos engine has none")
-        idx, off, m_off, frames, map_ptr, len_ptr, device, keep = _warp_inputs(idx, out_offsets, maps, map_offsets,
-                                                                               map_frames, pair_len)
-        windows = _warp_windows(windows, idx.size)
-        total = int(off[-1])
-        out = np.zeros(total, dtype=np.float64)
-        pcm = np.zeros(total, dtype=np.int32) if want_pcm32 else None
-        tail = (off.ctypes.data, idx.size, map_ptr, m_off.ctypes.data, frames.ctypes.data, len_ptr,
-                nat.WARP_MAP_DEVICE if device else 0, out.ctypes.data, pcm.ctypes.data if pcm is not None else None)
-        if windows is None:
-            rc = nat.lib().ssym_reconstruct_warped(self.ctx, smp.ptr, idx.ctypes.data, *tail)
-        else:
-            rc = nat.lib().ssym_reconstruct_warped_spans(self.ctx, smp.ptr, idx.ctypes.data, windows[0].ctypes.data,
-                                                         windows[1].ctypes.data, *tail)
-        nat.check(rc, self.ctx)
-        del keep
+        out, pcm, _ = _warp_call(self, "reconstruct_warped", smp, idx, out_offsets, maps, map_offsets, map_frames, pair_len,
+                                 None, want_pcm32, False, windows)
         return (out, pcm) if want_pcm32 else out
 
     def reconstruct_wsola(self, smp, idx, out_offsets, maps, map_offsets, map_frames, pair_len=None, search: int = 0,
@@ -1302,26 +1317,8 @@ class Engine:
         slots hold 2^64 - 1).  search = 0 gives reconstruct_warped's samples bit for bit.  windows as for
         reconstruct_warped (ssym_reconstruct_wsola_spans): lags stay inside the window and the positions count from its
         first sample.  dtw engines only."""
-        if self.metric != "dtw":
-            raise nat.SsymError(nat.SSYM_E_UNSUPPORTED, "reconstruct_wsola follows dtw alignments: a refcos engine has none")
-        search = _wsola_search(search)
-        idx, off, m_off, frames, map_ptr, len_ptr, device, keep = _warp_inputs(idx, out_offsets, maps, map_offsets,
-                                                                               map_frames, pair_len)
-        total = int(off[-1])
-        out = np.zeros(total, dtype=np.float64)
-        pcm = np.zeros(total, dtype=np.int32) if want_pcm32 else None
-        pos = np.full(int(m_off[-1]), np.iinfo(np.uint64).max, dtype=np.uint64) if want_pos else None
-        windows = _warp_windows(windows, idx.size)
-        tail = (off.ctypes.data, idx.size, map_ptr, m_off.ctypes.data, frames.ctypes.data, len_ptr, search,
-                nat.WARP_MAP_DEVICE if device else 0, pos.ctypes.data if pos is not None and pos.size else None,
-                out.ctypes.data, pcm.ctypes.data if pcm is not None else None)
-        if windows is None:
-            rc = nat.lib().ssym_reconstruct_wsola(self.ctx, smp.ptr, idx.ctypes.data, *tail)
-        else:
-            rc = nat.lib().ssym_reconstruct_wsola_spans(self.ctx, smp.ptr, idx.ctypes.data, windows[0].ctypes.data,
-                                                        windows[1].ctypes.data, *tail)
-        nat.check(rc, self.ctx)
-        del keep
+        out, pcm, pos = _warp_call(self, "reconstruct_wsola", smp, idx, out_offsets, maps, map_offsets, map_frames, pair_len,
+                                   search, want_pcm32, want_pos, windows)
         res = (out,) + ((pcm,) if want_pcm32 else ()) + ((pos,) if want_pos else ())
         return res if len(res) > 1 else out
 

@@ -63,8 +63,13 @@ def test_header_states_the_semantics_and_the_kernels_are_the_existing_ones():
                           ("wsola.hip", ["wsola_search_kernel", "wsola_synth_kernel"])):
         src = _read("soundsym_amd", "csrc", path)
         assert re.findall(r"__global__[^\n]*void (\w+)\(", src) == kernels
-        for struct in re.findall(r"struct (?:AlignArgs|WarpArgs|WsolaArgs) \{.*?\n\};", src, re.S):
-            assert "span" not in struct.lower() and "win_" not in struct and "window table" not in struct
+    # (the two resynthesis files take their common arguments, WarpArgs, from warp_common.hpp, which holds no kernel)
+    src = "".join(_read("soundsym_amd", "csrc", path) for path in ("dtw_align.hip", "warp_common.hpp", "warp.hip", "wsola.hip"))
+    assert "__global__" not in _read("soundsym_amd", "csrc", "warp_common.hpp")
+    structs = re.findall(r"struct (AlignArgs|WarpArgs|WsolaArgs)( : WarpArgs)? \{(.*?)\n\};", src, re.S)
+    assert [(name, base) for name, base, _ in structs] == [("AlignArgs", ""), ("WarpArgs", ""), ("WsolaArgs", " : WarpArgs")]
+    for _, _, struct in structs:
+        assert "span" not in struct.lower() and "win_" not in struct and "window table" not in struct
 
 
 def test_null_context_is_refused_without_a_device(native_lib):

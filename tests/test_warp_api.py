@@ -46,6 +46,8 @@ def test_the_header_carries_the_definition():
                    "SSYM_WARP_MAP_DEVICE", "SSYM_OUT_DEVICE", "SSYM_E_EMPTY_DICT", "One synchronisation"):
         assert phrase in doc, phrase
     kernel = _read("soundsym_amd", "csrc", "warp.hip")
+    assert "warp_synth(" in kernel                                 # the kernel's text is the shared header's
+    kernel += _read("soundsym_amd", "csrc", "warp_common.hpp")
     assert "__dadd_rn" in kernel and "__dmul_rn" in kernel and "__ddiv_rn" in kernel and "atomicAdd" not in kernel
 
 

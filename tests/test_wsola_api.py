@@ -39,6 +39,8 @@ def test_the_header_carries_the_definition():
                    "One synchronisation", "bit for bit"):
         assert phrase in doc, phrase
     kernel = _read("soundsym_amd", "csrc", "wsola.hip")
+    assert "warp_synth(" in kernel                                 # the synthesis kernel's text is the shared header's
+    kernel += _read("soundsym_amd", "csrc", "warp_common.hpp")
     for word in ("__dadd_rn", "__dmul_rn", "__ddiv_rn", "__dsqrt_rn", "wsola_search_kernel", "wsola_synth_kernel"):
         assert word in kernel
     assert "atomic" not in kernel
