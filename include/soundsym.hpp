@@ -224,6 +224,11 @@ class SoundDictionary {
     {
         if (sounds.empty())
             throw EmptyDictionary();
+        if (targets.empty()) {   // n_targets = 0 succeeds and does nothing (soundsym_amd.h); no NULL of an empty vector reaches the library
+            if (costs)
+                costs->clear();
+            return {};
+        }
         std::vector<double> flat;
         std::vector<uint64_t> off;
         pack_features(targets, flat, off);
@@ -244,6 +249,8 @@ class SoundDictionary {
     {
         if (sounds.empty())
             throw EmptyDictionary();
+        if (targets.empty())
+            return {};
         std::vector<double> flat;
         std::vector<uint64_t> off;
         pack_features(targets, flat, off);
@@ -264,6 +271,8 @@ class SoundDictionary {
     {
         if (sounds.empty())
             throw EmptyDictionary();
+        if (targets.empty())
+            return {};
         std::vector<double> flat;
         std::vector<uint64_t> off;
         pack_features(targets, flat, off);
@@ -297,6 +306,8 @@ class SoundDictionary {
     {
         if (sounds.empty())
             throw EmptyDictionary();
+        if (targets.empty() && indices.empty())
+            return {};
         const uint32_t n = (uint32_t)targets.size();
         std::vector<double> flat;
         std::vector<uint64_t> off;
@@ -343,6 +354,8 @@ class SoundDictionary {
     {
         if (sounds.empty())
             throw EmptyDictionary();
+        if (targets.empty() && indices.empty())
+            return {};
         const uint32_t n = (uint32_t)targets.size();
         std::vector<double> flat;
         std::vector<uint64_t> off;
@@ -398,6 +411,8 @@ class SoundDictionary {
     {
         if (sounds.empty())
             throw EmptyDictionary();
+        if (targets.empty() && (!indices || indices->empty()))
+            return {};
         const uint32_t n = (uint32_t)targets.size();
         std::vector<double> flat;
         std::vector<uint64_t> off;
@@ -437,6 +452,8 @@ class SoundDictionary {
     {
         if (sounds.empty())
             throw EmptyDictionary();
+        if (targets.empty() && spots.empty())
+            return {};
         const uint32_t n = (uint32_t)targets.size();
         std::vector<double> flat;
         std::vector<uint64_t> off;
@@ -481,6 +498,8 @@ class SoundDictionary {
                                    uint32_t step = SSYM_STEP_SYMMETRIC) const
     {
         const std::vector<Alignment> al = align_spans(targets, spots, step);
+        if (targets.empty())
+            return {};
         const uint32_t n = (uint32_t)targets.size();
         std::vector<uint64_t> moff(n + 1, 0), ooff(n + 1, 0), soff(sounds.size() + 1, 0), wfirst(n, 0), wlen(n, 0);
         std::vector<uint32_t> map, frames(n), len(n), idx(n, 0);
