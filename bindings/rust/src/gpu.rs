@@ -173,6 +173,12 @@ extern "C" {
                                    index_base: u32, step: u32, out_idx: *mut u32, out_cost: *mut f64, flags: u32) -> i32;
     pub fn ssym_pair_matrix_step(ctx: *mut SsymCtx, dict: *const SsymDict, q: *const SsymQueries, step: u32,
                                  out_matrix: *mut f64) -> i32;
+    // the cover: every target tiled by dictionary segments, cut points and segments chosen together for the least total of
+    // paced costs (+ piece_penalty per piece); the four piece arrays hold one slot per target frame of the query set, target
+    // t's pieces from slot frame_offset[t] on, unused slots SSYM_NO_MATCH / +inf; segments of at most 128 frames
+    pub fn ssym_dtw_cover(ctx: *mut SsymCtx, dict: *const SsymDict, q: *const SsymQueries, piece_penalty: f64, flags: u32,
+                          out_count: *mut u32, out_total: *mut f64, out_src: *mut u32, out_start: *mut u32,
+                          out_end: *mut u32, out_cost: *mut f64) -> i32;
 
     // source-sharded runs, exchange done by the caller (device pointers): filter / all-reduce(MIN) / finish / merge
     pub fn ssym_match_begin(ctx: *mut SsymCtx, dict: *const SsymDict, q: *const SsymQueries, distance: *const f64,

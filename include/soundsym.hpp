@@ -444,6 +444,44 @@ class SoundDictionary {
                                              : Spot{idx[t], start[t], end[t], cost[t]};
         return out;
     }
+    // every target tiled by dictionary sounds, cut points and sounds chosen together so that the paced alignment costs of
+    // the pieces sum to the least total over every tiling (ssym_dtw_cover; soundsym_amd.h "Cover"; dtw contexts without a
+    // band; the crate has no counterpart).  A piece covers frames start_frame ... end_frame (inclusive) of the TARGET with
+    // sounds[source_index] at cost, a sum over the piece's frames; total includes piece_penalty per piece.  No cover (no
+    // frames, a NaN frame, a stretch no sound can pace): no pieces, total +inf
+    struct Cover {
+        std::vector<Spot> pieces;
+        double total;
+        bool empty() const { return pieces.empty(); }
+    };
+    std::vector<Cover> cover(const std::vector<ArcSound> &targets, double piece_penalty = 0.0) const
+    {
+        if (sounds.empty())
+            throw EmptyDictionary();
+        if (targets.empty())
+            return {};
+        const uint32_t n = (uint32_t)targets.size();
+        std::vector<double> flat;
+        std::vector<uint64_t> off;
+        pack_features(targets, flat, off);
+        ssym_queries *q = nullptr;
+        ctx_->check(ssym_queries_create(ctx_->get(), flat.data(), off.data(), n, (uint32_t)NCOEFFS, &q));
+        const size_t frames = (size_t)(off[n] - off[0]), room = frames ? frames : 1;      // (no NULL of an empty vector)
+        std::vector<uint32_t> count(n), src(room), start(room), end(room);
+        std::vector<double> total(n), cost(room);
+        const int32_t rc = ssym_dtw_cover(ctx_->get(), resident(), q, piece_penalty, 0, count.data(), total.data(), src.data(),
+                                          start.data(), end.data(), cost.data());
+        ssym_queries_destroy(ctx_->get(), q);
+        ctx_->check(rc);
+        std::vector<Cover> out(n);
+        for (uint32_t t = 0; t < n; ++t) {
+            out[t].total = total[t];
+            const size_t at = (size_t)(off[t] - off[0]);
+            for (uint32_t k = 0; k < count[t]; ++k)
+                out[t].pieces.push_back(Spot{src[at + k], start[at + k], end[at + k], cost[at + k]});
+        }
+        return out;
+    }
     // align with a Spot per target instead of an index: target t against frames start_frame ... end_frame of
     // sounds[source_index], where they lie in the resident dictionary (ssym_dtw_align_spans; soundsym_amd.h "Span
     // alignment").  path and frame_map count from the span's first frame; an empty Spot gives an empty Alignment

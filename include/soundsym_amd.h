@@ -508,6 +508,41 @@ SSYM_API int32_t ssym_match_queries_step(ssym_ctx *ctx, const ssym_dict *dict, c
 SSYM_API int32_t ssym_pair_matrix_step(ssym_ctx *ctx, const ssym_dict *dict, const ssym_queries *q, uint32_t step,
                                        double *out_matrix);
 
+/* Cover (DESIGN.md section 2 "Cover" and section 5.23): every target tiled by dictionary segments, the cut points and the
+ * segments chosen together so that the paced costs of the pieces sum to the least total over every tiling.  Under the paced
+ * pattern every tiling of a T-frame target has exactly T cells, so totals compare and total / T is a mean per frame.
+ * For one target X of T frames and sources n = 0 ... N-1 of Fa[n] frames, in the arithmetic of "Paced alignment" above:
+ *   w(n,s,L)  = cost(n, X[s ... s+L-1]) of "Paced matching": +inf where the shape rule says no, else E(Fa-1, L-1); a source of
+ *               Fa frames covers windows of ceil((Fa+1)/2) ... 2 Fa frames only
+ *   M(s,L)    = the first least w(n,s,L) over n ascending from (none, +inf), strict < (NaN and +inf never win) -> src(s,L)
+ *   best(-1)  = 0
+ *   best(e)   = scan L = 1 ... min(e+1, 2 Fmax) ascending from (none, +inf), strict <, over the L that have a src(e-L+1, L):
+ *               v = (M(e-L+1, L) + piece_penalty) + best(e-L)  -> the first least v, its (L, src, M)
+ *   cover     : walk back from e = T-1 while best is finite: piece (src, start = e-L+1, end = e, cost = M); e <- e-L
+ *   total     = best(T-1); count = pieces, reported in ascending start;  no cover (T = 0, best(T-1) not finite): count 0,
+ *               total +inf
+ * So the pieces tile [0, T); a piece's cost has the bits ssym_pair_matrix_step and ssym_dtw_align_step give under
+ * SSYM_STEP_PACED for (src, the cut X[start ... end]); acc = 0, acc = (cost_k + piece_penalty) + acc in piece order gives
+ * total's bits; total is the least such sum; on a tie the lower source index wins, then the shorter last piece.  A NaN or
+ * +-inf in a target frame: no cover.  A dictionary segment with a NaN frame is never chosen.  No read leaves its buffer.
+ *   piece_penalty  >= 0, finite: added per piece, trades total fit for fewer, longer pieces; 0 is the plain optimum
+ *   out_count, out_total   n_targets u32 / f64
+ *   out_src, out_start, out_end, out_cost   one slot per target frame of the whole query set; target t's pieces start at
+ *               slot frame_offset[t] (a cover never has more pieces than frames); unused slots hold (SSYM_NO_MATCH,
+ *               SSYM_NO_MATCH, SSYM_NO_MATCH, +inf).  start / end count frames inside the target.  Costs are sums.
+ *   flags       SSYM_OUT_DEVICE: the six outputs are device memory
+ * The targets of one call are independent covers.
+ * Limits: a dtw context without a band, dim <= 64, every dictionary segment of at most 128 frames (kCoverMaxSourceFrames),
+ * and scratch of frames x 2 Fmax x 12 + frames x 16 bytes <= 512 MiB (frames: the target frames of the call, Fmax: the
+ * longest dictionary segment; the M / src tables of one source block and the back-pointers).  Beyond them and on a refcos
+ * context: SSYM_E_UNSUPPORTED before any device work, with the outputs unwritten.  A NaN, negative or infinite
+ * piece_penalty: SSYM_E_INVALID.  An empty dictionary: SSYM_E_EMPTY_DICT.  n_targets = 0 succeeds and does nothing.  One
+ * synchronisation per call.  ssym_get_timings afterwards: main_ms = the forward pass (with its fold), reduce_ms = the chain,
+ * n_pairs = n_sources x the call's target frames. */
+SSYM_API int32_t ssym_dtw_cover(ssym_ctx *ctx, const ssym_dict *dict, const ssym_queries *q, double piece_penalty,
+                                uint32_t flags, uint32_t *out_count, double *out_total, uint32_t *out_src,
+                                uint32_t *out_start, uint32_t *out_end, double *out_cost);
+
 /* Source-sharded multi-GPU, dtw metric: the one real exchange the path has.  Each rank's filter gives,
  * per target, an upper bound on the best key in ITS shard; a rank whose shard does not hold a
  * target's neighbour would otherwise re-score ~10^2 of its own pairs per target for nothing.

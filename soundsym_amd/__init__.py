@@ -15,10 +15,12 @@ from .engine import DeviceFrames, Engine, Gmm, Spotter, Stream, pack_segments, s
 from .api import (  # noqa: F401
     Alignment,
     BIN,
+    Cover,
     HOP,
     NCLUSTERS,
     NCOEFFS,
     Partitioner,
+    Piece,
     Sound,
     SoundDictionary,
     SoundSequence,
@@ -36,8 +38,8 @@ from .api import (  # noqa: F401
 )
 
 __all__ = [
-    "ABI_SYMBOLS", "Alignment", "BIN", "DeviceFrames", "EmptyDictionaryError", "Engine", "Gmm", "HOP", "LIB_PATH", "NCLUSTERS", "NCOEFFS",
-    "Partitioner", "Sound", "SoundDictionary", "SoundSequence", "Spot", "SsymError", "analyze_mfccs", "analyze_sounds", "build",
+    "ABI_SYMBOLS", "Alignment", "BIN", "Cover", "DeviceFrames", "EmptyDictionaryError", "Engine", "Gmm", "HOP", "LIB_PATH", "NCLUSTERS", "NCOEFFS",
+    "Partitioner", "Piece", "Sound", "SoundDictionary", "SoundSequence", "Spot", "SsymError", "analyze_mfccs", "analyze_sounds", "build",
     "cosine_sim_angular", "discretize",
     "discretize_with_model", "length_fit", "pack_segments", "push_sounds", "Spotter", "Stream", "stream_plan", "train_model", "Watch", "watch",
 ]

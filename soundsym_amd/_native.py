@@ -63,6 +63,7 @@ ABI_SYMBOLS = [
     "ssym_dtw_spot_step", "ssym_spot_queries_step", "ssym_dtw_spot_all_step",
     "ssym_dtw_align_step",
     "ssym_match_queries_step", "ssym_pair_matrix_step",
+    "ssym_dtw_cover",
     "ssym_spotter_create_step",
     "ssym_reconstruct_warped", "ssym_reconstruct_wsola",
     "ssym_dtw_align_spans_sizes", "ssym_dtw_align_spans", "ssym_reconstruct_warped_spans", "ssym_reconstruct_wsola_spans",
@@ -259,6 +260,8 @@ def lib() -> ctypes.CDLL:
     L.ssym_match_queries_step.argtypes = [vp, vp, vp, vp, u32, u32, vp, vp, u32]
     L.ssym_pair_matrix_step.restype = i32
     L.ssym_pair_matrix_step.argtypes = [vp, vp, vp, u32, vp]
+    L.ssym_dtw_cover.restype = i32
+    L.ssym_dtw_cover.argtypes = [vp, vp, vp, f64, u32, vp, vp, vp, vp, vp, vp]
     L.ssym_dtw_align_step.restype = i32
     L.ssym_dtw_align_step.argtypes = [vp, vp, vp, vp, vp, u32, u32, u32, vp, vp, vp, vp, vp, vp, u32]
     L.ssym_dtw_spot.restype = i32

@@ -27,7 +27,7 @@ from typing import List, Optional, Sequence
 import numpy as np
 
 from ._native import NO_MATCH, SSYM_E_UNSUPPORTED, EmptyDictionaryError, SsymError
-from .engine import Engine, _wsola_search, pack_segments, pitch_lags
+from .engine import Engine, _cover_penalty, _wsola_search, pack_segments, pitch_lags
 
 NCOEFFS = 12   # src/lib.rs:22
 NCLUSTERS = 26 # src/lib.rs:23
@@ -452,6 +452,109 @@ class Spot:
             return "Spot(empty)"
         return "Spot(source_index=%d, frames=%d...%d, cost=%r)" % (self.source_index, self.start_frame, self.end_frame,
                                                                    self.cost)
+
+
+class Piece:
+    """One piece of a Cover: frames `start_frame` ... `end_frame` (INCLUSIVE) of the TARGET, covered by dictionary sound
+    `source_index` at `cost`, the paced alignment cost of (that sound, those frames) -- a sum over the piece's frames;
+    `cost_per_frame` is cost / num_frames(), a mean that compares across pieces."""
+
+    __slots__ = ("source_index", "start_frame", "end_frame", "cost")
+
+    def __init__(self, source_index: int, start_frame: int, end_frame: int, cost: float):
+        self.source_index, self.start_frame, self.end_frame = int(source_index), int(start_frame), int(end_frame)
+        self.cost = float(cost)
+        if self.source_index < 0 or not 0 <= self.start_frame <= self.end_frame:
+            raise ValueError("a piece spans start_frame ... end_frame with 0 <= start_frame <= end_frame and names a sound")
+
+    def num_frames(self) -> int:
+        return self.end_frame - self.start_frame + 1
+
+    @property
+    def cost_per_frame(self) -> float:
+        return self.cost / float(self.num_frames())
+
+    def sample_span(self, num_samples: int):
+        """(first sample, one past the last sample) of the piece in a target of num_samples samples, by Spot.sample_span's
+        rule: frame f starts at sample f * HOP, and the last frame ends where the next one would start, or with the sound."""
+        n = int(num_samples)
+        return (self.start_frame * HOP, min((self.end_frame + 1) * HOP, n))
+
+    def __repr__(self) -> str:
+        return "Piece(source_index=%d, frames=%d...%d, cost=%r)" % (self.source_index, self.start_frame, self.end_frame,
+                                                                    self.cost)
+
+
+class Cover:
+    """A target tiled by dictionary sounds (ssym_dtw_cover; definition in include/soundsym_amd.h and DESIGN.md section 2
+    "Cover"): `pieces` in ascending start, tiling frames 0 ... num_frames - 1 of the target, and `total`, the least sum of
+    (piece cost + piece_penalty) over every tiling and every choice of sounds.  Every paced path has one cell per target
+    frame, so `total_per_frame` = total / num_frames is a mean per frame.  A target without a cover (no frames, a NaN
+    frame, a stretch no dictionary sound can pace) gives an empty Cover: falsy, no pieces, total +inf."""
+
+    __slots__ = ("pieces", "total", "num_frames")
+
+    def __init__(self, pieces: Sequence["Piece"], total: float, num_frames: int):
+        self.pieces, self.total, self.num_frames = list(pieces), float(total), int(num_frames)
+        if self.num_frames < 0:
+            raise ValueError("a cover tiles num_frames >= 0 frames")
+        at = 0
+        for p in self.pieces:
+            if not isinstance(p, Piece) or p.start_frame != at:
+                raise ValueError("the pieces of a cover tile the target: each starts where the one before it ended")
+            at = p.end_frame + 1
+        if self.pieces and at != self.num_frames:
+            raise ValueError("the pieces of a cover tile the target: the last one ends with it")
+
+    @staticmethod
+    def none(num_frames: int = 0) -> "Cover":
+        return Cover([], float("inf"), num_frames)
+
+    def __len__(self) -> int:
+        return len(self.pieces)
+
+    def __bool__(self) -> bool:
+        return bool(self.pieces)
+
+    @property
+    def total_per_frame(self) -> float:
+        return self.total / float(self.num_frames) if self.pieces else float("inf")
+
+    def indices(self) -> np.ndarray:
+        """The dictionary sound of every piece, int64: what align and warp take as indices for the cut target."""
+        return np.array([p.source_index for p in self.pieces], dtype=np.int64)
+
+    def segment_lengths(self, num_samples: int) -> List[int]:
+        """The cut as lengths in samples, as Partitioner.partition returns them: num_frames() * HOP per piece, and the
+        last piece runs to the end of a sound of num_samples samples.  SoundDictionary.from_segments takes them as they
+        are.  An empty cover has no segments."""
+        n = int(num_samples)
+        if n < 0:
+            raise ValueError("num_samples must not be negative")
+        if not self.pieces:
+            return []
+        if self.pieces[-1].start_frame * HOP > n:
+            raise ValueError("the last piece starts beyond num_samples: the cover belongs to a longer sound")
+        return [p.num_frames() * HOP for p in self.pieces[:-1]] + [n - self.pieces[-1].start_frame * HOP]
+
+    def __repr__(self) -> str:
+        return "Cover(empty)" if not self.pieces else "Cover(%d pieces, total=%r)" % (len(self.pieces), self.total)
+
+
+def _cover_sounds(sound: "Sound", cover: "Cover") -> List["Sound"]:
+    """The target cut at the cover's pieces: samples by segment_lengths (Piece.sample_span, the last piece running to the
+    end of the sound), MFCC rows start_frame ... end_frame."""
+    if not isinstance(cover, Cover):
+        raise ValueError("a Cover is needed")
+    if cover and cover.num_frames != sound.num_frames():
+        raise ValueError("the cover tiles another number of frames than the sound has")
+    smp, rows = sound.samples(), sound.mfcc_arrays()
+    out, at = [], 0
+    for p, n in zip(cover.pieces, cover.segment_lengths(smp.size)):
+        out.append(Sound(smp[at:at + n].copy(), sound.sample_rate(), rows[p.start_frame:p.end_frame + 1].copy(), None,
+                         sound.ncoeffs))
+        at += n
+    return out
 
 
 class Watch:
@@ -885,6 +988,53 @@ class SoundDictionary:
             q.close()
         return (spots,) + (res if isinstance(res, tuple) else (res,))
 
+    def cover(self, targets: Sequence[Sound], piece_penalty: float = 0.0) -> List["Cover"]:
+        """Every target tiled by dictionary sounds, the cut points and the sounds chosen together on the GPU so that the
+        paced alignment costs of the pieces sum to the least total (ssym_dtw_cover, one call; dtw engines without a band):
+        a partition of the target that has seen the dictionary.  piece_penalty >= 0 is added per piece and trades total
+        fit for fewer, longer pieces; 0 is the plain optimum.  Every piece's cost is what align(step="paced") gives for
+        (its sound, its frames of the target).  A target without a cover gives an empty Cover."""
+        penalty = _cover_penalty(piece_penalty)
+        targets = list(targets)
+        if not self.sounds:
+            raise EmptyDictionaryError(-2, "empty dictionary")
+        if getattr(self.engine, "metric", None) != "dtw":
+            raise SsymError(SSYM_E_UNSUPPORTED, "cover aligns with dtw: a refcos engine has no alignment")
+        if not targets:
+            return []
+        flat, off = pack_segments([t.mfccs() for t in targets], self._dim(), self.engine.np_dtype)
+        q = self.engine.queries(flat, off, self._dim())
+        try:
+            count, total, src, start, end, cost = self.engine.dtw_cover(self.resident(), q, penalty)
+        finally:
+            q.close()
+        off = np.asarray(off, dtype=np.int64)
+        out = []
+        for t in range(len(targets)):
+            a, frames = int(off[t]), int(off[t + 1] - off[t])
+            if not count[t]:
+                out.append(Cover.none(frames))
+                continue
+            out.append(Cover([Piece(src[k], start[k], end[k], cost[k]) for k in range(a, a + int(count[t]))], total[t], frames))
+        return out
+
+    def reconstruct_covered(self, target: Sound, piece_penalty: float = 0.0, search: int = 0, want_pcm32: bool = False):
+        """cover, cut, warp: the target is covered (ssym_dtw_cover), cut at the pieces (samples by
+        Cover.segment_lengths, MFCC rows start_frame ... end_frame) and every piece warped from its sound under the paced
+        pattern -- self.warp(pieces, indices=cover.indices(), step="paced", search=search), the existing calls.  Returns
+        (cover, samples), with want_pcm32 (cover, samples, pcm); the samples are len(target.samples()).  A target without
+        a cover takes what SoundSequence([target]).reconstruct_from_dictionary gives it whole."""
+        penalty = _cover_penalty(piece_penalty)
+        search = _wsola_search(search)
+        if not isinstance(target, Sound):
+            raise ValueError("reconstruct_covered takes one Sound")
+        cover = self.cover([target], penalty)[0]
+        if not cover:
+            res = SoundSequence([target]).reconstruct_from_dictionary(self, want_pcm32)
+        else:
+            res = self.warp(_cover_sounds(target, cover), cover.indices(), want_pcm32, search, step="paced")
+        return (cover,) + (res if isinstance(res, tuple) else (res,))
+
     def spot(self, targets: Sequence[Sound], indices=None, step: str = "symmetric") -> List["Spot"]:
         """Where inside the dictionary's (unsegmented) recordings every target sounds: subsequence DTW on the GPU (dtw
         engines without a band).  indices=None: every recording is tried for every target and the best one kept, the
@@ -1083,6 +1233,13 @@ class SoundSequence:
         # every sound's features in one ssym_mfcc_batch (Sound.from_samples' framing, bit for bit)
         feats = analyze_mfccs([c[0] for c in cuts], rate, sound.ncoeffs, engine)
         return SoundSequence([Sound(c[0], rate, m, c[1], sound.ncoeffs) for c, m in zip(cuts, feats)])
+
+    @staticmethod
+    def from_cover(sound: Sound, cover: "Cover") -> "SoundSequence":
+        """The target as the sequence of its pieces: `sound` cut at the pieces of `cover` (SoundDictionary.cover), samples
+        by Cover.segment_lengths and MFCC rows start_frame ... end_frame, so that align, warp and clone_from_dictionary
+        take the pieces as they are.  An empty cover gives an empty sequence."""
+        return SoundSequence(_cover_sounds(sound, cover))
 
     @staticmethod
     def from_distances(distances: Sequence[float], start: Sound,

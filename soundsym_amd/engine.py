@@ -73,6 +73,14 @@ def _spot_step(step):
     raise ValueError('step must be "symmetric" or "paced"')
 
 
+def _cover_penalty(piece_penalty) -> float:
+    """piece_penalty of dtw_cover as a float, checked before the library is asked."""
+    penalty = float(piece_penalty)
+    if not 0.0 <= penalty < float("inf"):
+        raise ValueError("piece_penalty must be finite and not negative")
+    return penalty
+
+
 def _spot_all_args(src, max_spots, max_cost):
     """(K, per-pair thresholds as a contiguous f64 array or None) of dtw_spot_all, checked before the library is asked."""
     k = int(max_spots)
@@ -671,7 +679,9 @@ class Engine:
         rc = fn(self.ctx, fptr, off.ctypes.data, n, dim, ctypes.byref(out))
         del keep
         nat.check(rc, self.ctx)
-        return _Handle(self, out.value, n, dim, kind)
+        h = _Handle(self, out.value, n, dim, kind)
+        h.offsets = off - off[0] if n > 0 else np.zeros(1, dtype=np.uint64)      # frames before every segment
+        return h
 
     def dictionary(self, feats, offsets, dim: int) -> _Handle:
         return self._make("dict", feats, offsets, dim)
@@ -1030,6 +1040,26 @@ class Engine:
                                                   cost.ctypes.data, start.ctypes.data, end.ctypes.data, 0)
         nat.check(rc, self.ctx)
         return idx, cost, start, end
+
+    def dtw_cover(self, d: _Handle, q: _Handle, piece_penalty: float = 0.0, on_device: bool = False):
+        """ssym_dtw_cover (dtw engines without a band): every target tiled by dictionary segments, cut points and
+        segments chosen together so that the paced costs of the pieces sum to the least total over every tiling, by the
+        definition in include/soundsym_amd.h ("Cover").  piece_penalty >= 0 is added per piece.  Returns (count uint32
+        [m], total f64 [m], src uint32 [F], start uint32 [F], end uint32 [F], cost f64 [F]) with F the target frames of
+        the whole query set: target t's pieces lie in slots q.offsets[t] ... q.offsets[t] + count[t] - 1 in ascending
+        start, start / end count frames inside the target (end inclusive), unused slots hold NO_MATCH and +inf, a
+        target without a cover has count 0 and total +inf.  Costs are sums.  on_device: SSYM_OUT_DEVICE, the six arrays
+        as torch tensors in device memory (the 32-bit tensors hold the call's u32 values)."""
+        penalty = _cover_penalty(piece_penalty)
+        m, frames = q.n, int(q.offsets[-1])
+        device = self.device if on_device else None
+        (count, pn), (total, pt), (src, ps), (start, pa), (end, pe), (cost, pc) = (
+            _output(device, (rows,), t) for rows, t in ((m, np.uint32), (m, np.float64), (frames, np.uint32),
+                                                        (frames, np.uint32), (frames, np.uint32), (frames, np.float64)))
+        rc = nat.lib().ssym_dtw_cover(self.ctx, d.ptr, q.ptr, penalty, 0 if device is None else nat.OUT_DEVICE, pn, pt, ps,
+                                      pa, pe, pc)
+        nat.check(rc, self.ctx)
+        return count, total, src, start, end, cost
 
     # -- feature front-end (F3) --------------------------------------------------------------
     def mfcc(self, samples, sample_rate: float, ncoeffs: int = 12, f_lo: float = 100.0, f_hi: float = 8000.0,
