@@ -15,15 +15,23 @@
 // always come from the exact f64 kernel.
 #include "ssym_internal.hpp"
 #include "dtw_filter_kernel.hpp"
+#include "dtw_filter_wg_kernel.hpp"
 #include "dtw_filter_pk_kernel.hpp"
 #include "dtw_filter_sp_kernel.hpp"
 #include "dtw_band_kernel.hpp"
 
 #include <algorithm>
+#include <atomic>
 #include <cmath>
 #include <cstdlib>
 
 namespace ssym {
+
+// launches of dtw_filter_wg_kernel in this process (read by ssym_debug_filter_wg_launches below: the tests' proof of which
+// kernel ran)
+static std::atomic<unsigned long long> g_filter_wg_launches{0};
+// dtw_filter_wg_kernel on the launches that qualify (launch_one); SSYM_FILTER_WG=0|1 overrides under the test hooks
+constexpr bool kFilterWgDefault = true;
 
 int filter_pieces(int dim)
 {
@@ -363,6 +371,37 @@ static void launch_one(hipStream_t st, const SegmentSet &src, const SegmentSet &
             return;
         }
     }
+    if constexpr (NT == 4) {
+        // Equal-pass launches: one ring of target columns per workgroup (dtw_filter_wg_kernel.hpp), its four waves on four
+        // consecutive pairs of one target group.  Its barriers need every wave of a workgroup to run the same passes over
+        // the same columns: whole blocks of four pairs, none of them padding only (such a pair would start at the last
+        // pass), and pass 0 holding a row of the shortest pair -- pairs ascend by length, so of pair spBase.
+        // (SSYM_FILTER_WG, read per launch: the tests compare both settings; same bits, launches and cells either way.)
+        const char *wgKnob = ssym_knob("SSYM_FILTER_WG");
+        const bool wgOn = wgKnob ? atoi(wgKnob) != 0 : kFilterWgDefault;
+        const int nRealPairs = (int)((src.n + 1) / 2);
+        auto pairLen = [&](int sp) -> int {
+            auto len = [&](uint32_t p) -> uint32_t {
+                if (p >= src.n)
+                    return 0u;
+                const uint32_t s = src.h_perm[p];
+                return (uint32_t)(src.h_off[s + 1] - src.h_off[s]);
+            };
+            return (int)std::max(len(2u * sp), len(2u * sp + 1u));
+        };
+        if (wgOn && !abandon && !skipTile && nSrcPairs > 0 && nSrcPairs % 4 == 0 && spBase + nSrcPairs <= nRealPairs &&
+            src.n % 2 == 0 && rowOrigin + 16 * NT > (int)src.frames_pad - pairLen(spBase)) {
+            if (cellsOut)
+                *cellsOut += launch_cells(src, tgt, spBase, nSrcPairs, rowOrigin, 16 * NT, nPasses, 0, 0);
+            // (grid and chunk above count waves' tasks; a workgroup's task is four of them, so both stay what they were)
+            dtw_filter_wg_kernel<SQ, KU><<<dim3(grid), 64 * kFilterWavesPerBlock, 0, st>>>(
+                (const _Float16 *)src.rec, (const _Float16 *)tgt.rec, src.len, tgt.len, (int)src.frames_pad, nPasses,
+                (int)tgt.frames_pad, (int)tgt.n_pad, nSrcPairs / 4, taskChunk, outScale, handoff, taskCtr, cmat,
+                rowOrigin, spBase);
+            g_filter_wg_launches.fetch_add(1, std::memory_order_relaxed);
+            return;
+        }
+    }
     if (cellsOut && !abandon)
         *cellsOut += launch_cells(src, tgt, spBase, nSrcPairs, rowOrigin, 16 * NT, nPasses, 0, 0);
     if (abandon)
@@ -674,6 +713,12 @@ int32_t launch_dtw_filter(ssym_ctx *ctx, const SegmentSet &src, const SegmentSet
 }
 
 }  // namespace ssym
+
+// tests and tools: launches of dtw_filter_wg_kernel in this process so far
+extern "C" __attribute__((visibility("default"))) unsigned long long ssym_debug_filter_wg_launches(void)
+{
+    return ssym::g_filter_wg_launches.load(std::memory_order_relaxed);
+}
 
 #ifdef SSYM_SP_PROF
 // tools only: read and clear the single-pass kernel's tick sums (dtw_filter_sp_kernel.hpp)
