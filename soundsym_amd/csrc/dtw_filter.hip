@@ -4,8 +4,8 @@
 // (SoundDictionary::at_distance, src/sound.rs:352-359, called once per target by
 // clone_from_dictionary, src/sound.rs:453-454) for the dtw metric.  Output is the f32 cost of every
 // (source, target) pair; select.hip picks candidates from it and dtw_exact.hip re-scores them.
-// The kernel itself is in dtw_filter_kernel.hpp; this file builds its operand records and
-// dispatches the (tiles per wave, row blocks) instantiation for the dictionary's longest segment.
+// The kernels are in dtw_filter_kernel.hpp and its siblings; this file builds their operand records and runs the launches
+// that plan_filter (dtw_filter_plan.hpp) plans from the segment lengths.
 //
 // Numerics: operands are scaled by a common power of two s so that max |s v| < 64 and split into f16
 // pieces (three record layouts, filter_pieces() in ssym_internal.hpp: up to 13 values per frame the
@@ -27,11 +27,9 @@
 
 namespace ssym {
 
-// launches of dtw_filter_wg_kernel in this process (read by ssym_debug_filter_wg_launches below: the tests' proof of which
-// kernel ran)
+// launches of dtw_filter_wg_kernel in this process (run_kernel; read by ssym_debug_filter_wg_launches below: the tests'
+// proof of which kernel ran)
 static std::atomic<unsigned long long> g_filter_wg_launches{0};
-// dtw_filter_wg_kernel on the launches that qualify (launch_one); SSYM_FILTER_WG=0|1 overrides under the test hooks
-constexpr bool kFilterWgDefault = true;
 
 int filter_pieces(int dim)
 {
@@ -229,191 +227,149 @@ static int32_t ensure_records(ssym_ctx *ctx, const SegmentSet &set, double scale
     return SSYM_OK;
 }
 
-// DP cells per lane (64 pairs of a task share them) a launch of the unbanded filter evaluates, padding included: per
-// source pair the rows of the passes it runs (dtw_filter_kernel skips leading passes that hold only padding;
-// dtw_filter_sp_kernel skips leading row blocks of `rowBlock` rows), per target group the columns of its longest member
-// (at least `minCols`).  Rows depend on the pair only and columns on the group only, so the sum is a product.
-static unsigned long long launch_cells(const SegmentSet &src, const SegmentSet &tgt, int spBase, int nSrcPairs,
-                                       int rowOrigin, int passRows, int nPasses, int rowBlock, int minCols, int pairsPerTask = 1,
-                                       bool skipTile = false)
+// The unbanded launcher's knobs (FilterKnobs, dtw_filter_plan.hpp), read once per filter call -- the only place that names
+// them.  Without the test hooks (one lookup) the product's defaults.
+static FilterKnobs read_filter_knobs()
 {
-    auto len = [](const SegmentSet &set, uint32_t slot) -> uint32_t {
-        if (slot >= set.n)
-            return 0u;
-        const uint32_t s = set.h_perm[slot];
-        return (uint32_t)(set.h_off[s + 1] - set.h_off[s]);
+    FilterKnobs k;
+    if (!ssym_knob("SSYM_TEST_HOOKS"))
+        return k;
+    auto num = [](const char *name, int unset) {
+        const char *v = ssym_knob(name);
+        return v ? atoi(v) : unset;
     };
-    unsigned long long rows = 0, cols = 0;
-    for (uint32_t g = 0; g < tgt.n_pad / 32; ++g) {
-        uint32_t m = 0;
-        for (uint32_t t = 0; t < 32; ++t)
-            m = std::max(m, len(tgt, 32 * g + t));
-        cols += rowBlock ? std::max<uint32_t>(m, (uint32_t)minCols) : m;
-    }
-    for (int sp = spBase; sp < spBase + nSrcPairs; ++sp) {
-        int longer = (int)std::max(len(src, 2u * sp), len(src, 2u * sp + 1u));
-        if (pairsPerTask > 1) {                  // multi-pair tasks: every pair of a task starts at the task's first row block
-            const int first = spBase + (sp - spBase) / pairsPerTask * pairsPerTask;
-            for (int k = first; k < std::min(first + pairsPerTask, spBase + nSrcPairs); ++k)
-                longer = std::max(longer, (int)std::max(len(src, 2u * k), len(src, 2u * k + 1u)));
-        }
-        const int r0min = (int)src.frames_pad - longer;
-        if (rowBlock) {
-            const int sk = std::min(std::max(r0min - rowOrigin, 0), 15) / rowBlock;
-            rows += (unsigned long long)(passRows - sk * rowBlock);
-        } else {
-            const int firstPass = std::min(std::max(r0min - rowOrigin, 0) / passRows, nPasses - 1);
-            rows += (unsigned long long)(nPasses - firstPass) * passRows;
-            if (skipTile && r0min - (rowOrigin + firstPass * passRows) >= 17)      // SKIP0: the first pass's empty first tile
-                rows -= 16;
-        }
-    }
-    return rows * cols;
+    k.pk = num("SSYM_FILTER_PK", 0) != 0;
+    k.sp = num("SSYM_FILTER_SP", 1) != 0;
+    const int mp = num("SSYM_SP_MULTIPAIR", 1);
+    k.spMultipair = mp == 0 || mp == 2 ? mp : 1;
+    k.spPairBlock = ssym_knob("SSYM_SP_PAIRBLOCK") ? std::max(num("SSYM_SP_PAIRBLOCK", 0), 0) : -1;
+    k.wg = num("SSYM_FILTER_WG", k.wg) != 0;
+    k.skip0 = num("SSYM_FILTER_SKIP0", 1) != 0;
+    k.nt8 = ssym_knob("SSYM_FILTER_NT8") != nullptr;
+    k.oneLaunch = ssym_knob("SSYM_FILTER_ONE_LAUNCH") != nullptr;
+    k.longClasses = num("SSYM_FILTER_LONG_CLASSES", 1) != 0;
+    k.pruneNt = num("SSYM_PRUNE_NT", 0);
+    return k;
 }
 
-template <int NT, bool SQ, int KU>
-static void launch_one(hipStream_t st, const SegmentSet &src, const SegmentSet &tgt, int nPasses,
-                       int gridBlocks, float outScale, float *handoff, unsigned *taskCtr, float *cmat,
-                       const float *abandon, unsigned long long *colCtr, const uint32_t *candSlot,
-                       int spBase, int nSrcPairs, int rowOrigin, unsigned long long *cellsOut, bool skipTile = false)
+// The plan's view of a set: the frames of the longest member of every `group` consecutive record slots -- source pairs (2),
+// target groups (32); slots [0, n) are real, ascending by length, the rest padding.  Built on a set's first filter call
+// (pack drops it): a search of 4096 x 4096 short segments is 1.6 ms, walking both sets' offsets 10 us of host time in
+// front of its first launch.
+static const std::vector<uint32_t> &plan_lens(const SegmentSet &set, uint32_t group)
 {
-    // sources of at most 16 frames (one tile, one pass): three waves per SIMD, see filter_ring() -- 11 %
-    // faster there; at 32 frames the gain was within 3 % and cost spills
-    // NT == 8 (experiment, SSYM_FILTER_NT8=1): the whole 128-row column of a pair in ONE wave's registers, one wave per
-    // SIMD with the whole register file -- no second pass, no hand-off rows
+    if (set.plan_lens.size() != set.n_pad / group) {       // (not built yet, or built for the set in the other role)
+        set.plan_lens.assign(set.n_pad / group, 0u);
+        for (uint32_t slot = 0; slot < set.n; ++slot) {
+            const uint32_t s = set.h_perm[slot];
+            uint32_t &m = set.plan_lens[slot / group];
+            m = std::max(m, (uint32_t)(set.h_off[s + 1] - set.h_off[s]));
+        }
+    }
+    return set.plan_lens;
+}
+
+// what every launch of one filter call shares
+struct FilterCall {
+    hipStream_t st;
+    const SegmentSet &src, &tgt;
+    bool sq;                        // squared local costs
+    int ku;                         // operand planes
+    float outScale;
+    float *handoff;
+    unsigned *taskCtr;              // kMaxClasses sets of 8 counters
+    float *cmat;
+    const float *abandon;
+    unsigned long long *colCtr;
+    const uint32_t *candSlot;
+};
+
+// One entry of the plan as the kernel launch it names: the instantiations of (tiles per pass, cost, operand planes).
+// false: the plan names a kernel these parameters have none of.
+template <int NT, bool SQ, int KU>
+static bool run_kernel(const FilterCall &c, const FilterLaunch &l)
+{
     constexpr int OCC = NT == 1 ? 3 : NT == 8 ? 1 : 2;
-    gridBlocks = gridBlocks / 2 * OCC;
-    const int nTgtGroups = (int)tgt.n_pad / 32;
-    const int nTasks = nSrcPairs * nTgtGroups;            // one wave's 64 pairs each
-    const int blocksWanted = (nTasks + kFilterWavesPerBlock - 1) / kFilterWavesPerBlock;
-    const int grid = std::min(gridBlocks, (blocksWanted + 7) / 8 * 8);
-    // tasks per grab: several SHORT tasks at a time so that the L2 atomics stay invisible (at 16 frames a
-    // task is ~1 us of work), one at a time once a task is long enough to matter for the tail; always
-    // at least 16 grabs per wave
-    // (a task's size by the MEAN target length, not the longest: a ragged set's typical task is what the grab amortises)
-    const long meanTgt = tgt.n ? (long)((tgt.total_frames + tgt.n - 1) / tgt.n) : 1;
-    const long cellsPerTask = (long)(16 * NT * nPasses) * std::max<long>(meanTgt, 1);
-    int taskChunk = (int)std::max(1L, std::min(8L, 8192 / std::max(1L, cellsPerTask)));
-    taskChunk = std::max(1, std::min(taskChunk, nTasks / (grid * kFilterWavesPerBlock * 16)));
-    // SSYM_FILTER_PK=1 (experiment, off in the product: +1...1.5 % measured): 64-row passes without early
-    // abandoning on the two-block kernel whose additions are packed (dtw_filter_pk_kernel.hpp)
-    static const bool pkOn = ssym_knob("SSYM_FILTER_PK") && atoi(ssym_knob("SSYM_FILTER_PK")) != 0;
-    if (NT == 4 && !abandon && pkOn) {
-        dtw_filter_pk_kernel<SQ, KU><<<dim3(grid), 64 * kFilterWavesPerBlock, 0, st>>>(
-            (const _Float16 *)src.rec, (const _Float16 *)tgt.rec, src.len, tgt.len, (int)src.frames_pad, nPasses,
-            (int)tgt.frames_pad, (int)tgt.n_pad, nSrcPairs, nTasks, taskChunk, outScale, handoff, taskCtr, cmat,
-            rowOrigin, spBase);
-        return;
-    }
-    // single-pass launches without early abandoning: the kernel that pipelines across tasks and skips padding rows
-    // (dtw_filter_sp_kernel.hpp; SSYM_FILTER_SP=0 keeps dtw_filter_kernel for A/B measurements, same bits either way)
-    static const bool spOn = !(ssym_knob("SSYM_FILTER_SP") && atoi(ssym_knob("SSYM_FILTER_SP")) == 0);
-    // (with three operand planes its LDS -- ring and staging block -- admits two workgroups per CU up to two tiles)
-    // sources of at most 16 frames: three source pairs per wave (two with three operand planes: LDS), dtw_filter_sp_kernel MP
-    // (SSYM_SP_MULTIPAIR, read per launch: 0 = never, 2 = whatever the size -- the tests' way to small multi-pair launches)
-    const char *mpKnob = ssym_knob("SSYM_SP_MULTIPAIR");
-    const bool mpOn = !(mpKnob && atoi(mpKnob) == 0), mpAlways = mpKnob && atoi(mpKnob) == 2;
-    if constexpr (NT == 1) {
-        // (... when the multi-pair tasks still give every wave slot of the chip one: a 284 x 55 search is 96 of them, each
-        //  sweeping its group's longest target three pairs wide while nine tenths of the SIMDs idle -- one pair per wave there)
-        constexpr int MPN = KU == 2 ? 3 : 2;
-        const long mpTasksWanted = (long)((nSrcPairs + MPN - 1) / MPN) * nTgtGroups;
-        if (!abandon && nPasses == 1 && spOn && mpOn && (mpAlways || mpTasksWanted >= (long)gridBlocks / OCC * 2 * kFilterWavesPerBlock)) {
-            const int taskPairs = (nSrcPairs + MPN - 1) / MPN;
-            const int mpTasks = taskPairs * nTgtGroups;
-            const int gridMp = std::min(gridBlocks / OCC * 2, ((mpTasks + kFilterWavesPerBlock - 1) / kFilterWavesPerBlock + 7) / 8 * 8);
-            const long cellsMp = (long)(16 * MPN) * std::max<long>(meanTgt, 1);
-            int chunkMp = (int)std::max(1L, std::min(8L, 8192 / std::max(1L, cellsMp)));
-            chunkMp = std::max(1, std::min(chunkMp, mpTasks / std::max(1, gridMp * kFilterWavesPerBlock * 16)));
-            static const char *pbKnob = ssym_knob("SSYM_SP_PAIRBLOCK");
-            int pairBlock = std::max(16, (1 << 20) / (MPN * 2 * 16 * kFilterRecHalfs * 2));
-            if (pbKnob)
-                pairBlock = atoi(pbKnob) > 0 ? atoi(pbKnob) : taskPairs;
-            dtw_filter_sp_kernel<MPN, SQ, 2, KU, kSpRowBlock, true><<<dim3(gridMp), 64 * kFilterWavesPerBlock, 0, st>>>(
-                (const _Float16 *)src.rec, (const _Float16 *)tgt.rec, src.len, tgt.len, (int)src.frames_pad,
-                (int)tgt.frames_pad, (int)tgt.n_pad, taskPairs, nSrcPairs, chunkMp, outScale, taskCtr, cmat, rowOrigin, spBase,
-                std::min(pairBlock, std::max(taskPairs, 1)));
-            if (cellsOut)
-                *cellsOut += launch_cells(src, tgt, spBase, nSrcPairs, rowOrigin, 16, 1, kSpRowBlock, kSpRing, MPN);
-            return;
+    const dim3 grid(l.grid), block(64 * kFilterWavesPerBlock);
+    const _Float16 *srec = (const _Float16 *)c.src.rec, *trec = (const _Float16 *)c.tgt.rec;
+    const int rowsPad = (int)c.src.frames_pad, colsPad = (int)c.tgt.frames_pad, tgtPad = (int)c.tgt.n_pad;
+    const int nSrcPairs = l.hi - l.lo, nTasks = nSrcPairs * (tgtPad / 32);
+    unsigned *ctr = c.taskCtr + l.ctrSet * 8 * kTaskCtrStride;
+    switch (l.kind) {
+    case FilterKernel::Mp:
+        if constexpr (NT == 1) {
+            dtw_filter_sp_kernel<KU == 2 ? 3 : 2, SQ, 2, KU, kSpRowBlock, true><<<grid, block, 0, c.st>>>(
+                srec, trec, c.src.len, c.tgt.len, rowsPad, colsPad, tgtPad, l.taskPairs, nSrcPairs, l.taskChunk, c.outScale,
+                ctr, c.cmat, l.origin, l.lo, l.pairBlock);
+            return true;
         }
-    }
-    if constexpr (NT <= 3 && (KU == 2 || NT <= 2)) {
-        if (!abandon && nPasses == 1 && spOn) {
-#ifndef SSYM_SP_OCC_NT2
-#define SSYM_SP_OCC_NT2 3        // two-tile tasks at three waves per SIMD (162 registers since the loop copies own their operand registers); 2: tools
-#endif
+        return false;
+    case FilterKernel::Sp:
+        if constexpr (NT <= 3 && (KU == 2 || NT <= 2)) {
             constexpr int OCCSP = (NT == 1 && KU == 2) ? 3 : (NT == 2 && KU == 2) ? SSYM_SP_OCC_NT2 : 2;
-            const int gridSp = std::min(gridBlocks / OCC * OCCSP, (blocksWanted + 7) / 8 * 8);
-            // source pairs per block of the task order: about 1 MB of their records (an XCD's L2 holds 4 MB: the block, the
-            // XCD's target groups, the cost rows being written); SSYM_SP_PAIRBLOCK overrides (0: one block, the old order)
-            static const char *pbKnob = ssym_knob("SSYM_SP_PAIRBLOCK");
-            int pairBlock = std::max(16, (1 << 20) / (2 * 16 * NT * kFilterRecHalfs * 2));
-            if (pbKnob)
-                pairBlock = atoi(pbKnob) > 0 ? atoi(pbKnob) : nSrcPairs;
-            dtw_filter_sp_kernel<NT, SQ, OCCSP, KU, kSpRowBlock><<<dim3(gridSp), 64 * kFilterWavesPerBlock, 0, st>>>(
-                (const _Float16 *)src.rec, (const _Float16 *)tgt.rec, src.len, tgt.len, (int)src.frames_pad,
-                (int)tgt.frames_pad, (int)tgt.n_pad, nSrcPairs, nTasks, taskChunk, outScale, taskCtr, cmat, rowOrigin, spBase,
-                std::min(pairBlock, std::max(nSrcPairs, 1)));
-            if (cellsOut)
-                *cellsOut += launch_cells(src, tgt, spBase, nSrcPairs, rowOrigin, 16 * NT, 1, kSpRowBlock, kSpRing);
-            return;
+            dtw_filter_sp_kernel<NT, SQ, OCCSP, KU, kSpRowBlock><<<grid, block, 0, c.st>>>(
+                srec, trec, c.src.len, c.tgt.len, rowsPad, colsPad, tgtPad, nSrcPairs, nTasks, l.taskChunk, c.outScale, ctr,
+                c.cmat, l.origin, l.lo, l.pairBlock);
+            return true;
         }
-    }
-    if constexpr (NT == 3 || NT == 4) {
-        if (skipTile && !abandon) {       // a class whose shorter sources leave the first tile of their first pass empty
-            if (cellsOut)
-                *cellsOut += launch_cells(src, tgt, spBase, nSrcPairs, rowOrigin, 16 * NT, nPasses, 0, 0, 1, true);
-            dtw_filter_kernel<NT, SQ, OCC, false, KU, true><<<dim3(grid), 64 * kFilterWavesPerBlock, 0, st>>>(
-                (const _Float16 *)src.rec, (const _Float16 *)tgt.rec, src.len, tgt.len, (int)src.frames_pad, nPasses,
-                (int)tgt.frames_pad, (int)tgt.n_pad, nSrcPairs, nTasks, taskChunk, outScale, handoff, taskCtr, cmat,
-                nullptr, nullptr, nullptr, rowOrigin, spBase);
-            return;
+        return false;
+    case FilterKernel::GenericSkip0:
+        if constexpr (NT == 3 || NT == 4) {
+            dtw_filter_kernel<NT, SQ, OCC, false, KU, true><<<grid, block, 0, c.st>>>(
+                srec, trec, c.src.len, c.tgt.len, rowsPad, l.passes, colsPad, tgtPad, nSrcPairs, nTasks, l.taskChunk,
+                c.outScale, c.handoff, ctr, c.cmat, nullptr, nullptr, nullptr, l.origin, l.lo);
+            return true;
         }
-    }
-    if constexpr (NT == 4) {
-        // Equal-pass launches: one ring of target columns per workgroup (dtw_filter_wg_kernel.hpp), its four waves on four
-        // consecutive pairs of one target group.  Its barriers need every wave of a workgroup to run the same passes over
-        // the same columns: whole blocks of four pairs, none of them padding only (such a pair would start at the last
-        // pass), and pass 0 holding a row of the shortest pair -- pairs ascend by length, so of pair spBase.
-        // (SSYM_FILTER_WG, read per launch: the tests compare both settings; same bits, launches and cells either way.)
-        const char *wgKnob = ssym_knob("SSYM_FILTER_WG");
-        const bool wgOn = wgKnob ? atoi(wgKnob) != 0 : kFilterWgDefault;
-        const int nRealPairs = (int)((src.n + 1) / 2);
-        auto pairLen = [&](int sp) -> int {
-            auto len = [&](uint32_t p) -> uint32_t {
-                if (p >= src.n)
-                    return 0u;
-                const uint32_t s = src.h_perm[p];
-                return (uint32_t)(src.h_off[s + 1] - src.h_off[s]);
-            };
-            return (int)std::max(len(2u * sp), len(2u * sp + 1u));
-        };
-        if (wgOn && !abandon && !skipTile && nSrcPairs > 0 && nSrcPairs % 4 == 0 && spBase + nSrcPairs <= nRealPairs &&
-            src.n % 2 == 0 && rowOrigin + 16 * NT > (int)src.frames_pad - pairLen(spBase)) {
-            if (cellsOut)
-                *cellsOut += launch_cells(src, tgt, spBase, nSrcPairs, rowOrigin, 16 * NT, nPasses, 0, 0);
-            // (grid and chunk above count waves' tasks; a workgroup's task is four of them, so both stay what they were)
-            dtw_filter_wg_kernel<SQ, KU><<<dim3(grid), 64 * kFilterWavesPerBlock, 0, st>>>(
-                (const _Float16 *)src.rec, (const _Float16 *)tgt.rec, src.len, tgt.len, (int)src.frames_pad, nPasses,
-                (int)tgt.frames_pad, (int)tgt.n_pad, nSrcPairs / 4, taskChunk, outScale, handoff, taskCtr, cmat,
-                rowOrigin, spBase);
+        return false;
+    case FilterKernel::Wg:
+        if constexpr (NT == 4) {
+            dtw_filter_wg_kernel<SQ, KU><<<grid, block, 0, c.st>>>(
+                srec, trec, c.src.len, c.tgt.len, rowsPad, l.passes, colsPad, tgtPad, nSrcPairs / 4, l.taskChunk, c.outScale,
+                c.handoff, ctr, c.cmat, l.origin, l.lo);
             g_filter_wg_launches.fetch_add(1, std::memory_order_relaxed);
-            return;
+            return true;
         }
+        return false;
+    case FilterKernel::Pk:
+        if constexpr (NT == 4) {
+            dtw_filter_pk_kernel<SQ, KU><<<grid, block, 0, c.st>>>(
+                srec, trec, c.src.len, c.tgt.len, rowsPad, l.passes, colsPad, tgtPad, nSrcPairs, nTasks, l.taskChunk,
+                c.outScale, c.handoff, ctr, c.cmat, l.origin, l.lo);
+            return true;
+        }
+        return false;
+    case FilterKernel::GenericPrune:
+        dtw_filter_kernel<NT, SQ, OCC, true, KU><<<grid, block, 0, c.st>>>(
+            srec, trec, c.src.len, c.tgt.len, rowsPad, l.passes, colsPad, tgtPad, nSrcPairs, nTasks, l.taskChunk, c.outScale,
+            c.handoff, ctr, c.cmat, c.abandon, c.colCtr, c.candSlot, l.origin, l.lo);
+        return true;
+    case FilterKernel::Generic:
+        dtw_filter_kernel<NT, SQ, OCC, false, KU><<<grid, block, 0, c.st>>>(
+            srec, trec, c.src.len, c.tgt.len, rowsPad, l.passes, colsPad, tgtPad, nSrcPairs, nTasks, l.taskChunk, c.outScale,
+            c.handoff, ctr, c.cmat, nullptr, nullptr, nullptr, l.origin, l.lo);
+        return true;
     }
-    if (cellsOut && !abandon)
-        *cellsOut += launch_cells(src, tgt, spBase, nSrcPairs, rowOrigin, 16 * NT, nPasses, 0, 0);
-    if (abandon)
-        dtw_filter_kernel<NT, SQ, OCC, true, KU><<<dim3(grid), 64 * kFilterWavesPerBlock, 0, st>>>(
-            (const _Float16 *)src.rec, (const _Float16 *)tgt.rec, src.len, tgt.len, (int)src.frames_pad, nPasses,
-            (int)tgt.frames_pad, (int)tgt.n_pad, nSrcPairs, nTasks, taskChunk, outScale, handoff, taskCtr, cmat,
-            abandon, colCtr, candSlot, rowOrigin, spBase);
-    else
-        dtw_filter_kernel<NT, SQ, OCC, false, KU><<<dim3(grid), 64 * kFilterWavesPerBlock, 0, st>>>(
-            (const _Float16 *)src.rec, (const _Float16 *)tgt.rec, src.len, tgt.len, (int)src.frames_pad, nPasses,
-            (int)tgt.frames_pad, (int)tgt.n_pad, nSrcPairs, nTasks, taskChunk, outScale, handoff, taskCtr, cmat,
-            nullptr, nullptr, nullptr, rowOrigin, spBase);
+    return false;
+}
+
+template <int NT>
+static bool run_tiles(const FilterCall &c, const FilterLaunch &l)
+{
+    if (c.sq)
+        return c.ku == 2 ? run_kernel<NT, true, 2>(c, l) : run_kernel<NT, true, 3>(c, l);
+    return c.ku == 2 ? run_kernel<NT, false, 2>(c, l) : run_kernel<NT, false, 3>(c, l);
+}
+
+static bool run_launch(const FilterCall &c, const FilterLaunch &l)
+{
+    switch (l.nt) {
+    case 1: return run_tiles<1>(c, l);
+    case 2: return run_tiles<2>(c, l);
+    case 3: return run_tiles<3>(c, l);
+    case 4: return run_tiles<4>(c, l);
+    case 8: return run_tiles<8>(c, l);      // SSYM_FILTER_NT8
+    }
+    return false;
 }
 
 template <int NTB, int WB, int OCC, bool SQ, int LASTN, bool PRUNE>
@@ -530,7 +486,7 @@ int32_t launch_dtw_filter(ssym_ctx *ctx, const SegmentSet &src, const SegmentSet
     ctx->filter_launches = 1;
     if (ctx->band >= 0 && !filter_band_as_bound(ctx, src, tgt))
         return launch_dtw_filter_banded(ctx, src, tgt, cmat, abandon, colCtr, candSlot);
-    FilterShape shape = filter_shape((int)src.max_frames);
+    const FilterShape shape = filter_shape((int)src.max_frames);
     if (shape.nt == 0 || (int)src.frames_pad != shape.rows() || src.n_pad % 8 != 0 || tgt.n_pad % 32 != 0) {
         ctx->err = "dtw filter: segment set not padded for the filter kernel";
         return SSYM_E_UNSUPPORTED;
@@ -540,18 +496,6 @@ int32_t launch_dtw_filter(ssym_ctx *ctx, const SegmentSet &src, const SegmentSet
         ctx->err = "dtw filter: targets too long for the hand-off rows";
         return SSYM_E_UNSUPPORTED;
     }
-    // Early abandoning: the work of a pruned task is about the area where D <= threshold, counted in whole
-    // row passes x columns, so lower passes waste less: with 32-row passes the headline grid takes 3.1 ms
-    // instead of 4.6.  But a task that cannot be cut short pays two more hand-offs per 128 rows (+17 % on
-    // data without close pairs).  Results do not depend on the pass height, so it follows the data: 32 rows
-    // when the previous pruned call on this context swept less than a quarter of its cells, 64 otherwise
-    // (and on the first call).  SSYM_PRUNE_NT=2|4 pins it for measurements.
-    const char *pin = abandon ? ssym_knob("SSYM_PRUNE_NT") : nullptr;
-    const int pinned = pin ? atoi(pin) : 0;
-    const int pruneNt = pinned == 2 || pinned == 4 ? pinned : (ctx->prune_swept < 0.25f ? 2 : 4);
-    const FilterShape setShape = shape;
-    if (abandon && shape.nt == 4 && pruneNt == 2)
-        shape = FilterShape{2, shape.rb * 2};
     const double scale = common_scale(src, tgt);
     int32_t rc = ensure_records(ctx, src, scale, src.frames_pad, -1);
     if (rc != SSYM_OK)
@@ -562,11 +506,10 @@ int32_t launch_dtw_filter(ssym_ctx *ctx, const SegmentSet &src, const SegmentSet
     // persistent grid: 2 workgroups of 4 waves per CU (2 waves per SIMD), a multiple of 8 so that
     // task & 7 is the XCD group; one hand-off row of [target frames][64] floats per wave
     const int gridBlocks = std::max(8, ctx->num_cus * 2 / 8 * 8);
-    // + 4 x 8 task counters behind the hand-off rows (one set per launch below)
+    // + kMaxClasses x 8 task counters behind the hand-off rows (one set per launch of the plan)
     // (sized for the three-workgroups-per-CU launch of the one-tile kernel too)
     const size_t handBytes = (size_t)(gridBlocks / 2 * 3) * kFilterWavesPerBlock * ((tgt.frames_pad + 3) / 4) * 256 * sizeof(float);
     const size_t ctrBytes = 8 * kTaskCtrStride * sizeof(unsigned);
-    constexpr int kMaxClasses = 10;                 // counter sets: three single-pass classes + up to seven multi-pass ones
     rc = ensure(ctx, ctx->handoff, handBytes + kMaxClasses * ctrBytes);
     if (rc != SSYM_OK)
         return rc;
@@ -574,140 +517,32 @@ int32_t launch_dtw_filter(ssym_ctx *ctx, const SegmentSet &src, const SegmentSet
     rc = zero_words(ctx, taskCtr, kMaxClasses * ctrBytes);
     if (rc != SSYM_OK)
         return rc;
-    hipStream_t st = ctx->stream;
     const bool sq = ctx->squared != 0;
-    const float outScale = (float)(sq ? 1.0 / (scale * scale) : 1.0 / scale);
-    float *hand = (float *)ctx->handoff.ptr;
-    ctx->launched_cells = 0;
-    ctx->filter_launches = 0;
+    const int dimUse = filter_dim_used((int)src.dim);
 
-    // Record slots are ordered by segment length, so source pairs fall into contiguous CLASSES by the
-    // 16-row tiles their longer member needs.  Pairs that fit one, two or three tiles run the single-pass
-    // variant with exactly that many (on the last rows of their end-aligned slots) -- a dictionary of
-    // 8...40-frame segments otherwise paid 48 rows for every pair --, the rest the set's own shape,
-    // whose leading all-padding passes are skipped per task.  One launch per non-empty class.
-    const int nPairs = (int)src.n_pad / 2;
-    auto pairLen = [&](int sp) -> uint32_t {      // longer member of source pair sp; slots [0, n) are real, ascending
-        auto len = [&](uint32_t p) -> uint32_t {
-            if (p >= src.n)
-                return 0u;
-            const uint32_t s = src.h_perm[p];
-            return (uint32_t)(src.h_off[s + 1] - src.h_off[s]);
-        };
-        return std::max(len(2u * sp), len(2u * sp + 1u));
-    };
-    const int nRealPairs = (int)((src.n + 1) / 2);  // pairs behind them hold padding only: they ride with the last class
-    auto firstAbove = [&](uint32_t frames) {        // first real pair whose longer member exceeds `frames`
-        int lo = 0, hi = nRealPairs;
-        while (lo < hi) {
-            const int mid = (lo + hi) / 2;
-            if (pairLen(mid) > frames)
-                hi = mid;
-            else
-                lo = mid + 1;
+    FilterPlanInput in;
+    in.pairLen = plan_lens(src, 2).data(), in.groupCols = plan_lens(tgt, 32).data();
+    in.srcN = src.n, in.srcNPad = src.n_pad, in.framesPad = src.frames_pad;
+    in.tgtN = tgt.n, in.tgtGroups = tgt.n_pad / 32, in.tgtTotalFrames = tgt.total_frames;
+    in.numCus = ctx->num_cus;
+    // operand planes the kernels multiply: record layout 3 leaves the third one zero
+    in.ku = filter_mfmas(filter_pieces(dimUse), dimUse);
+    in.abandon = abandon != nullptr;
+    in.pruneSwept = ctx->prune_swept;
+    in.knobs = read_filter_knobs();
+    const std::vector<FilterLaunch> plan = plan_filter(in);
+
+    ctx->filter_launches = (int)plan.size();
+    ctx->launched_cells = 0;
+    for (const FilterLaunch &l : plan)
+        ctx->launched_cells += l.cells;
+    const FilterCall call{ctx->stream, src, tgt, sq, in.ku, (float)(sq ? 1.0 / (scale * scale) : 1.0 / scale),
+                          (float *)ctx->handoff.ptr, taskCtr, cmat, abandon, colCtr, candSlot};
+    for (const FilterLaunch &l : plan)
+        if (!run_launch(call, l)) {
+            ctx->err = "dtw filter: the plan names a kernel that is not built";
+            return SSYM_E_UNSUPPORTED;
         }
-        return lo;
-    };
-    const int topTiles = setShape.nt;               // tiles of the set's own shape (4 = multi-pass)
-    static const bool oneLaunch = ssym_knob("SSYM_FILTER_ONE_LAUNCH") != nullptr;     // measurements: the set's shape for every pair
-    int bound[4] = {0, 0, 0, 0};                    // bound[c]: first pair that needs more than c tiles
-    for (int c = 1; c < topTiles; ++c)
-        bound[c] = oneLaunch ? 0 : firstAbove(16u * c);
-    // operand planes the kernel multiplies: record layout 3 leaves the third one zero
-    const bool two = filter_mfmas(filter_pieces(filter_dim_used((int)src.dim)), filter_dim_used((int)src.dim)) == 2;
-    bool skipTile = false;                          // set for a multi-pass class below
-#define SSYM_LAUNCH1(NT_, SQ_, KU_, PASSES_, ORIGIN_, LO_, HI_, K_)                                               \
-    launch_one<NT_, SQ_, KU_>(st, src, tgt, PASSES_, gridBlocks, outScale, hand, taskCtr + (K_) * 8 * kTaskCtrStride, \
-                              cmat, abandon, colCtr, candSlot, LO_, (HI_) - (LO_), ORIGIN_, &ctx->launched_cells, skipTile)
-#define SSYM_LAUNCH(NT_, PASSES_, ORIGIN_, LO_, HI_, K_)                                                          \
-    if ((HI_) > (LO_)) {                                                                                          \
-        ++ctx->filter_launches;                                                                                   \
-        if (sq && two) SSYM_LAUNCH1(NT_, true, 2, PASSES_, ORIGIN_, LO_, HI_, K_);                                \
-        else if (sq) SSYM_LAUNCH1(NT_, true, 3, PASSES_, ORIGIN_, LO_, HI_, K_);                                  \
-        else if (two) SSYM_LAUNCH1(NT_, false, 2, PASSES_, ORIGIN_, LO_, HI_, K_);                                \
-        else SSYM_LAUNCH1(NT_, false, 3, PASSES_, ORIGIN_, LO_, HI_, K_);                                         \
-    }
-    const int rowsPad = (int)src.frames_pad;
-    if (topTiles == 4) {
-        SSYM_LAUNCH(1, 1, rowsPad - 16, bound[0], bound[1], 0)
-        SSYM_LAUNCH(2, 1, rowsPad - 32, bound[1], bound[2], 1)
-        SSYM_LAUNCH(3, 1, rowsPad - 48, bound[2], bound[3], 2)
-        static const bool nt8 = ssym_knob("SSYM_FILTER_NT8") != nullptr;
-        static const bool oneLong = ssym_knob("SSYM_FILTER_LONG_CLASSES") && atoi(ssym_knob("SSYM_FILTER_LONG_CLASSES")) == 0;
-        if (shape.nt == 2) {
-            SSYM_LAUNCH(2, shape.rb, 0, bound[3], nPairs, 3)
-        } else if (nt8 && shape.rb == 2 && !abandon) {
-            SSYM_LAUNCH(8, 1, 0, bound[3], nPairs, 3)
-        } else if (abandon || oneLong || oneLaunch) {
-            SSYM_LAUNCH(4, shape.rb, 0, bound[3], nPairs, 3)
-        } else {
-            // Sources beyond 48 frames, ragged: a pair pays whole row passes, so a 70-frame source swept in passes of 64
-            // rows pays 128 -- but 96 in passes of 48.  The pairs (ascending by length) are cut into classes by the shape
-            // that pads them least, passes of 64 rows (four tiles) or of 48 (three), the last rows of their end-aligned
-            // slots as for the short classes; a class of fewer than 128 pairs rides with the next one (any larger shape
-            // holds it), and so does everything beyond the counter sets there are.  Equal lengths: one class, the set's
-            // own shape, as before.
-            struct LongClass { int nt, passes, lo, hi; };
-            LongClass cls[kMaxClasses];
-            int nCls = 0;
-            auto best = [&](uint32_t len, int &nt, int &passes) {
-                const int p4 = (int)((std::max(len, 1u) + 63) / 64), p3 = (int)((std::max(len, 1u) + 47) / 48);
-                if (48 * p3 < 64 * p4) { nt = 3; passes = p3; } else { nt = 4; passes = p4; }
-            };
-            for (int sp = bound[3]; sp < nPairs;) {
-                int nt, passes;
-                best(sp < nRealPairs ? pairLen(sp) : 0u, nt, passes);
-                // the run of pairs this shape is the best for: up to the first pair longer than its rows
-                const int end = std::max(sp + 1, std::min(nPairs, sp < nRealPairs ? firstAbove((uint32_t)(16 * nt * passes)) : nPairs));
-                cls[nCls++] = LongClass{nt, passes, sp, end == nRealPairs ? nPairs : end};     // (padding pairs ride with the last real one)
-                sp = cls[nCls - 1].hi;
-                if (nCls == kMaxClasses - 3 && sp < nPairs) {                                   // no counter set left: the set's own shape takes the rest
-                    cls[nCls - 1] = LongClass{4, shape.rb, cls[nCls - 1].lo, nPairs};
-                    break;
-                }
-            }
-            // small classes join their successor (whose rows are at least theirs); the last one keeps its own
-            for (int c = 0; c + 1 < nCls;) {
-                if (cls[c].hi - cls[c].lo < 128) {
-                    cls[c + 1].lo = cls[c].lo;
-                    for (int k = c; k + 1 < nCls; ++k)
-                        cls[k] = cls[k + 1];
-                    --nCls;
-                } else {
-                    ++c;
-                }
-            }
-            const char *skipKnob = ssym_knob("SSYM_FILTER_SKIP0");        // (read per launch: the tests compare both settings)
-            const bool skipOn = !(skipKnob && atoi(skipKnob) == 0);
-            for (int c = 0; c < nCls; ++c) {
-                const int origin = rowsPad - 16 * cls[c].nt * cls[c].passes;
-                // at least an eighth of the class's pairs leave the first tile of their first pass empty: the variant that
-                // skips such tiles' cells (equal lengths and classes that fill their rows keep the plain kernel)
-                const int rowsCls = 16 * cls[c].nt * cls[c].passes;
-                int skipping = 0;
-                for (int sp = cls[c].lo; sp < std::min(cls[c].hi, nRealPairs); ++sp)
-                    skipping += (rowsCls - (int)pairLen(sp)) % (16 * cls[c].nt) >= 17;
-                skipTile = skipOn && 8 * skipping >= cls[c].hi - cls[c].lo && skipping > 0;
-                if (cls[c].nt == 3) {
-                    SSYM_LAUNCH(3, cls[c].passes, origin, cls[c].lo, cls[c].hi, 3 + c)
-                } else {
-                    SSYM_LAUNCH(4, cls[c].passes, origin, cls[c].lo, cls[c].hi, 3 + c)
-                }
-            }
-            skipTile = false;
-        }
-    } else if (topTiles == 3) {
-        SSYM_LAUNCH(1, 1, rowsPad - 16, bound[0], bound[1], 0)
-        SSYM_LAUNCH(2, 1, rowsPad - 32, bound[1], bound[2], 1)
-        SSYM_LAUNCH(3, 1, 0, bound[2], nPairs, 2)
-    } else if (topTiles == 2) {
-        SSYM_LAUNCH(1, 1, rowsPad - 16, bound[0], bound[1], 0)
-        SSYM_LAUNCH(2, 1, 0, bound[1], nPairs, 1)
-    } else {
-        SSYM_LAUNCH(1, 1, 0, 0, nPairs, 0)
-    }
-#undef SSYM_LAUNCH
-#undef SSYM_LAUNCH1
     SSYM_HIP_CHECK(ctx, hipGetLastError());
     return SSYM_OK;
 }

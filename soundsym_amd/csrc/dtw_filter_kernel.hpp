@@ -66,6 +66,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "dtw_filter_plan.hpp"   // kFilterRecHalfs, kFilterWavesPerBlock, kTaskCtrStride: shared with the host's launch plan
+
 #ifndef SSYM_FILTER_MODE
 #define SSYM_FILTER_MODE 0   // 0 = product; tools only: 1 = MFMA without DP, 2 = DP without MFMA
 #endif
@@ -77,7 +79,6 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int kFilterRowsPerTile = 16;   // frames of one source per 32x32 tile
 constexpr int kFilterKM = 3;             // chained K=16 MFMAs per tile
-constexpr int kFilterRecHalfs = 48;      // f16 values per frame record (96 bytes)
 constexpr int kFilterMaxDim2 = 13;       // two f16 pieces per value: 3*13 product slots + 6 norm slots <= 48
 constexpr int kFilterMaxDim1 = 42;       // one f16 piece per value:  42 product slots + 6 norm slots <= 48
 
@@ -178,8 +179,6 @@ __device__ __forceinline__ float dp_column(const half8 (&A)[NT][KU], const half8
     return up;   // D(last row of the block, j)
 }
 
-constexpr int kFilterWavesPerBlock = 4;
-
 // Column addressing: every global address of the column loop is (a wave-uniform base in scalar registers) + (the lane's
 // constant 16-byte offset) + (an instruction offset).  The base is made opaque so that it stays scalar: left alone, the
 // optimiser folds the lane offset into it and re-forms a 64-bit VECTOR address per access (a v_mad_i64_i32 per staged
@@ -196,7 +195,6 @@ constexpr int kFilterWavesPerBlock = 4;
 // 4 columns (a later test costs a sixth of the columns such a task sweeps at all), afterwards every kPruneEvery
 constexpr int kPruneFine = SSYM_PRUNE_FINE;
 constexpr int kPruneEvery = SSYM_PRUNE_EVERY;   // PRUNE: columns between two abandon tests (a test is BR/2 v_min3 + a vote)
-constexpr int kTaskCtrStride = 64;      // the 8 task counters sit in separate 256-byte lines (separate L2 channels)
 // Target columns staged in LDS per wave: 4 at two waves per SIMD (three columns of lead); the single-pass
 // kernels for short sources (NT <= 2) can run three waves per SIMD with a ring of 2 (one column of
 // lead, latency covered by occupancy) so that three workgroups fit the LDS.

@@ -56,11 +56,7 @@ __device__ unsigned long long ssym_sp_prof[12];
 #define SSYM_SP_ACC(k_, d_)
 #endif
 
-#ifndef SSYM_SP_ROWBLOCK
-#define SSYM_SP_ROWBLOCK 4
-#endif
-constexpr int kSpRowBlock = SSYM_SP_ROWBLOCK;                    // G: DP rows of the first tile are skipped in blocks of G
-constexpr int kSpRing = 4;                                     // staged columns per wave
+// (kSpRowBlock, the row block G, and kSpRing, the staged columns per wave: dtw_filter_plan.hpp)
 constexpr int sp_slot_bytes(int ku) { return ku * 1024; }      // 64 lanes x KU x 16 B operands of one column
 
 // One column: NT tiles, the first from row R0 (rows above hold padding for both sources of the wave); the next tile's

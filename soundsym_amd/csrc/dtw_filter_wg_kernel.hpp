@@ -46,7 +46,7 @@
 //     INVARIANT: every wave of a workgroup executes the same sequence of barriers.  The task (block, target group) is the
 //     workgroup's, so nCols -- the longest target of the shared group -- is the same in all four waves; nPasses is the
 //     launch's; every pair starts at pass 0 (the host launches this kernel only where pass 0 holds a row of the shortest
-//     pair of the range, dtw_filter.hip launch_one, so firstPass is not computed here); hop, got, rangeLen and the chunk's
+//     pair of the range, dtw_filter_plan.hpp plan_filter, so firstPass is not computed here); hop, got, rangeLen and the chunk's
 //     bounds are the workgroup's.  No condition that differs between the waves of a workgroup encloses a barrier: the only
 //     wave-dependent branch (wave 0 takes the chunk) holds none.
 //   * LDS: 16 slots x 3 KB + 4 waves x 2 KB of top buffers = 56 KB per workgroup, as much as dtw_filter_kernel's four rings of four slots.

@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "soundsym_amd.h"
+#include "dtw_filter_plan.hpp"
 
 // Measurement and test knobs (SSYM_FILTER_*, SSYM_REFCOS_*, SSYM_EXACT_*, SSYM_CELLS_*, SSYM_PRUNE_NT ...: none changes a
 // result) are read only in a process that asked for the library's test hooks with SSYM_TEST_HOOKS=1 -- a production
@@ -26,20 +27,8 @@ inline const char *ssym_knob(const char *name)
 
 namespace ssym {
 
-// dtw filter geometry (see dtw_filter_kernel.hpp): a source slot holds 16*nt*rb rows, processed by
-// one wave in rb passes of nt 32x32 tiles each.
-struct FilterShape {
-    int nt = 0, rb = 0;
-    int rows() const { return 16 * nt * rb; }
-};
-inline FilterShape filter_shape(int max_frames)
-{
-    if (max_frames <= 16) return FilterShape{1, 1};
-    if (max_frames <= 32) return FilterShape{2, 1};
-    if (max_frames <= 48) return FilterShape{3, 1};
-    if (max_frames <= 4096) return FilterShape{4, (max_frames + 63) / 64};
-    return FilterShape{};   // beyond the filter's reach: exact kernel only
-}
+// dtw filter geometry (FilterShape, filter_shape) and the planes and values its kernels use (filter_mfmas, filter_dim_used):
+// dtw_filter_plan.hpp
 
 // How a frame's values are laid into the filter records (dtw_filter_kernel.hpp):
 //   1  one f16 piece per value, frames of 14...42 values (42 product slots + 6 norm slots of K = 48);
@@ -48,12 +37,6 @@ inline FilterShape filter_shape(int max_frames)
 //      norms those of the represented frames in two pieces each -- two MFMAs per tile instead of three (the third plane
 //      of the records stays zero).  The default for up to 13 values; SSYM_FILTER_K48=1 keeps layout 2 (measurements).
 int filter_pieces(int dim);
-// MFMAs the unbanded filter issues per 32 x 32 tile for that layout
-// (layout 1 needs dim + 6 slots: frames of 14...26 values fit two planes as well)
-inline int filter_mfmas(int pieces, int dim) { return (pieces == 3 || (pieces == 1 && dim + 6 <= 32)) ? 2 : 3; }
-// values per frame the filter sees: frames wider than 42 values enter with their first 42 only, which
-// makes the filter's cost a LOWER bound of the pair's cost ("wide frames")
-inline int filter_dim_used(int dim) { return dim <= 42 ? dim : 42; }
 
 // doubles allocated behind a set's values: 16-byte loads that start on a segment's last value stay inside the buffer
 constexpr size_t kRawTailPad = 2;
@@ -93,6 +76,7 @@ struct SegmentSet {
     // selection kernels keeps the caller's indices.
     uint32_t *perm = nullptr;
     std::vector<uint32_t> h_perm;
+    mutable std::vector<uint32_t> plan_lens;    // the filter plan's lengths (dtw_filter.hip plan_lens), built on first use
     mutable size_t rec_bytes = 0;
     mutable uint32_t rec_slots = 0;   // record slots per segment in `rec`
     mutable int rec_lead = 0;         // slot of frame 0 (-1: end-aligned)

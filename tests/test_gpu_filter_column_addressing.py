@@ -21,9 +21,9 @@ The packed kernel (csrc/dtw_filter_pk_kernel.hpp, SSYM_FILTER_PK=1) takes launch
 gives the 65-, 129- and 70/80-frame cases passes of 48 rows (three tiles, SKIP0 for two of them): under the knob alone
 they would run the kernel under test again.  So the packed child also sets SSYM_FILTER_LONG_CLASSES=0, which launches
 every pair beyond 48 frames on the set's own shape of four tiles -- results do not depend on the pass height -- and the
-packed kernel then computes every case.  That it did is read from the launch's cell count: launch_one returns for the
-packed kernel before it counts the launch's cells, so a packed search reports none.  Both knobs are latched per process:
-one child process per setting runs the whole table; the plain child (SSYM_FILTER_PK=0) is this process's twin.
+packed kernel then computes every case.  That it did is read from the launch's cell count: the plan counts no cells
+for a launch of the packed kernel, so a packed search reports none.  One child process per setting runs the whole table;
+the plain child (SSYM_FILTER_PK=0) is this process's twin.
 """
 import os
 import subprocess

@@ -11,8 +11,8 @@ compare two different launches.
 
 Per case: the whole filter matrix within the per-pair bound of tests/bounds.py after the scratch has been filled with
 another search of the same lengths, the exact matrix and every target's argmin against the oracle, the same bits under
-SSYM_FILTER_SKIP0=0 (read per launch: in process), and under SSYM_FILTER_LONG_CLASSES=0 and SSYM_FILTER_ONE_LAUNCH
-(latched once per process: a child process each).  One source of 4097 frames takes the search off the filter.
+SSYM_FILTER_SKIP0=0 (in process), and under SSYM_FILTER_LONG_CLASSES=0 and SSYM_FILTER_ONE_LAUNCH (a child process
+each).  One source of 4097 frames takes the search off the filter.
 
 Worst measured |filter - oracle| / tolerance per case: LAB.md, "filter variants beyond 48 frames".
 """
@@ -125,7 +125,7 @@ def test_a_source_beyond_4096_frames_takes_the_exact_kernel(oracle):
         e.close()
 
 
-# ---- knobs latched once per process: a child process each ------------------------------------------------------------
+# ---- the whole table under a knob: a child process each ---------------------------------------------------------------
 _CHILD = r"""
 import sys, numpy as np
 sys.path.insert(0, sys.argv[1]); sys.path.insert(0, sys.argv[2])

@@ -1,4 +1,4 @@
-"""Every launch variant of the dtw MFMA filter (csrc/dtw_filter.hip launch_one), pair by pair against the oracle.
+"""Every launch variant of the dtw MFMA filter (csrc/dtw_filter_plan.hpp plan_filter, csrc/dtw_filter.hip run_launch), pair by pair against the oracle.
 
 The selection drops a pair whose filter cost, minus its bound (csrc/dtw_margin.hpp), cannot win, and the exact f64
 re-score only sees the survivors: a filter value outside its bound, or a (target group, source pair) task the scheduler
@@ -11,8 +11,8 @@ prove that the case ran the variant it names and that the A/B comparisons below 
 
 Per case: the whole filter matrix within the per-pair bound of tests/bounds.py after the scratch has been filled with
 another search of the same shape, the exact matrix and the argmin of every target against the oracle, and the same bits
-with the knobs that pick another variant (SSYM_SP_MULTIPAIR=0 in process; SSYM_FILTER_SP=0 and SSYM_SP_PAIRBLOCK=0,
-latched once per process, in a child process each).
+with the knobs that pick another variant (SSYM_SP_MULTIPAIR=0 in process; SSYM_FILTER_SP=0 and SSYM_SP_PAIRBLOCK=0 in a
+child process each).
 """
 import os
 import subprocess
@@ -196,7 +196,7 @@ def test_filter_variant_against_oracle(oracle, case):
         e.close()
 
 
-# ---- knobs latched once per process: a child process each ------------------------------------------------------------
+# ---- the whole table under a knob: a child process each ---------------------------------------------------------------
 _CHILD = r"""
 import sys, numpy as np
 sys.path.insert(0, sys.argv[1]); sys.path.insert(0, sys.argv[2])

@@ -1,5 +1,5 @@
 """dtw_filter_wg_kernel (csrc/dtw_filter_wg_kernel.hpp): the sibling of the headline filter kernel whose four waves share
-one ring of target columns, and its gating in csrc/dtw_filter.hip launch_one.
+one ring of target columns, and its gating in csrc/dtw_filter_plan.hpp plan_filter.
 
 Every case runs the same search with SSYM_FILTER_WG=1 and =0 (read per launch) on one context: the filter matrix of both
 legs has the same bits, the sibling's is within tests/bounds.py's per-pair bound of the oracle after the scratch has been
@@ -135,6 +135,9 @@ def test_sibling_against_plain_kernel_and_oracle(oracle, name):
         on, packed = _search(e, dim, src, tgt, wg=True)
         off, _ = _search(e, dim, src, tgt, wg=False)
         assert (on["wg_matrix"], off["wg_matrix"]) == (1, 0), (on["wg_matrix"], off["wg_matrix"])
+        plan_off, _ = filter_plan(_lens(src), _lens(tgt), dim, num_cus(), wg=False)      # the plan's gate says the same
+        assert ([x.wg for x in plan], [x.wg for x in plan_off]) == ([True], [False])
+        assert [x._replace(wg=False) for x in plan] == plan_off
         assert on["wg_match"] >= 1 and off["wg_match"] == 0
         assert on["used_filter"] == off["used_filter"] == 1
         assert on["launches"] == off["launches"] == len(plan)
@@ -180,6 +183,9 @@ def test_refusals_keep_the_plain_kernels(oracle, kind):
             assert res["wg_match"] == 0
         else:
             assert (res["wg_matrix"], res["wg_match"]) == (0, 0)
+            if band < 0:                                  # the plan's gate says the same
+                plan, _ = filter_plan(_lens(src), _lens(tgt), 13, num_cus())
+                assert len(plan) == 1 and sum(x.wg for x in plan) == res["wg_matrix"], plan
         want_idx, want_cost, _ = _oracle(oracle, 13, False, packed, band=band)
         _check_search(res, want_idx, want_cost)
     finally:
