@@ -15,6 +15,7 @@ use std::os::raw::{c_char, c_void};
 #[repr(C)] pub struct SsymGmm { _p: [u8; 0] }
 #[repr(C)] pub struct SsymStream { _p: [u8; 0] }
 #[repr(C)] pub struct SsymSpotter { _p: [u8; 0] }
+#[repr(C)] pub struct SsymCoverer { _p: [u8; 0] }
 
 pub const SSYM_ABI_VERSION: i32 = 3;
 
@@ -321,6 +322,22 @@ extern "C" {
     // frame costs a bounded stretch of a lane, and the state is two rows per (lane, target); max_cost stays a sum
     pub fn ssym_spotter_create_step(ctx: *mut SsymCtx, q: *const SsymQueries, n_lanes: u32, max_cost: *const f64,
                                     step: u32, out: *mut *mut SsymSpotter) -> i32;
+    // the live cover ("Live cover" in soundsym_amd.h): growing targets tiled by the segments of one resident dictionary, every
+    // piece reported by the push after which no longer recording could change it; the dictionary must outlive the coverer
+    pub fn ssym_coverer_create(ctx: *mut SsymCtx, dict: *const SsymDict, n_lanes: u32, piece_penalty: f64,
+                               out: *mut *mut SsymCoverer) -> i32;
+    pub fn ssym_coverer_destroy(ctx: *mut SsymCtx, cv: *mut SsymCoverer) -> i32;
+    pub fn ssym_coverer_push(ctx: *mut SsymCtx, cv: *mut SsymCoverer, feats: *const f64, frame_offsets: *const u64,
+                             flags: u32, out_n_pieces: *mut u64) -> i32;
+    pub fn ssym_coverer_follow(ctx: *mut SsymCtx, cv: *mut SsymCoverer, stream: *const SsymStream, flags: u32,
+                               out_n_pieces: *mut u64) -> i32;
+    pub fn ssym_coverer_pieces(ctx: *mut SsymCtx, cv: *const SsymCoverer, out_lane: *mut u32, out_src: *mut u32,
+                               out_start: *mut u32, out_end: *mut u32, out_cost: *mut f64, flags: u32) -> i32;
+    pub fn ssym_coverer_flush(ctx: *mut SsymCtx, cv: *mut SsymCoverer, lane: u32, out_n_pieces: *mut u64) -> i32;
+    pub fn ssym_coverer_best(ctx: *mut SsymCtx, cv: *const SsymCoverer, out_total: *mut f64, out_covered: *mut u32,
+                             out_committed: *mut u32, flags: u32) -> i32;
+    pub fn ssym_coverer_counts(cv: *const SsymCoverer, out_frames: *mut u64, out_capacity: *mut u64) -> i32;
+    pub fn ssym_coverer_reset(ctx: *mut SsymCtx, cv: *mut SsymCoverer, lane: u32) -> i32;
 }
 
 /// `Err(message)` for any status but SSYM_OK; SSYM_E_EMPTY_DICT keeps the crate's behaviour (a panic, :369).

@@ -771,6 +771,109 @@ class Spotter {
     ssym_spotter *sp_ = nullptr;
 };
 
+// n_lanes growing targets tiled by the segments of a dictionary (ssym_coverer; soundsym_amd.h "Live cover"): every piece is
+// reported by the push after which no longer recording could change it, the pieces from reset to flush are
+// SoundDictionary::cover's for the whole, and best() gives its total for what a lane has consumed.  The coverer packs the
+// sounds' features into a dictionary of its own and keeps it for as long as it lives.
+class Coverer {
+  public:
+    using Spot = SoundDictionary::Spot;
+    struct Piece {
+        uint32_t lane;
+        Spot piece;                 // source_index = the dictionary sound; start / end count the lane's frames, end inclusive
+    };
+    struct Best {
+        double total;               // SoundDictionary::cover's total of everything consumed; +inf without a cover
+        uint32_t covered;           // frames of the longest prefix that has a cover
+        uint32_t committed;         // frames whose pieces have been emitted
+    };
+    Coverer(std::shared_ptr<Context> ctx, const std::vector<ArcSound> &sounds, uint32_t n_lanes = 1, double piece_penalty = 0.0)
+        : ctx_(std::move(ctx)), lanes_(n_lanes)
+    {
+        std::vector<double> flat;
+        std::vector<uint64_t> off;
+        pack_features(sounds, flat, off);
+        ctx_->check(ssym_dict_create(ctx_->get(), flat.data(), off.data(), (uint32_t)sounds.size(), (uint32_t)NCOEFFS, &dict_));
+        const int32_t rc = ssym_coverer_create(ctx_->get(), dict_, n_lanes, piece_penalty, &cv_);
+        if (rc != SSYM_OK) {
+            ssym_dict_destroy(ctx_->get(), dict_);
+            ctx_->check(rc);
+        }
+    }
+    ~Coverer()
+    {
+        ssym_coverer_destroy(ctx_->get(), cv_);      // the coverer reads the dictionary: it goes first
+        ssym_dict_destroy(ctx_->get(), dict_);
+    }
+    Coverer(const Coverer &) = delete;
+    Coverer &operator=(const Coverer &) = delete;
+
+    // lane l consumes frames [frame_offsets[l], frame_offsets[l + 1]) of feats (NCOEFFS values each); the pieces it commits
+    std::vector<Piece> push(const std::vector<double> &feats, const std::vector<uint64_t> &frame_offsets)
+    {
+        if (frame_offsets.size() != (size_t)lanes_ + 1)
+            throw Error(SSYM_E_INVALID, "frame_offsets must hold n_lanes + 1 entries");
+        uint64_t n = 0;
+        ctx_->check(ssym_coverer_push(ctx_->get(), cv_, feats.data(), frame_offsets.data(), 0, &n));
+        return pieces(n);
+    }
+    // every lane consumes, device to device, what the stream's lane holds beyond the frames consumed
+    std::vector<Piece> follow(const ssym_stream *stream)
+    {
+        uint64_t n = 0;
+        ctx_->check(ssym_coverer_follow(ctx_->get(), cv_, stream, 0, &n));
+        return pieces(n);
+    }
+    // "the lane has ended": the rest of its cover; the lane consumes nothing more until reset
+    std::vector<Piece> flush(uint32_t lane)
+    {
+        uint64_t n = 0;
+        ctx_->check(ssym_coverer_flush(ctx_->get(), cv_, lane, &n));
+        return pieces(n);
+    }
+    std::vector<Best> best() const
+    {
+        std::vector<double> total(lanes_);
+        std::vector<uint32_t> covered(lanes_), committed(lanes_);
+        ctx_->check(ssym_coverer_best(ctx_->get(), cv_, total.data(), covered.data(), committed.data(), 0));
+        std::vector<Best> out(lanes_);
+        for (uint32_t l = 0; l < lanes_; ++l)
+            out[l] = Best{total[l], covered[l], committed[l]};
+        return out;
+    }
+    std::vector<uint64_t> counts() const
+    {
+        std::vector<uint64_t> out(lanes_);
+        ctx_->check(ssym_coverer_counts(cv_, out.data(), nullptr));
+        return out;
+    }
+    // frames the ring of back-pointers holds per lane
+    uint64_t capacity() const
+    {
+        uint64_t cap = 0;
+        ctx_->check(ssym_coverer_counts(cv_, nullptr, &cap));
+        return cap;
+    }
+    void reset(uint32_t lane) { ctx_->check(ssym_coverer_reset(ctx_->get(), cv_, lane)); }
+
+  private:
+    std::vector<Piece> pieces(uint64_t n) const
+    {
+        std::vector<uint32_t> lane(n), src(n), start(n), end(n);
+        std::vector<double> cost(n);
+        if (n)
+            ctx_->check(ssym_coverer_pieces(ctx_->get(), cv_, lane.data(), src.data(), start.data(), end.data(), cost.data(), 0));
+        std::vector<Piece> out(n);
+        for (uint64_t k = 0; k < n; ++k)
+            out[k] = Piece{lane[k], Spot{src[k], start[k], end[k], cost[k]}};
+        return out;
+    }
+    std::shared_ptr<Context> ctx_;
+    uint32_t lanes_ = 0;
+    ssym_dict *dict_ = nullptr;
+    ssym_coverer *cv_ = nullptr;
+};
+
 // One rank of a SoundDictionary split over the GPUs of one node (source-axis shards, one rank -- thread or process --
 // per GPU): rank g holds sounds [lo, lo + shard.size()) of the whole dictionary and is handed the same targets as every
 // other rank; match_indices returns GLOBAL indices, the same complete answer on every rank, bit for bit the unsharded

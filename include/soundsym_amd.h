@@ -59,6 +59,7 @@ typedef struct ssym_comm ssym_comm;       /* one rank of a source-sharded run: a
 typedef struct ssym_gmm ssym_gmm;         /* a trained Gaussian mixture (the partitioner's model)    */
 typedef struct ssym_stream ssym_stream;   /* growing sounds: samples + analysis resident on the GPU  */
 typedef struct ssym_spotter ssym_spotter; /* targets watched in growing sources: resumable spotting   */
+typedef struct ssym_coverer ssym_coverer; /* growing targets tiled by dictionary segments: live cover  */
 
 enum {
     SSYM_OK = 0,
@@ -1098,6 +1099,73 @@ SSYM_API int32_t ssym_spotter_reset(ssym_ctx *ctx, ssym_spotter *sp, uint32_t la
  * 24 bytes x (frames of all targets) x n_lanes under SSYM_STEP_PACED and stays 12 under SSYM_STEP_SYMMETRIC. */
 SSYM_API int32_t ssym_spotter_create_step(ssym_ctx *ctx, const ssym_queries *q, uint32_t n_lanes, const double *max_cost,
                                           uint32_t step, ssym_spotter **out);
+
+/* Live cover (DESIGN.md section 2 "Live cover" and section 5.24): the cover of targets that grow.  A coverer holds n_lanes
+ * growing targets against ONE resident dictionary and reports every piece with the push after which no longer recording
+ * could change it.  c, w, M, src, best, the tie rules and the arithmetic are those of "Cover" above, word for word.  For one
+ * lane, X is everything consumed so far, n its frame count, W = 2 max(Fmax, 1), Fmax the dictionary's longest segment at
+ * creation:
+ *   resume   : the lane holds n, its last W-1 frames, best(e) for the last W ends, the back-pointers (L, src, M) of every
+ *              frame after the committed end, done (the last committed end, -1 at first) and lastFinite (the largest e with
+ *              a finite best(e), -1 at first: best(-1) = 0).  Consuming frames n ... n+m-1 computes M(s,L) for every window
+ *              that ends in them and best(e) and the back-pointers for e = n ... n+m-1, exactly as "Cover" does.
+ *   horizon  : H(n) = { e : max(-1, n-W) <= e <= n-1, best(e) finite }   (-1 belongs to it while n < W)
+ *   walk(e)  : the pieces the back-pointers give from e down to -1, in ascending start   (walk(-1) is empty)
+ *   commit   : C(n) = the longest common prefix of walk(e) over e in H(n); H(n) empty: nothing new.  A push emits the pieces
+ *              of C(n) not emitted before, and done = the end of the last of them.
+ *   flush    : emits the pieces of walk(lastFinite) not emitted before.  The lane has then ENDED: it consumes nothing more
+ *              until ssym_coverer_reset (ssym_coverer_push with frames for it: SSYM_E_INVALID; ssym_coverer_follow skips it).
+ *   best     : total = best(n-1) (+inf for n = 0 or when not finite), covered = lastFinite + 1, committed = done + 1
+ * So: (1) after any push, total has the bits ssym_dtw_cover returns for the frames consumed so far as one target; (2) C(n)
+ * depends on the frames consumed, not on how they were cut into pushes, slices or lanes, and only grows; (3) never revised:
+ * the cover of every longer recording that has one starts with C(n), pieces, cuts and cost bits; (4) with best(n-1) finite
+ * the pieces emitted from reset to flush are ssym_dtw_cover's for the whole, else they are its cover of X[0 ... lastFinite];
+ * (5) a piece's cost is the paced alignment's for the cut; (6) a NaN or +-inf target frame ends the lane's coverable prefix
+ * before it: nothing is committed past it, total stays +inf, the flush gives the cover of the prefix, other lanes are
+ * untouched; a dictionary segment with a NaN frame is never chosen; no read leaves its buffer; (7) device state per lane is
+ * the W-1 tail frames, the ring of best values and the back-pointers of the uncommitted stretch n-1-done, held in a ring of
+ * frames whose capacity is a power of two, 1024 at least, grown (doubling) when the uncommitted stretch plus a slice's
+ * frames would not fit; nothing scales with the stream.  The uncommitted stretch has no hard bound.
+ *
+ * ssym_coverer_create: dict's resident features are READ BY THE COVERER FOR AS LONG AS IT LIVES: destroy the coverer first.
+ *   A dictionary appended to since: SSYM_E_INVALID at the next push / follow.  piece_penalty as for ssym_dtw_cover.
+ * ssym_coverer_push: appends feats[frame_offsets[l] .. frame_offsets[l+1]) (frames of the dictionary's dim, f64, HOST
+ *   memory whatever the context's dtype) to lane l, for every lane; an empty range leaves a lane alone.
+ *   out_n_pieces   the pieces this call emitted (read them with ssym_coverer_pieces)
+ * ssym_coverer_follow: for every lane, consumes the frames the stream's lane holds beyond those consumed, device to device.
+ *   The stream must belong to ctx and have the coverer's lanes and n_coeffs = the dictionary's dim; a lane that holds
+ *   fewer frames than were consumed (the stream was reset) is SSYM_E_INVALID: call ssym_coverer_reset.
+ * ssym_coverer_pieces: the pieces of the last push / follow / flush, out_n_pieces of them, ordered by (lane, start); each
+ *   output nullable (HOST, or device memory with SSYM_OUT_DEVICE).  start / end count frames of the lane since its reset.
+ * ssym_coverer_flush: the flush of one lane.
+ * ssym_coverer_best: [n_lanes] each, nullable (HOST, or device memory with SSYM_OUT_DEVICE).
+ * ssym_coverer_counts: frames consumed per lane (n_lanes u64) and the capacity of the back-pointer ring in frames (one
+ *   u64), HOST, each nullable.  Host arithmetic, no device work.
+ * ssym_coverer_reset: one lane back to "nothing consumed".
+ * Limits, checked at creation before any device work: a dtw context without a band, dim <= 64, every dictionary segment of
+ * at most 128 frames (kCoverMaxSourceFrames), at most 65535 lanes, and lanes x 2 Fmax x 2 Fmax x 12 bytes <= 512 MiB:
+ * SSYM_E_UNSUPPORTED beyond them and on a refcos context.  An empty dictionary: SSYM_E_EMPTY_DICT.  A NaN, negative or
+ * infinite piece_penalty: SSYM_E_INVALID.  A lane consumes at most 2^31 - 1 frames (SSYM_E_UNSUPPORTED beyond).  NULL
+ * handles, decreasing offsets, a lane outside the coverer, a handle of another context, a stream whose lanes or n_coeffs
+ * differ: SSYM_E_INVALID with a message, the coverer as it was and the outputs unwritten.
+ * The tables of one call are lanes x (W - 1 + new frames) x W x 12 bytes per source block; a push that would pass the
+ * cover's 512 MiB runs as several slices of frames in the same call, with a commit after each and the same results.  One
+ * synchronisation per slice.  ssym_get_timings afterwards: main_ms = the forward pass (gather and fold included),
+ * reduce_ms = chain, commit and emission, n_pairs = n_sources x the frames the call consumed. */
+SSYM_API int32_t ssym_coverer_create(ssym_ctx *ctx, const ssym_dict *dict, uint32_t n_lanes, double piece_penalty,
+                                     ssym_coverer **out);
+SSYM_API int32_t ssym_coverer_destroy(ssym_ctx *ctx, ssym_coverer *cv);
+SSYM_API int32_t ssym_coverer_push(ssym_ctx *ctx, ssym_coverer *cv, const double *feats, const uint64_t *frame_offsets,
+                                   uint32_t flags, uint64_t *out_n_pieces);
+SSYM_API int32_t ssym_coverer_follow(ssym_ctx *ctx, ssym_coverer *cv, const ssym_stream *stream, uint32_t flags,
+                                     uint64_t *out_n_pieces);
+SSYM_API int32_t ssym_coverer_pieces(ssym_ctx *ctx, const ssym_coverer *cv, uint32_t *out_lane, uint32_t *out_src,
+                                     uint32_t *out_start, uint32_t *out_end, double *out_cost, uint32_t flags);
+SSYM_API int32_t ssym_coverer_flush(ssym_ctx *ctx, ssym_coverer *cv, uint32_t lane, uint64_t *out_n_pieces);
+SSYM_API int32_t ssym_coverer_best(ssym_ctx *ctx, const ssym_coverer *cv, double *out_total, uint32_t *out_covered,
+                                   uint32_t *out_committed, uint32_t flags);
+SSYM_API int32_t ssym_coverer_counts(const ssym_coverer *cv, uint64_t *out_frames, uint64_t *out_capacity);
+SSYM_API int32_t ssym_coverer_reset(ssym_ctx *ctx, ssym_coverer *cv, uint32_t lane);
 
 #ifdef __cplusplus
 }

@@ -11,12 +11,13 @@ from ._native import (  # noqa: F401
     SsymError,
     build,
 )
-from .engine import DeviceFrames, Engine, Gmm, Spotter, Stream, pack_segments, stream_plan  # noqa: F401
+from .engine import Coverer, DeviceFrames, Engine, Gmm, Spotter, Stream, pack_segments, stream_plan  # noqa: F401
 from .api import (  # noqa: F401
     Alignment,
     BIN,
     Cover,
     HOP,
+    LiveCover,
     NCLUSTERS,
     NCOEFFS,
     Partitioner,
@@ -38,7 +39,7 @@ from .api import (  # noqa: F401
 )
 
 __all__ = [
-    "ABI_SYMBOLS", "Alignment", "BIN", "Cover", "DeviceFrames", "EmptyDictionaryError", "Engine", "Gmm", "HOP", "LIB_PATH", "NCLUSTERS", "NCOEFFS",
+    "ABI_SYMBOLS", "Alignment", "BIN", "Cover", "Coverer", "DeviceFrames", "EmptyDictionaryError", "Engine", "Gmm", "HOP", "LIB_PATH", "LiveCover", "NCLUSTERS", "NCOEFFS",
     "Partitioner", "Piece", "Sound", "SoundDictionary", "SoundSequence", "Spot", "SsymError", "analyze_mfccs", "analyze_sounds", "build",
     "cosine_sim_angular", "discretize",
     "discretize_with_model", "length_fit", "pack_segments", "push_sounds", "Spotter", "Stream", "stream_plan", "train_model", "Watch", "watch",

@@ -65,6 +65,8 @@ ABI_SYMBOLS = [
     "ssym_match_queries_step", "ssym_pair_matrix_step",
     "ssym_dtw_cover",
     "ssym_spotter_create_step",
+    "ssym_coverer_create", "ssym_coverer_destroy", "ssym_coverer_push", "ssym_coverer_follow", "ssym_coverer_pieces",
+    "ssym_coverer_flush", "ssym_coverer_best", "ssym_coverer_counts", "ssym_coverer_reset",
     "ssym_reconstruct_warped", "ssym_reconstruct_wsola",
     "ssym_dtw_align_spans_sizes", "ssym_dtw_align_spans", "ssym_reconstruct_warped_spans", "ssym_reconstruct_wsola_spans",
 ]
@@ -387,6 +389,24 @@ def lib() -> ctypes.CDLL:
     L.ssym_spotter_counts.argtypes = [vp, vp]
     L.ssym_spotter_reset.restype = i32
     L.ssym_spotter_reset.argtypes = [vp, vp, u32]
+    L.ssym_coverer_create.restype = i32
+    L.ssym_coverer_create.argtypes = [vp, vp, u32, f64, pvp]
+    L.ssym_coverer_destroy.restype = i32
+    L.ssym_coverer_destroy.argtypes = [vp, vp]
+    L.ssym_coverer_push.restype = i32
+    L.ssym_coverer_push.argtypes = [vp, vp, vp, vp, u32, ctypes.POINTER(u64)]
+    L.ssym_coverer_follow.restype = i32
+    L.ssym_coverer_follow.argtypes = [vp, vp, vp, u32, ctypes.POINTER(u64)]
+    L.ssym_coverer_pieces.restype = i32
+    L.ssym_coverer_pieces.argtypes = [vp, vp, vp, vp, vp, vp, vp, u32]
+    L.ssym_coverer_flush.restype = i32
+    L.ssym_coverer_flush.argtypes = [vp, vp, u32, ctypes.POINTER(u64)]
+    L.ssym_coverer_best.restype = i32
+    L.ssym_coverer_best.argtypes = [vp, vp, vp, vp, vp, u32]
+    L.ssym_coverer_counts.restype = i32
+    L.ssym_coverer_counts.argtypes = [vp, vp, ctypes.POINTER(u64)]
+    L.ssym_coverer_reset.restype = i32
+    L.ssym_coverer_reset.argtypes = [vp, vp, u32]
     _lib = L
     return L
 

@@ -557,6 +557,70 @@ def _cover_sounds(sound: "Sound", cover: "Cover") -> List["Sound"]:
     return out
 
 
+class LiveCover:
+    """Growing Sounds covered live by a dictionary (`SoundDictionary.cover_live`): the sounds' shared stream followed by a
+    Coverer (DESIGN.md section 2 "Live cover").  Pieces are (sound index, Piece), a Piece's frames those of the sound; a
+    piece, once returned, is final: it is how the cover of the whole sound starts, whatever the sound gains later."""
+
+    def __init__(self, sounds, stream, coverer, piece_penalty: float):
+        self.sounds, self.stream, self.coverer, self.piece_penalty = sounds, stream, coverer, float(piece_penalty)
+        self._emitted = [[] for _ in sounds]
+
+    def _pieces(self):
+        lane, src, start, end, cost = self.coverer.pieces()
+        out = [(int(lane[k]), Piece(src[k], start[k], end[k], cost[k])) for k in range(lane.size)]
+        for l, p in out:
+            self._emitted[l].append(p)
+        return out
+
+    def poll(self):
+        """Consume what the sounds have gained since the last poll (device to device) and return the pieces that commits,
+        ordered by (sound, start)."""
+        self.coverer.follow(self.stream)
+        return self._pieces()
+
+    def flush(self):
+        """"The sounds have ended": the rest of every sound's cover.  The cover consumes nothing more afterwards."""
+        out = []
+        for lane in range(self.coverer.n_lanes):
+            self.coverer.flush(lane)
+            out += self._pieces()
+        return out
+
+    def covers(self) -> List["Cover"]:
+        """One Cover per sound from everything emitted so far: it tiles the frames committed, and its total is the chain's
+        own sum over its pieces -- after flush, SoundDictionary.cover's Cover of the sound (of its coverable prefix, when a
+        NaN frame or a stretch nothing can pace ends that early)."""
+        out = []
+        for pieces in self._emitted:
+            if not pieces:
+                out.append(Cover.none(0))
+                continue
+            acc = 0.0
+            for p in pieces:
+                acc = (p.cost + self.piece_penalty) + acc
+            out.append(Cover(pieces, acc, pieces[-1].end_frame + 1))
+        return out
+
+    def pending(self):
+        """(frames consumed, frames covered, frames committed, total), one entry per sound: total is
+        SoundDictionary.cover's for what was consumed, +inf without a cover."""
+        total, covered, committed = self.coverer.best()
+        return self.coverer.counts()[0].astype(np.int64), covered.astype(np.int64), committed.astype(np.int64), total
+
+    def close(self):
+        self.coverer.close()
+
+
+def _shared_stream(sounds, what: str):
+    """The stream that resident sounds share, sound i in lane i -- what one push_sounds(sounds, ...) leaves."""
+    first = sounds[0]._stream if sounds else None
+    if first is None or not first[0].ptr or first[0].n_lanes != len(sounds) or \
+            any(s._stream is None or s._stream[0] is not first[0] or s._stream[1] != i for i, s in enumerate(sounds)):
+        raise ValueError(what + ": the sounds must share one stream (feed them together with push_sounds first)")
+    return first[0]
+
+
 class Watch:
     """Targets watched in growing Sounds (`watch`): the sounds' shared stream followed by a Spotter.  Events are
     (sound index, target index, Spot) with Spot.source_index the sound index; frames are those of the sound, so
@@ -618,11 +682,7 @@ def watch(sounds: Sequence[Sound], targets: Sequence[Sound], max_cost=None, engi
         if step != "paced":
             raise ValueError('max_cost_per_frame needs step="paced": only there is cost / frames a mean per-frame distance')
     sounds, targets = list(sounds), list(targets)
-    first = sounds[0]._stream if sounds else None
-    if first is None or not first[0].ptr or first[0].n_lanes != len(sounds) or \
-            any(s._stream is None or s._stream[0] is not first[0] or s._stream[1] != i for i, s in enumerate(sounds)):
-        raise ValueError("watch: the sounds must share one stream (feed them together with push_sounds first)")
-    st = first[0]
+    st = _shared_stream(sounds, "watch")
     e = engine or st.engine
     if e is not st.engine:
         raise ValueError("watch: the engine must be the one that holds the sounds' stream")
@@ -1017,6 +1077,63 @@ class SoundDictionary:
                 continue
             out.append(Cover([Piece(src[k], start[k], end[k], cost[k]) for k in range(a, a + int(count[t]))], total[t], frames))
         return out
+
+    def _cover_checks(self, piece_penalty, what: str) -> float:
+        penalty = _cover_penalty(piece_penalty)
+        if not self.sounds:
+            raise EmptyDictionaryError(-2, "empty dictionary")
+        if getattr(self.engine, "metric", None) != "dtw":
+            raise SsymError(SSYM_E_UNSUPPORTED, what + " aligns with dtw: a refcos engine has no alignment")
+        return penalty
+
+    def cover_live(self, sounds: Sequence[Sound], piece_penalty: float = 0.0) -> "LiveCover":
+        """Cover Sounds that are still growing (fed with push_samples / push_sounds): a Coverer on this dictionary follows
+        the sounds' stream (ssym_coverer_*, DESIGN.md section 2 "Live cover"; dtw engines without a band).  The sounds must
+        be resident and share one stream, sound i in lane i -- what one push_sounds(sounds, ...) leaves -- ValueError
+        otherwise, before any device work.  LiveCover.poll() returns the pieces no longer recording can change,
+        flush() the rest; on f64 engines the pieces from first poll to flush are `cover`'s, bit for bit.  On f32 engines
+        `cover` rounds the targets' features to f32 first while the coverer reads the stream's f64 frames as they are (as
+        `watch` does), so the two can differ there.  The LiveCover keeps the dictionary's resident copy: close it before
+        the dictionary changes."""
+        penalty = self._cover_checks(piece_penalty, "cover_live")
+        sounds = list(sounds)
+        st = _shared_stream(sounds, "cover_live")
+        if self.engine is not st.engine:
+            raise ValueError("cover_live: the dictionary's engine must be the one that holds the sounds' stream")
+        if st.ncoeffs != self._dim():
+            raise ValueError("cover_live: the sounds' ncoeffs must be the dictionary's")
+        return LiveCover(sounds, st, self.engine.coverer(self.resident(), len(sounds), penalty), penalty)
+
+    def cover_long(self, target: Sound, piece_penalty: float = 0.0, block_frames: int = 4096) -> "Cover":
+        """`cover` for one target of any length: a one-lane Coverer is pushed the target's frames block_frames at a time
+        and flushed, so the tables never hold more than a block and the dictionary's horizon.  The Cover is `cover`'s, bit
+        for bit, where `cover` takes the target (on f32 engines the features are rounded to f32 first, as `cover` does)."""
+        penalty = self._cover_checks(piece_penalty, "cover_long")
+        if isinstance(target, (list, tuple)):
+            raise ValueError("cover_long takes one Sound")
+        block = int(block_frames)
+        if block < 1 or block != block_frames:
+            raise ValueError("block_frames must be a whole number of frames, at least 1")
+        rows = np.asarray(target.mfcc_arrays(), dtype=self.engine.np_dtype).astype(np.float64)
+        if rows.shape[1:] != (self._dim(),):
+            raise ValueError("cover_long: the target's ncoeffs must be the dictionary's")
+        frames = rows.shape[0]
+        cv = self.engine.coverer(self.resident(), 1, penalty)
+        try:
+            pieces = []
+
+            def take():
+                _, src, start, end, cost = cv.pieces()
+                pieces.extend(Piece(src[k], start[k], end[k], cost[k]) for k in range(src.size))
+            for at in range(0, frames, block):
+                if cv.push(rows[at:at + block]):
+                    take()
+            total = float(cv.best()[0][0])
+            if cv.flush(0):
+                take()
+        finally:
+            cv.close()
+        return Cover(pieces, total, frames) if np.isfinite(total) else Cover.none(frames)
 
     def reconstruct_covered(self, target: Sound, piece_penalty: float = 0.0, search: int = 0, want_pcm32: bool = False):
         """cover, cut, warp: the target is covered (ssym_dtw_cover), cut at the pieces (samples by

@@ -38,7 +38,10 @@
 //             candidates of a step are spread over the lanes (L ascending within a lane, strict <) and reduced by (v, L).
 //             Lane 0 then walks the back-pointers twice (count, then fill in ascending start) with plain stores.
 // No kernel waits on another workgroup: stream order is the only ordering between the three.
+// The coverer (dtw_coverer.hip, "Live cover") launches the forward pass and its fold through cover_forward below, on a buffer
+// of its own, and runs the chain's step (dtw_cover_chain.hpp) in a resumable kernel: one body each for both callers.
 #include "dtw_wave.hpp"
+#include "dtw_cover_chain.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -60,7 +63,7 @@ constexpr uint32_t kCoverGridY = 65535, kCoverGridZ = 65535;
 
 namespace {
 
-constexpr uint32_t kNone = 0xffffffffu;
+constexpr uint32_t kNone = kCoverNone;
 
 __device__ __forceinline__ uint64_t min64(uint64_t x, uint64_t y) { return x < y ? x : y; }
 
@@ -239,33 +242,9 @@ __global__ __launch_bounds__(64) void cover_chain_kernel(const ChainArgs a)
         double last = INF;                               // best(T-1); T = 0: no cover
         for (uint64_t e = 0; e < T; ++e) {
             const uint32_t lMax = (uint32_t)min64((uint64_t)a.width, e + 1);
-            double bestV = INF, bestM = INF;
-            uint32_t bestL = kNone, bestS = kNone;
-            for (uint32_t L = lane + 1; L <= lMax; L += 64) {
-                const size_t o = (size_t)(L - 1) * a.frames + g0 + (e + 1 - L);
-                const uint32_t src = a.tabSrc[o];
-                if (src == kNone)
-                    continue;
-                const double m = a.tabM[o];
-                const double v = __dadd_rn(__dadd_rn(m, a.penalty), ring[(e + 1 - L) & (kCoverRing - 1)]);
-                if (v < bestV) {                         // L ascends within a lane: the shorter piece stays
-                    bestV = v;
-                    bestM = m;
-                    bestL = L;
-                    bestS = src;
-                }
-            }
-#pragma unroll
-            for (int m = 32; m >= 1; m >>= 1) {
-                const double oV = __shfl_xor(bestV, m), oM = __shfl_xor(bestM, m);
-                const uint32_t oL = (uint32_t)__shfl_xor((int)bestL, m), oS = (uint32_t)__shfl_xor((int)bestS, m);
-                if (oV < bestV || (oV == bestV && oL < bestL)) {
-                    bestV = oV;
-                    bestM = oM;
-                    bestL = oL;
-                    bestS = oS;
-                }
-            }
+            const CoverPick pick = cover_chain_step(a.tabM, a.tabSrc, a.frames, g0 + e, lMax, a.penalty, ring, kCoverRing - 1, e, lane);
+            const double bestV = pick.v, bestM = pick.m;
+            const uint32_t bestL = pick.len, bestS = pick.src;
             if (lane == 0) {
                 ring[(e + 1) & (kCoverRing - 1)] = bestV;
                 a.bpLen[g0 + e] = bestL;
@@ -299,6 +278,13 @@ __global__ __launch_bounds__(64) void cover_chain_kernel(const ChainArgs a)
     }
 }
 
+}  // namespace
+
+CoverLimits cover_limits()
+{
+    return CoverLimits{kCoverMaxSourceFrames, kCoverMaxDim, kCoverRing, kCoverScratchBytes};
+}
+
 // what the call refuses of a context, every message once
 int32_t check_cover_ctx(ssym_ctx *ctx, const char *fn)
 {
@@ -312,6 +298,19 @@ int32_t check_cover_ctx(ssym_ctx *ctx, const char *fn)
     }
     return SSYM_OK;
 }
+
+// ... and of a dictionary
+int32_t check_cover_dict(ssym_ctx *ctx, const char *fn, const SegmentSet &src)
+{
+    if (src.max_frames > kCoverMaxSourceFrames || src.dim > kCoverMaxDim) {
+        ctx->err = std::string(fn) + ": a dictionary segment has more than " + std::to_string(kCoverMaxSourceFrames) +
+                   " frames, or frames have more than " + std::to_string(kCoverMaxDim) + " values";
+        return SSYM_E_UNSUPPORTED;
+    }
+    return SSYM_OK;
+}
+
+namespace {
 
 // starts per workgroup, columns per strip and LDS of a launch whose longest source has fmax frames: E and N [fmax][S]
 // and the c tile [fmax][S + JC].  64 starts where they fit with a strip of at least 8 columns, halved until they do;
@@ -338,6 +337,91 @@ CoverShape cover_shape(uint32_t fmax, uint32_t startsKnob, uint32_t stripKnob)
         JC = std::min(std::max(stripKnob, 1u), fit(kCoverLdsBytes));
     return CoverShape{S, JC, perCol * (3 * (size_t)S + JC)};
 }
+
+}  // namespace
+
+// The forward pass and its fold for nTgt targets (tgtRaw, tgtOff: DEVICE; hTgtOff: the same offsets on the HOST), enqueued
+// on the context's stream: the launch geometry of ssym_dtw_cover and of the coverer.  The tables of the source blocks go
+// into ctx->cover_tab, block 0's holding the folded result afterwards, with room for extraF64 doubles and extraU32 words
+// (the caller's back-pointers) in the same buffer.  The caller has checked that one block's tables and the extra room fit
+// kCoverScratchBytes.
+int32_t cover_forward(ssym_ctx *ctx, const SegmentSet &src, const double *tgtRaw, const uint64_t *tgtOff, const uint64_t *hTgtOff,
+                      uint32_t nTgt, uint64_t extraF64, uint64_t extraU32, CoverTables *out)
+{
+    const uint32_t N = src.n, M = nTgt;
+    const uint64_t F = hTgtOff[M] - hTgtOff[0];
+    const uint32_t width = 2 * std::max(src.max_frames, 1u);
+    const uint64_t tableBytes = F * width * (sizeof(double) + sizeof(uint32_t));      // one block's M and src
+    const uint64_t backBytes = extraF64 * sizeof(double) + extraU32 * sizeof(uint32_t);
+    hipStream_t st = ctx->stream;
+    uint64_t maxFrames = 0;
+    for (uint32_t t = 0; t < M; ++t)
+        maxFrames = std::max(maxFrames, hTgtOff[t + 1] - hTgtOff[t]);
+
+    // geometry.  The knobs (SSYM_TEST_HOOKS=1 only) are read at every launch; none changes a result.
+    uint32_t startsKnob = 0, stripKnob = 0, blockKnob = 0;
+    if (const char *k = ssym_knob("SSYM_COVER_STARTS"))
+        startsKnob = (uint32_t)std::max(1, atoi(k));
+    if (const char *k = ssym_knob("SSYM_COVER_STRIP"))
+        stripKnob = (uint32_t)std::max(1, atoi(k));
+    if (const char *k = ssym_knob("SSYM_COVER_BLOCK"))
+        blockKnob = (uint32_t)std::max(1, atoi(k));
+    const CoverShape shape = cover_shape(src.max_frames, startsKnob, stripKnob);
+    const uint64_t tiles = (maxFrames + shape.starts - 1) / shape.starts;
+    uint64_t tilesAll = 0;
+    for (uint32_t t = 0; t < M; ++t)
+        tilesAll += (hTgtOff[t + 1] - hTgtOff[t] + shape.starts - 1) / shape.starts;
+    // source blocks: enough workgroups to balance the device, as many tables as the scratch holds
+    const uint64_t wantBlocks = std::max<uint64_t>(1, ((uint64_t)ctx->num_cus * kCoverWorkgroupsPerCu + tilesAll) / (tilesAll + 1));
+    const uint64_t roomBlocks = tableBytes ? std::max<uint64_t>(1, (kCoverScratchBytes - backBytes) / tableBytes) : 1;
+    uint64_t nBlocks = std::min<uint64_t>({wantBlocks, roomBlocks, (uint64_t)kCoverGridY, (uint64_t)(N + kCoverBlockMin - 1) / kCoverBlockMin});
+    uint32_t blockSrc = (uint32_t)((N + nBlocks - 1) / std::max<uint64_t>(nBlocks, 1));
+    if (blockKnob)
+        blockSrc = std::max<uint32_t>(blockKnob, (uint32_t)((N + std::min<uint64_t>(roomBlocks, kCoverGridY) - 1) /
+                                                            std::min<uint64_t>(roomBlocks, kCoverGridY)));
+    nBlocks = (N + blockSrc - 1) / blockSrc;
+
+    const int32_t rc = ensure(ctx, ctx->cover_tab, (size_t)(nBlocks * tableBytes + backBytes) + 64);
+    if (rc != SSYM_OK)
+        return rc;
+    const uint64_t entries = F * width;
+    double *tabM = (double *)ctx->cover_tab.ptr;
+    double *moreF64 = tabM + nBlocks * entries;
+    uint32_t *tabSrc = (uint32_t *)(moreF64 + extraF64);
+    *out = CoverTables{tabM, tabSrc, moreF64, tabSrc + nBlocks * entries, width};
+    if (F) {
+        CoverArgs a{};
+        a.srcRaw = src.raw;
+        a.srcOff = src.off;
+        a.nSrc = N;
+        a.tgtRaw = tgtRaw;
+        a.tgtOff = tgtOff;
+        a.nTgt = M;
+        a.dim = src.dim;
+        a.squared = ctx->squared;
+        a.blockSrc = blockSrc;
+        a.starts = shape.starts;
+        a.strip = shape.strip;
+        a.width = width;
+        a.frames = F;
+        a.tabM = tabM;
+        a.tabSrc = tabSrc;
+        if (shape.lds > 64 * 1024)
+            SSYM_HIP_CHECK(ctx, hipFuncSetAttribute((const void *)cover_forward_kernel,
+                                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)shape.lds));
+        const dim3 grid((unsigned)tiles, (unsigned)nBlocks, std::min(M, kCoverGridZ));
+        const unsigned threads = (shape.starts + 63) / 64 * 64;
+        cover_forward_kernel<<<grid, threads, shape.lds, st>>>(a);
+        SSYM_HIP_CHECK(ctx, hipGetLastError());
+        if (nBlocks > 1) {
+            cover_fold_kernel<<<(unsigned)((entries + 255) / 256), 256, 0, st>>>(tabM, tabSrc, (uint32_t)nBlocks, entries);
+            SSYM_HIP_CHECK(ctx, hipGetLastError());
+        }
+    }
+    return SSYM_OK;
+}
+
+namespace {
 
 int32_t dtw_cover(ssym_ctx *ctx, const ssym_dict *dict, const ssym_queries *q, double piece_penalty, uint32_t flags,
                   uint32_t *out_count, double *out_total, uint32_t *out_src, uint32_t *out_start, uint32_t *out_end,
@@ -374,11 +458,9 @@ int32_t dtw_cover(ssym_ctx *ctx, const ssym_dict *dict, const ssym_queries *q, d
         ctx->err = std::string(fn) + ": out_count, out_total, out_src, out_start, out_end and out_cost must not be NULL";
         return SSYM_E_INVALID;
     }
-    if (src.max_frames > kCoverMaxSourceFrames || src.dim > kCoverMaxDim) {
-        ctx->err = std::string(fn) + ": a dictionary segment has more than " + std::to_string(kCoverMaxSourceFrames) +
-                   " frames, or frames have more than " + std::to_string(kCoverMaxDim) + " values";
-        return SSYM_E_UNSUPPORTED;
-    }
+    rc = check_cover_dict(ctx, fn, src);
+    if (rc != SSYM_OK)
+        return rc;
     const uint32_t width = 2 * std::max(src.max_frames, 1u);
     const uint64_t tableBytes = F * width * (sizeof(double) + sizeof(uint32_t));      // one block's M and src
     const uint64_t backBytes = F * (sizeof(double) + 2 * sizeof(uint32_t));
@@ -390,39 +472,7 @@ int32_t dtw_cover(ssym_ctx *ctx, const ssym_dict *dict, const ssym_queries *q, d
     SSYM_HIP_CHECK(ctx, hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
 
-    // geometry.  The knobs (SSYM_TEST_HOOKS=1 only) are read at every launch; none changes a result.
-    uint32_t startsKnob = 0, stripKnob = 0, blockKnob = 0;
-    if (const char *k = ssym_knob("SSYM_COVER_STARTS"))
-        startsKnob = (uint32_t)std::max(1, atoi(k));
-    if (const char *k = ssym_knob("SSYM_COVER_STRIP"))
-        stripKnob = (uint32_t)std::max(1, atoi(k));
-    if (const char *k = ssym_knob("SSYM_COVER_BLOCK"))
-        blockKnob = (uint32_t)std::max(1, atoi(k));
-    const CoverShape shape = cover_shape(src.max_frames, startsKnob, stripKnob);
-    const uint64_t tiles = (tgt.max_frames + shape.starts - 1) / shape.starts;
-    uint64_t tilesAll = 0;
-    for (uint32_t t = 0; t < M; ++t)
-        tilesAll += (tgt.h_off[t + 1] - tgt.h_off[t] + shape.starts - 1) / shape.starts;
-    // source blocks: enough workgroups to balance the device, as many tables as the scratch holds
-    const uint64_t wantBlocks = std::max<uint64_t>(1, ((uint64_t)ctx->num_cus * kCoverWorkgroupsPerCu + tilesAll) / (tilesAll + 1));
-    const uint64_t roomBlocks = tableBytes ? std::max<uint64_t>(1, (kCoverScratchBytes - backBytes) / tableBytes) : 1;
-    uint64_t nBlocks = std::min<uint64_t>({wantBlocks, roomBlocks, (uint64_t)kCoverGridY, (uint64_t)(N + kCoverBlockMin - 1) / kCoverBlockMin});
-    uint32_t blockSrc = (uint32_t)((N + nBlocks - 1) / std::max<uint64_t>(nBlocks, 1));
-    if (blockKnob)
-        blockSrc = std::max<uint32_t>(blockKnob, (uint32_t)((N + std::min<uint64_t>(roomBlocks, kCoverGridY) - 1) /
-                                                            std::min<uint64_t>(roomBlocks, kCoverGridY)));
-    nBlocks = (N + blockSrc - 1) / blockSrc;
-
     Blocks bl(ctx);
-    rc = ensure(ctx, ctx->cover_tab, (size_t)(nBlocks * tableBytes + backBytes) + 64);
-    if (rc != SSYM_OK)
-        return rc;
-    const uint64_t entries = F * width;
-    double *tabM = (double *)ctx->cover_tab.ptr;
-    double *bpCost = tabM + nBlocks * entries;
-    uint32_t *tabSrc = (uint32_t *)(bpCost + F);
-    uint32_t *bpLen = tabSrc + nBlocks * entries, *bpSrc = bpLen + F;
-
     // outputs: the caller's device arrays in place, or one f64 and one u32 block copied back after the chain
     const bool inPlace = (flags & SSYM_OUT_DEVICE) != 0;
     double *dF64 = nullptr;
@@ -451,35 +501,12 @@ int32_t dtw_cover(ssym_ctx *ctx, const ssym_dict *dict, const ssym_queries *q, d
 
     hipEvent_t *ev = ctx->ev;
     SSYM_HIP_CHECK(ctx, hipEventRecord(ev[0], st));
-    if (F) {
-        CoverArgs a{};
-        a.srcRaw = src.raw;
-        a.srcOff = src.off;
-        a.nSrc = N;
-        a.tgtRaw = tgt.raw;
-        a.tgtOff = tgt.off;
-        a.nTgt = M;
-        a.dim = src.dim;
-        a.squared = ctx->squared;
-        a.blockSrc = blockSrc;
-        a.starts = shape.starts;
-        a.strip = shape.strip;
-        a.width = width;
-        a.frames = F;
-        a.tabM = tabM;
-        a.tabSrc = tabSrc;
-        if (shape.lds > 64 * 1024)
-            SSYM_HIP_CHECK(ctx, hipFuncSetAttribute((const void *)cover_forward_kernel,
-                                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)shape.lds));
-        const dim3 grid((unsigned)tiles, (unsigned)nBlocks, std::min(M, kCoverGridZ));
-        const unsigned threads = (shape.starts + 63) / 64 * 64;
-        cover_forward_kernel<<<grid, threads, shape.lds, st>>>(a);
-        SSYM_HIP_CHECK(ctx, hipGetLastError());
-        if (nBlocks > 1) {
-            cover_fold_kernel<<<(unsigned)((entries + 255) / 256), 256, 0, st>>>(tabM, tabSrc, (uint32_t)nBlocks, entries);
-            SSYM_HIP_CHECK(ctx, hipGetLastError());
-        }
-    }
+    CoverTables tab{};
+    rc = cover_forward(ctx, src, tgt.raw, tgt.off, tgt.h_off.data(), M, F, 2 * F, &tab);       // + the back-pointers
+    if (rc != SSYM_OK)
+        return rc;
+    double *tabM = tab.tabM, *bpCost = tab.moreF64;
+    uint32_t *tabSrc = tab.tabSrc, *bpLen = tab.moreU32, *bpSrc = bpLen + F;
     SSYM_HIP_CHECK(ctx, hipEventRecord(ev[1], st));
     c.tabM = tabM;
     c.tabSrc = tabSrc;

@@ -451,6 +451,24 @@ int32_t match_paced(ssym_ctx *ctx, const ssym_dict *dict, const ssym_queries *q,
                     uint32_t *out_idx, double *out_cost, uint32_t flags, const char *fn);
 int32_t pair_matrix_paced(ssym_ctx *ctx, const ssym_dict *dict, const ssym_queries *q, double *out_matrix, const char *fn);
 
+// dtw_cover.hip: what the cover shares with the coverer (dtw_coverer.hip) -- the limits, the refusals and the forward pass
+struct CoverLimits {
+    uint32_t max_source_frames, max_dim, ring;      // ring: best(e) of the chain lives at (e + 1) mod ring, a power of two
+    uint64_t scratch_bytes;
+};
+CoverLimits cover_limits();
+int32_t check_cover_ctx(ssym_ctx *ctx, const char *fn);
+int32_t check_cover_dict(ssym_ctx *ctx, const char *fn, const SegmentSet &src);
+struct CoverTables {
+    double *tabM;                // [width][frames] after the fold
+    uint32_t *tabSrc;
+    double *moreF64;             // the extra room asked for
+    uint32_t *moreU32;
+    uint32_t width;              // 2 max(Fmax, 1)
+};
+int32_t cover_forward(ssym_ctx *ctx, const SegmentSet &src, const double *tgtRaw, const uint64_t *tgtOff, const uint64_t *hTgtOff,
+                      uint32_t nTgt, uint64_t extraF64, uint64_t extraU32, CoverTables *out);
+
 // chain.hip
 int32_t launch_chain_argmin(ssym_ctx *ctx, const double *base, size_t row_stride, const uint32_t *row_sel,
                             uint32_t n, double distance, double init, bool report_value, uint32_t step,

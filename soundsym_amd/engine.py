@@ -540,6 +540,107 @@ class Spotter:
             pass
 
 
+class Coverer:
+    """`n_lanes` growing targets tiled by the segments of one resident dictionary (ssym_coverer; definition in
+    include/soundsym_amd.h and DESIGN.md section 2 "Live cover"): every piece is reported by the push after which no
+    longer recording could change it, the pieces from reset to flush are ssym_dtw_cover's for the whole, and `best` gives
+    ssym_dtw_cover's total for everything consumed so far.  The coverer reads the dictionary's resident features for as
+    long as it lives: it keeps `d` alive and must be closed before it."""
+
+    def __init__(self, engine: "Engine", ptr: int, d: _Handle, n_lanes: int, piece_penalty: float):
+        self.engine, self.ptr, self.d, self.n_lanes, self.dim = engine, ptr, d, n_lanes, d.dim
+        self.piece_penalty = piece_penalty
+        self.n_pieces = 0
+
+    def _lane(self, lane) -> int:
+        if not 0 <= int(lane) < self.n_lanes:
+            raise ValueError(f"lane {lane} outside 0..{self.n_lanes - 1}")
+        return int(lane)
+
+    def push(self, feats, frame_offsets=None) -> int:
+        """ssym_coverer_push: lane l consumes the frames feats[frame_offsets[l]:frame_offsets[l+1]] ([frames][dim]; a
+        one-lane coverer takes the bare block).  Returns the number of pieces the push committed (`pieces` reads them)."""
+        x = np.ascontiguousarray(feats, dtype=np.float64).reshape(-1)
+        if x.size % self.dim:
+            raise ValueError(f"feats must hold whole frames of {self.dim} values")
+        if frame_offsets is None:
+            if self.n_lanes != 1:
+                raise ValueError("push: a coverer of several lanes needs frame_offsets")
+            frame_offsets = [0, x.size // self.dim]
+        off = np.ascontiguousarray(frame_offsets, dtype=np.uint64).reshape(-1)
+        if off.size != self.n_lanes + 1 or np.any(np.diff(off.astype(np.int64)) < 0) or int(off[-1]) * self.dim > x.size:
+            raise ValueError("frame_offsets: n_lanes + 1 non-decreasing frame offsets within `feats`")
+        n = ctypes.c_uint64()
+        nat.check(nat.lib().ssym_coverer_push(self.engine.ctx, self.ptr, x.ctypes.data if x.size else None, off.ctypes.data,
+                                              0, ctypes.byref(n)), self.engine.ctx)
+        self.n_pieces = int(n.value)
+        return self.n_pieces
+
+    def follow(self, stream: "Stream") -> int:
+        """ssym_coverer_follow: every lane consumes, device to device, the frames the stream's lane holds beyond those
+        consumed (a lane that has ended is skipped).  Returns as push."""
+        if stream.n_lanes != self.n_lanes or stream.ncoeffs != self.dim:
+            raise ValueError("follow: the stream's lanes and ncoeffs must be the coverer's lanes and dim")
+        n = ctypes.c_uint64()
+        nat.check(nat.lib().ssym_coverer_follow(self.engine.ctx, self.ptr, stream.ptr, 0, ctypes.byref(n)), self.engine.ctx)
+        self.n_pieces = int(n.value)
+        return self.n_pieces
+
+    def pieces(self, on_device: bool = False):
+        """The pieces of the last push / follow / flush, ordered by (lane, start): (lane uint32 [n], src uint32 [n], start
+        uint32 [n], end uint32 [n], cost f64 [n]); start / end count the lane's frames since its reset, end inclusive.
+        on_device: SSYM_OUT_DEVICE, the five arrays as torch tensors in device memory."""
+        n = self.n_pieces
+        device = self.engine.device if on_device else None
+        (lane, pl), (src, ps), (start, pa), (end, pe), (cost, pc) = (
+            _output(device, (n,), t) for t in (np.uint32, np.uint32, np.uint32, np.uint32, np.float64))
+        if n:
+            nat.check(nat.lib().ssym_coverer_pieces(self.engine.ctx, self.ptr, pl, ps, pa, pe, pc,
+                                                    0 if device is None else nat.OUT_DEVICE), self.engine.ctx)
+        return lane, src, start, end, cost
+
+    def flush(self, lane: int = 0) -> int:
+        """ssym_coverer_flush: "the lane has ended" -- the rest of its cover is emitted, and the lane consumes nothing more
+        until `reset`.  Returns the number of pieces."""
+        n = ctypes.c_uint64()
+        nat.check(nat.lib().ssym_coverer_flush(self.engine.ctx, self.ptr, self._lane(lane), ctypes.byref(n)), self.engine.ctx)
+        self.n_pieces = int(n.value)
+        return self.n_pieces
+
+    def best(self, on_device: bool = False):
+        """(total f64, covered uint32, committed uint32), each [n_lanes]: ssym_dtw_cover's total for what the lane has
+        consumed so far (+inf without a cover), the frames of the longest prefix that has a cover, and the frames whose
+        pieces have been emitted."""
+        device = self.engine.device if on_device else None
+        (total, pt), (covered, pc), (committed, pm) = (_output(device, (self.n_lanes,), t)
+                                                      for t in (np.float64, np.uint32, np.uint32))
+        nat.check(nat.lib().ssym_coverer_best(self.engine.ctx, self.ptr, pt, pc, pm, 0 if device is None else nat.OUT_DEVICE),
+                  self.engine.ctx)
+        return total, covered, committed
+
+    def counts(self):
+        """(frames consumed per lane [n_lanes] u64, capacity of the back-pointer ring in frames)."""
+        out = np.zeros(self.n_lanes, dtype=np.uint64)
+        cap = ctypes.c_uint64()
+        nat.check(nat.lib().ssym_coverer_counts(self.ptr, out.ctypes.data, ctypes.byref(cap)), self.engine.ctx)
+        return out, int(cap.value)
+
+    def reset(self, lane: int = 0) -> None:
+        """One lane back to "nothing consumed"."""
+        nat.check(nat.lib().ssym_coverer_reset(self.engine.ctx, self.ptr, self._lane(lane)), self.engine.ctx)
+
+    def close(self):
+        if self.ptr and self.engine.ctx:
+            nat.lib().ssym_coverer_destroy(self.engine.ctx, self.ptr)
+        self.ptr = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class Comm:
     """One rank of a source-sharded run: an RCCL communicator bound to an Engine (ssym_comm)."""
 
@@ -1130,6 +1231,17 @@ class Engine:
             rc = nat.lib().ssym_spotter_create_step(*head, which, ctypes.byref(out))
         nat.check(rc, self.ctx)
         return Spotter(self, out.value, q, lanes, step)
+
+    def coverer(self, d: _Handle, n_lanes: int = 1, piece_penalty: float = 0.0) -> Coverer:
+        """ssym_coverer_create: `n_lanes` growing targets covered live by the segments of `d` (dtw engines without a
+        band; "Live cover").  piece_penalty >= 0 is added per piece, as for dtw_cover."""
+        penalty = _cover_penalty(piece_penalty)
+        lanes = int(n_lanes)
+        if lanes < 1:
+            raise ValueError("n_lanes must be at least 1")
+        out = ctypes.c_void_p()
+        nat.check(nat.lib().ssym_coverer_create(self.ctx, d.ptr, lanes, penalty, ctypes.byref(out)), self.ctx)
+        return Coverer(self, out.value, d, lanes, penalty)
 
     @staticmethod
     def mfcc_num_frames(n_samples: int, pad_tail: bool = False) -> int:
