@@ -92,21 +92,31 @@ def check_matrix(sets, want):
     rc, mat, untouched = matrix(sets)
     assert rc == nat.SSYM_OK, error(sets)
     assert untouched
-    bad = [(s, t, mat[s, t], want[s, t]) for s in range(want.shape[0]) for t in range(want.shape[1])
-           if not same_bits(mat[s, t], want[s, t])]
-    assert not bad, bad[:5]
+    want = np.asarray(want, dtype=np.float64)
+    assert mat.shape == want.shape
+    # same_bits entry by entry, on the whole matrix at once (a matrix may have half a million entries)
+    differ = ~((bits(mat) == bits(want)) | (np.isnan(mat) & np.isnan(want)))
+    bad = [(int(s), int(t), mat[s, t], want[s, t]) for s, t in np.argwhere(differ)[:5]]
+    assert not bad, bad
     return mat
 
 
-def check_match(sets, want, distance=None, base=0, **kw):
-    """The call against the restatement's fold of `want` (the restatement's matrix)."""
+def _first(a, b):
+    """The first entries at which two arrays differ, for a message that stays readable with 65 600 targets."""
+    at = np.flatnonzero(~((a == b) | ((a != a) & (b != b))))[:5]
+    return at.tolist(), a[at].tolist(), b[at].tolist()
+
+
+def check_match(sets, want, distance=None, base=0, folded=None, **kw):
+    """The call against the restatement's fold of `want` (the restatement's matrix).  folded: that fold, (idx, cost) of
+    ref.fold(want, distance, base), where the caller has it already (a fold is a plain loop over every pair)."""
     rc, idx, cost, untouched = match(sets, distance, base, **kw)
     assert rc == nat.SSYM_OK, error(sets)
     assert untouched
-    widx, wcost = ref.fold(want, distance, base)
-    assert np.array_equal(idx, widx), (idx.tolist(), widx.tolist())
+    widx, wcost = ref.fold(want, distance, base) if folded is None else folded
+    assert np.array_equal(idx, widx), _first(idx, widx)
     if kw.get("want_cost", True):
-        assert same_bits(cost, wcost), (cost.tolist(), wcost.tolist())
+        assert same_bits(cost, wcost), _first(cost, wcost)
     else:
         assert (cost == SENTF).all()
     return idx, cost
