@@ -47,6 +47,7 @@ pub const SSYM_PITCH_VOICED: u32 = 16;
 pub const SSYM_PITCH_WINDOW: u64 = 2048;
 pub const SSYM_PITCH_HOP: u64 = 1024;
 pub const SSYM_NO_MATCH: u32 = 0xffff_ffff;
+pub const SSYM_COVER_GAP: u32 = 0xffff_fffe;
 pub const SSYM_COMM_ID_BYTES: usize = 128;
 
 #[repr(C)]
@@ -180,6 +181,11 @@ extern "C" {
     pub fn ssym_dtw_cover(ctx: *mut SsymCtx, dict: *const SsymDict, q: *const SsymQueries, piece_penalty: f64, flags: u32,
                           out_count: *mut u32, out_total: *mut f64, out_src: *mut u32, out_start: *mut u32,
                           out_end: *mut u32, out_cost: *mut f64) -> i32;
+    // ... with target frames left uncovered at gap_cost per frame ("Cover with gaps"): a gap frame is the piece
+    // (SSYM_COVER_GAP = 0xFFFFFFFE, e, e, gap_cost), one slot per frame; gap_cost = +inf is ssym_dtw_cover
+    pub fn ssym_dtw_cover_gaps(ctx: *mut SsymCtx, dict: *const SsymDict, q: *const SsymQueries, piece_penalty: f64,
+                               gap_cost: f64, flags: u32, out_count: *mut u32, out_total: *mut f64, out_src: *mut u32,
+                               out_start: *mut u32, out_end: *mut u32, out_cost: *mut f64) -> i32;
 
     // source-sharded runs, exchange done by the caller (device pointers): filter / all-reduce(MIN) / finish / merge
     pub fn ssym_match_begin(ctx: *mut SsymCtx, dict: *const SsymDict, q: *const SsymQueries, distance: *const f64,
@@ -326,6 +332,9 @@ extern "C" {
     // piece reported by the push after which no longer recording could change it; the dictionary must outlive the coverer
     pub fn ssym_coverer_create(ctx: *mut SsymCtx, dict: *const SsymDict, n_lanes: u32, piece_penalty: f64,
                                out: *mut *mut SsymCoverer) -> i32;
+    // ... with gaps: a NaN or +-inf frame becomes a gap frame and the lane goes on; every other call works on it unchanged
+    pub fn ssym_coverer_create_gaps(ctx: *mut SsymCtx, dict: *const SsymDict, n_lanes: u32, piece_penalty: f64, gap_cost: f64,
+                                    out: *mut *mut SsymCoverer) -> i32;
     pub fn ssym_coverer_destroy(ctx: *mut SsymCtx, cv: *mut SsymCoverer) -> i32;
     pub fn ssym_coverer_push(ctx: *mut SsymCtx, cv: *mut SsymCoverer, feats: *const f64, frame_offsets: *const u64,
                              flags: u32, out_n_pieces: *mut u64) -> i32;

@@ -2,7 +2,7 @@
 """examples/cover.py -- a reconstruction whose target is cut by the dictionary itself.
 
     python examples/cover.py -s TARGET.wav -d DICT.wav|DIR -o OUT.wav [--penalty 0] [--search 256] [--depth 5] [--threshold 4]
-                             [--seed 0]
+                             [--seed 0] [--gap-cost X] [--gap-fill silence|target]
 
 The dictionary is a folder of sounds (SoundDictionary.from_path) or one recording cut by a Partitioner trained on it, as
 examples/reconstruction.py --partition cuts it.  The target is NOT cut beforehand: SoundDictionary.reconstruct_covered tiles
@@ -10,7 +10,9 @@ it with dictionary sounds, cut points and sounds chosen together on the GPU so t
 sum to the least total (ssym_dtw_cover), then warps every piece from its sound along its paced alignment (the existing
 align and warp calls).  --penalty X adds X per piece and trades total fit for fewer, longer pieces.  --search N (at most 512
 samples) resynthesises with the waveform-similarity search.  One line per piece: source, frames, cost per frame.  Sounds of
-more than 128 frames are left out of the dictionary: a cover takes none longer.
+more than 128 frames are left out of the dictionary: a cover takes none longer.  --gap-cost X lets frames stay uncovered at X
+each (ssym_dtw_cover_gaps): a stretch that no sound fits better than X per frame -- breath, a door, a frame that is not
+finite -- is left out and comes back as silence, or as the target's own samples with --gap-fill target; one line per gap.
 """
 import argparse
 import os
@@ -34,6 +36,8 @@ def main(argv=None):
     ap.add_argument("--depth", type=int, default=5)
     ap.add_argument("--threshold", type=int, default=4)
     ap.add_argument("--seed", type=int, default=0, help="draws the mixture's starting frames")
+    ap.add_argument("--gap-cost", type=float, default=None, help="price per frame left uncovered (default: no gaps)")
+    ap.add_argument("--gap-fill", choices=("silence", "target"), default="silence", help="what a gap sounds like")
     args = ap.parse_args(argv)
 
     engine = Engine(metric="dtw", dtype="f64")
@@ -46,14 +50,21 @@ def main(argv=None):
     dictionary.sounds = [s for s in dictionary.sounds if 0 < s.num_frames() <= MAX_FRAMES]
     target = Sound.from_path(args.s, engine=engine)
 
-    cover, samples, pcm = dictionary.reconstruct_covered(target, args.penalty, search=args.search, want_pcm32=True)
+    cover, samples, pcm = dictionary.reconstruct_covered(target, args.penalty, search=args.search, want_pcm32=True,
+                                                         gap_cost=args.gap_cost, gap_fill=args.gap_fill)
     for p in cover.pieces:
+        if p.is_gap:
+            print(f"{'(gap)':>16}  frames {p.start_frame:6d} ... {p.end_frame:6d}  ({p.num_frames():3d} left uncovered)      "
+                  f"{p.cost_per_frame:.4f} per frame")
+            continue
         name = dictionary.sounds[p.source_index].name or "#%d" % p.source_index
         print(f"{name:>16}  frames {p.start_frame:6d} ... {p.end_frame:6d}  ({p.num_frames():3d} of the sound's "
               f"{dictionary.sounds[p.source_index].num_frames():3d})  {p.cost_per_frame:.4f} per frame")
     if cover:
-        print(f"{len(cover)} pieces over {cover.num_frames} frames from {len(dictionary.sounds)} dictionary sounds, "
+        print(f"{len(cover.sounding)} pieces over {cover.num_frames} frames from {len(dictionary.sounds)} dictionary sounds, "
               f"{cover.total_per_frame:.4f} per frame")
+        if args.gap_cost is not None:
+            print(f"{len(cover.gaps)} gaps leave {cover.num_frames - cover.covered_frames} frames uncovered")
     else:
         print("no cover (a frame that is not finite, or a stretch no dictionary sound can pace): the length-fitted match instead")
     write_wav32(args.o, sample_rate=target.sample_rate(), pcm=pcm)

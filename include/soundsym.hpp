@@ -456,6 +456,19 @@ class SoundDictionary {
     };
     std::vector<Cover> cover(const std::vector<ArcSound> &targets, double piece_penalty = 0.0) const
     {
+        return cover_call(targets, piece_penalty, nullptr);
+    }
+    // ... with target frames left uncovered at gap_cost per frame (ssym_dtw_cover_gaps; soundsym_amd.h "Cover with gaps";
+    // gap_cost >= 0, +inf: no gaps).  A maximal run of gap frames is one entry of pieces with source_index = SSYM_COVER_GAP,
+    // its frames start_frame ... end_frame and cost = gap_cost x its frames; total is the call's.  With a finite gap_cost
+    // every target with a frame has a cover
+    std::vector<Cover> cover(const std::vector<ArcSound> &targets, double piece_penalty, double gap_cost) const
+    {
+        return cover_call(targets, piece_penalty, &gap_cost);
+    }
+    // the body of both: gap_cost NULL is ssym_dtw_cover
+    std::vector<Cover> cover_call(const std::vector<ArcSound> &targets, double piece_penalty, const double *gap_cost) const
+    {
         if (sounds.empty())
             throw EmptyDictionary();
         if (targets.empty())
@@ -469,16 +482,25 @@ class SoundDictionary {
         const size_t frames = (size_t)(off[n] - off[0]), room = frames ? frames : 1;      // (no NULL of an empty vector)
         std::vector<uint32_t> count(n), src(room), start(room), end(room);
         std::vector<double> total(n), cost(room);
-        const int32_t rc = ssym_dtw_cover(ctx_->get(), resident(), q, piece_penalty, 0, count.data(), total.data(), src.data(),
-                                          start.data(), end.data(), cost.data());
+        const int32_t rc = gap_cost ? ssym_dtw_cover_gaps(ctx_->get(), resident(), q, piece_penalty, *gap_cost, 0, count.data(),
+                                                          total.data(), src.data(), start.data(), end.data(), cost.data())
+                                    : ssym_dtw_cover(ctx_->get(), resident(), q, piece_penalty, 0, count.data(), total.data(),
+                                                     src.data(), start.data(), end.data(), cost.data());
         ssym_queries_destroy(ctx_->get(), q);
         ctx_->check(rc);
         std::vector<Cover> out(n);
         for (uint32_t t = 0; t < n; ++t) {
             out[t].total = total[t];
             const size_t at = (size_t)(off[t] - off[0]);
-            for (uint32_t k = 0; k < count[t]; ++k)
-                out[t].pieces.push_back(Spot{src[at + k], start[at + k], end[at + k], cost[at + k]});
+            for (uint32_t k = 0; k < count[t]; ++k) {
+                std::vector<Spot> &ps = out[t].pieces;
+                if (src[at + k] == SSYM_COVER_GAP && !ps.empty() && ps.back().source_index == SSYM_COVER_GAP) {
+                    ps.back().end_frame = end[at + k];                       // a run of gap frames is one entry
+                    ps.back().cost = *gap_cost * (double)(ps.back().end_frame - ps.back().start_frame + 1);
+                } else {
+                    ps.push_back(Spot{src[at + k], start[at + k], end[at + k], cost[at + k]});
+                }
+            }
         }
         return out;
     }

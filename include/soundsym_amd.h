@@ -544,6 +544,28 @@ SSYM_API int32_t ssym_dtw_cover(ssym_ctx *ctx, const ssym_dict *dict, const ssym
                                 uint32_t flags, uint32_t *out_count, double *out_total, uint32_t *out_src,
                                 uint32_t *out_start, uint32_t *out_end, double *out_cost);
 
+/* Cover with gaps (DESIGN.md section 2 "Cover with gaps" and section 5.23): the cover, with target frames left uncovered at
+ * gap_cost per frame.  Everything of "Cover" above holds word for word: c, w, M, src, the scan over L, best(-1) = 0.  One
+ * candidate is added to each step:
+ *   best(e)   : the scan of "Cover" gives (v, L, src, M) or (+inf, none)
+ *               vg = gap_cost + best(e-1)
+ *               if vg < v (strict):  best(e) = vg, back-pointer (L = 1, src = SSYM_COVER_GAP, M = gap_cost)
+ *   cover     : walk back as before; a gap frame is the piece (SSYM_COVER_GAP, start = e, end = e, cost = gap_cost)
+ *   total     : acc = 0; a piece: acc = (cost + piece_penalty) + acc; a gap frame: acc = gap_cost + acc  -> total's bits
+ * A gap is reported FRAME BY FRAME, one slot each (so a cover still never has more pieces than frames); piece_penalty is not
+ * charged on a gap frame; a piece wins a tie against a gap.  So: (1) the pieces and gap frames tile [0, T); (2) a piece's
+ * cost is still the paced alignment's for the cut, bit for bit; (3) the re-summation above gives total; (4) total is the
+ * least such sum over every tiling with gaps; (5) with a finite gap_cost every target of T >= 1 frames has a cover: a NaN or
+ * +-inf target frame is a gap frame, and the frames on both sides of it are covered; (6) gap_cost = +inf never wins: the six
+ * outputs are ssym_dtw_cover's, bit for bit; (7) no read leaves its buffer.
+ *   gap_cost    >= 0 and finite, or +inf: the price per frame, comparable with a piece's cost per frame
+ * Outputs, flags, limits, refusals, scratch and timings are ssym_dtw_cover's.  A NaN, negative or -inf gap_cost:
+ * SSYM_E_INVALID before any device work, with the outputs unwritten. */
+#define SSYM_COVER_GAP 0xFFFFFFFEu
+SSYM_API int32_t ssym_dtw_cover_gaps(ssym_ctx *ctx, const ssym_dict *dict, const ssym_queries *q, double piece_penalty,
+                                     double gap_cost, uint32_t flags, uint32_t *out_count, double *out_total,
+                                     uint32_t *out_src, uint32_t *out_start, uint32_t *out_end, double *out_cost);
+
 /* Source-sharded multi-GPU, dtw metric: the one real exchange the path has.  Each rank's filter gives,
  * per target, an upper bound on the best key in ITS shard; a rank whose shard does not hold a
  * target's neighbour would otherwise re-score ~10^2 of its own pairs per target for nothing.
@@ -1151,9 +1173,19 @@ SSYM_API int32_t ssym_spotter_create_step(ssym_ctx *ctx, const ssym_queries *q, 
  * The tables of one call are lanes x (W - 1 + new frames) x W x 12 bytes per source block; a push that would pass the
  * cover's 512 MiB runs as several slices of frames in the same call, with a commit after each and the same results.  One
  * synchronisation per slice.  ssym_get_timings afterwards: main_ms = the forward pass (gather and fold included),
- * reduce_ms = chain, commit and emission, n_pairs = n_sources x the frames the call consumed. */
+ * reduce_ms = chain, commit and emission, n_pairs = n_sources x the frames the call consumed.
+ *
+ * ssym_coverer_create_gaps: a coverer whose chain takes the gap candidate of "Cover with gaps" at gap_cost per frame (>= 0 and
+ *   finite, or +inf, which is ssym_coverer_create; NaN, negative or -inf: SSYM_E_INVALID).  Every other ssym_coverer_* call
+ *   works on it unchanged; "ssym_dtw_cover" above then reads "ssym_dtw_cover_gaps with the same gap_cost".  A gap frame is a
+ *   piece of one frame and 1 <= W, so the horizon argument holds as it stands and (1) to (5) and (7) hold with gaps;
+ *   ssym_coverer_pieces reports a gap frame as (lane, SSYM_COVER_GAP, e, e, gap_cost).  With a finite gap_cost every best(e)
+ *   is finite, so lastFinite = n - 1 and covered = n, and (6) is replaced by: a NaN or +-inf frame becomes a gap frame and
+ *   the lane goes on; other lanes are untouched. */
 SSYM_API int32_t ssym_coverer_create(ssym_ctx *ctx, const ssym_dict *dict, uint32_t n_lanes, double piece_penalty,
                                      ssym_coverer **out);
+SSYM_API int32_t ssym_coverer_create_gaps(ssym_ctx *ctx, const ssym_dict *dict, uint32_t n_lanes, double piece_penalty,
+                                          double gap_cost, ssym_coverer **out);
 SSYM_API int32_t ssym_coverer_destroy(ssym_ctx *ctx, ssym_coverer *cv);
 SSYM_API int32_t ssym_coverer_push(ssym_ctx *ctx, ssym_coverer *cv, const double *feats, const uint64_t *frame_offsets,
                                    uint32_t flags, uint64_t *out_n_pieces);

@@ -16,6 +16,7 @@ from .api import (  # noqa: F401
     Alignment,
     BIN,
     Cover,
+    Gap,
     HOP,
     LiveCover,
     NCLUSTERS,
@@ -39,7 +40,7 @@ from .api import (  # noqa: F401
 )
 
 __all__ = [
-    "ABI_SYMBOLS", "Alignment", "BIN", "Cover", "Coverer", "DeviceFrames", "EmptyDictionaryError", "Engine", "Gmm", "HOP", "LIB_PATH", "LiveCover", "NCLUSTERS", "NCOEFFS",
+    "ABI_SYMBOLS", "Alignment", "BIN", "Cover", "Coverer", "DeviceFrames", "EmptyDictionaryError", "Engine", "Gap", "Gmm", "HOP", "LIB_PATH", "LiveCover", "NCLUSTERS", "NCOEFFS",
     "Partitioner", "Piece", "Sound", "SoundDictionary", "SoundSequence", "Spot", "SsymError", "analyze_mfccs", "analyze_sounds", "build",
     "cosine_sim_angular", "discretize",
     "discretize_with_model", "length_fit", "pack_segments", "push_sounds", "Spotter", "Stream", "stream_plan", "train_model", "Watch", "watch",

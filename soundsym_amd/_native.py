@@ -63,10 +63,10 @@ ABI_SYMBOLS = [
     "ssym_dtw_spot_step", "ssym_spot_queries_step", "ssym_dtw_spot_all_step",
     "ssym_dtw_align_step",
     "ssym_match_queries_step", "ssym_pair_matrix_step",
-    "ssym_dtw_cover",
+    "ssym_dtw_cover", "ssym_dtw_cover_gaps",
     "ssym_spotter_create_step",
     "ssym_coverer_create", "ssym_coverer_destroy", "ssym_coverer_push", "ssym_coverer_follow", "ssym_coverer_pieces",
-    "ssym_coverer_flush", "ssym_coverer_best", "ssym_coverer_counts", "ssym_coverer_reset",
+    "ssym_coverer_flush", "ssym_coverer_best", "ssym_coverer_counts", "ssym_coverer_reset", "ssym_coverer_create_gaps",
     "ssym_reconstruct_warped", "ssym_reconstruct_wsola",
     "ssym_dtw_align_spans_sizes", "ssym_dtw_align_spans", "ssym_reconstruct_warped_spans", "ssym_reconstruct_wsola_spans",
 ]
@@ -74,6 +74,7 @@ COMM_ID_BYTES = 128        # SSYM_COMM_ID_BYTES
 
 
 NO_MATCH = 0xFFFFFFFF      # SSYM_NO_MATCH
+COVER_GAP = 0xFFFFFFFE     # SSYM_COVER_GAP
 MFCC_PAD_TAIL = 4           # SSYM_MFCC_PAD_TAIL
 TOPK_MAX = 64              # SSYM_TOPK_MAX
 GMM_STANDARDIZE = 8        # SSYM_GMM_STANDARDIZE
@@ -264,6 +265,8 @@ def lib() -> ctypes.CDLL:
     L.ssym_pair_matrix_step.argtypes = [vp, vp, vp, u32, vp]
     L.ssym_dtw_cover.restype = i32
     L.ssym_dtw_cover.argtypes = [vp, vp, vp, f64, u32, vp, vp, vp, vp, vp, vp]
+    L.ssym_dtw_cover_gaps.restype = i32
+    L.ssym_dtw_cover_gaps.argtypes = [vp, vp, vp, f64, f64, u32, vp, vp, vp, vp, vp, vp]
     L.ssym_dtw_align_step.restype = i32
     L.ssym_dtw_align_step.argtypes = [vp, vp, vp, vp, vp, u32, u32, u32, vp, vp, vp, vp, vp, vp, u32]
     L.ssym_dtw_spot.restype = i32
@@ -391,6 +394,8 @@ def lib() -> ctypes.CDLL:
     L.ssym_spotter_reset.argtypes = [vp, vp, u32]
     L.ssym_coverer_create.restype = i32
     L.ssym_coverer_create.argtypes = [vp, vp, u32, f64, pvp]
+    L.ssym_coverer_create_gaps.restype = i32
+    L.ssym_coverer_create_gaps.argtypes = [vp, vp, u32, f64, f64, pvp]
     L.ssym_coverer_destroy.restype = i32
     L.ssym_coverer_destroy.argtypes = [vp, vp]
     L.ssym_coverer_push.restype = i32

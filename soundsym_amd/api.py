@@ -26,8 +26,8 @@ from typing import List, Optional, Sequence
 
 import numpy as np
 
-from ._native import NO_MATCH, SSYM_E_UNSUPPORTED, EmptyDictionaryError, SsymError
-from .engine import Engine, _cover_penalty, _wsola_search, pack_segments, pitch_lags
+from ._native import COVER_GAP, NO_MATCH, SSYM_E_UNSUPPORTED, EmptyDictionaryError, SsymError
+from .engine import Engine, _cover_gap_cost, _cover_penalty, _wsola_search, pack_segments, pitch_lags
 
 NCOEFFS = 12   # src/lib.rs:22
 NCLUSTERS = 26 # src/lib.rs:23
@@ -460,6 +460,7 @@ class Piece:
     `cost_per_frame` is cost / num_frames(), a mean that compares across pieces."""
 
     __slots__ = ("source_index", "start_frame", "end_frame", "cost")
+    is_gap = False
 
     def __init__(self, source_index: int, start_frame: int, end_frame: int, cost: float):
         self.source_index, self.start_frame, self.end_frame = int(source_index), int(start_frame), int(end_frame)
@@ -485,12 +486,61 @@ class Piece:
                                                                     self.cost)
 
 
+class Gap:
+    """A maximal run of frames a Cover leaves uncovered (cover(gap_cost=), "Cover with gaps"): frames `start_frame` ...
+    `end_frame` (INCLUSIVE) of the TARGET, at `cost` = gap_cost x num_frames(); `cost_per_frame` is the price per frame, the
+    figure a Piece's cost_per_frame competed with.  No dictionary sound belongs to it."""
+
+    __slots__ = ("start_frame", "end_frame", "cost")
+    is_gap = True
+
+    def __init__(self, start_frame: int, end_frame: int, cost: float):
+        self.start_frame, self.end_frame, self.cost = int(start_frame), int(end_frame), float(cost)
+        if not 0 <= self.start_frame <= self.end_frame:
+            raise ValueError("a gap spans start_frame ... end_frame with 0 <= start_frame <= end_frame")
+        if not self.cost >= 0.0:
+            raise ValueError("a gap's cost must not be negative or NaN")
+
+    def num_frames(self) -> int:
+        return self.end_frame - self.start_frame + 1
+
+    @property
+    def cost_per_frame(self) -> float:
+        return self.cost / float(self.num_frames())
+
+    def sample_span(self, num_samples: int):
+        """(first sample, one past the last sample) of the gap in a target of num_samples samples: Piece.sample_span's rule."""
+        n = int(num_samples)
+        return (self.start_frame * HOP, min((self.end_frame + 1) * HOP, n))
+
+    def __repr__(self) -> str:
+        return "Gap(frames=%d...%d, cost=%r)" % (self.start_frame, self.end_frame, self.cost)
+
+
+def _cover_tiles(src, start, end, cost) -> List:
+    """The Pieces and Gaps of one cover from what the library reports: a gap comes frame by frame as (COVER_GAP, e, e,
+    gap_cost), and a run of them is one Gap at gap_cost x its frames."""
+    out = []
+    for k in range(len(src)):
+        if int(src[k]) != COVER_GAP:
+            out.append(Piece(src[k], start[k], end[k], cost[k]))
+        elif out and out[-1].is_gap and out[-1].end_frame + 1 == int(start[k]):
+            run = out[-1]
+            out[-1] = Gap(run.start_frame, end[k], float(cost[k]) * (int(end[k]) - run.start_frame + 1))
+        else:
+            out.append(Gap(start[k], end[k], float(cost[k]) * (int(end[k]) - int(start[k]) + 1)))
+    return out
+
+
 class Cover:
     """A target tiled by dictionary sounds (ssym_dtw_cover; definition in include/soundsym_amd.h and DESIGN.md section 2
     "Cover"): `pieces` in ascending start, tiling frames 0 ... num_frames - 1 of the target, and `total`, the least sum of
     (piece cost + piece_penalty) over every tiling and every choice of sounds.  Every paced path has one cell per target
     frame, so `total_per_frame` = total / num_frames is a mean per frame.  A target without a cover (no frames, a NaN
-    frame, a stretch no dictionary sound can pace) gives an empty Cover: falsy, no pieces, total +inf."""
+    frame, a stretch no dictionary sound can pace) gives an empty Cover: falsy, no pieces, total +inf.
+    With gaps (cover(gap_cost=), "Cover with gaps") `pieces` holds Gaps among the Pieces -- the tiles, `is_gap` tells them
+    apart -- each Gap a maximal run of uncovered frames; total then adds gap_cost per gap frame and no piece_penalty for
+    it.  `gaps` are the Gaps, `sounding` the Pieces, `covered_frames` the frames the Pieces cover."""
 
     __slots__ = ("pieces", "total", "num_frames")
 
@@ -498,11 +548,13 @@ class Cover:
         self.pieces, self.total, self.num_frames = list(pieces), float(total), int(num_frames)
         if self.num_frames < 0:
             raise ValueError("a cover tiles num_frames >= 0 frames")
-        at = 0
+        at, after_gap = 0, False
         for p in self.pieces:
-            if not isinstance(p, Piece) or p.start_frame != at:
+            if not isinstance(p, (Piece, Gap)) or p.start_frame != at:
                 raise ValueError("the pieces of a cover tile the target: each starts where the one before it ended")
-            at = p.end_frame + 1
+            if p.is_gap and after_gap:
+                raise ValueError("a gap of a cover is a maximal run of frames: no gap follows a gap")
+            at, after_gap = p.end_frame + 1, p.is_gap
         if self.pieces and at != self.num_frames:
             raise ValueError("the pieces of a cover tile the target: the last one ends with it")
 
@@ -520,14 +572,30 @@ class Cover:
     def total_per_frame(self) -> float:
         return self.total / float(self.num_frames) if self.pieces else float("inf")
 
+    @property
+    def sounding(self) -> List["Piece"]:
+        """The Pieces: the tiles a dictionary sound covers."""
+        return [p for p in self.pieces if not p.is_gap]
+
+    @property
+    def gaps(self) -> List["Gap"]:
+        """The Gaps: the maximal runs of frames left uncovered."""
+        return [p for p in self.pieces if p.is_gap]
+
+    @property
+    def covered_frames(self) -> int:
+        """The frames dictionary sounds cover: num_frames less the gaps' frames (0 for an empty cover)."""
+        return sum(p.num_frames() for p in self.pieces if not p.is_gap)
+
     def indices(self) -> np.ndarray:
-        """The dictionary sound of every piece, int64: what align and warp take as indices for the cut target."""
-        return np.array([p.source_index for p in self.pieces], dtype=np.int64)
+        """The dictionary sound of every sounding piece (gaps have none), int64: what align and warp take as indices for
+        the cut target."""
+        return np.array([p.source_index for p in self.pieces if not p.is_gap], dtype=np.int64)
 
     def segment_lengths(self, num_samples: int) -> List[int]:
         """The cut as lengths in samples, as Partitioner.partition returns them: num_frames() * HOP per piece, and the
         last piece runs to the end of a sound of num_samples samples.  SoundDictionary.from_segments takes them as they
-        are.  An empty cover has no segments."""
+        are.  An empty cover has no segments.  Every tile counts, gaps included."""
         n = int(num_samples)
         if n < 0:
             raise ValueError("num_samples must not be negative")
@@ -538,12 +606,17 @@ class Cover:
         return [p.num_frames() * HOP for p in self.pieces[:-1]] + [n - self.pieces[-1].start_frame * HOP]
 
     def __repr__(self) -> str:
-        return "Cover(empty)" if not self.pieces else "Cover(%d pieces, total=%r)" % (len(self.pieces), self.total)
+        if not self.pieces:
+            return "Cover(empty)"
+        gaps = self.gaps
+        if gaps:
+            return "Cover(%d pieces, %d gaps, total=%r)" % (len(self.pieces) - len(gaps), len(gaps), self.total)
+        return "Cover(%d pieces, total=%r)" % (len(self.pieces), self.total)
 
 
 def _cover_sounds(sound: "Sound", cover: "Cover") -> List["Sound"]:
     """The target cut at the cover's pieces: samples by segment_lengths (Piece.sample_span, the last piece running to the
-    end of the sound), MFCC rows start_frame ... end_frame."""
+    end of the sound), MFCC rows start_frame ... end_frame.  Gaps are cut out: only the sounding pieces come back."""
     if not isinstance(cover, Cover):
         raise ValueError("a Cover is needed")
     if cover and cover.num_frames != sound.num_frames():
@@ -551,8 +624,9 @@ def _cover_sounds(sound: "Sound", cover: "Cover") -> List["Sound"]:
     smp, rows = sound.samples(), sound.mfcc_arrays()
     out, at = [], 0
     for p, n in zip(cover.pieces, cover.segment_lengths(smp.size)):
-        out.append(Sound(smp[at:at + n].copy(), sound.sample_rate(), rows[p.start_frame:p.end_frame + 1].copy(), None,
-                         sound.ncoeffs))
+        if not p.is_gap:
+            out.append(Sound(smp[at:at + n].copy(), sound.sample_rate(), rows[p.start_frame:p.end_frame + 1].copy(), None,
+                             sound.ncoeffs))
         at += n
     return out
 
@@ -560,15 +634,23 @@ def _cover_sounds(sound: "Sound", cover: "Cover") -> List["Sound"]:
 class LiveCover:
     """Growing Sounds covered live by a dictionary (`SoundDictionary.cover_live`): the sounds' shared stream followed by a
     Coverer (DESIGN.md section 2 "Live cover").  Pieces are (sound index, Piece), a Piece's frames those of the sound; a
-    piece, once returned, is final: it is how the cover of the whole sound starts, whatever the sound gains later."""
+    piece, once returned, is final: it is how the cover of the whole sound starts, whatever the sound gains later.
+    With a gap_cost (cover_live(gap_cost=)) a call also returns (sound index, Gap): the gap frames the call committed, a run
+    of them as one Gap; the run may go on in the next call, and `covers` merges across calls."""
 
-    def __init__(self, sounds, stream, coverer, piece_penalty: float):
+    def __init__(self, sounds, stream, coverer, piece_penalty: float, gap_cost=None):
         self.sounds, self.stream, self.coverer, self.piece_penalty = sounds, stream, coverer, float(piece_penalty)
-        self._emitted = [[] for _ in sounds]
+        self.gap_cost = gap_cost
+        self._emitted = [[] for _ in sounds]             # per sound, the Pieces and Gaps returned so far
+        self._costs = [[] for _ in sounds]               # ... and (is a gap frame, cost) as the coverer reported them
 
     def _pieces(self):
         lane, src, start, end, cost = self.coverer.pieces()
-        out = [(int(lane[k]), Piece(src[k], start[k], end[k], cost[k])) for k in range(lane.size)]
+        out = []
+        for l in np.unique(lane):
+            at = np.flatnonzero(lane == l)
+            self._costs[int(l)] += [(int(src[k]) == COVER_GAP, float(cost[k])) for k in at]
+            out += [(int(l), p) for p in _cover_tiles(src[at], start[at], end[at], cost[at])]
         for l, p in out:
             self._emitted[l].append(p)
         return out
@@ -592,13 +674,20 @@ class LiveCover:
         own sum over its pieces -- after flush, SoundDictionary.cover's Cover of the sound (of its coverable prefix, when a
         NaN frame or a stretch nothing can pace ends that early)."""
         out = []
-        for pieces in self._emitted:
-            if not pieces:
+        for emitted, costs in zip(self._emitted, self._costs):
+            if not emitted:
                 out.append(Cover.none(0))
                 continue
             acc = 0.0
-            for p in pieces:
-                acc = (p.cost + self.piece_penalty) + acc
+            for gap, cost in costs:                      # frame by frame; a gap frame carries no piece_penalty
+                acc = (cost + acc) if gap else ((cost + self.piece_penalty) + acc)
+            pieces = []
+            for p in emitted:                            # a run of gap frames that two calls share is one Gap
+                if p.is_gap and pieces and pieces[-1].is_gap:
+                    first = pieces[-1].start_frame
+                    pieces[-1] = Gap(first, p.end_frame, self.gap_cost * (p.end_frame - first + 1))
+                else:
+                    pieces.append(p)
             out.append(Cover(pieces, acc, pieces[-1].end_frame + 1))
         return out
 
@@ -1048,13 +1137,18 @@ class SoundDictionary:
             q.close()
         return (spots,) + (res if isinstance(res, tuple) else (res,))
 
-    def cover(self, targets: Sequence[Sound], piece_penalty: float = 0.0) -> List["Cover"]:
+    def cover(self, targets: Sequence[Sound], piece_penalty: float = 0.0, gap_cost=None) -> List["Cover"]:
         """Every target tiled by dictionary sounds, the cut points and the sounds chosen together on the GPU so that the
         paced alignment costs of the pieces sum to the least total (ssym_dtw_cover, one call; dtw engines without a band):
         a partition of the target that has seen the dictionary.  piece_penalty >= 0 is added per piece and trades total
         fit for fewer, longer pieces; 0 is the plain optimum.  Every piece's cost is what align(step="paced") gives for
-        (its sound, its frames of the target).  A target without a cover gives an empty Cover."""
-        penalty = _cover_penalty(piece_penalty)
+        (its sound, its frames of the target).  A target without a cover gives an empty Cover.
+        gap_cost (None: no gaps, everything above as it is): target frames may stay uncovered at gap_cost >= 0 per frame
+        (ssym_dtw_cover_gaps, "Cover with gaps") -- the price is a cost per frame, so it says how bad a Piece's
+        cost_per_frame may get before silence is better.  The Cover then holds Gaps (maximal runs) among its Pieces; every
+        target with a frame has a cover, and a NaN or infinite frame costs one gap frame, not the whole target.
+        float("inf") gives the Covers of None."""
+        penalty, gap = _cover_penalty(piece_penalty), _cover_gap_cost(gap_cost)
         targets = list(targets)
         if not self.sounds:
             raise EmptyDictionaryError(-2, "empty dictionary")
@@ -1065,7 +1159,7 @@ class SoundDictionary:
         flat, off = pack_segments([t.mfccs() for t in targets], self._dim(), self.engine.np_dtype)
         q = self.engine.queries(flat, off, self._dim())
         try:
-            count, total, src, start, end, cost = self.engine.dtw_cover(self.resident(), q, penalty)
+            count, total, src, start, end, cost = self.engine.dtw_cover(self.resident(), q, penalty, gap_cost=gap)
         finally:
             q.close()
         off = np.asarray(off, dtype=np.int64)
@@ -1075,7 +1169,8 @@ class SoundDictionary:
             if not count[t]:
                 out.append(Cover.none(frames))
                 continue
-            out.append(Cover([Piece(src[k], start[k], end[k], cost[k]) for k in range(a, a + int(count[t]))], total[t], frames))
+            b = a + int(count[t])
+            out.append(Cover(_cover_tiles(src[a:b], start[a:b], end[a:b], cost[a:b]), total[t], frames))
         return out
 
     def _cover_checks(self, piece_penalty, what: str) -> float:
@@ -1086,7 +1181,7 @@ class SoundDictionary:
             raise SsymError(SSYM_E_UNSUPPORTED, what + " aligns with dtw: a refcos engine has no alignment")
         return penalty
 
-    def cover_live(self, sounds: Sequence[Sound], piece_penalty: float = 0.0) -> "LiveCover":
+    def cover_live(self, sounds: Sequence[Sound], piece_penalty: float = 0.0, gap_cost=None) -> "LiveCover":
         """Cover Sounds that are still growing (fed with push_samples / push_sounds): a Coverer on this dictionary follows
         the sounds' stream (ssym_coverer_*, DESIGN.md section 2 "Live cover"; dtw engines without a band).  The sounds must
         be resident and share one stream, sound i in lane i -- what one push_sounds(sounds, ...) leaves -- ValueError
@@ -1094,21 +1189,23 @@ class SoundDictionary:
         flush() the rest; on f64 engines the pieces from first poll to flush are `cover`'s, bit for bit.  On f32 engines
         `cover` rounds the targets' features to f32 first while the coverer reads the stream's f64 frames as they are (as
         `watch` does), so the two can differ there.  The LiveCover keeps the dictionary's resident copy: close it before
-        the dictionary changes."""
-        penalty = self._cover_checks(piece_penalty, "cover_live")
+        the dictionary changes.  gap_cost as for `cover` (ssym_coverer_create_gaps): a NaN or infinite frame then becomes
+        a gap frame and the sound goes on being covered; covers() after flush are cover(gap_cost=)'s."""
+        penalty, gap = self._cover_checks(piece_penalty, "cover_live"), _cover_gap_cost(gap_cost)
         sounds = list(sounds)
         st = _shared_stream(sounds, "cover_live")
         if self.engine is not st.engine:
             raise ValueError("cover_live: the dictionary's engine must be the one that holds the sounds' stream")
         if st.ncoeffs != self._dim():
             raise ValueError("cover_live: the sounds' ncoeffs must be the dictionary's")
-        return LiveCover(sounds, st, self.engine.coverer(self.resident(), len(sounds), penalty), penalty)
+        return LiveCover(sounds, st, self.engine.coverer(self.resident(), len(sounds), penalty, gap), penalty, gap)
 
-    def cover_long(self, target: Sound, piece_penalty: float = 0.0, block_frames: int = 4096) -> "Cover":
+    def cover_long(self, target: Sound, piece_penalty: float = 0.0, block_frames: int = 4096, gap_cost=None) -> "Cover":
         """`cover` for one target of any length: a one-lane Coverer is pushed the target's frames block_frames at a time
         and flushed, so the tables never hold more than a block and the dictionary's horizon.  The Cover is `cover`'s, bit
-        for bit, where `cover` takes the target (on f32 engines the features are rounded to f32 first, as `cover` does)."""
-        penalty = self._cover_checks(piece_penalty, "cover_long")
+        for bit, where `cover` takes the target (on f32 engines the features are rounded to f32 first, as `cover` does).
+        gap_cost as for `cover`."""
+        penalty, gap = self._cover_checks(piece_penalty, "cover_long"), _cover_gap_cost(gap_cost)
         if isinstance(target, (list, tuple)):
             raise ValueError("cover_long takes one Sound")
         block = int(block_frames)
@@ -1118,13 +1215,13 @@ class SoundDictionary:
         if rows.shape[1:] != (self._dim(),):
             raise ValueError("cover_long: the target's ncoeffs must be the dictionary's")
         frames = rows.shape[0]
-        cv = self.engine.coverer(self.resident(), 1, penalty)
+        cv = self.engine.coverer(self.resident(), 1, penalty, gap)
         try:
-            pieces = []
+            raw = []
 
             def take():
                 _, src, start, end, cost = cv.pieces()
-                pieces.extend(Piece(src[k], start[k], end[k], cost[k]) for k in range(src.size))
+                raw.extend((src[k], start[k], end[k], cost[k]) for k in range(src.size))
             for at in range(0, frames, block):
                 if cv.push(rows[at:at + block]):
                     take()
@@ -1133,24 +1230,55 @@ class SoundDictionary:
                 take()
         finally:
             cv.close()
-        return Cover(pieces, total, frames) if np.isfinite(total) else Cover.none(frames)
+        return Cover(_cover_tiles(*zip(*raw)) if raw else [], total, frames) if np.isfinite(total) else Cover.none(frames)
 
-    def reconstruct_covered(self, target: Sound, piece_penalty: float = 0.0, search: int = 0, want_pcm32: bool = False):
+    def reconstruct_covered(self, target: Sound, piece_penalty: float = 0.0, search: int = 0, want_pcm32: bool = False,
+                            gap_cost=None, gap_fill: str = "silence"):
         """cover, cut, warp: the target is covered (ssym_dtw_cover), cut at the pieces (samples by
         Cover.segment_lengths, MFCC rows start_frame ... end_frame) and every piece warped from its sound under the paced
         pattern -- self.warp(pieces, indices=cover.indices(), step="paced", search=search), the existing calls.  Returns
         (cover, samples), with want_pcm32 (cover, samples, pcm); the samples are len(target.samples()).  A target without
-        a cover takes what SoundSequence([target]).reconstruct_from_dictionary gives it whole."""
-        penalty = _cover_penalty(piece_penalty)
+        a cover takes what SoundSequence([target]).reconstruct_from_dictionary gives it whole.
+        gap_cost as for `cover`.  The sounding pieces then go through warp exactly as above, and every Gap's stretch of
+        samples (its entry of Cover.segment_lengths: Gap.sample_span, a gap that ends the target running to the sound's last
+        sample) is spliced in between them as zeros (gap_fill="silence") or as the target's own samples ("target"; their
+        32-bit conversion is warp's: truncated, saturated, NaN as 0)."""
+        penalty, gap = _cover_penalty(piece_penalty), _cover_gap_cost(gap_cost)
         search = _wsola_search(search)
+        if gap_fill not in ("silence", "target"):
+            raise ValueError('gap_fill must be "silence" or "target"')
         if not isinstance(target, Sound):
             raise ValueError("reconstruct_covered takes one Sound")
-        cover = self.cover([target], penalty)[0]
+        cover = self.cover([target], penalty, gap)[0]
         if not cover:
             res = SoundSequence([target]).reconstruct_from_dictionary(self, want_pcm32)
-        else:
+        elif not cover.gaps:
             res = self.warp(_cover_sounds(target, cover), cover.indices(), want_pcm32, search, step="paced")
+        else:
+            res = self._splice_gaps(target, cover, gap_fill, want_pcm32, search)
         return (cover,) + (res if isinstance(res, tuple) else (res,))
+
+    def _splice_gaps(self, target: Sound, cover: "Cover", gap_fill: str, want_pcm32: bool, search: int):
+        """reconstruct_covered for a cover with gaps: warp's samples of the sounding pieces, the gaps' stretches between
+        them."""
+        smp = np.asarray(target.samples(), dtype=np.float64)
+        res = self.warp(_cover_sounds(target, cover), cover.indices(), want_pcm32, search, step="paced")
+        warped = res if isinstance(res, tuple) else (res,)
+        outs = [np.zeros(smp.size), np.zeros(smp.size, dtype=np.int32)][:len(warped)]
+        at = took = 0
+        for p, n in zip(cover.pieces, cover.segment_lengths(smp.size)):
+            if not p.is_gap:
+                for o, w in zip(outs, warped):
+                    o[at:at + n] = w[took:took + n]
+                took += n
+            elif gap_fill == "target":
+                outs[0][at:at + n] = smp[at:at + n]
+                if want_pcm32:
+                    with np.errstate(invalid="ignore", over="ignore"):
+                        x = np.nan_to_num(2147483647.0 * smp[at:at + n], nan=0.0)
+                        outs[1][at:at + n] = np.trunc(np.clip(x, -2147483648.0, 2147483647.0)).astype(np.int64).astype(np.int32)
+            at += n
+        return tuple(outs) if want_pcm32 else outs[0]
 
     def spot(self, targets: Sequence[Sound], indices=None, step: str = "symmetric") -> List["Spot"]:
         """Where inside the dictionary's (unsegmented) recordings every target sounds: subsequence DTW on the GPU (dtw
@@ -1355,7 +1483,7 @@ class SoundSequence:
     def from_cover(sound: Sound, cover: "Cover") -> "SoundSequence":
         """The target as the sequence of its pieces: `sound` cut at the pieces of `cover` (SoundDictionary.cover), samples
         by Cover.segment_lengths and MFCC rows start_frame ... end_frame, so that align, warp and clone_from_dictionary
-        take the pieces as they are.  An empty cover gives an empty sequence."""
+        take the pieces as they are.  An empty cover gives an empty sequence.  Gaps are skipped."""
         return SoundSequence(_cover_sounds(sound, cover))
 
     @staticmethod

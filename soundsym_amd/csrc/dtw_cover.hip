@@ -19,6 +19,10 @@
 //   cover    : walk back from e = T-1 while best is finite: piece (src, start = e-L+1, end = e, cost = M); e <- e-L
 //   total    = best(T-1);  count = pieces;  pieces reported in ascending start
 //   no cover : T = 0, or best(T-1) not finite -> count 0, total +inf
+// Cover with gaps (ssym_dtw_cover_gaps) adds one candidate to each step: vg = gap_cost + best(e-1); if vg < v (strict, so a
+// piece keeps a tie) best(e) = vg with the back-pointer (L = 1, SSYM_COVER_GAP, M = gap_cost).  The walk reports a gap frame
+// as the piece (SSYM_COVER_GAP, e, e, gap_cost); piece_penalty is not charged on it.  gap_cost = +inf never wins: that is
+// ssym_dtw_cover.  With a finite gap_cost every best(e) is finite, so every target of at least one frame has a cover.
 //
 // Mapping.  A column of the paced recurrence depends on the column before it alone, so ONE forward pass per (n, s) over the
 // longest window, 2 Fa columns, yields w(n,s,L) for every L: after column L-1 the bottom row holds it.  And the local
@@ -214,6 +218,7 @@ struct ChainArgs {
     uint32_t width;
     uint64_t frames;
     double penalty;
+    double gapCost;              // the price of a frame left uncovered; +inf: the plain cover
     uint32_t *bpLen, *bpSrc;     // [frames] back-pointers: the last piece of the best cover of X[0 ... e]
     double *bpCost;              // [frames]
     uint32_t *outCount;          // [nTgt]
@@ -242,7 +247,8 @@ __global__ __launch_bounds__(64) void cover_chain_kernel(const ChainArgs a)
         double last = INF;                               // best(T-1); T = 0: no cover
         for (uint64_t e = 0; e < T; ++e) {
             const uint32_t lMax = (uint32_t)min64((uint64_t)a.width, e + 1);
-            const CoverPick pick = cover_chain_step(a.tabM, a.tabSrc, a.frames, g0 + e, lMax, a.penalty, ring, kCoverRing - 1, e, lane);
+            const CoverPick pick = cover_chain_step(a.tabM, a.tabSrc, a.frames, g0 + e, lMax, a.penalty, a.gapCost, ring, kCoverRing - 1,
+                                                    e, lane);
             const double bestV = pick.v, bestM = pick.m;
             const uint32_t bestL = pick.len, bestS = pick.src;
             if (lane == 0) {
@@ -257,7 +263,8 @@ __global__ __launch_bounds__(64) void cover_chain_kernel(const ChainArgs a)
         if (lane == 0) {
             uint32_t count = 0;
             if (last < INF) {
-                // a finite best(e) has a last piece, and what lies before it has a finite best as well
+                // a finite best(e) has a last piece (a gap frame is a piece of one frame), and what lies before it has a
+                // finite best as well
                 for (int64_t e = (int64_t)T - 1; e >= 0; e -= a.bpLen[g0 + e])
                     ++count;
                 uint32_t k = count;
@@ -423,11 +430,11 @@ int32_t cover_forward(ssym_ctx *ctx, const SegmentSet &src, const double *tgtRaw
 
 namespace {
 
-int32_t dtw_cover(ssym_ctx *ctx, const ssym_dict *dict, const ssym_queries *q, double piece_penalty, uint32_t flags,
-                  uint32_t *out_count, double *out_total, uint32_t *out_src, uint32_t *out_start, uint32_t *out_end,
-                  double *out_cost)
+// ssym_dtw_cover (gap_cost = +inf) and ssym_dtw_cover_gaps: one body, the chain's gap candidate is the only difference
+int32_t dtw_cover(ssym_ctx *ctx, const char *fn, const ssym_dict *dict, const ssym_queries *q, double piece_penalty, double gap_cost,
+                  uint32_t flags, uint32_t *out_count, double *out_total, uint32_t *out_src, uint32_t *out_start,
+                  uint32_t *out_end, double *out_cost)
 {
-    const char *fn = "ssym_dtw_cover";
     if (!ctx)
         return SSYM_E_INVALID;
     int32_t rc = check_cover_ctx(ctx, fn);
@@ -438,6 +445,10 @@ int32_t dtw_cover(ssym_ctx *ctx, const ssym_dict *dict, const ssym_queries *q, d
         return rc;
     if (!(piece_penalty >= 0.0) || std::isinf(piece_penalty)) {
         ctx->err = std::string(fn) + ": piece_penalty must be finite and not negative";
+        return SSYM_E_INVALID;
+    }
+    if (!(gap_cost >= 0.0)) {
+        ctx->err = std::string(fn) + ": gap_cost must not be negative or NaN (+inf: no gaps)";
         return SSYM_E_INVALID;
     }
     const SegmentSet &src = dict->set, &tgt = q->set;
@@ -515,6 +526,7 @@ int32_t dtw_cover(ssym_ctx *ctx, const ssym_dict *dict, const ssym_queries *q, d
     c.width = width;
     c.frames = F;
     c.penalty = piece_penalty;
+    c.gapCost = gap_cost;
     c.bpLen = bpLen;
     c.bpSrc = bpSrc;
     c.bpCost = bpCost;
@@ -556,7 +568,18 @@ int32_t ssym_dtw_cover(ssym_ctx *ctx, const ssym_dict *dict, const ssym_queries 
                        double *out_cost)
 {
     return guarded(ctx, [&]() -> int32_t {
-        return dtw_cover(ctx, dict, q, piece_penalty, flags, out_count, out_total, out_src, out_start, out_end, out_cost);
+        return dtw_cover(ctx, "ssym_dtw_cover", dict, q, piece_penalty, __builtin_inf(), flags, out_count, out_total, out_src,
+                         out_start, out_end, out_cost);
+    });
+}
+
+int32_t ssym_dtw_cover_gaps(ssym_ctx *ctx, const ssym_dict *dict, const ssym_queries *q, double piece_penalty, double gap_cost,
+                            uint32_t flags, uint32_t *out_count, double *out_total, uint32_t *out_src, uint32_t *out_start,
+                            uint32_t *out_end, double *out_cost)
+{
+    return guarded(ctx, [&]() -> int32_t {
+        return dtw_cover(ctx, "ssym_dtw_cover_gaps", dict, q, piece_penalty, gap_cost, flags, out_count, out_total, out_src,
+                         out_start, out_end, out_cost);
     });
 }
 }

@@ -1,5 +1,5 @@
-// dtw_cover_chain.hpp -- one step of the cover's chain (DESIGN.md 2 "Cover"): best(e) and its back-pointer from the folded
-// M / src tables and the ring of earlier best values.  cover_chain_kernel (dtw_cover.hip) runs it over a whole target,
+// dtw_cover_chain.hpp -- one step of the cover's chain (DESIGN.md 2 "Cover", "Cover with gaps"): best(e) and its back-pointer
+// from the folded M / src tables, the ring of earlier best values and the price of leaving frame e uncovered.  cover_chain_kernel (dtw_cover.hip) runs it over a whole target,
 // coverer_chain_kernel (dtw_coverer.hip) over the frames a push brought: one body, so the two cannot drift apart.
 #pragma once
 
@@ -10,6 +10,7 @@
 namespace ssym {
 
 constexpr uint32_t kCoverNone = 0xffffffffu;
+constexpr uint32_t kCoverGap = 0xfffffffeu;              // SSYM_COVER_GAP: the "source" of a frame left uncovered
 
 struct CoverPick {
     double v, m;                 // best(e) and the cost M of its last piece
@@ -20,11 +21,15 @@ struct CoverPick {
 // window that STARTS at the column, so the window of L frames that ends at e is read at col + 1 - L); lMax: the longest
 // window that ends at e; ring: best(x) at (x + 1) & ringMask, e counted as the ring counts it.  The <= 2 Fmax candidates
 // are spread over the lanes (L ascending within a lane, strict <) and reduced by (v, L); every lane returns the result.
+// gapCost: the price of leaving frame e uncovered, >= 0 or +inf.  The gap candidate gapCost + best(e-1) is read in LDS alone
+// (best(e-1) is in the ring already) and wins under strict < only, so a piece keeps a tie and +inf never wins: with
+// gapCost = +inf the step is the plain cover's.  A gap is the pick (len 1, kCoverGap, gapCost); no penalty is charged on it.
 __device__ __forceinline__ CoverPick cover_chain_step(const double *tabM, const uint32_t *tabSrc, uint64_t frames, uint64_t col,
-                                                      uint32_t lMax, double penalty, const double *ring, uint32_t ringMask,
-                                                      uint64_t e, uint32_t lane)
+                                                      uint32_t lMax, double penalty, double gapCost, const double *ring,
+                                                      uint32_t ringMask, uint64_t e, uint32_t lane)
 {
     const double INF = __builtin_inf();
+    const double gapV = __dadd_rn(gapCost, ring[e & ringMask]);          // gap_cost + best(e-1)
     double bestV = INF, bestM = INF;
     uint32_t bestL = kCoverNone, bestS = kCoverNone;
     for (uint32_t L = lane + 1; L <= lMax; L += 64) {
@@ -52,6 +57,8 @@ __device__ __forceinline__ CoverPick cover_chain_step(const double *tabM, const 
             bestS = oS;
         }
     }
+    if (gapV < bestV)
+        return CoverPick{gapV, gapCost, 1u, kCoverGap};
     return CoverPick{bestV, bestM, bestL, bestS};
 }
 

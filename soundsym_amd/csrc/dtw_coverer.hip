@@ -38,6 +38,11 @@
 //             minimum, until all positions are equal.  Lane 0 counts the pieces from there down to done and writes them into
 //             the call's piece log in ascending start, with plain stores.  A flush is the same emission from lastFinite.
 // No kernel waits on another workgroup, none spins: stream order is the only ordering between them.
+//
+// Gaps (ssym_coverer_create_gaps).  The chain's step takes the gap candidate of "Cover with gaps": a frame left uncovered is a
+// piece of one frame with the source SSYM_COVER_GAP and the cost gap_cost.  1 <= W, so the horizon argument holds as it
+// stands, and commit, flush and emission walk gap frames like any other piece.  With a finite gap_cost every best(e) is
+// finite: lastFinite = n - 1, H(n) is never empty, and a NaN or +-inf frame is a gap frame the lane goes on past.
 #include "dtw_wave.hpp"
 #include "dtw_cover_chain.hpp"
 
@@ -77,6 +82,7 @@ struct ssym_coverer {
     uint32_t dictN = 0;                      // the dictionary as it was at creation
     uint64_t dictFrames = 0;
     double penalty = 0.0;
+    double gapCost = 0.0;                    // +inf from ssym_coverer_create: no gaps
     uint64_t sliceMax = 0;                   // frames per lane and slice the scratch allows
     // host mirrors of the lanes
     std::vector<uint64_t> consumed;
@@ -153,6 +159,7 @@ struct CovChainArgs {
     uint32_t ring, width;
     uint64_t frames;
     double penalty;
+    double gapCost;              // the price of a frame left uncovered; +inf: the plain cover
     uint64_t backCap;
     uint32_t *bpLen, *bpSrc;
     double *bpCost;
@@ -179,7 +186,8 @@ __global__ __launch_bounds__(64) void coverer_chain_kernel(const CovChainArgs a)
         // a window of L frames that ends at e starts at e + 1 - L >= 0, and in the buffer at tail + k + 1 - L >= 0: with
         // tail = min(n, W - 1) the first says both
         const uint32_t lMax = (uint32_t)(e + 1 < a.width ? e + 1 : a.width);
-        const CoverPick pick = cover_chain_step(a.tabM, a.tabSrc, a.frames, col0 + k, lMax, a.penalty, ringL, a.ring - 1, e, lane);
+        const CoverPick pick = cover_chain_step(a.tabM, a.tabSrc, a.frames, col0 + k, lMax, a.penalty, a.gapCost, ringL, a.ring - 1,
+                                                    e, lane);
         if (lane == 0) {
             ringL[(e + 1) & (a.ring - 1)] = pick.v;
             const size_t o = b0 + (e & (a.backCap - 1));
@@ -441,9 +449,10 @@ int32_t log_room(ssym_ctx *ctx, ssym_coverer *cv, uint64_t need)
     return SSYM_OK;
 }
 
-int32_t coverer_create(ssym_ctx *ctx, const ssym_dict *dict, uint32_t n_lanes, double piece_penalty, ssym_coverer **out)
+// ssym_coverer_create (gap_cost = +inf) and ssym_coverer_create_gaps: the chain's gap candidate is the only difference
+int32_t coverer_create(ssym_ctx *ctx, const char *fn, const ssym_dict *dict, uint32_t n_lanes, double piece_penalty, double gap_cost,
+                       ssym_coverer **out)
 {
-    const char *fn = "ssym_coverer_create";
     if (!out) {
         ctx->err = std::string(fn) + ": out is NULL";
         return SSYM_E_INVALID;
@@ -458,6 +467,10 @@ int32_t coverer_create(ssym_ctx *ctx, const ssym_dict *dict, uint32_t n_lanes, d
     }
     if (!(piece_penalty >= 0.0) || std::isinf(piece_penalty)) {
         ctx->err = std::string(fn) + ": piece_penalty must be finite and not negative";
+        return SSYM_E_INVALID;
+    }
+    if (!(gap_cost >= 0.0)) {
+        ctx->err = std::string(fn) + ": gap_cost must not be negative or NaN (+inf: no gaps)";
         return SSYM_E_INVALID;
     }
     const SegmentSet &src = dict->set;
@@ -492,6 +505,7 @@ int32_t coverer_create(ssym_ctx *ctx, const ssym_dict *dict, uint32_t n_lanes, d
     cv->dictN = src.n;
     cv->dictFrames = src.total_frames;
     cv->penalty = piece_penalty;
+    cv->gapCost = gap_cost;
     cv->sliceMax = std::min<uint64_t>(lim.scratch_bytes / perFrame - (W - 1), kCovererMaxLaneFrames);
     cv->consumed.assign(n_lanes, 0);
     cv->done.assign(n_lanes, -1);
@@ -627,6 +641,7 @@ int32_t coverer_run(ssym_ctx *ctx, ssym_coverer *cv, const std::vector<const dou
             c.width = W;
             c.frames = frames;
             c.penalty = cv->penalty;
+            c.gapCost = cv->gapCost;
             c.backCap = cv->backCap;
             c.bpLen = cv->bpLen;
             c.bpSrc = cv->bpSrc;
@@ -917,7 +932,19 @@ int32_t ssym_coverer_create(ssym_ctx *ctx, const ssym_dict *dict, uint32_t n_lan
 {
     if (!ctx)
         return SSYM_E_INVALID;
-    return guarded(ctx, [&]() -> int32_t { return coverer_create(ctx, dict, n_lanes, piece_penalty, out); });
+    return guarded(ctx, [&]() -> int32_t {
+        return coverer_create(ctx, "ssym_coverer_create", dict, n_lanes, piece_penalty, __builtin_inf(), out);
+    });
+}
+
+int32_t ssym_coverer_create_gaps(ssym_ctx *ctx, const ssym_dict *dict, uint32_t n_lanes, double piece_penalty, double gap_cost,
+                                 ssym_coverer **out)
+{
+    if (!ctx)
+        return SSYM_E_INVALID;
+    return guarded(ctx, [&]() -> int32_t {
+        return coverer_create(ctx, "ssym_coverer_create_gaps", dict, n_lanes, piece_penalty, gap_cost, out);
+    });
 }
 
 int32_t ssym_coverer_destroy(ssym_ctx *ctx, ssym_coverer *cv)

@@ -81,6 +81,17 @@ def _cover_penalty(piece_penalty) -> float:
     return penalty
 
 
+def _cover_gap_cost(gap_cost):
+    """gap_cost of dtw_cover / coverer: None (no gaps: the calls without the argument) or a float >= 0 (+inf allowed),
+    checked before the library is asked."""
+    if gap_cost is None:
+        return None
+    gap = float(gap_cost)
+    if not gap >= 0.0:
+        raise ValueError("gap_cost must not be negative or NaN (None or +inf: no gaps)")
+    return gap
+
+
 def _spot_all_args(src, max_spots, max_cost):
     """(K, per-pair thresholds as a contiguous f64 array or None) of dtw_spot_all, checked before the library is asked."""
     k = int(max_spots)
@@ -547,9 +558,9 @@ class Coverer:
     ssym_dtw_cover's total for everything consumed so far.  The coverer reads the dictionary's resident features for as
     long as it lives: it keeps `d` alive and must be closed before it."""
 
-    def __init__(self, engine: "Engine", ptr: int, d: _Handle, n_lanes: int, piece_penalty: float):
+    def __init__(self, engine: "Engine", ptr: int, d: _Handle, n_lanes: int, piece_penalty: float, gap_cost=None):
         self.engine, self.ptr, self.d, self.n_lanes, self.dim = engine, ptr, d, n_lanes, d.dim
-        self.piece_penalty = piece_penalty
+        self.piece_penalty, self.gap_cost = piece_penalty, gap_cost
         self.n_pieces = 0
 
     def _lane(self, lane) -> int:
@@ -589,6 +600,7 @@ class Coverer:
     def pieces(self, on_device: bool = False):
         """The pieces of the last push / follow / flush, ordered by (lane, start): (lane uint32 [n], src uint32 [n], start
         uint32 [n], end uint32 [n], cost f64 [n]); start / end count the lane's frames since its reset, end inclusive.
+        On a coverer with a gap_cost a frame left uncovered is the piece (lane, COVER_GAP, e, e, gap_cost).
         on_device: SSYM_OUT_DEVICE, the five arrays as torch tensors in device memory."""
         n = self.n_pieces
         device = self.engine.device if on_device else None
@@ -1142,7 +1154,7 @@ class Engine:
         nat.check(rc, self.ctx)
         return idx, cost, start, end
 
-    def dtw_cover(self, d: _Handle, q: _Handle, piece_penalty: float = 0.0, on_device: bool = False):
+    def dtw_cover(self, d: _Handle, q: _Handle, piece_penalty: float = 0.0, on_device: bool = False, gap_cost=None):
         """ssym_dtw_cover (dtw engines without a band): every target tiled by dictionary segments, cut points and
         segments chosen together so that the paced costs of the pieces sum to the least total over every tiling, by the
         definition in include/soundsym_amd.h ("Cover").  piece_penalty >= 0 is added per piece.  Returns (count uint32
@@ -1150,15 +1162,22 @@ class Engine:
         the whole query set: target t's pieces lie in slots q.offsets[t] ... q.offsets[t] + count[t] - 1 in ascending
         start, start / end count frames inside the target (end inclusive), unused slots hold NO_MATCH and +inf, a
         target without a cover has count 0 and total +inf.  Costs are sums.  on_device: SSYM_OUT_DEVICE, the six arrays
-        as torch tensors in device memory (the 32-bit tensors hold the call's u32 values)."""
-        penalty = _cover_penalty(piece_penalty)
+        as torch tensors in device memory (the 32-bit tensors hold the call's u32 values).
+        gap_cost (None: ssym_dtw_cover as it is): ssym_dtw_cover_gaps, "Cover with gaps" -- a target frame may stay
+        uncovered at gap_cost >= 0 per frame (+inf: never, the results of None).  A gap frame is reported frame by frame
+        as the piece (nat.COVER_GAP, e, e, gap_cost); no piece_penalty is charged on it and a piece wins a tie.  With a
+        finite gap_cost every target with a frame has a cover."""
+        penalty, gap = _cover_penalty(piece_penalty), _cover_gap_cost(gap_cost)
         m, frames = q.n, int(q.offsets[-1])
         device = self.device if on_device else None
         (count, pn), (total, pt), (src, ps), (start, pa), (end, pe), (cost, pc) = (
             _output(device, (rows,), t) for rows, t in ((m, np.uint32), (m, np.float64), (frames, np.uint32),
                                                         (frames, np.uint32), (frames, np.uint32), (frames, np.float64)))
-        rc = nat.lib().ssym_dtw_cover(self.ctx, d.ptr, q.ptr, penalty, 0 if device is None else nat.OUT_DEVICE, pn, pt, ps,
-                                      pa, pe, pc)
+        flags = 0 if device is None else nat.OUT_DEVICE
+        if gap is None:
+            rc = nat.lib().ssym_dtw_cover(self.ctx, d.ptr, q.ptr, penalty, flags, pn, pt, ps, pa, pe, pc)
+        else:
+            rc = nat.lib().ssym_dtw_cover_gaps(self.ctx, d.ptr, q.ptr, penalty, gap, flags, pn, pt, ps, pa, pe, pc)
         nat.check(rc, self.ctx)
         return count, total, src, start, end, cost
 
@@ -1232,16 +1251,22 @@ class Engine:
         nat.check(rc, self.ctx)
         return Spotter(self, out.value, q, lanes, step)
 
-    def coverer(self, d: _Handle, n_lanes: int = 1, piece_penalty: float = 0.0) -> Coverer:
+    def coverer(self, d: _Handle, n_lanes: int = 1, piece_penalty: float = 0.0, gap_cost=None) -> Coverer:
         """ssym_coverer_create: `n_lanes` growing targets covered live by the segments of `d` (dtw engines without a
-        band; "Live cover").  piece_penalty >= 0 is added per piece, as for dtw_cover."""
-        penalty = _cover_penalty(piece_penalty)
+        band; "Live cover").  piece_penalty >= 0 is added per piece, as for dtw_cover.  gap_cost (None:
+        ssym_coverer_create as it is): ssym_coverer_create_gaps -- frames may stay uncovered at gap_cost each, as for
+        dtw_cover; a NaN or infinite frame then becomes a gap frame and the lane goes on."""
+        penalty, gap = _cover_penalty(piece_penalty), _cover_gap_cost(gap_cost)
         lanes = int(n_lanes)
         if lanes < 1:
             raise ValueError("n_lanes must be at least 1")
         out = ctypes.c_void_p()
-        nat.check(nat.lib().ssym_coverer_create(self.ctx, d.ptr, lanes, penalty, ctypes.byref(out)), self.ctx)
-        return Coverer(self, out.value, d, lanes, penalty)
+        if gap is None:
+            rc = nat.lib().ssym_coverer_create(self.ctx, d.ptr, lanes, penalty, ctypes.byref(out))
+        else:
+            rc = nat.lib().ssym_coverer_create_gaps(self.ctx, d.ptr, lanes, penalty, gap, ctypes.byref(out))
+        nat.check(rc, self.ctx)
+        return Coverer(self, out.value, d, lanes, penalty, gap)
 
     @staticmethod
     def mfcc_num_frames(n_samples: int, pad_tail: bool = False) -> int:

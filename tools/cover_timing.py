@@ -14,7 +14,10 @@ route that gave the same answer before it (LAB.md).
 One MI355X, one process.  A host clock around each call, which ends in its own synchronisation: median of --reps calls
 after --warmup calls; beside it the device time of the call's kernels (ssym_get_timings: main_ms, reduce_ms).
 
-    python tools/cover_timing.py [--reps 10] [--warmup 3] [--only a4096,a16384,b,c]
+    python tools/cover_timing.py [--reps 10] [--warmup 3] [--only a4096,a16384,b,c] [--gap-cost X]
+
+--gap-cost X times ssym_dtw_cover_gaps at that price per frame in place of ssym_dtw_cover on the same shapes; (c) then times
+the call alone (the earlier route has no gaps to compare with).
 """
 import argparse
 import os
@@ -58,12 +61,12 @@ def forward_cells(fa, frames):
     return total
 
 
-def shape(name, src, target, dim, reps, warmup, penalty=0.0):
+def shape(name, src, target, dim, reps, warmup, penalty=0.0, gap_cost=None):
     e = Engine(metric="dtw", dtype="f32")
     d, q = e.dictionary(*pack_segments(src, dim, np.float32), dim), e.queries(*pack_segments([target], dim, np.float32), dim)
     fa = np.array([s.shape[0] for s in src])
     cells = forward_cells(fa, target.shape[0])
-    call = lambda: e.dtw_cover(d, q, penalty)
+    call = lambda: e.dtw_cover(d, q, penalty, gap_cost=gap_cost)
     t = median_ms(call, reps, warmup)
     count, total = call()[:2]
     tm = e.timings()
@@ -109,18 +112,24 @@ def earlier_route(e, d, src, target, dim, penalty):
     return pieces[::-1], float(best[T]), len(wins)
 
 
-def against_the_earlier_route(src, target, dim, reps, warmup, penalty=0.0):
+def against_the_earlier_route(src, target, dim, reps, warmup, penalty=0.0, gap_cost=None):
     e = Engine(metric="dtw", dtype="f32")
     d = e.dictionary(*pack_segments(src, dim, np.float32), dim)
 
     def new():
         q = e.queries(*pack_segments([target], dim, np.float32), dim)       # (the upload is part of both routes)
-        out = e.dtw_cover(d, q, penalty)
+        out = e.dtw_cover(d, q, penalty, gap_cost=gap_cost)
         q.close()
         return out
     t_new = median_ms(new, reps, warmup)
     count, total, s, a, b, c = new()
     tm = e.timings()
+    if gap_cost is not None:
+        gaps = int((s[:int(count[0])] == 0xFFFFFFFE).sum())
+        print(f"(c) {len(src)} sources x {target.shape[0]} frames, gap_cost {gap_cost}: cover with gaps {fmt(t_new)} (forward "
+              f"{tm['main_ms']:.3f}, chain {tm['reduce_ms']:.3f})  {gaps} gap frames", flush=True)
+        e.close()
+        return
     old = lambda: earlier_route(e, d, src, target, dim, penalty)
     t_old = median_ms(old, max(3, reps // 3), 1)
     pieces, old_total, windows = old()
@@ -143,6 +152,7 @@ def main():
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--only", default="a4096,a16384,b,c")
+    ap.add_argument("--gap-cost", type=float, default=None)
     args = ap.parse_args()
     only = set(args.only.split(","))
     rng = np.random.default_rng(0x5EED0C07)
@@ -150,13 +160,14 @@ def main():
     ragged = lambda count: [mk(int(f), 13) for f in rng.integers(5, 41, size=count)]
     src = ragged(4096)
     if "a4096" in only:
-        shape("(a) ragged 5...40 f x 13 d", src, mk(4096, 13), 13, args.reps, args.warmup)
+        shape("(a) ragged 5...40 f x 13 d", src, mk(4096, 13), 13, args.reps, args.warmup, gap_cost=args.gap_cost)
     if "a16384" in only:
-        shape("(a) ragged 5...40 f x 13 d", src, mk(16384, 13), 13, args.reps, args.warmup)
+        shape("(a) ragged 5...40 f x 13 d", src, mk(16384, 13), 13, args.reps, args.warmup, gap_cost=args.gap_cost)
     if "b" in only:
-        shape("(b) 128 f x 13 d", [mk(128, 13) for _ in range(512)], mk(4096, 13), 13, args.reps, args.warmup)
+        shape("(b) 128 f x 13 d", [mk(128, 13) for _ in range(512)], mk(4096, 13), 13, args.reps, args.warmup,
+              gap_cost=args.gap_cost)
     if "c" in only:
-        against_the_earlier_route(ragged(256), mk(512, 13), 13, args.reps, args.warmup)
+        against_the_earlier_route(ragged(256), mk(512, 13), 13, args.reps, args.warmup, gap_cost=args.gap_cost)
 
 
 if __name__ == "__main__":
