@@ -186,6 +186,13 @@ extern "C" {
     pub fn ssym_dtw_cover_gaps(ctx: *mut SsymCtx, dict: *const SsymDict, q: *const SsymQueries, piece_penalty: f64,
                                gap_cost: f64, flags: u32, out_count: *mut u32, out_total: *mut f64, out_src: *mut u32,
                                out_start: *mut u32, out_end: *mut u32, out_cost: *mut f64) -> i32;
+    // the mosaic: every target tiled by free spans of dictionary segments of any length under the paced pattern, cuts,
+    // segments, spans and paths chosen together; out_start lists a target's piece and gap-frame starts from slot
+    // frame_offset[t] on (unused: SSYM_NO_MATCH), out_src / out_frame / out_frame_cost hold one entry per target frame
+    // (a gap frame: SSYM_COVER_GAP, SSYM_NO_MATCH, gap_cost); every output may be null
+    pub fn ssym_dtw_mosaic(ctx: *mut SsymCtx, dict: *const SsymDict, q: *const SsymQueries, piece_penalty: f64,
+                           gap_cost: f64, flags: u32, out_count: *mut u32, out_total: *mut f64, out_start: *mut u32,
+                           out_src: *mut u32, out_frame: *mut u32, out_frame_cost: *mut f64) -> i32;
 
     // source-sharded runs, exchange done by the caller (device pointers): filter / all-reduce(MIN) / finish / merge
     pub fn ssym_match_begin(ctx: *mut SsymCtx, dict: *const SsymDict, q: *const SsymQueries, distance: *const f64,

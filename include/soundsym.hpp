@@ -504,6 +504,74 @@ class SoundDictionary {
         }
         return out;
     }
+    // every target tiled by free spans of the dictionary's sounds, the cuts, the sounds, the spans and the paced paths chosen
+    // together (ssym_dtw_mosaic; soundsym_amd.h "Mosaic"; dtw contexts without a band; the crate has no counterpart): neither
+    // side needs cutting beforehand.  A piece plays frames start_frame ... end_frame (inclusive) of the TARGET by frames
+    // source_first ... source_last of sounds[source_index] along frame_map (the sound's frame per frame of the piece); cost
+    // is the chain of its frame costs (acc = c, acc = c + acc).  gap_cost >= 0 (+inf, the default: no gaps): a maximal run
+    // of uncovered frames is one entry with source_index = SSYM_COVER_GAP, source_first = source_last = SSYM_NO_MATCH, no
+    // frame_map and cost = the sum of its frames' prices.  total includes piece_penalty per piece and gap_cost per gap
+    // frame; frame_costs holds c (or gap_cost) for every target frame.  No mosaic: no pieces, total +inf
+    struct MosaicPiece {
+        uint32_t source_index, source_first, source_last, start_frame, end_frame;
+        double cost;
+        std::vector<uint32_t> frame_map;
+        bool is_gap() const { return source_index == SSYM_COVER_GAP; }
+    };
+    struct Mosaic {
+        std::vector<MosaicPiece> pieces;
+        double total;
+        std::vector<double> frame_costs;
+        bool empty() const { return pieces.empty(); }
+    };
+    std::vector<Mosaic> mosaic(const std::vector<ArcSound> &targets, double piece_penalty, double gap_cost = __builtin_inf()) const
+    {
+        if (sounds.empty())
+            throw EmptyDictionary();
+        if (targets.empty())
+            return {};
+        const uint32_t n = (uint32_t)targets.size();
+        std::vector<double> flat;
+        std::vector<uint64_t> off;
+        pack_features(targets, flat, off);
+        ssym_queries *q = nullptr;
+        ctx_->check(ssym_queries_create(ctx_->get(), flat.data(), off.data(), n, (uint32_t)NCOEFFS, &q));
+        const size_t frames = (size_t)(off[n] - off[0]), room = frames ? frames : 1;      // (no NULL of an empty vector)
+        std::vector<uint32_t> count(n), start(room), src(room), frame(room);
+        std::vector<double> total(n), cost(room);
+        const int32_t rc = ssym_dtw_mosaic(ctx_->get(), resident(), q, piece_penalty, gap_cost, 0, count.data(), total.data(),
+                                           start.data(), src.data(), frame.data(), cost.data());
+        ssym_queries_destroy(ctx_->get(), q);
+        ctx_->check(rc);
+        std::vector<Mosaic> out(n);
+        for (uint32_t t = 0; t < n; ++t) {
+            out[t].total = total[t];
+            const size_t at = (size_t)(off[t] - off[0]), T = (size_t)(off[t + 1] - off[t]);
+            if (!count[t])
+                continue;
+            out[t].frame_costs.assign(cost.begin() + at, cost.begin() + at + T);
+            std::vector<MosaicPiece> &ps = out[t].pieces;
+            for (uint32_t k = 0; k < count[t]; ++k) {
+                const size_t s = start[at + k], e = k + 1 < count[t] ? start[at + k + 1] : T;     // frames s ... e - 1
+                if (src[at + s] == SSYM_COVER_GAP) {
+                    if (!ps.empty() && ps.back().is_gap()) {                 // a run of gap frames is one entry
+                        ps.back().end_frame = (uint32_t)s;
+                        ps.back().cost = cost[at + s] * (double)(ps.back().end_frame - ps.back().start_frame + 1);
+                    } else {
+                        ps.push_back(MosaicPiece{SSYM_COVER_GAP, SSYM_NO_MATCH, SSYM_NO_MATCH, (uint32_t)s, (uint32_t)s,
+                                                 cost[at + s], {}});
+                    }
+                    continue;
+                }
+                double acc = cost[at + s];
+                for (size_t j = s + 1; j < e; ++j)
+                    acc = cost[at + j] + acc;
+                ps.push_back(MosaicPiece{src[at + s], frame[at + s], frame[at + e - 1], (uint32_t)s, (uint32_t)(e - 1), acc,
+                                         std::vector<uint32_t>(frame.begin() + at + s, frame.begin() + at + e)});
+            }
+        }
+        return out;
+    }
     // align with a Spot per target instead of an index: target t against frames start_frame ... end_frame of
     // sounds[source_index], where they lie in the resident dictionary (ssym_dtw_align_spans; soundsym_amd.h "Span
     // alignment").  path and frame_map count from the span's first frame; an empty Spot gives an empty Alignment

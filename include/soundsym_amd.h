@@ -566,6 +566,58 @@ SSYM_API int32_t ssym_dtw_cover_gaps(ssym_ctx *ctx, const ssym_dict *dict, const
                                      double gap_cost, uint32_t flags, uint32_t *out_count, double *out_total,
                                      uint32_t *out_src, uint32_t *out_start, uint32_t *out_end, double *out_cost);
 
+/* Mosaic (DESIGN.md section 2 "Mosaic" and section 5.25): every target tiled by pieces, each piece ANY span of ANY dictionary
+ * segment aligned under the paced pattern; the cuts, the segments, the spans and the paths are chosen together.  Neither
+ * side needs cutting beforehand: the dictionary may be whole recordings of any length.  Under the paced pattern every
+ * tiling of a T-frame target has exactly T cells, so totals compare and total / T is a mean per frame.
+ * c, the squared option and the arithmetic are those of "Paced spotting" above, word for word.  The dictionary's segments
+ * are laid end to end: g = 0 ... G-1 is a global source frame, seg(g) its segment, pos(g) its frame within it; empty
+ * segments contribute nothing.  Every cell has the states N and H of the paced pattern.  For one target X of T frames:
+ *   best(-1) = 0
+ *   column j = 0 ... T-1:
+ *     S      = piece_penalty + best(j-1)                            (the price of opening a piece at column j)
+ *     P(g)   = E(g-1, j-1) if pos(g) >= 1, else +inf
+ *              if pos(g) >= 2 and E(g-2, j-1) < P: E(g-2, j-1)       (strict <; j = 0: P = +inf)
+ *     open(g)= not (P(g) <= S)                                      (a tie continues the piece; a NaN P opens)
+ *     Q      = S if open(g) else P(g)
+ *     H(g,j) = c(g,j) + N(g,j-1)                                    (+inf at j = 0; a repeat may only follow a source step)
+ *     N(g,j) = c(g,j) + Q
+ *     E(g,j) = N(g,j); if H(g,j) < N(g,j): H(g,j)                   (strict <: a tie keeps N)
+ *     (v,arg)= the first least E(g,j) over g ascending from (+inf, none), strict <   (NaN and +inf never win)
+ *     vg     = gap_cost + best(j-1);  if vg < v (strict): best(j) = vg, arg(j) = GAP;  else best(j) = v, arg(j) = arg
+ *   total    = best(T-1);  no mosaic: T = 0, or total not finite -> count 0, total +inf
+ *   backward : j = T-1, at arg(j).  GAP: frame j is a gap frame, go to arg(j-1).  Otherwise the state is H if H < N there,
+ *              else N.  State H at (g,j): the cell before is (g, j-1) in state N.  State N at (g,j): if open(g) at column
+ *              j, a piece starts here, go to arg(j-1); else the cell before is (g-2, j-1) if the P rule took it, else
+ *              (g-1, j-1), in its E state.
+ * So (1) pieces and gap frames tile [0, T); within a piece the source frame advances by 0, 1 or 2 per target frame, never
+ * by 0 twice in a row, and a piece never crosses a segment boundary; (2) acc = 0; a frame that opens a piece: acc = c +
+ * (piece_penalty + acc); one that continues a piece: acc = c + acc; a gap frame: acc = gap_cost + acc -> total's bits;
+ * (3) total is the least such sum over every mosaic; (4) a NaN source frame is never on a path; a NaN target frame means
+ * no mosaic without gaps and exactly one gap frame with a finite gap_cost; (5) no read leaves its buffer.  At
+ * piece_penalty = 0 the optimum is frame-wise and a stretched span comes back in fragments: ask with a penalty > 0.
+ *   piece_penalty  >= 0, finite: charged once per piece, never on a gap frame
+ *   gap_cost       >= 0 and finite, or +inf (no gaps): the price of a target frame left uncovered
+ *   out_count, out_total   n_targets u32 / f64: pieces + gap frames, and total
+ *   out_start      one slot per target frame of the whole query set, target t's from slot frame_offset[t]: the target
+ *                  frames at which a piece or a gap frame starts, ascending; unused slots hold SSYM_NO_MATCH
+ *   out_src, out_frame, out_frame_cost   per target frame: the segment, the frame within it and c; a gap frame:
+ *                  (SSYM_COVER_GAP, SSYM_NO_MATCH, gap_cost); without a mosaic (SSYM_NO_MATCH, SSYM_NO_MATCH, +inf)
+ *   flags          SSYM_OUT_DEVICE: the outputs are device memory.  Every output may be NULL.
+ * The targets of one call are independent mosaics.
+ * Limits: a dtw context without a band, dim <= 64, and for the call's longest target G x T + 32 G + 4 T + 8 bytes (one
+ * workgroup's direction bytes, two columns of state and column picks) + G + 8 G dim bytes (pos and the transposed frames,
+ * once per call) of scratch <= 512 MiB, G the dictionary's frames; a call with more targets than fit runs them in rounds
+ * on fewer workgroups.  Segments may be as long as a
+ * dictionary holds.  Beyond the limits and on a refcos context: SSYM_E_UNSUPPORTED before any device work, with the
+ * outputs unwritten.  A NaN, negative or infinite piece_penalty, a NaN, negative or -inf gap_cost: SSYM_E_INVALID.  An
+ * empty dictionary: SSYM_E_EMPTY_DICT.  n_targets = 0 succeeds and does nothing.  One synchronisation per call.
+ * ssym_get_timings afterwards: main_ms = the forward and back-trace kernels, main_launches = the rounds, n_pairs = G x the
+ * call's target frames. */
+SSYM_API int32_t ssym_dtw_mosaic(ssym_ctx *ctx, const ssym_dict *dict, const ssym_queries *q, double piece_penalty,
+                                 double gap_cost, uint32_t flags, uint32_t *out_count, double *out_total,
+                                 uint32_t *out_start, uint32_t *out_src, uint32_t *out_frame, double *out_frame_cost);
+
 /* Source-sharded multi-GPU, dtw metric: the one real exchange the path has.  Each rank's filter gives,
  * per target, an upper bound on the best key in ITS shard; a rank whose shard does not hold a
  * target's neighbour would otherwise re-score ~10^2 of its own pairs per target for nothing.

@@ -19,6 +19,8 @@ from .api import (  # noqa: F401
     Gap,
     HOP,
     LiveCover,
+    Mosaic,
+    MosaicPiece,
     NCLUSTERS,
     NCOEFFS,
     Partitioner,
@@ -40,7 +42,7 @@ from .api import (  # noqa: F401
 )
 
 __all__ = [
-    "ABI_SYMBOLS", "Alignment", "BIN", "Cover", "Coverer", "DeviceFrames", "EmptyDictionaryError", "Engine", "Gap", "Gmm", "HOP", "LIB_PATH", "LiveCover", "NCLUSTERS", "NCOEFFS",
+    "ABI_SYMBOLS", "Alignment", "BIN", "Cover", "Coverer", "DeviceFrames", "EmptyDictionaryError", "Engine", "Gap", "Gmm", "HOP", "LIB_PATH", "LiveCover", "Mosaic", "MosaicPiece", "NCLUSTERS", "NCOEFFS",
     "Partitioner", "Piece", "Sound", "SoundDictionary", "SoundSequence", "Spot", "SsymError", "analyze_mfccs", "analyze_sounds", "build",
     "cosine_sim_angular", "discretize",
     "discretize_with_model", "length_fit", "pack_segments", "push_sounds", "Spotter", "Stream", "stream_plan", "train_model", "Watch", "watch",

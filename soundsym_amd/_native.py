@@ -63,7 +63,7 @@ ABI_SYMBOLS = [
     "ssym_dtw_spot_step", "ssym_spot_queries_step", "ssym_dtw_spot_all_step",
     "ssym_dtw_align_step",
     "ssym_match_queries_step", "ssym_pair_matrix_step",
-    "ssym_dtw_cover", "ssym_dtw_cover_gaps",
+    "ssym_dtw_cover", "ssym_dtw_cover_gaps", "ssym_dtw_mosaic",
     "ssym_spotter_create_step",
     "ssym_coverer_create", "ssym_coverer_destroy", "ssym_coverer_push", "ssym_coverer_follow", "ssym_coverer_pieces",
     "ssym_coverer_flush", "ssym_coverer_best", "ssym_coverer_counts", "ssym_coverer_reset", "ssym_coverer_create_gaps",
@@ -267,6 +267,8 @@ def lib() -> ctypes.CDLL:
     L.ssym_dtw_cover.argtypes = [vp, vp, vp, f64, u32, vp, vp, vp, vp, vp, vp]
     L.ssym_dtw_cover_gaps.restype = i32
     L.ssym_dtw_cover_gaps.argtypes = [vp, vp, vp, f64, f64, u32, vp, vp, vp, vp, vp, vp]
+    L.ssym_dtw_mosaic.restype = i32
+    L.ssym_dtw_mosaic.argtypes = [vp, vp, vp, f64, f64, u32, vp, vp, vp, vp, vp, vp]
     L.ssym_dtw_align_step.restype = i32
     L.ssym_dtw_align_step.argtypes = [vp, vp, vp, vp, vp, u32, u32, u32, vp, vp, vp, vp, vp, vp, u32]
     L.ssym_dtw_spot.restype = i32

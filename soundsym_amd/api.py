@@ -614,6 +614,161 @@ class Cover:
         return "Cover(%d pieces, total=%r)" % (len(self.pieces), self.total)
 
 
+class MosaicPiece:
+    """One piece of a Mosaic: frames `start_frame` ... `end_frame` (INCLUSIVE) of the TARGET, played by frames
+    `source_first` ... `source_last` (INCLUSIVE) of dictionary sound `source_index` along `frame_map`, the sound's frame for
+    every frame of the piece (int64; it advances by 0, 1 or 2 per frame, never by 0 twice in a row).  `cost` is the chain of
+    the piece's frame costs, acc = c(first frame), acc = c + acc -- a sum over the piece's frames -- and `cost_per_frame`
+    is cost / num_frames(), a mean that compares across pieces."""
+
+    __slots__ = ("source_index", "source_first", "source_last", "start_frame", "end_frame", "cost", "frame_map")
+    is_gap = False
+
+    def __init__(self, source_index: int, source_first: int, source_last: int, start_frame: int, end_frame: int, cost: float,
+                 frame_map):
+        self.source_index, self.source_first, self.source_last = int(source_index), int(source_first), int(source_last)
+        self.start_frame, self.end_frame, self.cost = int(start_frame), int(end_frame), float(cost)
+        self.frame_map = np.asarray(frame_map, dtype=np.int64).reshape(-1).copy()
+        if self.source_index < 0 or not 0 <= self.start_frame <= self.end_frame:
+            raise ValueError("a piece spans start_frame ... end_frame with 0 <= start_frame <= end_frame and names a sound")
+        if self.frame_map.size != self.num_frames():
+            raise ValueError("a piece's frame_map holds one source frame per frame of the piece")
+        steps = np.diff(self.frame_map)
+        if (self.frame_map[0] != self.source_first or self.frame_map[-1] != self.source_last or self.source_first < 0
+                or ((steps < 0) | (steps > 2)).any() or ((steps[1:] == 0) & (steps[:-1] == 0)).any()):
+            raise ValueError("a piece's frame_map runs from source_first to source_last in steps of 0, 1 or 2, never 0 twice")
+
+    def num_frames(self) -> int:
+        return self.end_frame - self.start_frame + 1
+
+    @property
+    def cost_per_frame(self) -> float:
+        return self.cost / float(self.num_frames())
+
+    def sample_span(self, num_samples: int):
+        """(first sample, one past the last sample) of the piece in a target of num_samples samples: Piece.sample_span's rule."""
+        n = int(num_samples)
+        return (self.start_frame * HOP, min((self.end_frame + 1) * HOP, n))
+
+    def source_sample_span(self, num_samples: int):
+        """(first sample, one past the last sample) of source_first ... source_last in a recording of num_samples samples:
+        Spot.sample_span's rule."""
+        n = int(num_samples)
+        return (min(self.source_first * HOP, n), min((self.source_last + 1) * HOP, n))
+
+    def __repr__(self) -> str:
+        return "MosaicPiece(frames=%d...%d, source_index=%d, source frames=%d...%d, cost=%r)" % (
+            self.start_frame, self.end_frame, self.source_index, self.source_first, self.source_last, self.cost)
+
+
+def _mosaic_tiles(start, src, frame, frame_cost) -> List:
+    """The MosaicPieces and Gaps of one mosaic from what the library reports for one target: `start` its piece and gap-frame
+    starts (ascending), `src`, `frame` and `frame_cost` its frames.  A gap comes frame by frame, and a run of them is one
+    Gap at the sum of its frames' prices; a piece's cost is the chain of its frame costs."""
+    frames = len(src)
+    cuts = [int(s) for s in start] + [frames]
+    out = []
+    for s, e in zip(cuts[:-1], cuts[1:]):
+        if int(src[s]) == COVER_GAP:
+            if out and out[-1].is_gap:
+                run = out[-1]
+                out[-1] = Gap(run.start_frame, s, float(frame_cost[s]) * (s - run.start_frame + 1))
+            else:
+                out.append(Gap(s, s, float(frame_cost[s])))
+            continue
+        acc = float(frame_cost[s])
+        for j in range(s + 1, e):
+            acc = float(frame_cost[j]) + acc
+        out.append(MosaicPiece(src[s], frame[s], frame[e - 1], s, e - 1, acc, frame[s:e]))
+    return out
+
+
+class Mosaic:
+    """A target tiled by free spans of dictionary sounds (ssym_dtw_mosaic; definition in include/soundsym_amd.h and
+    DESIGN.md section 2 "Mosaic"): `pieces` in ascending start -- MosaicPieces and, with a gap_cost, Gaps (maximal runs of
+    uncovered frames; `is_gap` tells them apart) -- tiling frames 0 ... num_frames - 1 of the target; `total`, the least sum
+    over every mosaic of the frame costs, piece_penalty per piece and gap_cost per gap frame; `frame_costs`, c for every
+    target frame (gap_cost on a gap frame).  Every tiling has one cell per target frame, so `total_per_frame` = total /
+    num_frames is a mean per frame.  A target without a mosaic (no frames; a NaN frame without gaps) gives an empty Mosaic:
+    falsy, no pieces, total +inf."""
+
+    __slots__ = ("pieces", "total", "num_frames", "frame_costs")
+
+    def __init__(self, pieces, total: float, num_frames: int, frame_costs=None):
+        self.pieces, self.total, self.num_frames = list(pieces), float(total), int(num_frames)
+        self.frame_costs = (np.full(self.num_frames, float("inf")) if frame_costs is None else
+                            np.asarray(frame_costs, dtype=np.float64).reshape(-1).copy())
+        if self.num_frames < 0 or self.frame_costs.size != self.num_frames:
+            raise ValueError("a mosaic tiles num_frames >= 0 frames and holds one frame cost for each")
+        at, after_gap = 0, False
+        for p in self.pieces:
+            if not isinstance(p, (MosaicPiece, Gap)) or p.start_frame != at:
+                raise ValueError("the pieces of a mosaic tile the target: each starts where the one before it ended")
+            if p.is_gap and after_gap:
+                raise ValueError("a gap of a mosaic is a maximal run of frames: no gap follows a gap")
+            at, after_gap = p.end_frame + 1, p.is_gap
+        if self.pieces and at != self.num_frames:
+            raise ValueError("the pieces of a mosaic tile the target: the last one ends with it")
+
+    @staticmethod
+    def none(num_frames: int = 0) -> "Mosaic":
+        return Mosaic([], float("inf"), num_frames)
+
+    def __len__(self) -> int:
+        return len(self.pieces)
+
+    def __bool__(self) -> bool:
+        return bool(self.pieces)
+
+    @property
+    def total_per_frame(self) -> float:
+        return self.total / float(self.num_frames) if self.pieces else float("inf")
+
+    @property
+    def sounding(self) -> List["MosaicPiece"]:
+        """The MosaicPieces: the tiles a dictionary sound plays."""
+        return [p for p in self.pieces if not p.is_gap]
+
+    @property
+    def gaps(self) -> List["Gap"]:
+        """The Gaps: the maximal runs of frames left uncovered."""
+        return [p for p in self.pieces if p.is_gap]
+
+    def segment_lengths(self, num_samples: int) -> List[int]:
+        """The cut as lengths in samples, by Cover.segment_lengths' rule: num_frames() * HOP per tile, the last tile running
+        to the end of a sound of num_samples samples."""
+        n = int(num_samples)
+        if n < 0:
+            raise ValueError("num_samples must not be negative")
+        if not self.pieces:
+            return []
+        if self.pieces[-1].start_frame * HOP > n:
+            raise ValueError("the last piece starts beyond num_samples: the mosaic belongs to a longer sound")
+        return [p.num_frames() * HOP for p in self.pieces[:-1]] + [n - self.pieces[-1].start_frame * HOP]
+
+    def __repr__(self) -> str:
+        if not self.pieces:
+            return "Mosaic(empty)"
+        gaps = self.gaps
+        if gaps:
+            return "Mosaic(%d pieces, %d gaps, total=%r)" % (len(self.pieces) - len(gaps), len(gaps), self.total)
+        return "Mosaic(%d pieces, total=%r)" % (len(self.pieces), self.total)
+
+
+def _mosaics(off, count, total, start, src, frame, frame_cost) -> List["Mosaic"]:
+    """One Mosaic per target from the six arrays of ssym_dtw_mosaic and the query set's frame offsets."""
+    off = np.asarray(off, dtype=np.int64)
+    out = []
+    for t in range(off.size - 1):
+        a, b = int(off[t]), int(off[t + 1])
+        if not count[t]:
+            out.append(Mosaic.none(b - a))
+            continue
+        out.append(Mosaic(_mosaic_tiles(start[a:a + int(count[t])], src[a:b], frame[a:b], frame_cost[a:b]), total[t], b - a,
+                          frame_cost[a:b]))
+    return out
+
+
 def _cover_sounds(sound: "Sound", cover: "Cover") -> List["Sound"]:
     """The target cut at the cover's pieces: samples by segment_lengths (Piece.sample_span, the last piece running to the
     end of the sound), MFCC rows start_frame ... end_frame.  Gaps are cut out: only the sounding pieces come back."""
@@ -1172,6 +1327,77 @@ class SoundDictionary:
             b = a + int(count[t])
             out.append(Cover(_cover_tiles(src[a:b], start[a:b], end[a:b], cost[a:b]), total[t], frames))
         return out
+
+    def mosaic(self, targets: Sequence[Sound], piece_penalty: float = 0.0, gap_cost=None) -> List["Mosaic"]:
+        """Every target tiled by free spans of the dictionary's sounds, the cuts, the sounds, the spans and the paced paths
+        chosen together on the GPU for the least total (ssym_dtw_mosaic, one call; dtw engines without a band): neither
+        the targets nor the dictionary's recordings need cutting beforehand, and a recording may be of any length.
+        piece_penalty >= 0 is charged once per piece and trades total fit for fewer, longer pieces; at 0 the optimum is
+        frame-wise (a stretched span comes back in fragments), so ask with a penalty > 0.  gap_cost (None: no gaps):
+        target frames may stay uncovered at gap_cost >= 0 per frame; the Mosaic then holds Gaps among its MosaicPieces,
+        every target with a frame has a mosaic, and a NaN frame costs one gap frame, not the whole target."""
+        penalty, gap = self._cover_checks(piece_penalty, "mosaic"), _cover_gap_cost(gap_cost)
+        targets = list(targets)
+        if not targets:
+            return []
+        flat, off = pack_segments([t.mfccs() for t in targets], self._dim(), self.engine.np_dtype)
+        q = self.engine.queries(flat, off, self._dim())
+        try:
+            arrays = self.engine.dtw_mosaic(self.resident(), q, penalty, gap)
+        finally:
+            q.close()
+        return _mosaics(off, *arrays)
+
+    def reconstruct_mosaic(self, target: Sound, piece_penalty: float = 0.0, gap_cost=None, gap_fill: str = "silence",
+                           search: int = 0, want_pcm32: bool = False):
+        """mosaic, then warp: every sounding piece of the target's Mosaic is resynthesised from its span of its recording
+        along its frame_map, in ONE call of the existing window reconstruction (ssym_reconstruct_warped_spans, or with
+        search > 0 ssym_reconstruct_wsola_spans): the window is the piece's source_sample_span, the map frame_map -
+        source_first, the output length the piece's entry of Mosaic.segment_lengths.  Gaps' stretches are spliced in as
+        zeros (gap_fill="silence") or as the target's own samples ("target"), as reconstruct_covered does.  Returns
+        (mosaic, samples), with want_pcm32 (mosaic, samples, pcm); the samples are len(target.samples()); a target
+        without a mosaic gives silence."""
+        penalty, gap = _cover_penalty(piece_penalty), _cover_gap_cost(gap_cost)
+        search = _wsola_search(search)
+        if gap_fill not in ("silence", "target"):
+            raise ValueError('gap_fill must be "silence" or "target"')
+        if not isinstance(target, Sound):
+            raise ValueError("reconstruct_mosaic takes one Sound")
+        mosaic = self.mosaic([target], penalty, gap)[0]
+        smp = np.asarray(target.samples(), dtype=np.float64)
+        outs = [np.zeros(smp.size), np.zeros(smp.size, dtype=np.int32)][:2 if want_pcm32 else 1]
+        lengths = mosaic.segment_lengths(smp.size)
+        sounding = [(p, n) for p, n in zip(mosaic.pieces, lengths) if not p.is_gap]
+        if sounding:
+            idx = np.array([p.source_index for p, _ in sounding], dtype=np.uint32)
+            spans = [p.source_sample_span(self.sounds[p.source_index].samples().size) for p, _ in sounding]
+            w_first = np.array([a for a, _ in spans], dtype=np.uint64)
+            w_len = np.array([max(a, b) - a for a, b in spans], dtype=np.uint64)
+            out_off = np.concatenate([[0], np.cumsum([n for _, n in sounding])]).astype(np.uint64)
+            frames = np.array([p.num_frames() for p, _ in sounding], dtype=np.uint32)
+            m_off = np.concatenate([[0], np.cumsum(frames)]).astype(np.uint64)
+            maps = np.concatenate([p.frame_map - p.source_first for p, _ in sounding]).astype(np.uint32)
+            if search:
+                res = self.engine.reconstruct_wsola(self.resident_samples(), idx, out_off, maps, m_off, frames, None, search,
+                                                    want_pcm32, windows=(w_first, w_len))
+            else:
+                res = self.engine.reconstruct_warped(self.resident_samples(), idx, out_off, maps, m_off, frames, None,
+                                                     want_pcm32, windows=(w_first, w_len))
+            warped = res if isinstance(res, tuple) else (res,)
+        at = took = 0
+        for p, n in zip(mosaic.pieces, lengths):
+            if not p.is_gap:
+                for o, w in zip(outs, warped):
+                    o[at:at + n] = w[took:took + n]
+                took += n
+            elif gap_fill == "target":
+                outs[0][at:at + n] = smp[at:at + n]
+                if want_pcm32:
+                    with np.errstate(invalid="ignore", over="ignore"):
+                        x = np.nan_to_num(2147483647.0 * smp[at:at + n], nan=0.0)
+                        outs[1][at:at + n] = np.trunc(np.clip(x, -2147483648.0, 2147483647.0)).astype(np.int64).astype(np.int32)
+            at += n
+        return (mosaic,) + tuple(outs)
 
     def _cover_checks(self, piece_penalty, what: str) -> float:
         penalty = _cover_penalty(piece_penalty)

@@ -131,6 +131,7 @@ struct ssym_ctx {
     ssym::DeviceBuf part;       // refcos partial argmin
     ssym::DeviceBuf paced_part; // paced matching: per (source block, target) first minimum -- keys, costs, indices
     ssym::DeviceBuf cover_tab;  // cover: the per-block M / src tables and the chain's back-pointers
+    ssym::DeviceBuf mosaic_tab; // mosaic: per workgroup the E / N slabs, the direction bytes and the column picks; pos(g)
     ssym::DeviceBuf one_ticket; // refcos_match_one_kernel: the "last workgroup" counter (zero between calls)
     ssym::DeviceBuf out_idx, out_cost;  // staging for host outputs
     ssym::DeviceBuf zeros;      // 256 bytes of 0.0: what refcos_mfma_kernel's staging DMA reads beyond a segment's end

@@ -1181,6 +1181,29 @@ class Engine:
         nat.check(rc, self.ctx)
         return count, total, src, start, end, cost
 
+    def dtw_mosaic(self, d: _Handle, q: _Handle, piece_penalty: float = 0.0, gap_cost=None, on_device: bool = False):
+        """ssym_dtw_mosaic (dtw engines without a band): every target tiled by pieces, each piece any span of any
+        dictionary segment aligned under the paced pattern; cuts, segments, spans and paths chosen together, by the
+        definition in include/soundsym_amd.h ("Mosaic").  Neither side needs cutting beforehand and a segment may be
+        as long as a dictionary holds.  piece_penalty >= 0 is charged once per piece; gap_cost (None: no gaps) >= 0
+        is the price of a target frame left uncovered.  Returns (count uint32 [m], total f64 [m], start uint32 [F],
+        src uint32 [F], frame uint32 [F], frame_cost f64 [F]) with F the target frames of the whole query set: target
+        t's piece and gap-frame starts lie in start[q.offsets[t] ... q.offsets[t] + count[t] - 1], ascending (unused
+        slots NO_MATCH); src / frame / frame_cost hold the segment, the frame within it and c for every target frame
+        (a gap frame: nat.COVER_GAP, NO_MATCH, gap_cost; without a mosaic NO_MATCH, NO_MATCH, +inf: count 0, total
+        +inf).  on_device: SSYM_OUT_DEVICE, the six arrays as torch tensors in device memory."""
+        penalty, gap = _cover_penalty(piece_penalty), _cover_gap_cost(gap_cost)
+        m, frames = q.n, int(q.offsets[-1])
+        device = self.device if on_device else None
+        (count, pn), (total, pt), (start, pa), (src, ps), (frame, pf), (cost, pc) = (
+            _output(device, (rows,), t) for rows, t in ((m, np.uint32), (m, np.float64), (frames, np.uint32),
+                                                        (frames, np.uint32), (frames, np.uint32), (frames, np.float64)))
+        flags = 0 if device is None else nat.OUT_DEVICE
+        rc = nat.lib().ssym_dtw_mosaic(self.ctx, d.ptr, q.ptr, penalty, float("inf") if gap is None else gap, flags,
+                                       pn, pt, pa, ps, pf, pc)
+        nat.check(rc, self.ctx)
+        return count, total, start, src, frame, cost
+
     # -- feature front-end (F3) --------------------------------------------------------------
     def mfcc(self, samples, sample_rate: float, ncoeffs: int = 12, f_lo: float = 100.0, f_hi: float = 8000.0,
              pad_tail: bool = False, want_mean: bool = False):
