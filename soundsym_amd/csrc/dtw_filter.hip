@@ -16,6 +16,7 @@
 #include "ssym_internal.hpp"
 #include "dtw_filter_kernel.hpp"
 #include "dtw_filter_wg_kernel.hpp"
+#include "dtw_filter_wg2_kernel.hpp"
 #include "dtw_filter_pk_kernel.hpp"
 #include "dtw_filter_sp_kernel.hpp"
 #include "dtw_band_kernel.hpp"
@@ -30,6 +31,11 @@ namespace ssym {
 // launches of dtw_filter_wg_kernel in this process (run_kernel; read by ssym_debug_filter_wg_launches below: the tests'
 // proof of which kernel ran)
 static std::atomic<unsigned long long> g_filter_wg_launches{0};
+// ... and those of them that took dtw_filter_wg2_kernel, the two-pass sibling (ssym_debug_filter_wg2_launches)
+static std::atomic<unsigned long long> g_filter_wg2_launches{0};
+// SSYM_FILTER_WG2=0 (under SSYM_TEST_HOOKS, read per filter call by read_filter_knobs): two-pass launches of the plan's Wg
+// kind stay on dtw_filter_wg_kernel -- A/B runs from one library.  Not a knob of the plan: the plan is the same either way.
+static std::atomic<bool> g_filter_wg2{true};
 
 int filter_pieces(int dim)
 {
@@ -232,6 +238,7 @@ static int32_t ensure_records(ssym_ctx *ctx, const SegmentSet &set, double scale
 static FilterKnobs read_filter_knobs()
 {
     FilterKnobs k;
+    g_filter_wg2.store(true, std::memory_order_relaxed);
     if (!ssym_knob("SSYM_TEST_HOOKS"))
         return k;
     auto num = [](const char *name, int unset) {
@@ -244,6 +251,7 @@ static FilterKnobs read_filter_knobs()
     k.spMultipair = mp == 0 || mp == 2 ? mp : 1;
     k.spPairBlock = ssym_knob("SSYM_SP_PAIRBLOCK") ? std::max(num("SSYM_SP_PAIRBLOCK", 0), 0) : -1;
     k.wg = num("SSYM_FILTER_WG", k.wg) != 0;
+    g_filter_wg2.store(num("SSYM_FILTER_WG2", 1) != 0, std::memory_order_relaxed);
     k.skip0 = num("SSYM_FILTER_SKIP0", 1) != 0;
     k.nt8 = ssym_knob("SSYM_FILTER_NT8") != nullptr;
     k.oneLaunch = ssym_knob("SSYM_FILTER_ONE_LAUNCH") != nullptr;
@@ -282,6 +290,7 @@ struct FilterCall {
     const float *abandon;
     unsigned long long *colCtr;
     const uint32_t *candSlot;
+    bool wg2;                       // two-pass Wg launches on dtw_filter_wg2_kernel (SSYM_FILTER_WG2)
 };
 
 // One entry of the plan as the kernel launch it names: the instantiations of (tiles per pass, cost, operand planes).
@@ -323,6 +332,15 @@ static bool run_kernel(const FilterCall &c, const FilterLaunch &l)
         return false;
     case FilterKernel::Wg:
         if constexpr (NT == 4) {
+            // exactly two passes: both at once on two waves per pair, the hand-off in LDS (dtw_filter_wg2_kernel.hpp)
+            if (l.passes == 2 && c.wg2) {
+                dtw_filter_wg2_kernel<SQ, KU><<<grid, block, 0, c.st>>>(
+                    srec, trec, c.src.len, c.tgt.len, rowsPad, colsPad, tgtPad, nSrcPairs / 4, l.taskChunk, c.outScale, ctr,
+                    c.cmat, l.origin, l.lo);
+                g_filter_wg_launches.fetch_add(1, std::memory_order_relaxed);
+                g_filter_wg2_launches.fetch_add(1, std::memory_order_relaxed);
+                return true;
+            }
             dtw_filter_wg_kernel<SQ, KU><<<grid, block, 0, c.st>>>(
                 srec, trec, c.src.len, c.tgt.len, rowsPad, l.passes, colsPad, tgtPad, nSrcPairs / 4, l.taskChunk, c.outScale,
                 c.handoff, ctr, c.cmat, l.origin, l.lo);
@@ -537,7 +555,8 @@ int32_t launch_dtw_filter(ssym_ctx *ctx, const SegmentSet &src, const SegmentSet
     for (const FilterLaunch &l : plan)
         ctx->launched_cells += l.cells;
     const FilterCall call{ctx->stream, src, tgt, sq, in.ku, (float)(sq ? 1.0 / (scale * scale) : 1.0 / scale),
-                          (float *)ctx->handoff.ptr, taskCtr, cmat, abandon, colCtr, candSlot};
+                          (float *)ctx->handoff.ptr, taskCtr, cmat, abandon, colCtr, candSlot,
+                          g_filter_wg2.load(std::memory_order_relaxed)};
     for (const FilterLaunch &l : plan)
         if (!run_launch(call, l)) {
             ctx->err = "dtw filter: the plan names a kernel that is not built";
@@ -553,6 +572,12 @@ int32_t launch_dtw_filter(ssym_ctx *ctx, const SegmentSet &src, const SegmentSet
 extern "C" __attribute__((visibility("default"))) unsigned long long ssym_debug_filter_wg_launches(void)
 {
     return ssym::g_filter_wg_launches.load(std::memory_order_relaxed);
+}
+
+// ... and those of them that were launches of dtw_filter_wg2_kernel
+extern "C" __attribute__((visibility("default"))) unsigned long long ssym_debug_filter_wg2_launches(void)
+{
+    return ssym::g_filter_wg2_launches.load(std::memory_order_relaxed);
 }
 
 #ifdef SSYM_SP_PROF

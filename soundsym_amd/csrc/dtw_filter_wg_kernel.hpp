@@ -142,7 +142,11 @@ __global__ __launch_bounds__(64 * kFilterWavesPerBlock, 2) void dtw_filter_wg_ke
             const int rowBase = rowOrigin + pass * BR;
             // the pass kind, workgroup-uniform.  (Opaque scalar integers: as booleans the two live through the column loop as
             // lane masks that the compiler negates through a VGPR, two vector instructions per four columns each.)
+#ifdef SSYM_ABL_NOHAND      // tools only (as in dtw_filter_kernel): no hand-off DMA and no hand-off store -- wrong values, valid timing
+            int haveTop = 0, passesLeft = nPasses - 1 - pass;
+#else
             int haveTop = pass, passesLeft = nPasses - 1 - pass;      // a row above this pass; 0 in the last pass
+#endif
             asm volatile("" : "+s"(haveTop), "+s"(passesLeft));     // (and again before each test in the column loop: a hoisted compare is a mask again)
 
             // this wave's column of group gr: virtual column 4 gr + wave (clamped to the last real column) -> slot (4 gr + wave) & 15
@@ -265,7 +269,11 @@ __global__ __launch_bounds__(64 * kFilterWavesPerBlock, 2) void dtw_filter_wg_ke
                         SSYM_FILTER_SBASE(passesLeft);
                         if (passesLeft != 0) {
                             // top boundary of the next pass: a column's bottoms are 256 contiguous bytes
+#ifndef SSYM_ABL_NOHAND
                             __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(bottom), handBuf, lane * 4, g * 1024 + q * 256, 0);
+#else
+                            res = (j == fb_m1 - 1) ? bottom : res;
+#endif
                         } else {
                             res = (j == fb_m1) ? bottom : res;      // D(fa-1, fb-1)
                         }
