@@ -306,6 +306,20 @@ int32_t check_cover_ctx(ssym_ctx *ctx, const char *fn)
     return SSYM_OK;
 }
 
+// ... of the prices: per piece, and per frame left uncovered
+int32_t check_cover_prices(ssym_ctx *ctx, const char *fn, double piece_penalty, double gap_cost)
+{
+    if (!(piece_penalty >= 0.0) || std::isinf(piece_penalty)) {
+        ctx->err = std::string(fn) + ": piece_penalty must be finite and not negative";
+        return SSYM_E_INVALID;
+    }
+    if (!(gap_cost >= 0.0)) {
+        ctx->err = std::string(fn) + ": gap_cost must not be negative or NaN (+inf: no gaps)";
+        return SSYM_E_INVALID;
+    }
+    return SSYM_OK;
+}
+
 // ... and of a dictionary
 int32_t check_cover_dict(ssym_ctx *ctx, const char *fn, const SegmentSet &src)
 {
@@ -443,14 +457,9 @@ int32_t dtw_cover(ssym_ctx *ctx, const char *fn, const ssym_dict *dict, const ss
     rc = check_handles(ctx->err, fn, dict, q);
     if (rc != SSYM_OK)
         return rc;
-    if (!(piece_penalty >= 0.0) || std::isinf(piece_penalty)) {
-        ctx->err = std::string(fn) + ": piece_penalty must be finite and not negative";
-        return SSYM_E_INVALID;
-    }
-    if (!(gap_cost >= 0.0)) {
-        ctx->err = std::string(fn) + ": gap_cost must not be negative or NaN (+inf: no gaps)";
-        return SSYM_E_INVALID;
-    }
+    rc = check_cover_prices(ctx, fn, piece_penalty, gap_cost);
+    if (rc != SSYM_OK)
+        return rc;
     const SegmentSet &src = dict->set, &tgt = q->set;
     const uint32_t N = src.n, M = tgt.n;
     const uint64_t F = tgt.total_frames;
@@ -485,30 +494,17 @@ int32_t dtw_cover(ssym_ctx *ctx, const char *fn, const ssym_dict *dict, const ss
 
     Blocks bl(ctx);
     // outputs: the caller's device arrays in place, or one f64 and one u32 block copied back after the chain
-    const bool inPlace = (flags & SSYM_OUT_DEVICE) != 0;
-    double *dF64 = nullptr;
-    uint32_t *dU32 = nullptr;
+    StagedOut out(flags, {{out_total, M}, {out_cost, F}}, {{out_count, M}, {out_src, F}, {out_start, F}, {out_end, F}});
+    rc = out.alloc(bl);
+    if (rc != SSYM_OK)
+        return rc;
     ChainArgs c{};
-    if (inPlace) {
-        c.outCount = out_count;
-        c.outTotal = out_total;
-        c.outSrc = out_src;
-        c.outStart = out_start;
-        c.outEnd = out_end;
-        c.outCost = out_cost;
-    } else {
-        rc = bl.get(&dF64, (size_t)M + F);
-        if (rc == SSYM_OK)
-            rc = bl.get(&dU32, (size_t)M + 3 * F);
-        if (rc != SSYM_OK)
-            return rc;
-        c.outTotal = dF64;
-        c.outCost = dF64 + M;
-        c.outCount = dU32;
-        c.outSrc = dU32 + M;
-        c.outStart = c.outSrc + F;
-        c.outEnd = c.outStart + F;
-    }
+    c.outTotal = out.f64[0];
+    c.outCost = out.f64[1];
+    c.outCount = out.u32[0];
+    c.outSrc = out.u32[1];
+    c.outStart = out.u32[2];
+    c.outEnd = out.u32[3];
 
     hipEvent_t *ev = ctx->ev;
     SSYM_HIP_CHECK(ctx, hipEventRecord(ev[0], st));
@@ -533,21 +529,9 @@ int32_t dtw_cover(ssym_ctx *ctx, const char *fn, const ssym_dict *dict, const ss
     cover_chain_kernel<<<std::min<unsigned>(M, (unsigned)ctx->num_cus * 8), 64, 0, st>>>(c);
     SSYM_HIP_CHECK(ctx, hipGetLastError());
     SSYM_HIP_CHECK(ctx, hipEventRecord(ev[2], st));
-    if (inPlace) {
-        SSYM_HIP_CHECK(ctx, hipStreamSynchronize(st));
-    } else {
-        std::vector<double> hF64((size_t)M + F);
-        std::vector<uint32_t> hU32((size_t)M + 3 * F);
-        SSYM_HIP_CHECK(ctx, hipMemcpyAsync(hF64.data(), dF64, sizeof(double) * hF64.size(), hipMemcpyDeviceToHost, st));
-        SSYM_HIP_CHECK(ctx, hipMemcpyAsync(hU32.data(), dU32, sizeof(uint32_t) * hU32.size(), hipMemcpyDeviceToHost, st));
-        SSYM_HIP_CHECK(ctx, hipStreamSynchronize(st));
-        std::copy(hF64.begin(), hF64.begin() + M, out_total);
-        std::copy(hF64.begin() + M, hF64.end(), out_cost);
-        std::copy(hU32.begin(), hU32.begin() + M, out_count);
-        std::copy(hU32.begin() + M, hU32.begin() + M + F, out_src);
-        std::copy(hU32.begin() + M + F, hU32.begin() + M + 2 * F, out_start);
-        std::copy(hU32.begin() + M + 2 * F, hU32.end(), out_end);
-    }
+    rc = out.finish(ctx);
+    if (rc != SSYM_OK)
+        return rc;
     tm.main_ms = ev_ms(ev[0], ev[1]);
     tm.reduce_ms = ev_ms(ev[1], ev[2]);
     tm.total_ms = ev_ms(ev[0], ev[2]);

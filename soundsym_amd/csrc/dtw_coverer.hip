@@ -45,13 +45,13 @@
 // finite: lastFinite = n - 1, H(n) is never empty, and a NaN or +-inf frame is a gap frame the lane goes on past.
 #include "dtw_wave.hpp"
 #include "dtw_cover_chain.hpp"
+#include "lane_feed.hpp"
 
 #include <algorithm>
-#include <cmath>
 
 namespace ssym {
 
-constexpr uint64_t kCovererMaxLaneFrames = 0x7fffffffull;        // a lane's ends and cut points are reported as u32
+// (the frames a lane may consume: lane_feed.hpp's kLaneMaxFrames -- a lane's ends and cut points are reported as u32)
 constexpr uint32_t kCovererMaxLanes = 65535;                      // one grid row per lane
 constexpr uint64_t kCovererBackMin = 1024;                       // frames of the back-pointer store, a power of two
 
@@ -337,12 +337,6 @@ __global__ __launch_bounds__(256) void coverer_best_kernel(const CovLane *lanes,
         committed[l] = (uint32_t)(s.done + 1);
 }
 
-template <class T>
-int32_t alloc_n(ssym_ctx *ctx, T **p, size_t count)
-{
-    return dev_alloc(ctx, (void **)p, std::max<size_t>(count * sizeof(T), 8));
-}
-
 void coverer_free(ssym_ctx *ctx, ssym_coverer *cv)
 {
     for (void *p : {(void *)cv->tail, (void *)cv->ringD, (void *)cv->lanes, (void *)cv->dSteps, (void *)cv->dBufOff,
@@ -352,21 +346,9 @@ void coverer_free(ssym_ctx *ctx, ssym_coverer *cv)
     delete cv;
 }
 
-// what every call refuses before anything else
-int32_t check_handle(ssym_ctx *ctx, const ssym_coverer *cv, const char *fn)
-{
-    if (!cv) {
-        ctx->err = std::string(fn) + ": the coverer handle is NULL";
-        return SSYM_E_INVALID;
-    }
-    if (cv->ctx != ctx) {
-        ctx->err = std::string(fn) + ": the coverer belongs to another context";
-        return SSYM_E_INVALID;
-    }
-    return SSYM_OK;
-}
+constexpr const char *kNoun = "coverer";
 
-// ... and what a call that reads the dictionary refuses
+// what a call that reads the dictionary refuses
 int32_t check_dict(ssym_ctx *ctx, const ssym_coverer *cv, const char *fn)
 {
     if (cv->dict->set.n != cv->dictN || cv->dict->set.total_frames != cv->dictFrames) {
@@ -374,6 +356,13 @@ int32_t check_dict(ssym_ctx *ctx, const ssym_coverer *cv, const char *fn)
         return SSYM_E_INVALID;
     }
     return SSYM_OK;
+}
+
+// the coverer as the lane feed (lane_feed.hpp) sees it: a flushed lane has ended, and push and follow read the dictionary
+LaneFeed feed_of(ssym_ctx *ctx, const ssym_coverer *cv)
+{
+    return LaneFeed{kNoun, "out_n_pieces", cv->nLanes, cv->dim, cv->consumed, &cv->ended, true,
+                    [ctx, cv](const char *fn) { return check_dict(ctx, cv, fn); }};
 }
 
 uint64_t pow2_at_least(uint64_t x)
@@ -465,14 +454,9 @@ int32_t coverer_create(ssym_ctx *ctx, const char *fn, const ssym_dict *dict, uin
         ctx->err = std::string(fn) + ": the dictionary handle is NULL or n_lanes is 0";
         return SSYM_E_INVALID;
     }
-    if (!(piece_penalty >= 0.0) || std::isinf(piece_penalty)) {
-        ctx->err = std::string(fn) + ": piece_penalty must be finite and not negative";
-        return SSYM_E_INVALID;
-    }
-    if (!(gap_cost >= 0.0)) {
-        ctx->err = std::string(fn) + ": gap_cost must not be negative or NaN (+inf: no gaps)";
-        return SSYM_E_INVALID;
-    }
+    rc = check_cover_prices(ctx, fn, piece_penalty, gap_cost);
+    if (rc != SSYM_OK)
+        return rc;
     const SegmentSet &src = dict->set;
     if (src.n == 0) {
         ctx->err = std::string(fn) + ": empty dictionary";
@@ -506,7 +490,7 @@ int32_t coverer_create(ssym_ctx *ctx, const char *fn, const ssym_dict *dict, uin
     cv->dictFrames = src.total_frames;
     cv->penalty = piece_penalty;
     cv->gapCost = gap_cost;
-    cv->sliceMax = std::min<uint64_t>(lim.scratch_bytes / perFrame - (W - 1), kCovererMaxLaneFrames);
+    cv->sliceMax = std::min<uint64_t>(lim.scratch_bytes / perFrame - (W - 1), kLaneMaxFrames);
     cv->consumed.assign(n_lanes, 0);
     cv->done.assign(n_lanes, -1);
     cv->lastFinite.assign(n_lanes, -1);
@@ -695,130 +679,44 @@ int32_t coverer_run(ssym_ctx *ctx, ssym_coverer *cv, const std::vector<const dou
     return SSYM_OK;
 }
 
-// m frames more on a lane that has consumed n
-int32_t check_lane_room(ssym_ctx *ctx, const char *fn, uint32_t lane, uint64_t n, uint64_t m)
-{
-    if (m > kCovererMaxLaneFrames || n + m > kCovererMaxLaneFrames) {
-        ctx->err = std::string(fn) + ": lane " + std::to_string(lane) + " would consume more than 2^31 - 1 = " +
-                   std::to_string(kCovererMaxLaneFrames) + " frames";
-        return SSYM_E_UNSUPPORTED;
-    }
-    return SSYM_OK;
-}
+// push, follow and flush: the handle, the feed's checks and frames (lane_feed.hpp), then the run
 
 int32_t coverer_push(ssym_ctx *ctx, ssym_coverer *cv, const double *feats, const uint64_t *frame_offsets, uint32_t flags,
                      uint64_t *out_n_pieces)
 {
     const char *fn = "ssym_coverer_push";
-    int32_t rc = check_handle(ctx, cv, fn);
-    if (rc != SSYM_OK)
-        return rc;
-    if (!frame_offsets || !out_n_pieces) {
-        ctx->err = std::string(fn) + ": frame_offsets and out_n_pieces must not be NULL";
-        return SSYM_E_INVALID;
-    }
-    rc = check_dict(ctx, cv, fn);
-    if (rc != SSYM_OK)
-        return rc;
-    const uint32_t nL = cv->nLanes, dim = cv->dim;
-    std::vector<uint64_t> m(nL);
-    for (uint32_t l = 0; l < nL; ++l) {
-        if (frame_offsets[l + 1] < frame_offsets[l]) {
-            ctx->err = std::string(fn) + ": frame_offsets decrease";
-            return SSYM_E_INVALID;
-        }
-        m[l] = frame_offsets[l + 1] - frame_offsets[l];
-        if (m[l] && cv->ended[l]) {
-            ctx->err = std::string(fn) + ": lane " + std::to_string(l) + " was flushed and has ended; call ssym_coverer_reset";
-            return SSYM_E_INVALID;
-        }
-        rc = check_lane_room(ctx, fn, l, cv->consumed[l], m[l]);
-        if (rc != SSYM_OK)
-            return rc;
-    }
-    const uint64_t total = frame_offsets[nL] - frame_offsets[0];
-    if (total && !feats) {
-        ctx->err = std::string(fn) + ": feats is NULL";
-        return SSYM_E_INVALID;
-    }
-    SSYM_HIP_CHECK(ctx, hipSetDevice(ctx->device));
     Blocks bl(ctx);
-    double *block = nullptr;
-    std::vector<const double *> rows(nL, nullptr);
-    if (total) {
-        rc = bl.get(&block, (size_t)total * dim);
-        if (rc != SSYM_OK)
-            return rc;
-        SSYM_HIP_CHECK(ctx, hipMemcpyAsync(block, feats + frame_offsets[0] * dim, sizeof(double) * total * dim,
-                                           hipMemcpyHostToDevice, ctx->stream));
-        for (uint32_t l = 0; l < nL; ++l)
-            rows[l] = block + (frame_offsets[l] - frame_offsets[0]) * dim;
-    }
+    std::vector<const double *> rows;
+    std::vector<uint64_t> m;
+    int32_t rc = check_handle(ctx, cv, kNoun, fn);
+    if (rc == SSYM_OK)
+        rc = feed_of(ctx, cv).push(ctx, fn, feats, frame_offsets, out_n_pieces, bl, rows, m);
+    if (rc != SSYM_OK)
+        return rc;
     return coverer_run(ctx, cv, rows, m, kCoverNone, out_n_pieces);
 }
 
 int32_t coverer_follow(ssym_ctx *ctx, ssym_coverer *cv, const ssym_stream *stream, uint32_t flags, uint64_t *out_n_pieces)
 {
     const char *fn = "ssym_coverer_follow";
-    int32_t rc = check_handle(ctx, cv, fn);
+    std::vector<const double *> rows;
+    std::vector<uint64_t> m;
+    int32_t rc = check_handle(ctx, cv, kNoun, fn);
+    if (rc == SSYM_OK)
+        rc = feed_of(ctx, cv).follow(ctx, fn, stream, out_n_pieces, rows, m);
     if (rc != SSYM_OK)
         return rc;
-    if (!stream || !out_n_pieces) {
-        ctx->err = std::string(fn) + ": stream and out_n_pieces must not be NULL";
-        return SSYM_E_INVALID;
-    }
-    rc = check_dict(ctx, cv, fn);
-    if (rc != SSYM_OK)
-        return rc;
-    uint32_t lanes = 0, nc = 0;
-    const ssym_ctx *owner = nullptr;
-    stream_shape(stream, &lanes, &nc, &owner);
-    if (owner != ctx) {
-        ctx->err = std::string(fn) + ": the stream belongs to another context";
-        return SSYM_E_INVALID;
-    }
-    const uint32_t nL = cv->nLanes, dim = cv->dim;
-    if (lanes != nL || nc != dim) {
-        ctx->err = std::string(fn) + ": the stream has " + std::to_string(lanes) + " lanes of " + std::to_string(nc) +
-                   " coefficients, the coverer " + std::to_string(nL) + " lanes of " + std::to_string(dim) + " values";
-        return SSYM_E_INVALID;
-    }
-    std::vector<uint64_t> m(nL);
-    std::vector<const double *> rows(nL, nullptr);
-    for (uint32_t l = 0; l < nL; ++l) {
-        const double *frames = nullptr;
-        uint64_t held = 0;
-        if (ssym_stream_frames_device(stream, l, &frames, &held) != SSYM_OK) {
-            ctx->err = std::string(fn) + ": the stream does not answer for lane " + std::to_string(l);
-            return SSYM_E_INVALID;
-        }
-        if (held < cv->consumed[l]) {
-            ctx->err = std::string(fn) + ": lane " + std::to_string(l) + " of the stream holds " + std::to_string(held) +
-                       " frames, fewer than the " + std::to_string(cv->consumed[l]) +
-                       " consumed: after ssym_stream_reset call ssym_coverer_reset";
-            return SSYM_E_INVALID;
-        }
-        m[l] = cv->ended[l] ? 0 : held - cv->consumed[l];               // a lane that has ended is skipped
-        rc = check_lane_room(ctx, fn, l, cv->consumed[l], m[l]);
-        if (rc != SSYM_OK)
-            return rc;
-        rows[l] = m[l] ? frames + cv->consumed[l] * dim : nullptr;
-    }
-    SSYM_HIP_CHECK(ctx, hipSetDevice(ctx->device));
     return coverer_run(ctx, cv, rows, m, kCoverNone, out_n_pieces);
 }
 
 int32_t coverer_flush(ssym_ctx *ctx, ssym_coverer *cv, uint32_t lane, uint64_t *out_n_pieces)
 {
     const char *fn = "ssym_coverer_flush";
-    int32_t rc = check_handle(ctx, cv, fn);
+    int32_t rc = check_handle(ctx, cv, kNoun, fn);
+    if (rc == SSYM_OK)
+        rc = feed_of(ctx, cv).lane(ctx, fn, lane, true, out_n_pieces);
     if (rc != SSYM_OK)
         return rc;
-    if (lane >= cv->nLanes || !out_n_pieces) {
-        ctx->err = std::string(fn) + ": lane outside the coverer's lanes, or out_n_pieces is NULL";
-        return SSYM_E_INVALID;
-    }
-    SSYM_HIP_CHECK(ctx, hipSetDevice(ctx->device));
     const std::vector<const double *> rows(cv->nLanes, nullptr);
     const std::vector<uint64_t> m(cv->nLanes, 0);
     return coverer_run(ctx, cv, rows, m, lane, out_n_pieces);
@@ -827,14 +725,11 @@ int32_t coverer_flush(ssym_ctx *ctx, ssym_coverer *cv, uint32_t lane, uint64_t *
 int32_t coverer_reset(ssym_ctx *ctx, ssym_coverer *cv, uint32_t lane)
 {
     const char *fn = "ssym_coverer_reset";
-    int32_t rc = check_handle(ctx, cv, fn);
+    int32_t rc = check_handle(ctx, cv, kNoun, fn);
+    if (rc == SSYM_OK)
+        rc = feed_of(ctx, cv).lane(ctx, fn, lane, false, nullptr);
     if (rc != SSYM_OK)
         return rc;
-    if (lane >= cv->nLanes) {
-        ctx->err = std::string(fn) + ": lane outside the coverer's lanes";
-        return SSYM_E_INVALID;
-    }
-    SSYM_HIP_CHECK(ctx, hipSetDevice(ctx->device));
     coverer_init_kernel<<<(cv->ring + 255) / 256, 256, 0, ctx->stream>>>(cv->lanes, cv->ringD, cv->ring, lane, 1u);
     SSYM_HIP_CHECK(ctx, hipGetLastError());
     SSYM_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
@@ -844,20 +739,10 @@ int32_t coverer_reset(ssym_ctx *ctx, ssym_coverer *cv, uint32_t lane)
     return SSYM_OK;
 }
 
-// n values of T from device memory to an output that is host memory, or device memory with SSYM_OUT_DEVICE
-template <class T>
-int32_t copy_out(ssym_ctx *ctx, T *out, const T *dev, size_t n, bool outDev)
-{
-    if (out && n)
-        SSYM_HIP_CHECK(ctx, hipMemcpyAsync(out, dev, sizeof(T) * n, outDev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost,
-                                           ctx->stream));
-    return SSYM_OK;
-}
-
 int32_t coverer_pieces(ssym_ctx *ctx, const ssym_coverer *cv, uint32_t *out_lane, uint32_t *out_src, uint32_t *out_start,
                        uint32_t *out_end, double *out_cost, uint32_t flags)
 {
-    int32_t rc = check_handle(ctx, cv, "ssym_coverer_pieces");
+    int32_t rc = check_handle(ctx, cv, kNoun, "ssym_coverer_pieces");
     if (rc != SSYM_OK)
         return rc;
     SSYM_HIP_CHECK(ctx, hipSetDevice(ctx->device));
@@ -886,7 +771,7 @@ int32_t coverer_pieces(ssym_ctx *ctx, const ssym_coverer *cv, uint32_t *out_lane
 int32_t coverer_best(ssym_ctx *ctx, const ssym_coverer *cv, double *out_total, uint32_t *out_covered, uint32_t *out_committed,
                      uint32_t flags)
 {
-    int32_t rc = check_handle(ctx, cv, "ssym_coverer_best");
+    int32_t rc = check_handle(ctx, cv, kNoun, "ssym_coverer_best");
     if (rc != SSYM_OK)
         return rc;
     if (!out_total && !out_covered && !out_committed)

@@ -356,14 +356,9 @@ int32_t dtw_mosaic(ssym_ctx *ctx, const ssym_dict *dict, const ssym_queries *q, 
     rc = check_handles(ctx->err, fn, dict, q);
     if (rc != SSYM_OK)
         return rc;
-    if (!(piece_penalty >= 0.0) || std::isinf(piece_penalty)) {
-        ctx->err = std::string(fn) + ": piece_penalty must be finite and not negative";
-        return SSYM_E_INVALID;
-    }
-    if (!(gap_cost >= 0.0)) {
-        ctx->err = std::string(fn) + ": gap_cost must not be negative or NaN (+inf: no gaps)";
-        return SSYM_E_INVALID;
-    }
+    rc = check_cover_prices(ctx, fn, piece_penalty, gap_cost);
+    if (rc != SSYM_OK)
+        return rc;
     const SegmentSet &src = dict->set, &tgt = q->set;
     const uint32_t M = tgt.n;
     const uint64_t F = tgt.total_frames, G = src.total_frames;
@@ -399,30 +394,18 @@ int32_t dtw_mosaic(ssym_ctx *ctx, const ssym_dict *dict, const ssym_queries *q, 
     hipStream_t st = ctx->stream;
 
     Blocks bl(ctx);
-    const bool inPlace = (flags & SSYM_OUT_DEVICE) != 0;
-    double *dF64 = nullptr;
-    uint32_t *dU32 = nullptr;
+    // outputs, every one nullable: the caller's device arrays in place, or one f64 and one u32 block copied back at the end
+    StagedOut out(flags, {{out_total, M}, {out_frame_cost, F}}, {{out_count, M}, {out_start, F}, {out_src, F}, {out_frame, F}});
+    rc = out.alloc(bl);
+    if (rc != SSYM_OK)
+        return rc;
     MosaicArgs a{};
-    if (inPlace) {
-        a.outCount = out_count;
-        a.outTotal = out_total;
-        a.outStart = out_start;
-        a.outSrc = out_src;
-        a.outFrame = out_frame;
-        a.outCost = out_frame_cost;
-    } else {
-        rc = bl.get(&dF64, (size_t)M + F);
-        if (rc == SSYM_OK)
-            rc = bl.get(&dU32, (size_t)M + 3 * F);
-        if (rc != SSYM_OK)
-            return rc;
-        a.outTotal = dF64;
-        a.outCost = dF64 + M;
-        a.outCount = dU32;
-        a.outStart = dU32 + M;
-        a.outSrc = a.outStart + F;
-        a.outFrame = a.outSrc + F;
-    }
+    a.outTotal = out.f64[0];
+    a.outCost = out.f64[1];
+    a.outCount = out.u32[0];
+    a.outStart = out.u32[1];
+    a.outSrc = out.u32[2];
+    a.outFrame = out.u32[3];
 
     // fewer workgroups than targets where the slabs would pass the cap: rounds of `grid` targets on the same slabs
     const uint64_t slab = mosaic_slab_bytes(G, maxT);
@@ -469,27 +452,9 @@ int32_t dtw_mosaic(ssym_ctx *ctx, const ssym_dict *dict, const ssym_queries *q, 
         ++tm.main_launches;
     }
     SSYM_HIP_CHECK(ctx, hipEventRecord(ev[2], st));
-    if (inPlace) {
-        SSYM_HIP_CHECK(ctx, hipStreamSynchronize(st));
-    } else {
-        std::vector<double> hF64((size_t)M + F);
-        std::vector<uint32_t> hU32((size_t)M + 3 * F);
-        SSYM_HIP_CHECK(ctx, hipMemcpyAsync(hF64.data(), dF64, sizeof(double) * hF64.size(), hipMemcpyDeviceToHost, st));
-        SSYM_HIP_CHECK(ctx, hipMemcpyAsync(hU32.data(), dU32, sizeof(uint32_t) * hU32.size(), hipMemcpyDeviceToHost, st));
-        SSYM_HIP_CHECK(ctx, hipStreamSynchronize(st));
-        if (out_total)
-            std::copy(hF64.begin(), hF64.begin() + M, out_total);
-        if (out_frame_cost)
-            std::copy(hF64.begin() + M, hF64.end(), out_frame_cost);
-        if (out_count)
-            std::copy(hU32.begin(), hU32.begin() + M, out_count);
-        if (out_start)
-            std::copy(hU32.begin() + M, hU32.begin() + M + F, out_start);
-        if (out_src)
-            std::copy(hU32.begin() + M + F, hU32.begin() + M + 2 * F, out_src);
-        if (out_frame)
-            std::copy(hU32.begin() + M + 2 * F, hU32.end(), out_frame);
-    }
+    rc = out.finish(ctx);
+    if (rc != SSYM_OK)
+        return rc;
     tm.main_ms = ev_ms(ev[1], ev[2]);
     tm.total_ms = ev_ms(ev[0], ev[2]);
     ctx->timings = tm;

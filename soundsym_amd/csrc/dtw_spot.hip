@@ -493,7 +493,7 @@ int32_t launch_spot(ssym_ctx *ctx, const Args &a, const WaveGeom &g, unsigned gr
 
 // what ends a call: the outputs back (the call's one synchronisation) and the timings (folded: spot_queries' fold ran
 // between ev[1] and ev[2])
-int32_t spot_finish(ssym_ctx *ctx, SpotOut &out, uint32_t n_pairs, bool folded = false)
+int32_t spot_finish(ssym_ctx *ctx, StagedOut &out, uint32_t n_pairs, bool folded = false)
 {
     const int32_t rc = out.finish(ctx);
     if (rc != SSYM_OK)
@@ -537,7 +537,7 @@ int32_t dtw_spot(ssym_ctx *ctx, const ssym_dict *dict, const ssym_queries *q, co
     SSYM_HIP_CHECK(ctx, hipSetDevice(ctx->device));
 
     Blocks bl(ctx);
-    SpotOut out(flags, out_cost, n_pairs, {{out_start, n_pairs}, {out_end, n_pairs}});
+    StagedOut out(flags, {{out_cost, n_pairs}}, {{out_start, n_pairs}, {out_end, n_pairs}});
     rc = out.alloc(bl);
     if (rc == SSYM_OK)
         rc = pairs.upload(ctx, bl);
@@ -545,7 +545,7 @@ int32_t dtw_spot(ssym_ctx *ctx, const ssym_dict *dict, const ssym_queries *q, co
         return rc;
     const WaveGeom g = wave_geom(ctx, maxFb, src.dim, n_pairs);
     SpotArgs a{};
-    spot_fill(a, ctx, src, tgt, pairs.dev, n_pairs, g, out.cost, out.words[0].dev, out.words[1].dev);
+    spot_fill(a, ctx, src, tgt, pairs.dev, n_pairs, g, out.f64[0], out.u32[0], out.u32[1]);
     rc = launch_spot(ctx, a, g, g.grid, step);
     if (rc != SSYM_OK)
         return rc;
@@ -607,7 +607,7 @@ int32_t dtw_spot_all(ssym_ctx *ctx, const ssym_dict *dict, const ssym_queries *q
         g.grid, std::max<uint64_t>(1, kSpotAllScratchBytes / (a.slotFrames * (sizeof(double) + sizeof(uint32_t)))));
 
     Blocks bl(ctx);
-    SpotOut out(flags, out_cost, nOut, {{out_start, nOut}, {out_end, nOut}, {out_count, n_pairs}});
+    StagedOut out(flags, {{out_cost, nOut}}, {{out_start, nOut}, {out_end, nOut}, {out_count, n_pairs}});
     double *dMax = nullptr;
     if (max_cost)
         rc = bl.get(&dMax, n_pairs);
@@ -623,9 +623,9 @@ int32_t dtw_spot_all(ssym_ctx *ctx, const ssym_dict *dict, const ssym_queries *q
         return rc;
     if (max_cost)
         SSYM_HIP_CHECK(ctx, hipMemcpyAsync(dMax, max_cost, sizeof(double) * n_pairs, hipMemcpyHostToDevice, ctx->stream));
-    spot_fill(a, ctx, src, tgt, pairs.dev, n_pairs, g, out.cost, out.words[0].dev, out.words[1].dev);
+    spot_fill(a, ctx, src, tgt, pairs.dev, n_pairs, g, out.f64[0], out.u32[0], out.u32[1]);
     a.maxSpots = max_spots;
-    a.count = out.words[2].dev;
+    a.count = out.u32[2];
     a.maxCost = dMax;
     rc = launch_spot(ctx, a, g, grid, step);
     if (rc != SSYM_OK)
@@ -668,7 +668,7 @@ int32_t spot_queries(ssym_ctx *ctx, const ssym_dict *dict, const ssym_queries *q
 
     // every (source, target) into scratch, then the fold into the outputs
     Blocks bl(ctx);
-    SpotOut out(flags, out_cost, M, {{out_idx, M}, {out_start, M}, {out_end, M}});
+    StagedOut out(flags, {{out_cost, M}}, {{out_idx, M}, {out_start, M}, {out_end, M}});
     double *mCost = nullptr;
     uint32_t *mSpan = nullptr;
     rc = bl.get(&mCost, nPairs);
@@ -684,8 +684,8 @@ int32_t spot_queries(ssym_ctx *ctx, const ssym_dict *dict, const ssym_queries *q
     rc = launch_spot(ctx, a, g, g.grid, step);
     if (rc != SSYM_OK)
         return rc;
-    spot_fold_kernel<<<(M + 255) / 256, 256, 0, st>>>(mCost, mSpan, mSpan + nPairs, N, M, index_base, out.words[0].dev, out.cost,
-                                                      out.words[1].dev, out.words[2].dev);
+    spot_fold_kernel<<<(M + 255) / 256, 256, 0, st>>>(mCost, mSpan, mSpan + nPairs, N, M, index_base, out.u32[0], out.f64[0],
+                                                      out.u32[1], out.u32[2]);
     SSYM_HIP_CHECK(ctx, hipGetLastError());
     SSYM_HIP_CHECK(ctx, hipEventRecord(ctx->ev[2], st));
     return spot_finish(ctx, out, nPairs, true);

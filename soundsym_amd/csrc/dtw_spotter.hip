@@ -35,6 +35,7 @@
 // c0 + R - 2 (for first + c0 + R = 1 a row that does not exist, written as (+inf, none) and never read: "second row above
 // exists" is first + c0 >= 2).  A row that does not exist yet is neither loaded from the state nor read from LDS.
 #include "dtw_wave.hpp"
+#include "lane_feed.hpp"
 
 #include <algorithm>
 #include <numeric>
@@ -42,12 +43,12 @@
 namespace ssym {
 
 // Limits (soundsym_amd.h "Watching"; ssym_dtw_spot's for a target, refused by the same check_spot_limits): frames of a
-// target, values per frame; frames a lane may consume (st is u32 and 0xffffffff means none: the dictionary's own limit)
+// target, values per frame; the frames a lane may consume are lane_feed.hpp's kLaneMaxFrames (st is u32 and 0xffffffff
+// means none: the dictionary's own limit)
 constexpr uint64_t kSpotterMaxTargetFrames = 4096;
 constexpr uint32_t kSpotterMaxDim = 64;
 // under SSYM_STEP_PACED: dtw_spot.hip's kPacedMaxTargetFrames, for its reason (two hand-off rows and the ring within LDS)
 constexpr uint64_t kSpotterPacedMaxTargetFrames = 2048;
-constexpr uint64_t kSpotterMaxLaneFrames = 2147483647;           // 2^31 - 1
 // the profile of one forward launch stays within ssym_dtw_spot_all's scratch limit: a longer push runs as several slices
 // of rows, which the carried state makes exact
 constexpr size_t kSpotterScratchBytes = (size_t)512 << 20;
@@ -600,24 +601,12 @@ void spotter_free(ssym_ctx *ctx, ssym_spotter *sp)
     delete sp;
 }
 
-template <class T>
-int32_t alloc_n(ssym_ctx *ctx, T **p, size_t count)
-{
-    return dev_alloc(ctx, (void **)p, std::max<size_t>(count * sizeof(T), 8));
-}
+constexpr const char *kNoun = "spotter";
 
-// what every call refuses before anything else
-int32_t check_handle(ssym_ctx *ctx, const ssym_spotter *sp, const char *fn)
+// the spotter as the lane feed (lane_feed.hpp) sees it: lanes never end, and without pairs a push has nothing to upload
+LaneFeed feed_of(const ssym_spotter *sp)
 {
-    if (!sp) {
-        ctx->err = std::string(fn) + ": the spotter handle is NULL";
-        return SSYM_E_INVALID;
-    }
-    if (sp->ctx != ctx) {
-        ctx->err = std::string(fn) + ": the spotter belongs to another context";
-        return SSYM_E_INVALID;
-    }
-    return SSYM_OK;
+    return LaneFeed{kNoun, "out_n_events", sp->nLanes, sp->q->set.dim, sp->consumed, nullptr, sp->nPairs != 0, nullptr};
 }
 
 // fn: ssym_spotter_create (step = SSYM_STEP_SYMMETRIC) or ssym_spotter_create_step
@@ -960,58 +949,20 @@ int32_t spotter_run(ssym_ctx *ctx, ssym_spotter *sp, const std::vector<const dou
     return SSYM_OK;
 }
 
-// m frames more on a lane that has consumed n
-int32_t check_lane_room(ssym_ctx *ctx, const char *fn, uint32_t lane, uint64_t n, uint64_t m)
-{
-    if (m > kSpotterMaxLaneFrames || n + m > kSpotterMaxLaneFrames) {
-        ctx->err = std::string(fn) + ": lane " + std::to_string(lane) + " would consume more than 2^31 - 1 = " +
-                   std::to_string(kSpotterMaxLaneFrames) + " frames";
-        return SSYM_E_UNSUPPORTED;
-    }
-    return SSYM_OK;
-}
+// push, follow and flush: the handle, the feed's checks and frames (lane_feed.hpp), then the run
 
 int32_t spotter_push(ssym_ctx *ctx, ssym_spotter *sp, const double *feats, const uint64_t *frame_offsets, uint32_t flags,
                      uint64_t *out_n_events, double *out_prof_d, uint32_t *out_prof_s)
 {
     const char *fn = "ssym_spotter_push";
-    int32_t rc = check_handle(ctx, sp, fn);
+    Blocks bl(ctx);
+    std::vector<const double *> rows;
+    std::vector<uint64_t> m;
+    int32_t rc = check_handle(ctx, sp, kNoun, fn);
+    if (rc == SSYM_OK)
+        rc = feed_of(sp).push(ctx, fn, feats, frame_offsets, out_n_events, bl, rows, m);
     if (rc != SSYM_OK)
         return rc;
-    if (!frame_offsets || !out_n_events) {
-        ctx->err = std::string(fn) + ": frame_offsets and out_n_events must not be NULL";
-        return SSYM_E_INVALID;
-    }
-    const uint32_t nL = sp->nLanes, dim = sp->q->set.dim;
-    std::vector<uint64_t> m(nL);
-    for (uint32_t l = 0; l < nL; ++l) {
-        if (frame_offsets[l + 1] < frame_offsets[l]) {
-            ctx->err = std::string(fn) + ": frame_offsets decrease";
-            return SSYM_E_INVALID;
-        }
-        m[l] = frame_offsets[l + 1] - frame_offsets[l];
-        rc = check_lane_room(ctx, fn, l, sp->consumed[l], m[l]);
-        if (rc != SSYM_OK)
-            return rc;
-    }
-    const uint64_t total = frame_offsets[nL] - frame_offsets[0];
-    if (total && !feats) {
-        ctx->err = std::string(fn) + ": feats is NULL";
-        return SSYM_E_INVALID;
-    }
-    SSYM_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-    Blocks bl(ctx);
-    double *block = nullptr;
-    std::vector<const double *> rows(nL, nullptr);
-    if (total && sp->nPairs) {
-        rc = bl.get(&block, (size_t)total * dim);
-        if (rc != SSYM_OK)
-            return rc;
-        SSYM_HIP_CHECK(ctx, hipMemcpyAsync(block, feats + frame_offsets[0] * dim, sizeof(double) * total * dim,
-                                           hipMemcpyHostToDevice, ctx->stream));
-        for (uint32_t l = 0; l < nL; ++l)
-            rows[l] = block + (frame_offsets[l] - frame_offsets[0]) * dim;
-    }
     return spotter_run(ctx, sp, rows, m, kNone, flags, out_n_events, out_prof_d, out_prof_s);
 }
 
@@ -1019,62 +970,24 @@ int32_t spotter_follow(ssym_ctx *ctx, ssym_spotter *sp, const ssym_stream *strea
                        double *out_prof_d, uint32_t *out_prof_s)
 {
     const char *fn = "ssym_spotter_follow";
-    int32_t rc = check_handle(ctx, sp, fn);
+    std::vector<const double *> rows;
+    std::vector<uint64_t> m;
+    int32_t rc = check_handle(ctx, sp, kNoun, fn);
+    if (rc == SSYM_OK)
+        rc = feed_of(sp).follow(ctx, fn, stream, out_n_events, rows, m);
     if (rc != SSYM_OK)
         return rc;
-    if (!stream || !out_n_events) {
-        ctx->err = std::string(fn) + ": stream and out_n_events must not be NULL";
-        return SSYM_E_INVALID;
-    }
-    uint32_t lanes = 0, nc = 0;
-    const ssym_ctx *owner = nullptr;
-    stream_shape(stream, &lanes, &nc, &owner);
-    if (owner != ctx) {
-        ctx->err = std::string(fn) + ": the stream belongs to another context";
-        return SSYM_E_INVALID;
-    }
-    const uint32_t nL = sp->nLanes, dim = sp->q->set.dim;
-    if (lanes != nL || nc != dim) {
-        ctx->err = std::string(fn) + ": the stream has " + std::to_string(lanes) + " lanes of " + std::to_string(nc) +
-                   " coefficients, the spotter " + std::to_string(nL) + " lanes of " + std::to_string(dim) + " values";
-        return SSYM_E_INVALID;
-    }
-    std::vector<uint64_t> m(nL);
-    std::vector<const double *> rows(nL, nullptr);
-    for (uint32_t l = 0; l < nL; ++l) {
-        const double *frames = nullptr;
-        uint64_t held = 0;
-        if (ssym_stream_frames_device(stream, l, &frames, &held) != SSYM_OK) {
-            ctx->err = std::string(fn) + ": the stream does not answer for lane " + std::to_string(l);
-            return SSYM_E_INVALID;
-        }
-        if (held < sp->consumed[l]) {
-            ctx->err = std::string(fn) + ": lane " + std::to_string(l) + " of the stream holds " + std::to_string(held) +
-                       " frames, fewer than the " + std::to_string(sp->consumed[l]) +
-                       " consumed: after ssym_stream_reset call ssym_spotter_reset";
-            return SSYM_E_INVALID;
-        }
-        m[l] = held - sp->consumed[l];
-        rc = check_lane_room(ctx, fn, l, sp->consumed[l], m[l]);
-        if (rc != SSYM_OK)
-            return rc;
-        rows[l] = m[l] ? frames + sp->consumed[l] * dim : nullptr;       // read in place: no copy
-    }
-    SSYM_HIP_CHECK(ctx, hipSetDevice(ctx->device));
     return spotter_run(ctx, sp, rows, m, kNone, flags, out_n_events, out_prof_d, out_prof_s);
 }
 
 int32_t spotter_flush(ssym_ctx *ctx, ssym_spotter *sp, uint32_t lane, uint64_t *out_n_events)
 {
     const char *fn = "ssym_spotter_flush";
-    int32_t rc = check_handle(ctx, sp, fn);
+    int32_t rc = check_handle(ctx, sp, kNoun, fn);
+    if (rc == SSYM_OK)
+        rc = feed_of(sp).lane(ctx, fn, lane, true, out_n_events);
     if (rc != SSYM_OK)
         return rc;
-    if (lane >= sp->nLanes || !out_n_events) {
-        ctx->err = std::string(fn) + ": lane outside the spotter's lanes, or out_n_events is NULL";
-        return SSYM_E_INVALID;
-    }
-    SSYM_HIP_CHECK(ctx, hipSetDevice(ctx->device));
     const std::vector<const double *> rows(sp->nLanes, nullptr);
     const std::vector<uint64_t> m(sp->nLanes, 0);
     return spotter_run(ctx, sp, rows, m, lane, 0, out_n_events, nullptr, nullptr);
@@ -1083,14 +996,11 @@ int32_t spotter_flush(ssym_ctx *ctx, ssym_spotter *sp, uint32_t lane, uint64_t *
 int32_t spotter_reset(ssym_ctx *ctx, ssym_spotter *sp, uint32_t lane)
 {
     const char *fn = "ssym_spotter_reset";
-    int32_t rc = check_handle(ctx, sp, fn);
+    int32_t rc = check_handle(ctx, sp, kNoun, fn);
+    if (rc == SSYM_OK)
+        rc = feed_of(sp).lane(ctx, fn, lane, false, nullptr);
     if (rc != SSYM_OK)
         return rc;
-    if (lane >= sp->nLanes) {
-        ctx->err = std::string(fn) + ": lane outside the spotter's lanes";
-        return SSYM_E_INVALID;
-    }
-    SSYM_HIP_CHECK(ctx, hipSetDevice(ctx->device));
     if (sp->nTgt) {
         spotter_init_kernel<<<(sp->nTgt + 255) / 256, 256, 0, ctx->stream>>>(init_args(sp), lane * sp->nTgt, sp->nTgt);
         SSYM_HIP_CHECK(ctx, hipGetLastError());
@@ -1100,20 +1010,10 @@ int32_t spotter_reset(ssym_ctx *ctx, ssym_spotter *sp, uint32_t lane)
     return SSYM_OK;
 }
 
-// n values of T from device memory to an output that is host memory, or device memory with SSYM_OUT_DEVICE
-template <class T>
-int32_t copy_out(ssym_ctx *ctx, T *out, const T *dev, size_t n, bool outDev)
-{
-    if (out && n)
-        SSYM_HIP_CHECK(ctx, hipMemcpyAsync(out, dev, sizeof(T) * n, outDev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost,
-                                           ctx->stream));
-    return SSYM_OK;
-}
-
 int32_t spotter_events(ssym_ctx *ctx, const ssym_spotter *sp, uint32_t *out_lane, uint32_t *out_target, double *out_cost,
                        uint32_t *out_start, uint32_t *out_end, uint32_t flags)
 {
-    int32_t rc = check_handle(ctx, sp, "ssym_spotter_events");
+    int32_t rc = check_handle(ctx, sp, kNoun, "ssym_spotter_events");
     if (rc != SSYM_OK || sp->nEvents == 0)
         return rc;
     SSYM_HIP_CHECK(ctx, hipSetDevice(ctx->device));
@@ -1132,7 +1032,7 @@ int32_t spotter_events(ssym_ctx *ctx, const ssym_spotter *sp, uint32_t *out_lane
 int32_t spotter_best(ssym_ctx *ctx, const ssym_spotter *sp, double *out_cost, uint32_t *out_start, uint32_t *out_end,
                      uint32_t flags)
 {
-    int32_t rc = check_handle(ctx, sp, "ssym_spotter_best");
+    int32_t rc = check_handle(ctx, sp, kNoun, "ssym_spotter_best");
     if (rc != SSYM_OK || sp->nPairs == 0)
         return rc;
     SSYM_HIP_CHECK(ctx, hipSetDevice(ctx->device));

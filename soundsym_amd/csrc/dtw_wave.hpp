@@ -291,43 +291,65 @@ inline size_t spot_lds_bytes(const WaveGeom &g, uint32_t step)
     return rows * g.fbCap * (sizeof(double) + sizeof(uint32_t)) + g.ringBytes;
 }
 
-// The output rule of the spot drivers: one f64 array and up to three u32 arrays.  Host outputs: the kernel writes device
-// scratch (alloc) -- the f64 array a block of its own, the u32 arrays packed into ONE block in the order given -- and
-// finish enqueues one copy back of each, synchronises and hands the words to the caller's arrays.  SSYM_OUT_DEVICE: the
-// kernel writes the caller's arrays in place and finish only synchronises.  Either way: the call's one synchronisation.
-struct SpotOut {
-    struct Words {
-        uint32_t *out;           // the caller's array
+// The output rule of the calls that give several arrays of f64 and of u32 (the spot drivers, dtw_cover.hip, dtw_mosaic.hip).
+// Host outputs: the kernel writes device scratch (alloc) -- the f64 arrays packed into ONE block in the order given, the u32
+// arrays into another; an output that is NULL has scratch like any other -- and finish enqueues one copy back of each block,
+// synchronises and hands the values to the caller's arrays that are not NULL.  SSYM_OUT_DEVICE: the kernel writes the
+// caller's arrays in place (a NULL is handed through as it is) and finish only synchronises.  Either way: the call's one
+// synchronisation.
+template <class T>
+struct OutBlock {
+    struct Part {
+        T *out;                  // the caller's array
         size_t n;
-        uint32_t *dev;           // where the kernel writes
+        T *dev;                  // where the kernel writes
     };
-    bool inPlace;
-    double *outCost, *cost;      // the caller's array, and where the kernel writes
-    size_t nCost;
-    Words words[3];
-    size_t nArrays = 0, nWords = 0;
+    std::vector<Part> parts;
+    size_t total = 0;
 
-    SpotOut(uint32_t flags, double *out_cost, size_t n_cost, std::initializer_list<std::pair<uint32_t *, size_t>> list)
-        : inPlace((flags & SSYM_OUT_DEVICE) != 0), outCost(out_cost), cost(out_cost), nCost(n_cost)
+    OutBlock(std::initializer_list<std::pair<T *, size_t>> list)
     {
-        for (const auto &w : list) {
-            words[nArrays++] = Words{w.first, w.second, w.first};
-            nWords += w.second;
+        for (const auto &a : list) {
+            parts.push_back(Part{a.first, a.second, a.first});
+            total += a.second;
         }
+    }
+    T *operator[](size_t i) const { return parts[i].dev; }
+    int32_t alloc(Blocks &bl)
+    {
+        T *block = nullptr;
+        const int32_t rc = bl.get(&block, total);
+        for (Part &p : parts) {
+            p.dev = block;
+            block += p.n;
+        }
+        return rc;
+    }
+    void hand_over(const T *from) const
+    {
+        for (const Part &p : parts) {
+            if (p.out)
+                std::copy(from, from + p.n, p.out);
+            from += p.n;
+        }
+    }
+};
+
+struct StagedOut {
+    bool inPlace;
+    OutBlock<double> f64;
+    OutBlock<uint32_t> u32;
+
+    StagedOut(uint32_t flags, std::initializer_list<std::pair<double *, size_t>> f, std::initializer_list<std::pair<uint32_t *, size_t>> u)
+        : inPlace((flags & SSYM_OUT_DEVICE) != 0), f64(f), u32(u)
+    {
     }
     int32_t alloc(Blocks &bl)
     {
         if (inPlace)
             return SSYM_OK;
-        uint32_t *block = nullptr;
-        int32_t rc = bl.get(&cost, nCost);
-        if (rc == SSYM_OK)
-            rc = bl.get(&block, nWords);
-        for (size_t i = 0; rc == SSYM_OK && i < nArrays; ++i) {
-            words[i].dev = block;
-            block += words[i].n;
-        }
-        return rc;
+        const int32_t rc = f64.alloc(bl);
+        return rc == SSYM_OK ? u32.alloc(bl) : rc;
     }
     int32_t finish(ssym_ctx *ctx)
     {
@@ -335,15 +357,13 @@ struct SpotOut {
             SSYM_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
             return SSYM_OK;
         }
-        std::vector<uint32_t> host(nWords);
-        SSYM_HIP_CHECK(ctx, hipMemcpyAsync(outCost, cost, sizeof(double) * nCost, hipMemcpyDeviceToHost, ctx->stream));
-        SSYM_HIP_CHECK(ctx, hipMemcpyAsync(host.data(), words[0].dev, sizeof(uint32_t) * nWords, hipMemcpyDeviceToHost, ctx->stream));
+        std::vector<double> hF64(f64.total);
+        std::vector<uint32_t> hU32(u32.total);
+        SSYM_HIP_CHECK(ctx, hipMemcpyAsync(hF64.data(), f64[0], sizeof(double) * f64.total, hipMemcpyDeviceToHost, ctx->stream));
+        SSYM_HIP_CHECK(ctx, hipMemcpyAsync(hU32.data(), u32[0], sizeof(uint32_t) * u32.total, hipMemcpyDeviceToHost, ctx->stream));
         SSYM_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-        const uint32_t *from = host.data();
-        for (size_t i = 0; i < nArrays; ++i) {
-            std::copy(from, from + words[i].n, words[i].out);
-            from += words[i].n;
-        }
+        f64.hand_over(hF64.data());
+        u32.hand_over(hU32.data());
         return SSYM_OK;
     }
 };

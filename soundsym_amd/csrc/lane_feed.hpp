@@ -1,0 +1,186 @@
+// lane_feed.hpp -- what the lane-fed objects share on the host: the spotter (dtw_spotter.hip) and the coverer
+// (dtw_coverer.hip) consume growing sounds lane by lane, in pushes of host frames or by following a stream's resident
+// frames, and flush or reset one lane.  The checks of those calls, their order, their messages and the upload of a push are
+// here once; what an object does with the frames (spotter_run, coverer_run) is its own.
+//
+// The order of the refusals is part of the interface ("the earlier of two faults is the one reported"):
+//   push   : frame_offsets / count NULL | the object's own check | lane by lane: offsets decrease, the lane has ended,
+//            the lane limit | feats NULL | hipSetDevice, upload
+//   follow : stream / count NULL | the object's own check | the stream's context | the stream's shape | lane by lane: holds
+//            fewer than consumed, the lane limit | hipSetDevice
+//   lane   : lane outside the lanes (flush: or count NULL) | hipSetDevice
+// and check_handle comes before each of them.
+#pragma once
+
+#include "ssym_internal.hpp"
+
+#include <algorithm>
+#include <functional>
+
+namespace ssym {
+
+// frames a lane may consume: its row numbers, ends and cut points are reported as u32, and 0xffffffff means none
+constexpr uint64_t kLaneMaxFrames = 2147483647;          // 2^31 - 1
+
+template <class T>
+int32_t alloc_n(ssym_ctx *ctx, T **p, size_t count)
+{
+    return dev_alloc(ctx, (void **)p, std::max<size_t>(count * sizeof(T), 8));
+}
+
+// n values of T from device memory to an output that is host memory, or device memory with SSYM_OUT_DEVICE
+template <class T>
+int32_t copy_out(ssym_ctx *ctx, T *out, const T *dev, size_t n, bool outDev)
+{
+    if (out && n)
+        SSYM_HIP_CHECK(ctx, hipMemcpyAsync(out, dev, sizeof(T) * n, outDev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost,
+                                           ctx->stream));
+    return SSYM_OK;
+}
+
+// what every call refuses before anything else; noun: "spotter", "coverer"
+template <class Handle>
+int32_t check_handle(ssym_ctx *ctx, const Handle *h, const char *noun, const char *fn)
+{
+    if (!h) {
+        ctx->err = std::string(fn) + ": the " + noun + " handle is NULL";
+        return SSYM_E_INVALID;
+    }
+    if (h->ctx != ctx) {
+        ctx->err = std::string(fn) + ": the " + noun + " belongs to another context";
+        return SSYM_E_INVALID;
+    }
+    return SSYM_OK;
+}
+
+// what is fed: a view of an object whose handle has been checked
+struct LaneFeed {
+    const char *noun;                                    // "spotter", "coverer"
+    const char *count;                                   // the name of the count output: "out_n_events", "out_n_pieces"
+    uint32_t nLanes, dim;
+    const std::vector<uint64_t> &consumed;               // frames per lane
+    const std::vector<uint8_t> *ended;                   // NULL: lanes never end
+    bool upload;                                         // false: the object has no use for the frames of a push
+    std::function<int32_t(const char *fn)> own;          // the object's own check behind the NULL checks of push and follow
+
+    // m frames more on a lane that has consumed n
+    int32_t check_lane_room(ssym_ctx *ctx, const char *fn, uint32_t lane, uint64_t n, uint64_t m) const
+    {
+        if (m > kLaneMaxFrames || n + m > kLaneMaxFrames) {
+            ctx->err = std::string(fn) + ": lane " + std::to_string(lane) + " would consume more than 2^31 - 1 = " +
+                       std::to_string(kLaneMaxFrames) + " frames";
+            return SSYM_E_UNSUPPORTED;
+        }
+        return SSYM_OK;
+    }
+
+    // lane l consumes the host frames feats[frame_offsets[l] ... frame_offsets[l + 1]): m[l] frames at rows[l], uploaded into a
+    // block of bl (enqueued on ctx's stream; bl outlives the object's run)
+    int32_t push(ssym_ctx *ctx, const char *fn, const double *feats, const uint64_t *frame_offsets, const uint64_t *out_n,
+                 Blocks &bl, std::vector<const double *> &rows, std::vector<uint64_t> &m) const
+    {
+        if (!frame_offsets || !out_n) {
+            ctx->err = std::string(fn) + ": frame_offsets and " + count + " must not be NULL";
+            return SSYM_E_INVALID;
+        }
+        int32_t rc = own ? own(fn) : SSYM_OK;
+        if (rc != SSYM_OK)
+            return rc;
+        m.assign(nLanes, 0);
+        rows.assign(nLanes, nullptr);
+        for (uint32_t l = 0; l < nLanes; ++l) {
+            if (frame_offsets[l + 1] < frame_offsets[l]) {
+                ctx->err = std::string(fn) + ": frame_offsets decrease";
+                return SSYM_E_INVALID;
+            }
+            m[l] = frame_offsets[l + 1] - frame_offsets[l];
+            if (m[l] && ended && (*ended)[l]) {
+                ctx->err = std::string(fn) + ": lane " + std::to_string(l) + " was flushed and has ended; call ssym_" + noun + "_reset";
+                return SSYM_E_INVALID;
+            }
+            rc = check_lane_room(ctx, fn, l, consumed[l], m[l]);
+            if (rc != SSYM_OK)
+                return rc;
+        }
+        const uint64_t total = frame_offsets[nLanes] - frame_offsets[0];
+        if (total && !feats) {
+            ctx->err = std::string(fn) + ": feats is NULL";
+            return SSYM_E_INVALID;
+        }
+        SSYM_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+        if (total && upload) {
+            double *block = nullptr;
+            rc = bl.get(&block, (size_t)total * dim);
+            if (rc != SSYM_OK)
+                return rc;
+            SSYM_HIP_CHECK(ctx, hipMemcpyAsync(block, feats + frame_offsets[0] * dim, sizeof(double) * total * dim,
+                                               hipMemcpyHostToDevice, ctx->stream));
+            for (uint32_t l = 0; l < nLanes; ++l)
+                rows[l] = block + (frame_offsets[l] - frame_offsets[0]) * dim;
+        }
+        return SSYM_OK;
+    }
+
+    // every lane consumes, in place, what the stream's lane holds beyond the frames consumed; a lane that has ended is skipped
+    int32_t follow(ssym_ctx *ctx, const char *fn, const ssym_stream *stream, const uint64_t *out_n,
+                   std::vector<const double *> &rows, std::vector<uint64_t> &m) const
+    {
+        if (!stream || !out_n) {
+            ctx->err = std::string(fn) + ": stream and " + count + " must not be NULL";
+            return SSYM_E_INVALID;
+        }
+        int32_t rc = own ? own(fn) : SSYM_OK;
+        if (rc != SSYM_OK)
+            return rc;
+        uint32_t lanes = 0, nc = 0;
+        const ssym_ctx *owner = nullptr;
+        stream_shape(stream, &lanes, &nc, &owner);
+        if (owner != ctx) {
+            ctx->err = std::string(fn) + ": the stream belongs to another context";
+            return SSYM_E_INVALID;
+        }
+        if (lanes != nLanes || nc != dim) {
+            ctx->err = std::string(fn) + ": the stream has " + std::to_string(lanes) + " lanes of " + std::to_string(nc) +
+                       " coefficients, the " + noun + " " + std::to_string(nLanes) + " lanes of " + std::to_string(dim) + " values";
+            return SSYM_E_INVALID;
+        }
+        m.assign(nLanes, 0);
+        rows.assign(nLanes, nullptr);
+        for (uint32_t l = 0; l < nLanes; ++l) {
+            const double *frames = nullptr;
+            uint64_t held = 0;
+            if (ssym_stream_frames_device(stream, l, &frames, &held) != SSYM_OK) {
+                ctx->err = std::string(fn) + ": the stream does not answer for lane " + std::to_string(l);
+                return SSYM_E_INVALID;
+            }
+            if (held < consumed[l]) {
+                ctx->err = std::string(fn) + ": lane " + std::to_string(l) + " of the stream holds " + std::to_string(held) +
+                           " frames, fewer than the " + std::to_string(consumed[l]) + " consumed: after ssym_stream_reset call ssym_" +
+                           noun + "_reset";
+                return SSYM_E_INVALID;
+            }
+            m[l] = ended && (*ended)[l] ? 0 : held - consumed[l];
+            rc = check_lane_room(ctx, fn, l, consumed[l], m[l]);
+            if (rc != SSYM_OK)
+                return rc;
+            rows[l] = m[l] ? frames + consumed[l] * dim : nullptr;           // read in place: no copy
+        }
+        SSYM_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+        return SSYM_OK;
+    }
+
+    // the lane of a flush (wantCount: its count output too) or of a reset
+    int32_t lane(ssym_ctx *ctx, const char *fn, uint32_t lane, bool wantCount, const uint64_t *out_n) const
+    {
+        if (lane >= nLanes || (wantCount && !out_n)) {
+            ctx->err = std::string(fn) + ": lane outside the " + noun + "'s lanes";
+            if (wantCount)
+                ctx->err += std::string(", or ") + count + " is NULL";
+            return SSYM_E_INVALID;
+        }
+        SSYM_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+        return SSYM_OK;
+    }
+};
+
+}  // namespace ssym

@@ -318,7 +318,7 @@ struct StageScope {                    // one per public entry point that moves 
     ~StageScope() { if (c) --c->api_depth; }
 };
 
-// a set of device blocks freed together (pitch.hip, mfcc.hip, sequence.hip)
+// a set of device blocks freed together: the scratch of one call, in every file that takes some
 struct Blocks {
     ssym_ctx *ctx;
     std::vector<void *> list;
@@ -459,6 +459,7 @@ struct CoverLimits {
 };
 CoverLimits cover_limits();
 int32_t check_cover_ctx(ssym_ctx *ctx, const char *fn);
+int32_t check_cover_prices(ssym_ctx *ctx, const char *fn, double piece_penalty, double gap_cost);
 int32_t check_cover_dict(ssym_ctx *ctx, const char *fn, const SegmentSet &src);
 struct CoverTables {
     double *tabM;                // [width][frames] after the fold

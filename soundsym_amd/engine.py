@@ -318,17 +318,21 @@ def stream_plan(n_old: int, n_add: int):
     return f0, f1 - f0, w0, w1 - w0
 
 
-class Stream:
+class _Lanes:
+    """What Stream, Spotter and Coverer share: `n_lanes` lanes, one of them named by a call."""
+
+    def _lane(self, lane) -> int:
+        if not 0 <= int(lane) < self.n_lanes:
+            raise ValueError(f"lane {lane} outside 0..{self.n_lanes - 1}")
+        return int(lane)
+
+
+class Stream(_Lanes):
     """Growing sounds on the engine's GPU (ssym_stream): `n_lanes` independent sounds whose samples,
     MFCC frames, max_power and per-coefficient sums stay resident; a push uploads and analyses only what is new."""
 
     def __init__(self, engine: "Engine", ptr: int, n_lanes: int, ncoeffs: int, sample_rate: float):
         self.engine, self.ptr, self.n_lanes, self.ncoeffs, self.sample_rate = engine, ptr, n_lanes, ncoeffs, sample_rate
-
-    def _lane(self, lane: int) -> int:
-        if not 0 <= int(lane) < self.n_lanes:
-            raise ValueError(f"lane {lane} outside 0..{self.n_lanes - 1}")
-        return int(lane)
 
     def counts(self) -> Tuple[np.ndarray, np.ndarray]:
         """(samples [n_lanes], frames [n_lanes]) held now (u64)."""
@@ -442,7 +446,23 @@ def _spotter_args(q, n_lanes, max_cost):
     return lanes, mc
 
 
-class Spotter:
+def _push_args(noun: str, n_lanes: int, dim: int, feats, frame_offsets):
+    """(frames as a flat contiguous f64 array, n_lanes + 1 u64 frame offsets) of Spotter.push and Coverer.push, checked
+    before the library is asked: whole frames, the bare block on one lane only, non-decreasing offsets within `feats`."""
+    x = np.ascontiguousarray(feats, dtype=np.float64).reshape(-1)
+    if x.size % dim:
+        raise ValueError(f"feats must hold whole frames of {dim} values")
+    if frame_offsets is None:
+        if n_lanes != 1:
+            raise ValueError(f"push: a {noun} of several lanes needs frame_offsets")
+        frame_offsets = [0, x.size // dim]
+    off = np.ascontiguousarray(frame_offsets, dtype=np.uint64).reshape(-1)
+    if off.size != n_lanes + 1 or np.any(np.diff(off.astype(np.int64)) < 0) or int(off[-1]) * dim > x.size:
+        raise ValueError("frame_offsets: n_lanes + 1 non-decreasing frame offsets within `feats`")
+    return x, off
+
+
+class Spotter(_Lanes):
     """The targets of a query set watched in `n_lanes` growing sources (ssym_spotter; definition in
     include/soundsym_amd.h and DESIGN.md section 2 "Watching"): a push costs the new frames alone, the best span so far is
     ssym_dtw_spot's for everything consumed, and occurrences are reported as events by a causal rule.  The spotter reads
@@ -473,16 +493,7 @@ class Spotter:
         """ssym_spotter_push: lane l consumes the frames feats[frame_offsets[l]:frame_offsets[l+1]] ([frames][dim]; a
         one-lane spotter takes the bare block).  Returns the number of events emitted, and with want_profile also the new
         rows of the profile per lane: two lists of [n_targets][new rows] arrays (delta f64, s uint32)."""
-        x = np.ascontiguousarray(feats, dtype=np.float64).reshape(-1)
-        if x.size % self.dim:
-            raise ValueError(f"feats must hold whole frames of {self.dim} values")
-        if frame_offsets is None:
-            if self.n_lanes != 1:
-                raise ValueError("push: a spotter of several lanes needs frame_offsets")
-            frame_offsets = [0, x.size // self.dim]
-        off = np.ascontiguousarray(frame_offsets, dtype=np.uint64).reshape(-1)
-        if off.size != self.n_lanes + 1 or np.any(np.diff(off.astype(np.int64)) < 0) or int(off[-1]) * self.dim > x.size:
-            raise ValueError("frame_offsets: n_lanes + 1 non-decreasing frame offsets within `feats`")
+        x, off = _push_args("spotter", self.n_lanes, self.dim, feats, frame_offsets)
         L = nat.lib()
         call = lambda n, pd, ps: L.ssym_spotter_push(self.engine.ctx, self.ptr, x.ctypes.data if x.size else None,
                                                      off.ctypes.data, 0, n, pd, ps)
@@ -511,10 +522,9 @@ class Spotter:
 
     def flush(self, lane: int = 0) -> int:
         """ssym_spotter_flush: "the lane has ended" -- what it has pending is emitted.  Returns the number of events."""
-        if not 0 <= int(lane) < self.n_lanes:
-            raise ValueError(f"lane {lane} outside 0..{self.n_lanes - 1}")
+        lane = self._lane(lane)
         n = ctypes.c_uint64()
-        nat.check(nat.lib().ssym_spotter_flush(self.engine.ctx, self.ptr, int(lane), ctypes.byref(n)), self.engine.ctx)
+        nat.check(nat.lib().ssym_spotter_flush(self.engine.ctx, self.ptr, lane, ctypes.byref(n)), self.engine.ctx)
         self.n_events = int(n.value)
         return self.n_events
 
@@ -535,9 +545,8 @@ class Spotter:
 
     def reset(self, lane: int = 0) -> None:
         """One lane back to "nothing consumed"."""
-        if not 0 <= int(lane) < self.n_lanes:
-            raise ValueError(f"lane {lane} outside 0..{self.n_lanes - 1}")
-        nat.check(nat.lib().ssym_spotter_reset(self.engine.ctx, self.ptr, int(lane)), self.engine.ctx)
+        lane = self._lane(lane)
+        nat.check(nat.lib().ssym_spotter_reset(self.engine.ctx, self.ptr, lane), self.engine.ctx)
 
     def close(self):
         if self.ptr and self.engine.ctx:
@@ -551,7 +560,7 @@ class Spotter:
             pass
 
 
-class Coverer:
+class Coverer(_Lanes):
     """`n_lanes` growing targets tiled by the segments of one resident dictionary (ssym_coverer; definition in
     include/soundsym_amd.h and DESIGN.md section 2 "Live cover"): every piece is reported by the push after which no
     longer recording could change it, the pieces from reset to flush are ssym_dtw_cover's for the whole, and `best` gives
@@ -563,24 +572,10 @@ class Coverer:
         self.piece_penalty, self.gap_cost = piece_penalty, gap_cost
         self.n_pieces = 0
 
-    def _lane(self, lane) -> int:
-        if not 0 <= int(lane) < self.n_lanes:
-            raise ValueError(f"lane {lane} outside 0..{self.n_lanes - 1}")
-        return int(lane)
-
     def push(self, feats, frame_offsets=None) -> int:
         """ssym_coverer_push: lane l consumes the frames feats[frame_offsets[l]:frame_offsets[l+1]] ([frames][dim]; a
         one-lane coverer takes the bare block).  Returns the number of pieces the push committed (`pieces` reads them)."""
-        x = np.ascontiguousarray(feats, dtype=np.float64).reshape(-1)
-        if x.size % self.dim:
-            raise ValueError(f"feats must hold whole frames of {self.dim} values")
-        if frame_offsets is None:
-            if self.n_lanes != 1:
-                raise ValueError("push: a coverer of several lanes needs frame_offsets")
-            frame_offsets = [0, x.size // self.dim]
-        off = np.ascontiguousarray(frame_offsets, dtype=np.uint64).reshape(-1)
-        if off.size != self.n_lanes + 1 or np.any(np.diff(off.astype(np.int64)) < 0) or int(off[-1]) * self.dim > x.size:
-            raise ValueError("frame_offsets: n_lanes + 1 non-decreasing frame offsets within `feats`")
+        x, off = _push_args("coverer", self.n_lanes, self.dim, feats, frame_offsets)
         n = ctypes.c_uint64()
         nat.check(nat.lib().ssym_coverer_push(self.engine.ctx, self.ptr, x.ctypes.data if x.size else None, off.ctypes.data,
                                               0, ctypes.byref(n)), self.engine.ctx)

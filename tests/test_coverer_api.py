@@ -54,7 +54,8 @@ def test_header_states_the_definition_and_the_limits():
     const = lambda src, name: int(re.search(r"\b%s\s*=\s*(\d+)" % name, src).group(1))
     frames, ring = const(cover, "kCoverMaxSourceFrames"), const(cover, "kCoverRing")
     assert const(coverer, "kCovererBackMin") == 1024 and const(coverer, "kCovererMaxLanes") == 65535
-    assert "kCovererMaxLaneFrames = 0x7fffffffull" in coverer
+    # the lane limit is the lane feed's, shared with the spotter
+    assert "kLaneMaxFrames" in coverer and "kLaneMaxFrames = %d;" % 0x7fffffff in _read("soundsym_amd", "csrc", "lane_feed.hpp")
     assert ring > 2 * frames and ring & (ring - 1) == 0     # the ring holds best(e) of the W ends of the horizon and best(-1)
     doc = header[header.index("Live cover (DESIGN.md"):header.index("ssym_coverer_create(ssym_ctx")]
     for line in ("H(n) = { e : max(-1, n-W) <= e <= n-1, best(e) finite }", "C(n) = the longest common prefix of walk(e) over e in H(n)",

@@ -60,7 +60,8 @@ def test_header_states_the_limits_and_what_the_rule_is_not():
     src, header = _read("soundsym_amd", "csrc", "dtw_spotter.hip"), _read("include", "soundsym_amd.h")
     frames = int(re.search(r"kSpotterMaxTargetFrames\s*=\s*(\d+);", src).group(1))
     dim = int(re.search(r"kSpotterMaxDim\s*=\s*(\d+);", src).group(1))
-    lane = int(re.search(r"kSpotterMaxLaneFrames\s*=\s*(\d+);", src).group(1))
+    assert "kLaneMaxFrames" in src                      # the lane limit is the lane feed's, shared with the coverer
+    lane = int(re.search(r"kLaneMaxFrames\s*=\s*(\d+);", _read("soundsym_amd", "csrc", "lane_feed.hpp")).group(1))
     assert (frames, dim, lane) == (4096, 64, 2 ** 31 - 1)
     assert "kSpotterScratchBytes = (size_t)512 << 20" in src
     doc = header[header.index("Watching (DESIGN.md"):header.index("ssym_spotter_create(ssym_ctx")]
