@@ -16,6 +16,7 @@ use std::os::raw::{c_char, c_void};
 #[repr(C)] pub struct SsymStream { _p: [u8; 0] }
 #[repr(C)] pub struct SsymSpotter { _p: [u8; 0] }
 #[repr(C)] pub struct SsymCoverer { _p: [u8; 0] }
+#[repr(C)] pub struct SsymMosaicker { _p: [u8; 0] }
 
 pub const SSYM_ABI_VERSION: i32 = 3;
 
@@ -354,6 +355,24 @@ extern "C" {
                              out_committed: *mut u32, flags: u32) -> i32;
     pub fn ssym_coverer_counts(cv: *const SsymCoverer, out_frames: *mut u64, out_capacity: *mut u64) -> i32;
     pub fn ssym_coverer_reset(ctx: *mut SsymCtx, cv: *mut SsymCoverer, lane: u32) -> i32;
+    // live mosaic ("Live mosaic"): n_lanes growing targets tiled by free spans of the recordings of one resident dictionary,
+    // every target frame reported by the push after which no longer recording could change it; gap_cost +inf: no gaps; the
+    // dictionary must outlive the mosaicker
+    pub fn ssym_mosaicker_create(ctx: *mut SsymCtx, dict: *const SsymDict, n_lanes: u32, piece_penalty: f64, gap_cost: f64,
+                                 out: *mut *mut SsymMosaicker) -> i32;
+    pub fn ssym_mosaicker_destroy(ctx: *mut SsymCtx, mk: *mut SsymMosaicker) -> i32;
+    pub fn ssym_mosaicker_push(ctx: *mut SsymCtx, mk: *mut SsymMosaicker, feats: *const f64, frame_offsets: *const u64,
+                               flags: u32, out_n_frames: *mut u64) -> i32;
+    pub fn ssym_mosaicker_follow(ctx: *mut SsymCtx, mk: *mut SsymMosaicker, stream: *const SsymStream, flags: u32,
+                                 out_n_frames: *mut u64) -> i32;
+    pub fn ssym_mosaicker_frames(ctx: *mut SsymCtx, mk: *const SsymMosaicker, out_lane: *mut u32, out_column: *mut u32,
+                                 out_src: *mut u32, out_frame: *mut u32, out_cost: *mut f64, out_start: *mut u32,
+                                 flags: u32) -> i32;
+    pub fn ssym_mosaicker_flush(ctx: *mut SsymCtx, mk: *mut SsymMosaicker, lane: u32, out_n_frames: *mut u64) -> i32;
+    pub fn ssym_mosaicker_best(ctx: *mut SsymCtx, mk: *const SsymMosaicker, out_total: *mut f64, out_covered: *mut u32,
+                               out_committed: *mut u32, flags: u32) -> i32;
+    pub fn ssym_mosaicker_counts(mk: *const SsymMosaicker, out_frames: *mut u64, out_capacity: *mut u64) -> i32;
+    pub fn ssym_mosaicker_reset(ctx: *mut SsymCtx, mk: *mut SsymMosaicker, lane: u32) -> i32;
 }
 
 /// `Err(message)` for any status but SSYM_OK; SSYM_E_EMPTY_DICT keeps the crate's behaviour (a panic, :369).

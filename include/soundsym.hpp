@@ -964,6 +964,115 @@ class Coverer {
     ssym_coverer *cv_ = nullptr;
 };
 
+// n_lanes growing targets tiled by free spans of a dictionary's uncut recordings (ssym_mosaicker; soundsym_amd.h "Live
+// mosaic"): every target frame is reported by the push after which no longer recording could change it, the frames from
+// reset to flush are SoundDictionary::mosaic's for the whole, and best() gives its total for what a lane has consumed.  The
+// mosaicker packs the sounds' features into a dictionary of its own and keeps it for as long as it lives.
+class Mosaicker {
+  public:
+    struct Frame {
+        uint32_t lane;
+        uint32_t column;            // the lane's frame, counted since its reset
+        uint32_t src;               // the dictionary sound, or SSYM_COVER_GAP
+        uint32_t frame;             // the sound's frame (SSYM_NO_MATCH on a gap frame)
+        double cost;                // c of the pair, or gap_cost
+        bool start;                 // a piece or a gap frame starts here
+    };
+    struct Best {
+        double total;               // SoundDictionary::mosaic's total of everything consumed; +inf without a mosaic
+        uint32_t covered;           // frames of the longest prefix that has a mosaic
+        uint32_t committed;         // frames that have been emitted
+    };
+    // gap_cost +inf: no gaps
+    Mosaicker(std::shared_ptr<Context> ctx, const std::vector<ArcSound> &sounds, uint32_t n_lanes = 1, double piece_penalty = 0.0,
+              double gap_cost = std::numeric_limits<double>::infinity())
+        : ctx_(std::move(ctx)), lanes_(n_lanes)
+    {
+        std::vector<double> flat;
+        std::vector<uint64_t> off;
+        pack_features(sounds, flat, off);
+        ctx_->check(ssym_dict_create(ctx_->get(), flat.data(), off.data(), (uint32_t)sounds.size(), (uint32_t)NCOEFFS, &dict_));
+        const int32_t rc = ssym_mosaicker_create(ctx_->get(), dict_, n_lanes, piece_penalty, gap_cost, &mk_);
+        if (rc != SSYM_OK) {
+            ssym_dict_destroy(ctx_->get(), dict_);
+            ctx_->check(rc);
+        }
+    }
+    ~Mosaicker()
+    {
+        ssym_mosaicker_destroy(ctx_->get(), mk_);    // the mosaicker reads the dictionary: it goes first
+        ssym_dict_destroy(ctx_->get(), dict_);
+    }
+    Mosaicker(const Mosaicker &) = delete;
+    Mosaicker &operator=(const Mosaicker &) = delete;
+
+    // lane l consumes frames [frame_offsets[l], frame_offsets[l + 1]) of feats (NCOEFFS values each); the frames it commits
+    std::vector<Frame> push(const std::vector<double> &feats, const std::vector<uint64_t> &frame_offsets)
+    {
+        if (frame_offsets.size() != (size_t)lanes_ + 1)
+            throw Error(SSYM_E_INVALID, "frame_offsets must hold n_lanes + 1 entries");
+        uint64_t n = 0;
+        ctx_->check(ssym_mosaicker_push(ctx_->get(), mk_, feats.data(), frame_offsets.data(), 0, &n));
+        return frames(n);
+    }
+    // every lane consumes, device to device, what the stream's lane holds beyond the frames consumed
+    std::vector<Frame> follow(const ssym_stream *stream)
+    {
+        uint64_t n = 0;
+        ctx_->check(ssym_mosaicker_follow(ctx_->get(), mk_, stream, 0, &n));
+        return frames(n);
+    }
+    // "the lane has ended": the rest of its mosaic; the lane consumes nothing more until reset
+    std::vector<Frame> flush(uint32_t lane)
+    {
+        uint64_t n = 0;
+        ctx_->check(ssym_mosaicker_flush(ctx_->get(), mk_, lane, &n));
+        return frames(n);
+    }
+    std::vector<Best> best() const
+    {
+        std::vector<double> total(lanes_);
+        std::vector<uint32_t> covered(lanes_), committed(lanes_);
+        ctx_->check(ssym_mosaicker_best(ctx_->get(), mk_, total.data(), covered.data(), committed.data(), 0));
+        std::vector<Best> out(lanes_);
+        for (uint32_t l = 0; l < lanes_; ++l)
+            out[l] = Best{total[l], covered[l], committed[l]};
+        return out;
+    }
+    std::vector<uint64_t> counts() const
+    {
+        std::vector<uint64_t> out(lanes_);
+        ctx_->check(ssym_mosaicker_counts(mk_, out.data(), nullptr));
+        return out;
+    }
+    // columns the ring of uncommitted columns holds per lane
+    uint64_t capacity() const
+    {
+        uint64_t cap = 0;
+        ctx_->check(ssym_mosaicker_counts(mk_, nullptr, &cap));
+        return cap;
+    }
+    void reset(uint32_t lane) { ctx_->check(ssym_mosaicker_reset(ctx_->get(), mk_, lane)); }
+
+  private:
+    std::vector<Frame> frames(uint64_t n) const
+    {
+        std::vector<uint32_t> lane(n), column(n), src(n), frame(n), start(n);
+        std::vector<double> cost(n);
+        if (n)
+            ctx_->check(ssym_mosaicker_frames(ctx_->get(), mk_, lane.data(), column.data(), src.data(), frame.data(), cost.data(),
+                                              start.data(), 0));
+        std::vector<Frame> out(n);
+        for (uint64_t k = 0; k < n; ++k)
+            out[k] = Frame{lane[k], column[k], src[k], frame[k], cost[k], start[k] != 0};
+        return out;
+    }
+    std::shared_ptr<Context> ctx_;
+    uint32_t lanes_ = 0;
+    ssym_dict *dict_ = nullptr;
+    ssym_mosaicker *mk_ = nullptr;
+};
+
 // One rank of a SoundDictionary split over the GPUs of one node (source-axis shards, one rank -- thread or process --
 // per GPU): rank g holds sounds [lo, lo + shard.size()) of the whole dictionary and is handed the same targets as every
 // other rank; match_indices returns GLOBAL indices, the same complete answer on every rank, bit for bit the unsharded

@@ -60,6 +60,7 @@ typedef struct ssym_gmm ssym_gmm;         /* a trained Gaussian mixture (the par
 typedef struct ssym_stream ssym_stream;   /* growing sounds: samples + analysis resident on the GPU  */
 typedef struct ssym_spotter ssym_spotter; /* targets watched in growing sources: resumable spotting   */
 typedef struct ssym_coverer ssym_coverer; /* growing targets tiled by dictionary segments: live cover  */
+typedef struct ssym_mosaicker ssym_mosaicker; /* growing targets tiled by free spans: live mosaic       */
 
 enum {
     SSYM_OK = 0,
@@ -1250,6 +1251,85 @@ SSYM_API int32_t ssym_coverer_best(ssym_ctx *ctx, const ssym_coverer *cv, double
                                    uint32_t *out_committed, uint32_t flags);
 SSYM_API int32_t ssym_coverer_counts(const ssym_coverer *cv, uint64_t *out_frames, uint64_t *out_capacity);
 SSYM_API int32_t ssym_coverer_reset(ssym_ctx *ctx, ssym_coverer *cv, uint32_t lane);
+
+/* Live mosaic (DESIGN.md section 2 "Live mosaic" and section 5.26): the mosaic of targets that grow.  A mosaicker holds
+ * n_lanes growing targets against ONE resident dictionary and reports every target frame with the push after which no longer
+ * recording could change it.  c, S, P, open, Q, H, N, E, best, arg, the tie rules and the arithmetic are those of "Mosaic"
+ * above, word for word.  For one lane, X is everything consumed so far and n its frame count:
+ *   resume   : the lane holds n, E(., n-1) and N(., n-1), best(n-1), the direction byte of every (g, j) and arg(j) for every
+ *              column j after the committed column, done (the last committed column, -1 at first), the committed tip (the
+ *              key at done; walks stop at column done + 1, so it need not be stored) and lastFinite (the largest j with a
+ *              finite best(j), -1 at first).  Consuming frames n ... n+m-1 runs columns n ... n+m-1 exactly as "Mosaic"
+ *              does.
+ *   key      : a position of the backward walk at column j: (g, H), (g, N) or GAP.  A walk steps from a key at column j to
+ *              one at column j-1 by the "backward" rule of "Mosaic".  Two walks that share a key at a column are the same
+ *              from there back.
+ *   live(n)  : S' = piece_penalty + best(n-1), as the next column will form it.  Every g with E(g, n-1) finite and <= S'
+ *              gives a hypothesis in the state byte bit 0 says (H if H < N, else N); every g whose bit 0 is set and whose
+ *              N(g, n-1) is finite and <= S' gives one in state N; GAP at column n-1 is one if arg(n-1) = GAP and best(n-1)
+ *              is finite.  NaN is never live.
+ *   commit   : c(n) = the largest column <= n-1 at which all walks of live(n) hold the same key, -1 if there is none; live(n)
+ *              empty: unchanged.  A push emits frames done+1 ... c(n), each with the outputs ssym_dtw_mosaic gives it: src
+ *              (or SSYM_COVER_GAP), frame, cost, and whether a piece or gap frame starts there.  Then done = c(n).
+ *   dead     : best(n-1) not finite makes every later column +inf (E and N are all non-finite and S = +inf); it cannot
+ *              happen with a finite gap_cost.  A dead lane goes on counting frames but stores nothing more and commits
+ *              nothing more.
+ *   flush    : emits the rest of the walk from arg(lastFinite) at column lastFinite.  The lane has then ENDED until
+ *              ssym_mosaicker_reset (ssym_mosaicker_push with frames for it: SSYM_E_INVALID; ssym_mosaicker_follow skips it).
+ *   best     : total = best(n-1) (+inf for n = 0 or when not finite), covered = lastFinite + 1, committed = done + 1
+ * Why: a state above S' is never used by column n.  E: as the P of a successor it is > S' and that successor opens, else the
+ * other predecessor was taken.  N: H(g,n) = c + N(g,n-1) wins only if it is < c + Q with Q <= S', and rounding is monotone.
+ * So every mosaic of every longer X passes through a live state at column n-1, and hence through the common key at c(n).
+ * So: (1) after any push, total has the bits ssym_dtw_mosaic returns for the frames consumed so far as one target; (2) c(n)
+ * depends on the frames consumed, not on how they were cut into pushes, slices or lanes, and only grows; (3) frames once
+ * emitted are never revised; (4) from reset to flush the frames emitted are ssym_dtw_mosaic's six arrays for the whole
+ * target, and if the lane died those for X[0 ... lastFinite]; (5) device state per lane is 32 G bytes of E / N, 24 G + 24 of
+ * the commit's key lists, and a ring of G + 4 + 8 dim bytes per uncommitted column (direction bytes, arg and the target
+ * frame, which the emitted frame cost is formed from): nothing grows with the stream.  The uncommitted stretch has no hard
+ * bound but the memory below.
+ *
+ * ssym_mosaicker_create: dict's resident features are READ BY THE MOSAICKER FOR AS LONG AS IT LIVES: destroy the mosaicker
+ *   first.  The transposed source frames and pos are made here, once.  A dictionary appended to since: SSYM_E_INVALID at
+ *   the next push / follow.  piece_penalty and gap_cost as for ssym_dtw_mosaic; a gap_cost of +inf means no gaps.
+ * ssym_mosaicker_push: appends feats[frame_offsets[l] .. frame_offsets[l+1]) (frames of the dictionary's dim, f64, HOST
+ *   memory whatever the context's dtype) to lane l, for every lane; an empty range leaves a lane alone.
+ *   out_n_frames   the frames this call emitted (read them with ssym_mosaicker_frames)
+ * ssym_mosaicker_follow: for every lane, consumes the frames the stream's lane holds beyond those consumed, device to
+ *   device; the stream as for ssym_coverer_follow.
+ * ssym_mosaicker_frames: the frames of the last push / follow / flush, out_n_frames of them, ordered by (lane, column); each
+ *   output nullable (HOST, or device memory with SSYM_OUT_DEVICE).  column counts the lane's frames since its reset;
+ *   (src, frame, cost) are ssym_dtw_mosaic's out_src, out_frame and out_frame_cost of that target frame; start is 1 where a
+ *   piece or a gap frame starts, else 0.
+ * ssym_mosaicker_flush: the flush of one lane; ssym_coverer_flush's rules.
+ * ssym_mosaicker_best: [n_lanes] each, nullable (HOST, or device memory with SSYM_OUT_DEVICE).
+ * ssym_mosaicker_counts: frames consumed per lane (n_lanes u64) and the capacity of the ring in columns (one u64), HOST,
+ *   each nullable.  Host arithmetic, no device work.
+ * ssym_mosaicker_reset: one lane back to "nothing consumed".
+ * Limits, checked at creation before any device work: a dtw context without a band, dim <= 64, at most 65535 lanes, and the
+ * state with a ring of 16 columns within 512 MiB: SSYM_E_UNSUPPORTED beyond them.  An empty dictionary: SSYM_E_EMPTY_DICT.
+ * Prices as for ssym_dtw_mosaic.  A lane consumes at most 2^31 - 1 frames.  Refusals and their order are the coverer's.
+ * The ring starts at the largest power of two <= 1024 columns with lanes x columns x (G + 4) <= 64 MiB (16 at least) and
+ * doubles when the uncommitted stretch plus a slice would not fit.  Everything the mosaicker owns beside a call's frame log
+ * stays within 512 MiB, the ring it leaves beside the new one while it doubles included: a call runs in slices with a
+ * commit after each, a slice is shortened to fit, and if the uncommitted stretch alone fills the cap the call returns
+ * SSYM_E_UNSUPPORTED with a message that says to flush -- what earlier slices consumed stays consumed and is in the log
+ * (after any failure of a later slice out_n_frames counts what the earlier ones logged).  One synchronisation per slice.  ssym_get_timings afterwards: main_ms = the
+ * forward pass, reduce_ms = commit and emission, n_pairs = G x the frames the call consumed. */
+SSYM_API int32_t ssym_mosaicker_create(ssym_ctx *ctx, const ssym_dict *dict, uint32_t n_lanes, double piece_penalty,
+                                       double gap_cost, ssym_mosaicker **out);
+SSYM_API int32_t ssym_mosaicker_destroy(ssym_ctx *ctx, ssym_mosaicker *mk);
+SSYM_API int32_t ssym_mosaicker_push(ssym_ctx *ctx, ssym_mosaicker *mk, const double *feats, const uint64_t *frame_offsets,
+                                     uint32_t flags, uint64_t *out_n_frames);
+SSYM_API int32_t ssym_mosaicker_follow(ssym_ctx *ctx, ssym_mosaicker *mk, const ssym_stream *stream, uint32_t flags,
+                                       uint64_t *out_n_frames);
+SSYM_API int32_t ssym_mosaicker_frames(ssym_ctx *ctx, const ssym_mosaicker *mk, uint32_t *out_lane, uint32_t *out_column,
+                                       uint32_t *out_src, uint32_t *out_frame, double *out_cost, uint32_t *out_start,
+                                       uint32_t flags);
+SSYM_API int32_t ssym_mosaicker_flush(ssym_ctx *ctx, ssym_mosaicker *mk, uint32_t lane, uint64_t *out_n_frames);
+SSYM_API int32_t ssym_mosaicker_best(ssym_ctx *ctx, const ssym_mosaicker *mk, double *out_total, uint32_t *out_covered,
+                                     uint32_t *out_committed, uint32_t flags);
+SSYM_API int32_t ssym_mosaicker_counts(const ssym_mosaicker *mk, uint64_t *out_frames, uint64_t *out_capacity);
+SSYM_API int32_t ssym_mosaicker_reset(ssym_ctx *ctx, ssym_mosaicker *mk, uint32_t lane);
 
 #ifdef __cplusplus
 }

@@ -11,7 +11,7 @@ from ._native import (  # noqa: F401
     SsymError,
     build,
 )
-from .engine import Coverer, DeviceFrames, Engine, Gmm, Spotter, Stream, pack_segments, stream_plan  # noqa: F401
+from .engine import Coverer, DeviceFrames, Engine, Gmm, Mosaicker, Spotter, Stream, pack_segments, stream_plan  # noqa: F401
 from .api import (  # noqa: F401
     Alignment,
     BIN,
@@ -19,6 +19,7 @@ from .api import (  # noqa: F401
     Gap,
     HOP,
     LiveCover,
+    LiveMosaic,
     Mosaic,
     MosaicPiece,
     NCLUSTERS,
@@ -42,7 +43,7 @@ from .api import (  # noqa: F401
 )
 
 __all__ = [
-    "ABI_SYMBOLS", "Alignment", "BIN", "Cover", "Coverer", "DeviceFrames", "EmptyDictionaryError", "Engine", "Gap", "Gmm", "HOP", "LIB_PATH", "LiveCover", "Mosaic", "MosaicPiece", "NCLUSTERS", "NCOEFFS",
+    "ABI_SYMBOLS", "Alignment", "BIN", "Cover", "Coverer", "DeviceFrames", "EmptyDictionaryError", "Engine", "Gap", "Gmm", "HOP", "LIB_PATH", "LiveCover", "LiveMosaic", "Mosaic", "MosaicPiece", "Mosaicker", "NCLUSTERS", "NCOEFFS",
     "Partitioner", "Piece", "Sound", "SoundDictionary", "SoundSequence", "Spot", "SsymError", "analyze_mfccs", "analyze_sounds", "build",
     "cosine_sim_angular", "discretize",
     "discretize_with_model", "length_fit", "pack_segments", "push_sounds", "Spotter", "Stream", "stream_plan", "train_model", "Watch", "watch",

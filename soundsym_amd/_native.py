@@ -67,6 +67,8 @@ ABI_SYMBOLS = [
     "ssym_spotter_create_step",
     "ssym_coverer_create", "ssym_coverer_destroy", "ssym_coverer_push", "ssym_coverer_follow", "ssym_coverer_pieces",
     "ssym_coverer_flush", "ssym_coverer_best", "ssym_coverer_counts", "ssym_coverer_reset", "ssym_coverer_create_gaps",
+    "ssym_mosaicker_create", "ssym_mosaicker_destroy", "ssym_mosaicker_push", "ssym_mosaicker_follow", "ssym_mosaicker_frames",
+    "ssym_mosaicker_flush", "ssym_mosaicker_best", "ssym_mosaicker_counts", "ssym_mosaicker_reset",
     "ssym_reconstruct_warped", "ssym_reconstruct_wsola",
     "ssym_dtw_align_spans_sizes", "ssym_dtw_align_spans", "ssym_reconstruct_warped_spans", "ssym_reconstruct_wsola_spans",
 ]
@@ -414,6 +416,24 @@ def lib() -> ctypes.CDLL:
     L.ssym_coverer_counts.argtypes = [vp, vp, ctypes.POINTER(u64)]
     L.ssym_coverer_reset.restype = i32
     L.ssym_coverer_reset.argtypes = [vp, vp, u32]
+    L.ssym_mosaicker_create.restype = i32
+    L.ssym_mosaicker_create.argtypes = [vp, vp, u32, f64, f64, pvp]
+    L.ssym_mosaicker_destroy.restype = i32
+    L.ssym_mosaicker_destroy.argtypes = [vp, vp]
+    L.ssym_mosaicker_push.restype = i32
+    L.ssym_mosaicker_push.argtypes = [vp, vp, vp, vp, u32, ctypes.POINTER(u64)]
+    L.ssym_mosaicker_follow.restype = i32
+    L.ssym_mosaicker_follow.argtypes = [vp, vp, vp, u32, ctypes.POINTER(u64)]
+    L.ssym_mosaicker_frames.restype = i32
+    L.ssym_mosaicker_frames.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, u32]
+    L.ssym_mosaicker_flush.restype = i32
+    L.ssym_mosaicker_flush.argtypes = [vp, vp, u32, ctypes.POINTER(u64)]
+    L.ssym_mosaicker_best.restype = i32
+    L.ssym_mosaicker_best.argtypes = [vp, vp, vp, vp, vp, u32]
+    L.ssym_mosaicker_counts.restype = i32
+    L.ssym_mosaicker_counts.argtypes = [vp, vp, ctypes.POINTER(u64)]
+    L.ssym_mosaicker_reset.restype = i32
+    L.ssym_mosaicker_reset.argtypes = [vp, vp, u32]
     _lib = L
     return L
 

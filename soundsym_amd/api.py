@@ -661,10 +661,11 @@ class MosaicPiece:
             self.start_frame, self.end_frame, self.source_index, self.source_first, self.source_last, self.cost)
 
 
-def _mosaic_tiles(start, src, frame, frame_cost) -> List:
+def _mosaic_tiles(start, src, frame, frame_cost, base: int = 0) -> List:
     """The MosaicPieces and Gaps of one mosaic from what the library reports for one target: `start` its piece and gap-frame
     starts (ascending), `src`, `frame` and `frame_cost` its frames.  A gap comes frame by frame, and a run of them is one
-    Gap at the sum of its frames' prices; a piece's cost is the chain of its frame costs."""
+    Gap at the sum of its frames' prices; a piece's cost is the chain of its frame costs.  base: the target frame the
+    arrays begin at (a stretch of a live mosaic); the tiles count the target's frames."""
     frames = len(src)
     cuts = [int(s) for s in start] + [frames]
     out = []
@@ -672,14 +673,14 @@ def _mosaic_tiles(start, src, frame, frame_cost) -> List:
         if int(src[s]) == COVER_GAP:
             if out and out[-1].is_gap:
                 run = out[-1]
-                out[-1] = Gap(run.start_frame, s, float(frame_cost[s]) * (s - run.start_frame + 1))
+                out[-1] = Gap(run.start_frame, base + s, float(frame_cost[s]) * (base + s - run.start_frame + 1))
             else:
-                out.append(Gap(s, s, float(frame_cost[s])))
+                out.append(Gap(base + s, base + s, float(frame_cost[s])))
             continue
         acc = float(frame_cost[s])
         for j in range(s + 1, e):
             acc = float(frame_cost[j]) + acc
-        out.append(MosaicPiece(src[s], frame[s], frame[e - 1], s, e - 1, acc, frame[s:e]))
+        out.append(MosaicPiece(src[s], frame[s], frame[e - 1], base + s, base + e - 1, acc, frame[s:e]))
     return out
 
 
@@ -854,6 +855,102 @@ class LiveCover:
 
     def close(self):
         self.coverer.close()
+
+
+class LiveMosaic:
+    """Growing Sounds tiled live by free spans of a dictionary's sounds (`SoundDictionary.mosaic_live`): the sounds' shared
+    stream followed by a Mosaicker (DESIGN.md section 2 "Live mosaic").  The mosaicker commits FRAMES, a frame or two
+    behind the input at moderate penalties; a piece is closed, and returned by poll as (sound index, MosaicPiece | Gap),
+    once the next start -- or the flush -- has been committed.  The open piece's committed frames stay inside the object
+    (`committed` shows them).  What is returned is final: it is how the mosaic of the whole sound starts, whatever the
+    sound gains later.  A run of gap frames comes as one Gap per call; the run may go on in the next call, and `mosaics`
+    merges across calls."""
+
+    def __init__(self, sounds, stream, mosaicker, piece_penalty: float, gap_cost=None):
+        self.sounds, self.stream, self.mosaicker, self.piece_penalty = sounds, stream, mosaicker, float(piece_penalty)
+        self.gap_cost = gap_cost
+        # per sound: (src, frame, cost, start) of every committed frame, and the frames already returned as closed pieces
+        self._frames = [([], [], [], []) for _ in sounds]
+        self._closed = [0 for _ in sounds]
+        self._emitted = [[] for _ in sounds]
+        self._held = []                                  # pieces closed by a poll that was refused part-way
+
+    def _take(self, ended=()):
+        lane, col, src, frame, cost, start = self.mosaicker.frames()
+        for k in range(lane.size):
+            rows = self._frames[int(lane[k])]
+            if int(col[k]) != len(rows[0]):
+                raise RuntimeError("the mosaicker's frames do not continue the frames committed before")
+            for row, v in zip(rows, (int(src[k]), int(frame[k]), float(cost[k]), int(start[k]))):
+                row.append(v)
+        out = []
+        for l, (src, frame, cost, start) in enumerate(self._frames):
+            a, n = self._closed[l], len(src)
+            cuts = [j for j in range(a, n) if start[j]]
+            b = n if l in ended else (cuts[-1] if cuts else a)       # the last start opens a piece that may still grow
+            if b <= a:
+                continue
+            tiles = _mosaic_tiles([j - a for j in cuts if j < b], src[a:b], np.array(frame[a:b], dtype=np.uint32), cost[a:b], a)
+            self._closed[l] = b
+            self._emitted[l] += tiles
+            out += [(l, p) for p in tiles]
+        if self._held:
+            out = sorted(self._held + out, key=lambda t: (t[0], t[1].start_frame))
+            self._held = []
+        return out
+
+    def poll(self):
+        """Consume what the sounds have gained since the last poll (device to device) and return the pieces that closes,
+        ordered by (sound, start).  A poll the mosaicker refuses part-way (SSYM_E_UNSUPPORTED: a sound's uncommitted
+        stretch fills the mosaicker's memory) raises, but what it consumed stays consumed and what it committed is kept:
+        `committed` shows it, and the pieces it closed come with the next poll or flush."""
+        try:
+            self.mosaicker.follow(self.stream)
+        except SsymError as err:
+            if err.code == SSYM_E_UNSUPPORTED:
+                self._held = self._take()
+            raise
+        return self._take()
+
+    def flush(self):
+        """"The sounds have ended": the rest of every sound's mosaic.  The mosaic consumes nothing more afterwards."""
+        out = []
+        for lane in range(self.mosaicker.n_lanes):
+            self.mosaicker.flush(lane)
+            out += self._take(ended=(lane,))
+        return sorted(out, key=lambda t: (t[0], t[1].start_frame))   # (only pieces held from a refused poll move)
+
+    def committed(self):
+        """Per sound (src uint32, frame uint32, frame_cost f64, start bool), one entry per committed frame -- the open
+        piece's included: what a caller that resynthesises frame by frame reads (a gap frame: COVER_GAP, NO_MATCH,
+        gap_cost)."""
+        return [(np.array(s, dtype=np.uint32), np.array(f, dtype=np.uint32), np.array(c, dtype=np.float64),
+                 np.array(a, dtype=bool)) for s, f, c, a in self._frames]
+
+    def mosaics(self) -> List["Mosaic"]:
+        """One Mosaic per sound from every frame committed so far: it tiles those frames, and its total is the recurrence's
+        own sum over them -- after flush, SoundDictionary.mosaic's Mosaic of the sound (of its prefix with a mosaic, when
+        a NaN frame ends that early without gaps)."""
+        out = []
+        for src, frame, cost, start in self._frames:
+            if not src:
+                out.append(Mosaic.none(0))
+                continue
+            acc = 0.0
+            for s, c, a in zip(src, cost, start):
+                acc = (c + (self.piece_penalty + acc)) if a and s != COVER_GAP else (c + acc)
+            cuts = [j for j in range(len(src)) if start[j]]
+            out.append(Mosaic(_mosaic_tiles(cuts, src, np.array(frame, dtype=np.uint32), cost), acc, len(src), cost))
+        return out
+
+    def pending(self):
+        """(frames consumed, frames with a mosaic, frames committed, total), one entry per sound: total is
+        SoundDictionary.mosaic's for what was consumed, +inf without a mosaic."""
+        total, covered, committed = self.mosaicker.best()
+        return self.mosaicker.counts()[0].astype(np.int64), covered.astype(np.int64), committed.astype(np.int64), total
+
+    def close(self):
+        self.mosaicker.close()
 
 
 def _shared_stream(sounds, what: str):
@@ -1349,21 +1446,26 @@ class SoundDictionary:
         return _mosaics(off, *arrays)
 
     def reconstruct_mosaic(self, target: Sound, piece_penalty: float = 0.0, gap_cost=None, gap_fill: str = "silence",
-                           search: int = 0, want_pcm32: bool = False):
+                           search: int = 0, want_pcm32: bool = False, mosaic: Optional["Mosaic"] = None):
         """mosaic, then warp: every sounding piece of the target's Mosaic is resynthesised from its span of its recording
         along its frame_map, in ONE call of the existing window reconstruction (ssym_reconstruct_warped_spans, or with
         search > 0 ssym_reconstruct_wsola_spans): the window is the piece's source_sample_span, the map frame_map -
         source_first, the output length the piece's entry of Mosaic.segment_lengths.  Gaps' stretches are spliced in as
         zeros (gap_fill="silence") or as the target's own samples ("target"), as reconstruct_covered does.  Returns
         (mosaic, samples), with want_pcm32 (mosaic, samples, pcm); the samples are len(target.samples()); a target
-        without a mosaic gives silence."""
+        without a mosaic gives silence.  mosaic (default None: computed here): a Mosaic of the target made elsewhere --
+        by mosaic_long, or a LiveMosaic's mosaics() -- is resynthesised as it is; piece_penalty and gap_cost are then not
+        used."""
         penalty, gap = _cover_penalty(piece_penalty), _cover_gap_cost(gap_cost)
         search = _wsola_search(search)
         if gap_fill not in ("silence", "target"):
             raise ValueError('gap_fill must be "silence" or "target"')
         if not isinstance(target, Sound):
             raise ValueError("reconstruct_mosaic takes one Sound")
-        mosaic = self.mosaic([target], penalty, gap)[0]
+        if mosaic is None:
+            mosaic = self.mosaic([target], penalty, gap)[0]
+        elif not isinstance(mosaic, Mosaic):
+            raise ValueError("mosaic must be a Mosaic")
         smp = np.asarray(target.samples(), dtype=np.float64)
         outs = [np.zeros(smp.size), np.zeros(smp.size, dtype=np.int32)][:2 if want_pcm32 else 1]
         lengths = mosaic.segment_lengths(smp.size)
@@ -1425,6 +1527,55 @@ class SoundDictionary:
         if st.ncoeffs != self._dim():
             raise ValueError("cover_live: the sounds' ncoeffs must be the dictionary's")
         return LiveCover(sounds, st, self.engine.coverer(self.resident(), len(sounds), penalty, gap), penalty, gap)
+
+    def mosaic_live(self, sounds: Sequence[Sound], piece_penalty: float = 0.0, gap_cost=None) -> "LiveMosaic":
+        """Tile Sounds that are still growing (fed with push_samples / push_sounds): a Mosaicker on this dictionary follows
+        the sounds' stream (ssym_mosaicker_*, DESIGN.md section 2 "Live mosaic"; dtw engines without a band).  The sounds
+        must be resident and share one stream, sound i in lane i -- what one push_sounds(sounds, ...) leaves -- ValueError
+        otherwise, before any device work.  LiveMosaic.poll() returns the pieces no longer recording can change, flush()
+        the rest; on f64 engines the mosaics() after flush are `mosaic`'s, bit for bit.  On f32 engines `mosaic` rounds
+        the targets' features to f32 first while the mosaicker reads the stream's f64 frames as they are (as `watch`
+        does), so the two can differ there.  The LiveMosaic keeps the dictionary's resident copy: close it before the
+        dictionary changes.  gap_cost as for `mosaic`: a NaN frame then becomes a gap frame and the sound goes on."""
+        penalty, gap = self._cover_checks(piece_penalty, "mosaic_live"), _cover_gap_cost(gap_cost)
+        sounds = list(sounds)
+        st = _shared_stream(sounds, "mosaic_live")
+        if self.engine is not st.engine:
+            raise ValueError("mosaic_live: the dictionary's engine must be the one that holds the sounds' stream")
+        if st.ncoeffs != self._dim():
+            raise ValueError("mosaic_live: the sounds' ncoeffs must be the dictionary's")
+        return LiveMosaic(sounds, st, self.engine.mosaicker(self.resident(), len(sounds), penalty, gap), penalty, gap)
+
+    def mosaic_long(self, target: Sound, piece_penalty: float = 0.0, block_frames: int = 4096, gap_cost=None) -> "Mosaic":
+        """`mosaic` for one target of any length: a one-lane Mosaicker is pushed the target's frames block_frames at a time
+        and flushed, so the tables hold the uncommitted columns alone, not one byte per (source frame, target frame).  The
+        Mosaic is `mosaic`'s, bit for bit, where `mosaic` takes the target (on f32 engines the features are rounded to f32
+        first, as `mosaic` does).  gap_cost as for `mosaic`."""
+        penalty, gap = self._cover_checks(piece_penalty, "mosaic_long"), _cover_gap_cost(gap_cost)
+        if isinstance(target, (list, tuple)):
+            raise ValueError("mosaic_long takes one Sound")
+        block = int(block_frames)
+        if block < 1 or block != block_frames:
+            raise ValueError("block_frames must be a whole number of frames, at least 1")
+        rows = np.asarray(target.mfcc_arrays(), dtype=self.engine.np_dtype).astype(np.float64)
+        if rows.shape[1:] != (self._dim(),):
+            raise ValueError("mosaic_long: the target's ncoeffs must be the dictionary's")
+        frames = rows.shape[0]
+        mk = self.engine.mosaicker(self.resident(), 1, penalty, gap)
+        try:
+            parts = []
+            for at in range(0, frames, block):
+                if mk.push(rows[at:at + block]):
+                    parts.append(mk.frames()[2:])
+            total = float(mk.best()[0][0])
+            if mk.flush(0):
+                parts.append(mk.frames()[2:])
+        finally:
+            mk.close()
+        if not np.isfinite(total):
+            return Mosaic.none(frames)
+        src, frame, cost, start = (np.concatenate(x) for x in zip(*parts))
+        return Mosaic(_mosaic_tiles(np.flatnonzero(start), src, frame, cost), total, frames, cost)
 
     def cover_long(self, target: Sound, piece_penalty: float = 0.0, block_frames: int = 4096, gap_cost=None) -> "Cover":
         """`cover` for one target of any length: a one-lane Coverer is pushed the target's frames block_frames at a time

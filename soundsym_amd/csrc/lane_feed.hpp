@@ -1,7 +1,8 @@
-// lane_feed.hpp -- what the lane-fed objects share on the host: the spotter (dtw_spotter.hip) and the coverer
-// (dtw_coverer.hip) consume growing sounds lane by lane, in pushes of host frames or by following a stream's resident
-// frames, and flush or reset one lane.  The checks of those calls, their order, their messages and the upload of a push are
-// here once; what an object does with the frames (spotter_run, coverer_run) is its own.
+// lane_feed.hpp -- what the lane-fed objects share on the host: the spotter (dtw_spotter.hip), the coverer
+// (dtw_coverer.hip) and the mosaicker (dtw_mosaicker.hip) consume growing sounds lane by lane, in pushes of host frames or
+// by following a stream's resident frames, and flush or reset one lane.  The checks of those calls, their order, their
+// messages and the upload of a push are here once; what an object does with the frames (spotter_run, coverer_run,
+// mosaicker_run) is its own.
 //
 // The order of the refusals is part of the interface ("the earlier of two faults is the one reported"):
 //   push   : frame_offsets / count NULL | the object's own check | lane by lane: offsets decrease, the lane has ended,
@@ -38,7 +39,7 @@ int32_t copy_out(ssym_ctx *ctx, T *out, const T *dev, size_t n, bool outDev)
     return SSYM_OK;
 }
 
-// what every call refuses before anything else; noun: "spotter", "coverer"
+// what every call refuses before anything else; noun: "spotter", "coverer", "mosaicker"
 template <class Handle>
 int32_t check_handle(ssym_ctx *ctx, const Handle *h, const char *noun, const char *fn)
 {
@@ -55,8 +56,8 @@ int32_t check_handle(ssym_ctx *ctx, const Handle *h, const char *noun, const cha
 
 // what is fed: a view of an object whose handle has been checked
 struct LaneFeed {
-    const char *noun;                                    // "spotter", "coverer"
-    const char *count;                                   // the name of the count output: "out_n_events", "out_n_pieces"
+    const char *noun;                                    // "spotter", "coverer", "mosaicker"
+    const char *count;                                   // the name of the count output: "out_n_events", "out_n_pieces", "out_n_frames"
     uint32_t nLanes, dim;
     const std::vector<uint64_t> &consumed;               // frames per lane
     const std::vector<uint8_t> *ended;                   // NULL: lanes never end

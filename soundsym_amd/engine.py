@@ -648,6 +648,94 @@ class Coverer(_Lanes):
             pass
 
 
+class Mosaicker(_Lanes):
+    """`n_lanes` growing targets tiled by free spans of the uncut recordings of one resident dictionary (ssym_mosaicker;
+    definition in include/soundsym_amd.h and DESIGN.md section 2 "Live mosaic"): every target frame is reported by the
+    push after which no longer recording could change it, the frames from reset to flush are ssym_dtw_mosaic's for the
+    whole, and `best` gives ssym_dtw_mosaic's total for everything consumed so far.  The mosaicker reads the dictionary's
+    resident features for as long as it lives: it keeps `d` alive and must be closed before it."""
+
+    def __init__(self, engine: "Engine", ptr: int, d: _Handle, n_lanes: int, piece_penalty: float, gap_cost=None):
+        self.engine, self.ptr, self.d, self.n_lanes, self.dim = engine, ptr, d, n_lanes, d.dim
+        self.piece_penalty, self.gap_cost = piece_penalty, gap_cost
+        self.n_frames = 0
+
+    def _ran(self, rc, n) -> int:
+        self.n_frames = int(n.value)          # (a call refused after some slices has those slices' frames in its log)
+        nat.check(rc, self.engine.ctx)
+        return self.n_frames
+
+    def push(self, feats, frame_offsets=None) -> int:
+        """ssym_mosaicker_push: lane l consumes the frames feats[frame_offsets[l]:frame_offsets[l+1]] ([frames][dim]; a
+        one-lane mosaicker takes the bare block).  Returns the number of frames the push committed (`frames` reads
+        them)."""
+        x, off = _push_args("mosaicker", self.n_lanes, self.dim, feats, frame_offsets)
+        n = ctypes.c_uint64()
+        return self._ran(nat.lib().ssym_mosaicker_push(self.engine.ctx, self.ptr, x.ctypes.data if x.size else None,
+                                                       off.ctypes.data, 0, ctypes.byref(n)), n)
+
+    def follow(self, stream: "Stream") -> int:
+        """ssym_mosaicker_follow: every lane consumes, device to device, the frames the stream's lane holds beyond those
+        consumed (a lane that has ended is skipped).  Returns as push."""
+        if stream.n_lanes != self.n_lanes or stream.ncoeffs != self.dim:
+            raise ValueError("follow: the stream's lanes and ncoeffs must be the mosaicker's lanes and dim")
+        n = ctypes.c_uint64()
+        return self._ran(nat.lib().ssym_mosaicker_follow(self.engine.ctx, self.ptr, stream.ptr, 0, ctypes.byref(n)), n)
+
+    def frames(self, on_device: bool = False):
+        """The frames of the last push / follow / flush, ordered by (lane, column): (lane uint32 [n], column uint32 [n],
+        src uint32 [n], frame uint32 [n], cost f64 [n], start uint32 [n]).  column counts the lane's frames since its
+        reset; (src, frame, cost) are dtw_mosaic's per-frame outputs (a gap frame: COVER_GAP, NO_MATCH, gap_cost); start
+        is 1 where a piece or a gap frame starts.  on_device: SSYM_OUT_DEVICE, the six arrays as torch tensors."""
+        n = self.n_frames
+        device = self.engine.device if on_device else None
+        (lane, pl), (col, pc), (src, ps), (frame, pf), (cost, pk), (start, pa) = (
+            _output(device, (n,), t) for t in (np.uint32, np.uint32, np.uint32, np.uint32, np.float64, np.uint32))
+        if n:
+            nat.check(nat.lib().ssym_mosaicker_frames(self.engine.ctx, self.ptr, pl, pc, ps, pf, pk, pa,
+                                                      0 if device is None else nat.OUT_DEVICE), self.engine.ctx)
+        return lane, col, src, frame, cost, start
+
+    def flush(self, lane: int = 0) -> int:
+        """ssym_mosaicker_flush: "the lane has ended" -- the rest of its mosaic is emitted, and the lane consumes nothing
+        more until `reset`.  Returns the number of frames."""
+        n = ctypes.c_uint64()
+        return self._ran(nat.lib().ssym_mosaicker_flush(self.engine.ctx, self.ptr, self._lane(lane), ctypes.byref(n)), n)
+
+    def best(self, on_device: bool = False):
+        """(total f64, covered uint32, committed uint32), each [n_lanes]: ssym_dtw_mosaic's total for what the lane has
+        consumed so far (+inf without a mosaic), the frames of the longest prefix that has a mosaic, and the frames
+        that have been emitted."""
+        device = self.engine.device if on_device else None
+        (total, pt), (covered, pc), (committed, pm) = (_output(device, (self.n_lanes,), t)
+                                                      for t in (np.float64, np.uint32, np.uint32))
+        nat.check(nat.lib().ssym_mosaicker_best(self.engine.ctx, self.ptr, pt, pc, pm, 0 if device is None else nat.OUT_DEVICE),
+                  self.engine.ctx)
+        return total, covered, committed
+
+    def counts(self):
+        """(frames consumed per lane [n_lanes] u64, capacity of the ring in columns)."""
+        out = np.zeros(self.n_lanes, dtype=np.uint64)
+        cap = ctypes.c_uint64()
+        nat.check(nat.lib().ssym_mosaicker_counts(self.ptr, out.ctypes.data, ctypes.byref(cap)), self.engine.ctx)
+        return out, int(cap.value)
+
+    def reset(self, lane: int = 0) -> None:
+        """One lane back to "nothing consumed"."""
+        nat.check(nat.lib().ssym_mosaicker_reset(self.engine.ctx, self.ptr, self._lane(lane)), self.engine.ctx)
+
+    def close(self):
+        if self.ptr and self.engine.ctx:
+            nat.lib().ssym_mosaicker_destroy(self.engine.ctx, self.ptr)
+        self.ptr = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class Comm:
     """One rank of a source-sharded run: an RCCL communicator bound to an Engine (ssym_comm)."""
 
@@ -1285,6 +1373,19 @@ class Engine:
             rc = nat.lib().ssym_coverer_create_gaps(self.ctx, d.ptr, lanes, penalty, gap, ctypes.byref(out))
         nat.check(rc, self.ctx)
         return Coverer(self, out.value, d, lanes, penalty, gap)
+
+    def mosaicker(self, d: _Handle, n_lanes: int = 1, piece_penalty: float = 0.0, gap_cost=None) -> Mosaicker:
+        """ssym_mosaicker_create: `n_lanes` growing targets tiled live by free spans of the recordings of `d` (dtw engines
+        without a band; "Live mosaic").  piece_penalty >= 0 is added per piece and gap_cost (None or +inf: no gaps) per
+        frame left uncovered, as for dtw_mosaic; with a gap_cost a NaN frame becomes a gap frame and the lane goes on."""
+        penalty, gap = _cover_penalty(piece_penalty), _cover_gap_cost(gap_cost)
+        lanes = int(n_lanes)
+        if lanes < 1:
+            raise ValueError("n_lanes must be at least 1")
+        out = ctypes.c_void_p()
+        nat.check(nat.lib().ssym_mosaicker_create(self.ctx, d.ptr, lanes, penalty, float("inf") if gap is None else gap,
+                                                  ctypes.byref(out)), self.ctx)
+        return Mosaicker(self, out.value, d, lanes, penalty, gap)
 
     @staticmethod
     def mfcc_num_frames(n_samples: int, pad_tail: bool = False) -> int:
