@@ -38,6 +38,7 @@
 //             minimum, until all positions are equal.  Lane 0 counts the pieces from there down to done and writes them into
 //             the call's piece log in ascending start, with plain stores.  A flush is the same emission from lastFinite.
 // No kernel waits on another workgroup, none spins: stream order is the only ordering between them.
+// Host: the checks and the upload of push / follow / flush / reset are lane_feed.hpp's, and so is the piece log (LaneLog).
 //
 // Gaps (ssym_coverer_create_gaps).  The chain's step takes the gap candidate of "Cover with gaps": a frame left uncovered is a
 // piece of one frame with the source SSYM_COVER_GAP and the cost gap_cost.  1 <= W, so the horizon argument holds as it
@@ -97,11 +98,8 @@ struct ssym_coverer {
     uint64_t backCap = 0;                    // frames per lane of the back-pointer store
     double *bpCost = nullptr;                // [nLanes][backCap], frame e at e mod backCap
     uint32_t *bpLen = nullptr, *bpSrc = nullptr;
-    // the piece log: the pieces of the last push / follow / flush, lane l's from logOff[l] on
-    double *logCost = nullptr;               // [logCap]
-    uint32_t *logWords = nullptr;            // [4][logCap]: lane, src, start, end
-    uint64_t logCap = 0;
-    std::vector<uint64_t> logOff, logCount;
+    // the piece log: the pieces of the last push / follow / flush; the words are lane, src, start, end
+    ssym::LaneLog log{4};
 };
 
 namespace ssym {
@@ -340,9 +338,10 @@ __global__ __launch_bounds__(256) void coverer_best_kernel(const CovLane *lanes,
 void coverer_free(ssym_ctx *ctx, ssym_coverer *cv)
 {
     for (void *p : {(void *)cv->tail, (void *)cv->ringD, (void *)cv->lanes, (void *)cv->dSteps, (void *)cv->dBufOff,
-                    (void *)cv->bpCost, (void *)cv->bpLen, (void *)cv->bpSrc, (void *)cv->logCost, (void *)cv->logWords})
+                    (void *)cv->bpCost, (void *)cv->bpLen, (void *)cv->bpSrc})
         if (p)
             dev_free(ctx, p);
+    cv->log.free(ctx);
     delete cv;
 }
 
@@ -363,14 +362,6 @@ LaneFeed feed_of(ssym_ctx *ctx, const ssym_coverer *cv)
 {
     return LaneFeed{kNoun, "out_n_pieces", cv->nLanes, cv->dim, cv->consumed, &cv->ended, true,
                     [ctx, cv](const char *fn) { return check_dict(ctx, cv, fn); }};
-}
-
-uint64_t pow2_at_least(uint64_t x)
-{
-    uint64_t p = 1;
-    while (p < x)
-        p <<= 1;
-    return p;
 }
 
 // the back-pointer store with room for `frames` per lane (a power of two); the uncommitted stretches move over
@@ -409,32 +400,6 @@ int32_t back_store(ssym_ctx *ctx, ssym_coverer *cv, uint64_t frames)
     cv->bpLen = len;
     cv->bpSrc = src;
     cv->backCap = cap;
-    return SSYM_OK;
-}
-
-// room for `need` pieces in the log; what it held is dropped (a call's log starts empty)
-int32_t log_room(ssym_ctx *ctx, ssym_coverer *cv, uint64_t need)
-{
-    if (need <= cv->logCap)
-        return SSYM_OK;
-    const uint64_t cap = pow2_at_least(std::max<uint64_t>(need, 256));
-    double *cost = nullptr;
-    uint32_t *words = nullptr;
-    int32_t rc = alloc_n(ctx, &cost, (size_t)cap);
-    if (rc == SSYM_OK)
-        rc = alloc_n(ctx, &words, 4 * (size_t)cap);
-    if (rc != SSYM_OK) {
-        if (cost)
-            dev_free(ctx, cost);
-        return rc;
-    }
-    SSYM_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    for (void *p : {(void *)cv->logCost, (void *)cv->logWords})
-        if (p)
-            dev_free(ctx, p);
-    cv->logCost = cost;
-    cv->logWords = words;
-    cv->logCap = cap;
     return SSYM_OK;
 }
 
@@ -495,8 +460,6 @@ int32_t coverer_create(ssym_ctx *ctx, const char *fn, const ssym_dict *dict, uin
     cv->done.assign(n_lanes, -1);
     cv->lastFinite.assign(n_lanes, -1);
     cv->ended.assign(n_lanes, 0);
-    cv->logOff.assign((size_t)n_lanes + 1, 0);
-    cv->logCount.assign(n_lanes, 0);
     rc = alloc_n(ctx, &cv->tail, (size_t)n_lanes * (W - 1) * src.dim);
     if (rc == SSYM_OK)
         rc = alloc_n(ctx, &cv->ringD, (size_t)n_lanes * cv->ring);
@@ -539,23 +502,14 @@ int32_t coverer_run(ssym_ctx *ctx, ssym_coverer *cv, const std::vector<const dou
     const SegmentSet &src = cv->dict->set;
     hipStream_t st = ctx->stream;
     ssym_timings tm{};
-    uint64_t slice = cv->sliceMax, total = 0;
+    uint64_t slice = cv->sliceMax;
     if (const char *k = ssym_knob("SSYM_COVERER_SLICE"))
         slice = std::min<uint64_t>(slice, (uint64_t)std::max(1, atoi(k)));
-    // the log: a piece has a frame at least, so a lane emits no more pieces than it has frames beyond done
-    uint64_t room = 0;
-    for (uint32_t l = 0; l < nL; ++l) {
-        cv->logOff[l] = room;
-        cv->logCount[l] = 0;
-        if (m[l] || l == flushLane)
-            room += cv->consumed[l] + m[l] - (uint64_t)(cv->done[l] + 1);
-        total += m[l];
-    }
-    cv->logOff[nL] = room;
-    tm.n_pairs = (uint64_t)src.n * total;
-    int32_t rc = log_room(ctx, cv, room);
+    int32_t rc = cv->log.begin(ctx, cv->consumed, cv->done, m, flushLane);
     if (rc != SSYM_OK)
         return rc;
+    for (uint32_t l = 0; l < nL; ++l)
+        tm.n_pairs += (uint64_t)src.n * m[l];
     // the frame buffer of a slice: per lane with new frames, its tail and at most `slice` of them
     uint64_t bufFrames = 0;
     for (uint32_t l = 0; l < nL; ++l)
@@ -579,7 +533,7 @@ int32_t coverer_run(ssym_ctx *ctx, ssym_coverer *cv, const std::vector<const dou
             const uint64_t ml = std::min(slice, m[l] - at[l]), n = cv->consumed[l];
             CovStep &s = steps[l];
             s.rows = ml ? rows[l] + at[l] * dim : nullptr;
-            s.logAt = cv->logOff[l] + cv->logCount[l];
+            s.logAt = cv->log.off[l] + cv->log.count[l];
             s.m = (uint32_t)ml;
             s.tail = (uint32_t)std::min<uint64_t>(n, W - 1);
             s.flush = flush && l == flushLane;
@@ -643,11 +597,11 @@ int32_t coverer_run(ssym_ctx *ctx, ssym_coverer *cv, const std::vector<const dou
         k.bpLen = cv->bpLen;
         k.bpSrc = cv->bpSrc;
         k.bpCost = cv->bpCost;
-        k.logLane = cv->logWords;
-        k.logSrc = cv->logWords + cv->logCap;
-        k.logStart = cv->logWords + 2 * cv->logCap;
-        k.logEnd = cv->logWords + 3 * cv->logCap;
-        k.logCost = cv->logCost;
+        k.logLane = cv->log.word(0);
+        k.logSrc = cv->log.word(1);
+        k.logStart = cv->log.word(2);
+        k.logEnd = cv->log.word(3);
+        k.logCost = cv->log.cost;
         coverer_commit_kernel<<<nL, 64, 0, st>>>(k);
         SSYM_HIP_CHECK(ctx, hipGetLastError());
         SSYM_HIP_CHECK(ctx, hipEventRecord(ev[2], st));
@@ -659,7 +613,7 @@ int32_t coverer_run(ssym_ctx *ctx, ssym_coverer *cv, const std::vector<const dou
             cv->consumed[l] = (uint64_t)state[l].n;
             cv->done[l] = state[l].done;
             cv->lastFinite[l] = state[l].lastFinite;
-            cv->logCount[l] += state[l].count;
+            cv->log.count[l] += state[l].count;
             at[l] += steps[l].m;
         }
         tm.main_ms += ev_ms(ev[0], ev[1]);
@@ -671,10 +625,7 @@ int32_t coverer_run(ssym_ctx *ctx, ssym_coverer *cv, const std::vector<const dou
     }
     if (flush)
         cv->ended[flushLane] = 1;
-    uint64_t pieces = 0;
-    for (uint32_t l = 0; l < nL; ++l)
-        pieces += cv->logCount[l];
-    *out_n_pieces = pieces;
+    *out_n_pieces = cv->log.total();
     ctx->timings = tm;
     return SSYM_OK;
 }
@@ -746,26 +697,8 @@ int32_t coverer_pieces(ssym_ctx *ctx, const ssym_coverer *cv, uint32_t *out_lane
     if (rc != SSYM_OK)
         return rc;
     SSYM_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-    const bool outDev = (flags & SSYM_OUT_DEVICE) != 0;
-    const size_t cap = cv->logCap;
     uint32_t *const outs[4] = {out_lane, out_src, out_start, out_end};
-    size_t to = 0;
-    bool any = false;
-    for (uint32_t l = 0; l < cv->nLanes; ++l) {          // the lanes' stretches of the log, one behind the other
-        const size_t from = cv->logOff[l], n = cv->logCount[l];
-        if (n == 0)
-            continue;
-        any = true;
-        rc = copy_out(ctx, out_cost ? out_cost + to : nullptr, cv->logCost + from, n, outDev);
-        for (int w = 0; w < 4 && rc == SSYM_OK; ++w)
-            rc = copy_out(ctx, outs[w] ? outs[w] + to : nullptr, cv->logWords + w * cap + from, n, outDev);
-        if (rc != SSYM_OK)
-            return rc;
-        to += n;
-    }
-    if (any)
-        SSYM_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    return SSYM_OK;
+    return cv->log.copy(ctx, out_cost, outs, (flags & SSYM_OUT_DEVICE) != 0);
 }
 
 int32_t coverer_best(ssym_ctx *ctx, const ssym_coverer *cv, double *out_total, uint32_t *out_covered, uint32_t *out_committed,
@@ -778,32 +711,16 @@ int32_t coverer_best(ssym_ctx *ctx, const ssym_coverer *cv, double *out_total, u
         return SSYM_OK;
     SSYM_HIP_CHECK(ctx, hipSetDevice(ctx->device));
     const uint32_t nL = cv->nLanes;
-    const unsigned grid = (nL + 255) / 256;
-    if (flags & SSYM_OUT_DEVICE) {
-        coverer_best_kernel<<<grid, 256, 0, ctx->stream>>>(cv->lanes, cv->ringD, cv->ring, nL, out_total, out_covered, out_committed);
-        SSYM_HIP_CHECK(ctx, hipGetLastError());
-        SSYM_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-        return SSYM_OK;
-    }
+    // the caller's device arrays in place, or one f64 and one u32 block copied back
+    StagedOut out(flags, {{out_total, nL}}, {{out_covered, nL}, {out_committed, nL}});
     Blocks bl(ctx);
-    double *dTotal = nullptr;
-    uint32_t *dWords = nullptr;
-    rc = bl.get(&dTotal, (size_t)nL);
-    if (rc == SSYM_OK)
-        rc = bl.get(&dWords, 2 * (size_t)nL);
+    rc = out.alloc(bl);
     if (rc != SSYM_OK)
         return rc;
-    coverer_best_kernel<<<grid, 256, 0, ctx->stream>>>(cv->lanes, cv->ringD, cv->ring, nL, dTotal, dWords, dWords + nL);
+    coverer_best_kernel<<<(nL + 255) / 256, 256, 0, ctx->stream>>>(cv->lanes, cv->ringD, cv->ring, nL, out.f64[0], out.u32[0],
+                                                                    out.u32[1]);
     SSYM_HIP_CHECK(ctx, hipGetLastError());
-    rc = copy_out(ctx, out_total, (const double *)dTotal, nL, false);
-    if (rc == SSYM_OK)
-        rc = copy_out(ctx, out_covered, (const uint32_t *)dWords, nL, false);
-    if (rc == SSYM_OK)
-        rc = copy_out(ctx, out_committed, (const uint32_t *)dWords + nL, nL, false);
-    if (rc != SSYM_OK)
-        return rc;
-    SSYM_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    return SSYM_OK;
+    return out.finish(ctx);
 }
 
 }  // namespace

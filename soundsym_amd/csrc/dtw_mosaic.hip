@@ -30,8 +30,10 @@
 //
 // Mapping.  Column j needs the least value of ALL of column j-1, over every source frame, so each column ends in a
 // reduction over the whole dictionary: the row wavefront of dtw_wave.hpp cannot express that.
-//   forward   mosaic_forward_kernel, one workgroup per target, the column loop inside.  The source frames are spread over
-//             the threads (g = thread, thread + blockDim, ...).  E and N of column j-1 sit in a ping-pong slab of global
+//   forward   mosaic_forward_kernel, one workgroup per target, the column loop inside; the body of a column is
+//             mosaic_column (dtw_mosaic_common.hpp), which the live mosaic's forward kernel runs as well -- the kernel keeps
+//             column -1, the first frame and the total.  The source frames are spread over the threads (g = thread,
+//             thread + blockDim, ...).  E and N of column j-1 sit in a ping-pong slab of global
 //             scratch per workgroup (4 G doubles, L2-resident at these sizes; one code path for every G); column -1 is a
 //             slab of +inf, which makes column 0 the general column.  A thread forms c(g,j) in the oracle's order from
 //             its source frame in global memory and the target frame in a two-row LDS ring (mosaic_cost: dtw_wave.hpp's
@@ -45,8 +47,10 @@
 //             the gap candidate itself: best(j) and the next S are in every thread's registers, thread 0 stores arg(j).
 //             The same barrier orders the slab, the ring row and the pairs (both double-buffered by the column's parity).
 //   backward  mosaic_backtrace_kernel, one workgroup per target on the forward launch's grid: thread 0 walks the bytes
-//             back, T steps at most, clamping g whatever the bytes hold, and leaves (g | start bit) or GAP per column in
-//             the arg row; it then lists the starts.  All threads fill the per-frame outputs from that row and pad.
+//             back from arg(T-1) (mosaic_walk, dtw_mosaic_common.hpp: the backward rule over keys, the one the live
+//             mosaic's commit runs; T steps at most, g clamped whatever the bytes hold) and leaves (g | start bit) or GAP
+//             per column in the arg row; it then lists and counts the starts.  All threads fill the per-frame outputs from
+//             that row (mosaic_frame) and pad.
 //             (As the forward kernel's tail the same lines cost that kernel 49 spilled SGPRs.)
 // A call whose slabs would pass the scratch cap runs fewer workgroups than targets: rounds of `grid` targets, a forward and
 // a back-trace launch each, in stream order on the same slabs.
@@ -62,24 +66,19 @@ namespace ssym {
 
 namespace {
 
-constexpr uint32_t kNone = kCoverNone, kGap = kCoverGap;
+constexpr uint32_t kNone = kCoverNone;
 
 struct MosaicArgs {
+    MosaicCore k;                // k.G: source frames of the whole dictionary; k.slab: [grid][4 G + 1], E / N of the two
+                                 // parities, then best(T-1)
     const double *srcRaw;
     const uint64_t *srcOff;
     uint32_t nSrc;
-    uint32_t G;                  // source frames of the whole dictionary
     const double *tgtRaw;
     const uint64_t *tgtOff;
     uint32_t nTgt;
     uint32_t t0;                 // the round's first target: workgroup b takes target t0 + b
-    uint32_t dim;
-    int squared;
-    double penalty, gapCost;
     uint64_t maxT;               // the longest target: what a workgroup's rows hold
-    const uint8_t *posc;         // [G] min(pos(g), 2)
-    const double *srcT;          // [dim][G] the source frames, transposed
-    double *state;               // [grid][4 G + 1]: E / N of the two parities, then best(T-1)
     uint32_t *path;              // [grid][maxT] arg(j); after the walk g | kMosaicStart, or GAP
     uint8_t *dir;                // [grid][maxT][G]
     uint32_t *outCount;          // [nTgt]; every output may be NULL
@@ -94,107 +93,36 @@ __global__ __launch_bounds__(kMosaicThreads) void mosaic_forward_kernel(const Mo
     __shared__ double partV[2][kMosaicMaxWaves];
     __shared__ uint32_t partG[2][kMosaicMaxWaves];
     const double INF = __builtin_inf();
-    const uint32_t tid = threadIdx.x, nthr = blockDim.x, wave = tid >> 6, nWaves = nthr >> 6;
-    const uint32_t G = a.G, dim = a.dim;
-    double *slab = a.state + (size_t)blockIdx.x * (4 * (size_t)G + 1);
-    uint32_t *path = a.path + (size_t)blockIdx.x * a.maxT;
-    uint8_t *dir = a.dir + (size_t)blockIdx.x * a.maxT * G;
+    const uint32_t tid = threadIdx.x, nthr = blockDim.x;
+    const uint32_t G = a.k.G, dim = a.k.dim;
+    MosaicCore k = a.k;
+    k.slab += (size_t)blockIdx.x * (4 * (size_t)G + 1);
+    const MosaicColumns cols{a.dir + (size_t)blockIdx.x * a.maxT * G, a.path + (size_t)blockIdx.x * a.maxT, G, ~0ull};
     const uint32_t t = a.t0 + blockIdx.x;
     if (t >= a.nTgt)
         return;
-    {
-        const uint64_t f0 = a.tgtOff[t];
-        const uint64_t T = a.tgtOff[t + 1] - f0;
-        const double *b0 = a.tgtRaw + f0 * dim;
-        // column -1: nothing to continue and nothing to repeat
-        for (uint32_t g = tid; g < G; g += nthr) {
-            slab[(size_t)2 * G + g] = INF;
-            slab[(size_t)3 * G + g] = INF;
-        }
-        if (T)
-            for (uint32_t e = tid; e < dim; e += nthr)
-                ring[0][e] = b0[e];
-        __syncthreads();
+    const uint64_t f0 = a.tgtOff[t];
+    const uint64_t T = a.tgtOff[t + 1] - f0;
+    const double *b0 = a.tgtRaw + f0 * dim;
+    // column -1: nothing to continue and nothing to repeat
+    for (uint32_t g = tid; g < G; g += nthr) {
+        k.slab[(size_t)2 * G + g] = INF;
+        k.slab[(size_t)3 * G + g] = INF;
+    }
+    if (T)
+        for (uint32_t e = tid; e < dim; e += nthr)
+            ring[0][e] = b0[e];
+    __syncthreads();
 
-        double best = 0.0;                                   // best(j-1), the same in every thread
-        for (uint64_t j = 0; j < T; ++j) {
-            const uint32_t par = (uint32_t)j & 1;
-            const double S = __dadd_rn(a.penalty, best);
-            const double *Eo = slab + (size_t)(par ^ 1) * 2 * G, *No = Eo + G;
-            double *En = slab + (size_t)par * 2 * G, *Nn = En + G;
-            uint8_t *dcol = dir + j * G;
-            double bv = INF;
-            uint32_t bg = kNone;
-            for (uint32_t g = tid; g < G; g += nthr) {
-                const uint32_t pc = a.posc[g];
-                const double nOld = No[g];
-                double P = INF;
-                uint32_t code = 0;
-                if (pc >= 1)
-                    P = Eo[g - 1];
-                if (pc >= 2) {
-                    const double e2 = Eo[g - 2];
-                    if (e2 < P) {
-                        P = e2;
-                        code = 1;
-                    }
-                }
-                if (!(P <= S)) {
-                    P = S;
-                    code = 2;
-                }
-                const double c = mosaic_cost(a.srcT + g, G, ring[par], dim, a.squared);
-                const double nD = __dadd_rn(c, P);
-                const double hD = __dadd_rn(c, nOld);
-                const bool rep = hD < nD;
-                const double eD = rep ? hD : nD;
-                En[g] = eD;
-                Nn[g] = nD;
-                dcol[g] = (uint8_t)(code << 1 | (rep ? 1u : 0u));
-                if (eD < bv) {                               // g ascends within a thread: the first minimum stays
-                    bv = eD;
-                    bg = g;
-                }
-            }
+    double best = 0.0;                                       // best(j-1), the same in every thread
+    for (uint64_t j = 0; j < T; ++j)
+        best = mosaic_column(k, cols, j, best, ring, partV, partG, [&](double *row) {
             if (j + 1 < T)
                 for (uint32_t e = tid; e < dim; e += nthr)
-                    ring[par ^ 1][e] = b0[(j + 1) * dim + e];
-#pragma unroll
-            for (int m = 32; m >= 1; m >>= 1) {
-                const double oV = __shfl_xor(bv, m);
-                const uint32_t oG = (uint32_t)__shfl_xor((int)bg, m);
-                if (oV < bv || (oV == bv && oG < bg)) {
-                    bv = oV;
-                    bg = oG;
-                }
-            }
-            if ((tid & 63) == 0) {
-                partV[par][wave] = bv;
-                partG[par][wave] = bg;
-            }
-            __syncthreads();
-            double v = INF;
-            uint32_t arg = kNone;
-            for (uint32_t w = 0; w < nWaves; ++w) {
-                const double oV = partV[par][w];
-                const uint32_t oG = partG[par][w];
-                if (oV < v || (oV == v && oG < arg)) {
-                    v = oV;
-                    arg = oG;
-                }
-            }
-            const double vg = __dadd_rn(a.gapCost, best);
-            if (vg < v) {
-                v = vg;
-                arg = kGap;
-            }
-            best = v;
-            if (tid == 0)
-                path[j] = arg;
-        }
-        if (tid == 0)
-            slab[(size_t)4 * G] = T ? best : INF;
-    }
+                    row[e] = b0[(j + 1) * dim + e];
+        });
+    if (tid == 0)
+        k.slab[(size_t)4 * G] = T ? best : INF;
 }
 
 __global__ __launch_bounds__(kMosaicThreads) void mosaic_backtrace_kernel(const MosaicArgs a)
@@ -202,89 +130,48 @@ __global__ __launch_bounds__(kMosaicThreads) void mosaic_backtrace_kernel(const 
     __shared__ uint32_t shCount;
     const double INF = __builtin_inf();
     const uint32_t tid = threadIdx.x, nthr = blockDim.x;
-    const uint32_t G = a.G, dim = a.dim;
-    uint32_t *path = a.path + (size_t)blockIdx.x * a.maxT;
-    const uint8_t *dir = a.dir + (size_t)blockIdx.x * a.maxT * G;
+    const uint32_t G = a.k.G, dim = a.k.dim;
+    const MosaicColumns cols{a.dir + (size_t)blockIdx.x * a.maxT * G, a.path + (size_t)blockIdx.x * a.maxT, G, ~0ull};
     const uint32_t t = a.t0 + blockIdx.x;
     if (t >= a.nTgt)
         return;
-    {
-        const uint64_t f0 = a.tgtOff[t];
-        const uint64_t T = a.tgtOff[t + 1] - f0;
-        const double *b0 = a.tgtRaw + f0 * dim;
-        const double best = a.state[(size_t)blockIdx.x * (4 * (size_t)G + 1) + (size_t)4 * G];
-        const bool ok = T > 0 && best < INF;
-        if (tid == 0) {
-            uint32_t count = 0;
-            if (ok) {
-                uint32_t g = path[T - 1];
-                bool forceN = false;
-                for (uint64_t j = T; j-- > 0;) {             // T steps, whatever the bytes hold
-                    if (g >= G) {                            // GAP (anything else beyond G cannot be; it is read as one)
-                        path[j] = kGap;
-                        ++count;
-                        forceN = false;
-                        if (j)
-                            g = path[j - 1];
-                        continue;
-                    }
-                    const uint32_t d = dir[j * G + g];
-                    if ((d & 1) && !forceN) {                // state H: the cell before is (g, j-1) in state N
-                        path[j] = g;
-                        forceN = true;
-                        continue;
-                    }
-                    forceN = false;
-                    const uint32_t code = d >> 1;
-                    if (code >= 2 || j == 0) {               // a piece starts here
-                        path[j] = g | kMosaicStart;
-                        ++count;
-                        if (j)
-                            g = path[j - 1];
-                    } else {
-                        path[j] = g;
-                        g = g > code ? g - 1 - code : 0;
-                    }
+    const uint64_t f0 = a.tgtOff[t];
+    const uint64_t T = a.tgtOff[t + 1] - f0;
+    const double *b0 = a.tgtRaw + f0 * dim;
+    const double best = a.k.slab[(size_t)blockIdx.x * (4 * (size_t)G + 1) + (size_t)4 * G];
+    const bool ok = T > 0 && best < INF;
+    if (tid == 0) {
+        uint32_t count = 0;
+        if (ok) {
+            const long long top = (long long)T - 1;
+            mosaic_walk(cols, mosaic_enter(cols, cols.word(top), top), top, -1);
+            for (uint64_t j = 0; j < T; ++j)
+                if (cols.arg[j] & kMosaicStart) {            // a piece or a gap frame starts: GAP has the bit as well
+                    if (a.outStart)
+                        a.outStart[f0 + count] = (uint32_t)j;
+                    ++count;
                 }
-                if (a.outStart) {
-                    uint32_t k = 0;
-                    for (uint64_t j = 0; j < T; ++j)
-                        if (path[j] & kMosaicStart)          // GAP has the bit as well
-                            a.outStart[f0 + k++] = (uint32_t)j;
-                }
-            }
-            if (a.outCount)
-                a.outCount[t] = count;
-            if (a.outTotal)
-                a.outTotal[t] = ok ? best : INF;
-            shCount = count;
         }
-        __syncthreads();
-        const uint32_t count = shCount;
-        for (uint64_t f = tid; f < T; f += nthr) {
-            uint32_t src = kNone, frame = kNone;
-            double cost = INF;
-            if (ok) {
-                const uint32_t p = path[f];
-                if (p == kGap) {
-                    src = kGap;
-                    cost = a.gapCost;
-                } else {
-                    const uint32_t g = min(p & ~kMosaicStart, G - 1);
-                    src = mosaic_segment(a.srcOff, a.nSrc, g);
-                    frame = (uint32_t)(g - a.srcOff[src]);
-                    cost = mosaic_cost(a.srcRaw + (size_t)g * dim, 1, b0 + f * dim, dim, a.squared);
-                }
-            }
-            if (a.outSrc)
-                a.outSrc[f0 + f] = src;
-            if (a.outFrame)
-                a.outFrame[f0 + f] = frame;
-            if (a.outCost)
-                a.outCost[f0 + f] = cost;
-            if (a.outStart && f >= count)
-                a.outStart[f0 + f] = kNone;
-        }
+        if (a.outCount)
+            a.outCount[t] = count;
+        if (a.outTotal)
+            a.outTotal[t] = ok ? best : INF;
+        shCount = count;
+    }
+    __syncthreads();
+    const uint32_t count = shCount;
+    for (uint64_t f = tid; f < T; f += nthr) {
+        MosaicFrame o{kNone, kNone, INF};
+        if (ok)
+            o = mosaic_frame(cols.arg[f], a.srcRaw, a.srcOff, a.nSrc, a.k, b0 + f * dim);
+        if (a.outSrc)
+            a.outSrc[f0 + f] = o.src;
+        if (a.outFrame)
+            a.outFrame[f0 + f] = o.frame;
+        if (a.outCost)
+            a.outCost[f0 + f] = o.cost;
+        if (a.outStart && f >= count)
+            a.outStart[f0 + f] = kNone;
     }
 }
 
@@ -367,24 +254,24 @@ int32_t dtw_mosaic(ssym_ctx *ctx, const ssym_dict *dict, const ssym_queries *q, 
     if (rc != SSYM_OK)
         return rc;
     char *base = (char *)ctx->mosaic_tab.ptr;
-    a.state = (double *)base;
+    a.k.slab = (double *)base;
     a.path = (uint32_t *)(base + stateBytes);
     double *srcT = (double *)(base + stateBytes + pathBytes);
     uint8_t *posc = (uint8_t *)(srcT + G * src.dim);
-    a.srcT = srcT;
-    a.posc = posc;
+    a.k.srcT = srcT;
+    a.k.posc = posc;
     a.dir = (uint8_t *)srcT + posBytes;
     a.srcRaw = src.raw;
     a.srcOff = src.off;
     a.nSrc = src.n;
-    a.G = (uint32_t)G;
+    a.k.G = (uint32_t)G;
     a.tgtRaw = tgt.raw;
     a.tgtOff = tgt.off;
     a.nTgt = M;
-    a.dim = src.dim;
-    a.squared = ctx->squared;
-    a.penalty = piece_penalty;
-    a.gapCost = gap_cost;
+    a.k.dim = src.dim;
+    a.k.squared = ctx->squared;
+    a.k.penalty = piece_penalty;
+    a.k.gapCost = gap_cost;
     a.maxT = maxT;
 
     hipEvent_t *ev = ctx->ev;

@@ -31,19 +31,22 @@
 //
 // Mapping.
 //   create    mosaic_prep_kernel (dtw_mosaic_common.hpp) once: pos(g) and the transposed source frames stay with the object.
-//   forward   mosaicker_forward_kernel, one workgroup per lane with new frames, the column loop of mosaic_forward_kernel:
-//             the same operations in the same order.  E / N of column j sit in the lane's slab at parity j & 1 (4 G doubles
-//             per lane), so column n-1 is where a push finds it; best(n-1) comes from the lane's record.  Direction bytes,
-//             arg(j) and the target frame (the emission's frame cost needs it) go into the lane's ring, column j at
-//             j mod cap.  The loop stops at the first column whose best is not finite: the slab of column lastFinite stays.
+//   forward   mosaicker_forward_kernel, one workgroup per lane with new frames: the column body is mosaic_column
+//             (dtw_mosaic_common.hpp), the one mosaic_forward_kernel runs.  E / N of column j sit in the lane's slab at
+//             parity j & 1 (4 G doubles per lane), so column n-1 is where a push finds it; best(n-1) comes from the lane's
+//             record.  Direction bytes, arg(j) and the target frame (the emission's frame cost needs it) go into the lane's
+//             ring, column j at j mod cap.  The loop stops at the first column whose best is not finite: the slab of column
+//             lastFinite stays.
 //   commit    mosaicker_commit_kernel, one workgroup per lane.  The live keys of column lastFinite are collected into a
 //             list; each step maps the list one column back through the ring into a second list, a key going in only if it
 //             is the first to raise its flag (duplicates drop as walks merge; the flags are lowered again before the next
 //             step).  It stops when one key is left (at once when the keys already agree) or at column done + 1.  Thread 0
-//             then walks from that key down to done + 1 as mosaic_backtrace_kernel's thread 0 does, leaving g | start bit
-//             or GAP in the arg ring, and all threads fill the call's frame log in ascending column with plain stores.
-//             A flush is the same emission from arg(lastFinite).
+//             then walks from that key down to done + 1, leaving g | start bit or GAP in the arg ring, and all threads fill
+//             the call's frame log in ascending column with plain stores.  The keys, the step back, the walk and the frame's
+//             (src, frame, cost) are dtw_mosaic_common.hpp's (mosaic_enter / mosaic_back, mosaic_walk, mosaic_frame), the ones
+//             mosaic_backtrace_kernel runs on the offline tables.  A flush is the same emission from arg(lastFinite).
 //   regrow    mosaicker_regrow_kernel moves the uncommitted columns when the ring doubles.
+// Host: the checks and the upload of push / follow / flush / reset are lane_feed.hpp's, and so is the frame log (LaneLog).
 // No workgroup waits on another: no spin wait; stream order is the only ordering between kernels.
 #include "dtw_mosaic_common.hpp"
 #include "lane_feed.hpp"
@@ -102,17 +105,14 @@ struct ssym_mosaicker {
     uint8_t *dir = nullptr;                  // [nLanes][cap][G], column j at j mod cap
     uint32_t *arg = nullptr;                 // [nLanes][cap]
     double *frames = nullptr;                // [nLanes][cap][dim]
-    // the frame log: the frames of the last push / follow / flush, lane l's from logOff[l] on
-    double *logCost = nullptr;               // [logCap]
-    uint32_t *logWords = nullptr;            // [5][logCap]: lane, column, src, frame, start
-    uint64_t logCap = 0;
-    std::vector<uint64_t> logOff, logCount;
+    // the frame log: the frames of the last push / follow / flush; the words are lane, column, src, frame, start
+    ssym::LaneLog log{5};
 };
 
 namespace ssym {
 namespace {
 
-constexpr uint32_t kNone = kCoverNone, kGap = kCoverGap;
+constexpr uint32_t kGap = kCoverGap;
 
 __global__ __launch_bounds__(256) void mosaicker_init_kernel(MosLane *lanes, uint32_t lane0, uint32_t nLanes)
 {
@@ -124,16 +124,21 @@ __global__ __launch_bounds__(256) void mosaicker_init_kernel(MosLane *lanes, uin
 struct MosForwardArgs {
     const MosStep *steps;
     MosLane *lanes;
-    uint32_t G, dim;
-    int squared;
-    double penalty, gapCost;
-    const uint8_t *posc;
-    const double *srcT;
-    double *slab;
+    MosaicCore k;                // k.slab: [nLanes][4 G]
     uint64_t cap;
     uint8_t *dir;
     uint32_t *arg;
     double *frames;
+};
+
+// the commit walks the same ring; its emission reads the dictionary's raw rows and fills the log
+struct MosCommitArgs : MosForwardArgs {
+    const double *srcRaw;
+    const uint64_t *srcOff;
+    uint32_t nSrc;
+    uint32_t *keys;
+    uint32_t *logLane, *logColumn, *logSrc, *logFrame, *logStart;
+    double *logCost;
 };
 
 __global__ __launch_bounds__(kMosaicThreads) void mosaicker_forward_kernel(const MosForwardArgs a)
@@ -142,8 +147,8 @@ __global__ __launch_bounds__(kMosaicThreads) void mosaicker_forward_kernel(const
     __shared__ double partV[2][kMosaicMaxWaves];
     __shared__ uint32_t partG[2][kMosaicMaxWaves];
     const double INF = __builtin_inf();
-    const uint32_t tid = threadIdx.x, nthr = blockDim.x, wave = tid >> 6, nWaves = nthr >> 6;
-    const uint32_t G = a.G, dim = a.dim, l = blockIdx.x;
+    const uint32_t tid = threadIdx.x, nthr = blockDim.x;
+    const uint32_t G = a.k.G, dim = a.k.dim, l = blockIdx.x;
     const MosStep s = a.steps[l];
     if (s.m == 0)
         return;
@@ -153,17 +158,17 @@ __global__ __launch_bounds__(kMosaicThreads) void mosaicker_forward_kernel(const
             a.lanes[l].n = st.n + s.m;
         return;
     }
-    double *slab = a.slab + (size_t)l * 4 * G;
+    MosaicCore k = a.k;
+    k.slab += (size_t)l * 4 * G;
     const uint64_t mask = a.cap - 1;
-    uint32_t *path = a.arg + (size_t)l * a.cap;
-    uint8_t *dir = a.dir + (size_t)l * a.cap * G;
+    const MosaicColumns cols{a.dir + (size_t)l * a.cap * G, a.arg + (size_t)l * a.cap, G, mask};
     double *kept = a.frames + (size_t)l * a.cap * dim;
     const double *b0 = s.rows;
     const uint64_t n = (uint64_t)st.n;
     if (n == 0)                                              // column -1: nothing to continue and nothing to repeat
         for (uint32_t g = tid; g < G; g += nthr) {
-            slab[(size_t)2 * G + g] = INF;
-            slab[(size_t)3 * G + g] = INF;
+            k.slab[(size_t)2 * G + g] = INF;
+            k.slab[(size_t)3 * G + g] = INF;
         }
     for (uint32_t e = tid; e < dim; e += nthr) {
         const double v = b0[e];
@@ -178,82 +183,14 @@ __global__ __launch_bounds__(kMosaicThreads) void mosaicker_forward_kernel(const
     uint64_t j = n;
     const uint64_t end = n + s.m;
     for (; j < end; ++j) {
-        const uint32_t par = (uint32_t)j & 1;
-        const double S = __dadd_rn(a.penalty, best);
-        const double *Eo = slab + (size_t)(par ^ 1) * 2 * G, *No = Eo + G;
-        double *En = slab + (size_t)par * 2 * G, *Nn = En + G;
-        uint8_t *dcol = dir + (j & mask) * G;
-        double bv = INF;
-        uint32_t bg = kNone;
-        for (uint32_t g = tid; g < G; g += nthr) {
-            const uint32_t pc = a.posc[g];
-            const double nOld = No[g];
-            double P = INF;
-            uint32_t code = 0;
-            if (pc >= 1)
-                P = Eo[g - 1];
-            if (pc >= 2) {
-                const double e2 = Eo[g - 2];
-                if (e2 < P) {
-                    P = e2;
-                    code = 1;
+        best = mosaic_column(k, cols, j, best, ring, partV, partG, [&](double *row) {
+            if (j + 1 < end)
+                for (uint32_t e = tid; e < dim; e += nthr) {
+                    const double v = b0[(j + 1 - n) * dim + e];
+                    row[e] = v;
+                    kept[((j + 1) & mask) * dim + e] = v;    // the emission's frame cost needs it
                 }
-            }
-            if (!(P <= S)) {
-                P = S;
-                code = 2;
-            }
-            const double c = mosaic_cost(a.srcT + g, G, ring[par], dim, a.squared);
-            const double nD = __dadd_rn(c, P);
-            const double hD = __dadd_rn(c, nOld);
-            const bool rep = hD < nD;
-            const double eD = rep ? hD : nD;
-            En[g] = eD;
-            Nn[g] = nD;
-            dcol[g] = (uint8_t)(code << 1 | (rep ? 1u : 0u));
-            if (eD < bv) {                                   // g ascends within a thread: the first minimum stays
-                bv = eD;
-                bg = g;
-            }
-        }
-        if (j + 1 < end)
-            for (uint32_t e = tid; e < dim; e += nthr) {
-                const double v = b0[(j + 1 - n) * dim + e];
-                ring[par ^ 1][e] = v;
-                kept[((j + 1) & mask) * dim + e] = v;
-            }
-#pragma unroll
-        for (int m = 32; m >= 1; m >>= 1) {
-            const double oV = __shfl_xor(bv, m);
-            const uint32_t oG = (uint32_t)__shfl_xor((int)bg, m);
-            if (oV < bv || (oV == bv && oG < bg)) {
-                bv = oV;
-                bg = oG;
-            }
-        }
-        if ((tid & 63) == 0) {
-            partV[par][wave] = bv;
-            partG[par][wave] = bg;
-        }
-        __syncthreads();
-        double v = INF;
-        uint32_t arg = kNone;
-        for (uint32_t w = 0; w < nWaves; ++w) {
-            const double oV = partV[par][w];
-            const uint32_t oG = partG[par][w];
-            if (oV < v || (oV == v && oG < arg)) {
-                v = oV;
-                arg = oG;
-            }
-        }
-        const double vg = __dadd_rn(a.gapCost, best);
-        if (vg < v) {
-            v = vg;
-            arg = kGap;
-        }
-        best = v;
-        if (tid == 0)
-            path[j & mask] = arg;
+        });
         if (!(best < INF)) {                                 // the lane dies here (every thread sees the same best)
             ++j;
             break;
@@ -272,25 +209,6 @@ __global__ __launch_bounds__(kMosaicThreads) void mosaicker_forward_kernel(const
     }
 }
 
-struct MosCommitArgs {
-    const MosStep *steps;
-    MosLane *lanes;
-    uint32_t G, dim;
-    int squared;
-    double penalty, gapCost;
-    const double *srcRaw;
-    const uint64_t *srcOff;
-    uint32_t nSrc;
-    const double *slab;
-    uint32_t *keys;
-    uint64_t cap;
-    const uint8_t *dir;
-    uint32_t *arg;
-    const double *frames;
-    uint32_t *logLane, *logColumn, *logSrc, *logFrame, *logStart;
-    double *logCost;
-};
-
 __global__ __launch_bounds__(kMosaicThreads) void mosaicker_commit_kernel(const MosCommitArgs a)
 {
     __shared__ uint32_t shN[2];
@@ -301,30 +219,12 @@ __global__ __launch_bounds__(kMosaicThreads) void mosaicker_commit_kernel(const 
         return;
     const double INF = __builtin_inf();
     const MosLane st = a.lanes[l];
-    const uint32_t G = a.G, dim = a.dim;
-    const uint64_t mask = a.cap - 1;
-    const uint8_t *dir = a.dir + (size_t)l * a.cap * G;
-    uint32_t *path = a.arg + (size_t)l * a.cap;
+    const uint32_t G = a.k.G, dim = a.k.dim;
+    const MosaicColumns cols{a.dir + (size_t)l * a.cap * G, a.arg + (size_t)l * a.cap, G, a.cap - 1};
     const double *kept = a.frames + (size_t)l * a.cap * dim;
     const size_t K = 2 * (size_t)G + 2;
     uint32_t *lists = a.keys + (size_t)l * 3 * K, *flag = lists + 2 * K;
     const long long done = st.done, top = st.lastFinite;
-    // a key: g << 1 | (1: state H), or GAP.  Whatever the ring holds, a key's g stays below G.
-    auto key_e = [&](uint32_t g, long long j) -> uint32_t {
-        return g >= G ? kGap : g << 1 | (dir[((uint64_t)j & mask) * G + g] & 1u);
-    };
-    // the key at column j - 1 of the walk that holds `key` at column j (j - 1 > done: its column is in the ring)
-    auto back = [&](uint32_t key, long long j) -> uint32_t {
-        if (key == kGap)
-            return key_e(path[(uint64_t)(j - 1) & mask], j - 1);
-        const uint32_t g = key >> 1;
-        if (key & 1)
-            return g << 1;
-        const uint32_t code = dir[((uint64_t)j & mask) * G + g] >> 1;
-        if (code >= 2)
-            return key_e(path[(uint64_t)(j - 1) & mask], j - 1);
-        return key_e(g > code ? g - 1 - code : 0, j - 1);
-    };
     auto slot = [&](uint32_t key) -> size_t { return key == kGap ? 2 * (size_t)G : key; };
 
     long long c = done;                                      // the last column that is final
@@ -332,17 +232,16 @@ __global__ __launch_bounds__(kMosaicThreads) void mosaicker_commit_kernel(const 
     if (top > done) {
         if (s.flush) {
             c = top;
-            tip = key_e(path[(uint64_t)top & mask], top);
+            tip = mosaic_enter(cols, cols.word(top), top).key;
         } else {
             // live(lastFinite + 1): for a lane that lives lastFinite = n - 1; for one that died the last commit there was
             if (tid == 0)
                 shN[0] = shN[1] = 0;
             __syncthreads();
-            const double S = __dadd_rn(a.penalty, st.bestFinite);
-            const double *E = a.slab + (size_t)l * 4 * G + (size_t)((uint64_t)top & 1) * 2 * G, *N = E + G;
-            const uint8_t *dcol = dir + ((uint64_t)top & mask) * G;
+            const double S = __dadd_rn(a.k.penalty, st.bestFinite);
+            const double *E = a.k.slab + (size_t)l * 4 * G + (size_t)((uint64_t)top & 1) * 2 * G, *N = E + G;
             for (uint32_t g = tid; g < G; g += nthr) {
-                const uint32_t d = dcol[g];
+                const uint32_t d = cols.byte(top, g);
                 const double e = E[g];
                 if (e > -INF && e <= S)
                     lists[atomicAdd(&shN[0], 1u)] = g << 1 | (d & 1u);
@@ -352,9 +251,10 @@ __global__ __launch_bounds__(kMosaicThreads) void mosaicker_commit_kernel(const 
                         lists[atomicAdd(&shN[0], 1u)] = g << 1;
                 }
             }
-            if (tid == 0 && path[(uint64_t)top & mask] == kGap)
+            if (tid == 0 && cols.word(top) == kGap)
                 lists[atomicAdd(&shN[0], 1u)] = kGap;
             __syncthreads();
+            // every step maps the list one column back (column col - 1 > done: it is in the ring)
             uint32_t cur = 0;
             long long col = top;
             uint32_t cnt = shN[0];
@@ -362,7 +262,7 @@ __global__ __launch_bounds__(kMosaicThreads) void mosaicker_commit_kernel(const 
                 const uint32_t *from = lists + cur * K;
                 uint32_t *to = lists + (cur ^ 1) * K;
                 for (uint32_t i = tid; i < cnt; i += nthr) {
-                    const uint32_t nk = back(from[i], col);
+                    const uint32_t nk = mosaic_back(cols, mosaic_pos(cols, from[i], col), col).key;
                     if (atomicExch(&flag[slot(nk)], 1u) == 0u)
                         to[atomicAdd(&shN[cur ^ 1], 1u)] = nk;
                 }
@@ -388,18 +288,7 @@ __global__ __launch_bounds__(kMosaicThreads) void mosaicker_commit_kernel(const 
     // no other barrier between the two
     __syncthreads();
     if (tid == 0) {
-        uint32_t key = tip;
-        for (long long col = c; col > done; --col) {
-            uint32_t word = kGap;
-            if (key != kGap) {
-                const uint32_t g = key >> 1;
-                const bool start = !(key & 1) && ((dir[((uint64_t)col & mask) * G + g] >> 1) >= 2 || col == 0);
-                word = g | (start ? kMosaicStart : 0u);
-            }
-            const uint32_t next = col - 1 > done ? back(key, col) : kGap;
-            path[(uint64_t)col & mask] = word;
-            key = next;
-        }
+        mosaic_walk(cols, mosaic_pos(cols, tip, c), c, done);
         a.lanes[l].done = c;
         a.lanes[l].count = (unsigned long long)(c - done);
         shC = c;
@@ -407,22 +296,15 @@ __global__ __launch_bounds__(kMosaicThreads) void mosaicker_commit_kernel(const 
     __syncthreads();
     c = shC;
     for (long long f = done + 1 + tid; f <= c; f += nthr) {
-        const uint32_t p = path[(uint64_t)f & mask];
-        uint32_t src = kGap, frame = kNone;
-        double cost = a.gapCost;
-        if (p != kGap) {
-            const uint32_t g = min(p & ~kMosaicStart, G - 1);
-            src = mosaic_segment(a.srcOff, a.nSrc, g);
-            frame = (uint32_t)(g - a.srcOff[src]);
-            cost = mosaic_cost(a.srcRaw + (size_t)g * dim, 1, kept + ((uint64_t)f & mask) * dim, dim, a.squared);
-        }
+        const uint32_t p = cols.word(f);
+        const MosaicFrame o = mosaic_frame(p, a.srcRaw, a.srcOff, a.nSrc, a.k, kept + ((uint64_t)f & cols.mask) * dim);
         const uint64_t k = s.logAt + (uint64_t)(f - done - 1);
         a.logLane[k] = l;
         a.logColumn[k] = (uint32_t)f;
-        a.logSrc[k] = src;
-        a.logFrame[k] = frame;
+        a.logSrc[k] = o.src;
+        a.logFrame[k] = o.frame;
         a.logStart[k] = (p & kMosaicStart) ? 1u : 0u;        // GAP has the bit as well
-        a.logCost[k] = cost;
+        a.logCost[k] = o.cost;
     }
 }
 
@@ -463,9 +345,10 @@ __global__ __launch_bounds__(256) void mosaicker_best_kernel(const MosLane *lane
 void mosaicker_free(ssym_ctx *ctx, ssym_mosaicker *mk)
 {
     for (void *p : {(void *)mk->srcT, (void *)mk->posc, (void *)mk->slab, (void *)mk->keys, (void *)mk->lanes, (void *)mk->dSteps,
-                    (void *)mk->dir, (void *)mk->arg, (void *)mk->frames, (void *)mk->logCost, (void *)mk->logWords})
+                    (void *)mk->dir, (void *)mk->arg, (void *)mk->frames})
         if (p)
             dev_free(ctx, p);
+    mk->log.free(ctx);
     delete mk;
 }
 
@@ -486,14 +369,6 @@ LaneFeed feed_of(ssym_ctx *ctx, const ssym_mosaicker *mk)
 {
     return LaneFeed{kNoun, "out_n_frames", mk->nLanes, mk->dim, mk->consumed, &mk->ended, true,
                     [ctx, mk](const char *fn) { return check_dict(ctx, mk, fn); }};
-}
-
-uint64_t pow2_at_least(uint64_t x)
-{
-    uint64_t p = 1;
-    while (p < x)
-        p <<= 1;
-    return p;
 }
 
 // bytes of one ring column of one lane: the direction bytes, arg and the target frame
@@ -537,32 +412,6 @@ int32_t ring_store(ssym_ctx *ctx, ssym_mosaicker *mk, uint64_t cap)
     mk->arg = arg;
     mk->frames = frames;
     mk->cap = cap;
-    return SSYM_OK;
-}
-
-// room for `need` frames in the log; what it held is dropped (a call's log starts empty)
-int32_t log_room(ssym_ctx *ctx, ssym_mosaicker *mk, uint64_t need)
-{
-    if (need <= mk->logCap)
-        return SSYM_OK;
-    const uint64_t cap = pow2_at_least(std::max<uint64_t>(need, 256));
-    double *cost = nullptr;
-    uint32_t *words = nullptr;
-    int32_t rc = alloc_n(ctx, &cost, (size_t)cap);
-    if (rc == SSYM_OK)
-        rc = alloc_n(ctx, &words, 5 * (size_t)cap);
-    if (rc != SSYM_OK) {
-        if (cost)
-            dev_free(ctx, cost);
-        return rc;
-    }
-    SSYM_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    for (void *p : {(void *)mk->logCost, (void *)mk->logWords})
-        if (p)
-            dev_free(ctx, p);
-    mk->logCost = cost;
-    mk->logWords = words;
-    mk->logCap = cap;
     return SSYM_OK;
 }
 
@@ -633,8 +482,6 @@ int32_t mosaicker_create(ssym_ctx *ctx, const ssym_dict *dict, uint32_t n_lanes,
     mk->stored.assign(n_lanes, 0);
     mk->ended.assign(n_lanes, 0);
     mk->dead.assign(n_lanes, 0);
-    mk->logOff.assign((size_t)n_lanes + 1, 0);
-    mk->logCount.assign(n_lanes, 0);
     // the initial ring: the largest power of two <= 1024 columns with lanes x cap x (G + 4) <= 64 MiB, 16 at least, within
     // the budget
     uint64_t cap = kMosaickerRingMax;
@@ -699,20 +546,11 @@ int32_t mosaicker_run(ssym_ctx *ctx, ssym_mosaicker *mk, const char *fn, const s
     while ((uint64_t)nL * (capMax * 3) * column_bytes(mk->G, dim) <= mk->budget - mk->fixedBytes)
         capMax *= 2;
     capMax = std::max(capMax, mk->cap);
-    // the log: a lane emits no more frames than it has beyond done
-    uint64_t room = 0, total = 0;
-    for (uint32_t l = 0; l < nL; ++l) {
-        mk->logOff[l] = room;
-        mk->logCount[l] = 0;
-        if (m[l] || l == flushLane)
-            room += mk->consumed[l] + m[l] - (uint64_t)(mk->done[l] + 1);
-        total += m[l];
-    }
-    mk->logOff[nL] = room;
-    tm.n_pairs = (uint64_t)mk->G * total;                     // cells
-    int32_t rc = log_room(ctx, mk, room);
+    int32_t rc = mk->log.begin(ctx, mk->consumed, mk->done, m, flushLane);
     if (rc != SSYM_OK)
         return rc;
+    for (uint32_t l = 0; l < nL; ++l)
+        tm.n_pairs += (uint64_t)mk->G * m[l];                 // cells
     std::vector<uint64_t> at(nL, 0);
     std::vector<MosStep> steps(nL);
     std::vector<MosLane> state(nL);
@@ -747,7 +585,7 @@ int32_t mosaicker_run(ssym_ctx *ctx, ssym_mosaicker *mk, const char *fn, const s
             const uint64_t ml = std::min(slice, m[l] - at[l]);
             MosStep &s = steps[l];
             s.rows = ml ? rows[l] + at[l] * dim : nullptr;
-            s.logAt = mk->logOff[l] + mk->logCount[l];
+            s.logAt = mk->log.off[l] + mk->log.count[l];
             s.m = (uint32_t)ml;
             s.flush = flush && l == flushLane;
             if (ml && !mk->dead[l])
@@ -762,49 +600,29 @@ int32_t mosaicker_run(ssym_ctx *ctx, ssym_mosaicker *mk, const char *fn, const s
             }
             SSYM_HIP_CHECK(ctx, hipMemcpyAsync(mk->dSteps, steps.data(), sizeof(MosStep) * nL, hipMemcpyHostToDevice, st));
             SSYM_HIP_CHECK(ctx, hipEventRecord(ev[0], st));
-            if (left) {
-                MosForwardArgs f{};
-                f.steps = mk->dSteps;
-                f.lanes = mk->lanes;
-                f.G = mk->G;
-                f.dim = dim;
-                f.squared = ctx->squared;
-                f.penalty = mk->penalty;
-                f.gapCost = mk->gapCost;
-                f.posc = mk->posc;
-                f.srcT = mk->srcT;
-                f.slab = mk->slab;
-                f.cap = mk->cap;
-                f.dir = mk->dir;
-                f.arg = mk->arg;
-                f.frames = mk->frames;
-                mosaicker_forward_kernel<<<nL, kMosaicThreads, 0, st>>>(f);
-                SSYM_HIP_CHECK(ctx, hipGetLastError());
-            }
-            SSYM_HIP_CHECK(ctx, hipEventRecord(ev[1], st));
             MosCommitArgs k{};
             k.steps = mk->dSteps;
             k.lanes = mk->lanes;
-            k.G = mk->G;
-            k.dim = dim;
-            k.squared = ctx->squared;
-            k.penalty = mk->penalty;
-            k.gapCost = mk->gapCost;
+            k.k = MosaicCore{mk->G, dim, ctx->squared, mk->penalty, mk->gapCost, mk->posc, mk->srcT, mk->slab};
             k.srcRaw = src.raw;
             k.srcOff = src.off;
             k.nSrc = src.n;
-            k.slab = mk->slab;
             k.keys = mk->keys;
             k.cap = mk->cap;
             k.dir = mk->dir;
             k.arg = mk->arg;
             k.frames = mk->frames;
-            k.logLane = mk->logWords;
-            k.logColumn = mk->logWords + mk->logCap;
-            k.logSrc = mk->logWords + 2 * mk->logCap;
-            k.logFrame = mk->logWords + 3 * mk->logCap;
-            k.logStart = mk->logWords + 4 * mk->logCap;
-            k.logCost = mk->logCost;
+            k.logLane = mk->log.word(0);
+            k.logColumn = mk->log.word(1);
+            k.logSrc = mk->log.word(2);
+            k.logFrame = mk->log.word(3);
+            k.logStart = mk->log.word(4);
+            k.logCost = mk->log.cost;
+            if (left) {
+                mosaicker_forward_kernel<<<nL, kMosaicThreads, 0, st>>>(k);          // (its part of the arguments)
+                SSYM_HIP_CHECK(ctx, hipGetLastError());
+            }
+            SSYM_HIP_CHECK(ctx, hipEventRecord(ev[1], st));
             mosaicker_commit_kernel<<<nL, kMosaicThreads, 0, st>>>(k);
             SSYM_HIP_CHECK(ctx, hipGetLastError());
             SSYM_HIP_CHECK(ctx, hipEventRecord(ev[2], st));
@@ -823,7 +641,7 @@ int32_t mosaicker_run(ssym_ctx *ctx, ssym_mosaicker *mk, const char *fn, const s
             mk->done[l] = state[l].done;
             mk->stored[l] = state[l].stored;
             mk->dead[l] = state[l].n > 0 && !(state[l].best < __builtin_inf());
-            mk->logCount[l] += state[l].count;
+            mk->log.count[l] += state[l].count;
             at[l] += steps[l].m;
         }
         tm.main_ms += ev_ms(ev[0], ev[1]);
@@ -835,10 +653,7 @@ int32_t mosaicker_run(ssym_ctx *ctx, ssym_mosaicker *mk, const char *fn, const s
     }
     if (flush && result == SSYM_OK)
         mk->ended[flushLane] = 1;
-    uint64_t frames = 0;
-    for (uint32_t l = 0; l < nL; ++l)
-        frames += mk->logCount[l];
-    *out_n_frames = frames;
+    *out_n_frames = mk->log.total();
     ctx->timings = tm;
     return result;
 }
@@ -909,26 +724,8 @@ int32_t mosaicker_frames(ssym_ctx *ctx, const ssym_mosaicker *mk, uint32_t *out_
     if (rc != SSYM_OK)
         return rc;
     SSYM_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-    const bool outDev = (flags & SSYM_OUT_DEVICE) != 0;
-    const size_t cap = mk->logCap;
     uint32_t *const outs[5] = {out_lane, out_column, out_src, out_frame, out_start};
-    size_t to = 0;
-    bool any = false;
-    for (uint32_t l = 0; l < mk->nLanes; ++l) {          // the lanes' stretches of the log, one behind the other
-        const size_t from = mk->logOff[l], n = mk->logCount[l];
-        if (n == 0)
-            continue;
-        any = true;
-        rc = copy_out(ctx, out_cost ? out_cost + to : nullptr, (const double *)mk->logCost + from, n, outDev);
-        for (int w = 0; w < 5 && rc == SSYM_OK; ++w)
-            rc = copy_out(ctx, outs[w] ? outs[w] + to : nullptr, (const uint32_t *)mk->logWords + w * cap + from, n, outDev);
-        if (rc != SSYM_OK)
-            return rc;
-        to += n;
-    }
-    if (any)
-        SSYM_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    return SSYM_OK;
+    return mk->log.copy(ctx, out_cost, outs, (flags & SSYM_OUT_DEVICE) != 0);
 }
 
 int32_t mosaicker_best(ssym_ctx *ctx, const ssym_mosaicker *mk, double *out_total, uint32_t *out_covered, uint32_t *out_committed,
@@ -941,32 +738,15 @@ int32_t mosaicker_best(ssym_ctx *ctx, const ssym_mosaicker *mk, double *out_tota
         return SSYM_OK;
     SSYM_HIP_CHECK(ctx, hipSetDevice(ctx->device));
     const uint32_t nL = mk->nLanes;
-    const unsigned grid = (nL + 255) / 256;
-    if (flags & SSYM_OUT_DEVICE) {
-        mosaicker_best_kernel<<<grid, 256, 0, ctx->stream>>>(mk->lanes, nL, out_total, out_covered, out_committed);
-        SSYM_HIP_CHECK(ctx, hipGetLastError());
-        SSYM_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-        return SSYM_OK;
-    }
+    // the caller's device arrays in place, or one f64 and one u32 block copied back
+    StagedOut out(flags, {{out_total, nL}}, {{out_covered, nL}, {out_committed, nL}});
     Blocks bl(ctx);
-    double *dTotal = nullptr;
-    uint32_t *dWords = nullptr;
-    rc = bl.get(&dTotal, (size_t)nL);
-    if (rc == SSYM_OK)
-        rc = bl.get(&dWords, 2 * (size_t)nL);
+    rc = out.alloc(bl);
     if (rc != SSYM_OK)
         return rc;
-    mosaicker_best_kernel<<<grid, 256, 0, ctx->stream>>>(mk->lanes, nL, dTotal, dWords, dWords + nL);
+    mosaicker_best_kernel<<<(nL + 255) / 256, 256, 0, ctx->stream>>>(mk->lanes, nL, out.f64[0], out.u32[0], out.u32[1]);
     SSYM_HIP_CHECK(ctx, hipGetLastError());
-    rc = copy_out(ctx, out_total, (const double *)dTotal, nL, false);
-    if (rc == SSYM_OK)
-        rc = copy_out(ctx, out_covered, (const uint32_t *)dWords, nL, false);
-    if (rc == SSYM_OK)
-        rc = copy_out(ctx, out_committed, (const uint32_t *)dWords + nL, nL, false);
-    if (rc != SSYM_OK)
-        return rc;
-    SSYM_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    return SSYM_OK;
+    return out.finish(ctx);
 }
 
 }  // namespace

@@ -2,7 +2,9 @@
 // (dtw_coverer.hip) and the mosaicker (dtw_mosaicker.hip) consume growing sounds lane by lane, in pushes of host frames or
 // by following a stream's resident frames, and flush or reset one lane.  The checks of those calls, their order, their
 // messages and the upload of a push are here once; what an object does with the frames (spotter_run, coverer_run,
-// mosaicker_run) is its own.
+// mosaicker_run) is its own.  So is the log of a call's results that the coverer and the mosaicker keep (LaneLog: its room,
+// its layout at the start of a call and the copy out; the spotter's event log keeps its contents while it grows and is
+// sorted, and stays with the spotter), and pow2_at_least.
 //
 // The order of the refusals is part of the interface ("the earlier of two faults is the one reported"):
 //   push   : frame_offsets / count NULL | the object's own check | lane by lane: offsets decrease, the lane has ended,
@@ -38,6 +40,106 @@ int32_t copy_out(ssym_ctx *ctx, T *out, const T *dev, size_t n, bool outDev)
                                            ctx->stream));
     return SSYM_OK;
 }
+
+inline uint64_t pow2_at_least(uint64_t x)
+{
+    uint64_t p = 1;
+    while (p < x)
+        p <<= 1;
+    return p;
+}
+
+// The log of a call (the coverer's pieces, the mosaicker's frames): what the last push / follow / flush emitted, one f64
+// array and nWords u32 arrays of `cap` entries each, lane l's entries from off[l] on, count[l] of them.  The commit kernels
+// fill it; the call that reads it copies the lanes' stretches out one behind the other.
+struct LaneLog {
+    uint32_t nWords;
+    double *cost = nullptr;                              // [cap]
+    uint32_t *words = nullptr;                           // [nWords][cap]
+    uint64_t cap = 0;
+    std::vector<uint64_t> off, count;                    // [nLanes + 1], [nLanes]
+
+    explicit LaneLog(uint32_t n) : nWords(n) {}
+    uint32_t *word(uint32_t w) const { return words + w * cap; }
+
+    // room for `need` entries; what the log held is dropped (a call's log starts empty)
+    int32_t room(ssym_ctx *ctx, uint64_t need)
+    {
+        if (need <= cap)
+            return SSYM_OK;
+        const uint64_t grown = pow2_at_least(std::max<uint64_t>(need, 256));
+        double *c = nullptr;
+        uint32_t *w = nullptr;
+        int32_t rc = alloc_n(ctx, &c, (size_t)grown);
+        if (rc == SSYM_OK)
+            rc = alloc_n(ctx, &w, nWords * (size_t)grown);
+        if (rc != SSYM_OK) {
+            if (c)
+                dev_free(ctx, c);
+            return rc;
+        }
+        SSYM_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+        free(ctx);
+        cost = c;
+        words = w;
+        cap = grown;
+        return SSYM_OK;
+    }
+
+    // a call begins: lane l with new frames (m[l]) or the flush has room for an entry per frame beyond done[l] -- an entry
+    // has a frame at least, so a lane emits no more
+    int32_t begin(ssym_ctx *ctx, const std::vector<uint64_t> &consumed, const std::vector<int64_t> &done,
+                  const std::vector<uint64_t> &m, uint32_t flushLane)
+    {
+        const uint32_t nL = (uint32_t)m.size();
+        off.assign((size_t)nL + 1, 0);
+        count.assign(nL, 0);
+        uint64_t need = 0;
+        for (uint32_t l = 0; l < nL; ++l) {
+            off[l] = need;
+            if (m[l] || l == flushLane)
+                need += consumed[l] + m[l] - (uint64_t)(done[l] + 1);
+        }
+        off[nL] = need;
+        return room(ctx, need);
+    }
+
+    uint64_t total() const
+    {
+        uint64_t n = 0;
+        for (const uint64_t c : count)
+            n += c;
+        return n;
+    }
+
+    // the lanes' stretches, one behind the other, into the outputs that are not NULL (outs: nWords of them); synchronises
+    int32_t copy(ssym_ctx *ctx, double *out_cost, uint32_t *const *outs, bool outDev) const
+    {
+        size_t to = 0;
+        for (size_t l = 0; l < count.size(); ++l) {
+            const size_t from = off[l], n = count[l];
+            int32_t rc = copy_out(ctx, out_cost ? out_cost + to : nullptr, (const double *)cost + from, n, outDev);
+            for (uint32_t w = 0; w < nWords && rc == SSYM_OK; ++w)
+                rc = copy_out(ctx, outs[w] ? outs[w] + to : nullptr, (const uint32_t *)word(w) + from, n, outDev);
+            if (rc != SSYM_OK)
+                return rc;
+            to += n;
+        }
+        if (to)
+            SSYM_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+        return SSYM_OK;
+    }
+
+    void free(ssym_ctx *ctx)
+    {
+        for (void *p : {(void *)cost, (void *)words})
+            if (p)
+                dev_free(ctx, p);
+        cost = nullptr;
+        words = nullptr;
+        cap = 0;
+    }
+};
 
 // what every call refuses before anything else; noun: "spotter", "coverer", "mosaicker"
 template <class Handle>

@@ -560,180 +560,128 @@ class Spotter(_Lanes):
             pass
 
 
-class Coverer(_Lanes):
-    """`n_lanes` growing targets tiled by the segments of one resident dictionary (ssym_coverer; definition in
-    include/soundsym_amd.h and DESIGN.md section 2 "Live cover"): every piece is reported by the push after which no
-    longer recording could change it, the pieces from reset to flush are ssym_dtw_cover's for the whole, and `best` gives
-    ssym_dtw_cover's total for everything consumed so far.  The coverer reads the dictionary's resident features for as
-    long as it lives: it keeps `d` alive and must be closed before it."""
+class _LiveTiling(_Lanes):
+    """What Coverer and Mosaicker share: `n_lanes` growing targets tiled from one resident dictionary, fed by push or follow,
+    ended lane by lane with flush.  A subclass names its noun (the ssym_<noun>_* calls), the attribute that holds the count
+    of the last call's results, what the count counts, and what its capacity is.  The object reads the dictionary's
+    resident features for as long as it lives: it keeps `d` alive and must be closed before it."""
+
+    _noun = _count = None
+    _count_on_refusal = False        # True: a refused call's count is recorded as well
 
     def __init__(self, engine: "Engine", ptr: int, d: _Handle, n_lanes: int, piece_penalty: float, gap_cost=None):
         self.engine, self.ptr, self.d, self.n_lanes, self.dim = engine, ptr, d, n_lanes, d.dim
         self.piece_penalty, self.gap_cost = piece_penalty, gap_cost
-        self.n_pieces = 0
+        setattr(self, self._count, 0)
+
+    def _call(self, name: str, *args) -> int:
+        return getattr(nat.lib(), f"ssym_{self._noun}_{name}")(self.engine.ctx, self.ptr, *args)
+
+    def _ran(self, name: str, *args) -> int:
+        """A call that ends in the count output: the count it leaves is that of the last call's results."""
+        n = ctypes.c_uint64()
+        rc = self._call(name, *args, ctypes.byref(n))
+        if self._count_on_refusal:
+            setattr(self, self._count, int(n.value))
+        nat.check(rc, self.engine.ctx)
+        setattr(self, self._count, int(n.value))
+        return int(n.value)
 
     def push(self, feats, frame_offsets=None) -> int:
-        """ssym_coverer_push: lane l consumes the frames feats[frame_offsets[l]:frame_offsets[l+1]] ([frames][dim]; a
-        one-lane coverer takes the bare block).  Returns the number of pieces the push committed (`pieces` reads them)."""
-        x, off = _push_args("coverer", self.n_lanes, self.dim, feats, frame_offsets)
-        n = ctypes.c_uint64()
-        nat.check(nat.lib().ssym_coverer_push(self.engine.ctx, self.ptr, x.ctypes.data if x.size else None, off.ctypes.data,
-                                              0, ctypes.byref(n)), self.engine.ctx)
-        self.n_pieces = int(n.value)
-        return self.n_pieces
+        """ssym_<noun>_push: lane l consumes the frames feats[frame_offsets[l]:frame_offsets[l+1]] ([frames][dim]; an object
+        of one lane takes the bare block).  Returns the number of pieces (coverer) or frames (mosaicker) the push committed;
+        `pieces` / `frames` reads them."""
+        x, off = _push_args(self._noun, self.n_lanes, self.dim, feats, frame_offsets)
+        return self._ran("push", x.ctypes.data if x.size else None, off.ctypes.data, 0)
 
     def follow(self, stream: "Stream") -> int:
-        """ssym_coverer_follow: every lane consumes, device to device, the frames the stream's lane holds beyond those
+        """ssym_<noun>_follow: every lane consumes, device to device, the frames the stream's lane holds beyond those
         consumed (a lane that has ended is skipped).  Returns as push."""
         if stream.n_lanes != self.n_lanes or stream.ncoeffs != self.dim:
-            raise ValueError("follow: the stream's lanes and ncoeffs must be the coverer's lanes and dim")
-        n = ctypes.c_uint64()
-        nat.check(nat.lib().ssym_coverer_follow(self.engine.ctx, self.ptr, stream.ptr, 0, ctypes.byref(n)), self.engine.ctx)
-        self.n_pieces = int(n.value)
-        return self.n_pieces
+            raise ValueError(f"follow: the stream's lanes and ncoeffs must be the {self._noun}'s lanes and dim")
+        return self._ran("follow", stream.ptr, 0)
+
+    def flush(self, lane: int = 0) -> int:
+        """ssym_<noun>_flush: "the lane has ended" -- the rest of its cover or mosaic is emitted, and the lane consumes
+        nothing more until `reset`.  Returns the number of pieces or frames."""
+        return self._ran("flush", self._lane(lane))
+
+    def _results(self, name: str, dtypes, on_device: bool):
+        """The arrays of the last call's results through ssym_<noun>_<name>, in the order of its outputs."""
+        n = getattr(self, self._count)
+        device = self.engine.device if on_device else None
+        outs = [_output(device, (n,), t) for t in dtypes]
+        if n:
+            nat.check(self._call(name, *(p for _, p in outs), 0 if device is None else nat.OUT_DEVICE), self.engine.ctx)
+        return [a for a, _ in outs]
+
+    def best(self, on_device: bool = False):
+        """(total f64, covered uint32, committed uint32), each [n_lanes]: the offline call's total (ssym_dtw_cover's or
+        ssym_dtw_mosaic's) for what the lane has consumed so far (+inf without a cover or mosaic), the frames of the longest
+        prefix that has one, and the frames whose pieces or frames have been emitted."""
+        device = self.engine.device if on_device else None
+        (total, pt), (covered, pc), (committed, pm) = (_output(device, (self.n_lanes,), t)
+                                                      for t in (np.float64, np.uint32, np.uint32))
+        nat.check(self._call("best", pt, pc, pm, 0 if device is None else nat.OUT_DEVICE), self.engine.ctx)
+        return total, covered, committed
+
+    def counts(self):
+        """(frames consumed per lane [n_lanes] u64, capacity: of the coverer's back-pointer ring in frames, of the
+        mosaicker's ring in columns)."""
+        out = np.zeros(self.n_lanes, dtype=np.uint64)
+        cap = ctypes.c_uint64()
+        nat.check(getattr(nat.lib(), f"ssym_{self._noun}_counts")(self.ptr, out.ctypes.data, ctypes.byref(cap)), self.engine.ctx)
+        return out, int(cap.value)
+
+    def reset(self, lane: int = 0) -> None:
+        """One lane back to "nothing consumed"."""
+        nat.check(self._call("reset", self._lane(lane)), self.engine.ctx)
+
+    def close(self):
+        if self.ptr and self.engine.ctx:
+            self._call("destroy")
+        self.ptr = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Coverer(_LiveTiling):
+    """`n_lanes` growing targets tiled by the segments of one resident dictionary (ssym_coverer; definition in
+    include/soundsym_amd.h and DESIGN.md section 2 "Live cover"): every piece is reported by the push after which no
+    longer recording could change it, the pieces from reset to flush are ssym_dtw_cover's for the whole, and `best` gives
+    ssym_dtw_cover's total for everything consumed so far.  The coverer reads the dictionary's resident features for as
+    long as it lives: it keeps `d` alive and must be closed before it.  After a refused call n_pieces is what it was."""
+
+    _noun, _count = "coverer", "n_pieces"
 
     def pieces(self, on_device: bool = False):
         """The pieces of the last push / follow / flush, ordered by (lane, start): (lane uint32 [n], src uint32 [n], start
         uint32 [n], end uint32 [n], cost f64 [n]); start / end count the lane's frames since its reset, end inclusive.
         On a coverer with a gap_cost a frame left uncovered is the piece (lane, COVER_GAP, e, e, gap_cost).
         on_device: SSYM_OUT_DEVICE, the five arrays as torch tensors in device memory."""
-        n = self.n_pieces
-        device = self.engine.device if on_device else None
-        (lane, pl), (src, ps), (start, pa), (end, pe), (cost, pc) = (
-            _output(device, (n,), t) for t in (np.uint32, np.uint32, np.uint32, np.uint32, np.float64))
-        if n:
-            nat.check(nat.lib().ssym_coverer_pieces(self.engine.ctx, self.ptr, pl, ps, pa, pe, pc,
-                                                    0 if device is None else nat.OUT_DEVICE), self.engine.ctx)
-        return lane, src, start, end, cost
-
-    def flush(self, lane: int = 0) -> int:
-        """ssym_coverer_flush: "the lane has ended" -- the rest of its cover is emitted, and the lane consumes nothing more
-        until `reset`.  Returns the number of pieces."""
-        n = ctypes.c_uint64()
-        nat.check(nat.lib().ssym_coverer_flush(self.engine.ctx, self.ptr, self._lane(lane), ctypes.byref(n)), self.engine.ctx)
-        self.n_pieces = int(n.value)
-        return self.n_pieces
-
-    def best(self, on_device: bool = False):
-        """(total f64, covered uint32, committed uint32), each [n_lanes]: ssym_dtw_cover's total for what the lane has
-        consumed so far (+inf without a cover), the frames of the longest prefix that has a cover, and the frames whose
-        pieces have been emitted."""
-        device = self.engine.device if on_device else None
-        (total, pt), (covered, pc), (committed, pm) = (_output(device, (self.n_lanes,), t)
-                                                      for t in (np.float64, np.uint32, np.uint32))
-        nat.check(nat.lib().ssym_coverer_best(self.engine.ctx, self.ptr, pt, pc, pm, 0 if device is None else nat.OUT_DEVICE),
-                  self.engine.ctx)
-        return total, covered, committed
-
-    def counts(self):
-        """(frames consumed per lane [n_lanes] u64, capacity of the back-pointer ring in frames)."""
-        out = np.zeros(self.n_lanes, dtype=np.uint64)
-        cap = ctypes.c_uint64()
-        nat.check(nat.lib().ssym_coverer_counts(self.ptr, out.ctypes.data, ctypes.byref(cap)), self.engine.ctx)
-        return out, int(cap.value)
-
-    def reset(self, lane: int = 0) -> None:
-        """One lane back to "nothing consumed"."""
-        nat.check(nat.lib().ssym_coverer_reset(self.engine.ctx, self.ptr, self._lane(lane)), self.engine.ctx)
-
-    def close(self):
-        if self.ptr and self.engine.ctx:
-            nat.lib().ssym_coverer_destroy(self.engine.ctx, self.ptr)
-        self.ptr = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        return tuple(self._results("pieces", (np.uint32, np.uint32, np.uint32, np.uint32, np.float64), on_device))
 
 
-class Mosaicker(_Lanes):
+class Mosaicker(_LiveTiling):
     """`n_lanes` growing targets tiled by free spans of the uncut recordings of one resident dictionary (ssym_mosaicker;
     definition in include/soundsym_amd.h and DESIGN.md section 2 "Live mosaic"): every target frame is reported by the
     push after which no longer recording could change it, the frames from reset to flush are ssym_dtw_mosaic's for the
     whole, and `best` gives ssym_dtw_mosaic's total for everything consumed so far.  The mosaicker reads the dictionary's
-    resident features for as long as it lives: it keeps `d` alive and must be closed before it."""
+    resident features for as long as it lives: it keeps `d` alive and must be closed before it.  A call refused after some
+    slices has those slices' frames in its log, so n_frames is recorded before the refusal is raised."""
 
-    def __init__(self, engine: "Engine", ptr: int, d: _Handle, n_lanes: int, piece_penalty: float, gap_cost=None):
-        self.engine, self.ptr, self.d, self.n_lanes, self.dim = engine, ptr, d, n_lanes, d.dim
-        self.piece_penalty, self.gap_cost = piece_penalty, gap_cost
-        self.n_frames = 0
-
-    def _ran(self, rc, n) -> int:
-        self.n_frames = int(n.value)          # (a call refused after some slices has those slices' frames in its log)
-        nat.check(rc, self.engine.ctx)
-        return self.n_frames
-
-    def push(self, feats, frame_offsets=None) -> int:
-        """ssym_mosaicker_push: lane l consumes the frames feats[frame_offsets[l]:frame_offsets[l+1]] ([frames][dim]; a
-        one-lane mosaicker takes the bare block).  Returns the number of frames the push committed (`frames` reads
-        them)."""
-        x, off = _push_args("mosaicker", self.n_lanes, self.dim, feats, frame_offsets)
-        n = ctypes.c_uint64()
-        return self._ran(nat.lib().ssym_mosaicker_push(self.engine.ctx, self.ptr, x.ctypes.data if x.size else None,
-                                                       off.ctypes.data, 0, ctypes.byref(n)), n)
-
-    def follow(self, stream: "Stream") -> int:
-        """ssym_mosaicker_follow: every lane consumes, device to device, the frames the stream's lane holds beyond those
-        consumed (a lane that has ended is skipped).  Returns as push."""
-        if stream.n_lanes != self.n_lanes or stream.ncoeffs != self.dim:
-            raise ValueError("follow: the stream's lanes and ncoeffs must be the mosaicker's lanes and dim")
-        n = ctypes.c_uint64()
-        return self._ran(nat.lib().ssym_mosaicker_follow(self.engine.ctx, self.ptr, stream.ptr, 0, ctypes.byref(n)), n)
+    _noun, _count, _count_on_refusal = "mosaicker", "n_frames", True
 
     def frames(self, on_device: bool = False):
         """The frames of the last push / follow / flush, ordered by (lane, column): (lane uint32 [n], column uint32 [n],
         src uint32 [n], frame uint32 [n], cost f64 [n], start uint32 [n]).  column counts the lane's frames since its
         reset; (src, frame, cost) are dtw_mosaic's per-frame outputs (a gap frame: COVER_GAP, NO_MATCH, gap_cost); start
         is 1 where a piece or a gap frame starts.  on_device: SSYM_OUT_DEVICE, the six arrays as torch tensors."""
-        n = self.n_frames
-        device = self.engine.device if on_device else None
-        (lane, pl), (col, pc), (src, ps), (frame, pf), (cost, pk), (start, pa) = (
-            _output(device, (n,), t) for t in (np.uint32, np.uint32, np.uint32, np.uint32, np.float64, np.uint32))
-        if n:
-            nat.check(nat.lib().ssym_mosaicker_frames(self.engine.ctx, self.ptr, pl, pc, ps, pf, pk, pa,
-                                                      0 if device is None else nat.OUT_DEVICE), self.engine.ctx)
-        return lane, col, src, frame, cost, start
-
-    def flush(self, lane: int = 0) -> int:
-        """ssym_mosaicker_flush: "the lane has ended" -- the rest of its mosaic is emitted, and the lane consumes nothing
-        more until `reset`.  Returns the number of frames."""
-        n = ctypes.c_uint64()
-        return self._ran(nat.lib().ssym_mosaicker_flush(self.engine.ctx, self.ptr, self._lane(lane), ctypes.byref(n)), n)
-
-    def best(self, on_device: bool = False):
-        """(total f64, covered uint32, committed uint32), each [n_lanes]: ssym_dtw_mosaic's total for what the lane has
-        consumed so far (+inf without a mosaic), the frames of the longest prefix that has a mosaic, and the frames
-        that have been emitted."""
-        device = self.engine.device if on_device else None
-        (total, pt), (covered, pc), (committed, pm) = (_output(device, (self.n_lanes,), t)
-                                                      for t in (np.float64, np.uint32, np.uint32))
-        nat.check(nat.lib().ssym_mosaicker_best(self.engine.ctx, self.ptr, pt, pc, pm, 0 if device is None else nat.OUT_DEVICE),
-                  self.engine.ctx)
-        return total, covered, committed
-
-    def counts(self):
-        """(frames consumed per lane [n_lanes] u64, capacity of the ring in columns)."""
-        out = np.zeros(self.n_lanes, dtype=np.uint64)
-        cap = ctypes.c_uint64()
-        nat.check(nat.lib().ssym_mosaicker_counts(self.ptr, out.ctypes.data, ctypes.byref(cap)), self.engine.ctx)
-        return out, int(cap.value)
-
-    def reset(self, lane: int = 0) -> None:
-        """One lane back to "nothing consumed"."""
-        nat.check(nat.lib().ssym_mosaicker_reset(self.engine.ctx, self.ptr, self._lane(lane)), self.engine.ctx)
-
-    def close(self):
-        if self.ptr and self.engine.ctx:
-            nat.lib().ssym_mosaicker_destroy(self.engine.ctx, self.ptr)
-        self.ptr = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        return tuple(self._results("frames", (np.uint32, np.uint32, np.uint32, np.uint32, np.float64, np.uint32), on_device))
 
 
 class Comm:
