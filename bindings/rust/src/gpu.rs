@@ -17,6 +17,7 @@ use std::os::raw::{c_char, c_void};
 #[repr(C)] pub struct SsymSpotter { _p: [u8; 0] }
 #[repr(C)] pub struct SsymCoverer { _p: [u8; 0] }
 #[repr(C)] pub struct SsymMosaicker { _p: [u8; 0] }
+#[repr(C)] pub struct SsymResynth { _p: [u8; 0] }
 
 pub const SSYM_ABI_VERSION: i32 = 3;
 
@@ -373,6 +374,20 @@ extern "C" {
                                out_committed: *mut u32, flags: u32) -> i32;
     pub fn ssym_mosaicker_counts(mk: *const SsymMosaicker, out_frames: *mut u64, out_capacity: *mut u64) -> i32;
     pub fn ssym_mosaicker_reset(ctx: *mut SsymCtx, mk: *mut SsymMosaicker, lane: u32) -> i32;
+    // live resynthesis (include/soundsym_amd.h "Live resynthesis"): committed mosaic frames to audio, push by push; the
+    // sample store must outlive the resynthesiser
+    pub fn ssym_resynth_create(ctx: *mut SsymCtx, store: *const SsymSamples, n_lanes: u32, search: u32,
+                               out: *mut *mut SsymResynth) -> i32;
+    pub fn ssym_resynth_destroy(ctx: *mut SsymCtx, rs: *mut SsymResynth) -> i32;
+    pub fn ssym_resynth_push(ctx: *mut SsymCtx, rs: *mut SsymResynth, lane: *const u32, column: *const u32, src: *const u32,
+                             frame: *const u32, start: *const u32, n_frames: u64, out_n_samples: *mut u64) -> i32;
+    pub fn ssym_resynth_take(ctx: *mut SsymCtx, rs: *mut SsymResynth, mk: *const SsymMosaicker, out_n_samples: *mut u64) -> i32;
+    pub fn ssym_resynth_samples(ctx: *mut SsymCtx, rs: *const SsymResynth, out_lane_offsets: *mut u64, out_samples: *mut f64,
+                                out_pcm32: *mut i32, flags: u32) -> i32;
+    pub fn ssym_resynth_flush(ctx: *mut SsymCtx, rs: *mut SsymResynth, lane: u32, total_samples: u64,
+                              out_n_samples: *mut u64) -> i32;
+    pub fn ssym_resynth_counts(rs: *const SsymResynth, out_frames: *mut u64, out_samples: *mut u64) -> i32;
+    pub fn ssym_resynth_reset(ctx: *mut SsymCtx, rs: *mut SsymResynth, lane: u32) -> i32;
 }
 
 /// `Err(message)` for any status but SSYM_OK; SSYM_E_EMPTY_DICT keeps the crate's behaviour (a panic, :369).

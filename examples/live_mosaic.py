@@ -2,7 +2,7 @@
 """examples/live_mosaic.py -- a recording tiled by free spans of uncut recordings while it is still arriving.
 
     python examples/live_mosaic.py -s TARGET.wav -d REC.wav|DIR [-o OUT.wav] [--block 4096] [--penalty 1.0] [--gap-cost X]
-                                   [--gap-fill silence|target] [--search 256]
+                                   [--gap-fill silence|target] [--search 256] [--live-audio]
 
 The dictionary is built as examples/mosaic.py builds it: one recording or a folder of recordings, each taken whole.  The
 target is fed --block samples at a time (Sound.push_samples, as a recording arrives), and SoundDictionary.mosaic_live follows
@@ -11,6 +11,9 @@ recording, its span, cost per frame -- by the block that closes it (the next sta
 end prints the rest.  What is printed is, piece for piece, what examples/mosaic.py prints for the whole recording.  -o writes
 the resynthesis of the finished mosaic (SoundDictionary.reconstruct_mosaic(mosaic=...)): nothing is computed twice.
 --gap-cost X lets frames stay uncovered at X each: a frame that is not finite then costs one gap frame and the mosaic goes on.
+--live-audio resynthesises while the target arrives (mosaic_live(audio=True), LiveMosaic.audio()): every block also prints
+the samples it released and the hops still held back (at most 4 without a search, at most 12 with one), and -o writes what
+was gathered push by push -- the same WAV as without the flag, sample for sample.
 """
 import argparse
 import os
@@ -18,7 +21,9 @@ import sys
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
-from soundsym_amd import Engine, Sound, SoundDictionary  # noqa: E402
+import numpy as np  # noqa: E402
+
+from soundsym_amd import HOP, Engine, Sound, SoundDictionary  # noqa: E402
 from soundsym_amd.io import write_wav32  # noqa: E402
 
 
@@ -32,6 +37,7 @@ def main(argv=None):
     ap.add_argument("--gap-cost", type=float, default=None, help="price per frame left uncovered (default: no gaps)")
     ap.add_argument("--gap-fill", choices=("silence", "target"), default="silence", help="what a gap sounds like")
     ap.add_argument("--search", type=int, default=256, help="WSOLA search width in samples (0: plain overlap-add)")
+    ap.add_argument("--live-audio", action="store_true", help="resynthesise while the target arrives (LiveMosaic.audio)")
     args = ap.parse_args(argv)
     if args.block < 1:
         ap.error("--block must be at least 1")
@@ -59,12 +65,28 @@ def main(argv=None):
     first = min(args.block, samples.size)
     target = Sound.from_samples(samples[:first], whole.sample_rate(), engine=engine)
     target.push_samples(samples[:0], engine)                          # resident: the stream the mosaic follows
-    live = dictionary.mosaic_live([target], args.penalty, args.gap_cost)
+    if args.live_audio:
+        live = dictionary.mosaic_live([target], args.penalty, args.gap_cost, audio=True, search=args.search, gap_fill=args.gap_fill)
+    else:
+        live = dictionary.mosaic_live([target], args.penalty, args.gap_cost)
+    heard = []                                                        # --live-audio: (samples, pcm) as they are released
+
+    def listen(at):
+        if not args.live_audio:
+            return
+        heard.append(live.audio(want_pcm32=True)[0])
+        released = sum(h[0].size for h in heard)
+        frames = int(live.pending()[2][0])
+        print(f"[{at:9d} samples] {heard[-1][0].size:7d} samples released, {max(frames - released // HOP, 0):2d} hops held")
+
     show(live.poll(), first)
+    listen(first)
     for at in range(first, samples.size, args.block):
         target.push_samples(samples[at:at + args.block], engine)
         show(live.poll(), min(at + args.block, samples.size))
+        listen(min(at + args.block, samples.size))
     show(live.flush(), samples.size)
+    listen(samples.size)
     consumed, covered, committed, total = live.pending()
     mosaic = live.mosaics()[0]
     live.close()
@@ -74,7 +96,12 @@ def main(argv=None):
     else:
         print(f"the mosaic ends after {int(covered[0])} of {int(consumed[0])} frames (a frame that is not finite and no --gap-cost)")
     out = None
-    if args.o and mosaic and covered[0] == consumed[0]:
+    if args.live_audio and mosaic and covered[0] == consumed[0]:
+        out, pcm = (np.concatenate([h[k] for h in heard]) for k in (0, 1))      # what was heard, push by push
+        if args.o:
+            write_wav32(args.o, sample_rate=target.sample_rate(), pcm=pcm)
+            print(f"{out.size} samples -> {args.o}")
+    elif args.o and mosaic and covered[0] == consumed[0]:
         _, out, pcm = dictionary.reconstruct_mosaic(target, args.penalty, args.gap_cost, args.gap_fill, args.search,
                                                     want_pcm32=True, mosaic=mosaic)
         write_wav32(args.o, sample_rate=target.sample_rate(), pcm=pcm)

@@ -1053,6 +1053,8 @@ class Mosaicker {
         return cap;
     }
     void reset(uint32_t lane) { ctx_->check(ssym_mosaicker_reset(ctx_->get(), mk_, lane)); }
+    // the library's handle: what Resynth::take reads the last frame log from
+    const ssym_mosaicker *handle() const { return mk_; }
 
   private:
     std::vector<Frame> frames(uint64_t n) const
@@ -1071,6 +1073,114 @@ class Mosaicker {
     uint32_t lanes_ = 0;
     ssym_dict *dict_ = nullptr;
     ssym_mosaicker *mk_ = nullptr;
+};
+
+// n_lanes lanes of live resynthesis from a dictionary's samples (ssym_resynth; soundsym_amd.h "Live resynthesis"): a lane
+// takes committed mosaic frames -- a Mosaicker's last frame log device to device (take) or host rows (push) -- and every call
+// returns the samples it releases, those whose bits no later frame can change; from reset to flush a lane's samples are the
+// offline piece-by-piece resynthesis of the finished mosaic, bit for bit.  The resynthesiser makes the sounds' samples
+// resident in a store of its own and keeps it for as long as it lives.
+class Resynth {
+  public:
+    struct Frame {
+        uint32_t lane;
+        uint32_t column;            // the lane's frame, counted since its reset
+        uint32_t src;               // the dictionary sound, or SSYM_COVER_GAP
+        uint32_t frame;             // the sound's frame
+        bool start;                 // a piece or a gap frame starts here
+    };
+    struct Samples {
+        std::vector<uint64_t> lane_offsets;     // n_lanes + 1: lane l's samples are [lane_offsets[l], lane_offsets[l + 1])
+        std::vector<double> samples;
+        std::vector<int32_t> pcm32;
+    };
+    // search: WSOLA's width in samples, at most 512; 0 is the plain warp
+    Resynth(std::shared_ptr<Context> ctx, const std::vector<ArcSound> &sounds, uint32_t n_lanes = 1, uint32_t search = 0)
+        : ctx_(std::move(ctx)), lanes_(n_lanes)
+    {
+        std::vector<double> samples;
+        std::vector<uint64_t> soff(sounds.size() + 1, 0);
+        for (std::size_t i = 0; i < sounds.size(); ++i) {
+            samples.insert(samples.end(), sounds[i]->samples().begin(), sounds[i]->samples().end());
+            soff[i + 1] = samples.size();
+        }
+        ctx_->check(ssym_samples_create(ctx_->get(), samples.data(), soff.data(), (uint32_t)sounds.size(), &store_));
+        const int32_t rc = ssym_resynth_create(ctx_->get(), store_, n_lanes, search, &rs_);
+        if (rc != SSYM_OK) {
+            ssym_samples_destroy(ctx_->get(), store_);
+            ctx_->check(rc);
+        }
+    }
+    ~Resynth()
+    {
+        ssym_resynth_destroy(ctx_->get(), rs_);      // the resynthesiser reads the store: it goes first
+        ssym_samples_destroy(ctx_->get(), store_);
+    }
+    Resynth(const Resynth &) = delete;
+    Resynth &operator=(const Resynth &) = delete;
+
+    // frames ordered by (lane, column) -- a Mosaicker's frames pass straight in; the samples they release
+    Samples push(const std::vector<Frame> &frames)
+    {
+        const size_t n = frames.size();
+        std::vector<uint32_t> lane(n), column(n), src(n), frame(n), start(n);
+        for (size_t k = 0; k < n; ++k) {
+            lane[k] = frames[k].lane, column[k] = frames[k].column, src[k] = frames[k].src, frame[k] = frames[k].frame;
+            start[k] = frames[k].start ? 1u : 0u;
+        }
+        uint64_t got = 0;
+        ctx_->check(ssym_resynth_push(ctx_->get(), rs_, lane.data(), column.data(), src.data(), frame.data(), start.data(), n, &got));
+        return samples(got);
+    }
+    Samples push(const std::vector<Mosaicker::Frame> &frames)
+    {
+        std::vector<Frame> rows(frames.size());
+        for (size_t k = 0; k < frames.size(); ++k)
+            rows[k] = Frame{frames[k].lane, frames[k].column, frames[k].src, frames[k].frame, frames[k].start};
+        return push(rows);
+    }
+    // the mosaicker's last frame log, consumed where it lies: no frame goes through the host
+    Samples take(const Mosaicker &mk)
+    {
+        uint64_t got = 0;
+        ctx_->check(ssym_resynth_take(ctx_->get(), rs_, mk.handle(), &got));
+        return samples(got);
+    }
+    // "the lane has ended with total_samples samples": the rest, the tail behind the last frame included
+    Samples flush(uint32_t lane, uint64_t total_samples)
+    {
+        uint64_t got = 0;
+        ctx_->check(ssym_resynth_flush(ctx_->get(), rs_, lane, total_samples, &got));
+        return samples(got);
+    }
+    // frames consumed per lane since its reset
+    std::vector<uint64_t> counts() const
+    {
+        std::vector<uint64_t> out(lanes_);
+        ctx_->check(ssym_resynth_counts(rs_, out.data(), nullptr));
+        return out;
+    }
+    // samples released per lane since its reset
+    std::vector<uint64_t> released() const
+    {
+        std::vector<uint64_t> out(lanes_);
+        ctx_->check(ssym_resynth_counts(rs_, nullptr, out.data()));
+        return out;
+    }
+    void reset(uint32_t lane) { ctx_->check(ssym_resynth_reset(ctx_->get(), rs_, lane)); }
+
+  private:
+    Samples samples(uint64_t n) const
+    {
+        Samples out{std::vector<uint64_t>((size_t)lanes_ + 1, 0), std::vector<double>(n), std::vector<int32_t>(n)};
+        ctx_->check(ssym_resynth_samples(ctx_->get(), rs_, out.lane_offsets.data(), n ? out.samples.data() : nullptr,
+                                         n ? out.pcm32.data() : nullptr, 0));
+        return out;
+    }
+    std::shared_ptr<Context> ctx_;
+    uint32_t lanes_ = 0;
+    ssym_samples *store_ = nullptr;
+    ssym_resynth *rs_ = nullptr;
 };
 
 // One rank of a SoundDictionary split over the GPUs of one node (source-axis shards, one rank -- thread or process --

@@ -61,6 +61,7 @@ typedef struct ssym_stream ssym_stream;   /* growing sounds: samples + analysis 
 typedef struct ssym_spotter ssym_spotter; /* targets watched in growing sources: resumable spotting   */
 typedef struct ssym_coverer ssym_coverer; /* growing targets tiled by dictionary segments: live cover  */
 typedef struct ssym_mosaicker ssym_mosaicker; /* growing targets tiled by free spans: live mosaic       */
+typedef struct ssym_resynth ssym_resynth; /* committed mosaic frames to audio, push by push: live resynthesis */
 
 enum {
     SSYM_OK = 0,
@@ -1330,6 +1331,75 @@ SSYM_API int32_t ssym_mosaicker_best(ssym_ctx *ctx, const ssym_mosaicker *mk, do
                                      uint32_t *out_committed, uint32_t flags);
 SSYM_API int32_t ssym_mosaicker_counts(const ssym_mosaicker *mk, uint64_t *out_frames, uint64_t *out_capacity);
 SSYM_API int32_t ssym_mosaicker_reset(ssym_ctx *ctx, ssym_mosaicker *mk, uint32_t lane);
+
+/* Live resynthesis (DESIGN.md section 2 "Live resynthesis" and section 5.27): committed mosaic frames to audio, push by push.
+ * A resynthesiser holds n_lanes lanes against ONE resident sample store.  A lane receives committed frames in column order --
+ * from a mosaicker's frame log device to device (ssym_resynth_take) or from host arrays (ssym_resynth_push) -- and releases
+ * output samples as soon as their bits can no longer change.  From reset to flush a lane's output is, bit for bit, what the
+ * window calls below "Sample windows" give piece by piece for the finished mosaic.  HOP = 256, BIN = 1024 and w[] are those
+ * of "Warped reconstruction", and so are its taps / value / pcm rules; the pos[] chain is that of "WSOLA reconstruction";
+ * the window rule is that of "Sample windows" -- all word for word.
+ *   input    : each frame is (src, frame, start), the mosaicker's log words.  src = SSYM_COVER_GAP is a gap frame.  A tile
+ *              starts at every frame with start = 1.  A sounding tile a...b has map[j] = frame_j, first = map[a], last =
+ *              map[b]; within a tile map steps by 0, 1 or 2, never by 0 twice in a row.
+ *   output   : of a lane that ended with N samples: tile i owns (b - a + 1) * HOP samples, the last tile N - a * HOP.  A
+ *              sounding tile is the _spans call's output with the window [min(first * HOP, n_src), min((last + 1) * HOP,
+ *              n_src)) of sound src, the map map - first, and pos[0] = 0 at the tile's first frame.  A gap tile is +0.0.  A
+ *              lane without frames is N zeros.  Hop j of the lane is samples [j * HOP, (j + 1) * HOP); its taps are frames
+ *              max(a, j - 3) ... j of its own tile only.
+ *   release  : L is the map value of the latest frame pushed into the open tile.  Hop j is released, in column order, when
+ *              its tile is closed (a later frame with start = 1 has arrived in the lane, or the lane is flushed), or when
+ *              map[j] + R <= L with R = 2 for search = 0 and R = floor((search + 1279) / 256) otherwise (5 up to 256, 6 up to
+ *              512), or at once when it is a gap frame.  An open tile is rendered with the window end (L + 1) * HOP, clipped
+ *              to n_src.
+ *   why      : search = 0: a tap j' of hop j reads source hops up to map[j'] + (j - j'); any two consecutive steps sum to at
+ *              least 1, so that is at most map[j] + 2.  search > 0: the template reads up to pos[j-1] + HOP + BIN - 1, at
+ *              most map[j] * HOP + search + 1279; candidates, admissibility and taps reach less far.  Every read that decides
+ *              a released hop therefore lies below (L + 1) * HOP: a later `last` cannot change it.
+ *   so       : at most 2 R hops of a lane are held back (4 for the plain warp, 12 for WSOLA), R on a diagonal map; what is
+ *              released depends on the frames consumed, not on how they were cut into pushes; device state is a ring of 16
+ *              frames per lane (the unreleased frames and the three before them with their pos).
+ *   flush    : (lane, total_samples) closes the open tile and releases the rest, the tail total_samples - frames * HOP
+ *              included.  The lane has then ENDED until ssym_resynth_reset.
+ *
+ * ssym_resynth_create: any context (as ssym_reconstruct_warped).  store is READ BY THE RESYNTHESISER FOR AS LONG AS IT LIVES:
+ *   destroy the resynthesiser first.  search: ssym_reconstruct_wsola's S, at most 512 (beyond: SSYM_E_INVALID); 0 is the plain
+ *   warp.  n_lanes 1 ... 65535 (0: SSYM_E_INVALID; more: SSYM_E_UNSUPPORTED).  An empty store: SSYM_E_EMPTY_DICT.  Refusals
+ *   come before any device work.
+ * ssym_resynth_push: n_frames frames in HOST arrays ordered by (lane, column).  Refusals, all SSYM_E_INVALID, nothing
+ *   consumed, the earliest entry's first fault reported, per entry in this order: a lane outside the lanes or out of order;
+ *   column does not continue the lane's count; the lane has ended; the lane's first frame has start = 0; src is neither a
+ *   sound of the store nor SSYM_COVER_GAP; a frame with start = 0 that names another sound than its tile, follows a gap
+ *   frame, or breaks the 0 / 1 / 2 rule.  A lane consumes at most 2^31 - 1 frames (SSYM_E_UNSUPPORTED).
+ *   out_n_samples  the samples this call released (read them with ssym_resynth_samples)
+ * ssym_resynth_take: consumes the mosaicker's last frame log (that of its last push / follow / flush) where it lies, in
+ *   device memory: no frame goes through the host.  The mosaicker must be of the same context and have as many lanes, and
+ *   every lane's log must continue the columns the lane has consumed: SSYM_E_INVALID otherwise.  Taking the same log twice:
+ *   SSYM_E_INVALID.  The frames of a mosaicker obey the tile rules by construction and are not checked again.
+ * ssym_resynth_samples: the samples of the last push / take / flush, lane by lane: lane l's are
+ *   [out_lane_offsets[l], out_lane_offsets[l+1]) of out_samples (f64) and out_pcm32 (warp_pcm32 of each).  out_lane_offsets
+ *   ([n_lanes + 1], always HOST), out_samples and out_pcm32 (HOST, or device memory with SSYM_OUT_DEVICE) are each nullable.
+ * ssym_resynth_flush: the flush of one lane.  total_samples < frames * HOP, a lane outside the lanes, a lane that has ended
+ *   or out_n_samples NULL: SSYM_E_INVALID.
+ * ssym_resynth_counts: frames consumed and samples released per lane since its reset (n_lanes u64 each, HOST, nullable).
+ *   Host arithmetic, no device work.
+ * ssym_resynth_reset: one lane back to "nothing consumed".
+ * One synchronisation per call: the released counts depend on device data and come back with it.  ssym_get_timings
+ * afterwards: main_ms = the search, reduce_ms = staging and synthesis, n_pairs = the frames the call consumed.  A call's hop
+ * list (32 bytes per released hop) and its samples (12 bytes each) are scratch of the object, reused by the next call. */
+SSYM_API int32_t ssym_resynth_create(ssym_ctx *ctx, const ssym_samples *store, uint32_t n_lanes, uint32_t search,
+                                     ssym_resynth **out);
+SSYM_API int32_t ssym_resynth_destroy(ssym_ctx *ctx, ssym_resynth *rs);
+SSYM_API int32_t ssym_resynth_push(ssym_ctx *ctx, ssym_resynth *rs, const uint32_t *lane, const uint32_t *column,
+                                   const uint32_t *src, const uint32_t *frame, const uint32_t *start, uint64_t n_frames,
+                                   uint64_t *out_n_samples);
+SSYM_API int32_t ssym_resynth_take(ssym_ctx *ctx, ssym_resynth *rs, const ssym_mosaicker *mk, uint64_t *out_n_samples);
+SSYM_API int32_t ssym_resynth_samples(ssym_ctx *ctx, const ssym_resynth *rs, uint64_t *out_lane_offsets, double *out_samples,
+                                      int32_t *out_pcm32, uint32_t flags);
+SSYM_API int32_t ssym_resynth_flush(ssym_ctx *ctx, ssym_resynth *rs, uint32_t lane, uint64_t total_samples,
+                                    uint64_t *out_n_samples);
+SSYM_API int32_t ssym_resynth_counts(const ssym_resynth *rs, uint64_t *out_frames, uint64_t *out_samples);
+SSYM_API int32_t ssym_resynth_reset(ssym_ctx *ctx, ssym_resynth *rs, uint32_t lane);
 
 #ifdef __cplusplus
 }

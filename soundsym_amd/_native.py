@@ -69,6 +69,8 @@ ABI_SYMBOLS = [
     "ssym_coverer_flush", "ssym_coverer_best", "ssym_coverer_counts", "ssym_coverer_reset", "ssym_coverer_create_gaps",
     "ssym_mosaicker_create", "ssym_mosaicker_destroy", "ssym_mosaicker_push", "ssym_mosaicker_follow", "ssym_mosaicker_frames",
     "ssym_mosaicker_flush", "ssym_mosaicker_best", "ssym_mosaicker_counts", "ssym_mosaicker_reset",
+    "ssym_resynth_create", "ssym_resynth_destroy", "ssym_resynth_push", "ssym_resynth_take", "ssym_resynth_samples",
+    "ssym_resynth_flush", "ssym_resynth_counts", "ssym_resynth_reset",
     "ssym_reconstruct_warped", "ssym_reconstruct_wsola",
     "ssym_dtw_align_spans_sizes", "ssym_dtw_align_spans", "ssym_reconstruct_warped_spans", "ssym_reconstruct_wsola_spans",
 ]
@@ -434,6 +436,22 @@ def lib() -> ctypes.CDLL:
     L.ssym_mosaicker_counts.argtypes = [vp, vp, ctypes.POINTER(u64)]
     L.ssym_mosaicker_reset.restype = i32
     L.ssym_mosaicker_reset.argtypes = [vp, vp, u32]
+    L.ssym_resynth_create.restype = i32
+    L.ssym_resynth_create.argtypes = [vp, vp, u32, u32, pvp]
+    L.ssym_resynth_destroy.restype = i32
+    L.ssym_resynth_destroy.argtypes = [vp, vp]
+    L.ssym_resynth_push.restype = i32
+    L.ssym_resynth_push.argtypes = [vp, vp, vp, vp, vp, vp, vp, u64, ctypes.POINTER(u64)]
+    L.ssym_resynth_take.restype = i32
+    L.ssym_resynth_take.argtypes = [vp, vp, vp, ctypes.POINTER(u64)]
+    L.ssym_resynth_samples.restype = i32
+    L.ssym_resynth_samples.argtypes = [vp, vp, vp, vp, vp, u32]
+    L.ssym_resynth_flush.restype = i32
+    L.ssym_resynth_flush.argtypes = [vp, vp, u32, u64, ctypes.POINTER(u64)]
+    L.ssym_resynth_counts.restype = i32
+    L.ssym_resynth_counts.argtypes = [vp, vp, vp]
+    L.ssym_resynth_reset.restype = i32
+    L.ssym_resynth_reset.argtypes = [vp, vp, u32]
     _lib = L
     return L
 

@@ -866,7 +866,7 @@ class LiveMosaic:
     sound gains later.  A run of gap frames comes as one Gap per call; the run may go on in the next call, and `mosaics`
     merges across calls."""
 
-    def __init__(self, sounds, stream, mosaicker, piece_penalty: float, gap_cost=None):
+    def __init__(self, sounds, stream, mosaicker, piece_penalty: float, gap_cost=None, resynth=None, gap_fill: str = "silence"):
         self.sounds, self.stream, self.mosaicker, self.piece_penalty = sounds, stream, mosaicker, float(piece_penalty)
         self.gap_cost = gap_cost
         # per sound: (src, frame, cost, start) of every committed frame, and the frames already returned as closed pieces
@@ -874,6 +874,11 @@ class LiveMosaic:
         self._closed = [0 for _ in sounds]
         self._emitted = [[] for _ in sounds]
         self._held = []                                  # pieces closed by a poll that was refused part-way
+        # mosaic_live(audio=True): a Resynth takes every frame log; per sound the (samples, pcm) blocks released and not
+        # yet returned by audio(), and the sample they start at
+        self.resynth, self.gap_fill = resynth, gap_fill
+        self._audio = [[] for _ in sounds]
+        self._audio_at = [0 for _ in sounds]
 
     def _take(self, ended=()):
         lane, col, src, frame, cost, start = self.mosaicker.frames()
@@ -909,16 +914,66 @@ class LiveMosaic:
         except SsymError as err:
             if err.code == SSYM_E_UNSUPPORTED:
                 self._held = self._take()
+                self._take_audio()
             raise
-        return self._take()
+        out = self._take()
+        self._take_audio()
+        return out
 
     def flush(self):
-        """"The sounds have ended": the rest of every sound's mosaic.  The mosaic consumes nothing more afterwards."""
+        """"The sounds have ended": the rest of every sound's mosaic.  The mosaic consumes nothing more afterwards.  With
+        audio, every sound's resynthesis ends too, at len(sound.samples()) samples."""
         out = []
         for lane in range(self.mosaicker.n_lanes):
             self.mosaicker.flush(lane)
             out += self._take(ended=(lane,))
+            self._take_audio()
+            if self.resynth is not None:
+                self.resynth.flush(lane, len(self.sounds[lane].samples()))
+                self._gather_audio()
         return sorted(out, key=lambda t: (t[0], t[1].start_frame))   # (only pieces held from a refused poll move)
+
+    def _take_audio(self):
+        """The resynthesiser consumes the mosaicker's last frame log, device to device; what that releases is kept for audio()."""
+        if self.resynth is not None:
+            self.resynth.take(self.mosaicker)
+            self._gather_audio()
+
+    def _gather_audio(self):
+        if not self.resynth.n_samples:
+            return
+        off, smp, pcm = self.resynth.samples(want_pcm32=True)
+        for l in range(len(self.sounds)):
+            a, b = int(off[l]), int(off[l + 1])
+            if b > a:
+                self._audio[l].append((smp[a:b], pcm[a:b]))
+
+    def audio(self, want_pcm32: bool = False):
+        """mosaic_live(audio=True): per sound, the samples released since the last call (f64; with want_pcm32 (samples,
+        pcm int32)).  Released samples are final: concatenated from the first poll to flush they are
+        reconstruct_mosaic(sound, mosaic=mosaics()[i], search=, gap_fill=)'s, bit for bit.  A sample leaves when no later
+        frame can change it: at most 4 frames behind the committed frames for search = 0, at most 12 with a search (DESIGN.md
+        section 2 "Live resynthesis").  gap_fill="target": gap stretches are filled here, on the host, with the sound's own
+        samples, as reconstruct_mosaic fills them."""
+        if self.resynth is None:
+            raise ValueError("audio: the LiveMosaic was made without audio (mosaic_live(audio=True))")
+        out = []
+        for l, sound in enumerate(self.sounds):
+            parts, self._audio[l] = self._audio[l], []
+            smp = np.concatenate([p[0] for p in parts]) if parts else np.zeros(0)
+            pcm = np.concatenate([p[1] for p in parts]) if parts else np.zeros(0, dtype=np.int32)
+            src = self._frames[l][0]
+            if self.gap_fill == "target" and smp.size and src:
+                k = np.arange(self._audio_at[l], self._audio_at[l] + smp.size)
+                gap = np.array(src, dtype=np.uint32)[np.minimum(k // HOP, len(src) - 1)] == COVER_GAP   # the last tile runs to the end
+                own = np.asarray(sound.samples(), dtype=np.float64)[k[gap]]
+                smp[gap] = own
+                with np.errstate(invalid="ignore", over="ignore"):
+                    x = np.nan_to_num(2147483647.0 * own, nan=0.0)
+                    pcm[gap] = np.trunc(np.clip(x, -2147483648.0, 2147483647.0)).astype(np.int64).astype(np.int32)
+            self._audio_at[l] += smp.size
+            out.append((smp, pcm) if want_pcm32 else smp)
+        return out
 
     def committed(self):
         """Per sound (src uint32, frame uint32, frame_cost f64, start bool), one entry per committed frame -- the open
@@ -950,6 +1005,8 @@ class LiveMosaic:
         return self.mosaicker.counts()[0].astype(np.int64), covered.astype(np.int64), committed.astype(np.int64), total
 
     def close(self):
+        if self.resynth is not None:
+            self.resynth.close()
         self.mosaicker.close()
 
 
@@ -1528,7 +1585,8 @@ class SoundDictionary:
             raise ValueError("cover_live: the sounds' ncoeffs must be the dictionary's")
         return LiveCover(sounds, st, self.engine.coverer(self.resident(), len(sounds), penalty, gap), penalty, gap)
 
-    def mosaic_live(self, sounds: Sequence[Sound], piece_penalty: float = 0.0, gap_cost=None) -> "LiveMosaic":
+    def mosaic_live(self, sounds: Sequence[Sound], piece_penalty: float = 0.0, gap_cost=None, audio: bool = False,
+                    search: int = 0, gap_fill: str = "silence") -> "LiveMosaic":
         """Tile Sounds that are still growing (fed with push_samples / push_sounds): a Mosaicker on this dictionary follows
         the sounds' stream (ssym_mosaicker_*, DESIGN.md section 2 "Live mosaic"; dtw engines without a band).  The sounds
         must be resident and share one stream, sound i in lane i -- what one push_sounds(sounds, ...) leaves -- ValueError
@@ -1536,15 +1594,31 @@ class SoundDictionary:
         the rest; on f64 engines the mosaics() after flush are `mosaic`'s, bit for bit.  On f32 engines `mosaic` rounds
         the targets' features to f32 first while the mosaicker reads the stream's f64 frames as they are (as `watch`
         does), so the two can differ there.  The LiveMosaic keeps the dictionary's resident copy: close it before the
-        dictionary changes.  gap_cost as for `mosaic`: a NaN frame then becomes a gap frame and the sound goes on."""
+        dictionary changes.  gap_cost as for `mosaic`: a NaN frame then becomes a gap frame and the sound goes on.
+        audio=True: the LiveMosaic also owns a Resynth on the dictionary's resident samples (ssym_resynth_*, "Live
+        resynthesis"): every poll hands it the committed frames device to device, and LiveMosaic.audio() returns the samples
+        that releases -- from the first poll to flush reconstruct_mosaic's (search and gap_fill as there), bit for bit.
+        With audio=False (the default) search and gap_fill are not used."""
         penalty, gap = self._cover_checks(piece_penalty, "mosaic_live"), _cover_gap_cost(gap_cost)
+        if audio:
+            search = _wsola_search(search)
+            if gap_fill not in ("silence", "target"):
+                raise ValueError('gap_fill must be "silence" or "target"')
         sounds = list(sounds)
         st = _shared_stream(sounds, "mosaic_live")
         if self.engine is not st.engine:
             raise ValueError("mosaic_live: the dictionary's engine must be the one that holds the sounds' stream")
         if st.ncoeffs != self._dim():
             raise ValueError("mosaic_live: the sounds' ncoeffs must be the dictionary's")
-        return LiveMosaic(sounds, st, self.engine.mosaicker(self.resident(), len(sounds), penalty, gap), penalty, gap)
+        mk = self.engine.mosaicker(self.resident(), len(sounds), penalty, gap)
+        if not audio:
+            return LiveMosaic(sounds, st, mk, penalty, gap)
+        try:
+            rs = self.engine.resynth(self.resident_samples(), len(sounds), search)
+        except Exception:
+            mk.close()
+            raise
+        return LiveMosaic(sounds, st, mk, penalty, gap, rs, gap_fill)
 
     def mosaic_long(self, target: Sound, piece_penalty: float = 0.0, block_frames: int = 4096, gap_cost=None) -> "Mosaic":
         """`mosaic` for one target of any length: a one-lane Mosaicker is pushed the target's frames block_frames at a time

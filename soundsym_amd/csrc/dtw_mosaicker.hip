@@ -107,6 +107,7 @@ struct ssym_mosaicker {
     double *frames = nullptr;                // [nLanes][cap][dim]
     // the frame log: the frames of the last push / follow / flush; the words are lane, column, src, frame, start
     ssym::LaneLog log{5};
+    uint64_t calls = 0;                      // push / follow / flush calls that began a log (host only): names a log to its reader
 };
 
 namespace ssym {
@@ -549,6 +550,7 @@ int32_t mosaicker_run(ssym_ctx *ctx, ssym_mosaicker *mk, const char *fn, const s
     int32_t rc = mk->log.begin(ctx, mk->consumed, mk->done, m, flushLane);
     if (rc != SSYM_OK)
         return rc;
+    ++mk->calls;
     for (uint32_t l = 0; l < nL; ++l)
         tm.n_pairs += (uint64_t)mk->G * m[l];                 // cells
     std::vector<uint64_t> at(nL, 0);
@@ -750,6 +752,13 @@ int32_t mosaicker_best(ssym_ctx *ctx, const ssym_mosaicker *mk, double *out_tota
 }
 
 }  // namespace
+
+// the last frame log as the resynthesiser takes it (lane_feed.hpp): lane l's first entry is column done[l] + 1 - count[l]
+MosaickerLog mosaicker_log(const ssym_mosaicker *mk)
+{
+    return MosaickerLog{mk->ctx, mk->nLanes, &mk->log, &mk->done, mk->calls};
+}
+
 }  // namespace ssym
 
 using namespace ssym;

@@ -4,7 +4,9 @@
 // messages and the upload of a push are here once; what an object does with the frames (spotter_run, coverer_run,
 // mosaicker_run) is its own.  So is the log of a call's results that the coverer and the mosaicker keep (LaneLog: its room,
 // its layout at the start of a call and the copy out; the spotter's event log keeps its contents while it grows and is
-// sorted, and stays with the spotter), and pow2_at_least.
+// sorted, and stays with the spotter), and pow2_at_least.  The resynthesiser (resynth.hip) is lane-fed too, with committed
+// frames instead of features: it takes check_handle, the lane limit and the lane check of flush / reset from here, keeps
+// its released samples in a LaneLog (one entry per sample) and reads the mosaicker's (MosaickerLog).
 //
 // The order of the refusals is part of the interface ("the earlier of two faults is the one reported"):
 //   push   : frame_offsets / count NULL | the object's own check | lane by lane: offsets decrease, the lane has ended,
@@ -141,7 +143,19 @@ struct LaneLog {
     }
 };
 
-// what every call refuses before anything else; noun: "spotter", "coverer", "mosaicker"
+// The mosaicker's last frame log where it lies (dtw_mosaicker.hip): what the resynthesiser (resynth.hip) takes device to
+// device.  Words 2, 3 and 4 are src, frame and start; lane l's first entry is column (*done)[l] + 1 - log->count[l]; `calls`
+// names the log (it counts the calls that began one).
+struct MosaickerLog {
+    const ssym_ctx *ctx;
+    uint32_t nLanes;
+    const LaneLog *log;
+    const std::vector<int64_t> *done;
+    uint64_t calls;
+};
+MosaickerLog mosaicker_log(const ssym_mosaicker *mk);
+
+// what every call refuses before anything else; noun: "spotter", "coverer", "mosaicker", "resynthesiser"
 template <class Handle>
 int32_t check_handle(ssym_ctx *ctx, const Handle *h, const char *noun, const char *fn)
 {

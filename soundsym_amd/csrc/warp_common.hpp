@@ -2,7 +2,8 @@
 // same overlap-add from searched frame positions): the frame geometry, the window's bits, the 32-bit conversion, the one
 // text of the synthesis kernel (warp_synth; warp_kernel and wsola_synth_kernel are its two wrappers) and the one host
 // driver path (WarpCall: refusals, staging block, uploads, outputs).  A .hip file keeps its kernels' names, its launches
-// and its timings; wsola.hip also the search and the positions.
+// and its timings; wsola.hip also the search and the positions.  One step of that search (wsola_step, with wsola_sums and
+// wsola_beats) is here too: wsola_search_kernel and the live resynthesis (resynth.hip: resynth_search_kernel) both run it.
 //
 // Gather form: one thread per output sample, which no other thread writes.  One 256-thread workgroup per (target, 4096-sample chunk),
 // as reconstruct_kernel.  Thread `tid` computes samples k = chunk + tid + 256 u, u = 0 .. 15; for a fixed u the whole
@@ -46,6 +47,137 @@ inline const std::vector<double> &warp_window()
         return w;
     }();
     return win;
+}
+
+// ---- one step of WSOLA's search (wsola.hip's definition), shared by wsola_search_kernel and resynth_search_kernel ----
+constexpr uint32_t kWsolaMaxSearch = 512;
+constexpr int kWsolaMaxRounds = (2 * (int)kWsolaMaxSearch + 1 + 255) / 256;      // 5 lags per thread at most
+constexpr int kWsolaNone = INT32_MIN;                                            // "no lag yet" in the argmax
+
+// does lag a (score sa) beat lag b?  Neither score is NaN; kWsolaNone loses to everything.
+__device__ __forceinline__ bool wsola_beats(double sa, int da, double sb, int db)
+{
+    if (da == kWsolaNone) return false;
+    if (db == kWsolaNone) return true;
+    if (sa != sb) return sa > sb;
+    const int aa = da < 0 ? -da : da, ab = db < 0 ? -db : db;
+    if (aa != ab) return aa < ab;
+    return da < db;
+}
+
+// the two sums of R lags of one thread, n ascending, products and sums rounded separately
+template <int R>
+__device__ __forceinline__ void wsola_sums(const double *__restrict__ sT, const double *__restrict__ sC, const int *lag,
+                                           double *c, double *e)
+{
+#pragma unroll
+    for (int r = 0; r < R; ++r)
+        c[r] = e[r] = 0.0;
+#pragma unroll 4
+    for (int n = 0; n < kWarpBin; ++n) {
+        const double tv = sT[n];
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            const double v = sC[lag[r] + n];
+            c[r] = __dadd_rn(c[r], __dmul_rn(tv, v));
+            e[r] = __dadd_rn(e[r], __dmul_rn(v, v));
+        }
+    }
+}
+
+// The LDS of a search workgroup (256 threads) and what a thread knows of its place in it.  sm: [BIN] template, then
+// [BIN + 2 S] candidate span -- (2 BIN + 2 S) doubles of dynamic LDS.
+struct WsolaStep {
+    double *sT, *sC;
+    double *wScore;              // [4]
+    int *wLag;                   // [4]
+    int tid, wave, S, L, rounds;
+    __device__ __forceinline__ WsolaStep(double *sm, double *score, int *lagOut, uint32_t search)
+        : sT(sm), sC(sm + kWarpBin), wScore(score), wLag(lagOut), tid((int)threadIdx.x), wave((int)threadIdx.x >> 6), S((int)search),
+          L(2 * (int)search + 1)
+    {
+        // rounds in which this wave owns a lag: lags wave * 64 + 256 r < L
+        rounds = L > wave * 64 ? (L - wave * 64 + 255) / 256 : 0;
+    }
+};
+
+// d* of one step, the same in every thread of the workgroup: x[0 .. sLen) the sound, prev = pos[j-1], nom = map[j] * HOP
+// (< 2^40).  The template (8 KiB) and the candidate span x[nom - S .. nom + S + BIN) (<= 16 KiB) go to LDS; thread tid owns
+// the lags tid, tid + 256, ... and runs their sums in the defined order; the argmax is a butterfly over the wave and a pass
+// over the four waves' winners -- the order (score, -|d|, -d) is total over distinct lags, so the tree's shape cannot
+// change the winner.  Every thread of the workgroup calls it, S > 0 or not.
+__device__ __forceinline__ int wsola_step(const WsolaStep &w, const double *__restrict__ x, uint64_t sLen, uint64_t prev, int64_t nom)
+{
+    const int tid = w.tid, S = w.S, L = w.L, rounds = w.rounds;
+    double *sT = w.sT, *sC = w.sC;
+    // admissible lags lo .. hi: 0 <= nom + d < sLen (sLen < 2^61: a store of doubles)
+    const int64_t lo = nom < (int64_t)S ? -nom : -(int64_t)S;
+    const int64_t hi = std::min<int64_t>((int64_t)S, (int64_t)sLen - 1 - nom);
+    if (!(S > 0 && lo <= hi))                // the same for every thread of the workgroup
+        return 0;
+    __syncthreads();                         // the step before has read its template and span
+    for (int i = tid; i < kWarpBin; i += 256) {
+        const uint64_t q = prev + (uint64_t)kWarpHop + (uint64_t)i;
+        sT[i] = q < sLen ? x[q] : 0.0;
+    }
+    for (int i = tid; i < kWarpBin + 2 * S; i += 256) {
+        const int64_t p = nom - (int64_t)S + (int64_t)i;
+        sC[i] = (p >= 0 && (uint64_t)p < sLen) ? x[p] : 0.0;
+    }
+    __syncthreads();
+    int lag[kWsolaMaxRounds];
+    double c[kWsolaMaxRounds], e[kWsolaMaxRounds];
+#pragma unroll
+    for (int r = 0; r < kWsolaMaxRounds; ++r)
+        lag[r] = std::min(tid + 256 * r, L - 1);     // a lane past the last lag repeats it: reads stay in the span
+    switch (rounds) {
+    case 1: wsola_sums<1>(sT, sC, lag, c, e); break;
+    case 2: wsola_sums<2>(sT, sC, lag, c, e); break;
+    case 3: wsola_sums<3>(sT, sC, lag, c, e); break;
+    case 4: wsola_sums<4>(sT, sC, lag, c, e); break;
+    case 5: wsola_sums<5>(sT, sC, lag, c, e); break;
+    default: break;
+    }
+    double bs = 0.0;
+    int bd = kWsolaNone;
+#pragma unroll
+    for (int r = 0; r < kWsolaMaxRounds; ++r) {
+        if (r >= rounds || tid + 256 * r >= L)
+            continue;
+        const int d = tid + 256 * r - S;
+        if ((int64_t)d < lo || (int64_t)d > hi)
+            continue;
+        const double sc = e[r] == 0.0 ? 0.0 : __ddiv_rn(c[r], __dsqrt_rn(e[r]));
+        if (sc != sc)
+            continue;                        // NaN never wins
+        if (wsola_beats(sc, d, bs, bd)) {
+            bs = sc;
+            bd = d;
+        }
+    }
+#pragma unroll
+    for (int v = 32; v >= 1; v >>= 1) {
+        const double os = __shfl_xor(bs, v, 64);
+        const int od = __shfl_xor(bd, v, 64);
+        if (wsola_beats(os, od, bs, bd)) {
+            bs = os;
+            bd = od;
+        }
+    }
+    if ((tid & 63) == 0) {
+        w.wScore[w.wave] = bs;
+        w.wLag[w.wave] = bd;
+    }
+    __syncthreads();
+    bs = w.wScore[0];
+    bd = w.wLag[0];
+#pragma unroll
+    for (int v = 1; v < 4; ++v)
+        if (wsola_beats(w.wScore[v], w.wLag[v], bs, bd)) {
+            bs = w.wScore[v];
+            bd = w.wLag[v];
+        }
+    return bd == kWsolaNone ? 0 : bd;
 }
 
 namespace {      // the including file's own, as the kernels that take these arguments: their mangled names stay

@@ -11,7 +11,8 @@
 // p = pos[j] + m.  Fallback: warp.hip's.
 //
 // wsola_search_kernel: the chain over j is serial, the targets are independent: one 256-thread workgroup per target,
-// grid-stride.  Per step the template (8 KiB) and the candidate span x[nom - S .. nom + S + BIN) (<= 16 KiB) go to LDS;
+// grid-stride.  A step is wsola_step (warp_common.hpp), which resynth_search_kernel (resynth.hip) runs as well.  Per step
+// the template (8 KiB) and the candidate span x[nom - S .. nom + S + BIN) (<= 16 KiB) go to LDS;
 // thread tid owns the lags tid, tid + 256, ... (at most five) and runs their sums n = 0 .. 1023 in the defined order, one
 // template read (a broadcast) and one span read (consecutive lanes, consecutive doubles) per lag and n.  A wave runs only
 // the rounds in which it owns a lag, so the odd 2 S + 1-th lag costs one wave one round.  The argmax is a butterfly over
@@ -25,10 +26,7 @@
 namespace ssym {
 namespace {
 
-constexpr uint32_t kWsolaMaxSearch = 512;
-constexpr int kWsolaMaxRounds = (2 * (int)kWsolaMaxSearch + 1 + 255) / 256;      // 5 lags per thread at most
 constexpr unsigned kWsolaMaxGrid = 2048;                                         // search workgroups; targets beyond: grid-stride
-constexpr int kWsolaNone = INT32_MIN;                                            // "no lag yet" in the argmax
 constexpr uint64_t kWsolaUnset = ~(uint64_t)0;                                   // a position slot the search did not write
 
 struct WsolaArgs : WarpArgs {   // the plain warp's (WarpCall::stage fills them), and:
@@ -37,47 +35,12 @@ struct WsolaArgs : WarpArgs {   // the plain warp's (WarpCall::stage fills them)
     uint64_t *pos;              // sample start of every source frame, laid out as map (mapOff is rebased to both)
 };
 
-// does lag a (score sa) beat lag b?  Neither score is NaN; kWsolaNone loses to everything.
-__device__ __forceinline__ bool wsola_beats(double sa, int da, double sb, int db)
-{
-    if (da == kWsolaNone) return false;
-    if (db == kWsolaNone) return true;
-    if (sa != sb) return sa > sb;
-    const int aa = da < 0 ? -da : da, ab = db < 0 ? -db : db;
-    if (aa != ab) return aa < ab;
-    return da < db;
-}
-
-// the two sums of R lags of one thread, n ascending, products and sums rounded separately
-template <int R>
-__device__ __forceinline__ void wsola_sums(const double *__restrict__ sT, const double *__restrict__ sC, const int *lag,
-                                           double *c, double *e)
-{
-#pragma unroll
-    for (int r = 0; r < R; ++r)
-        c[r] = e[r] = 0.0;
-#pragma unroll 4
-    for (int n = 0; n < kWarpBin; ++n) {
-        const double tv = sT[n];
-#pragma unroll
-        for (int r = 0; r < R; ++r) {
-            const double v = sC[lag[r] + n];
-            c[r] = __dadd_rn(c[r], __dmul_rn(tv, v));
-            e[r] = __dadd_rn(e[r], __dmul_rn(v, v));
-        }
-    }
-}
-
 __global__ __launch_bounds__(256) void wsola_search_kernel(const WsolaArgs a)
 {
     extern __shared__ double sm[];               // [BIN] template, then [BIN + 2 S] candidate span
     __shared__ double wScore[4];
     __shared__ int wLag[4];
-    double *sT = sm, *sC = sm + kWarpBin;
-    const int tid = (int)threadIdx.x, wave = tid >> 6;
-    const int S = (int)a.search, L = 2 * S + 1;
-    // rounds in which this wave owns a lag: lags wave * 64 + 256 r < L
-    const int rounds = L > wave * 64 ? (L - wave * 64 + 255) / 256 : 0;
+    const WsolaStep w(sm, wScore, wLag, a.search);
 
     for (uint32_t t = blockIdx.x; t < a.nTargets; t += gridDim.x) {
         const uint32_t F = (a.pairLen && a.pairLen[t] == 0) ? 0u : a.mapFrames[t];
@@ -93,81 +56,12 @@ __global__ __launch_bounds__(256) void wsola_search_kernel(const WsolaArgs a)
         const uint32_t *__restrict__ map = a.map + a.mapOff[t];
         uint64_t *pos = a.pos + a.mapOff[t];
         uint64_t prev = (uint64_t)map[0] * (uint64_t)kWarpHop;
-        if (tid == 0)
+        if (w.tid == 0)
             pos[0] = prev;
         for (uint32_t j = 1; j < F; ++j) {
             const int64_t nom = (int64_t)((uint64_t)map[j] * (uint64_t)kWarpHop);       // < 2^40
-            // admissible lags lo .. hi: 0 <= nom + d < sLen (sLen < 2^61: a store of doubles)
-            const int64_t lo = nom < (int64_t)S ? -nom : -(int64_t)S;
-            const int64_t hi = std::min<int64_t>((int64_t)S, (int64_t)sLen - 1 - nom);
-            int best = 0;
-            if (S > 0 && lo <= hi) {             // the same for every thread of the workgroup
-                __syncthreads();                 // the step before has read its template and span
-                for (int i = tid; i < kWarpBin; i += 256) {
-                    const uint64_t q = prev + (uint64_t)kWarpHop + (uint64_t)i;
-                    sT[i] = q < sLen ? x[q] : 0.0;
-                }
-                for (int i = tid; i < kWarpBin + 2 * S; i += 256) {
-                    const int64_t p = nom - (int64_t)S + (int64_t)i;
-                    sC[i] = (p >= 0 && (uint64_t)p < sLen) ? x[p] : 0.0;
-                }
-                __syncthreads();
-                int lag[kWsolaMaxRounds];
-                double c[kWsolaMaxRounds], e[kWsolaMaxRounds];
-#pragma unroll
-                for (int r = 0; r < kWsolaMaxRounds; ++r)
-                    lag[r] = std::min(tid + 256 * r, L - 1);     // a lane past the last lag repeats it: reads stay in the span
-                switch (rounds) {
-                case 1: wsola_sums<1>(sT, sC, lag, c, e); break;
-                case 2: wsola_sums<2>(sT, sC, lag, c, e); break;
-                case 3: wsola_sums<3>(sT, sC, lag, c, e); break;
-                case 4: wsola_sums<4>(sT, sC, lag, c, e); break;
-                case 5: wsola_sums<5>(sT, sC, lag, c, e); break;
-                default: break;
-                }
-                double bs = 0.0;
-                int bd = kWsolaNone;
-#pragma unroll
-                for (int r = 0; r < kWsolaMaxRounds; ++r) {
-                    if (r >= rounds || tid + 256 * r >= L)
-                        continue;
-                    const int d = tid + 256 * r - S;
-                    if ((int64_t)d < lo || (int64_t)d > hi)
-                        continue;
-                    const double sc = e[r] == 0.0 ? 0.0 : __ddiv_rn(c[r], __dsqrt_rn(e[r]));
-                    if (sc != sc)
-                        continue;                // NaN never wins
-                    if (wsola_beats(sc, d, bs, bd)) {
-                        bs = sc;
-                        bd = d;
-                    }
-                }
-#pragma unroll
-                for (int w = 32; w >= 1; w >>= 1) {
-                    const double os = __shfl_xor(bs, w, 64);
-                    const int od = __shfl_xor(bd, w, 64);
-                    if (wsola_beats(os, od, bs, bd)) {
-                        bs = os;
-                        bd = od;
-                    }
-                }
-                if ((tid & 63) == 0) {
-                    wScore[wave] = bs;
-                    wLag[wave] = bd;
-                }
-                __syncthreads();
-                bs = wScore[0];
-                bd = wLag[0];
-#pragma unroll
-                for (int w = 1; w < 4; ++w)
-                    if (wsola_beats(wScore[w], wLag[w], bs, bd)) {
-                        bs = wScore[w];
-                        bd = wLag[w];
-                    }
-                best = bd == kWsolaNone ? 0 : bd;
-            }
-            prev = (uint64_t)(nom + (int64_t)best);
-            if (tid == 0)
+            prev = (uint64_t)(nom + (int64_t)wsola_step(w, x, sLen, prev, nom));
+            if (w.tid == 0)
                 pos[j] = prev;
         }
     }

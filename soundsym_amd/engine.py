@@ -684,6 +684,81 @@ class Mosaicker(_LiveTiling):
         return tuple(self._results("frames", (np.uint32, np.uint32, np.uint32, np.uint32, np.float64, np.uint32), on_device))
 
 
+class Resynth(_Lanes):
+    """`n_lanes` lanes of live resynthesis against one resident sample store (ssym_resynth; definition in
+    include/soundsym_amd.h and DESIGN.md section 2 "Live resynthesis"): a lane takes committed mosaic frames -- a
+    Mosaicker's frame log device to device (`take`) or host arrays (`push`) -- and releases output samples as soon as their
+    bits can no longer change; from reset to flush a lane's output is reconstruct_mosaic's, bit for bit.  The object reads
+    the sample store for as long as it lives: it keeps `store` alive and must be closed before it.  n_samples: the samples
+    the last push / take / flush released, `samples` reads them."""
+
+    def __init__(self, engine: "Engine", ptr: int, store, n_lanes: int, search: int):
+        self.engine, self.ptr, self.store, self.n_lanes, self.search = engine, ptr, store, n_lanes, search
+        self.n_samples = 0
+
+    def _ran(self, name: str, *args) -> int:
+        n = ctypes.c_uint64()
+        nat.check(getattr(nat.lib(), "ssym_resynth_" + name)(self.engine.ctx, self.ptr, *args, ctypes.byref(n)), self.engine.ctx)
+        self.n_samples = int(n.value)
+        return self.n_samples
+
+    def push(self, lane, column, src, frame, start) -> int:
+        """ssym_resynth_push: frames in host arrays ordered by (lane, column) -- a Mosaicker.frames() result's lane,
+        column, src, frame and start pass straight in.  Returns the number of samples released."""
+        arrays = [np.ascontiguousarray(a, dtype=np.uint32).reshape(-1) for a in (lane, column, src, frame, start)]
+        n = arrays[0].size
+        if any(a.size != n for a in arrays):
+            raise ValueError("push: lane, column, src, frame and start must hold one entry per frame")
+        return self._ran("push", *(a.ctypes.data if n else None for a in arrays), n)
+
+    def take(self, mosaicker: "Mosaicker") -> int:
+        """ssym_resynth_take: consume the mosaicker's last frame log where it lies, device to device.  Returns as push."""
+        if mosaicker.n_lanes != self.n_lanes:
+            raise ValueError("take: the mosaicker's lanes must be the resynthesiser's")
+        return self._ran("take", mosaicker.ptr)
+
+    def flush(self, lane: int, total_samples: int) -> int:
+        """ssym_resynth_flush: "the lane has ended with total_samples samples" -- the open tile is closed, the rest and the
+        tail behind the last frame are released, and the lane consumes nothing more until `reset`."""
+        total = int(total_samples)
+        if total < 0 or total != total_samples:
+            raise ValueError("total_samples must be a whole number of samples, not negative")
+        return self._ran("flush", self._lane(lane), total)
+
+    def samples(self, want_pcm32: bool = False, on_device: bool = False):
+        """The samples of the last push / take / flush: (lane_offsets uint64 [n_lanes + 1], samples f64 [n_samples]) and
+        with want_pcm32 the int32 samples too; lane l's are [lane_offsets[l], lane_offsets[l + 1]).  on_device:
+        SSYM_OUT_DEVICE, the samples as torch tensors in device memory (the offsets stay a numpy array)."""
+        off = np.zeros(self.n_lanes + 1, dtype=np.uint64)
+        device = self.engine.device if on_device else None
+        (out, po), (pcm, pp) = _output(device, (self.n_samples,), np.float64), _output(device, (self.n_samples,), np.int32)
+        nat.check(nat.lib().ssym_resynth_samples(self.engine.ctx, self.ptr, off.ctypes.data, po if self.n_samples else None,
+                                                 pp if want_pcm32 and self.n_samples else None,
+                                                 0 if device is None else nat.OUT_DEVICE), self.engine.ctx)
+        return (off, out, pcm) if want_pcm32 else (off, out)
+
+    def counts(self):
+        """(frames consumed, samples released) per lane since its reset, uint64 [n_lanes] each."""
+        frames, smp = np.zeros(self.n_lanes, dtype=np.uint64), np.zeros(self.n_lanes, dtype=np.uint64)
+        nat.check(nat.lib().ssym_resynth_counts(self.ptr, frames.ctypes.data, smp.ctypes.data), self.engine.ctx)
+        return frames, smp
+
+    def reset(self, lane: int = 0) -> None:
+        """One lane back to "nothing consumed"."""
+        nat.check(nat.lib().ssym_resynth_reset(self.engine.ctx, self.ptr, self._lane(lane)), self.engine.ctx)
+
+    def close(self):
+        if self.ptr and self.engine.ctx:
+            nat.lib().ssym_resynth_destroy(self.engine.ctx, self.ptr)
+        self.ptr = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class Comm:
     """One rank of a source-sharded run: an RCCL communicator bound to an Engine (ssym_comm)."""
 
@@ -1334,6 +1409,17 @@ class Engine:
         nat.check(nat.lib().ssym_mosaicker_create(self.ctx, d.ptr, lanes, penalty, float("inf") if gap is None else gap,
                                                   ctypes.byref(out)), self.ctx)
         return Mosaicker(self, out.value, d, lanes, penalty, gap)
+
+    def resynth(self, samples_store, n_lanes: int = 1, search: int = 0) -> Resynth:
+        """ssym_resynth_create: `n_lanes` lanes of live resynthesis from the resident samples `samples_store` (Engine.samples;
+        "Live resynthesis").  search: reconstruct_wsola's, 0 ... 512 samples; 0 is the plain warp."""
+        search = _wsola_search(search)
+        lanes = int(n_lanes)
+        if lanes < 1:
+            raise ValueError("n_lanes must be at least 1")
+        out = ctypes.c_void_p()
+        nat.check(nat.lib().ssym_resynth_create(self.ctx, samples_store.ptr, lanes, search, ctypes.byref(out)), self.ctx)
+        return Resynth(self, out.value, samples_store, lanes, search)
 
     @staticmethod
     def mfcc_num_frames(n_samples: int, pad_tail: bool = False) -> int:
