@@ -38,6 +38,8 @@ pub const SSYM_DTYPE_F32: i32 = 1;
 
 pub const SSYM_OUT_DEVICE: u32 = 1;
 pub const SSYM_WARP_MAP_DEVICE: u32 = 32;
+pub const SSYM_FOLLOW_SAMPLES_DEVICE: u32 = 64;   // ssym_follow_envelope: `samples` is device memory
+pub const SSYM_FOLLOW_REF_DEVICE: u32 = 128;      // ... and `ref`
 pub const SSYM_DTW_FORCE_EXACT: u32 = 2;
 pub const SSYM_DTW_PRUNE: u32 = 4;
 pub const SSYM_STEP_SYMMETRIC: u32 = 0;  // the recurrence of ssym_dtw_spot: the _step calls are then the plain ones
@@ -261,6 +263,13 @@ extern "C" {
                                         win_len: *const u64, out_offsets: *const u64, n_targets: u32, frame_map: *const u32,
                                         map_offsets: *const u64, map_frames: *const u32, pair_len: *const u32, search: u32,
                                         flags: u32, out_pos: *mut u64, out_samples: *mut f64, out_pcm32: *mut i32) -> i32;
+
+    // envelope following: reconstructions (packed by out_offsets) scaled hop by hop to the loudness of their references
+    // (packed by ref_offsets), no gain above max_gain; out_gain (nullable): g(b) of all targets packed in target order.
+    // flags: SSYM_FOLLOW_SAMPLES_DEVICE, SSYM_FOLLOW_REF_DEVICE, SSYM_OUT_DEVICE (the three outputs).  Any context
+    pub fn ssym_follow_envelope(ctx: *mut SsymCtx, samples: *const f64, out_offsets: *const u64, n_targets: u32,
+                                reference: *const f64, ref_offsets: *const u64, max_gain: f64, flags: u32,
+                                out_samples: *mut f64, out_pcm32: *mut i32, out_gain: *mut f64) -> i32;
 
     // feature front-end (own MFCC definition -- parity with vox_box unpinned)
     pub fn ssym_mfcc_num_frames(n_samples: u64, flags: u32, out_frames: *mut u64) -> i32;

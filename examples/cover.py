@@ -2,6 +2,7 @@
 """examples/cover.py -- a reconstruction whose target is cut by the dictionary itself.
 
     python examples/cover.py -s TARGET.wav -d DICT.wav|DIR -o OUT.wav [--penalty 0] [--search 256] [--depth 5] [--threshold 4]
+                             [--follow [--max-gain 8]]
                              [--seed 0] [--gap-cost X] [--gap-fill silence|target]
 
 The dictionary is a folder of sounds (SoundDictionary.from_path) or one recording cut by a Partitioner trained on it, as
@@ -13,6 +14,8 @@ samples) resynthesises with the waveform-similarity search.  One line per piece:
 more than 128 frames are left out of the dictionary: a cover takes none longer.  --gap-cost X lets frames stay uncovered at X
 each (ssym_dtw_cover_gaps): a stretch that no sound fits better than X per frame -- breath, a door, a frame that is not
 finite -- is left out and comes back as silence, or as the target's own samples with --gap-fill target; one line per gap.
+--follow sends the output through the envelope follower (ssym_follow_envelope): hop by hop it takes the loudness of the
+target, no gain above --max-gain (default 8); without the flag the output file is what it was.
 """
 import argparse
 import os
@@ -38,7 +41,10 @@ def main(argv=None):
     ap.add_argument("--seed", type=int, default=0, help="draws the mixture's starting frames")
     ap.add_argument("--gap-cost", type=float, default=None, help="price per frame left uncovered (default: no gaps)")
     ap.add_argument("--gap-fill", choices=("silence", "target"), default="silence", help="what a gap sounds like")
+    ap.add_argument("--follow", action="store_true", help="the output takes the target's loudness (envelope following)")
+    ap.add_argument("--max-gain", type=float, default=8.0, help="with --follow: the greatest gain")
     args = ap.parse_args(argv)
+    follow = dict(dynamics="target", max_gain=args.max_gain) if args.follow else {}
 
     engine = Engine(metric="dtw", dtype="f64")
     if os.path.isdir(args.d):
@@ -51,7 +57,7 @@ def main(argv=None):
     target = Sound.from_path(args.s, engine=engine)
 
     cover, samples, pcm = dictionary.reconstruct_covered(target, args.penalty, search=args.search, want_pcm32=True,
-                                                         gap_cost=args.gap_cost, gap_fill=args.gap_fill)
+                                                         gap_cost=args.gap_cost, gap_fill=args.gap_fill, **follow)
     for p in cover.pieces:
         if p.is_gap:
             print(f"{'(gap)':>16}  frames {p.start_frame:6d} ... {p.end_frame:6d}  ({p.num_frames():3d} left uncovered)      "

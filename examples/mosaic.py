@@ -2,7 +2,7 @@
 """examples/mosaic.py -- concatenative resynthesis from uncut recordings: neither side is cut beforehand.
 
     python examples/mosaic.py -s TARGET.wav -d REC.wav|DIR -o OUT.wav [--penalty 1.0] [--gap-cost X] [--gap-fill silence|target]
-                              [--search 256]
+                              [--search 256] [--follow [--max-gain 8]]
 
 The dictionary is one recording or a folder of recordings, each taken whole, of any length.  SoundDictionary.
 reconstruct_mosaic tiles the target with free spans of the recordings -- cuts, recordings, spans and paced paths chosen
@@ -12,6 +12,8 @@ pieces; at 0 the optimum is frame-wise and stretched spans come back in fragment
 frames stay uncovered at X each: they come back as silence, or as the target's own samples with --gap-fill target.
 --search N (at most 512 samples) resynthesises with the waveform-similarity search.  One line per piece:
 [t0-t1] <- recording r [s0-s1] cost/frame.
+--follow sends the output through the envelope follower (ssym_follow_envelope): hop by hop it takes the loudness of the
+target, no gain above --max-gain (default 8); without the flag the output file is what it was.
 """
 import argparse
 import os
@@ -32,7 +34,10 @@ def main(argv=None):
     ap.add_argument("--gap-cost", type=float, default=None, help="price per frame left uncovered (default: no gaps)")
     ap.add_argument("--gap-fill", choices=("silence", "target"), default="silence", help="what a gap sounds like")
     ap.add_argument("--search", type=int, default=256, help="WSOLA search width in samples (0: plain overlap-add)")
+    ap.add_argument("--follow", action="store_true", help="the output takes the target's loudness (envelope following)")
+    ap.add_argument("--max-gain", type=float, default=8.0, help="with --follow: the greatest gain")
     args = ap.parse_args(argv)
+    follow = dict(dynamics="target", max_gain=args.max_gain) if args.follow else {}
 
     engine = Engine(metric="dtw", dtype="f64")
     if os.path.isdir(args.d):
@@ -44,7 +49,7 @@ def main(argv=None):
     target = Sound.from_path(args.s, engine=engine)
 
     mosaic, samples, pcm = dictionary.reconstruct_mosaic(target, args.penalty, args.gap_cost, args.gap_fill, args.search,
-                                                         want_pcm32=True)
+                                                         want_pcm32=True, **follow)
     for p in mosaic.pieces:
         if p.is_gap:
             print(f"[{p.start_frame:6d}-{p.end_frame:6d}] <- (gap, {p.num_frames()} frames left uncovered)  "

@@ -2,6 +2,7 @@
 """examples/spot.py -- a reconstruction from recordings that were never cut.
 
     python examples/spot.py -s TARGET.wav -d DICT.wav|DIR -o OUT.wav [--paced] [--search 0] [--depth 5] [--threshold 4] [--seed 0]
+                            [--follow [--max-gain 8]]
 
 The target is cut by a Partitioner as examples/warp.py cuts it (trained on the first dictionary recording); the dictionary
 recordings stay whole.  Every target segment is located inside the recordings by subsequence DTW
@@ -15,6 +16,8 @@ normalised by any length.
 target frame takes one source frame, at most one source frame in a row is skipped or repeated.  The span of a segment then
 has about half to twice its frames, the alignment of the span has the cost the spot reported, and cost / frames is a
 mean per-frame distance: it is printed per segment, and its mean over the segments at the end.
+--follow sends the output through the envelope follower (ssym_follow_envelope): hop by hop it takes the loudness of the
+target, no gain above --max-gain (default 8); without the flag the output file is what it was.
 """
 import argparse
 import os
@@ -38,7 +41,10 @@ def main(argv=None):
     ap.add_argument("--depth", type=int, default=5)
     ap.add_argument("--threshold", type=int, default=4)
     ap.add_argument("--seed", type=int, default=0, help="draws the mixture's starting frames")
+    ap.add_argument("--follow", action="store_true", help="the output takes the target's loudness (envelope following)")
+    ap.add_argument("--max-gain", type=float, default=8.0, help="with --follow: the greatest gain")
     args = ap.parse_args(argv)
+    follow = dict(dynamics="target", max_gain=args.max_gain) if args.follow else {}
 
     engine = Engine(metric="dtw", dtype="f64")
     if os.path.isdir(args.d):
@@ -63,7 +69,7 @@ def main(argv=None):
         per_frame = f", per frame {sp.cost_per_frame:.6g}" if args.paced else ""
         print(f"segment {t:4d} ({targets[t].num_frames():3d} frames): {name} frames {sp.start_frame}...{sp.end_frame} "
               f"({sp.num_frames()} frames), cost {sp.cost:.6g}{per_frame}")
-    samples, pcm = dictionary.warp(targets, spans=spots, want_pcm32=True, search=args.search, **step)
+    samples, pcm = dictionary.warp(targets, spans=spots, want_pcm32=True, search=args.search, **step, **follow)
     if args.paced:
         means = [sp.cost_per_frame for sp in spots if sp]
         print(f"mean cost_per_frame over {len(means)} spotted segments: {np.mean(means) if means else float('nan'):.6g}")

@@ -2,6 +2,7 @@
 """examples/warp.py -- a reconstruction whose matches follow the target's timing.
 
     python examples/warp.py -s TARGET.wav -d DICT.wav -o OUT.wav [--plain PLAIN.wav] [--search 0] [--depth 5] [--threshold 4]
+                            [--follow [--max-gain 8]]
                             [--seed 0] [--paced]
 
 Both recordings are cut by a Partitioner trained on the dictionary recording, as examples/reconstruction.py --partition
@@ -16,6 +17,8 @@ move is printed.
 and ssym_dtw_align_step with SSYM_STEP_PACED): every target frame takes one source frame, the match is the segment with the
 least such cost, and no target falls back to the length fit because the symmetric search chose a segment the pattern cannot
 align.  Beside the output it prints how many targets the symmetric search would have handed such a pair.
+--follow sends the output through the envelope follower (ssym_follow_envelope): hop by hop it takes the loudness of the
+target, no gain above --max-gain (default 8); without the flag the output file is what it was.
 """
 import argparse
 import os
@@ -40,7 +43,10 @@ def main(argv=None):
     ap.add_argument("--threshold", type=int, default=4)
     ap.add_argument("--seed", type=int, default=0, help="draws the mixture's starting frames")
     ap.add_argument("--paced", action="store_true", help="match, align and warp under the paced step pattern")
+    ap.add_argument("--follow", action="store_true", help="the output takes the target's loudness (envelope following)")
+    ap.add_argument("--max-gain", type=float, default=8.0, help="with --follow: the greatest gain")
     args = ap.parse_args(argv)
+    follow = dict(dynamics="target", max_gain=args.max_gain) if args.follow else {}
 
     engine = Engine(metric="dtw", dtype="f64")
     partitioner = Partitioner.from_path(args.d, engine=engine).threshold(args.threshold).depth(args.depth)
@@ -59,7 +65,8 @@ def main(argv=None):
               f"{float(np.mean(paced_cost[np.isfinite(paced_cost)])) if np.isfinite(paced_cost).any() else float('nan'):.4f}; "
               f"the symmetric search would have handed {lost} of them a pair with no paced path")
     if args.search:
-        samples, pcm, pos, m_off = dictionary.warp(sequence.sounds(), want_pcm32=True, search=args.search, want_pos=True, **step)
+        samples, pcm, pos, m_off = dictionary.warp(sequence.sounds(), want_pcm32=True, search=args.search, want_pos=True, **step,
+                                                   **follow)
         aligned = dictionary.align(sequence.sounds(), **step)
         moved = frames = 0
         for t, al in enumerate(aligned):
@@ -68,7 +75,7 @@ def main(argv=None):
             frames += nominal.size
         print(f"search {args.search}: {moved} of {frames} frames ({100.0 * moved / max(frames, 1):.1f} %) moved off their nominal place")
     else:
-        samples, pcm = sequence.reconstruct_warped_from_dictionary(dictionary, want_pcm32=True, **step)
+        samples, pcm = sequence.reconstruct_warped_from_dictionary(dictionary, want_pcm32=True, **step, **follow)
     write_wav32(args.o, sample_rate=target.sample_rate(), pcm=pcm)
     print(f"{len(dictionary.sounds)} dictionary segments, {len(sequence.sounds())} target segments, "
           f"{samples.size} samples -> {args.o}")

@@ -21,6 +21,7 @@
 
 #include <algorithm>
 #include <cstdint>
+#include <limits>
 #include <memory>
 #include <optional>
 #include <stdexcept>
@@ -148,6 +149,50 @@ inline void pack_features(const std::vector<ArcSound> &sounds, std::vector<doubl
         flat.insert(flat.end(), m.begin(), m.end());
         off.push_back(off.back() + m.size() / NCOEFFS);
     }
+}
+
+// What a reconstruction does about loudness: None plays every matched span at the level it was recorded at, Target sends
+// the result through follow_envelope against the targets' own samples.
+enum class Dynamics { None, Target };
+
+// Envelope following (ssym_follow_envelope; any context): the reconstructions `samples`, packed by out_offsets, scaled hop
+// by hop to the loudness of the references `ref`, packed by ref_offsets -- a reference shorter than its reconstruction is
+// silent from its end, what it has beyond the reconstruction's length is not used; no gain above max_gain (finite, at
+// least 1).  Returns the samples; gains (nullable) receives g(b) of all targets packed in target order, ceil(n / 256) + 1
+// per target of n > 0 samples.
+inline std::vector<double> follow_envelope(const Context &ctx, const std::vector<double> &samples,
+                                           const std::vector<uint64_t> &out_offsets, const std::vector<double> &ref,
+                                           const std::vector<uint64_t> &ref_offsets, double max_gain = 8.0,
+                                           std::vector<double> *gains = nullptr)
+{
+    if (out_offsets.empty() || ref_offsets.size() != out_offsets.size())
+        throw Error(SSYM_E_INVALID, "follow_envelope: n + 1 out_offsets and n + 1 ref_offsets for n targets");
+    if (samples.size() < out_offsets.back() || ref.size() < ref_offsets.back())
+        throw Error(SSYM_E_INVALID, "follow_envelope: samples or ref hold fewer values than their offsets ask for");
+    const uint32_t n = (uint32_t)(out_offsets.size() - 1);
+    std::vector<double> out(out_offsets.back());
+    if (gains) {
+        std::size_t count = 0;
+        for (uint32_t t = 0; t < n && out_offsets[t + 1] >= out_offsets[t]; ++t)
+            if (const uint64_t len = out_offsets[t + 1] - out_offsets[t])
+                count += (std::size_t)((len + SSYM_MFCC_HOP - 1) / SSYM_MFCC_HOP + 1);
+        gains->assign(count, 0.0);
+    }
+    ctx.check(ssym_follow_envelope(ctx.get(), samples.data(), out_offsets.data(), n, ref.data(), ref_offsets.data(), max_gain, 0,
+                                   out.empty() ? nullptr : out.data(), nullptr,
+                                   gains && !gains->empty() ? gains->data() : nullptr));
+    return out;
+}
+
+// the Dynamics::Target tail of the reconstructing methods: one follow_envelope call against the targets' own samples
+template <class Targets>
+inline std::vector<double> follow_targets(const Context &ctx, std::vector<double> out, const Targets &targets,
+                                          const std::vector<uint64_t> &ooff, double max_gain)
+{
+    std::vector<double> ref;
+    for (const auto &t : targets)
+        ref.insert(ref.end(), t->samples().begin(), t->samples().end());
+    return follow_envelope(ctx, out, ooff, ref, ooff, max_gain);
 }
 
 class SoundDictionary {
@@ -349,9 +394,12 @@ class SoundDictionary {
     // maps pass through the host here; a caller with device buffers hands ssym_dtw_align's SSYM_OUT_DEVICE outputs
     // to ssym_reconstruct_warped with SSYM_WARP_MAP_DEVICE.)  search > 0 (at most 512 samples): ssym_reconstruct_wsola
     // instead -- every source frame may move that far to where it continues the frame before it in phase.
+    // dynamics = Dynamics::Target: the result goes through one follow_envelope call against the targets' own samples
+    // (max_gain as there, checked before anything else); Dynamics::None: the reconstruction as it is, no extra call.
     std::vector<double> warp(const std::vector<ArcSound> &targets, const std::vector<uint32_t> &indices,
-                             uint32_t search = 0) const
+                             uint32_t search = 0, Dynamics dynamics = Dynamics::None, double max_gain = 8.0) const
     {
+        check_max_gain(max_gain);
         if (sounds.empty())
             throw EmptyDictionary();
         if (targets.empty() && indices.empty())
@@ -393,7 +441,13 @@ class SoundDictionary {
                                               frames.data(), len.data(), 0, out.data(), nullptr);
         ssym_samples_destroy(ctx_->get(), smp);
         ctx_->check(rc);
-        return out;
+        return dynamics == Dynamics::Target ? follow_targets(*ctx_, std::move(out), targets, ooff, max_gain) : out;
+    }
+    // max_gain of the reconstructing methods, refused before any device work whether it is used or not
+    static void check_max_gain(double max_gain)
+    {
+        if (!(max_gain >= 1.0) || max_gain > std::numeric_limits<double>::max())
+            throw Error(SSYM_E_INVALID, "max_gain must be finite and at least 1");
     }
     // where inside the dictionary's (unsegmented) recordings every target sounds: subsequence DTW (ssym_spot_queries, or
     // ssym_dtw_spot with indices[t] naming the recording of target t; dtw contexts without a band; the crate has no
@@ -621,10 +675,12 @@ class SoundDictionary {
     // warp with a Spot per target: every span aligned and resynthesised where it lies, the sample window being frame
     // start_frame's first sample up to where frame end_frame + 1 would start, or the recording's end
     // (ssym_dtw_align_spans + ssym_reconstruct_warped_spans, or with search > 0 ssym_reconstruct_wsola_spans).  An empty
-    // Spot gives zeros
+    // Spot gives zeros.  dynamics and max_gain as for warp
     std::vector<double> warp_spans(const std::vector<ArcSound> &targets, const std::vector<Spot> &spots, uint32_t search = 0,
-                                   uint32_t step = SSYM_STEP_SYMMETRIC) const
+                                   uint32_t step = SSYM_STEP_SYMMETRIC, Dynamics dynamics = Dynamics::None,
+                                   double max_gain = 8.0) const
     {
+        check_max_gain(max_gain);
         const std::vector<Alignment> al = align_spans(targets, spots, step);
         if (targets.empty())
             return {};
@@ -662,7 +718,7 @@ class SoundDictionary {
                                                    map.data(), moff.data(), frames.data(), len.data(), 0, out.data(), nullptr);
         ssym_samples_destroy(ctx_->get(), smp);
         ctx_->check(rc);
-        return out;
+        return dynamics == Dynamics::Target ? follow_targets(*ctx_, std::move(out), targets, ooff, max_gain) : out;
     }
     // every place a target sounds: per target its occurrences by ascending cost, pairwise disjoint within a recording
     // (ssym_dtw_spot_all, one call).  With indices, target t is searched in sounds[indices[t]]; without, in every sound:

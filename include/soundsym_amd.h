@@ -893,6 +893,59 @@ SSYM_API int32_t ssym_reconstruct_wsola_spans(ssym_ctx *ctx, const ssym_samples 
                                               const uint32_t *pair_len, uint32_t search, uint32_t flags, uint64_t *out_pos,
                                               double *out_samples, int32_t *out_pcm32);
 
+/* Envelope following (DESIGN.md section 2 "Envelope following" and section 5.28): a post-pass that any reconstruction can go
+ * through, after which it has the loudness of its target.  Every resynthesis above plays a matched span at the level it was
+ * recorded at; this call scales it, hop by hop, to the level of the reference.  Definition.  For target t:
+ *   - y[0..n) is the reconstruction, with n = out_offsets[t+1] - out_offsets[t].
+ *   - x[0..nx) is the reference, the target's own samples, with nx = ref_offsets[t+1] - ref_offsets[t].
+ *   - x[k] reads +0.0 for k >= nx.
+ *   - x[k] for k >= n is never read.
+ *   - w[] is the window table of mfcc_frame.hpp.
+ *   - J = ceil(n / HOP).
+ *   - Target t has B = J + 1 boundaries b = 0...J when n > 0, and none when n = 0.
+ *
+ *   energy  : E_s(b) = sum over m = 0...1023 ascending, from +0.0, of  w[m]*(s[k]*s[k]),  k = (b-2)*HOP + m,
+ *             only the m with 0 <= k < n;  t = s*s; t = w[m]*t; acc = acc + t -- three roundings, no contraction
+ *   gain    : g(b) = sqrt(E_x(b) / E_y(b))   (IEEE division and square root)
+ *             if g(b) is NaN: g(b) = 1.0      (0/0: both silent; or a non-finite sample in a window)
+ *             else if g(b) > max_gain: g(b) = max_gain     (+inf included: a silent reconstruction under a sounding target)
+ *   sample  : j = k / HOP (integer), f = (k - j*HOP) / 256.0 (exact),
+ *             a = g(j)*(1.0 - f);  c = g(j+1)*f;  out[k] = y[k]*(a + c)       -- each product and the sum rounded separately
+ *   pcm     : out_pcm32 = ssym_reconstruct's conversion of out[k]
+ *
+ * The window of boundary b is centred on sample b*HOP.  It is hop-aligned.  Hop j of the output needs g(j) and g(j+1), so
+ * it needs samples below (j+3)*HOP, two hops of look-ahead.  That is stated so that a later live follower can be held to
+ * this call bit for bit.
+ *   samples        out_offsets[n] f64: the reconstructions, packed (HOST, or device with SSYM_FOLLOW_SAMPLES_DEVICE)
+ *   out_offsets    n_targets + 1 u64 (HOST): start at 0, do not decrease
+ *   ref            ref_offsets[n] f64: the references, packed (HOST, or device with SSYM_FOLLOW_REF_DEVICE); may be NULL
+ *                  when ref_offsets[n] = 0
+ *   ref_offsets    n_targets + 1 u64 (HOST): start at 0, do not decrease
+ *   max_gain       the greatest gain, finite and at least 1
+ *   flags          SSYM_FOLLOW_SAMPLES_DEVICE, SSYM_FOLLOW_REF_DEVICE: that input is device memory; SSYM_OUT_DEVICE: the
+ *                  three outputs are device memory
+ *   out_samples    nullable, out_offsets[n] f64.  May be `samples` itself when both are device memory: the gains are
+ *                  complete before any sample is rewritten
+ *   out_pcm32      nullable, out_offsets[n] i32
+ *   out_gain       nullable, the g(b) of all targets packed in target order, sum of B_t f64
+ * No read leaves a target's own [0, n) / [0, nx): no other target's samples, and nothing of x at or beyond n, influence a
+ * target's output.  A NULL ctx; unknown flag bits; a max_gain that is NaN, below 1 or infinite; NULL out_offsets or
+ * ref_offsets with n_targets > 0; offsets that do not start at 0 or that decrease; NULL samples, or NULL ref with
+ * ref_offsets[n] > 0, while out_offsets[n] > 0: SSYM_E_INVALID.  2^31 targets or more; a target of 2^40 samples or more;
+ * more than 2^31 - 1 blocks of 32 boundaries over all targets (a target of n > 0 samples has ceil(n / 256) + 1
+ * boundaries, each target's rounded up to whole blocks): SSYM_E_UNSUPPORTED.  All with a message in ssym_last_error (but for
+ * the NULL ctx), before any device work and with the outputs unwritten, in this order: ctx, flags, max_gain, the number of
+ * targets, NULL offsets, the offsets' start, then target by target its decrease before its length, the blocks, NULL
+ * samples or ref.  Every n_targets below 2^31 is launched: the apply kernel takes the targets 65535 at a time.  n_targets = 0, out_offsets[n] = 0 or all three outputs NULL: SSYM_OK, nothing written.
+ * Any context works, refcos included: nothing here aligns.  One synchronisation per call.  ssym_get_timings: main_ms the
+ * gain kernel, reduce_ms the apply kernel (0 when only out_gain is asked for), total_ms both.  Host inputs are staged in
+ * the scratch ssym_reconstruct uses, so the call may run between ssym_match_begin and ssym_match_finish as that call may. */
+#define SSYM_FOLLOW_SAMPLES_DEVICE 64u
+#define SSYM_FOLLOW_REF_DEVICE 128u
+SSYM_API int32_t ssym_follow_envelope(ssym_ctx *ctx, const double *samples, const uint64_t *out_offsets, uint32_t n_targets,
+                                      const double *ref, const uint64_t *ref_offsets, double max_gain, uint32_t flags,
+                                      double *out_samples, int32_t *out_pcm32, double *out_gain);
+
 /* Feature front-end, the step before the hot path: what
  * Sound::from_samples(.., None, ..) computes through analyze_mfccs (src/sound.rs:215-242) --
  * 1024-sample Hanning windows hopped by 256 (src/lib.rs:24-25), per window `n_coeffs` MFCCs between

@@ -36,6 +36,7 @@ from .api import (  # noqa: F401
     cosine_sim_angular,
     discretize,
     discretize_with_model,
+    follow_envelope,
     length_fit,
     push_sounds,
     train_model,
@@ -46,5 +47,5 @@ __all__ = [
     "ABI_SYMBOLS", "Alignment", "BIN", "Cover", "Coverer", "DeviceFrames", "EmptyDictionaryError", "Engine", "Gap", "Gmm", "HOP", "LIB_PATH", "LiveCover", "LiveMosaic", "Mosaic", "MosaicPiece", "Mosaicker", "NCLUSTERS", "NCOEFFS",
     "Partitioner", "Piece", "Resynth", "Sound", "SoundDictionary", "SoundSequence", "Spot", "SsymError", "analyze_mfccs", "analyze_sounds", "build",
     "cosine_sim_angular", "discretize",
-    "discretize_with_model", "length_fit", "pack_segments", "push_sounds", "Spotter", "Stream", "stream_plan", "train_model", "Watch", "watch",
+    "discretize_with_model", "follow_envelope", "length_fit", "pack_segments", "push_sounds", "Spotter", "Stream", "stream_plan", "train_model", "Watch", "watch",
 ]

@@ -34,6 +34,7 @@ OUT_DEVICE = 1
 DTW_FORCE_EXACT = 2
 DTW_PRUNE = 4
 WARP_MAP_DEVICE = 32       # SSYM_WARP_MAP_DEVICE
+FOLLOW_SAMPLES_DEVICE, FOLLOW_REF_DEVICE = 64, 128      # SSYM_FOLLOW_SAMPLES_DEVICE, SSYM_FOLLOW_REF_DEVICE
 STEP_SYMMETRIC, STEP_PACED = 0, 1       # SSYM_STEP_SYMMETRIC, SSYM_STEP_PACED
 
 # every symbol include/soundsym_amd.h declares (tests check the library exports all of them)
@@ -73,6 +74,7 @@ ABI_SYMBOLS = [
     "ssym_resynth_flush", "ssym_resynth_counts", "ssym_resynth_reset",
     "ssym_reconstruct_warped", "ssym_reconstruct_wsola",
     "ssym_dtw_align_spans_sizes", "ssym_dtw_align_spans", "ssym_reconstruct_warped_spans", "ssym_reconstruct_wsola_spans",
+    "ssym_follow_envelope",
 ]
 COMM_ID_BYTES = 128        # SSYM_COMM_ID_BYTES
 
@@ -310,6 +312,8 @@ def lib() -> ctypes.CDLL:
     L.ssym_reconstruct_warped_spans.argtypes = [vp, vp, vp, vp, vp, vp, u32, vp, vp, vp, vp, u32, vp, vp]
     L.ssym_reconstruct_wsola_spans.restype = i32
     L.ssym_reconstruct_wsola_spans.argtypes = [vp, vp, vp, vp, vp, vp, u32, vp, vp, vp, vp, u32, u32, vp, vp, vp]
+    L.ssym_follow_envelope.restype = i32
+    L.ssym_follow_envelope.argtypes = [vp, vp, vp, u32, vp, vp, f64, u32, vp, vp, vp]
     L.ssym_comm_unique_id.restype = i32
     L.ssym_comm_unique_id.argtypes = [vp]
     L.ssym_comm_create.restype = i32

@@ -27,7 +27,7 @@ from typing import List, Optional, Sequence
 import numpy as np
 
 from ._native import COVER_GAP, NO_MATCH, SSYM_E_UNSUPPORTED, EmptyDictionaryError, SsymError
-from .engine import Engine, _cover_gap_cost, _cover_penalty, _wsola_search, pack_segments, pitch_lags
+from .engine import FOLLOW_MAX_GAIN, Engine, _cover_gap_cost, _cover_penalty, _wsola_search, follow_dynamics, pack_segments, pitch_lags
 
 NCOEFFS = 12   # src/lib.rs:22
 NCLUSTERS = 26 # src/lib.rs:23
@@ -1116,6 +1116,33 @@ def watch(sounds: Sequence[Sound], targets: Sequence[Sound], max_cost=None, engi
     return Watch(sounds, st, sp, q, frames)
 
 
+def _follow_targets(engine, res, targets, gain, want_pcm32: bool):
+    """The dynamics="target" tail of the reconstructing methods.  res is what the method would have returned from its
+    synthesis: the samples, or a tuple that starts with them (then their 32-bit conversion with want_pcm32, then whatever
+    else).  The samples go through ONE Engine.follow_envelope call against the targets' own samples, target by target;
+    the samples and the conversion are replaced by that call's, everything else stays."""
+    parts = res if isinstance(res, tuple) else (res,)
+    ref = [np.asarray(t.samples(), dtype=np.float64).reshape(-1) for t in targets]
+    off = np.concatenate([[0], np.cumsum([r.size for r in ref])]).astype(np.uint64)
+    out = engine.follow_envelope(parts[0], off, np.concatenate(ref) if ref else np.zeros(0), off, gain, want_pcm32)
+    out = out if isinstance(out, tuple) else (out,)
+    new = out + tuple(parts[len(out):])
+    return new if isinstance(res, tuple) else new[0]
+
+
+def follow_envelope(sound: Sound, reference: Sound, max_gain: float = FOLLOW_MAX_GAIN, engine: Optional[Engine] = None) -> Sound:
+    """`sound` with the loudness of `reference`, hop by hop (ssym_follow_envelope; definition in include/soundsym_amd.h):
+    a new Sound of sound's length, rate and name whose features are analysed when they are asked for.  Where the
+    reference is shorter it counts as silent; what it has beyond sound's length is not used.  max_gain: the greatest
+    gain, finite and at least 1."""
+    gain = follow_dynamics("target", max_gain)
+    if not isinstance(sound, Sound) or not isinstance(reference, Sound):
+        raise ValueError("follow_envelope takes two Sounds")
+    y, x = sound.samples(), reference.samples()
+    out = (engine or default_engine()).follow_envelope(y, [0, y.size], x, [0, x.size], gain)
+    return Sound(out, sound.sample_rate(), None, sound.name, sound.ncoeffs)
+
+
 class SoundDictionary:
     """Cache of Sounds searched by similarity (src/sound.rs:290-371)."""
 
@@ -1341,7 +1368,8 @@ class SoundDictionary:
         return [Alignment(cost[t], paths[t], maps[t], int(indices[t])) for t in range(len(targets))]
 
     def warp(self, targets: Sequence[Sound], indices=None, want_pcm32: bool = False, search: int = 0,
-             want_pos: bool = False, step: str = "symmetric", match_step=None, spans=None, context: bool = False):
+             want_pos: bool = False, step: str = "symmetric", match_step=None, spans=None, context: bool = False,
+             dynamics=None, max_gain: float = FOLLOW_MAX_GAIN):
         """The reconstruction of the targets with every match warped onto its target's timing (dtw engines): match
         (unless indices[t] names the dictionary sound of target t), align with the outputs left on the device, and
         resynthesise along the maps -- ssym_match_queries, ssym_dtw_align, ssym_reconstruct_warped; the maps never
@@ -1359,8 +1387,11 @@ class SoundDictionary:
         the samples of spot.sample_span()): the results of cut(spots).warp(targets, indices=arange) bit for bit, zeros for an
         empty Spot, with no second dictionary and no second sample store.  context=True (with spans) lets every window run
         on to the end of its recording: look-ahead taps and WSOLA candidates past the span's end then read the
-        recording's real continuation instead of dropping out; nothing else changes."""
+        recording's real continuation instead of dropping out; nothing else changes.  dynamics="target": what the call
+        would have returned goes through one Engine.follow_envelope call against the targets' own samples, so every
+        stretch takes its target's loudness, no gain above max_gain (None: this method as it was, no extra call)."""
         _spot_step(step)
+        gain = follow_dynamics(dynamics, max_gain)
         targets = list(targets)
         span_args = None
         if spans is not None:
@@ -1390,16 +1421,19 @@ class SoundDictionary:
         q = self.engine.queries(flat, off, self._dim())
         try:
             if span_args is not None:
-                return self._warp_spans(q, span_args, out_off, step, search, want_pcm32, want_pos)
+                res = self._warp_spans(q, span_args, out_off, step, search, want_pcm32, want_pos)
+                return res if gain is None else _follow_targets(self.engine, res, targets, gain, want_pcm32)
             if indices is None:
                 indices, _ = self.engine.match(self.resident(), q, **match_kw)
             _, lengths, _, maps, _, m_off = self.engine.dtw_align_device(self.resident(), q, indices, **_step_kw(step))
             if not search:
-                return self.engine.reconstruct_warped(self.resident_samples(), indices, out_off, maps, m_off,
-                                                      np.diff(m_off.astype(np.int64)), lengths, want_pcm32)
+                res = self.engine.reconstruct_warped(self.resident_samples(), indices, out_off, maps, m_off,
+                                                     np.diff(m_off.astype(np.int64)), lengths, want_pcm32)
+                return res if gain is None else _follow_targets(self.engine, res, targets, gain, want_pcm32)
             res = self.engine.reconstruct_wsola(self.resident_samples(), indices, out_off, maps, m_off,
                                                 np.diff(m_off.astype(np.int64)), lengths, search, want_pcm32, want_pos)
-            return res + (m_off,) if want_pos else res
+            res = res + (m_off,) if want_pos else res
+            return res if gain is None else _follow_targets(self.engine, res, targets, gain, want_pcm32)
         finally:
             q.close()
 
@@ -1417,13 +1451,14 @@ class SoundDictionary:
         return res + (m_off,) if want_pos else res
 
     def reconstruct_spotted(self, targets: Sequence[Sound], step: str = "symmetric", search: int = 0,
-                            want_pcm32: bool = False):
+                            want_pcm32: bool = False, dynamics=None, max_gain: float = FOLLOW_MAX_GAIN):
         """spot, then warp(spans=) on one upload of the targets: every target is located in the dictionary's recordings
         (ssym_spot_queries), its span aligned with the outputs left on the device (ssym_dtw_align_spans) and
         resynthesised from the resident samples (ssym_reconstruct_warped_spans, or with search > 0
         ssym_reconstruct_wsola_spans) -- three library calls, one query set, no cut.  Returns (spots, samples), with
-        want_pcm32 (spots, samples, pcm)."""
+        want_pcm32 (spots, samples, pcm).  dynamics and max_gain as for warp."""
         _spot_step(step)
+        gain = follow_dynamics(dynamics, max_gain)
         if not self.sounds:
             raise EmptyDictionaryError(-2, "empty dictionary")
         if getattr(self.engine, "metric", None) != "dtw":
@@ -1444,6 +1479,8 @@ class SoundDictionary:
                                    want_pcm32, False)
         finally:
             q.close()
+        if gain is not None:
+            res = _follow_targets(self.engine, res, targets, gain, want_pcm32)
         return (spots,) + (res if isinstance(res, tuple) else (res,))
 
     def cover(self, targets: Sequence[Sound], piece_penalty: float = 0.0, gap_cost=None) -> List["Cover"]:
@@ -1503,7 +1540,8 @@ class SoundDictionary:
         return _mosaics(off, *arrays)
 
     def reconstruct_mosaic(self, target: Sound, piece_penalty: float = 0.0, gap_cost=None, gap_fill: str = "silence",
-                           search: int = 0, want_pcm32: bool = False, mosaic: Optional["Mosaic"] = None):
+                           search: int = 0, want_pcm32: bool = False, mosaic: Optional["Mosaic"] = None, dynamics=None,
+                           max_gain: float = FOLLOW_MAX_GAIN):
         """mosaic, then warp: every sounding piece of the target's Mosaic is resynthesised from its span of its recording
         along its frame_map, in ONE call of the existing window reconstruction (ssym_reconstruct_warped_spans, or with
         search > 0 ssym_reconstruct_wsola_spans): the window is the piece's source_sample_span, the map frame_map -
@@ -1512,8 +1550,11 @@ class SoundDictionary:
         (mosaic, samples), with want_pcm32 (mosaic, samples, pcm); the samples are len(target.samples()); a target
         without a mosaic gives silence.  mosaic (default None: computed here): a Mosaic of the target made elsewhere --
         by mosaic_long, or a LiveMosaic's mosaics() -- is resynthesised as it is; piece_penalty and gap_cost are then not
-        used."""
+        used.  dynamics="target": the spliced samples, gaps included, go through one Engine.follow_envelope call against
+        the target's samples (max_gain as there), so the pieces take the target's loudness and a gap_fill="target" stretch
+        meets a gain of 1 from two hops inside its ends; None: this method as it was."""
         penalty, gap = _cover_penalty(piece_penalty), _cover_gap_cost(gap_cost)
+        gain = follow_dynamics(dynamics, max_gain)
         search = _wsola_search(search)
         if gap_fill not in ("silence", "target"):
             raise ValueError('gap_fill must be "silence" or "target"')
@@ -1556,6 +1597,8 @@ class SoundDictionary:
                         x = np.nan_to_num(2147483647.0 * smp[at:at + n], nan=0.0)
                         outs[1][at:at + n] = np.trunc(np.clip(x, -2147483648.0, 2147483647.0)).astype(np.int64).astype(np.int32)
             at += n
+        if gain is not None:
+            outs = _follow_targets(self.engine, tuple(outs), [target], gain, want_pcm32)
         return (mosaic,) + tuple(outs)
 
     def _cover_checks(self, piece_penalty, what: str) -> float:
@@ -1684,7 +1727,7 @@ class SoundDictionary:
         return Cover(_cover_tiles(*zip(*raw)) if raw else [], total, frames) if np.isfinite(total) else Cover.none(frames)
 
     def reconstruct_covered(self, target: Sound, piece_penalty: float = 0.0, search: int = 0, want_pcm32: bool = False,
-                            gap_cost=None, gap_fill: str = "silence"):
+                            gap_cost=None, gap_fill: str = "silence", dynamics=None, max_gain: float = FOLLOW_MAX_GAIN):
         """cover, cut, warp: the target is covered (ssym_dtw_cover), cut at the pieces (samples by
         Cover.segment_lengths, MFCC rows start_frame ... end_frame) and every piece warped from its sound under the paced
         pattern -- self.warp(pieces, indices=cover.indices(), step="paced", search=search), the existing calls.  Returns
@@ -1693,8 +1736,11 @@ class SoundDictionary:
         gap_cost as for `cover`.  The sounding pieces then go through warp exactly as above, and every Gap's stretch of
         samples (its entry of Cover.segment_lengths: Gap.sample_span, a gap that ends the target running to the sound's last
         sample) is spliced in between them as zeros (gap_fill="silence") or as the target's own samples ("target"; their
-        32-bit conversion is warp's: truncated, saturated, NaN as 0)."""
+        32-bit conversion is warp's: truncated, saturated, NaN as 0).  dynamics="target": the samples, after the splice,
+        go through one Engine.follow_envelope call against the whole target's samples (max_gain as there); None: this
+        method as it was."""
         penalty, gap = _cover_penalty(piece_penalty), _cover_gap_cost(gap_cost)
+        gain = follow_dynamics(dynamics, max_gain)
         search = _wsola_search(search)
         if gap_fill not in ("silence", "target"):
             raise ValueError('gap_fill must be "silence" or "target"')
@@ -1707,6 +1753,8 @@ class SoundDictionary:
             res = self.warp(_cover_sounds(target, cover), cover.indices(), want_pcm32, search, step="paced")
         else:
             res = self._splice_gaps(target, cover, gap_fill, want_pcm32, search)
+        if gain is not None:
+            res = _follow_targets(self.engine, res, [target], gain, want_pcm32)
         return (cover,) + (res if isinstance(res, tuple) else (res,))
 
     def _splice_gaps(self, target: Sound, cover: "Cover", gap_fill: str, want_pcm32: bool, search: int):
@@ -2005,35 +2053,42 @@ class SoundSequence:
             return []
         return dict_.spot_all(self._sounds, max_spots=max_spots, max_cost=max_cost, **_step_kw(step, max_cost_per_frame))
 
-    def reconstruct_from_dictionary(self, dict_: "SoundDictionary", want_pcm32: bool = False):
+    def reconstruct_from_dictionary(self, dict_: "SoundDictionary", want_pcm32: bool = False, dynamics=None,
+                                    max_gain: float = FOLLOW_MAX_GAIN):
         """clone_from_dictionary(dict).to_sound().samples() in one go (src/sound.rs:451-480): match
         on the GPU, then gather / length-fit / concatenate on the GPU (ssym_reconstruct), optionally
-        with write_file's 32-bit conversion (:139)."""
+        with write_file's 32-bit conversion (:139).  dynamics="target": the result goes through one
+        Engine.follow_envelope call against this sequence's sounds (max_gain as there); None: this method as it was."""
+        gain = follow_dynamics(dynamics, max_gain)
         if not self._sounds:
             return (np.zeros(0), np.zeros(0, dtype=np.int32)) if want_pcm32 else np.zeros(0)
         idx, _ = dict_.match_indices(self._sounds, None)
         lens = np.array([s.samples().size for s in self._sounds], dtype=np.uint64)
         out_off = np.concatenate([[0], np.cumsum(lens)]).astype(np.uint64)
-        return dict_.engine.reconstruct(dict_.resident_samples(), idx, out_off, want_pcm32)
+        res = dict_.engine.reconstruct(dict_.resident_samples(), idx, out_off, want_pcm32)
+        return res if gain is None else _follow_targets(dict_.engine, res, self._sounds, gain, want_pcm32)
 
     def reconstruct_warped_from_dictionary(self, dict_: "SoundDictionary", want_pcm32: bool = False, search: int = 0,
-                                           step: str = "symmetric", match_step=None):
+                                           step: str = "symmetric", match_step=None, dynamics=None,
+                                           max_gain: float = FOLLOW_MAX_GAIN):
         """reconstruct_from_dictionary with every match warped onto its target's timing instead of cut off or padded
         (SoundDictionary.warp: match, align, resynthesise along the alignment, all on the GPU; dtw engines).
         search > 0: with the waveform-similarity search of that width in samples (at most 512).  step and match_step as
-        for SoundDictionary.warp."""
+        for SoundDictionary.warp, dynamics and max_gain too."""
         search = _wsola_search(search)
+        follow_kw = {} if follow_dynamics(dynamics, max_gain) is None else {"dynamics": dynamics, "max_gain": max_gain}
         _spot_step(step)
         match_kw = {} if match_step is None else {"match_step": match_step}
         _match_kw(step, match_step)
         if not self._sounds:
             return (np.zeros(0), np.zeros(0, dtype=np.int32)) if want_pcm32 else np.zeros(0)
-        return dict_.warp(self._sounds, None, want_pcm32, search, **_step_kw(step), **match_kw)
+        return dict_.warp(self._sounds, None, want_pcm32, search, **_step_kw(step), **match_kw, **follow_kw)
 
     def reconstruct_spotted_from_dictionary(self, dict_: "SoundDictionary", step: str = "symmetric", search: int = 0,
-                                            want_pcm32: bool = False):
-        """dict_.reconstruct_spotted of this sequence's sounds: (spots, samples[, pcm])."""
-        return dict_.reconstruct_spotted(self._sounds, step, search, want_pcm32)
+                                            want_pcm32: bool = False, dynamics=None, max_gain: float = FOLLOW_MAX_GAIN):
+        """dict_.reconstruct_spotted of this sequence's sounds: (spots, samples[, pcm]).  dynamics and max_gain as there."""
+        follow_kw = {} if follow_dynamics(dynamics, max_gain) is None else {"dynamics": dynamics, "max_gain": max_gain}
+        return dict_.reconstruct_spotted(self._sounds, step, search, want_pcm32, **follow_kw)
 
     def to_sound(self) -> Sound:                                        # src/sound.rs:475-483
         parts = [s.samples() for s in self._sounds]

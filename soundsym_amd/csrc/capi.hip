@@ -685,4 +685,14 @@ int32_t ssym_merge_shards(ssym_ctx *ctx, uint32_t n_shards, uint32_t n_targets, 
     });
 }
 
+int32_t ssym_follow_envelope(ssym_ctx *ctx, const double *samples, const uint64_t *out_offsets, uint32_t n_targets,
+                             const double *ref, const uint64_t *ref_offsets, double max_gain, uint32_t flags,
+                             double *out_samples, int32_t *out_pcm32, double *out_gain)
+{
+    return guarded(ctx, [&]() -> int32_t {
+    return follow_envelope(ctx, samples, out_offsets, n_targets, ref, ref_offsets, max_gain, flags, out_samples, out_pcm32,
+                           out_gain);
+    });
+}
+
 }  // extern "C"

@@ -471,6 +471,11 @@ struct CoverTables {
 int32_t cover_forward(ssym_ctx *ctx, const SegmentSet &src, const double *tgtRaw, const uint64_t *tgtOff, const uint64_t *hTgtOff,
                       uint32_t nTgt, uint64_t extraF64, uint64_t extraU32, CoverTables *out);
 
+// follow.hip: ssym_follow_envelope's body (capi.hip holds the entry point)
+int32_t follow_envelope(ssym_ctx *ctx, const double *samples, const uint64_t *out_offsets, uint32_t n_targets, const double *ref,
+                        const uint64_t *ref_offsets, double max_gain, uint32_t flags, double *out_samples, int32_t *out_pcm32,
+                        double *out_gain);
+
 // chain.hip
 int32_t launch_chain_argmin(ssym_ctx *ctx, const double *base, size_t row_stride, const uint32_t *row_sel,
                             uint32_t n, double distance, double init, bool report_value, uint32_t step,

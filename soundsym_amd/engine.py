@@ -181,6 +181,58 @@ def _warp_inputs(idx, out_offsets, maps, map_offsets, map_frames, pair_len):
     return idx, off, m_off, frames, map_ptr, len_ptr, device, keep
 
 
+FOLLOW_MAX_GAIN = 8.0
+
+
+def _follow_max_gain(max_gain) -> float:
+    """max_gain of follow_envelope as a float, checked before the library is asked: finite and at least 1."""
+    try:
+        gain = float(max_gain)
+    except (TypeError, ValueError):
+        raise ValueError("max_gain must be a number") from None
+    if not 1.0 <= gain < float("inf"):
+        raise ValueError("max_gain must be finite and at least 1")
+    return gain
+
+
+def follow_dynamics(dynamics, max_gain):
+    """The dynamics= / max_gain= keywords of the reconstructing methods, checked before any device work: None (the method as
+    it was) or the checked max_gain of dynamics="target"."""
+    if dynamics is not None and dynamics != "target":
+        raise ValueError('dynamics must be None or "target"')
+    gain = _follow_max_gain(max_gain)
+    return gain if dynamics == "target" else None
+
+
+def _follow_samples(x, need: int, what: str):
+    """(pointer, device?, what to keep alive) of follow_envelope's samples or ref: a numpy array, or f64 device memory (a
+    contiguous torch CUDA tensor, a DeviceFrames-style pointer) of at least `need` values."""
+    if _is_device_tensor(x):
+        size = getattr(x, "element_size", None)
+        if callable(size) and size() != 8 or "float64" not in str(getattr(x, "dtype", "float64")):
+            raise ValueError(f"follow_envelope: {what} in device memory must be float64")
+        contiguous = getattr(x, "is_contiguous", None)
+        if callable(contiguous) and not contiguous():
+            raise ValueError(f"follow_envelope: the device tensor {what} must be contiguous")
+        have = int(x.numel())
+        ptr = int(x.data_ptr()) if have else None
+        keep, device = x, True
+    else:
+        keep = np.ascontiguousarray(x if x is not None else [], dtype=np.float64).reshape(-1)
+        have, ptr, device = keep.size, (keep.ctypes.data if keep.size else None), False
+    if have < need:
+        raise ValueError(f"follow_envelope: {what} holds {have} values, its offsets ask for {need}")
+    return ptr, device, keep
+
+
+def follow_boundaries(out_offsets) -> np.ndarray:
+    """Offsets of the targets' gains in follow_envelope's packed gain array: n + 1 int64, target t has ceil(n_t / HOP) + 1
+    boundaries when it has samples and none when it has not."""
+    off = np.asarray(out_offsets, dtype=np.uint64).astype(np.int64)
+    n = off[1:] - off[:-1]
+    return np.concatenate([[0], np.cumsum(np.where(n > 0, (n + nat.MFCC_HOP - 1) // nat.MFCC_HOP + 1, 0))]).astype(np.int64)
+
+
 WSOLA_MAX_SEARCH = 512
 
 
@@ -1640,6 +1692,36 @@ class Engine:
         out, pcm, pos = _warp_call(self, "reconstruct_wsola", smp, idx, out_offsets, maps, map_offsets, map_frames, pair_len,
                                    search, want_pcm32, want_pos, windows)
         res = (out,) + ((pcm,) if want_pcm32 else ()) + ((pos,) if want_pos else ())
+        return res if len(res) > 1 else out
+
+    def follow_envelope(self, samples, out_offsets, ref, ref_offsets, max_gain=FOLLOW_MAX_GAIN, want_pcm32: bool = False,
+                        want_gains: bool = False, on_device: bool = False):
+        """ssym_follow_envelope: reconstructions scaled hop by hop to the loudness of their references (definition in
+        include/soundsym_amd.h).  samples: the reconstructions packed by out_offsets; ref: the targets' own samples packed
+        by ref_offsets; each a numpy array or f64 device memory (a torch CUDA tensor), as reconstruct_warped accepts maps.
+        max_gain: the greatest gain, finite and at least 1.  Returns the samples, with want_pcm32 also their 32-bit
+        conversion, with want_gains also the gains g(b) of all targets packed in target order (follow_boundaries gives
+        their offsets); numpy arrays, or with on_device torch tensors on the engine's GPU.  Any engine, refcos included."""
+        gain = _follow_max_gain(max_gain)
+        off = np.ascontiguousarray(out_offsets, dtype=np.uint64).reshape(-1)
+        r_off = np.ascontiguousarray(ref_offsets, dtype=np.uint64).reshape(-1)
+        if off.size < 1 or r_off.size != off.size:
+            raise ValueError("follow_envelope: n + 1 out_offsets and n + 1 ref_offsets for n targets")
+        if off[0] != 0 or r_off[0] != 0 or np.any(off[1:] < off[:-1]) or np.any(r_off[1:] < r_off[:-1]):
+            raise ValueError("follow_envelope: out_offsets and ref_offsets must start at 0 and not decrease")
+        total, n_gains = int(off[-1]), int(follow_boundaries(off)[-1])
+        y_ptr, y_dev, keep_y = _follow_samples(samples, total, "samples")
+        x_ptr, x_dev, keep_x = _follow_samples(ref, int(r_off[-1]), "ref")
+        device = self.device if on_device else None
+        (out, p_out), (pcm, p_pcm), (gains, p_gains) = (_output(device, (rows,), t) for rows, t in (
+            (total, np.float64), (total if want_pcm32 else 0, np.int32), (n_gains if want_gains else 0, np.float64)))
+        flags = ((nat.FOLLOW_SAMPLES_DEVICE if y_dev else 0) | (nat.FOLLOW_REF_DEVICE if x_dev else 0)
+                 | (nat.OUT_DEVICE if on_device else 0))
+        nat.check(nat.lib().ssym_follow_envelope(self.ctx, y_ptr, off.ctypes.data, off.size - 1, x_ptr, r_off.ctypes.data, gain,
+                                                 flags, p_out if total else None, p_pcm if want_pcm32 and total else None,
+                                                 p_gains if want_gains and n_gains else None), self.ctx)
+        del keep_y, keep_x
+        res = (out,) + ((pcm,) if want_pcm32 else ()) + ((gains,) if want_gains else ())
         return res if len(res) > 1 else out
 
     def merge_shards(self, costs, idx, out_idx, out_cost, distance=None) -> None:
