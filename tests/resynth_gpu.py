@@ -1,9 +1,11 @@
 """What the GPU tests of the resynthesiser share -- TEST INFRASTRUCTURE: a resynthesiser with one restatement lane
-(tests/live_resynth_ref.py) per lane, every call made on both and compared bit for bit, samples and pcm."""
+(tests/live_resynth_ref.py) per lane, every call made on both and compared bit for bit, samples and pcm (Live); the same
+over the linear oracle of tests/resynth_slices.py, for many lanes and long tiles (SlicedLive)."""
 import numpy as np
 
 import live_resynth_ref as ref
 from live_resynth_ref import GAP, HOP, NO_MATCH
+from resynth_slices import SlicedLane
 from warp_ref import pcm32
 
 G = (GAP, NO_MATCH, 1)
@@ -77,6 +79,74 @@ class Live:
         self.rs.reset(lane)
         self.refs[lane] = ref.LiveResynth(self.sounds, self.search, None, self.cache)
         self.rows[lane], self.out[lane] = [], []
+
+    def held(self, lane):
+        return self.refs[lane].held
+
+    def close(self):
+        self.rs.close()
+
+
+class SlicedLive:
+    """A resynthesiser and the linear oracle (tests/resynth_slices.py), for many lanes and long tiles: lanes {lane: (rows,
+    total_samples)} is what each lane will consume and end with, so a call names only how many rows each lane takes.  Every
+    call is compared bit for bit, samples and pcm, with its count, the lane offsets and counts(); a flush compares the lane's
+    concatenation since its reset with `offline`.  Only the lanes of a call are walked in Python: the others are held to empty
+    stretches by the offsets, so 65535 lanes cost no more than five."""
+
+    def __init__(self, engine, store, sounds, n_lanes, search, lanes, cache=None):
+        self.sounds, self.n_lanes, self.search, self.cache = sounds, n_lanes, search, cache
+        self.rs = engine.resynth(store, n_lanes, search)
+        self.refs = {l: SlicedLane(sounds, rows, total, search, cache) for l, (rows, total) in lanes.items()}
+        self.out = {l: [] for l in lanes}
+        self.frames, self.samples = np.zeros(n_lanes, dtype=np.uint64), np.zeros(n_lanes, dtype=np.uint64)
+        self.calls = []                              # per call {lane: (room, hops released)}: what the hop list held
+
+    def _compare(self, n, want, what):
+        sizes = np.zeros(self.n_lanes, dtype=np.uint64)
+        for l, w in want.items():
+            sizes[l] = w.size
+        want_off = np.concatenate([[0], np.cumsum(sizes)]).astype(np.uint64)
+        off, smp, pcm = self.rs.samples(want_pcm32=True)
+        assert n == self.rs.n_samples == smp.size == pcm.size == int(want_off[-1]), (what, n, int(want_off[-1]))
+        assert np.array_equal(off, want_off), what
+        for l in sorted(want):
+            a, b = int(off[l]), int(off[l + 1])
+            same(smp[a:b], want[l], "%s, lane %d" % (what, l))
+            assert np.array_equal(pcm[a:b], pcm32(want[l])), (what, l)
+            self.out[l].append(want[l])
+        self.samples += sizes
+        frames, released = self.rs.counts()
+        assert np.array_equal(frames, self.frames) and np.array_equal(released, self.samples), what
+
+    def push(self, take, what="push"):
+        """take {lane: rows to consume}; a lane with 0 is absent from the arrays, as a lane left out is."""
+        rows = {l: self.refs[l].rows(k) for l, k in take.items() if k}
+        at = {l: self.refs[l].n for l in rows}
+        room = {l: self.refs[l].held + k for l, k in take.items() if k}
+        n = self.rs.push(*columns(rows, at))
+        want = {l: self.refs[l].push(k) for l, k in take.items()}
+        for l, k in take.items():
+            self.frames[l] += k
+        self.calls.append({l: (room[l], want[l].size // HOP) for l in room})
+        self._compare(n, want, what)
+        return n
+
+    def flush(self, lane, total=None):
+        """Flush `lane`; a lane without frames ends with `total` samples."""
+        if lane not in self.refs:
+            self.refs[lane], self.out[lane] = SlicedLane(self.sounds, [], total, self.search, self.cache), []
+        r = self.refs[lane]
+        assert total is None or total == r.total
+        n = self.rs.flush(lane, r.total)
+        self._compare(n, {lane: r.flush()}, "flush of lane %d" % lane)
+        same(np.concatenate(self.out[lane]), r.whole, "lane %d, reset to flush" % lane)
+        return n
+
+    def reset(self, lane, rows, total):
+        self.rs.reset(lane)
+        self.refs[lane], self.out[lane] = SlicedLane(self.sounds, rows, total, self.search, self.cache), []
+        self.frames[lane] = self.samples[lane] = 0
 
     def held(self, lane):
         return self.refs[lane].held
