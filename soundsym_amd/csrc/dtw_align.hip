@@ -224,10 +224,11 @@ __global__ __launch_bounds__(64) void dtw_align_kernel(const AlignArgs a)
 }
 
 // Paced alignment (ssym_dtw_align_step with SSYM_STEP_PACED; DESIGN.md 2 "Paced alignment", 5.19): the path of the paced
-// step pattern between pinned ends.  N, H, E and the arithmetic are dtw_paced_kernel's (dtw_spot.hip); what differs is
+// step pattern between pinned ends.  N, H, E and the arithmetic are the paced cell's (dtw_wave.hpp: SSYM_PACED_PRED,
+// SSYM_PACED_STATES -- the text dtw_paced_kernel runs, so a cost here has a paced spot's bits); what differs is
 // column 0 (N(0,0) = c(0,0), every other row +inf: the path starts at source frame 0) and what a cell leaves behind: no
-// start word, but two bits -- skip (P came from row i - 2) and rep (H < N) -- packed 16 per dword like dtw_align_kernel's
-// codes, in LDS up to dirLdsBytes and in the workgroup's global slab beyond.
+// start word, but one bit per comparison of the cell -- skip (P came from row i - 2) and rep (H < N) -- packed 16 per
+// dword like dtw_align_kernel's codes, in LDS up to dirLdsBytes and in the workgroup's global slab beyond.
 //   forward   dtw_paced_kernel's wavefront: N and E of the previous column per lane, d1 = E(r-1, j-1) and d2 = E(r-2, j-1)
 //             by DPP, two f64 hand-off rows written in place by lanes 63 and 62 (the order argument is the one given there)
 //   backward  lane 0 walks Fb - 1 steps from (Fa-1, Fb-1) with the wanted state in a register: E (the cell's better state:
@@ -306,19 +307,10 @@ __global__ __launch_bounds__(64) void dtw_align_paced_kernel(const AlignArgs a)
                     double nD = r == 0 ? c : INF;         // column 0: the path starts at source frame 0, in state N
                     double eD = nD;
                     if (j > 0) {
-                        double pD = d1;
-                        uint32_t code = 0;
-                        if (d2 < pD) {
-                            pD = d2;
-                            code = 1u;                    // skip
-                        }
-                        nD = __dadd_rn(c, pD);
-                        const double hD = __dadd_rn(c, mineN);
-                        eD = nD;
-                        if (hD < nD) {
-                            eD = hD;
-                            code |= 2u;                   // rep
-                        }
+                        double pD;
+                        uint32_t code = 0;                // the two code bits ride on the cell's two comparisons
+                        SSYM_PACED_PRED(pD, d1, d2, code = 1u)                         // skip
+                        SSYM_PACED_STATES(nD, eD, c, pD, mineN, code |= 2u)           // rep
                         pack |= code << (2 * (j & 15));
                     }
                     if ((j & 15) == 15 || j == Fb - 1) {

@@ -159,14 +159,9 @@ __global__ __launch_bounds__(kCoverMaxStarts) void cover_forward_kernel(const Co
                         for (uint32_t i = Fa; i-- > 0;) {
                             const double e2 = i >= 2 ? E[(size_t)(i - 2) * S + tid] : INF;  // E(i-2, j-1)
                             const double c = C[(size_t)i * W + tid + jj];
-                            double pD = e1;
-                            if (e2 < pD)
-                                pD = e2;
-                            const double nD = __dadd_rn(c, pD);
-                            const double hD = __dadd_rn(c, N[(size_t)i * S + tid]);
-                            double eD = nD;
-                            if (hD < nD)
-                                eD = hD;
+                            double pD, nD, eD;            // (a cost alone: nothing rides on the comparisons)
+                            SSYM_PACED_PRED(pD, e1, e2, (void)0)
+                            SSYM_PACED_STATES(nD, eD, c, pD, N[(size_t)i * S + tid], (void)0)
                             N[(size_t)i * S + tid] = nD;
                             E[(size_t)i * S + tid] = eD;
                             if (i == Fa - 1)

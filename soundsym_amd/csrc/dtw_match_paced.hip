@@ -19,8 +19,9 @@
 //   idx[t] = argmin_s |cost(s,t) - distance[t]|   (distance NULL = 0), the first minimum, the fold starting at (0, +inf):
 //   a NaN or +inf key never wins, out_cost is the winner's cost, a target nothing beats gets 0 + index_base and +inf.
 //
-// Mapping: a cost-only forward pass on dtw_wave.hpp's pieces.  The per-cell recurrence is dtw_align_paced_kernel's (d1 / d2
-// by DPP, two f64 hand-off rows for a source of more than 64 frames); no codes, no slabs, no backward walk.
+// Mapping: a cost-only forward pass on dtw_wave.hpp's pieces.  The cell is the one text dtw_align_paced_kernel runs too
+// (SSYM_PACED_PRED, SSYM_PACED_STATES), on its wavefront (d1 / d2 by DPP, two f64 hand-off rows for a source of more than 64
+// frames); no codes, no slabs, no backward walk.
 //   packing   a wave serves ONE target and several sources at once: consecutive shape-feasible sources of <= 64 frames
 //             lie side by side in the 64 lanes (a 5 ... 40-frame dictionary: 2 - 8 pairs per wave), all reading the same
 //             target ring.  A lane knows its source, its local row r and Fa, and works on column tau - r.  The lane at
@@ -180,14 +181,9 @@ __global__ __launch_bounds__(64) void dtw_match_paced_kernel(const MatchPacedArg
                         double nD = r == 0 ? c : INF;         // column 0: the path starts at source frame 0, in state N
                         double eD = nD;
                         if (j > 0) {
-                            double pD = d1;
-                            if (d2 < pD)
-                                pD = d2;
-                            nD = __dadd_rn(c, pD);
-                            const double hD = __dadd_rn(c, mineN);
-                            eD = nD;
-                            if (hD < nD)
-                                eD = hD;
+                            double pD;                    // (a cost alone: nothing rides on the comparisons)
+                            SSYM_PACED_PRED(pD, d1, d2, (void)0)
+                            SSYM_PACED_STATES(nD, eD, c, pD, mineN, (void)0)
                         }
                         if (longSrc) {
                             if (lane == 63)

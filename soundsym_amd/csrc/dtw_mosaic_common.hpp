@@ -107,26 +107,22 @@ __device__ __forceinline__ double mosaic_column(const MosaicCore &k, const Mosai
     for (uint32_t g = tid; g < G; g += nthr) {
         const uint32_t pc = k.posc[g];
         const double nOld = No[g];
-        double P = INF;
+        // dtw_wave.hpp's paced cell, with the new piece (S) between its two halves; a segment's first frames have no rows above
+        double P = INF, nD, eD;
         uint32_t code = 0;
+        bool rep = false;
         if (pc >= 1)
             P = Eo[g - 1];
         if (pc >= 2) {
-            const double e2 = Eo[g - 2];
-            if (e2 < P) {
-                P = e2;
-                code = 1;
-            }
+            const double e1 = P, e2 = Eo[g - 2];
+            SSYM_PACED_PRED(P, e1, e2, code = 1)
         }
         if (!(P <= S)) {
             P = S;
             code = 2;
         }
         const double c = mosaic_cost(k.srcT + g, G, ring[par], k.dim, k.squared);
-        const double nD = __dadd_rn(c, P);
-        const double hD = __dadd_rn(c, nOld);
-        const bool rep = hD < nD;
-        const double eD = rep ? hD : nD;
+        SSYM_PACED_STATES(nD, eD, c, P, nOld, rep = true)
         En[g] = eD;
         Nn[g] = nD;
         dcol[g] = (uint8_t)(code << 1 | (rep ? 1u : 0u));

@@ -256,6 +256,8 @@ __global__ __launch_bounds__(64) void dtw_spot_kernel(const Args a)
 // step) and H (entered by repeating the source frame), and E, the better of them (strict <: a tie keeps N):
 //   N(i,0) = c(i,0), sN(i,0) = i, H(i,0) = +inf;   j >= 1:  P = E(i-1,j-1), replaced by E(i-2,j-1) if that is < P;
 //   N(i,j) = c(i,j) + P, sN = P's start;   H(i,j) = c(i,j) + N(i,j-1), sH = sN(i,j-1);   outside the matrix +inf.
+// The cell is dtw_wave.hpp's paced cell, the one text of all six kernels of the pattern, taken here as its two macros
+// (SSYM_PACED_PRED, SSYM_PACED_STATES) with the start words handed in as the statements that ride on the comparisons.
 // The end column is E(., Fb-1); end, cost, start and the occurrences are taken from it as dtw_spot_kernel takes them.
 //
 // The wavefront is dtw_spot_kernel's.  What differs: the lane keeps (N, sN) of its previous column beside E; what passes
@@ -347,21 +349,11 @@ __global__ __launch_bounds__(64) void dtw_paced_kernel(const Args a)
                     double nD = c, eD = c;                // column 0: a path may start at any source frame, in state N
                     uint32_t nS = r, eS = r;
                     if (j > 0) {
-                        double pD = d1D;
-                        uint32_t pS = d1S;
-                        if (d2D < pD) {
-                            pD = d2D;
-                            pS = d2S;
-                        }
-                        nD = __dadd_rn(c, pD);
-                        nS = pS;
-                        const double hD = __dadd_rn(c, mineN);
-                        eD = nD;
-                        eS = nS;
-                        if (hD < nD) {
-                            eD = hD;
-                            eS = mineNS;
-                        }
+                        double pD;
+                        uint32_t pS = d1S;                // the start words ride on the cell's two comparisons
+                        SSYM_PACED_PRED(pD, d1D, d2D, pS = d2S)
+                        nS = eS = pS;
+                        SSYM_PACED_STATES(nD, eD, c, pD, mineN, eS = mineNS)
                     }
                     if (lane == 63) {
                         bound1D[j] = eD;

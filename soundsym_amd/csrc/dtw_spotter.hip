@@ -22,7 +22,9 @@
 // Paced watching (ssym_spotter_create_step with SSYM_STEP_PACED; DESIGN.md 2 "Paced watching", 5.20):
 // dtw_watch_paced_kernel is to dtw_paced_kernel what dtw_watch_kernel is to dtw_spot_kernel.  Row i of the paced
 // recurrence needs rows i - 1 and i - 2 of E alone, so the state is TWO hand-off rows per pair (24 bytes per target frame)
-// and the step loop is dtw_paced_kernel's.  The reporting kernels, the log and the slices do not know the step.
+// and the cell is the text dtw_paced_kernel runs (dtw_wave.hpp: SSYM_PACED_PRED, SSYM_PACED_STATES); the step loop is the
+// kernel's own, in the form that allows a row above a short chunk.  The reporting kernels, the log and the slices do not
+// know the step.
 // In-place order of the two LDS rows (bound1 = the row above the chunk, bound2 = the one above that).  A chunk of R rows
 // (R = rowsHere, 1 ... 64; only R = 64 is followed by another chunk) has its bottom row in lane R - 1, which writes
 // bound1[x] at step x + R - 1, and the row above it in lane R - 2, which writes bound2[x] at step x + R - 2; for R = 1
@@ -297,21 +299,11 @@ __global__ __launch_bounds__(64) void dtw_watch_paced_kernel(const WatchPacedArg
                     double nD = c, eD = c;                // column 0: a path may start at any source frame, in state N
                     uint32_t nS = r, eS = r;
                     if (j > 0) {
-                        double pD = d1D;
-                        uint32_t pS = d1S;
-                        if (d2D < pD) {
-                            pD = d2D;
-                            pS = d2S;
-                        }
-                        nD = __dadd_rn(c, pD);
-                        nS = pS;
-                        const double hD = __dadd_rn(c, mineN);
-                        eD = nD;
-                        eS = nS;
-                        if (hD < nD) {
-                            eD = hD;
-                            eS = mineNS;
-                        }
+                        double pD;
+                        uint32_t pS = d1S;                // the start words ride on the cell's two comparisons
+                        SSYM_PACED_PRED(pD, d1D, d2D, pS = d2S)
+                        nS = eS = pS;
+                        SSYM_PACED_STATES(nD, eD, c, pD, mineN, eS = mineNS)
                     }
                     if (rowsHere == 1) {                  // (lane 0) the row that was above becomes the second row above
                         bound2D[j] = in1D;

@@ -1,8 +1,12 @@
 // dtw_wave.hpp -- the anti-diagonal wavefront forward pass dtw_align.hip and dtw_spot.hip share (and the lane - 1 move
 // and ring stride dtw_exact.hip shares with them), each piece written once, plus the host side their drivers and
 // dtw_spotter.hip's share: launch geometry, the pair-list checks and upload, and the spot family's refusals, LDS size and
-// output rule.  Each kernel keeps its own step loop; what is here is what must not differ between them.  (dtw_align_kernel
-// still carries the text of wave_load_frame and wave_refill in its body, for the reason given there: change them together.)
+// output rule.  What is here is what must not differ between the kernels, the paced pattern's cell included
+// (SSYM_PACED_PRED, SSYM_PACED_STATES: one text for the six kernels that run it).
+// Each kernel keeps its own step loop: the symmetric spot cell and its loop stand twice, in dtw_spot_kernel and
+// dtw_watch_kernel, because one shared loop was measured slower than either kernel's own on some shape.
+// (dtw_align_kernel still carries the text of wave_load_frame and wave_refill in its body, for the reason given there:
+// change them together.)
 //
 // The pass: one wave per pair, grid-stride over the list.  Lane l owns source row c0 + l of a 64-row chunk and works on
 // target column j = tau - l at step tau.  D(i-1, j) comes from lane l - 1 by a DPP move, D(i-1, j-1) is what came one step
@@ -108,6 +112,35 @@ __device__ __forceinline__ uint32_t wave_pred(double up, double lf, double dg)
 {
     return (dg <= up && dg <= lf) ? 0u : (up <= lf ? 1u : 2u);
 }
+
+// The paced step pattern's cell, once, for the six kernels that run it: dtw_paced_kernel,
+// dtw_watch_paced_kernel, dtw_align_paced_kernel, dtw_match_paced_kernel, cover_forward_kernel and mosaic_column.  Two
+// pieces, because the mosaic puts a third candidate (a new piece) between them.  What rides on a comparison (a start
+// word, a code bit, a flag) is a statement the caller hands in, run where the comparison holds; (void)0 where nothing does.
+// Macros, because as functions that hand the comparisons back as flags the cell changes what the kernels compile to:
+// dtw_paced_kernel keeps its instruction count and registers, holds the second comparison in another SGPR pair and runs
+// 1 % slower on two of three workloads.  In this shape all six compile to the instructions they had with
+// their own copies.
+// The predecessor: P = d1 = E(i-1, j-1), replaced by d2 = E(i-2, j-1) if that is < d1 (strict: a tie keeps row i - 1, and so
+// does a NaN on either side); ON_SKIP runs where P came from row i - 2
+#define SSYM_PACED_PRED(P, d1, d2, ON_SKIP)                                                                               \
+    P = (d1);                                                                                                             \
+    if ((d2) < P) {                                                                                                       \
+        P = (d2);                                                                                                         \
+        ON_SKIP;                                                                                                          \
+    }
+// The states: N = c + P, H = c + nPrev (nPrev = N(i, j-1)), each sum rounded once; E = N, replaced by H if that is < N
+// (strict: a tie keeps N); ON_REP runs where E is H, the source frame repeated
+#define SSYM_PACED_STATES(N, E, c, P, nPrev, ON_REP)                                                                      \
+    N = __dadd_rn(c, P);                                                                                                  \
+    {                                                                                                                     \
+        const double h_ = __dadd_rn(c, nPrev);                                                                            \
+        E = N;                                                                                                            \
+        if (h_ < N) {                                                                                                     \
+            E = h_;                                                                                                       \
+            ON_REP;                                                                                                       \
+        }                                                                                                                 \
+    }
 
 // the first minimum among the 64 lanes' candidates (bestD f64, bestEnd u32, bestSt u32), ordered by (D, row), in every
 // lane; a lane without a candidate holds (+inf, 0xffffffff), which loses against every candidate and ties with its like.

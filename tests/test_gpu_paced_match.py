@@ -1,14 +1,17 @@
 """Paced matching on the GPU (ssym_match_queries_step and ssym_pair_matrix_step with SSYM_STEP_PACED) against the numpy
 restatement (tests/paced_match_ref.py), bit for bit: the matrix and the match on ragged sets in both dtypes, squared and
 not, against ssym_dtw_align_step's costs over the full pair list, with distances, an index base and device outputs; the
-case that motivates the call and the planted cuts that cost exactly 0.0; every match aligned at its cost; features that
-are not finite; the symmetric step as the existing calls; the same bits whatever the context ran before; every refusal."""
+case that motivates the call and the planted cuts that cost exactly 0.0; both ties of the cell on integer features; every
+match aligned at its cost; features that are not finite; the symmetric step as the existing calls; the same bits whatever
+the context ran before; every refusal."""
 import numpy as np
 import pytest
 
 import nonfinite_cases
 import paced_match_ref as ref
 import paced_path_ref
+from dtw_path_ref import local_costs
+from paced_ref import _down
 from paced_match_gpu import (INF, NAN, PACED, SENT32, SENTF, SYMMETRIC, Sets, align_costs, bits, check_match, check_matrix,
                              error, match, matrix, real, same_as_align, same_bits)
 from soundsym_amd import HOP, Sound, SoundDictionary, SoundSequence, SsymError
@@ -118,6 +121,39 @@ def test_planted_cuts_cost_exactly_zero():
             assert rc == nat.SSYM_OK and idx.tolist() == [1, 3, 5, 6]
             assert (bits(cost) == bits(np.zeros(4))).all()
             check_match(sets, ref.matrix(src, tgt, squared))
+
+
+# -- both ties of the cell ----------------------------------------------------------------------------------------------------
+def _finite_ties(a, b):
+    """(cells with E(i-2,j-1) == E(i-1,j-1), cells with H == N), finite values only, of paced_path_ref.forward's recurrence."""
+    c = local_costs(a, b, True)
+    n = np.full(c.shape[0], INF)
+    n[0] = c[0, 0]
+    e, pred, state = n.copy(), 0, 0
+    for j in range(1, c.shape[1]):
+        p, p2 = _down(e, 1, INF), _down(e, 2, INF)
+        pred += int(((p2 == p) & np.isfinite(p)).sum())
+        h, n = c[:, j] + n, c[:, j] + np.minimum(p, p2)
+        state += int(((h == n) & np.isfinite(n)).sum())
+        e = np.minimum(h, n)
+    return pred, state
+
+
+def test_both_ties_of_the_cell_on_integer_features():
+    """Features in {0, 1, 2}, one value per frame, sources of 3 ... 5 frames, targets of 3 and 4: every sum is exact, so the
+    second diagonal equals the first and H equals N in many cells, and strict < has to keep row i - 1 and state N."""
+    rng = np.random.default_rng(0x71E5)
+    ints = lambda f: rng.integers(0, 3, size=(f, 1)).astype(np.float64)
+    src = [ints(3 + k % 3) for k in range(12)]
+    tgt = [ints(3 + k % 2) for k in range(6)]
+    ties = np.array([_finite_ties(a, b) for a in src for b in tgt if paced_path_ref.feasible(a.shape[0], b.shape[0])])
+    assert (ties.sum(axis=0) > 20).all()
+    for squared in (False, True):
+        want = ref.matrix(src, tgt, squared)
+        assert np.isfinite(want).sum() > 40
+        with Sets(src, tgt, 1, squared=squared) as sets:
+            same_as_align(check_matrix(sets, want), align_costs(sets)[0])
+            check_match(sets, want)
 
 
 # -- features that are not finite ----------------------------------------------------------------------------------------------
