@@ -18,6 +18,7 @@ use std::os::raw::{c_char, c_void};
 #[repr(C)] pub struct SsymCoverer { _p: [u8; 0] }
 #[repr(C)] pub struct SsymMosaicker { _p: [u8; 0] }
 #[repr(C)] pub struct SsymResynth { _p: [u8; 0] }
+#[repr(C)] pub struct SsymFollower { _p: [u8; 0] }
 
 pub const SSYM_ABI_VERSION: i32 = 3;
 
@@ -397,6 +398,17 @@ extern "C" {
                               out_n_samples: *mut u64) -> i32;
     pub fn ssym_resynth_counts(rs: *const SsymResynth, out_frames: *mut u64, out_samples: *mut u64) -> i32;
     pub fn ssym_resynth_reset(ctx: *mut SsymCtx, rs: *mut SsymResynth, lane: u32) -> i32;
+    // live envelope following (include/soundsym_amd.h "Live envelope following"): loudness tracking, push by push; samples and
+    // ref are host memory, or device memory with SSYM_FOLLOW_SAMPLES_DEVICE / SSYM_FOLLOW_REF_DEVICE
+    pub fn ssym_follower_create(ctx: *mut SsymCtx, n_lanes: u32, max_gain: f64, out: *mut *mut SsymFollower) -> i32;
+    pub fn ssym_follower_destroy(ctx: *mut SsymCtx, fl: *mut SsymFollower) -> i32;
+    pub fn ssym_follower_push(ctx: *mut SsymCtx, fl: *mut SsymFollower, samples: *const f64, sample_offsets: *const u64,
+                              reference: *const f64, ref_offsets: *const u64, flags: u32, out_n_samples: *mut u64) -> i32;
+    pub fn ssym_follower_flush(ctx: *mut SsymCtx, fl: *mut SsymFollower, lane: u32, out_n_samples: *mut u64) -> i32;
+    pub fn ssym_follower_samples(ctx: *mut SsymCtx, fl: *const SsymFollower, out_lane_offsets: *mut u64, out_samples: *mut f64,
+                                 out_pcm32: *mut i32, out_gain_offsets: *mut u64, out_gain: *mut f64, flags: u32) -> i32;
+    pub fn ssym_follower_counts(fl: *const SsymFollower, out_ny: *mut u64, out_nx: *mut u64, out_released: *mut u64) -> i32;
+    pub fn ssym_follower_reset(ctx: *mut SsymCtx, fl: *mut SsymFollower, lane: u32) -> i32;
 }
 
 /// `Err(message)` for any status but SSYM_OK; SSYM_E_EMPTY_DICT keeps the crate's behaviour (a panic, :369).

@@ -2,7 +2,7 @@
 """examples/live_mosaic.py -- a recording tiled by free spans of uncut recordings while it is still arriving.
 
     python examples/live_mosaic.py -s TARGET.wav -d REC.wav|DIR [-o OUT.wav] [--block 4096] [--penalty 1.0] [--gap-cost X]
-                                   [--gap-fill silence|target] [--search 256] [--live-audio]
+                                   [--gap-fill silence|target] [--search 256] [--live-audio] [--follow [--max-gain 8]]
 
 The dictionary is built as examples/mosaic.py builds it: one recording or a folder of recordings, each taken whole.  The
 target is fed --block samples at a time (Sound.push_samples, as a recording arrives), and SoundDictionary.mosaic_live follows
@@ -14,6 +14,9 @@ the resynthesis of the finished mosaic (SoundDictionary.reconstruct_mosaic(mosai
 --live-audio resynthesises while the target arrives (mosaic_live(audio=True), LiveMosaic.audio()): every block also prints
 the samples it released and the hops still held back (at most 4 without a search, at most 12 with one), and -o writes what
 was gathered push by push -- the same WAV as without the flag, sample for sample.
+--follow gives the resynthesis the target's loudness, hop by hop (dynamics="target", at most --max-gain): without --live-audio
+through reconstruct_mosaic, with it through the LiveMosaic's Follower, which holds two or three hops more -- again the same
+WAV either way.
 """
 import argparse
 import os
@@ -38,6 +41,9 @@ def main(argv=None):
     ap.add_argument("--gap-fill", choices=("silence", "target"), default="silence", help="what a gap sounds like")
     ap.add_argument("--search", type=int, default=256, help="WSOLA search width in samples (0: plain overlap-add)")
     ap.add_argument("--live-audio", action="store_true", help="resynthesise while the target arrives (LiveMosaic.audio)")
+    ap.add_argument("--follow", action="store_true",
+                    help="the resynthesis takes the target's loudness, hop by hop (dynamics=\"target\"; live with --live-audio)")
+    ap.add_argument("--max-gain", type=float, default=8.0, help="the greatest gain of --follow, finite and at least 1")
     args = ap.parse_args(argv)
     if args.block < 1:
         ap.error("--block must be at least 1")
@@ -66,7 +72,8 @@ def main(argv=None):
     target = Sound.from_samples(samples[:first], whole.sample_rate(), engine=engine)
     target.push_samples(samples[:0], engine)                          # resident: the stream the mosaic follows
     if args.live_audio:
-        live = dictionary.mosaic_live([target], args.penalty, args.gap_cost, audio=True, search=args.search, gap_fill=args.gap_fill)
+        live = dictionary.mosaic_live([target], args.penalty, args.gap_cost, audio=True, search=args.search, gap_fill=args.gap_fill,
+                                      dynamics="target" if args.follow else None, max_gain=args.max_gain)
     else:
         live = dictionary.mosaic_live([target], args.penalty, args.gap_cost)
     heard = []                                                        # --live-audio: (samples, pcm) as they are released
@@ -77,7 +84,8 @@ def main(argv=None):
         heard.append(live.audio(want_pcm32=True)[0])
         released = sum(h[0].size for h in heard)
         frames = int(live.pending()[2][0])
-        print(f"[{at:9d} samples] {heard[-1][0].size:7d} samples released, {max(frames - released // HOP, 0):2d} hops held")
+        print(f"[{at:9d} samples] {heard[-1][0].size:7d} samples released, {max(frames - released // HOP, 0):2d} hops held"
+              + (" (two or three of them by the follower)" if args.follow else ""))
 
     show(live.poll(), first)
     listen(first)
@@ -103,7 +111,8 @@ def main(argv=None):
             print(f"{out.size} samples -> {args.o}")
     elif args.o and mosaic and covered[0] == consumed[0]:
         _, out, pcm = dictionary.reconstruct_mosaic(target, args.penalty, args.gap_cost, args.gap_fill, args.search,
-                                                    want_pcm32=True, mosaic=mosaic)
+                                                    want_pcm32=True, mosaic=mosaic, dynamics="target" if args.follow else None,
+                                                    max_gain=args.max_gain)
         write_wav32(args.o, sample_rate=target.sample_rate(), pcm=pcm)
         print(f"{out.size} samples -> {args.o}")
     return mosaic, out

@@ -1239,6 +1239,84 @@ class Resynth {
     ssym_resynth *rs_ = nullptr;
 };
 
+// Live envelope following (ssym_follower_*, "Live envelope following" in soundsym_amd.h): follow_envelope's resumable form.
+// A lane takes the resynthesis and the reference -- the target's own samples -- as they grow, in any amounts, and every
+// push returns what it releases: the hops whose two gain boundaries are settled, two hops of look-ahead on both signals.
+// From reset to flush a lane's samples and gains are follow_envelope's for what it consumed, bit for bit.
+class Follower {
+  public:
+    struct Samples {
+        std::vector<uint64_t> lane_offsets;     // n_lanes + 1: lane l's samples are [lane_offsets[l], lane_offsets[l + 1])
+        std::vector<double> samples;
+        std::vector<int32_t> pcm32;
+        std::vector<uint64_t> gain_offsets;     // n_lanes + 1: the gains of the boundaries the call settled, lane by lane
+        std::vector<double> gains;
+    };
+    struct Counts {
+        std::vector<uint64_t> ny, nx, released; // per lane since its reset: consumed of either signal, samples released
+    };
+    // max_gain: finite and at least 1; n_lanes 1 ... 16384
+    explicit Follower(std::shared_ptr<Context> ctx, uint32_t n_lanes = 1, double max_gain = 8.0) : ctx_(std::move(ctx)), lanes_(n_lanes)
+    {
+        ctx_->check(ssym_follower_create(ctx_->get(), n_lanes, max_gain, &fl_));
+    }
+    ~Follower() { ssym_follower_destroy(ctx_->get(), fl_); }
+    Follower(const Follower &) = delete;
+    Follower &operator=(const Follower &) = delete;
+
+    // lane l consumes samples[sample_offsets[l] ... sample_offsets[l + 1]) and ref[ref_offsets[l] ... ref_offsets[l + 1])
+    Samples push(const std::vector<double> &samples, const std::vector<uint64_t> &sample_offsets, const std::vector<double> &ref,
+                 const std::vector<uint64_t> &ref_offsets)
+    {
+        if (sample_offsets.size() != (size_t)lanes_ + 1 || ref_offsets.size() != (size_t)lanes_ + 1)
+            throw Error(SSYM_E_INVALID, "Follower::push: n_lanes + 1 sample_offsets and n_lanes + 1 ref_offsets");
+        if (samples.size() < sample_offsets.back() || ref.size() < ref_offsets.back())
+            throw Error(SSYM_E_INVALID, "Follower::push: samples or ref hold fewer values than their offsets ask for");
+        uint64_t got = 0;
+        ctx_->check(ssym_follower_push(ctx_->get(), fl_, samples.empty() ? nullptr : samples.data(), sample_offsets.data(),
+                                       ref.empty() ? nullptr : ref.data(), ref_offsets.data(), 0, &got));
+        return samples_of_last_call();
+    }
+    // a follower of one lane takes the bare signals
+    Samples push(const std::vector<double> &samples, const std::vector<double> &ref)
+    {
+        return push(samples, {0, samples.size()}, ref, {0, ref.size()});
+    }
+    // "the lane has ended": the remaining boundaries with the offline clipping, the rest of the resynthesis
+    Samples flush(uint32_t lane = 0)
+    {
+        uint64_t got = 0;
+        ctx_->check(ssym_follower_flush(ctx_->get(), fl_, lane, &got));
+        return samples_of_last_call();
+    }
+    Counts counts() const
+    {
+        Counts c{std::vector<uint64_t>(lanes_), std::vector<uint64_t>(lanes_), std::vector<uint64_t>(lanes_)};
+        ctx_->check(ssym_follower_counts(fl_, c.ny.data(), c.nx.data(), c.released.data()));
+        return c;
+    }
+    void reset(uint32_t lane = 0) { ctx_->check(ssym_follower_reset(ctx_->get(), fl_, lane)); }
+
+  private:
+    Samples samples_of_last_call() const
+    {
+        Samples out;
+        out.lane_offsets.assign((size_t)lanes_ + 1, 0);
+        out.gain_offsets.assign((size_t)lanes_ + 1, 0);
+        ctx_->check(ssym_follower_samples(ctx_->get(), fl_, out.lane_offsets.data(), nullptr, nullptr, out.gain_offsets.data(), nullptr, 0));
+        out.samples.resize(out.lane_offsets.back());
+        out.pcm32.resize(out.lane_offsets.back());
+        out.gains.resize(out.gain_offsets.back());
+        ctx_->check(ssym_follower_samples(ctx_->get(), fl_, nullptr, out.samples.empty() ? nullptr : out.samples.data(),
+                                          out.pcm32.empty() ? nullptr : out.pcm32.data(), nullptr,
+                                          out.gains.empty() ? nullptr : out.gains.data(), 0));
+        return out;
+    }
+    std::shared_ptr<Context> ctx_;
+    uint32_t lanes_ = 0;
+    ssym_follower *fl_ = nullptr;
+};
+
 // One rank of a SoundDictionary split over the GPUs of one node (source-axis shards, one rank -- thread or process --
 // per GPU): rank g holds sounds [lo, lo + shard.size()) of the whole dictionary and is handed the same targets as every
 // other rank; match_indices returns GLOBAL indices, the same complete answer on every rank, bit for bit the unsharded

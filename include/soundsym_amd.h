@@ -62,6 +62,7 @@ typedef struct ssym_spotter ssym_spotter; /* targets watched in growing sources:
 typedef struct ssym_coverer ssym_coverer; /* growing targets tiled by dictionary segments: live cover  */
 typedef struct ssym_mosaicker ssym_mosaicker; /* growing targets tiled by free spans: live mosaic       */
 typedef struct ssym_resynth ssym_resynth; /* committed mosaic frames to audio, push by push: live resynthesis */
+typedef struct ssym_follower ssym_follower; /* loudness tracking, push by push: live envelope following */
 
 enum {
     SSYM_OK = 0,
@@ -914,8 +915,8 @@ SSYM_API int32_t ssym_reconstruct_wsola_spans(ssym_ctx *ctx, const ssym_samples 
  *   pcm     : out_pcm32 = ssym_reconstruct's conversion of out[k]
  *
  * The window of boundary b is centred on sample b*HOP.  It is hop-aligned.  Hop j of the output needs g(j) and g(j+1), so
- * it needs samples below (j+3)*HOP, two hops of look-ahead.  That is stated so that a later live follower can be held to
- * this call bit for bit.
+ * it needs samples below (j+3)*HOP, two hops of look-ahead.  The live follower (ssym_follower_*, "Live envelope following"
+ * below) releases on exactly that and is held to this call bit for bit.
  *   samples        out_offsets[n] f64: the reconstructions, packed (HOST, or device with SSYM_FOLLOW_SAMPLES_DEVICE)
  *   out_offsets    n_targets + 1 u64 (HOST): start at 0, do not decrease
  *   ref            ref_offsets[n] f64: the references, packed (HOST, or device with SSYM_FOLLOW_REF_DEVICE); may be NULL
@@ -1453,6 +1454,61 @@ SSYM_API int32_t ssym_resynth_flush(ssym_ctx *ctx, ssym_resynth *rs, uint32_t la
                                     uint64_t *out_n_samples);
 SSYM_API int32_t ssym_resynth_counts(const ssym_resynth *rs, uint64_t *out_frames, uint64_t *out_samples);
 SSYM_API int32_t ssym_resynth_reset(ssym_ctx *ctx, ssym_resynth *rs, uint32_t lane);
+
+/* Live envelope following (DESIGN.md section 2 "Live envelope following" and section 5.29): ssym_follow_envelope's resumable
+ * form.  A follower holds n_lanes lanes and one max_gain.  A lane receives two growing signals: y, the resynthesis, and x, the
+ * reference (the target's own samples).  Either arrives in any amounts: not hop-aligned, neither has to lead the other.  ny
+ * and nx are the counts consumed since the lane's reset.  HOP, BIN, w[] and the energy, gain, sample and pcm rules are those
+ * of "Envelope following" above, word for word.
+ *   settle   : with h = floor(min(ny, nx) / HOP), before a flush: boundary b is settled when (b + 2)*HOP <= min(ny, nx) --
+ *              max(0, h - 1) boundaries so far -- and hop j is released when boundaries j and j + 1 are settled -- max(0, h - 2)
+ *              hops so far.  The counts are host arithmetic on how much was consumed, never on sample values or on how the
+ *              samples were cut into pushes.
+ *   flush    : ends the lane with n = ny.  Every remaining boundary b <= J = ceil(n / HOP) is computed with the offline
+ *              clipping: k >= n is left out, x[k] reads +0.0 for k >= nx, x at or beyond n is dropped unread.  The rest of y
+ *              leaves, the tail included.  A lane flushed at ny = 0 releases nothing.  The lane has then ENDED until
+ *              ssym_follower_reset.
+ *   why      : a settled boundary's window [(b-2)*HOP, (b+2)*HOP) lies wholly below both counts: no later sample and no later
+ *              n enters its sum; terms with k < 0 are +0.0 in both routes.  So from reset to flush a lane's samples and gains
+ *              are ssym_follow_envelope's for (y[0..ny), x[0..nx)), bit for bit.  Releasing one hop earlier changes bits.
+ *   state    : per lane and signal the samples from (r - 2)*HOP on (r: the hops released; g(r) sits in the lane's record), in
+ *              a ring indexed by absolute sample index modulo a power-of-two capacity shared by the lanes: at least 2048, grown
+ *              to the longest held stretch plus the call's samples.  Both rings of an object stay within 512 MiB, so at most
+ *              16384 lanes are accepted, and a call that would pass the cap is refused with nothing consumed.  A lane consumes
+ *              fewer than 2^40 samples per signal.
+ *
+ * ssym_follower_create: any context.  max_gain finite and at least 1, n_lanes 1 ... 16384 (0: SSYM_E_INVALID; more:
+ *   SSYM_E_UNSUPPORTED).  Refusals come before any device work, in the order ctx, out, max_gain, lanes.
+ * ssym_follower_push: lane l consumes samples[sample_offsets[l] ... sample_offsets[l+1]) of y and ref[ref_offsets[l] ...
+ *   ref_offsets[l+1]) of x.  Both offset arrays are [n_lanes + 1] u64 (HOST), start at 0 and do not decrease.  samples and ref
+ *   are HOST memory, or device memory with SSYM_FOLLOW_SAMPLES_DEVICE / SSYM_FOLLOW_REF_DEVICE; either may be NULL when it
+ *   holds nothing.  Refusals are SSYM_E_INVALID or SSYM_E_UNSUPPORTED, nothing is consumed, the earliest fault is reported, in
+ *   this order: the handle, unknown flag bits, NULL offsets or count, the offsets' start, then lane by lane (a decrease; the
+ *   lane has ended; the 2^40 limit, SSYM_E_UNSUPPORTED), the ring cap (SSYM_E_UNSUPPORTED), NULL arrays.
+ *   out_n_samples  the samples this call released over all lanes (read them with ssym_follower_samples)
+ * ssym_follower_flush: the flush of one lane.  A lane outside the lanes, a lane that has ended or out_n_samples NULL:
+ *   SSYM_E_INVALID.
+ * ssym_follower_samples: what the last push or flush released, lane by lane: lane l's samples are [out_lane_offsets[l],
+ *   out_lane_offsets[l+1]) of out_samples (f64) and out_pcm32 (ssym_reconstruct's conversion of each); the gains of the
+ *   boundaries that call settled are [out_gain_offsets[l], out_gain_offsets[l+1]) of out_gain, in boundary order.  Every
+ *   pointer is nullable.  The two offset arrays ([n_lanes + 1] u64) are always HOST; the rest is HOST memory, or device
+ *   memory with SSYM_OUT_DEVICE.
+ * ssym_follower_counts: ny, nx and the samples released per lane since its reset (n_lanes u64 each, HOST, nullable).  Host
+ *   arithmetic, no device work.
+ * ssym_follower_reset: one lane back to "nothing consumed".
+ * One synchronisation per push or flush (a call whose sample log has to grow waits once more, as the resynthesiser's).
+ * ssym_get_timings afterwards: main_ms = the gain kernel, reduce_ms = append plus
+ * apply, n_pairs = the boundaries the call settled.  A call's samples (12 bytes each) and gains are scratch of the object,
+ * reused by the next call. */
+SSYM_API int32_t ssym_follower_create(ssym_ctx *ctx, uint32_t n_lanes, double max_gain, ssym_follower **out);
+SSYM_API int32_t ssym_follower_destroy(ssym_ctx *ctx, ssym_follower *fl);
+SSYM_API int32_t ssym_follower_push(ssym_ctx *ctx, ssym_follower *fl, const double *samples, const uint64_t *sample_offsets,
+                                    const double *ref, const uint64_t *ref_offsets, uint32_t flags, uint64_t *out_n_samples);
+SSYM_API int32_t ssym_follower_flush(ssym_ctx *ctx, ssym_follower *fl, uint32_t lane, uint64_t *out_n_samples);
+SSYM_API int32_t ssym_follower_samples(ssym_ctx *ctx, const ssym_follower *fl, uint64_t *out_lane_offsets, double *out_samples,
+                                       int32_t *out_pcm32, uint64_t *out_gain_offsets, double *out_gain, uint32_t flags);
+SSYM_API int32_t ssym_follower_counts(const ssym_follower *fl, uint64_t *out_ny, uint64_t *out_nx, uint64_t *out_released);
+SSYM_API int32_t ssym_follower_reset(ssym_ctx *ctx, ssym_follower *fl, uint32_t lane);
 
 #ifdef __cplusplus
 }

@@ -11,7 +11,7 @@ from ._native import (  # noqa: F401
     SsymError,
     build,
 )
-from .engine import Coverer, DeviceFrames, Engine, Gmm, Mosaicker, Resynth, Spotter, Stream, pack_segments, stream_plan  # noqa: F401
+from .engine import Coverer, DeviceFrames, Engine, Follower, Gmm, Mosaicker, Resynth, Spotter, Stream, pack_segments, stream_plan  # noqa: F401
 from .api import (  # noqa: F401
     Alignment,
     BIN,
@@ -47,5 +47,5 @@ __all__ = [
     "ABI_SYMBOLS", "Alignment", "BIN", "Cover", "Coverer", "DeviceFrames", "EmptyDictionaryError", "Engine", "Gap", "Gmm", "HOP", "LIB_PATH", "LiveCover", "LiveMosaic", "Mosaic", "MosaicPiece", "Mosaicker", "NCLUSTERS", "NCOEFFS",
     "Partitioner", "Piece", "Resynth", "Sound", "SoundDictionary", "SoundSequence", "Spot", "SsymError", "analyze_mfccs", "analyze_sounds", "build",
     "cosine_sim_angular", "discretize",
-    "discretize_with_model", "follow_envelope", "length_fit", "pack_segments", "push_sounds", "Spotter", "Stream", "stream_plan", "train_model", "Watch", "watch",
+    "discretize_with_model", "follow_envelope", "Follower", "length_fit", "pack_segments", "push_sounds", "Spotter", "Stream", "stream_plan", "train_model", "Watch", "watch",
 ]

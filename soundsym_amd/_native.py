@@ -75,6 +75,8 @@ ABI_SYMBOLS = [
     "ssym_reconstruct_warped", "ssym_reconstruct_wsola",
     "ssym_dtw_align_spans_sizes", "ssym_dtw_align_spans", "ssym_reconstruct_warped_spans", "ssym_reconstruct_wsola_spans",
     "ssym_follow_envelope",
+    "ssym_follower_create", "ssym_follower_destroy", "ssym_follower_push", "ssym_follower_flush", "ssym_follower_samples",
+    "ssym_follower_counts", "ssym_follower_reset",
 ]
 COMM_ID_BYTES = 128        # SSYM_COMM_ID_BYTES
 
@@ -456,6 +458,20 @@ def lib() -> ctypes.CDLL:
     L.ssym_resynth_counts.argtypes = [vp, vp, vp]
     L.ssym_resynth_reset.restype = i32
     L.ssym_resynth_reset.argtypes = [vp, vp, u32]
+    L.ssym_follower_create.restype = i32
+    L.ssym_follower_create.argtypes = [vp, u32, f64, pvp]
+    L.ssym_follower_destroy.restype = i32
+    L.ssym_follower_destroy.argtypes = [vp, vp]
+    L.ssym_follower_push.restype = i32
+    L.ssym_follower_push.argtypes = [vp, vp, vp, vp, vp, vp, u32, ctypes.POINTER(u64)]
+    L.ssym_follower_flush.restype = i32
+    L.ssym_follower_flush.argtypes = [vp, vp, u32, ctypes.POINTER(u64)]
+    L.ssym_follower_samples.restype = i32
+    L.ssym_follower_samples.argtypes = [vp, vp, vp, vp, vp, vp, vp, u32]
+    L.ssym_follower_counts.restype = i32
+    L.ssym_follower_counts.argtypes = [vp, vp, vp, vp]
+    L.ssym_follower_reset.restype = i32
+    L.ssym_follower_reset.argtypes = [vp, vp, u32]
     _lib = L
     return L
 

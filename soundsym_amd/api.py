@@ -866,7 +866,8 @@ class LiveMosaic:
     sound gains later.  A run of gap frames comes as one Gap per call; the run may go on in the next call, and `mosaics`
     merges across calls."""
 
-    def __init__(self, sounds, stream, mosaicker, piece_penalty: float, gap_cost=None, resynth=None, gap_fill: str = "silence"):
+    def __init__(self, sounds, stream, mosaicker, piece_penalty: float, gap_cost=None, resynth=None, gap_fill: str = "silence",
+                 follower=None):
         self.sounds, self.stream, self.mosaicker, self.piece_penalty = sounds, stream, mosaicker, float(piece_penalty)
         self.gap_cost = gap_cost
         # per sound: (src, frame, cost, start) of every committed frame, and the frames already returned as closed pieces
@@ -879,6 +880,11 @@ class LiveMosaic:
         self.resynth, self.gap_fill = resynth, gap_fill
         self._audio = [[] for _ in sounds]
         self._audio_at = [0 for _ in sounds]
+        # mosaic_live(dynamics="target"): a Follower takes what audio() has spliced, against the sounds' own samples; per
+        # sound whether flush() has ended it and whether the follower's lane has been flushed since
+        self.follower = follower
+        self._ended = [False for _ in sounds]
+        self._followed = [False for _ in sounds]
 
     def _take(self, ended=()):
         lane, col, src, frame, cost, start = self.mosaicker.frames()
@@ -931,6 +937,7 @@ class LiveMosaic:
             if self.resynth is not None:
                 self.resynth.flush(lane, len(self.sounds[lane].samples()))
                 self._gather_audio()
+                self._ended[lane] = True
         return sorted(out, key=lambda t: (t[0], t[1].start_frame))   # (only pieces held from a refused poll move)
 
     def _take_audio(self):
@@ -954,7 +961,9 @@ class LiveMosaic:
         reconstruct_mosaic(sound, mosaic=mosaics()[i], search=, gap_fill=)'s, bit for bit.  A sample leaves when no later
         frame can change it: at most 4 frames behind the committed frames for search = 0, at most 12 with a search (DESIGN.md
         section 2 "Live resynthesis").  gap_fill="target": gap stretches are filled here, on the host, with the sound's own
-        samples, as reconstruct_mosaic fills them."""
+        samples, as reconstruct_mosaic fills them.  With dynamics="target" what is returned has gone through the LiveMosaic's
+        Follower as well, after the gap splice, against the sound's own samples: it trails the resynthesiser by two more
+        hops, and from the first poll to flush it is reconstruct_mosaic(..., dynamics="target", max_gain=)'s, bit for bit."""
         if self.resynth is None:
             raise ValueError("audio: the LiveMosaic was made without audio (mosaic_live(audio=True))")
         out = []
@@ -972,6 +981,40 @@ class LiveMosaic:
                     x = np.nan_to_num(2147483647.0 * own, nan=0.0)
                     pcm[gap] = np.trunc(np.clip(x, -2147483648.0, 2147483647.0)).astype(np.int64).astype(np.int32)
             self._audio_at[l] += smp.size
+            out.append((smp, pcm) if want_pcm32 else smp)
+        return out if self.follower is None else self._follow(out, want_pcm32)
+
+    def _follow(self, spliced, want_pcm32: bool):
+        """What audio() has spliced goes into the follower, one push for all sounds, with the sounds' own samples up to the
+        same count; a sound that flush() has ended is then flushed there too.  Returns what that released, per sound."""
+        spliced = [p[0] if want_pcm32 else p for p in spliced]
+        ny, nx, _ = self.follower.counts()
+        ref = []
+        for l, (sound, smp) in enumerate(zip(self.sounds, spliced)):
+            own = np.asarray(sound.samples(), dtype=np.float64).reshape(-1)
+            ref.append(own[min(int(nx[l]), own.size):min(int(ny[l]) + smp.size, own.size)])
+        parts = [[] for _ in self.sounds]
+
+        def gather():
+            if self.follower.n_samples:
+                off, smp, pcm = self.follower.samples(want_pcm32=True)
+                for l in range(len(self.sounds)):
+                    a, b = int(off[l]), int(off[l + 1])
+                    if b > a:
+                        parts[l].append((smp[a:b], pcm[a:b]))
+        if any(a.size for a in spliced) or any(a.size for a in ref):
+            offsets = lambda arrays: np.concatenate([[0], np.cumsum([a.size for a in arrays])]).astype(np.uint64)      # noqa: E731
+            self.follower.push(np.concatenate(spliced), offsets(spliced), np.concatenate(ref), offsets(ref))
+            gather()
+        for l in range(len(self.sounds)):
+            if self._ended[l] and not self._followed[l]:
+                self.follower.flush(l)
+                self._followed[l] = True
+                gather()
+        out = []
+        for p in parts:
+            smp = np.concatenate([q[0] for q in p]) if p else np.zeros(0)
+            pcm = np.concatenate([q[1] for q in p]) if p else np.zeros(0, dtype=np.int32)
             out.append((smp, pcm) if want_pcm32 else smp)
         return out
 
@@ -1005,6 +1048,8 @@ class LiveMosaic:
         return self.mosaicker.counts()[0].astype(np.int64), covered.astype(np.int64), committed.astype(np.int64), total
 
     def close(self):
+        if self.follower is not None:
+            self.follower.close()
         if self.resynth is not None:
             self.resynth.close()
         self.mosaicker.close()
@@ -1629,7 +1674,7 @@ class SoundDictionary:
         return LiveCover(sounds, st, self.engine.coverer(self.resident(), len(sounds), penalty, gap), penalty, gap)
 
     def mosaic_live(self, sounds: Sequence[Sound], piece_penalty: float = 0.0, gap_cost=None, audio: bool = False,
-                    search: int = 0, gap_fill: str = "silence") -> "LiveMosaic":
+                    search: int = 0, gap_fill: str = "silence", dynamics=None, max_gain: float = FOLLOW_MAX_GAIN) -> "LiveMosaic":
         """Tile Sounds that are still growing (fed with push_samples / push_sounds): a Mosaicker on this dictionary follows
         the sounds' stream (ssym_mosaicker_*, DESIGN.md section 2 "Live mosaic"; dtw engines without a band).  The sounds
         must be resident and share one stream, sound i in lane i -- what one push_sounds(sounds, ...) leaves -- ValueError
@@ -1641,7 +1686,14 @@ class SoundDictionary:
         audio=True: the LiveMosaic also owns a Resynth on the dictionary's resident samples (ssym_resynth_*, "Live
         resynthesis"): every poll hands it the committed frames device to device, and LiveMosaic.audio() returns the samples
         that releases -- from the first poll to flush reconstruct_mosaic's (search and gap_fill as there), bit for bit.
-        With audio=False (the default) search and gap_fill are not used."""
+        With audio=False (the default) search and gap_fill are not used.
+        dynamics="target" (with audio=True): the LiveMosaic also owns a Follower (ssym_follower_*, "Live envelope
+        following"): audio() feeds it what the resynthesiser released -- after the gap splice, as reconstruct_mosaic follows
+        after its splice -- beside the sound's own samples, and returns what that releases: from the first poll to flush
+        reconstruct_mosaic(..., dynamics="target", max_gain=)'s, bit for bit.  None: everything as it was, no follower."""
+        gain = follow_dynamics(dynamics, max_gain)
+        if gain is not None and not audio:
+            raise ValueError('dynamics="target" follows the audio: it needs audio=True')
         penalty, gap = self._cover_checks(piece_penalty, "mosaic_live"), _cover_gap_cost(gap_cost)
         if audio:
             search = _wsola_search(search)
@@ -1661,7 +1713,15 @@ class SoundDictionary:
         except Exception:
             mk.close()
             raise
-        return LiveMosaic(sounds, st, mk, penalty, gap, rs, gap_fill)
+        fl = None
+        if gain is not None:
+            try:
+                fl = self.engine.follower(len(sounds), gain)
+            except Exception:
+                rs.close()
+                mk.close()
+                raise
+        return LiveMosaic(sounds, st, mk, penalty, gap, rs, gap_fill, fl)
 
     def mosaic_long(self, target: Sound, piece_penalty: float = 0.0, block_frames: int = 4096, gap_cost=None) -> "Mosaic":
         """`mosaic` for one target of any length: a one-lane Mosaicker is pushed the target's frames block_frames at a time

@@ -27,17 +27,17 @@
 //
 // follow_apply_kernel: warp_kernel's grid, a workgroup per (target, 4096-sample chunk), one thread per output sample and
 // hop, f the same for all 16 samples of a thread.  The chunk's 17 gains sit in LDS, every read a broadcast.
-#include "warp_common.hpp"
+//
+// The block geometry, the chain, the gain's division, square root and selects and a sample's arithmetic are
+// follow_common.hpp's (follow_chain, follow_gain, follow_sample): the live follower (follower.hip) runs the same text.  Every
+// product there is a __dmul_rn, every sum a __dadd_rn, the gain a __dsqrt_rn of a __ddiv_rn: nothing contracts, whatever the
+// compiler is told.
+#include "follow_common.hpp"
 
 namespace ssym {
 namespace {
 
-constexpr int kFollowBlock = 32;                           // boundaries per workgroup of follow_gain_kernel
-constexpr int kFollowHops = kFollowBlock + kWarpTaps - 1;  // 35 hops under a full block's windows
-constexpr int kFollowPitch = kWarpHop + 1;                 // doubles from one staged hop to the next
-constexpr uint64_t kFollowMaxLen = 1ull << 40;             // samples per target: boundaries then fit 32 bits with room
 constexpr uint32_t kFollowGridY = 65535;                   // targets per launch of follow_apply_kernel (the grid's y)
-static_assert(kFollowBlock == 32 && kWarpHop == 256 && kWarpBin == 1024, "follow_gain_kernel: one wave of chains, 256 stagers");
 
 struct FollowArgs {
     const double *y;            // the reconstructions, packed by outOff (may be the array `out` of the apply kernel)
@@ -94,44 +94,10 @@ __global__ __launch_bounds__(256) void follow_gain_kernel(const FollowArgs a)
     const int sig = tid >> 5, bl = tid & 31;
     // a lane past the block's last boundary repeats it: reads stay in the staged span
     const double *s = (sig ? sx : sy) + std::min(bl, nb - 1) * kFollowPitch;
-    // sixteen steps at a time, the next sixteen's reads issued before the sum goes through these (one wave: nothing else
-    // hides an LDS read); a group of 16 never straddles a hop, so its slots are consecutive
-    constexpr int U = 16;
-    double acc = 0.0, v[U], w[U];
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-        v[u] = s[u];
-        w[u] = sw[u];
-    }
-    for (int m = 0; m < kWarpBin; m += U) {
-        double nv[U], nw[U];
-        const int mn = m + U < kWarpBin ? m + U : m;            // the last group reads itself again: in range, unused
-        const double *sn = s + mn + (mn >> 8);                  // hop mn / 256 of the window, pitch 257
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            nv[u] = sn[u];
-            nw[u] = sw[mn + u];
-        }
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            double p = __dmul_rn(v[u], v[u]);
-            p = __dmul_rn(w[u], p);
-            acc = __dadd_rn(acc, p);
-        }
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            v[u] = nv[u];
-            w[u] = nw[u];
-        }
-    }
+    const double acc = follow_chain(s, sw);
     const double ex = __shfl(acc, bl + 32, 64);
     if (sig == 0 && bl < nb) {
-        double g = __dsqrt_rn(__ddiv_rn(ex, acc));
-        if (g != g)
-            g = 1.0;
-        else if (g > a.maxGain)
-            g = a.maxGain;
-        a.gain[a.gainOff[t] + b0 + (uint32_t)bl] = g;
+        a.gain[a.gainOff[t] + b0 + (uint32_t)bl] = follow_gain(ex, acc, a.maxGain);
     }
 }
 
@@ -166,8 +132,7 @@ __global__ __launch_bounds__(256) void follow_apply_kernel(const FollowArgs a, u
             const uint64_t k = k0 + (uint64_t)(u + q) * 256;
             if (k >= n)
                 continue;
-            const double ga = __dmul_rn(sG[u + q], fm), gc = __dmul_rn(sG[u + q + 1], f);
-            const double r = __dmul_rn(v[q], __dadd_rn(ga, gc));
+            const double r = follow_sample(v[q], sG[u + q], sG[u + q + 1], f, fm);
             if (out)
                 out[o0 + k] = r;
             if (pcm)
@@ -291,8 +256,7 @@ int32_t follow_envelope(ssym_ctx *ctx, const double *samples, const uint64_t *ou
     a.maxGain = max_gain;
     a.gain = dGain;
     // LDS for the launch's largest block: a batch of short targets keeps several workgroups on a CU
-    const size_t lds = (kWarpBin + 2 * (size_t)(std::min<uint64_t>(maxB, kFollowBlock) + kWarpTaps - 1) * kFollowPitch) * sizeof(double);
-    static_assert((kWarpBin + 2 * kFollowHops * kFollowPitch) * sizeof(double) <= 160 * 1024, "follow_gain_kernel: a CU's LDS");
+    const size_t lds = follow_lds_doubles(maxB) * sizeof(double);
     if (lds > 64 * 1024)
         SSYM_HIP_CHECK(ctx, hipFuncSetAttribute((const void *)follow_gain_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     const bool apply = dOut || dPcm;

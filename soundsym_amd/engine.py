@@ -811,6 +811,98 @@ class Resynth(_Lanes):
             pass
 
 
+FOLLOWER_MAX_LANES = 16384
+
+
+class Follower(_Lanes):
+    """`n_lanes` lanes of live envelope following (ssym_follower; definition in include/soundsym_amd.h and DESIGN.md
+    section 2 "Live envelope following"): a lane takes the resynthesis y and the reference x as they grow, in any amounts,
+    and releases every output hop once its two boundaries are settled -- two hops of look-ahead on both signals; from reset
+    to flush a lane's samples and gains are follow_envelope's for what it consumed, bit for bit.  n_samples: the samples the
+    last push / flush released, `samples` reads them."""
+
+    def __init__(self, engine: "Engine", ptr: int, n_lanes: int, max_gain: float):
+        self.engine, self.ptr, self.n_lanes, self.max_gain = engine, ptr, n_lanes, max_gain
+        self.n_samples = 0
+
+    def _ran(self, name: str, *args) -> int:
+        n = ctypes.c_uint64()
+        nat.check(getattr(nat.lib(), "ssym_follower_" + name)(self.engine.ctx, self.ptr, *args, ctypes.byref(n)), self.engine.ctx)
+        self.n_samples = int(n.value)
+        return self.n_samples
+
+    def _offsets(self, offsets, x, what: str) -> np.ndarray:
+        if offsets is None:
+            if self.n_lanes != 1:
+                raise ValueError(f"push: {what} offsets are needed with more than one lane")
+            return np.array([0, 0 if x is None else (int(x.numel()) if _is_device_tensor(x) else np.asarray(x).size)], dtype=np.uint64)
+        off = np.ascontiguousarray(offsets, dtype=np.uint64).reshape(-1)
+        if off.size != self.n_lanes + 1:
+            raise ValueError(f"push: n_lanes + 1 {what} offsets")
+        if off[0] != 0 or np.any(off[1:] < off[:-1]):
+            raise ValueError(f"push: the {what} offsets must start at 0 and not decrease")
+        return off
+
+    def push(self, samples, sample_offsets=None, ref=None, ref_offsets=None) -> int:
+        """ssym_follower_push: lane l consumes samples[sample_offsets[l]:sample_offsets[l+1]] of the resynthesis and
+        ref[ref_offsets[l]:ref_offsets[l+1]] of the reference (a follower of one lane takes the bare arrays).  Either is a
+        numpy array or f64 device memory (a contiguous torch CUDA tensor: Resynth.samples(on_device=True) passes straight
+        in); None holds nothing.  Returns the number of samples released."""
+        off, r_off = self._offsets(sample_offsets, samples, "sample"), self._offsets(ref_offsets, ref, "ref")
+        y_ptr, y_dev, keep_y = _follow_samples(samples, int(off[-1]), "samples")
+        x_ptr, x_dev, keep_x = _follow_samples(ref, int(r_off[-1]), "ref")
+        flags = (nat.FOLLOW_SAMPLES_DEVICE if y_dev else 0) | (nat.FOLLOW_REF_DEVICE if x_dev else 0)
+        n = self._ran("push", y_ptr, off.ctypes.data, x_ptr, r_off.ctypes.data, flags)
+        del keep_y, keep_x
+        return n
+
+    def flush(self, lane: int = 0) -> int:
+        """ssym_follower_flush: "the lane has ended" -- every remaining boundary is settled with the offline clipping, the
+        rest of the resynthesis leaves, and the lane consumes nothing more until `reset`."""
+        return self._ran("flush", self._lane(lane))
+
+    def samples(self, want_pcm32: bool = False, want_gains: bool = False, on_device: bool = False):
+        """What the last push / flush released: (lane_offsets uint64 [n_lanes + 1], samples f64 [n_samples]); with
+        want_pcm32 the int32 samples too; with want_gains also (gain_offsets uint64 [n_lanes + 1], gains f64) -- the gains
+        of the boundaries that call settled, lane by lane.  on_device: SSYM_OUT_DEVICE, samples, pcm and gains as torch
+        tensors in device memory (the offsets stay numpy arrays)."""
+        off, g_off = np.zeros(self.n_lanes + 1, dtype=np.uint64), np.zeros(self.n_lanes + 1, dtype=np.uint64)
+        device = self.engine.device if on_device else None
+        nat.check(nat.lib().ssym_follower_samples(self.engine.ctx, self.ptr, off.ctypes.data, None, None, g_off.ctypes.data, None, 0),
+                  self.engine.ctx)
+        n, n_gains = int(off[-1]), int(g_off[-1]) if want_gains else 0
+        (out, po), (pcm, pp), (gain, pg) = (_output(device, (n,), np.float64), _output(device, (n,), np.int32),
+                                            _output(device, (n_gains,), np.float64))
+        if n or n_gains:
+            nat.check(nat.lib().ssym_follower_samples(self.engine.ctx, self.ptr, None, po if n else None,
+                                                      pp if want_pcm32 and n else None, None, pg if n_gains else None,
+                                                      0 if device is None else nat.OUT_DEVICE), self.engine.ctx)
+        res = (off, out) + ((pcm,) if want_pcm32 else ())
+        return res + ((g_off, gain) if want_gains else ())
+
+    def counts(self):
+        """(ny, nx, released): samples of the resynthesis and of the reference consumed, and samples released, per lane
+        since its reset, uint64 [n_lanes] each."""
+        ny, nx, rel = (np.zeros(self.n_lanes, dtype=np.uint64) for _ in range(3))
+        nat.check(nat.lib().ssym_follower_counts(self.ptr, ny.ctypes.data, nx.ctypes.data, rel.ctypes.data), self.engine.ctx)
+        return ny, nx, rel
+
+    def reset(self, lane: int = 0) -> None:
+        """One lane back to "nothing consumed"."""
+        nat.check(nat.lib().ssym_follower_reset(self.engine.ctx, self.ptr, self._lane(lane)), self.engine.ctx)
+
+    def close(self):
+        if self.ptr and self.engine.ctx:
+            nat.lib().ssym_follower_destroy(self.engine.ctx, self.ptr)
+        self.ptr = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class Comm:
     """One rank of a source-sharded run: an RCCL communicator bound to an Engine (ssym_comm)."""
 
@@ -1472,6 +1564,19 @@ class Engine:
         out = ctypes.c_void_p()
         nat.check(nat.lib().ssym_resynth_create(self.ctx, samples_store.ptr, lanes, search, ctypes.byref(out)), self.ctx)
         return Resynth(self, out.value, samples_store, lanes, search)
+
+    def follower(self, n_lanes: int = 1, max_gain=FOLLOW_MAX_GAIN) -> Follower:
+        """ssym_follower_create: `n_lanes` lanes (1 ... 16 384) of live envelope following ("Live envelope following");
+        max_gain as follow_envelope's, finite and at least 1.  Any engine: nothing here aligns."""
+        gain = _follow_max_gain(max_gain)
+        lanes = int(n_lanes)
+        if lanes < 1 or lanes != n_lanes or isinstance(n_lanes, bool):
+            raise ValueError("n_lanes must be a whole number, at least 1")
+        if lanes > FOLLOWER_MAX_LANES:
+            raise ValueError(f"n_lanes must be at most {FOLLOWER_MAX_LANES}")
+        out = ctypes.c_void_p()
+        nat.check(nat.lib().ssym_follower_create(self.ctx, lanes, gain, ctypes.byref(out)), self.ctx)
+        return Follower(self, out.value, lanes, gain)
 
     @staticmethod
     def mfcc_num_frames(n_samples: int, pad_tail: bool = False) -> int:
