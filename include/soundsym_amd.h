@@ -1279,9 +1279,10 @@ SSYM_API int32_t ssym_spotter_create_step(ssym_ctx *ctx, const ssym_queries *q, 
  * handles, decreasing offsets, a lane outside the coverer, a handle of another context, a stream whose lanes or n_coeffs
  * differ: SSYM_E_INVALID with a message, the coverer as it was and the outputs unwritten.
  * The tables of one call are lanes x (W - 1 + new frames) x W x 12 bytes per source block; a push that would pass the
- * cover's 512 MiB runs as several slices of frames in the same call, with a commit after each and the same results.  One
- * synchronisation per slice.  ssym_get_timings afterwards: main_ms = the forward pass (gather and fold included),
- * reduce_ms = chain, commit and emission, n_pairs = n_sources x the frames the call consumed.
+ * cover's 512 MiB runs as several slices of frames in the same call, with a commit after each and the same results.  What
+ * earlier slices consumed stays consumed and is in the log (after any failure of a later slice out_n_pieces counts what the
+ * earlier ones logged).  One synchronisation per slice.  ssym_get_timings afterwards: main_ms = the forward pass (gather
+ * and fold included), reduce_ms = chain, commit and emission, n_pairs = n_sources x the frames the call consumed.
  *
  * ssym_coverer_create_gaps: a coverer whose chain takes the gap candidate of "Cover with gaps" at gap_cost per frame (>= 0 and
  *   finite, or +inf, which is ssym_coverer_create; NaN, negative or -inf: SSYM_E_INVALID).  Every other ssym_coverer_* call

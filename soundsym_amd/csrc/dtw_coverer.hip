@@ -38,7 +38,11 @@
 //             minimum, until all positions are equal.  Lane 0 counts the pieces from there down to done and writes them into
 //             the call's piece log in ascending start, with plain stores.  A flush is the same emission from lastFinite.
 // No kernel waits on another workgroup, none spins: stream order is the only ordering between them.
-// Host: the checks and the upload of push / follow / flush / reset are lane_feed.hpp's, and so is the piece log (LaneLog).
+// Host: the checks, the upload and the bodies of push / follow / flush / reset are lane_feed.hpp's, and so is the piece log
+// (LaneLog).  What the coverer shares with the mosaicker is lane_tiling.hpp's: the base of the handle, the dictionary check,
+// the first refusals of create, best's host body, the hand-over of a grown back-pointer store, and the loop over a call's
+// slices (tiling_run): gather and forward between its first two events, chain and commit between the last two.  A slice
+// that fails leaves through that loop's epilogue.  The slice's plan, frame buffer and bufOff are here (CovererSlices).
 //
 // Gaps (ssym_coverer_create_gaps).  The chain's step takes the gap candidate of "Cover with gaps": a frame left uncovered is a
 // piece of one frame with the source SSYM_COVER_GAP and the cost gap_cost.  1 <= W, so the horizon argument holds as it
@@ -47,6 +51,7 @@
 #include "dtw_wave.hpp"
 #include "dtw_cover_chain.hpp"
 #include "lane_feed.hpp"
+#include "lane_tiling.hpp"
 
 #include <algorithm>
 
@@ -76,19 +81,13 @@ struct CovStep {
 
 }  // namespace ssym
 
-struct ssym_coverer {
-    ssym_ctx *ctx = nullptr;
-    const ssym_dict *dict = nullptr;
-    uint32_t nLanes = 0, dim = 0, width = 0, ring = 0;
-    uint32_t dictN = 0;                      // the dictionary as it was at creation
-    uint64_t dictFrames = 0;
-    double penalty = 0.0;
-    double gapCost = 0.0;                    // +inf from ssym_coverer_create: no gaps
+// beside what every live tiling holds (lane_tiling.hpp; gapCost is +inf from ssym_coverer_create, and the words of the log,
+// the pieces of the last push / follow / flush, are lane, src, start, end)
+struct ssym_coverer : ssym::LaneTiling {
+    ssym_coverer() : LaneTiling(4) {}
+    uint32_t width = 0, ring = 0;
     uint64_t sliceMax = 0;                   // frames per lane and slice the scratch allows
-    // host mirrors of the lanes
-    std::vector<uint64_t> consumed;
-    std::vector<int64_t> done, lastFinite;
-    std::vector<uint8_t> ended;
+    std::vector<int64_t> lastFinite;         // host mirror of the lanes'
     // device
     double *tail = nullptr;                  // [nLanes][W - 1][dim]: the last min(n, W - 1) frames, oldest first
     double *ringD = nullptr;                 // [nLanes][ring]: best(e) at (e + 1) mod ring
@@ -98,8 +97,6 @@ struct ssym_coverer {
     uint64_t backCap = 0;                    // frames per lane of the back-pointer store
     double *bpCost = nullptr;                // [nLanes][backCap], frame e at e mod backCap
     uint32_t *bpLen = nullptr, *bpSrc = nullptr;
-    // the piece log: the pieces of the last push / follow / flush; the words are lane, src, start, end
-    ssym::LaneLog log{4};
 };
 
 namespace ssym {
@@ -347,23 +344,6 @@ void coverer_free(ssym_ctx *ctx, ssym_coverer *cv)
 
 constexpr const char *kNoun = "coverer";
 
-// what a call that reads the dictionary refuses
-int32_t check_dict(ssym_ctx *ctx, const ssym_coverer *cv, const char *fn)
-{
-    if (cv->dict->set.n != cv->dictN || cv->dict->set.total_frames != cv->dictFrames) {
-        ctx->err = std::string(fn) + ": the dictionary was appended to after the coverer was created; create a new coverer";
-        return SSYM_E_INVALID;
-    }
-    return SSYM_OK;
-}
-
-// the coverer as the lane feed (lane_feed.hpp) sees it: a flushed lane has ended, and push and follow read the dictionary
-LaneFeed feed_of(ssym_ctx *ctx, const ssym_coverer *cv)
-{
-    return LaneFeed{kNoun, "out_n_pieces", cv->nLanes, cv->dim, cv->consumed, &cv->ended, true,
-                    [ctx, cv](const char *fn) { return check_dict(ctx, cv, fn); }};
-}
-
 // the back-pointer store with room for `frames` per lane (a power of two); the uncommitted stretches move over
 int32_t back_store(ssym_ctx *ctx, ssym_coverer *cv, uint64_t frames)
 {
@@ -376,57 +356,28 @@ int32_t back_store(ssym_ctx *ctx, ssym_coverer *cv, uint64_t frames)
         rc = alloc_n(ctx, &len, count);
     if (rc == SSYM_OK)
         rc = alloc_n(ctx, &src, count);
-    if (rc != SSYM_OK) {
-        for (void *p : {(void *)cost, (void *)len, (void *)src})
-            if (p)
-                dev_free(ctx, p);
-        return rc;
-    }
-    if (cv->backCap) {
-        coverer_regrow_kernel<<<dim3(4, cv->nLanes), 256, 0, ctx->stream>>>(cv->lanes, cv->backCap, cap, cv->bpLen, cv->bpSrc,
-                                                                             cv->bpCost, len, src, cost);
-        const hipError_t e = hipGetLastError();
-        const hipError_t e2 = hipStreamSynchronize(ctx->stream);         // the old store is freed below
-        if (e != hipSuccess || e2 != hipSuccess) {
-            ctx->err = std::string("coverer: ") + hipGetErrorString(e != hipSuccess ? e : e2);
-            for (void *p : {(void *)cost, (void *)len, (void *)src})
-                dev_free(ctx, p);
-            return SSYM_E_HIP;
-        }
-        for (void *p : {(void *)cv->bpCost, (void *)cv->bpLen, (void *)cv->bpSrc})
-            dev_free(ctx, p);
-    }
-    cv->bpCost = cost;
-    cv->bpLen = len;
-    cv->bpSrc = src;
-    cv->backCap = cap;
-    return SSYM_OK;
+    return ring_swap(
+        ctx, kNoun, rc, {cv->bpCost, cv->bpLen, cv->bpSrc}, {cost, len, src}, cv->backCap != 0,
+        [&] {
+            coverer_regrow_kernel<<<dim3(4, cv->nLanes), 256, 0, ctx->stream>>>(cv->lanes, cv->backCap, cap, cv->bpLen, cv->bpSrc,
+                                                                                 cv->bpCost, len, src, cost);
+        },
+        [&] {
+            cv->bpCost = cost;
+            cv->bpLen = len;
+            cv->bpSrc = src;
+            cv->backCap = cap;
+        });
 }
 
 // ssym_coverer_create (gap_cost = +inf) and ssym_coverer_create_gaps: the chain's gap candidate is the only difference
 int32_t coverer_create(ssym_ctx *ctx, const char *fn, const ssym_dict *dict, uint32_t n_lanes, double piece_penalty, double gap_cost,
                        ssym_coverer **out)
 {
-    if (!out) {
-        ctx->err = std::string(fn) + ": out is NULL";
-        return SSYM_E_INVALID;
-    }
-    *out = nullptr;
-    int32_t rc = check_cover_ctx(ctx, fn);
-    if (rc != SSYM_OK)
-        return rc;
-    if (!dict || n_lanes == 0) {
-        ctx->err = std::string(fn) + ": the dictionary handle is NULL or n_lanes is 0";
-        return SSYM_E_INVALID;
-    }
-    rc = check_cover_prices(ctx, fn, piece_penalty, gap_cost);
+    int32_t rc = tiling_create_checks(ctx, fn, dict, n_lanes, piece_penalty, gap_cost, out);
     if (rc != SSYM_OK)
         return rc;
     const SegmentSet &src = dict->set;
-    if (src.n == 0) {
-        ctx->err = std::string(fn) + ": empty dictionary";
-        return SSYM_E_EMPTY_DICT;
-    }
     rc = check_cover_dict(ctx, fn, src);
     if (rc != SSYM_OK)
         return rc;
@@ -445,21 +396,11 @@ int32_t coverer_create(ssym_ctx *ctx, const char *fn, const ssym_dict *dict, uin
     }
     SSYM_HIP_CHECK(ctx, hipSetDevice(ctx->device));
     ssym_coverer *cv = new ssym_coverer;
-    cv->ctx = ctx;
-    cv->dict = dict;
-    cv->nLanes = n_lanes;
-    cv->dim = src.dim;
+    cv->bind(ctx, dict, n_lanes, piece_penalty, gap_cost);
     cv->width = W;
     cv->ring = lim.ring;
-    cv->dictN = src.n;
-    cv->dictFrames = src.total_frames;
-    cv->penalty = piece_penalty;
-    cv->gapCost = gap_cost;
     cv->sliceMax = std::min<uint64_t>(lim.scratch_bytes / perFrame - (W - 1), kLaneMaxFrames);
-    cv->consumed.assign(n_lanes, 0);
-    cv->done.assign(n_lanes, -1);
     cv->lastFinite.assign(n_lanes, -1);
-    cv->ended.assign(n_lanes, 0);
     rc = alloc_n(ctx, &cv->tail, (size_t)n_lanes * (W - 1) * src.dim);
     if (rc == SSYM_OK)
         rc = alloc_n(ctx, &cv->ringD, (size_t)n_lanes * cv->ring);
@@ -492,82 +433,71 @@ int32_t coverer_create(ssym_ctx *ctx, const char *fn, const ssym_dict *dict, uin
     return SSYM_OK;
 }
 
-// The body of push, follow and flush.  rows[l]: lane l's m[l] new frames (DEVICE); flushLane: the lane to flush, or kCoverNone.
-// The frames go through in slices of at most `slice` per lane, with a commit after each; the host reads the lanes' state
-// back after every slice, which is also the call's synchronisation.
-int32_t coverer_run(ssym_ctx *ctx, ssym_coverer *cv, const std::vector<const double *> &rows, const std::vector<uint64_t> &m,
-                    uint32_t flushLane, uint64_t *out_n_pieces)
-{
-    const uint32_t nL = cv->nLanes, dim = cv->dim, W = cv->width;
-    const SegmentSet &src = cv->dict->set;
-    hipStream_t st = ctx->stream;
-    ssym_timings tm{};
-    uint64_t slice = cv->sliceMax;
-    if (const char *k = ssym_knob("SSYM_COVERER_SLICE"))
-        slice = std::min<uint64_t>(slice, (uint64_t)std::max(1, atoi(k)));
-    int32_t rc = cv->log.begin(ctx, cv->consumed, cv->done, m, flushLane);
-    if (rc != SSYM_OK)
-        return rc;
-    for (uint32_t l = 0; l < nL; ++l)
-        tm.n_pairs += (uint64_t)src.n * m[l];
-    // the frame buffer of a slice: per lane with new frames, its tail and at most `slice` of them
-    uint64_t bufFrames = 0;
-    for (uint32_t l = 0; l < nL; ++l)
-        if (m[l])
-            bufFrames += (W - 1) + std::min(slice, m[l]);
-    Blocks bl(ctx);
-    double *buf = nullptr;
-    if (bufFrames) {
-        rc = bl.get(&buf, (size_t)bufFrames * dim);
-        if (rc != SSYM_OK)
-            return rc;
-    }
-    std::vector<uint64_t> at(nL, 0), bufOff((size_t)nL + 1);
-    std::vector<CovStep> steps(nL);
-    std::vector<CovLane> state(nL);
-    hipEvent_t *ev = ctx->ev;
-    bool flush = flushLane != kCoverNone;
-    for (;;) {
-        uint64_t frames = 0, need = 0, left = 0;
+// The coverer's part of a push, follow or flush (the loop is tiling_run, lane_tiling.hpp): the frames go through in slices of
+// at most `slice` per lane, and a slice's frame buffer has [tail | new] of every lane with new frames, lane l's at bufOff[l]
+// (it goes up with the steps).  The buffer is allocated with the first slice's room, behind the log's.
+struct CovererSlices {
+    ssym_ctx *ctx;
+    ssym_coverer *cv;
+    uint64_t slice;
+    Blocks &bl;
+    uint64_t bufFrames;                      // what the largest slice of the call needs
+    double *buf;
+    std::vector<uint64_t> bufOff;            // [nLanes + 1], in frames
+    CoverTables tab;                         // the forward pass's tables of the slice
+
+    int32_t plan(const TilingCall &call, std::vector<CovStep> &steps, uint64_t *left, uint64_t *need)
+    {
+        const uint32_t nL = cv->nLanes, W = cv->width;
+        uint64_t frames = 0;
         for (uint32_t l = 0; l < nL; ++l) {
-            const uint64_t ml = std::min(slice, m[l] - at[l]), n = cv->consumed[l];
             CovStep &s = steps[l];
-            s.rows = ml ? rows[l] + at[l] * dim : nullptr;
-            s.logAt = cv->log.off[l] + cv->log.count[l];
-            s.m = (uint32_t)ml;
+            const uint64_t ml = tiling_step(cv, call, l, slice, &s), n = cv->consumed[l];
             s.tail = (uint32_t)std::min<uint64_t>(n, W - 1);
-            s.flush = flush && l == flushLane;
             s.pad = 0;
             bufOff[l] = frames;
             frames += ml ? s.tail + ml : 0;
             if (ml)
-                need = std::max(need, n - (uint64_t)(cv->done[l] + 1) + ml);
-            left += ml;
+                *need = std::max(*need, n - (uint64_t)(cv->done[l] + 1) + ml);
+            *left += ml;
         }
         bufOff[nL] = frames;
-        if (left == 0 && !flush)
-            break;
-        if (need > cv->backCap) {
-            rc = back_store(ctx, cv, need);
+        return SSYM_OK;
+    }
+
+    int32_t grow(uint64_t need)
+    {
+        if (!buf && bufFrames) {
+            const int32_t rc = bl.get(&buf, (size_t)bufFrames * cv->dim);
             if (rc != SSYM_OK)
                 return rc;
         }
-        SSYM_HIP_CHECK(ctx, hipMemcpyAsync(cv->dSteps, steps.data(), sizeof(CovStep) * nL, hipMemcpyHostToDevice, st));
-        SSYM_HIP_CHECK(ctx, hipMemcpyAsync(cv->dBufOff, bufOff.data(), sizeof(uint64_t) * (nL + 1), hipMemcpyHostToDevice, st));
-        SSYM_HIP_CHECK(ctx, hipEventRecord(ev[0], st));
-        CoverTables tab{};
-        if (left) {
+        return need > cv->backCap ? back_store(ctx, cv, need) : SSYM_OK;
+    }
+
+    // gather, the new tails, and the tables of the buffer
+    int32_t forward(bool any)
+    {
+        const uint32_t nL = cv->nLanes, dim = cv->dim, W = cv->width;
+        hipStream_t st = ctx->stream;
+        tab = CoverTables{};
+        if (any) {
             const unsigned gx = (unsigned)std::min<uint64_t>(((uint64_t)(W - 1 + slice) * dim + 255) / 256, 64);
             coverer_gather_kernel<<<dim3(gx, nL), 256, 0, st>>>(cv->dSteps, cv->dBufOff, cv->tail, buf, dim, W - 1);
             SSYM_HIP_CHECK(ctx, hipGetLastError());
             coverer_tail_kernel<<<dim3(std::min(gx, 8u), nL), 256, 0, st>>>(cv->dSteps, cv->dBufOff, cv->tail, buf, dim, W - 1);
             SSYM_HIP_CHECK(ctx, hipGetLastError());
-            rc = cover_forward(ctx, src, buf, cv->dBufOff, bufOff.data(), nL, 0, 0, &tab);
-            if (rc != SSYM_OK)
-                return rc;
+            return cover_forward(ctx, cv->dict->set, buf, cv->dBufOff, bufOff.data(), nL, 0, 0, &tab);
         }
-        SSYM_HIP_CHECK(ctx, hipEventRecord(ev[1], st));
-        if (left) {
+        return SSYM_OK;
+    }
+
+    // the chain over the new ends, then the commit (or the flush's emission)
+    int32_t commit(bool any)
+    {
+        const uint32_t nL = cv->nLanes, W = cv->width;
+        hipStream_t st = ctx->stream;
+        if (any) {
             CovChainArgs c{};
             c.tabM = tab.tabM;
             c.tabSrc = tab.tabSrc;
@@ -577,7 +507,7 @@ int32_t coverer_run(ssym_ctx *ctx, ssym_coverer *cv, const std::vector<const dou
             c.ringD = cv->ringD;
             c.ring = cv->ring;
             c.width = W;
-            c.frames = frames;
+            c.frames = bufOff[nL];
             c.penalty = cv->penalty;
             c.gapCost = cv->gapCost;
             c.backCap = cv->backCap;
@@ -604,90 +534,35 @@ int32_t coverer_run(ssym_ctx *ctx, ssym_coverer *cv, const std::vector<const dou
         k.logCost = cv->log.cost;
         coverer_commit_kernel<<<nL, 64, 0, st>>>(k);
         SSYM_HIP_CHECK(ctx, hipGetLastError());
-        SSYM_HIP_CHECK(ctx, hipEventRecord(ev[2], st));
-        SSYM_HIP_CHECK(ctx, hipMemcpyAsync(state.data(), cv->lanes, sizeof(CovLane) * nL, hipMemcpyDeviceToHost, st));
-        SSYM_HIP_CHECK(ctx, hipStreamSynchronize(st));
-        for (uint32_t l = 0; l < nL; ++l) {
-            if (steps[l].m == 0 && !steps[l].flush)
-                continue;
-            cv->consumed[l] = (uint64_t)state[l].n;
-            cv->done[l] = state[l].done;
-            cv->lastFinite[l] = state[l].lastFinite;
-            cv->log.count[l] += state[l].count;
-            at[l] += steps[l].m;
-        }
-        tm.main_ms += ev_ms(ev[0], ev[1]);
-        tm.reduce_ms += ev_ms(ev[1], ev[2]);
-        tm.total_ms += ev_ms(ev[0], ev[2]);
-        tm.main_launches += left ? 1 : 0;
-        if (flush)
-            break;
+        return SSYM_OK;
     }
-    if (flush)
-        cv->ended[flushLane] = 1;
-    *out_n_pieces = cv->log.total();
-    ctx->timings = tm;
-    return SSYM_OK;
+
+    void fold(uint32_t l, const CovLane &lane) { cv->lastFinite[l] = lane.lastFinite; }
+};
+
+// what push, follow and flush hand to the entry bodies (lane_feed.hpp): the coverer's feed and its run
+LaneFeed coverer_feed(ssym_ctx *ctx, const ssym_coverer *cv)
+{
+    return feed_of(ctx, cv, kNoun, "out_n_pieces");
 }
 
-// push, follow and flush: the handle, the feed's checks and frames (lane_feed.hpp), then the run
-
-int32_t coverer_push(ssym_ctx *ctx, ssym_coverer *cv, const double *feats, const uint64_t *frame_offsets, uint32_t flags,
-                     uint64_t *out_n_pieces)
+auto coverer_run(ssym_ctx *ctx, ssym_coverer *cv, uint64_t *out_n_pieces)
 {
-    const char *fn = "ssym_coverer_push";
-    Blocks bl(ctx);
-    std::vector<const double *> rows;
-    std::vector<uint64_t> m;
-    int32_t rc = check_handle(ctx, cv, kNoun, fn);
-    if (rc == SSYM_OK)
-        rc = feed_of(ctx, cv).push(ctx, fn, feats, frame_offsets, out_n_pieces, bl, rows, m);
-    if (rc != SSYM_OK)
-        return rc;
-    return coverer_run(ctx, cv, rows, m, kCoverNone, out_n_pieces);
-}
-
-int32_t coverer_follow(ssym_ctx *ctx, ssym_coverer *cv, const ssym_stream *stream, uint32_t flags, uint64_t *out_n_pieces)
-{
-    const char *fn = "ssym_coverer_follow";
-    std::vector<const double *> rows;
-    std::vector<uint64_t> m;
-    int32_t rc = check_handle(ctx, cv, kNoun, fn);
-    if (rc == SSYM_OK)
-        rc = feed_of(ctx, cv).follow(ctx, fn, stream, out_n_pieces, rows, m);
-    if (rc != SSYM_OK)
-        return rc;
-    return coverer_run(ctx, cv, rows, m, kCoverNone, out_n_pieces);
-}
-
-int32_t coverer_flush(ssym_ctx *ctx, ssym_coverer *cv, uint32_t lane, uint64_t *out_n_pieces)
-{
-    const char *fn = "ssym_coverer_flush";
-    int32_t rc = check_handle(ctx, cv, kNoun, fn);
-    if (rc == SSYM_OK)
-        rc = feed_of(ctx, cv).lane(ctx, fn, lane, true, out_n_pieces);
-    if (rc != SSYM_OK)
-        return rc;
-    const std::vector<const double *> rows(cv->nLanes, nullptr);
-    const std::vector<uint64_t> m(cv->nLanes, 0);
-    return coverer_run(ctx, cv, rows, m, lane, out_n_pieces);
-}
-
-int32_t coverer_reset(ssym_ctx *ctx, ssym_coverer *cv, uint32_t lane)
-{
-    const char *fn = "ssym_coverer_reset";
-    int32_t rc = check_handle(ctx, cv, kNoun, fn);
-    if (rc == SSYM_OK)
-        rc = feed_of(ctx, cv).lane(ctx, fn, lane, false, nullptr);
-    if (rc != SSYM_OK)
-        return rc;
-    coverer_init_kernel<<<(cv->ring + 255) / 256, 256, 0, ctx->stream>>>(cv->lanes, cv->ringD, cv->ring, lane, 1u);
-    SSYM_HIP_CHECK(ctx, hipGetLastError());
-    SSYM_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    cv->consumed[lane] = 0;
-    cv->done[lane] = cv->lastFinite[lane] = -1;
-    cv->ended[lane] = 0;
-    return SSYM_OK;
+    return [=](const char *fn, const std::vector<const double *> &rows, const std::vector<uint64_t> &m, uint32_t flushLane) -> int32_t {
+        const uint32_t nL = cv->nLanes, W = cv->width;
+        uint64_t slice = cv->sliceMax;
+        if (const char *k = ssym_knob("SSYM_COVERER_SLICE"))
+            slice = std::min<uint64_t>(slice, (uint64_t)std::max(1, atoi(k)));
+        // the frame buffer of a slice: per lane with new frames, its tail and at most `slice` of them
+        uint64_t bufFrames = 0;
+        for (uint32_t l = 0; l < nL; ++l)
+            if (m[l])
+                bufFrames += (W - 1) + std::min(slice, m[l]);
+        Blocks bl(ctx);
+        CovererSlices o{ctx, cv, slice, bl, bufFrames, nullptr, std::vector<uint64_t>((size_t)nL + 1), CoverTables{}};
+        return tiling_run(ctx, cv, o, cv->dSteps, cv->lanes, cv->dict->set.n, fn, rows, m, flushLane, out_n_pieces,
+                          Upload{cv->dBufOff, o.bufOff.data(), sizeof(uint64_t) * (nL + 1)});
+    };
 }
 
 int32_t coverer_pieces(ssym_ctx *ctx, const ssym_coverer *cv, uint32_t *out_lane, uint32_t *out_src, uint32_t *out_start,
@@ -704,23 +579,12 @@ int32_t coverer_pieces(ssym_ctx *ctx, const ssym_coverer *cv, uint32_t *out_lane
 int32_t coverer_best(ssym_ctx *ctx, const ssym_coverer *cv, double *out_total, uint32_t *out_covered, uint32_t *out_committed,
                      uint32_t flags)
 {
-    int32_t rc = check_handle(ctx, cv, kNoun, "ssym_coverer_best");
-    if (rc != SSYM_OK)
-        return rc;
-    if (!out_total && !out_covered && !out_committed)
-        return SSYM_OK;
-    SSYM_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-    const uint32_t nL = cv->nLanes;
-    // the caller's device arrays in place, or one f64 and one u32 block copied back
-    StagedOut out(flags, {{out_total, nL}}, {{out_covered, nL}, {out_committed, nL}});
-    Blocks bl(ctx);
-    rc = out.alloc(bl);
-    if (rc != SSYM_OK)
-        return rc;
-    coverer_best_kernel<<<(nL + 255) / 256, 256, 0, ctx->stream>>>(cv->lanes, cv->ringD, cv->ring, nL, out.f64[0], out.u32[0],
-                                                                    out.u32[1]);
-    SSYM_HIP_CHECK(ctx, hipGetLastError());
-    return out.finish(ctx);
+    return tiling_best(ctx, cv, kNoun, "ssym_coverer_best", out_total, out_covered, out_committed, flags,
+                       [&](double *total, uint32_t *covered, uint32_t *committed) {
+                           const uint32_t nL = cv->nLanes;
+                           coverer_best_kernel<<<(nL + 255) / 256, 256, 0, ctx->stream>>>(cv->lanes, cv->ringD, cv->ring, nL, total,
+                                                                                           covered, committed);
+                       });
 }
 
 }  // namespace
@@ -751,29 +615,19 @@ int32_t ssym_coverer_create_gaps(ssym_ctx *ctx, const ssym_dict *dict, uint32_t 
 
 int32_t ssym_coverer_destroy(ssym_ctx *ctx, ssym_coverer *cv)
 {
-    if (!cv)
-        return SSYM_OK;
-    if (!ctx || cv->ctx != ctx)
-        return SSYM_E_INVALID;
-    (void)hipSetDevice(ctx->device);
-    (void)hipStreamSynchronize(ctx->stream);
-    coverer_free(ctx, cv);
-    return SSYM_OK;
+    return lane_destroy(ctx, cv, coverer_free);
 }
 
 int32_t ssym_coverer_push(ssym_ctx *ctx, ssym_coverer *cv, const double *feats, const uint64_t *frame_offsets, uint32_t flags,
                           uint64_t *out_n_pieces)
 {
-    if (!ctx)
-        return SSYM_E_INVALID;
-    return guarded(ctx, [&]() -> int32_t { return coverer_push(ctx, cv, feats, frame_offsets, flags, out_n_pieces); });
+    return lane_push(ctx, cv, kNoun, "ssym_coverer_push", coverer_feed, feats, frame_offsets, out_n_pieces,
+                     coverer_run(ctx, cv, out_n_pieces));
 }
 
 int32_t ssym_coverer_follow(ssym_ctx *ctx, ssym_coverer *cv, const ssym_stream *stream, uint32_t flags, uint64_t *out_n_pieces)
 {
-    if (!ctx)
-        return SSYM_E_INVALID;
-    return guarded(ctx, [&]() -> int32_t { return coverer_follow(ctx, cv, stream, flags, out_n_pieces); });
+    return lane_follow(ctx, cv, kNoun, "ssym_coverer_follow", coverer_feed, stream, out_n_pieces, coverer_run(ctx, cv, out_n_pieces));
 }
 
 int32_t ssym_coverer_pieces(ssym_ctx *ctx, const ssym_coverer *cv, uint32_t *out_lane, uint32_t *out_src, uint32_t *out_start,
@@ -788,9 +642,7 @@ int32_t ssym_coverer_pieces(ssym_ctx *ctx, const ssym_coverer *cv, uint32_t *out
 
 int32_t ssym_coverer_flush(ssym_ctx *ctx, ssym_coverer *cv, uint32_t lane, uint64_t *out_n_pieces)
 {
-    if (!ctx)
-        return SSYM_E_INVALID;
-    return guarded(ctx, [&]() -> int32_t { return coverer_flush(ctx, cv, lane, out_n_pieces); });
+    return lane_flush(ctx, cv, kNoun, "ssym_coverer_flush", coverer_feed, lane, out_n_pieces, coverer_run(ctx, cv, out_n_pieces));
 }
 
 int32_t ssym_coverer_best(ssym_ctx *ctx, const ssym_coverer *cv, double *out_total, uint32_t *out_covered,
@@ -814,9 +666,15 @@ int32_t ssym_coverer_counts(const ssym_coverer *cv, uint64_t *out_frames, uint64
 
 int32_t ssym_coverer_reset(ssym_ctx *ctx, ssym_coverer *cv, uint32_t lane)
 {
-    if (!ctx)
-        return SSYM_E_INVALID;
-    return guarded(ctx, [&]() -> int32_t { return coverer_reset(ctx, cv, lane); });
+    return lane_reset(ctx, cv, kNoun, "ssym_coverer_reset", coverer_feed, lane, [&]() -> int32_t {
+        coverer_init_kernel<<<(cv->ring + 255) / 256, 256, 0, ctx->stream>>>(cv->lanes, cv->ringD, cv->ring, lane, 1u);
+        SSYM_HIP_CHECK(ctx, hipGetLastError());
+        SSYM_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+        cv->consumed[lane] = 0;
+        cv->done[lane] = cv->lastFinite[lane] = -1;
+        cv->ended[lane] = 0;
+        return SSYM_OK;
+    });
 }
 
 }  // extern "C"

@@ -46,10 +46,15 @@
 //             (src, frame, cost) are dtw_mosaic_common.hpp's (mosaic_enter / mosaic_back, mosaic_walk, mosaic_frame), the ones
 //             mosaic_backtrace_kernel runs on the offline tables.  A flush is the same emission from arg(lastFinite).
 //   regrow    mosaicker_regrow_kernel moves the uncommitted columns when the ring doubles.
-// Host: the checks and the upload of push / follow / flush / reset are lane_feed.hpp's, and so is the frame log (LaneLog).
+// Host: the checks, the upload and the bodies of push / follow / flush / reset are lane_feed.hpp's, and so is the frame log
+// (LaneLog).  What the mosaicker shares with the coverer is lane_tiling.hpp's: the base of the handle, the dictionary check,
+// the first refusals of create, best's host body, the hand-over of a grown ring, and the loop over a call's slices
+// (tiling_run): forward between its first two events, commit between the last two.  A slice that is refused or fails leaves
+// through that loop's epilogue.  The slice's plan with its budget refusal is here (MosaickerSlices).
 // No workgroup waits on another: no spin wait; stream order is the only ordering between kernels.
 #include "dtw_mosaic_common.hpp"
 #include "lane_feed.hpp"
+#include "lane_tiling.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -81,19 +86,15 @@ struct MosStep {
 
 }  // namespace ssym
 
-struct ssym_mosaicker {
-    ssym_ctx *ctx = nullptr;
-    const ssym_dict *dict = nullptr;
-    uint32_t nLanes = 0, dim = 0, G = 0;
-    uint32_t dictN = 0;                      // the dictionary as it was at creation
-    uint64_t dictFrames = 0;
-    double penalty = 0.0, gapCost = 0.0;     // gapCost +inf: no gaps
+// beside what every live tiling holds (lane_tiling.hpp; the words of the log, the frames of the last push / follow / flush,
+// are lane, column, src, frame, start)
+struct ssym_mosaicker : ssym::LaneTiling {
+    ssym_mosaicker() : LaneTiling(5) {}
+    uint32_t G = 0;
     uint64_t budget = 0;                     // bytes the object may own
     uint64_t fixedBytes = 0;                 // what it owns beside the ring
-    // host mirrors of the lanes
-    std::vector<uint64_t> consumed;
-    std::vector<int64_t> done, stored;
-    std::vector<uint8_t> ended, dead;
+    std::vector<int64_t> stored;             // host mirrors of the lanes'
+    std::vector<uint8_t> dead;
     // device
     double *srcT = nullptr;                  // [dim][G]
     uint8_t *posc = nullptr;                 // [G]
@@ -105,9 +106,6 @@ struct ssym_mosaicker {
     uint8_t *dir = nullptr;                  // [nLanes][cap][G], column j at j mod cap
     uint32_t *arg = nullptr;                 // [nLanes][cap]
     double *frames = nullptr;                // [nLanes][cap][dim]
-    // the frame log: the frames of the last push / follow / flush; the words are lane, column, src, frame, start
-    ssym::LaneLog log{5};
-    uint64_t calls = 0;                      // push / follow / flush calls that began a log (host only): names a log to its reader
 };
 
 namespace ssym {
@@ -355,23 +353,6 @@ void mosaicker_free(ssym_ctx *ctx, ssym_mosaicker *mk)
 
 constexpr const char *kNoun = "mosaicker";
 
-// what a call that reads the dictionary refuses
-int32_t check_dict(ssym_ctx *ctx, const ssym_mosaicker *mk, const char *fn)
-{
-    if (mk->dict->set.n != mk->dictN || mk->dict->set.total_frames != mk->dictFrames) {
-        ctx->err = std::string(fn) + ": the dictionary was appended to after the mosaicker was created; create a new mosaicker";
-        return SSYM_E_INVALID;
-    }
-    return SSYM_OK;
-}
-
-// the mosaicker as the lane feed (lane_feed.hpp) sees it: a flushed lane has ended, and push and follow read the dictionary
-LaneFeed feed_of(ssym_ctx *ctx, const ssym_mosaicker *mk)
-{
-    return LaneFeed{kNoun, "out_n_frames", mk->nLanes, mk->dim, mk->consumed, &mk->ended, true,
-                    [ctx, mk](const char *fn) { return check_dict(ctx, mk, fn); }};
-}
-
 // bytes of one ring column of one lane: the direction bytes, arg and the target frame
 uint64_t column_bytes(uint64_t G, uint32_t dim)
 {
@@ -389,31 +370,18 @@ int32_t ring_store(ssym_ctx *ctx, ssym_mosaicker *mk, uint64_t cap)
         rc = alloc_n(ctx, &arg, (size_t)mk->nLanes * cap);
     if (rc == SSYM_OK)
         rc = alloc_n(ctx, &frames, (size_t)mk->nLanes * cap * mk->dim);
-    if (rc != SSYM_OK) {
-        for (void *p : {(void *)dir, (void *)arg, (void *)frames})
-            if (p)
-                dev_free(ctx, p);
-        return rc;
-    }
-    if (mk->cap) {
-        mosaicker_regrow_kernel<<<dim3(16, mk->nLanes), 256, 0, ctx->stream>>>(mk->lanes, mk->G, mk->dim, mk->cap, cap, mk->dir, mk->arg,
-                                                                               mk->frames, dir, arg, frames);
-        const hipError_t e = hipGetLastError();
-        const hipError_t e2 = hipStreamSynchronize(ctx->stream);         // the old ring is freed below
-        if (e != hipSuccess || e2 != hipSuccess) {
-            ctx->err = std::string("mosaicker: ") + hipGetErrorString(e != hipSuccess ? e : e2);
-            for (void *p : {(void *)dir, (void *)arg, (void *)frames})
-                dev_free(ctx, p);
-            return SSYM_E_HIP;
-        }
-        for (void *p : {(void *)mk->dir, (void *)mk->arg, (void *)mk->frames})
-            dev_free(ctx, p);
-    }
-    mk->dir = dir;
-    mk->arg = arg;
-    mk->frames = frames;
-    mk->cap = cap;
-    return SSYM_OK;
+    return ring_swap(
+        ctx, kNoun, rc, {mk->dir, mk->arg, mk->frames}, {dir, arg, frames}, mk->cap != 0,
+        [&] {
+            mosaicker_regrow_kernel<<<dim3(16, mk->nLanes), 256, 0, ctx->stream>>>(mk->lanes, mk->G, mk->dim, mk->cap, cap, mk->dir,
+                                                                                   mk->arg, mk->frames, dir, arg, frames);
+        },
+        [&] {
+            mk->dir = dir;
+            mk->arg = arg;
+            mk->frames = frames;
+            mk->cap = cap;
+        });
 }
 
 uint64_t knob_u64(const char *name, uint64_t otherwise)
@@ -426,26 +394,10 @@ int32_t mosaicker_create(ssym_ctx *ctx, const ssym_dict *dict, uint32_t n_lanes,
                          ssym_mosaicker **out)
 {
     const char *fn = "ssym_mosaicker_create";
-    if (!out) {
-        ctx->err = std::string(fn) + ": out is NULL";
-        return SSYM_E_INVALID;
-    }
-    *out = nullptr;
-    int32_t rc = check_cover_ctx(ctx, fn);
-    if (rc != SSYM_OK)
-        return rc;
-    if (!dict || n_lanes == 0) {
-        ctx->err = std::string(fn) + ": the dictionary handle is NULL or n_lanes is 0";
-        return SSYM_E_INVALID;
-    }
-    rc = check_cover_prices(ctx, fn, piece_penalty, gap_cost);
+    int32_t rc = tiling_create_checks(ctx, fn, dict, n_lanes, piece_penalty, gap_cost, out);
     if (rc != SSYM_OK)
         return rc;
     const SegmentSet &src = dict->set;
-    if (src.n == 0) {
-        ctx->err = std::string(fn) + ": empty dictionary";
-        return SSYM_E_EMPTY_DICT;
-    }
     if (src.dim > kMosaicMaxDim) {
         ctx->err = std::string(fn) + ": frames have more than " + std::to_string(kMosaicMaxDim) + " values";
         return SSYM_E_UNSUPPORTED;
@@ -467,21 +419,11 @@ int32_t mosaicker_create(ssym_ctx *ctx, const ssym_dict *dict, uint32_t n_lanes,
     }
     SSYM_HIP_CHECK(ctx, hipSetDevice(ctx->device));
     ssym_mosaicker *mk = new ssym_mosaicker;
-    mk->ctx = ctx;
-    mk->dict = dict;
-    mk->nLanes = n_lanes;
-    mk->dim = src.dim;
+    mk->bind(ctx, dict, n_lanes, piece_penalty, gap_cost);
     mk->G = (uint32_t)G;
-    mk->dictN = src.n;
-    mk->dictFrames = src.total_frames;
-    mk->penalty = piece_penalty;
-    mk->gapCost = gap_cost;
     mk->budget = budget;
     mk->fixedBytes = fixed;
-    mk->consumed.assign(n_lanes, 0);
-    mk->done.assign(n_lanes, -1);
     mk->stored.assign(n_lanes, 0);
-    mk->ended.assign(n_lanes, 0);
     mk->dead.assign(n_lanes, 0);
     // the initial ring: the largest power of two <= 1024 columns with lanes x cap x (G + 4) <= 64 MiB, 16 at least, within
     // the budget
@@ -530,193 +472,110 @@ int32_t mosaicker_create(ssym_ctx *ctx, const ssym_dict *dict, uint32_t n_lanes,
     return SSYM_OK;
 }
 
-// The body of push, follow and flush.  rows[l]: lane l's m[l] new frames (DEVICE); flushLane: the lane to flush, or kCoverNone.
-// The frames go through in slices of at most `slice` per lane, with a commit after each; the host reads the lanes' records
-// back after every slice, which is also the call's synchronisation.
-int32_t mosaicker_run(ssym_ctx *ctx, ssym_mosaicker *mk, const char *fn, const std::vector<const double *> &rows,
-                      const std::vector<uint64_t> &m, uint32_t flushLane, uint64_t *out_n_frames)
-{
-    const uint32_t nL = mk->nLanes, dim = mk->dim;
-    const SegmentSet &src = mk->dict->set;
-    hipStream_t st = ctx->stream;
-    ssym_timings tm{};
-    const uint64_t sliceMax = std::max<uint64_t>(knob_u64("SSYM_MOSAICKER_SLICE", kLaneMaxFrames), 1);
-    // the most columns a ring may grow to within the budget (a power of two): while it doubles, the ring it leaves (half of
-    // it at most) exists beside it
-    uint64_t capMax = kMosaickerRingMin;
-    while ((uint64_t)nL * (capMax * 3) * column_bytes(mk->G, dim) <= mk->budget - mk->fixedBytes)
-        capMax *= 2;
-    capMax = std::max(capMax, mk->cap);
-    int32_t rc = mk->log.begin(ctx, mk->consumed, mk->done, m, flushLane);
-    if (rc != SSYM_OK)
-        return rc;
-    ++mk->calls;
-    for (uint32_t l = 0; l < nL; ++l)
-        tm.n_pairs += (uint64_t)mk->G * m[l];                 // cells
-    std::vector<uint64_t> at(nL, 0);
-    std::vector<MosStep> steps(nL);
-    std::vector<MosLane> state(nL);
-    hipEvent_t *ev = ctx->ev;
-    const bool flush = flushLane != kCoverNone;
-    int32_t result = SSYM_OK;
-    for (;;) {
+// The mosaicker's part of a push, follow or flush (the loop is tiling_run, lane_tiling.hpp): the frames go through in slices
+// of at most sliceMax per lane, and of no more than the ring can take beside what it holds.
+struct MosaickerSlices {
+    ssym_ctx *ctx;
+    ssym_mosaicker *mk;
+    uint64_t sliceMax;
+    uint64_t capMax;                         // the most columns the ring may grow to within the budget
+    MosCommitArgs k;                         // the slice's kernel arguments
+
+    // columns of lane l the ring holds uncommitted
+    uint64_t pending(uint32_t l) const { return (uint64_t)(mk->stored[l] - (mk->done[l] + 1)); }
+
+    int32_t plan(const TilingCall &call, std::vector<MosStep> &steps, uint64_t *left, uint64_t *need)
+    {
+        const uint32_t nL = mk->nLanes;
         // the slice: what the ring takes beside the longest uncommitted stretch of a lane that still has frames
-        uint64_t left = 0, pending = 0;
+        uint64_t most = 0;
         for (uint32_t l = 0; l < nL; ++l)
-            if (m[l] > at[l]) {
-                left += m[l] - at[l];
+            if (call.m[l] > call.at[l]) {
+                *left += call.m[l] - call.at[l];
                 if (!mk->dead[l])
-                    pending = std::max(pending, (uint64_t)(mk->stored[l] - (mk->done[l] + 1)));
+                    most = std::max(most, pending(l));
             }
-        if (left == 0 && !flush)
-            break;
         uint64_t slice = sliceMax;
-        if (left) {
-            if (pending >= capMax) {
-                ctx->err = std::string(fn) + ": the uncommitted columns of a lane fill the " + std::to_string(mk->budget >> 20) +
-                           " MiB the mosaicker may own (" + std::to_string(pending) + " columns of " +
-                           std::to_string(column_bytes(mk->G, dim)) + " bytes on " + std::to_string(nL) +
+        if (*left) {
+            if (most >= capMax) {
+                ctx->err = std::string(call.fn) + ": the uncommitted columns of a lane fill the " + std::to_string(mk->budget >> 20) +
+                           " MiB the mosaicker may own (" + std::to_string(most) + " columns of " +
+                           std::to_string(column_bytes(mk->G, mk->dim)) + " bytes on " + std::to_string(nL) +
                            " lanes); flush the lane (ssym_mosaicker_flush) and reset it";
-                result = SSYM_E_UNSUPPORTED;
-                break;
+                return SSYM_E_UNSUPPORTED;
             }
-            slice = std::min(slice, capMax - pending);
+            slice = std::min(slice, capMax - most);
         }
-        uint64_t need = 0;
         for (uint32_t l = 0; l < nL; ++l) {
-            const uint64_t ml = std::min(slice, m[l] - at[l]);
-            MosStep &s = steps[l];
-            s.rows = ml ? rows[l] + at[l] * dim : nullptr;
-            s.logAt = mk->log.off[l] + mk->log.count[l];
-            s.m = (uint32_t)ml;
-            s.flush = flush && l == flushLane;
+            const uint64_t ml = tiling_step(mk, call, l, slice, &steps[l]);
             if (ml && !mk->dead[l])
-                need = std::max(need, (uint64_t)(mk->stored[l] - (mk->done[l] + 1)) + ml);
+                *need = std::max(*need, pending(l) + ml);
         }
-        // the slice's device work; a failure leaves through the epilogue below, which reports what earlier slices logged
-        rc = [&]() -> int32_t {
-            if (need > mk->cap) {
-                const int32_t grown = ring_store(ctx, mk, pow2_at_least(need));
-                if (grown != SSYM_OK)
-                    return grown;
-            }
-            SSYM_HIP_CHECK(ctx, hipMemcpyAsync(mk->dSteps, steps.data(), sizeof(MosStep) * nL, hipMemcpyHostToDevice, st));
-            SSYM_HIP_CHECK(ctx, hipEventRecord(ev[0], st));
-            MosCommitArgs k{};
-            k.steps = mk->dSteps;
-            k.lanes = mk->lanes;
-            k.k = MosaicCore{mk->G, dim, ctx->squared, mk->penalty, mk->gapCost, mk->posc, mk->srcT, mk->slab};
-            k.srcRaw = src.raw;
-            k.srcOff = src.off;
-            k.nSrc = src.n;
-            k.keys = mk->keys;
-            k.cap = mk->cap;
-            k.dir = mk->dir;
-            k.arg = mk->arg;
-            k.frames = mk->frames;
-            k.logLane = mk->log.word(0);
-            k.logColumn = mk->log.word(1);
-            k.logSrc = mk->log.word(2);
-            k.logFrame = mk->log.word(3);
-            k.logStart = mk->log.word(4);
-            k.logCost = mk->log.cost;
-            if (left) {
-                mosaicker_forward_kernel<<<nL, kMosaicThreads, 0, st>>>(k);          // (its part of the arguments)
-                SSYM_HIP_CHECK(ctx, hipGetLastError());
-            }
-            SSYM_HIP_CHECK(ctx, hipEventRecord(ev[1], st));
-            mosaicker_commit_kernel<<<nL, kMosaicThreads, 0, st>>>(k);
-            SSYM_HIP_CHECK(ctx, hipGetLastError());
-            SSYM_HIP_CHECK(ctx, hipEventRecord(ev[2], st));
-            SSYM_HIP_CHECK(ctx, hipMemcpyAsync(state.data(), mk->lanes, sizeof(MosLane) * nL, hipMemcpyDeviceToHost, st));
-            SSYM_HIP_CHECK(ctx, hipStreamSynchronize(st));
-            return SSYM_OK;
-        }();
-        if (rc != SSYM_OK) {
-            result = rc;
-            break;
-        }
-        for (uint32_t l = 0; l < nL; ++l) {
-            if (steps[l].m == 0 && !steps[l].flush)
-                continue;
-            mk->consumed[l] = (uint64_t)state[l].n;
-            mk->done[l] = state[l].done;
-            mk->stored[l] = state[l].stored;
-            mk->dead[l] = state[l].n > 0 && !(state[l].best < __builtin_inf());
-            mk->log.count[l] += state[l].count;
-            at[l] += steps[l].m;
-        }
-        tm.main_ms += ev_ms(ev[0], ev[1]);
-        tm.reduce_ms += ev_ms(ev[1], ev[2]);
-        tm.total_ms += ev_ms(ev[0], ev[2]);
-        tm.main_launches += left ? 1 : 0;
-        if (flush)
-            break;
+        return SSYM_OK;
     }
-    if (flush && result == SSYM_OK)
-        mk->ended[flushLane] = 1;
-    *out_n_frames = mk->log.total();
-    ctx->timings = tm;
-    return result;
+
+    int32_t grow(uint64_t need) { return need > mk->cap ? ring_store(ctx, mk, pow2_at_least(need)) : SSYM_OK; }
+
+    int32_t forward(bool any)
+    {
+        const SegmentSet &src = mk->dict->set;
+        k = MosCommitArgs{};
+        k.steps = mk->dSteps;
+        k.lanes = mk->lanes;
+        k.k = MosaicCore{mk->G, mk->dim, ctx->squared, mk->penalty, mk->gapCost, mk->posc, mk->srcT, mk->slab};
+        k.srcRaw = src.raw;
+        k.srcOff = src.off;
+        k.nSrc = src.n;
+        k.keys = mk->keys;
+        k.cap = mk->cap;
+        k.dir = mk->dir;
+        k.arg = mk->arg;
+        k.frames = mk->frames;
+        k.logLane = mk->log.word(0);
+        k.logColumn = mk->log.word(1);
+        k.logSrc = mk->log.word(2);
+        k.logFrame = mk->log.word(3);
+        k.logStart = mk->log.word(4);
+        k.logCost = mk->log.cost;
+        if (any) {
+            mosaicker_forward_kernel<<<mk->nLanes, kMosaicThreads, 0, ctx->stream>>>(k);          // (its part of the arguments)
+            SSYM_HIP_CHECK(ctx, hipGetLastError());
+        }
+        return SSYM_OK;
+    }
+
+    int32_t commit(bool)
+    {
+        mosaicker_commit_kernel<<<mk->nLanes, kMosaicThreads, 0, ctx->stream>>>(k);
+        SSYM_HIP_CHECK(ctx, hipGetLastError());
+        return SSYM_OK;
+    }
+
+    void fold(uint32_t l, const MosLane &lane)
+    {
+        mk->stored[l] = lane.stored;
+        mk->dead[l] = lane.n > 0 && !(lane.best < __builtin_inf());
+    }
+};
+
+// what push, follow and flush hand to the entry bodies (lane_feed.hpp): the mosaicker's feed and its run
+LaneFeed mosaicker_feed(ssym_ctx *ctx, const ssym_mosaicker *mk)
+{
+    return feed_of(ctx, mk, kNoun, "out_n_frames");
 }
 
-int32_t mosaicker_push(ssym_ctx *ctx, ssym_mosaicker *mk, const double *feats, const uint64_t *frame_offsets, uint32_t flags,
-                       uint64_t *out_n_frames)
+auto mosaicker_run(ssym_ctx *ctx, ssym_mosaicker *mk, uint64_t *out_n_frames)
 {
-    const char *fn = "ssym_mosaicker_push";
-    Blocks bl(ctx);
-    std::vector<const double *> rows;
-    std::vector<uint64_t> m;
-    int32_t rc = check_handle(ctx, mk, kNoun, fn);
-    if (rc == SSYM_OK)
-        rc = feed_of(ctx, mk).push(ctx, fn, feats, frame_offsets, out_n_frames, bl, rows, m);
-    if (rc != SSYM_OK)
-        return rc;
-    return mosaicker_run(ctx, mk, fn, rows, m, kCoverNone, out_n_frames);
-}
-
-int32_t mosaicker_follow(ssym_ctx *ctx, ssym_mosaicker *mk, const ssym_stream *stream, uint32_t flags, uint64_t *out_n_frames)
-{
-    const char *fn = "ssym_mosaicker_follow";
-    std::vector<const double *> rows;
-    std::vector<uint64_t> m;
-    int32_t rc = check_handle(ctx, mk, kNoun, fn);
-    if (rc == SSYM_OK)
-        rc = feed_of(ctx, mk).follow(ctx, fn, stream, out_n_frames, rows, m);
-    if (rc != SSYM_OK)
-        return rc;
-    return mosaicker_run(ctx, mk, fn, rows, m, kCoverNone, out_n_frames);
-}
-
-int32_t mosaicker_flush(ssym_ctx *ctx, ssym_mosaicker *mk, uint32_t lane, uint64_t *out_n_frames)
-{
-    const char *fn = "ssym_mosaicker_flush";
-    int32_t rc = check_handle(ctx, mk, kNoun, fn);
-    if (rc == SSYM_OK)
-        rc = feed_of(ctx, mk).lane(ctx, fn, lane, true, out_n_frames);
-    if (rc != SSYM_OK)
-        return rc;
-    const std::vector<const double *> rows(mk->nLanes, nullptr);
-    const std::vector<uint64_t> m(mk->nLanes, 0);
-    return mosaicker_run(ctx, mk, fn, rows, m, lane, out_n_frames);
-}
-
-int32_t mosaicker_reset(ssym_ctx *ctx, ssym_mosaicker *mk, uint32_t lane)
-{
-    const char *fn = "ssym_mosaicker_reset";
-    int32_t rc = check_handle(ctx, mk, kNoun, fn);
-    if (rc == SSYM_OK)
-        rc = feed_of(ctx, mk).lane(ctx, fn, lane, false, nullptr);
-    if (rc != SSYM_OK)
-        return rc;
-    mosaicker_init_kernel<<<1, 256, 0, ctx->stream>>>(mk->lanes, lane, 1u);
-    SSYM_HIP_CHECK(ctx, hipGetLastError());
-    SSYM_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    mk->consumed[lane] = 0;
-    mk->done[lane] = -1;
-    mk->stored[lane] = 0;
-    mk->ended[lane] = mk->dead[lane] = 0;
-    return SSYM_OK;
+    return [=](const char *fn, const std::vector<const double *> &rows, const std::vector<uint64_t> &m, uint32_t flushLane) -> int32_t {
+        const uint64_t sliceMax = std::max<uint64_t>(knob_u64("SSYM_MOSAICKER_SLICE", kLaneMaxFrames), 1);
+        // the most columns a ring may grow to within the budget (a power of two): while it doubles, the ring it leaves (half
+        // of it at most) exists beside it
+        uint64_t capMax = kMosaickerRingMin;
+        while ((uint64_t)mk->nLanes * (capMax * 3) * column_bytes(mk->G, mk->dim) <= mk->budget - mk->fixedBytes)
+            capMax *= 2;
+        MosaickerSlices o{ctx, mk, sliceMax, std::max(capMax, mk->cap), MosCommitArgs{}};
+        return tiling_run(ctx, mk, o, mk->dSteps, mk->lanes, mk->G, fn, rows, m, flushLane, out_n_frames);
+    };
 }
 
 int32_t mosaicker_frames(ssym_ctx *ctx, const ssym_mosaicker *mk, uint32_t *out_lane, uint32_t *out_column, uint32_t *out_src,
@@ -733,22 +592,11 @@ int32_t mosaicker_frames(ssym_ctx *ctx, const ssym_mosaicker *mk, uint32_t *out_
 int32_t mosaicker_best(ssym_ctx *ctx, const ssym_mosaicker *mk, double *out_total, uint32_t *out_covered, uint32_t *out_committed,
                        uint32_t flags)
 {
-    int32_t rc = check_handle(ctx, mk, kNoun, "ssym_mosaicker_best");
-    if (rc != SSYM_OK)
-        return rc;
-    if (!out_total && !out_covered && !out_committed)
-        return SSYM_OK;
-    SSYM_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-    const uint32_t nL = mk->nLanes;
-    // the caller's device arrays in place, or one f64 and one u32 block copied back
-    StagedOut out(flags, {{out_total, nL}}, {{out_covered, nL}, {out_committed, nL}});
-    Blocks bl(ctx);
-    rc = out.alloc(bl);
-    if (rc != SSYM_OK)
-        return rc;
-    mosaicker_best_kernel<<<(nL + 255) / 256, 256, 0, ctx->stream>>>(mk->lanes, nL, out.f64[0], out.u32[0], out.u32[1]);
-    SSYM_HIP_CHECK(ctx, hipGetLastError());
-    return out.finish(ctx);
+    return tiling_best(ctx, mk, kNoun, "ssym_mosaicker_best", out_total, out_covered, out_committed, flags,
+                       [&](double *total, uint32_t *covered, uint32_t *committed) {
+                           const uint32_t nL = mk->nLanes;
+                           mosaicker_best_kernel<<<(nL + 255) / 256, 256, 0, ctx->stream>>>(mk->lanes, nL, total, covered, committed);
+                       });
 }
 
 }  // namespace
@@ -775,29 +623,20 @@ int32_t ssym_mosaicker_create(ssym_ctx *ctx, const ssym_dict *dict, uint32_t n_l
 
 int32_t ssym_mosaicker_destroy(ssym_ctx *ctx, ssym_mosaicker *mk)
 {
-    if (!mk)
-        return SSYM_OK;
-    if (!ctx || mk->ctx != ctx)
-        return SSYM_E_INVALID;
-    (void)hipSetDevice(ctx->device);
-    (void)hipStreamSynchronize(ctx->stream);
-    mosaicker_free(ctx, mk);
-    return SSYM_OK;
+    return lane_destroy(ctx, mk, mosaicker_free);
 }
 
 int32_t ssym_mosaicker_push(ssym_ctx *ctx, ssym_mosaicker *mk, const double *feats, const uint64_t *frame_offsets, uint32_t flags,
                             uint64_t *out_n_frames)
 {
-    if (!ctx)
-        return SSYM_E_INVALID;
-    return guarded(ctx, [&]() -> int32_t { return mosaicker_push(ctx, mk, feats, frame_offsets, flags, out_n_frames); });
+    return lane_push(ctx, mk, kNoun, "ssym_mosaicker_push", mosaicker_feed, feats, frame_offsets, out_n_frames,
+                     mosaicker_run(ctx, mk, out_n_frames));
 }
 
 int32_t ssym_mosaicker_follow(ssym_ctx *ctx, ssym_mosaicker *mk, const ssym_stream *stream, uint32_t flags, uint64_t *out_n_frames)
 {
-    if (!ctx)
-        return SSYM_E_INVALID;
-    return guarded(ctx, [&]() -> int32_t { return mosaicker_follow(ctx, mk, stream, flags, out_n_frames); });
+    return lane_follow(ctx, mk, kNoun, "ssym_mosaicker_follow", mosaicker_feed, stream, out_n_frames,
+                       mosaicker_run(ctx, mk, out_n_frames));
 }
 
 int32_t ssym_mosaicker_frames(ssym_ctx *ctx, const ssym_mosaicker *mk, uint32_t *out_lane, uint32_t *out_column, uint32_t *out_src,
@@ -812,9 +651,7 @@ int32_t ssym_mosaicker_frames(ssym_ctx *ctx, const ssym_mosaicker *mk, uint32_t 
 
 int32_t ssym_mosaicker_flush(ssym_ctx *ctx, ssym_mosaicker *mk, uint32_t lane, uint64_t *out_n_frames)
 {
-    if (!ctx)
-        return SSYM_E_INVALID;
-    return guarded(ctx, [&]() -> int32_t { return mosaicker_flush(ctx, mk, lane, out_n_frames); });
+    return lane_flush(ctx, mk, kNoun, "ssym_mosaicker_flush", mosaicker_feed, lane, out_n_frames, mosaicker_run(ctx, mk, out_n_frames));
 }
 
 int32_t ssym_mosaicker_best(ssym_ctx *ctx, const ssym_mosaicker *mk, double *out_total, uint32_t *out_covered,
@@ -838,9 +675,16 @@ int32_t ssym_mosaicker_counts(const ssym_mosaicker *mk, uint64_t *out_frames, ui
 
 int32_t ssym_mosaicker_reset(ssym_ctx *ctx, ssym_mosaicker *mk, uint32_t lane)
 {
-    if (!ctx)
-        return SSYM_E_INVALID;
-    return guarded(ctx, [&]() -> int32_t { return mosaicker_reset(ctx, mk, lane); });
+    return lane_reset(ctx, mk, kNoun, "ssym_mosaicker_reset", mosaicker_feed, lane, [&]() -> int32_t {
+        mosaicker_init_kernel<<<1, 256, 0, ctx->stream>>>(mk->lanes, lane, 1u);
+        SSYM_HIP_CHECK(ctx, hipGetLastError());
+        SSYM_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+        mk->consumed[lane] = 0;
+        mk->done[lane] = -1;
+        mk->stored[lane] = 0;
+        mk->ended[lane] = mk->dead[lane] = 0;
+        return SSYM_OK;
+    });
 }
 
 }  // extern "C"

@@ -36,6 +36,10 @@
 // lane is active for every column, so after a chunk both rows hold Fb fresh entries: bound1 = row c0 + R - 1, bound2 = row
 // c0 + R - 2 (for first + c0 + R = 1 a row that does not exist, written as (+inf, none) and never read: "second row above
 // exists" is first + c0 >= 2).  A row that does not exist yet is neither loaded from the state nor read from LDS.
+//
+// Host: the checks, the upload and the bodies of push / follow / flush / reset and of destroy are lane_feed.hpp's; the
+// spotter hands in its feed and spotter_run, with the profile outputs of the call.  spotter_run, the event log that grows and
+// is sorted, and the reads are here.
 #include "dtw_wave.hpp"
 #include "lane_feed.hpp"
 
@@ -596,7 +600,7 @@ void spotter_free(ssym_ctx *ctx, ssym_spotter *sp)
 constexpr const char *kNoun = "spotter";
 
 // the spotter as the lane feed (lane_feed.hpp) sees it: lanes never end, and without pairs a push has nothing to upload
-LaneFeed feed_of(const ssym_spotter *sp)
+LaneFeed feed_of(ssym_ctx *, const ssym_spotter *sp)
 {
     return LaneFeed{kNoun, "out_n_events", sp->nLanes, sp->q->set.dim, sp->consumed, nullptr, sp->nPairs != 0, nullptr};
 }
@@ -941,65 +945,14 @@ int32_t spotter_run(ssym_ctx *ctx, ssym_spotter *sp, const std::vector<const dou
     return SSYM_OK;
 }
 
-// push, follow and flush: the handle, the feed's checks and frames (lane_feed.hpp), then the run
-
-int32_t spotter_push(ssym_ctx *ctx, ssym_spotter *sp, const double *feats, const uint64_t *frame_offsets, uint32_t flags,
-                     uint64_t *out_n_events, double *out_prof_d, uint32_t *out_prof_s)
+// what push, follow and flush hand to the entry bodies (lane_feed.hpp) beside the feed: the run with the profile outputs of
+// the call (a flush has none)
+auto spotter_runner(ssym_ctx *ctx, ssym_spotter *sp, uint32_t flags, uint64_t *out_n_events, double *out_prof_d, uint32_t *out_prof_s)
 {
-    const char *fn = "ssym_spotter_push";
-    Blocks bl(ctx);
-    std::vector<const double *> rows;
-    std::vector<uint64_t> m;
-    int32_t rc = check_handle(ctx, sp, kNoun, fn);
-    if (rc == SSYM_OK)
-        rc = feed_of(sp).push(ctx, fn, feats, frame_offsets, out_n_events, bl, rows, m);
-    if (rc != SSYM_OK)
-        return rc;
-    return spotter_run(ctx, sp, rows, m, kNone, flags, out_n_events, out_prof_d, out_prof_s);
-}
-
-int32_t spotter_follow(ssym_ctx *ctx, ssym_spotter *sp, const ssym_stream *stream, uint32_t flags, uint64_t *out_n_events,
-                       double *out_prof_d, uint32_t *out_prof_s)
-{
-    const char *fn = "ssym_spotter_follow";
-    std::vector<const double *> rows;
-    std::vector<uint64_t> m;
-    int32_t rc = check_handle(ctx, sp, kNoun, fn);
-    if (rc == SSYM_OK)
-        rc = feed_of(sp).follow(ctx, fn, stream, out_n_events, rows, m);
-    if (rc != SSYM_OK)
-        return rc;
-    return spotter_run(ctx, sp, rows, m, kNone, flags, out_n_events, out_prof_d, out_prof_s);
-}
-
-int32_t spotter_flush(ssym_ctx *ctx, ssym_spotter *sp, uint32_t lane, uint64_t *out_n_events)
-{
-    const char *fn = "ssym_spotter_flush";
-    int32_t rc = check_handle(ctx, sp, kNoun, fn);
-    if (rc == SSYM_OK)
-        rc = feed_of(sp).lane(ctx, fn, lane, true, out_n_events);
-    if (rc != SSYM_OK)
-        return rc;
-    const std::vector<const double *> rows(sp->nLanes, nullptr);
-    const std::vector<uint64_t> m(sp->nLanes, 0);
-    return spotter_run(ctx, sp, rows, m, lane, 0, out_n_events, nullptr, nullptr);
-}
-
-int32_t spotter_reset(ssym_ctx *ctx, ssym_spotter *sp, uint32_t lane)
-{
-    const char *fn = "ssym_spotter_reset";
-    int32_t rc = check_handle(ctx, sp, kNoun, fn);
-    if (rc == SSYM_OK)
-        rc = feed_of(sp).lane(ctx, fn, lane, false, nullptr);
-    if (rc != SSYM_OK)
-        return rc;
-    if (sp->nTgt) {
-        spotter_init_kernel<<<(sp->nTgt + 255) / 256, 256, 0, ctx->stream>>>(init_args(sp), lane * sp->nTgt, sp->nTgt);
-        SSYM_HIP_CHECK(ctx, hipGetLastError());
-        SSYM_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    }
-    sp->consumed[lane] = 0;
-    return SSYM_OK;
+    static_assert(kNone == kLaneNone, "a call without a flush names the same lane to the feed and to the run");
+    return [=](const char *, const std::vector<const double *> &rows, const std::vector<uint64_t> &m, uint32_t flushLane) {
+        return spotter_run(ctx, sp, rows, m, flushLane, flags, out_n_events, out_prof_d, out_prof_s);
+    };
 }
 
 int32_t spotter_events(ssym_ctx *ctx, const ssym_spotter *sp, uint32_t *out_lane, uint32_t *out_target, double *out_cost,
@@ -1069,34 +1022,21 @@ int32_t ssym_spotter_create_step(ssym_ctx *ctx, const ssym_queries *q, uint32_t 
 
 int32_t ssym_spotter_destroy(ssym_ctx *ctx, ssym_spotter *sp)
 {
-    if (!sp)
-        return SSYM_OK;
-    if (!ctx || sp->ctx != ctx)
-        return SSYM_E_INVALID;
-    (void)hipSetDevice(ctx->device);
-    (void)hipStreamSynchronize(ctx->stream);
-    spotter_free(ctx, sp);
-    return SSYM_OK;
+    return lane_destroy(ctx, sp, spotter_free);
 }
 
 int32_t ssym_spotter_push(ssym_ctx *ctx, ssym_spotter *sp, const double *feats, const uint64_t *frame_offsets, uint32_t flags,
                           uint64_t *out_n_events, double *out_profile_cost, uint32_t *out_profile_start)
 {
-    if (!ctx)
-        return SSYM_E_INVALID;
-    return guarded(ctx, [&]() -> int32_t {
-        return spotter_push(ctx, sp, feats, frame_offsets, flags, out_n_events, out_profile_cost, out_profile_start);
-    });
+    return lane_push(ctx, sp, kNoun, "ssym_spotter_push", feed_of, feats, frame_offsets, out_n_events,
+                     spotter_runner(ctx, sp, flags, out_n_events, out_profile_cost, out_profile_start));
 }
 
 int32_t ssym_spotter_follow(ssym_ctx *ctx, ssym_spotter *sp, const ssym_stream *stream, uint32_t flags,
                             uint64_t *out_n_events, double *out_profile_cost, uint32_t *out_profile_start)
 {
-    if (!ctx)
-        return SSYM_E_INVALID;
-    return guarded(ctx, [&]() -> int32_t {
-        return spotter_follow(ctx, sp, stream, flags, out_n_events, out_profile_cost, out_profile_start);
-    });
+    return lane_follow(ctx, sp, kNoun, "ssym_spotter_follow", feed_of, stream, out_n_events,
+                       spotter_runner(ctx, sp, flags, out_n_events, out_profile_cost, out_profile_start));
 }
 
 int32_t ssym_spotter_events(ssym_ctx *ctx, const ssym_spotter *sp, uint32_t *out_lane, uint32_t *out_target, double *out_cost,
@@ -1111,9 +1051,8 @@ int32_t ssym_spotter_events(ssym_ctx *ctx, const ssym_spotter *sp, uint32_t *out
 
 int32_t ssym_spotter_flush(ssym_ctx *ctx, ssym_spotter *sp, uint32_t lane, uint64_t *out_n_events)
 {
-    if (!ctx)
-        return SSYM_E_INVALID;
-    return guarded(ctx, [&]() -> int32_t { return spotter_flush(ctx, sp, lane, out_n_events); });
+    return lane_flush(ctx, sp, kNoun, "ssym_spotter_flush", feed_of, lane, out_n_events,
+                      spotter_runner(ctx, sp, 0, out_n_events, nullptr, nullptr));
 }
 
 int32_t ssym_spotter_best(ssym_ctx *ctx, const ssym_spotter *sp, double *out_cost, uint32_t *out_start, uint32_t *out_end,
@@ -1134,9 +1073,15 @@ int32_t ssym_spotter_counts(const ssym_spotter *sp, uint64_t *out_frames)
 
 int32_t ssym_spotter_reset(ssym_ctx *ctx, ssym_spotter *sp, uint32_t lane)
 {
-    if (!ctx)
-        return SSYM_E_INVALID;
-    return guarded(ctx, [&]() -> int32_t { return spotter_reset(ctx, sp, lane); });
+    return lane_reset(ctx, sp, kNoun, "ssym_spotter_reset", feed_of, lane, [&]() -> int32_t {
+        if (sp->nTgt) {
+            spotter_init_kernel<<<(sp->nTgt + 255) / 256, 256, 0, ctx->stream>>>(init_args(sp), lane * sp->nTgt, sp->nTgt);
+            SSYM_HIP_CHECK(ctx, hipGetLastError());
+            SSYM_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+        }
+        sp->consumed[lane] = 0;
+        return SSYM_OK;
+    });
 }
 
 }  // extern "C"

@@ -522,14 +522,7 @@ int32_t ssym_follower_create(ssym_ctx *ctx, uint32_t n_lanes, double max_gain, s
 
 int32_t ssym_follower_destroy(ssym_ctx *ctx, ssym_follower *fl)
 {
-    if (!fl)
-        return SSYM_OK;
-    if (!ctx || fl->ctx != ctx)
-        return SSYM_E_INVALID;
-    (void)hipSetDevice(ctx->device);
-    (void)hipStreamSynchronize(ctx->stream);
-    follower_free(ctx, fl);
-    return SSYM_OK;
+    return lane_destroy(ctx, fl, follower_free);
 }
 
 int32_t ssym_follower_push(ssym_ctx *ctx, ssym_follower *fl, const double *samples, const uint64_t *sample_offsets, const double *ref,

@@ -1,12 +1,15 @@
 // lane_feed.hpp -- what the lane-fed objects share on the host: the spotter (dtw_spotter.hip), the coverer
 // (dtw_coverer.hip) and the mosaicker (dtw_mosaicker.hip) consume growing sounds lane by lane, in pushes of host frames or
 // by following a stream's resident frames, and flush or reset one lane.  The checks of those calls, their order, their
-// messages and the upload of a push are here once; what an object does with the frames (spotter_run, coverer_run,
-// mosaicker_run) is its own.  So is the log of a call's results that the coverer and the mosaicker keep (LaneLog: its room,
-// its layout at the start of a call and the copy out; the spotter's event log keeps its contents while it grows and is
-// sorted, and stays with the spotter), and pow2_at_least.  The resynthesiser (resynth.hip) is lane-fed too, with committed
-// frames instead of features: it takes check_handle, the lane limit and the lane check of flush / reset from here, keeps
-// its released samples in a LaneLog (one entry per sample) and reads the mosaicker's (MosaickerLog).
+// messages and the upload of a push are here once (LaneFeed), and so are the bodies of the four entry points and of destroy
+// (lane_push, lane_follow, lane_flush, lane_reset, lane_destroy): an object hands in its feed and what it does with the
+// frames (spotter_run; the coverer's and the mosaicker's runs are one loop too, lane_tiling.hpp's tiling_run).  Here as
+// well: the log of a call's results that the coverer and the mosaicker keep (LaneLog: its room, its layout at the start of a
+// call and the copy out; the spotter's event log keeps its contents while it grows and is sorted, and stays with the
+// spotter), and pow2_at_least.  The resynthesiser (resynth.hip) is lane-fed too, with committed frames instead of features:
+// it takes check_handle, the lane limit and the lane check of flush / reset from here, keeps its released samples in a
+// LaneLog (one entry per sample) and reads the mosaicker's (MosaickerLog); it and the follower (follower.hip) are destroyed
+// by lane_destroy.
 //
 // The order of the refusals is part of the interface ("the earlier of two faults is the one reported"):
 //   push   : frame_offsets / count NULL | the object's own check | lane by lane: offsets decrease, the lane has ended,
@@ -14,7 +17,7 @@
 //   follow : stream / count NULL | the object's own check | the stream's context | the stream's shape | lane by lane: holds
 //            fewer than consumed, the lane limit | hipSetDevice
 //   lane   : lane outside the lanes (flush: or count NULL) | hipSetDevice
-// and check_handle comes before each of them.
+// and check_handle comes before each of them; the object's run comes behind them.
 #pragma once
 
 #include "ssym_internal.hpp"
@@ -26,6 +29,7 @@ namespace ssym {
 
 // frames a lane may consume: its row numbers, ends and cut points are reported as u32, and 0xffffffff means none
 constexpr uint64_t kLaneMaxFrames = 2147483647;          // 2^31 - 1
+constexpr uint32_t kLaneNone = 0xffffffffu;              // the lane to flush of a call that flushes none
 
 template <class T>
 int32_t alloc_n(ssym_ctx *ctx, T **p, size_t count)
@@ -299,5 +303,86 @@ struct LaneFeed {
         return SSYM_OK;
     }
 };
+
+// The bodies of ssym_<noun>_push / _follow / _flush / _reset, from the extern "C" function's first line on: a NULL context
+// is refused without a message and no exception leaves (guarded, ssym_internal.hpp); check_handle; the feed's checks; the
+// object's part.
+//   feed(ctx, h)                   : the object's LaneFeed (asked for once the handle is checked)
+//   run(fn, rows, m, flushLane)    : consume m[l] frames at rows[l] (DEVICE) on every lane, then flush flushLane (kLaneNone:
+//                                    none); whatever else the entry point takes rides in the callable
+//   own()                          : reset's part of the object -- its init kernel and its mirrors of the lane
+
+template <class Handle, class Body>
+int32_t lane_entry(ssym_ctx *ctx, Handle *h, const char *noun, const char *fn, Body body)
+{
+    if (!ctx)
+        return SSYM_E_INVALID;
+    return guarded(ctx, [&]() -> int32_t {
+        const int32_t rc = check_handle(ctx, h, noun, fn);
+        return rc == SSYM_OK ? body() : rc;
+    });
+}
+
+template <class Handle, class Feed, class Run>
+int32_t lane_push(ssym_ctx *ctx, Handle *h, const char *noun, const char *fn, Feed feed, const double *feats,
+                  const uint64_t *frame_offsets, const uint64_t *out_n, Run run)
+{
+    return lane_entry(ctx, h, noun, fn, [&]() -> int32_t {
+        Blocks bl(ctx);                                  // the uploaded frames: they outlive the run
+        std::vector<const double *> rows;
+        std::vector<uint64_t> m;
+        const int32_t rc = feed(ctx, h).push(ctx, fn, feats, frame_offsets, out_n, bl, rows, m);
+        return rc == SSYM_OK ? run(fn, rows, m, kLaneNone) : rc;
+    });
+}
+
+template <class Handle, class Feed, class Run>
+int32_t lane_follow(ssym_ctx *ctx, Handle *h, const char *noun, const char *fn, Feed feed, const ssym_stream *stream,
+                    const uint64_t *out_n, Run run)
+{
+    return lane_entry(ctx, h, noun, fn, [&]() -> int32_t {
+        std::vector<const double *> rows;
+        std::vector<uint64_t> m;
+        const int32_t rc = feed(ctx, h).follow(ctx, fn, stream, out_n, rows, m);
+        return rc == SSYM_OK ? run(fn, rows, m, kLaneNone) : rc;
+    });
+}
+
+template <class Handle, class Feed, class Run>
+int32_t lane_flush(ssym_ctx *ctx, Handle *h, const char *noun, const char *fn, Feed feed, uint32_t lane, const uint64_t *out_n,
+                   Run run)
+{
+    return lane_entry(ctx, h, noun, fn, [&]() -> int32_t {
+        const int32_t rc = feed(ctx, h).lane(ctx, fn, lane, true, out_n);
+        if (rc != SSYM_OK)
+            return rc;
+        const std::vector<const double *> rows(h->nLanes, nullptr);
+        const std::vector<uint64_t> m(h->nLanes, 0);
+        return run(fn, rows, m, lane);
+    });
+}
+
+template <class Handle, class Feed, class Own>
+int32_t lane_reset(ssym_ctx *ctx, Handle *h, const char *noun, const char *fn, Feed feed, uint32_t lane, Own own)
+{
+    return lane_entry(ctx, h, noun, fn, [&]() -> int32_t {
+        const int32_t rc = feed(ctx, h).lane(ctx, fn, lane, false, nullptr);
+        return rc == SSYM_OK ? own() : rc;
+    });
+}
+
+// ssym_<noun>_destroy: NULL is destroyed already; the stream has done with the object's memory before release(ctx, h) frees it
+template <class Handle, class Release>
+int32_t lane_destroy(ssym_ctx *ctx, Handle *h, Release release)
+{
+    if (!h)
+        return SSYM_OK;
+    if (!ctx || h->ctx != ctx)
+        return SSYM_E_INVALID;
+    (void)hipSetDevice(ctx->device);
+    (void)hipStreamSynchronize(ctx->stream);
+    release(ctx, h);
+    return SSYM_OK;
+}
 
 }  // namespace ssym

@@ -667,14 +667,7 @@ int32_t ssym_resynth_create(ssym_ctx *ctx, const ssym_samples *store, uint32_t n
 
 int32_t ssym_resynth_destroy(ssym_ctx *ctx, ssym_resynth *rs)
 {
-    if (!rs)
-        return SSYM_OK;
-    if (!ctx || rs->ctx != ctx)
-        return SSYM_E_INVALID;
-    (void)hipSetDevice(ctx->device);
-    (void)hipStreamSynchronize(ctx->stream);
-    resynth_free(ctx, rs);
-    return SSYM_OK;
+    return lane_destroy(ctx, rs, resynth_free);
 }
 
 int32_t ssym_resynth_push(ssym_ctx *ctx, ssym_resynth *rs, const uint32_t *lane, const uint32_t *column, const uint32_t *src,

@@ -1,12 +1,12 @@
-"""The refusals of the two lane-fed objects word for word: ssym_spotter_* and ssym_coverer_* push, follow, flush, reset,
-events / pieces and best.  Every refusal's code and exact ssym_last_error text, the entry point's own name and the
-object's noun in it, and for every two faults one call can have, in the order of the checks
+"""The refusals of the three lane-fed objects word for word: ssym_spotter_*, ssym_coverer_* and ssym_mosaicker_* push,
+follow, flush, reset, events / pieces / frames and best.  Every refusal's code and exact ssym_last_error text, the entry
+point's own name and the object's noun in it, and for every two faults one call can have, in the order of the checks
 
-    push   : handle, NULL frame_offsets / count, (coverer) dictionary appended to, then lane by lane: offsets decrease,
-             (coverer) the lane has ended, lane limit; then NULL feats
-    follow : handle, NULL stream / count, (coverer) dictionary appended to, the stream's context, the stream's shape, then
-             lane by lane: holds fewer than consumed (an ended lane too), lane limit
-    flush  : handle, lane / NULL count          reset : handle, lane          events / pieces, best : handle
+    push   : handle, NULL frame_offsets / count, (coverer, mosaicker) dictionary appended to, then lane by lane: offsets
+             decrease, (coverer, mosaicker) the lane has ended, lane limit; then NULL feats
+    follow : handle, NULL stream / count, (coverer, mosaicker) dictionary appended to, the stream's context, the stream's
+             shape, then lane by lane: holds fewer than consumed (an ended lane too), lane limit
+    flush  : handle, lane / NULL count     reset : handle, lane     events / pieces / frames, best : handle
 
 one call with both that reports the earlier one.  The count output is sentinel-filled and stays untouched on every refusal,
 and so do the object's counts and best; the accepted calls after the refusals give, bit for bit, what they give an object
@@ -27,16 +27,17 @@ pytestmark = pytest.mark.gpu
 OK, INV, UNS = nat.SSYM_OK, nat.SSYM_E_INVALID, nat.SSYM_E_UNSUPPORTED
 SENT = 77
 LANES, DIM = 2, 3
-COUNT = {"spotter": "out_n_events", "coverer": "out_n_pieces"}
-READ = {"spotter": "events", "coverer": "pieces"}
+COUNT = {"spotter": "out_n_events", "coverer": "out_n_pieces", "mosaicker": "out_n_frames"}
+READ = {"spotter": "events", "coverer": "pieces", "mosaicker": "frames"}
+TILINGS = ["coverer", "mosaicker"]                       # a flushed lane has ended, and push and follow read the dictionary
 
-# {fn}: the entry point, {noun}: spotter / coverer, {count}: out_n_events / out_n_pieces
+# {fn}: the entry point, {noun}: spotter / coverer / mosaicker, {count}: out_n_events / out_n_pieces / out_n_frames
 NULL_HANDLE = "{fn}: the {noun} handle is NULL"
 FOREIGN = "{fn}: the {noun} belongs to another context"
 PUSH_NULL = "{fn}: frame_offsets and {count} must not be NULL"
-APPENDED = "{fn}: the dictionary was appended to after the coverer was created; create a new coverer"
+APPENDED = "{fn}: the dictionary was appended to after the {noun} was created; create a new {noun}"
 DECREASE = "{fn}: frame_offsets decrease"
-ENDED = "{fn}: lane {lane} was flushed and has ended; call ssym_coverer_reset"
+ENDED = "{fn}: lane {lane} was flushed and has ended; call ssym_{noun}_reset"
 LIMIT = "{fn}: lane {lane} would consume more than 2^31 - 1 = 2147483647 frames"
 FEATS = "{fn}: feats is NULL"
 FOLLOW_NULL = "{fn}: stream and {count} must not be NULL"
@@ -71,7 +72,9 @@ class _World:
         self.foreign = self.other.stream(3, 44100.0, 3)
 
     def make(self, noun, d=None):
-        return self.e.spotter(self.q, LANES) if noun == "spotter" else self.e.coverer(d or self.d, LANES, 0.5)
+        if noun == "spotter":
+            return self.e.spotter(self.q, LANES)
+        return getattr(self.e, noun)(d or self.d, LANES, 0.5)
 
     def fill(self, st):
         st.push(np.concatenate(self.waves), _off(0, self.waves[0].size, self.waves[0].size + self.waves[1].size))
@@ -119,7 +122,7 @@ class _Calls:
 
     def read(self, ctx=True, obj=True):
         u, f = self.u.ctypes.data, self.f.ctypes.data
-        words = (u, u, f, u, u) if self.noun == "spotter" else (u, u, u, u, f)
+        words = {"spotter": (u, u, f, u, u), "coverer": (u, u, u, u, f), "mosaicker": (u, u, u, u, f, u)}[self.noun]
         return self.fn(READ[self.noun])(self._ctx(ctx), self.obj.ptr if obj else None, *words, 0)
 
     def best(self, ctx=True, obj=True):
@@ -156,14 +159,17 @@ class _Calls:
         return (counts if self.noun == "spotter" else counts[0]).tolist()
 
     def state(self):
-        """Everything the object answers about itself, as bytes: the frames consumed, best, and the events / pieces of the last
-        accepted call with their number."""
+        """Everything the object answers about itself, as bytes: the frames consumed, best, and the events / pieces / frames of
+        the last accepted call with their number."""
         if self.noun == "spotter":
             self.obj.n_events = self.last
             log = self.obj.events()
-        else:
+        elif self.noun == "coverer":
             self.obj.n_pieces = self.last
             log = self.obj.pieces()
+        else:
+            self.obj.n_frames = self.last
+            log = self.obj.frames()
         return self.counts(), self.last, [a.tobytes() for a in self.obj.best()], [a.tobytes() for a in log]
 
 
@@ -173,7 +179,7 @@ def _handle_refusals(c, name, **kw):
     c.refused(name, INV, FOREIGN, ctx=False, **kw)
 
 
-@pytest.mark.parametrize("noun", ["spotter", "coverer"])
+@pytest.mark.parametrize("noun", ["spotter"] + TILINGS)
 def test_every_refusal_of_push_flush_reset_and_the_reads_word_for_word_and_the_earlier_of_two(world, noun):
     w = world
     objs = [w.make(noun), w.make(noun)]                  # the second is never refused anything
@@ -182,7 +188,7 @@ def test_every_refusal_of_push_flush_reset_and_the_reads_word_for_word_and_the_e
     first, second, third = _off(0, 6, 11), _off(11, 15, 15), _off(15, 19, 26)
     for k in calls:
         k.accept("push", first)
-        k.accept("flush", 1)                             # lane 1 of a coverer has ended now; a spotter's goes on
+        k.accept("flush", 1)                             # lane 1 of a tiling has ended now; a spotter's goes on
     before = c.state()
     assert before == calls[1].state()
     big = 2 ** 31
@@ -204,7 +210,7 @@ def test_every_refusal_of_push_flush_reset_and_the_reads_word_for_word_and_the_e
     c.refused("push", UNS, LIMIT, arg=_off(0, big, 5))                                       # limit on lane 0, decrease on lane 1
     c.refused("push", UNS, LIMIT, arg=_off(0, big, big), feats=False)                        # limit, NULL feats
     c.fill = dict(lane=1)
-    if noun == "coverer":
+    if noun in TILINGS:
         c.refused("push", INV, ENDED, arg=_off(0, 0, 3))
         c.refused("push", INV, ENDED, arg=_off(0, 0, big))                                   # ended and over the limit, one lane
         c.refused("push", INV, ENDED, arg=_off(0, 0, 3), feats=False)                        # ended, NULL feats
@@ -245,7 +251,7 @@ def test_every_refusal_of_push_flush_reset_and_the_reads_word_for_word_and_the_e
         o.close()
 
 
-@pytest.mark.parametrize("noun", ["spotter", "coverer"])
+@pytest.mark.parametrize("noun", ["spotter"] + TILINGS)
 def test_every_refusal_of_follow_word_for_word_and_the_earlier_of_two(world, noun):
     w = world
     st = w.e.stream(LANES, 44100.0, DIM)
@@ -253,7 +259,7 @@ def test_every_refusal_of_follow_word_for_word_and_the_earlier_of_two(world, nou
     obj = w.make(noun)
     c = _Calls(w, noun, obj)
     c.accept("follow", st)
-    c.accept("flush", 1)                                 # 10 and 8 frames consumed; lane 1 of a coverer has ended
+    c.accept("flush", 1)                                 # 10 and 8 frames consumed; lane 1 of a tiling has ended
     before = c.state()
     assert c.counts() == [10, 8]
 
@@ -270,7 +276,7 @@ def test_every_refusal_of_follow_word_for_word_and_the_earlier_of_two(world, nou
     c.refused("follow", INV, SHAPE, arg=w.st12)
     st.reset(1)
     c.fill = dict(lane=1, held=0, consumed=8)
-    c.refused("follow", INV, FEWER, arg=st)                                                  # (a coverer's ended lane as well)
+    c.refused("follow", INV, FEWER, arg=st)                                                  # (a tiling's ended lane as well)
     st.reset(0)
     c.fill = dict(lane=0, held=0, consumed=10)
     c.refused("follow", INV, FEWER, arg=st)                                                  # fewer on both lanes: the first
@@ -290,11 +296,9 @@ def test_every_refusal_of_follow_word_for_word_and_the_earlier_of_two(world, nou
         h.close()
 
 
-def test_a_dictionary_appended_to_is_reported_in_its_place(world):
-    """The coverer's own check: behind the NULL checks of push and follow, in front of the offsets and the stream."""
-    w = world
-    obj = w.make("coverer", w.d2)
-    c = _Calls(w, "coverer", obj)
+def _appended_to_is_reported_in_its_place(w, noun):
+    obj = w.make(noun, w.d2)
+    c = _Calls(w, noun, obj)
     c.accept("push", _off(0, 3, 6))
     c.accept("flush", 1)
     before = c.state()
@@ -312,9 +316,19 @@ def test_a_dictionary_appended_to_is_reported_in_its_place(world):
     c.refused("follow", INV, FOLLOW_NULL, arg=None)                                          # NULL stream, appended to
     c.refused("follow", INV, APPENDED, arg=w.foreign)                                        # appended to, the stream's context
     c.refused("follow", INV, APPENDED, arg=w.st3)                                            # appended to, the stream's shape
-    # flush, reset, pieces and best do not read the dictionary
+    # flush, reset, pieces / frames and best do not read the dictionary
     assert c.state() == before
     for call in (("flush", 0), ("reset", 0), ("reset", 1)):
         c.accept(*call)
     assert c.counts() == [0, 0]
     obj.close()
+
+
+def test_a_dictionary_appended_to_is_reported_in_its_place(world):
+    """The coverer's own check: behind the NULL checks of push and follow, in front of the offsets and the stream."""
+    _appended_to_is_reported_in_its_place(world, "coverer")
+
+
+def test_a_dictionary_appended_to_is_reported_in_its_place_by_a_mosaicker(world):
+    """The mosaicker's own check is the coverer's, at the same place and in the same words."""
+    _appended_to_is_reported_in_its_place(world, "mosaicker")
