@@ -36,6 +36,10 @@ static std::atomic<unsigned long long> g_filter_wg2_launches{0};
 // SSYM_FILTER_WG2=0 (under SSYM_TEST_HOOKS, read per filter call by read_filter_knobs): two-pass launches of the plan's Wg
 // kind stay on dtw_filter_wg_kernel -- A/B runs from one library.  Not a knob of the plan: the plan is the same either way.
 static std::atomic<bool> g_filter_wg2{true};
+// ... and those of the wg2 launches that took its uniform-length instantiation (ssym_debug_filter_wg2u_launches)
+static std::atomic<unsigned long long> g_filter_wg2u_launches{0};
+// SSYM_FILTER_WG2U=0 (under SSYM_TEST_HOOKS, read beside SSYM_FILTER_WG2): uniform sets keep the general wg2 kernel
+static std::atomic<bool> g_filter_wg2u{true};
 
 int filter_pieces(int dim)
 {
@@ -239,6 +243,7 @@ static FilterKnobs read_filter_knobs()
 {
     FilterKnobs k;
     g_filter_wg2.store(true, std::memory_order_relaxed);
+    g_filter_wg2u.store(true, std::memory_order_relaxed);
     if (!ssym_knob("SSYM_TEST_HOOKS"))
         return k;
     auto num = [](const char *name, int unset) {
@@ -252,6 +257,7 @@ static FilterKnobs read_filter_knobs()
     k.spPairBlock = ssym_knob("SSYM_SP_PAIRBLOCK") ? std::max(num("SSYM_SP_PAIRBLOCK", 0), 0) : -1;
     k.wg = num("SSYM_FILTER_WG", k.wg) != 0;
     g_filter_wg2.store(num("SSYM_FILTER_WG2", 1) != 0, std::memory_order_relaxed);
+    g_filter_wg2u.store(num("SSYM_FILTER_WG2U", 1) != 0, std::memory_order_relaxed);
     k.skip0 = num("SSYM_FILTER_SKIP0", 1) != 0;
     k.nt8 = ssym_knob("SSYM_FILTER_NT8") != nullptr;
     k.oneLaunch = ssym_knob("SSYM_FILTER_ONE_LAUNCH") != nullptr;
@@ -268,13 +274,27 @@ static const std::vector<uint32_t> &plan_lens(const SegmentSet &set, uint32_t gr
 {
     if (set.plan_lens.size() != set.n_pad / group) {       // (not built yet, or built for the set in the other role)
         set.plan_lens.assign(set.n_pad / group, 0u);
+        set.plan_min_lens.assign(set.n_pad / group, 0xffffffffu);
         for (uint32_t slot = 0; slot < set.n; ++slot) {
             const uint32_t s = set.h_perm[slot];
-            uint32_t &m = set.plan_lens[slot / group];
-            m = std::max(m, (uint32_t)(set.h_off[s + 1] - set.h_off[s]));
+            const uint32_t f = (uint32_t)(set.h_off[s + 1] - set.h_off[s]);
+            uint32_t &m = set.plan_lens[slot / group], &lo = set.plan_min_lens[slot / group];
+            m = std::max(m, f);
+            lo = std::min(lo, f);
         }
     }
     return set.plan_lens;
+}
+
+// The uniform gate's facts, kept with the set beside plan_lens (built with them): the one frame count of the real members
+// of the groups [lo, hi), 0 when they differ or when one of the groups' slots is padding.  (Slots ascend by length: the
+// range's shortest member is in its first group, its longest in its last.)
+static uint32_t uniform_len(const SegmentSet &set, uint32_t group, uint32_t lo, uint32_t hi)
+{
+    const std::vector<uint32_t> &longest = plan_lens(set, group);
+    if (lo >= hi || hi > longest.size() || (uint64_t)hi * group > set.n)
+        return 0;
+    return set.plan_min_lens[lo] == longest[hi - 1] ? longest[hi - 1] : 0;
 }
 
 // what every launch of one filter call shares
@@ -291,6 +311,7 @@ struct FilterCall {
     unsigned long long *colCtr;
     const uint32_t *candSlot;
     bool wg2;                       // two-pass Wg launches on dtw_filter_wg2_kernel (SSYM_FILTER_WG2)
+    uint32_t uniF;                  // the targets' one frame count when wg2's uniform instantiation may serve them, else 0
 };
 
 // One entry of the plan as the kernel launch it names: the instantiations of (tiles per pass, cost, operand planes).
@@ -334,6 +355,18 @@ static bool run_kernel(const FilterCall &c, const FilterLaunch &l)
         if constexpr (NT == 4) {
             // exactly two passes: both at once on two waves per pair, the hand-off in LDS (dtw_filter_wg2_kernel.hpp)
             if (l.passes == 2 && c.wg2) {
+                // lengths that do not differ -- every target real and of c.uniF frames, every source of the launch's pairs
+                // of uniFa, the launch's rows the slots' last 128: the instantiation without the lengths' bookkeeping
+                const uint32_t uniFa = c.uniF && rowsPad - l.origin == 128 ? uniform_len(c.src, 2, l.lo, l.hi) : 0;
+                if (uniFa > 64 && uniFa <= 128) {
+                    dtw_filter_wg2_kernel<SQ, KU, true><<<grid, block, 0, c.st>>>(
+                        srec, trec, c.src.len, c.tgt.len, rowsPad, colsPad, tgtPad, nSrcPairs / 4, l.taskChunk, c.outScale, ctr,
+                        c.cmat, l.origin, l.lo, (int)c.uniF, (int)uniFa);
+                    g_filter_wg_launches.fetch_add(1, std::memory_order_relaxed);
+                    g_filter_wg2_launches.fetch_add(1, std::memory_order_relaxed);
+                    g_filter_wg2u_launches.fetch_add(1, std::memory_order_relaxed);
+                    return true;
+                }
                 dtw_filter_wg2_kernel<SQ, KU><<<grid, block, 0, c.st>>>(
                     srec, trec, c.src.len, c.tgt.len, rowsPad, colsPad, tgtPad, nSrcPairs / 4, l.taskChunk, c.outScale, ctr,
                     c.cmat, l.origin, l.lo);
@@ -554,9 +587,14 @@ int32_t launch_dtw_filter(ssym_ctx *ctx, const SegmentSet &src, const SegmentSet
     ctx->launched_cells = 0;
     for (const FilterLaunch &l : plan)
         ctx->launched_cells += l.cells;
+    // wg2's uniform instantiation: every target real and of one frame count, at least four and a multiple of four
+    uint32_t uniF = g_filter_wg2u.load(std::memory_order_relaxed) && !abandon && tgt.n == tgt.n_pad
+                        ? uniform_len(tgt, 32, 0, tgt.n_pad / 32) : 0;
+    if (uniF < 4 || uniF % 4 != 0 || uniF > tgt.frames_pad)
+        uniF = 0;
     const FilterCall call{ctx->stream, src, tgt, sq, in.ku, (float)(sq ? 1.0 / (scale * scale) : 1.0 / scale),
                           (float *)ctx->handoff.ptr, taskCtr, cmat, abandon, colCtr, candSlot,
-                          g_filter_wg2.load(std::memory_order_relaxed)};
+                          g_filter_wg2.load(std::memory_order_relaxed), uniF};
     for (const FilterLaunch &l : plan)
         if (!run_launch(call, l)) {
             ctx->err = "dtw filter: the plan names a kernel that is not built";
@@ -578,6 +616,12 @@ extern "C" __attribute__((visibility("default"))) unsigned long long ssym_debug_
 extern "C" __attribute__((visibility("default"))) unsigned long long ssym_debug_filter_wg2_launches(void)
 {
     return ssym::g_filter_wg2_launches.load(std::memory_order_relaxed);
+}
+
+// ... and those of them that took its uniform-length instantiation
+extern "C" __attribute__((visibility("default"))) unsigned long long ssym_debug_filter_wg2u_launches(void)
+{
+    return ssym::g_filter_wg2u_launches.load(std::memory_order_relaxed);
 }
 
 #ifdef SSYM_SP_PROF

@@ -306,6 +306,7 @@ static int32_t build_derived(ssym_ctx *ctx, SegmentSet &set)
     dev_free(ctx, set.len_order); set.len_order = nullptr; set.len_order_n = 0;
     refcos_q8_release(ctx, set);
     set.plan_lens.clear();
+    set.plan_min_lens.clear();
 
     set.max_frames = 0;
     for (uint32_t i = 0; i < n; ++i)

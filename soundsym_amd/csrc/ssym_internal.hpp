@@ -77,6 +77,7 @@ struct SegmentSet {
     uint32_t *perm = nullptr;
     std::vector<uint32_t> h_perm;
     mutable std::vector<uint32_t> plan_lens;    // the filter plan's lengths (dtw_filter.hip plan_lens), built on first use
+    mutable std::vector<uint32_t> plan_min_lens;    // ... and the shortest real member of each of its groups (the uniform gate)
     mutable size_t rec_bytes = 0;
     mutable uint32_t rec_slots = 0;   // record slots per segment in `rec`
     mutable int rec_lead = 0;         // slot of frame 0 (-1: end-aligned)
